@@ -18,19 +18,34 @@ N > 1 runs one rank per GPU over RCCL, cameras sharded over the ranks
 launch line; RANK / WORLD_SIZE come from the environment) or, when WORLD_SIZE is unset, this
 script starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` itself as a
 CHILD process -- before anything here touches the GPU -- and relays rank 0's line and the
-children's exit code.  Rank 0 prints ONE JSON line.  `roofline` and `kernels` are measured live with HIP events around every
-launch of profiled passes on one stream; `cpu_baseline` times the CPU oracle on the
-host cores (N = 1 only).
+children's exit code.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, the config and the per-step percentiles of those K steps).  `--dump-outputs DIR`
+writes what the last timed step computed as DIR/*.npy (float32).  Everything else runs only
+with `--full`: `roofline` and `kernels` (HIP events around every launch of profiled passes on
+one stream), the uint8-ingest and driver legs, `cpu_baseline` (the CPU oracle on the host
+cores, N = 1 only), the parity figures against the host oracle and the reference fixture, the
+invalid-frame check, the bf16x3 and medium-model lines, the batch-1 latency and, at N > 1, the
+stage timeline and the side legs.
 """
 import argparse
 import json
 import os
+import signal
 import statistics
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+# A rank started by torch.distributed.run: the launcher stops every rank (SIGTERM) as soon as one exits non-zero, which
+# can cut a rank short while it still imports torch.  The signal is held until this rank has checked its device in
+# main(), so every rank's own refusal reaches stderr.
+_HELD_SIGTERM = []
+if __name__ == "__main__" and "LOCAL_RANK" in os.environ:
+    signal.signal(signal.SIGTERM, lambda *_: _HELD_SIGTERM.append(1))
 
 import torch  # noqa: E402
 
@@ -239,7 +254,14 @@ def main():
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the multi-GPU (camera-sharded, RCCL) code path even with one rank")
     ap.add_argument("--profile-passes", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every side measurement and check (per-kernel roofline, CPU "
+                         "baseline, parity against the oracle and the fixtures, other precisions, sizes and legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (points3D, confidences, valid) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))          # nothing above has touched the GPU
@@ -257,6 +279,10 @@ def main():
     if local_rank >= have:
         raise SystemExit("bench.py rank %d: --gpus %d needs %d GPUs on this node, %d visible" %
                          (rank, world, local_world, have))
+    if "LOCAL_RANK" in os.environ:
+        signal.signal(signal.SIGTERM, signal.SIG_DFL)
+        if _HELD_SIGTERM:
+            signal.raise_signal(signal.SIGTERM)
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     sharded = world > 1 or args.force_sharded
@@ -416,9 +442,18 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
-    res = step()
+    # single GPU: the output buffers still hold what the last timed step computed; camera-sharded: the pipelined
+    # submits keep their results, so one more step of the same frames gives them
+    res = outs if not sharded else step()
     torch.cuda.synchronize()
     res = [[r.clone() for r in o] for o in res]    # the output buffers are reused below
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for i, name in enumerate(("points3D", "confidences", "valid")):
+            # (streams, time_batch, ...): one row per time batch of the step, in stream order
+            np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                    torch.stack([o[i] for o in res]).float().cpu().numpy())
     valid = sum(int(o[2].sum().item()) for o in res) * (n_groups * K if sharded else 1)
     rank_fail = None
     if sharded:
@@ -468,10 +503,10 @@ def main():
 
     parity_fail = False
     P = max(1, args.profile_passes)
-    if sharded and rank != 0:
+    if args.full and sharded and rank != 0:
         for _ in range(P + 1):                     # rank 0 profiles P+1 steps: keep the collectives matched
             step()
-    if rank == 0:
+    if args.full and rank == 0:
         # ---- per-kernel roofline, HIP events around every launch of ONE stream's time batch
         # (kernels timed alone; at N > 1: rank 0's share of the camera-sharded step).  Median
         # over P passes per launch position, after one discarded profiled pass.
@@ -540,7 +575,7 @@ def main():
                 "note": "executed matrix-core FLOPs of one step (channel padding included, Winograd at 12/27 of the "
                         "direct count) / ms_per_step; the remainder is HBM-bound kernels, stalls and launch gaps"}
 
-    if rank == 0 and not sharded and not args.no_uint8:
+    if args.full and rank == 0 and not sharded and not args.no_uint8:
         # ---- the same step fed uint8 BGR frames as the decoder delivers
         # them, (a) resident in HBM, (b) copied from pinned host memory inside the timed
         # region (PCIe-inclusive rate; never the headline `value`)
@@ -630,7 +665,7 @@ def main():
             line["driver"] = {"error": repr(e)}
         del dev_u8, host
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # ---- CPU baseline: the oracle (port of the reference) on the host cores,
         # same workload, bounded sample of whole frames
         from oracle import hybridnet_oracle as O
@@ -689,7 +724,7 @@ def main():
             except Exception as e:                                  # noqa: BLE001
                 line["host_oracle_index_flips"] = {"error": repr(e)[:200]}
     fixture_tag = c.get("fixture", args.config) if size == c.get("size", "small") else None
-    if rank == 0 and world == 1 and fixture_tag is not None:
+    if args.full and rank == 0 and world == 1 and fixture_tag is not None:
         # frame 0 of this workload is a fixture case of tests/golden/predictor.npz, i.e. the
         # output of the imported upstream reference on the same input
         import numpy as np
@@ -699,7 +734,7 @@ def main():
             line["parity_max_abs_mm_vs_reference_fixture"] = float(
                 np.abs(res[0][0][0].cpu().numpy() - gold[0]).max())
 
-    if rank == 0 and not sharded and T >= 3:
+    if args.full and rank == 0 and not sharded and T >= 3:
         # ---- side check (outside the timed region): one frame set of the batch replaced by an empty (all
         # zero) one must not disturb its neighbours (time-batch slots are independent instances).  Whether the
         # empty set itself is reported invalid depends on the weights: with these random-init networks the
@@ -720,7 +755,7 @@ def main():
         except Exception as e:
             line["invalid_frame_check"] = {"error": repr(e)[:200]}
 
-    if rank == 0 and not sharded and not args.no_reduced_precision and pred.precision == "f32":
+    if args.full and rank == 0 and not sharded and not args.no_reduced_precision and pred.precision == "f32":
         # ---- separately labelled reduced-precision line (BASELINE configs[1] is worded "bf16"; the
         # reference's own fast path is half precision, jarvis3D.py:93,107,122): V2V's 3x3x3 convolutions
         # on the bf16 matrix cores with split operands (csrc/conv3d_bf16x3.hip), everything else as in
@@ -767,7 +802,7 @@ def main():
         except Exception as e:                      # the side line never costs the headline
             line["reduced_precision"] = {"error": repr(e)[:300]}
 
-    if rank == 0 and not sharded and not args.no_secondary:
+    if args.full and rank == 0 and not sharded and not args.no_secondary:
         # ---- the reference's own call pattern: ONE multi-view frame set per forward (batch 1),
         # stream-ordered back to back (no host sync inside the loop)
         try:
@@ -795,7 +830,8 @@ def main():
         except Exception as e:
             line["single_frame_latency_ms"] = repr(e)[:200]
 
-    if rank == 0 and not sharded and not args.no_secondary and size == "small" and args.config == "cfg3":
+    if (args.full and rank == 0 and not sharded and not args.no_secondary and size == "small" and
+            args.config == "cfg3"):
         # ---- SURVEY 8d secondary line: the `medium` models (config.py's default size) on the
         # same workload, same method, fewer steps
         try:
@@ -855,7 +891,7 @@ def main():
         except Exception as e:                      # the secondary line never costs the headline
             line["secondary"] = {"error": repr(e)[:200]}
 
-    if sharded:
+    if args.full and sharded:
         # ---- per-stage timeline of three pipelined submits on every rank (HIP events on the streams the stages
         # run on, ms since the first submit): what DESIGN.md section 5's prediction of the overlap is checked against
         # without a second run.  Collectives inside: every rank runs this, in the same order.
@@ -877,12 +913,13 @@ def main():
         allr = [None] * world
         dist.all_gather_object(allr, mine)
         line["stage_ms_per_rank"] = allr
+    if sharded:
         line["rccl"] = {"world": dist.get_world_size(), "group_size": gs, "groups": n_groups,
                         "version": ".".join(str(v) for v in torch.cuda.nccl.version()),
                         "exchange": shs[0].exchange, "three_d": args.three_d,
                         "valid_frames_per_step_per_rank": valid_per_rank}
         assert line["rccl"]["world"] == args.gpus == world
-    if sharded and (world > 1 or os.environ.get("JH_BENCH_SIDE_LEGS")) and not args.no_side_legs:
+    if args.full and sharded and (world > 1 or os.environ.get("JH_BENCH_SIDE_LEGS")) and not args.no_side_legs:
         line.update(side_legs(args, c, common, sd_c, sd_h, calib_dev, device_frames, dev, dist, world, T, gs,
                               make_sharded if args.three_d == "sharded" else None, fr, barrier))
     if sharded:

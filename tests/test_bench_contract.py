@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                           "--time-batch", "8", "--streams", "2", "--no-cpu-baseline", "--no-uint8", "--no-secondary"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -46,10 +46,35 @@ def test_bench_line():
     assert all(k["bound"] == ("hbm" if k["frac_hbm"] > k["frac_mfma"] else "mfma") for k in convs)
 
 
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes what the last timed step computed,
+    whose frame 0 is the reference's own output for the cfg3 fixture input."""
+    import numpy as np
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+                          "--time-batch", "8", "--streams", "2", "--dump-outputs", str(dump)],
+                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["unit"] == "multi-view frames/s" and line["metric"].startswith("multi-view frames/s")
+    assert line["value"] > 0 and abs(line["value"] - 16 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"] + 1e-3
+    for key in ("roofline", "kernels", "cpu_baseline", "reduced_precision", "secondary", "invalid_frame_check",
+                "parity_max_abs_mm_vs_reference_fixture", "uint8_ingest", "driver"):
+        assert key not in line, key
+    pts, conf, valid = [np.load(dump / (n + ".npy")) for n in ("points3D", "confidences", "valid")]
+    assert pts.dtype == conf.dtype == valid.dtype == np.float32
+    assert pts.shape == (2, 8, 23, 3) and conf.shape == (2, 8, 23) and valid.shape == (2, 8)
+    assert valid.sum() == line["config"]["valid_frames_per_step"] == 16 and np.isfinite(pts).all()
+    assert np.array_equal(pts[0], pts[1]) and np.array_equal(conf[0], conf[1])   # same frames on both streams
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "predictor.npz"))["cfg3.points3D"]
+    assert np.abs(pts[0, 0] - gold[0]).max() < 1e-3
+
+
 def test_bench_line_with_cpu_baseline_is_strict_on_any_host():
     """With the CPU baseline leg on: the host-oracle comparison is made with the HIP gather indices substituted
     (oracle.host_parity) and held to the north-star bar; every index flip of this host is a truncation tie."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                           "--time-batch", "8", "--streams", "1", "--cpu-seconds", "1", "--no-uint8", "--no-secondary",
                           "--no-reduced-precision", "--profile-passes", "1"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900)

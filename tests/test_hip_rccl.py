@@ -83,12 +83,12 @@ def test_sharded_predictor_over_rccl(mode, nccl_world1, golden):
 
 
 def test_bench_camera_sharded_leg_over_rccl():
-    """bench.py --force-sharded: the multi-GPU leg of the bench (RCCL process group, two
+    """bench.py --full --force-sharded: the multi-GPU leg of the bench (RCCL process group, two
     pipelined camera-sharded pipelines, side legs) on one rank, through the bench contract."""
     env = dict(os.environ, JH_BENCH_SIDE_LEGS="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-sharded", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-sharded", "--steps", "2",
                           "--warmup", "1", "--time-batch", "2", "--profile-passes", "1"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -5,7 +5,7 @@ pat=${1:-bifpn}; shift
 root=$(pwd)
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kt_run
-rocprofv3 --kernel-trace --stats -d /tmp/kt_run -o run -- python3 $root/bench.py --steps 10 --warmup 3 --streams 1 \
+rocprofv3 --kernel-trace --stats -d /tmp/kt_run -o run -- python3 $root/bench.py --full --steps 10 --warmup 3 --streams 1 \
   --no-reduced-precision --no-cpu-baseline --no-uint8 --no-secondary "$@" > /tmp/kt_run.log 2>&1 || { tail -5 /tmp/kt_run.log; exit 1; }
 db=$(find /tmp/kt_run -name "*.db" | head -1)
 python3 - $db "$pat" <<'PY'

@@ -9,7 +9,7 @@ round=${1:-r06}
 root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$root"
 T=32
-cmd="bench.py --streams 1 --time-batch $T --steps 2 --warmup 1 --no-cpu-baseline --no-uint8 --no-secondary --profile-passes 1"
+cmd="bench.py --full --streams 1 --time-batch $T --steps 2 --warmup 1 --no-cpu-baseline --no-uint8 --no-secondary --profile-passes 1"
 for c in FETCH_SIZE WRITE_SIZE; do
   tools/pmc_pass.sh ${round}_bench_T$T "$c" "%" -- python3 $cmd > /dev/null
   cp gpurun_out/pmc_${round}_bench_T$T/${round}_bench_T${T}_$c.txt gpurun_out/${round}_bench_T${T}_pmc_$c.txt
