@@ -227,6 +227,22 @@ int jh_predictor_stage_keypoints_u8(jh_predictor* pr, const uint8_t* frames_dev,
 int jh_predictor_forward_u8(jh_predictor* pr, const uint8_t* frames_dev, float* points_dev,
                             float* conf_dev, int32_t* valid_dev, void* stream);
 
+/* YUV 4:2:0 ingest (ABI v4, additive): frames as video decoders produce them natively, half the bytes of
+ * uint8 BGR.  Each camera image is one contiguous (3H/2, W) uint8 buffer, H and W even:
+ *   JH_FRAME_I420 (FFmpeg yuv420p): the Y plane (H, W), then U (H/2, W/2), then V (H/2, W/2);
+ *   JH_FRAME_NV12 (hardware decoders): the Y plane, then one interleaved plane (H/2, W), U first.
+ * frames (T,cam_n,3H/2,W).  Every pixel is converted to BGR bytes with the fixed-point BT.601 limited-range
+ * arithmetic of OpenCV's cvtColor(COLOR_YUV2BGR_I420 / _NV12), chroma shared by each 2 x 2 block; those bytes
+ * then take the uint8 path unchanged, so the result equals, bit for bit, jh_predictor_forward_u8 on the converted
+ * frames.  The conversion runs inside the resize / crop kernels.  A graph-replaying predictor keeps one captured
+ * graph per frame format.  JH_FRAME_RGB_F32 / JH_FRAME_BGR_U8 name the formats of the plain / _u8 entry points. */
+#define JH_FRAME_RGB_F32 0
+#define JH_FRAME_BGR_U8 1
+#define JH_FRAME_I420 2
+#define JH_FRAME_NV12 3
+int jh_predictor_forward_yuv(jh_predictor* pr, const uint8_t* frames_dev, int format, float* points_dev,
+                             float* conf_dev, int32_t* valid_dev, void* stream);
+
 /* Integer path of the last call, for parity tests: center3d float (T,3),
  * center3d int (T,3), center_hm (T,C,2), det (T,C,3).  Any pointer may be NULL. */
 int jh_predictor_debug(jh_predictor* pr, float* center3d_f_dev, int32_t* center3d_i_dev,
@@ -256,6 +272,10 @@ int jh_predictor2d_forward(jh_predictor2d* pr, const float* frames_dev, int32_t*
 int jh_predictor2d_forward_u8(jh_predictor2d* pr, const uint8_t* frames_dev, int32_t* points_dev,
                               float* conf_dev, int32_t* valid_dev, void* stream);
 
+/* frames (T,3H/2,W) YUV 4:2:0, format JH_FRAME_I420 or JH_FRAME_NV12 (as jh_predictor_forward_yuv). */
+int jh_predictor2d_forward_yuv(jh_predictor2d* pr, const uint8_t* frames_dev, int format, int32_t* points_dev,
+                               float* conf_dev, int32_t* valid_dev, void* stream);
+
 /* ---- per-launch timing (HIP events on the launch stream; used by bench.py for
  * the roofline figures).  begin() switches recording on for every kernel the
  * library launches from this process; end() synchronises and returns the number
@@ -283,6 +303,11 @@ int jh_op_depthwise(int k, int c, const float* w_host, const float* x_dev, int n
  * y_dev (N,C,h,w) RAW depthwise output, pool_dev (N,C) = sum over pixels of SiLU(InstanceNorm(y)). */
 int jh_op_depthwise_pool(int k, int c, const float* w_host, const float* x_dev, int n, int h, int w,
                          float* y_dev, float* pool_dev, void* stream);
+
+/* The YUV 4:2:0 -> BGR conversion of jh_predictor_forward_yuv on its own: frames (n,3h/2,w) in format
+ * JH_FRAME_I420 / JH_FRAME_NV12 -> out_bgr (n,h,w,3) uint8 BGR (device pointers; h, w even). */
+int jh_op_yuv420_to_bgr(const uint8_t* frames_dev, int format, int n, int h, int w, uint8_t* out_bgr_dev,
+                        void* stream);
 
 /* One fused BiFPN node (jarvis/efficienttrack/model.py:301-353 fusion expressions + :223-232
  * SeparableConvBlock.forward, without its trailing InstanceNorm):

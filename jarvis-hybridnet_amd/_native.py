@@ -104,11 +104,13 @@ _SIGS = {
     "jh_predictor_stage_center_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_stage_keypoints_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_forward_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_predictor_forward_yuv": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor2d_create": (c_int, [c_void_p, c_void_p, ctypes.POINTER(PredictorConfig),
                                       ctypes.POINTER(c_void_p)]),
     "jh_predictor2d_destroy": (None, [c_void_p]),
     "jh_predictor2d_forward": (c_int, [c_void_p] * 6),
     "jh_predictor2d_forward_u8": (c_int, [c_void_p] * 6),
+    "jh_predictor2d_forward_yuv": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_debug": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_hybridnet_forward": (c_int, [c_void_p] * 9),
     "jh_op_conv": (c_int, [c_int] * 7 + [c_void_p, c_void_p, c_void_p] + [c_int] * 4 +
@@ -117,6 +119,7 @@ _SIGS = {
                                 c_void_p, c_void_p]),
     "jh_op_depthwise_pool": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                      c_void_p]),
+    "jh_op_yuv420_to_bgr": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "jh_op_bifpn_node": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_float), c_int, c_int, c_int,
                                  c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
@@ -145,6 +148,29 @@ def lib():
             raise RuntimeError("libjarvis_hip.so ABI version mismatch")
         _lib = handle
     return _lib
+
+
+# frame_format names of the Python API -> JH_FRAME_* of include/jarvis_hip.h.  'bgr': uint8 BGR (H,W,3) images as
+# cv2 delivers them; 'i420' / 'nv12': YUV 4:2:0, one contiguous (3H/2, W) uint8 image per camera, H and W even.
+FRAME_FORMATS = {"bgr": 1, "i420": 2, "nv12": 3}
+YUV_FORMATS = ("i420", "nv12")
+
+
+def frame_format(name):
+    """A frame_format argument checked: None (the frame tensor's dtype decides, the behaviour without the argument)
+    or one of FRAME_FORMATS; anything else raises ValueError."""
+    if name is not None and name not in FRAME_FORMATS:
+        raise ValueError("frame_format must be one of %s or None, got %r" % (sorted(FRAME_FORMATS), name))
+    return name
+
+
+def yuv_frame_hw(shape):
+    """(rows, W) of a YUV 4:2:0 image -> (H, W).  rows = 3H/2 with H and W even: ValueError otherwise (an odd
+    frame height leaves rows that are no multiple of 3)."""
+    rows, w = int(shape[-2]), int(shape[-1])
+    if rows <= 0 or rows % 3 or w <= 0 or w % 2:
+        raise ValueError("a YUV 4:2:0 image is (3H/2, W) bytes with H and W even; got (%d, %d)" % (rows, w))
+    return rows // 3 * 2, w
 
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x3_wide": 2}

@@ -58,27 +58,41 @@ class NativePredictor:
             self.handle, N.ptr(N.dev(cam)), N.ptr(N.dev(intr)), N.ptr(N.dev(dist)), N.stream()))
 
     # ---- single-GPU forward ----------------------------------------------
-    def forward(self, frames, out=None):
-        """frames (T,C,3,H,W) fp32 RGB, or (T,C,H,W,3) uint8 BGR as decoded
-        -> points (T,J,3), conf (T,J), valid (T) int32."""
-        self._check_frames(frames, self.Cloc)
+    def forward(self, frames, out=None, frame_format=None):
+        """frames (T,C,3,H,W) fp32 RGB, or (T,C,H,W,3) uint8 BGR as decoded, or with frame_format 'i420' / 'nv12'
+        (T,C,3H/2,W) uint8 YUV 4:2:0 -> points (T,J,3), conf (T,J), valid (T) int32.  frame_format None: the
+        dtype decides between fp32 RGB and uint8 BGR; 'bgr' requires uint8 BGR."""
+        frame_format = N.frame_format(frame_format)
+        self._check_frames(frames, self.Cloc, frame_format)
         dev = frames.device
         if out is None:
             out = (torch.empty((self.T, self.J, 3), device=dev),
                    torch.empty((self.T, self.J), device=dev),
                    torch.empty((self.T,), device=dev, dtype=torch.int32))
+        if frame_format in N.YUV_FORMATS:
+            N.check(N.lib().jh_predictor_forward_yuv(self.handle, N.ptr(frames), N.FRAME_FORMATS[frame_format],
+                                                     N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.stream()))
+            return out
         fn = N.lib().jh_predictor_forward_u8 if frames.dtype == torch.uint8 else \
             N.lib().jh_predictor_forward
         N.check(fn(self.handle, N.ptr(frames), N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]),
                    N.stream()))
         return out
 
-    def _check_frames(self, frames, cams):
+    def _check_frames(self, frames, cams, frame_format=None):
         """Raw pointers cross the C ABI: refuse anything whose bytes would be misread."""
         H, W = self.cfg.img_h, self.cfg.img_w
         if not (torch.is_tensor(frames) and frames.is_cuda and frames.is_contiguous()):
             raise RuntimeError("frames must be a contiguous CUDA (HIP) tensor")
-        if frames.dtype == torch.uint8:
+        if frame_format in N.YUV_FORMATS:
+            if H % 2 or W % 2:
+                raise ValueError("YUV 4:2:0 frames need an even height and width; this predictor is %d x %d" % (H, W))
+            if frames.dtype != torch.uint8:
+                raise RuntimeError("%s frames must be uint8 (T,C,3H/2,W); got dtype %s" % (frame_format, frames.dtype))
+            want = (self.T, cams, H * 3 // 2, W)
+        elif frame_format == "bgr" and frames.dtype != torch.uint8:
+            raise RuntimeError("frame_format 'bgr' needs uint8 (T,C,H,W,3) frames; got dtype %s" % frames.dtype)
+        elif frames.dtype == torch.uint8:
             want = (self.T, cams, H, W, 3)
         elif frames.dtype == torch.float32:
             want = (self.T, cams, 3, H, W)
@@ -86,7 +100,10 @@ class NativePredictor:
             raise RuntimeError("frames must be float32 RGB (T,C,3,H,W) or uint8 BGR (T,C,H,W,3); "
                                "got dtype %s" % frames.dtype)
         if tuple(frames.shape) != want:
-            raise RuntimeError("frames shape %s, expected %s" % (tuple(frames.shape), want))
+            hint = ""
+            if frames.dtype == torch.uint8 and frames.dim() == 4 and frame_format not in N.YUV_FORMATS:
+                hint = " (YUV 4:2:0 frames: pass frame_format='i420' or 'nv12')"
+            raise RuntimeError("frames shape %s, expected %s%s" % (tuple(frames.shape), want, hint))
 
     # ---- camera-sharded stages -------------------------------------------
     def stage_center(self, frames, det):
@@ -187,10 +204,12 @@ class MultiStreamPredictor:
                     t.record_stream(s)
         self._calib = key
 
-    def forward(self, frames, out=None, then=None):
+    def forward(self, frames, out=None, then=None, frame_format=None):
         """`then(outputs)`, when given, runs inside the batch's stream context right behind the forward and
         before its event is recorded (the drivers enqueue the device->host copy of the results there); its
-        return value replaces the outputs."""
+        return value replaces the outputs.  frame_format: as NativePredictor.forward."""
+        frame_format = N.frame_format(frame_format)
+        self.preds[0]._check_frames(frames, self.preds[0].Cloc, frame_format)     # before any stream work
         i = self._next
         self._next = (i + 1) % len(self.preds)
         s = self.streams[i]
@@ -203,7 +222,7 @@ class MultiStreamPredictor:
         for t in (out or ()):
             t.record_stream(s)
         with torch.cuda.stream(s):
-            res = self.preds[i].forward(frames, out)
+            res = self.preds[i].forward(frames, out, frame_format=frame_format)
             if then is not None:
                 res = then(res)
             ev = torch.cuda.Event(enable_timing=self.timing)

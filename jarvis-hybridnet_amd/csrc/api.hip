@@ -277,6 +277,12 @@ int jh_reconstruct_point(const float* points2d_dev, const float* maxvals_dev, in
     if (_pf.on) _pf.end(s);                                    \
   } while (0)
 
+// bytes of frame data per source pixel of a frame format (kSrc*): fp32 RGB 12, uint8 BGR 3, YUV 4:2:0 1.5
+static double frame_px_bytes(int fmt) { return fmt == kSrcRgbF32 ? 12.0 : fmt == kSrcBgrU8 ? 3.0 : 1.5; }
+
+static_assert(JH_FRAME_RGB_F32 == kSrcRgbF32 && JH_FRAME_BGR_U8 == kSrcBgrU8 && JH_FRAME_I420 == kSrcI420 &&
+                  JH_FRAME_NV12 == kSrcNV12, "frame format codes of the C ABI are preprocess.h's SRC");
+
 struct jh_predictor {
   jh_predictor_config cfg{};
   int T3 = 0;
@@ -306,7 +312,7 @@ struct jh_predictor {
   const void* const* cur_cell = nullptr;     // non-null only while the forward is being captured
   float *g_points = nullptr, *g_conf = nullptr;
   hipStream_t gstream = nullptr;             // capture stream (the caller's may be the null stream)
-  hipGraphExec_t gexec[2] = {nullptr, nullptr};   // [fp32 frames, uint8 frames]
+  hipGraphExec_t gexec[4] = {nullptr, nullptr, nullptr, nullptr};   // one per frame format (kSrc*, preprocess.h)
   ~jh_predictor() {
     for (auto& e : gexec) if (e) (void)hipGraphExecDestroy(e);
     if (gstream) (void)hipStreamDestroy(gstream);
@@ -443,7 +449,7 @@ int jh_predictor_set_calibration(jh_predictor* pr, const float* cam_dev, const f
   return 0;
 }
 
-static int stage_center_impl(jh_predictor* pr, const void* frames_dev, int src_u8, float* det_dev,
+static int stage_center_impl(jh_predictor* pr, const void* frames_dev, int fmt, float* det_dev,
                              void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   JH_REQUIRE(pr->center, "predictor was created without CenterDetect weights");
@@ -451,16 +457,15 @@ static int stage_center_impl(jh_predictor* pr, const void* frames_dev, int src_u
   if (pr->center->stem_fusable) {
     // resize + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->center->stem_src;
-    src.mode = 1; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.src_u8 = src_u8;
+    src.mode = 1; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.fmt = fmt;
     src.H = pr->cfg.img_h; src.W = pr->cfg.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = pr->cfg.mean[i]; src.stdv[i] = pr->cfg.std[i]; }
-    // algorithmic bytes of the fused launch: the four bilinear taps of every network-input pixel (3 channels,
-    // 1 or 4 bytes each) + the stem's 16-channel output at half resolution (16 B per input pixel)
-    // (stem output: 16 or 32 channels at half resolution = 16 or 32 B per input pixel)
-    pr->center->set_stem_traffic((double)N * S * S * (12.0 * (src_u8 ? 1 : 4) + pr->center->stem_channels()));
+    // algorithmic bytes of the fused launch: the four bilinear taps of every network-input pixel (frame_px_bytes
+    // each) + the stem's output at half resolution (16 or 32 channels = 16 or 32 B per input pixel)
+    pr->center->set_stem_traffic((double)N * S * S * (4.0 * frame_px_bytes(fmt) + pr->center->stem_channels()));
   } else {
-    JH_PROF("preprocess_resize", 0.0, (double)N * S * S * (12.0 * (src_u8 ? 1 : 4) + 3 * 4),
-            launch_preprocess_resize(frames_dev, src_u8, pr->center->input.p, N, pr->cfg.img_h,
+    JH_PROF("preprocess_resize", 0.0, (double)N * S * S * (4.0 * frame_px_bytes(fmt) + 3 * 4),
+            launch_preprocess_resize(frames_dev, fmt, pr->center->input.p, N, pr->cfg.img_h,
                                      pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, pr->cur_cell));
   }
   if (pr->center->run(s)) return 1;
@@ -479,7 +484,7 @@ int jh_predictor_stage_center_u8(jh_predictor* pr, const uint8_t* frames_dev, fl
   return stage_center_impl(pr, frames_dev, 1, det_dev, stream);
 }
 
-static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, int src_u8,
+static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, int fmt,
                                 const float* det_all_dev, float* heat_dev, void* stream,
                                 int det_blocks = 1, bool next_centre_set = false) {
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -505,14 +510,14 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, int sr
   if (pr->kp->stem_fusable) {
     // crop + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->kp->stem_src;
-    src.mode = 2; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.src_u8 = src_u8;
+    src.mode = 2; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.fmt = fmt;
     src.center_hm = pr->chm_cur(); src.Cloc = pr->Cloc; src.C = pr->C; src.cam0 = c.cam_lo;
     src.H = c.img_h; src.W = c.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = c.mean[i]; src.stdv[i] = c.std[i]; }
-    pr->kp->set_stem_traffic((double)pr->T * pr->Cloc * pr->B * pr->B * (3.0 * (src_u8 ? 1 : 4) + pr->kp->stem_channels()));
+    pr->kp->set_stem_traffic((double)pr->T * pr->Cloc * pr->B * pr->B * (frame_px_bytes(fmt) + pr->kp->stem_channels()));
   } else {
-    JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->Cloc * pr->B * pr->B * (src_u8 ? 15.0 : 24.0),
-            launch_preprocess_crop(frames_dev, src_u8, pr->chm_cur(), pr->kp->input.p, pr->T, pr->Cloc, pr->C,
+    JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->Cloc * pr->B * pr->B * (frame_px_bytes(fmt) + 12.0),
+            launch_preprocess_crop(frames_dev, fmt, pr->chm_cur(), pr->kp->input.p, pr->T, pr->Cloc, pr->C,
                                    c.cam_lo, c.img_h, c.img_w, pr->B, c.mean, c.std, s, pr->cur_cell));
   }
   if (pr->kp->run(s)) return 1;
@@ -569,10 +574,10 @@ int jh_predictor_stage_3d_blocks(jh_predictor* pr, const float* heat_blocks_dev,
   return 0;
 }
 
-static int forward_eager(jh_predictor* pr, const void* frames_dev, int src_u8, float* points_dev,
+static int forward_eager(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
                          float* conf_dev, int32_t* valid_dev, void* stream) {
-  if (stage_center_impl(pr, frames_dev, src_u8, pr->det_all, stream)) return 1;
-  if (stage_keypoints_impl(pr, frames_dev, src_u8, pr->det_all, nullptr, stream)) return 1;
+  if (stage_center_impl(pr, frames_dev, fmt, pr->det_all, stream)) return 1;
+  if (stage_keypoints_impl(pr, frames_dev, fmt, pr->det_all, nullptr, stream)) return 1;
   return jh_predictor_stage_3d(pr, pr->kp->heat.p, 0, points_dev, conf_dev, valid_dev, stream);
 }
 
@@ -582,15 +587,15 @@ static int forward_eager(jh_predictor* pr, const void* frames_dev, int src_u8, f
 // graph serves every later call: set the cell, launch the graph, copy the results out -- three
 // submissions instead of ~150.  Calibration lives in the predictor's buffers (set_calibration
 // copies into them), weights are immutable for the life of a predictor: nothing to invalidate.
-static int forward_graph(jh_predictor* pr, const void* frames_dev, int src_u8, float* points_dev,
+static int forward_graph(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
                          float* conf_dev, int32_t* valid_dev, hipStream_t s) {
-  hipGraphExec_t& exec = pr->gexec[src_u8 ? 1 : 0];
+  hipGraphExec_t& exec = pr->gexec[fmt];
   if (!exec) {
     hipGraph_t g = nullptr;
     if (!pr->gstream) JH_CHECK_HIP(hipStreamCreateWithFlags(&pr->gstream, hipStreamNonBlocking));
     JH_CHECK_HIP(hipStreamBeginCapture(pr->gstream, hipStreamCaptureModeRelaxed));
     pr->cur_cell = pr->frames_cell;
-    const int rc = forward_eager(pr, nullptr, src_u8, pr->g_points, pr->g_conf, nullptr, pr->gstream);
+    const int rc = forward_eager(pr, nullptr, fmt, pr->g_points, pr->g_conf, nullptr, pr->gstream);
     pr->cur_cell = nullptr;
     const hipError_t e = hipStreamEndCapture(pr->gstream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return 1; }
@@ -610,7 +615,7 @@ static int forward_graph(jh_predictor* pr, const void* frames_dev, int src_u8, f
   return 0;
 }
 
-static int forward_impl(jh_predictor* pr, const void* frames_dev, int src_u8, float* points_dev,
+static int forward_impl(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
                         float* conf_dev, int32_t* valid_dev, void* stream) {
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
   JH_REQUIRE(pr->T3 == pr->T, "forward needs time_batch_3d == time_batch");
@@ -621,8 +626,8 @@ static int forward_impl(jh_predictor* pr, const void* frames_dev, int src_u8, fl
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (pr->use_graph && !profiler().on) (void)hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs);
   if (!pr->use_graph || profiler().on || cs != hipStreamCaptureStatusNone)
-    return forward_eager(pr, frames_dev, src_u8, points_dev, conf_dev, valid_dev, stream);
-  return forward_graph(pr, frames_dev, src_u8, points_dev, conf_dev, valid_dev, static_cast<hipStream_t>(stream));
+    return forward_eager(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, stream);
+  return forward_graph(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, static_cast<hipStream_t>(stream));
 }
 int jh_predictor_forward(jh_predictor* pr, const float* frames_dev, float* points_dev,
                          float* conf_dev, int32_t* valid_dev, void* stream) {
@@ -631,6 +636,14 @@ int jh_predictor_forward(jh_predictor* pr, const float* frames_dev, float* point
 int jh_predictor_forward_u8(jh_predictor* pr, const uint8_t* frames_dev, float* points_dev,
                             float* conf_dev, int32_t* valid_dev, void* stream) {
   return forward_impl(pr, frames_dev, 1, points_dev, conf_dev, valid_dev, stream);
+}
+
+int jh_predictor_forward_yuv(jh_predictor* pr, const uint8_t* frames_dev, int format, float* points_dev,
+                             float* conf_dev, int32_t* valid_dev, void* stream) {
+  JH_REQUIRE(format == JH_FRAME_I420 || format == JH_FRAME_NV12, "jh_predictor_forward_yuv: format must be "
+             "JH_FRAME_I420 or JH_FRAME_NV12");
+  JH_REQUIRE(pr && pr->cfg.img_h % 2 == 0 && pr->cfg.img_w % 2 == 0, "YUV 4:2:0 frames need an even height and width");
+  return forward_impl(pr, frames_dev, format, points_dev, conf_dev, valid_dev, stream);
 }
 
 int jh_predictor_debug(jh_predictor* pr, float* center3d_f_dev, int32_t* center3d_i_dev,
@@ -710,13 +723,15 @@ int jh_predictor2d_create(const jh_params* center_params, const jh_params* kp_pa
 
 void jh_predictor2d_destroy(jh_predictor2d* pr) { delete pr; }
 
-static int forward2d_impl(jh_predictor2d* pr, const void* frames, int src_u8, int32_t* points_dev,
+static int forward2d_impl(jh_predictor2d* pr, const void* frames, int fmt, int32_t* points_dev,
                           float* conf_dev, int32_t* valid_dev, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const auto& c = pr->cfg;
   const int S = c.center_size;
-  JH_PROF("preprocess_resize", 0.0, (double)pr->T * S * S * 24.0,
-          launch_preprocess_resize(frames, src_u8, pr->center->input.p, pr->T, c.img_h, c.img_w, S,
+  // algorithmic bytes as in the 3D stages: four taps (resize) or one pixel (crop) of frame data + the float4 written.
+  // (These counts used to be a flat 24 B per pixel for every format: fp32 resize is 60, uint8 crop 15.)
+  JH_PROF("preprocess_resize", 0.0, (double)pr->T * S * S * (4.0 * frame_px_bytes(fmt) + 12.0),
+          launch_preprocess_resize(frames, fmt, pr->center->input.p, pr->T, c.img_h, c.img_w, S,
                                    c.mean, c.std, s));
   if (pr->center->run(s)) return 1;
   const Act& h = pr->center->heat;
@@ -726,8 +741,8 @@ static int forward2d_impl(jh_predictor2d* pr, const void* frames, int src_u8, in
   const float sx = (float)c.img_w / (float)S, sy = (float)c.img_h / (float)S;
   if (launch_center2d(pr->det, pr->chm, pr->valid, pr->T, sx, sy, pr->B / 2, c.img_w, c.img_h, s))
     return 1;
-  JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->B * pr->B * 24.0,
-          launch_preprocess_crop(frames, src_u8, pr->chm, pr->kp->input.p, pr->T, 1, 1, 0, c.img_h,
+  JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->B * pr->B * (frame_px_bytes(fmt) + 12.0),
+          launch_preprocess_crop(frames, fmt, pr->chm, pr->kp->input.p, pr->T, 1, 1, 0, c.img_h,
                                  c.img_w, pr->B, c.mean, c.std, s));
   if (pr->kp->run(s)) return 1;
   const Act& k = pr->kp->heat;
@@ -747,6 +762,14 @@ int jh_predictor2d_forward(jh_predictor2d* pr, const float* frames_dev, int32_t*
 int jh_predictor2d_forward_u8(jh_predictor2d* pr, const uint8_t* frames_dev, int32_t* points_dev,
                               float* conf_dev, int32_t* valid_dev, void* stream) {
   return forward2d_impl(pr, frames_dev, 1, points_dev, conf_dev, valid_dev, stream);
+}
+
+int jh_predictor2d_forward_yuv(jh_predictor2d* pr, const uint8_t* frames_dev, int format, int32_t* points_dev,
+                               float* conf_dev, int32_t* valid_dev, void* stream) {
+  JH_REQUIRE(format == JH_FRAME_I420 || format == JH_FRAME_NV12, "jh_predictor2d_forward_yuv: format must be "
+             "JH_FRAME_I420 or JH_FRAME_NV12");
+  JH_REQUIRE(pr && pr->cfg.img_h % 2 == 0 && pr->cfg.img_w % 2 == 0, "YUV 4:2:0 frames need an even height and width");
+  return forward2d_impl(pr, frames_dev, format, points_dev, conf_dev, valid_dev, stream);
 }
 
 // ------------------------------------------------------------------- profiling
@@ -861,6 +884,17 @@ int jh_op_depthwise(int k, int c, const float* w_host, const float* x_dev, int n
   if (launch_depthwise(x, wd, k, y.p, stats, s)) return 1;
   if (norm_act >= 0 && launch_norm_apply(y, stats, 1e-5, norm_act, nullptr, nullptr, y.p, nullptr, s)) return 1;
   if (launch_from_channel_last(y, y_dev, s)) return 1;
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int jh_op_yuv420_to_bgr(const uint8_t* frames_dev, int format, int n, int h, int w, uint8_t* out_bgr_dev,
+                        void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(frames_dev && out_bgr_dev, "null frame / output pointer");
+  JH_REQUIRE(format == JH_FRAME_I420 || format == JH_FRAME_NV12, "jh_op_yuv420_to_bgr: format must be "
+             "JH_FRAME_I420 or JH_FRAME_NV12");
+  if (launch_yuv420_to_bgr(frames_dev, format, out_bgr_dev, n, h, w, s)) return 1;
   JH_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }

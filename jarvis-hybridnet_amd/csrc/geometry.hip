@@ -33,19 +33,24 @@ __global__ __launch_bounds__(256) void preprocess_resize_kernel(
   }
 }
 
-int launch_preprocess_resize(const void* frames, int src_u8, float* out, int N, int H, int W, int S,
+int launch_preprocess_resize(const void* frames, int fmt, float* out, int N, int H, int W, int S,
                              const float* mean, const float* stdv, hipStream_t s,
                              const void* const* frames_cell) {
   const size_t total = (size_t)N * S * S;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 8192) blocks = 8192;
   const float3 m = make_float3(mean[0], mean[1], mean[2]), sd = make_float3(stdv[0], stdv[1], stdv[2]);
-  if (src_u8)
-    hipLaunchKernelGGL(preprocess_resize_kernel<1>, dim3(blocks), dim3(256), 0, s, frames, out, N, H,
-                       W, S, (float)H / (float)S, (float)W / (float)S, m, sd, frames_cell);
-  else
-    hipLaunchKernelGGL(preprocess_resize_kernel<0>, dim3(blocks), dim3(256), 0, s, frames, out, N, H,
-                       W, S, (float)H / (float)S, (float)W / (float)S, m, sd, frames_cell);
+  JH_REQUIRE(fmt >= kSrcRgbF32 && fmt <= kSrcNV12, "frame format");
+#define JH_RESIZE(F)                                                                                         \
+  hipLaunchKernelGGL(preprocess_resize_kernel<F>, dim3(blocks), dim3(256), 0, s, frames, out, N, H, W, S,    \
+                     (float)H / (float)S, (float)W / (float)S, m, sd, frames_cell)
+  switch (fmt) {
+    case kSrcRgbF32: JH_RESIZE(kSrcRgbF32); break;
+    case kSrcBgrU8: JH_RESIZE(kSrcBgrU8); break;
+    case kSrcI420: JH_RESIZE(kSrcI420); break;
+    default: JH_RESIZE(kSrcNV12); break;
+  }
+#undef JH_RESIZE
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -68,19 +73,54 @@ __global__ __launch_bounds__(256) void preprocess_crop_kernel(
   }
 }
 
-int launch_preprocess_crop(const void* frames, int src_u8, const int* center_hm, float* out, int T,
+int launch_preprocess_crop(const void* frames, int fmt, const int* center_hm, float* out, int T,
                            int Cloc, int C, int cam0, int H, int W, int B, const float* mean,
                            const float* stdv, hipStream_t s, const void* const* frames_cell) {
   const size_t total = (size_t)T * Cloc * B * B;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 8192) blocks = 8192;
   const float3 m = make_float3(mean[0], mean[1], mean[2]), sd = make_float3(stdv[0], stdv[1], stdv[2]);
-  if (src_u8)
-    hipLaunchKernelGGL(preprocess_crop_kernel<1>, dim3(blocks), dim3(256), 0, s, frames, center_hm,
-                       out, T, Cloc, C, cam0, H, W, B, m, sd, frames_cell);
+  JH_REQUIRE(fmt >= kSrcRgbF32 && fmt <= kSrcNV12, "frame format");
+#define JH_CROP(F)                                                                                            \
+  hipLaunchKernelGGL(preprocess_crop_kernel<F>, dim3(blocks), dim3(256), 0, s, frames, center_hm, out, T, Cloc, \
+                     C, cam0, H, W, B, m, sd, frames_cell)
+  switch (fmt) {
+    case kSrcRgbF32: JH_CROP(kSrcRgbF32); break;
+    case kSrcBgrU8: JH_CROP(kSrcBgrU8); break;
+    case kSrcI420: JH_CROP(kSrcI420); break;
+    default: JH_CROP(kSrcNV12); break;
+  }
+#undef JH_CROP
+  JH_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// YUV 4:2:0 (SRC 2 / 3) -> [N][H][W][3] uint8 BGR through the conversion the resize / crop use (yuv420_px): the
+// unit-test form of that device function.  One thread per output pixel.
+template <int SRC>
+__global__ __launch_bounds__(256) void yuv420_to_bgr_kernel(const void* __restrict__ frames,
+                                                            unsigned char* __restrict__ out, int N, int H, int W) {
+  const size_t total = (size_t)N * H * W;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (size_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % W), y = (int)((i / W) % H);
+    const size_t n = i / ((size_t)H * W);
+    const Rgb8 p = yuv420_px<SRC>(frames, n, y, x, H, W);
+    out[i * 3 + 0] = (unsigned char)p.b;
+    out[i * 3 + 1] = (unsigned char)p.g;
+    out[i * 3 + 2] = (unsigned char)p.r;
+  }
+}
+
+int launch_yuv420_to_bgr(const void* frames, int fmt, unsigned char* out, int N, int H, int W, hipStream_t s) {
+  JH_REQUIRE(fmt == kSrcI420 || fmt == kSrcNV12, "YUV 4:2:0 format");
+  JH_REQUIRE(N >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "YUV 4:2:0 frames need an even height and width");
+  const size_t total = (size_t)N * H * W;
+  int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  if (fmt == kSrcI420)
+    hipLaunchKernelGGL(yuv420_to_bgr_kernel<kSrcI420>, dim3(blocks), dim3(256), 0, s, frames, out, N, H, W);
   else
-    hipLaunchKernelGGL(preprocess_crop_kernel<0>, dim3(blocks), dim3(256), 0, s, frames, center_hm,
-                       out, T, Cloc, C, cam0, H, W, B, m, sd, frames_cell);
+    hipLaunchKernelGGL(yuv420_to_bgr_kernel<kSrcNV12>, dim3(blocks), dim3(256), 0, s, frames, out, N, H, W);
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -523,7 +523,10 @@ int EffTrackPlan::build(const ParamMap& pm, const std::string& pre, int size, in
            if (stem_src.mode) return launch_stem_conv_src(stem_src, xin, wd, xo, sc(st), s);
            return launch_stem_conv(xin, wd, xo, sc(st), s);
          });
-    stem_fusable = JH_ENV_KNOB("JH_STEM_FUSE") != 0;
+    // JH_STEM_FUSE=0: the stand-alone resize / crop kernels feed the stem instead (read at plan build time, so a
+    // process may build plans of both forms)
+    const char* fuse = getenv("JH_STEM_FUSE");
+    stem_fusable = !(fuse && atoi(fuse) == 0);
   } else if (add_conv(pm, conv_desc(2, 3, 2, 1, 3, stem), bb + "_conv_stem.weight", "", false, input, x.a,
                       nullptr, true, &st)) return 1;
   // the stem's InstanceNorm + swish is applied by the first block's conv on load

@@ -7,19 +7,76 @@
 
 namespace jh {
 
-// Two frame formats: SRC = 0: [N][3][H][W] fp32 RGB in [0,1] (the API input of
+// Four frame formats: SRC = 0: [N][3][H][W] fp32 RGB in [0,1] (the API input of
 // JarvisPredictor3D.forward); SRC = 1: [N][H][W][3] uint8 BGR as the video decoder
 // delivers it, converted like predict3D.py:79-80 (`.float()...[:, [2,1,0]] / 255.`) on
-// the fly, so the 4x larger fp32 frame never exists.
+// the fly, so the 4x larger fp32 frame never exists; SRC = 2 / 3: YUV 4:2:0 as decoders
+// produce it natively, one contiguous [3H/2][W] byte image per camera (H, W even):
+// SRC = 2 (I420): the Y plane [H][W], then U [H/2][W/2], then V [H/2][W/2];
+// SRC = 3 (NV12): the Y plane, then one interleaved [H/2][W/2][2] plane, U first.
+// A YUV pixel is converted to the BGR bytes cv2.cvtColor(COLOR_YUV2BGR_I420 / _NV12) gives
+// (yuv420_px) and those bytes enter the uint8 arithmetic unchanged.
+enum { kSrcRgbF32 = 0, kSrcBgrU8 = 1, kSrcI420 = 2, kSrcNV12 = 3 };
+
 template <int SRC>
 __device__ __forceinline__ float frame_px(const void* frames, size_t n, int c, int y, int x, int H,
                                           int W) {
+  static_assert(SRC == kSrcRgbF32 || SRC == kSrcBgrU8, "frame_px: interleaved / planar RGB formats only");
   if (SRC == 0)
     return static_cast<const float*>(frames)[((n * 3 + c) * H + y) * W + x];
   const unsigned char* p = static_cast<const unsigned char*>(frames) + ((n * H + y) * W + x) * 3;
   // the reference driver divides on the GPU, where torch evaluates `x / 255.` as
   // x * (1.f / 255.f) (division by a host scalar is a multiplication by its reciprocal)
   return __fmul_rn((float)p[2 - c], __fdiv_rn(1.f, 255.f));
+}
+
+// BT.601 limited range -> (R, G, B) bytes: the fixed-point arithmetic of OpenCV's
+// cvtColor(COLOR_YUV2BGR_I420 / _NV12) (imgproc/src/color_yuv.simd.hpp).  Every partial sum
+// stays below 2^30 in magnitude; >> on a negative int is an arithmetic shift.
+struct Rgb8 { int r, g, b; };
+__host__ __device__ __forceinline__ Rgb8 yuv_to_rgb8(int Y, int U, int V) {
+  constexpr int CY = 1220542, CUB = 2116026, CUG = -409993, CVG = -852492, CVR = 1673527;
+  constexpr int SHIFT = 20, HALF = 1 << (SHIFT - 1);
+  const int u = U - 128, v = V - 128;
+  const int yy = (Y > 16 ? Y - 16 : 0) * CY + HALF;
+  const auto clamp8 = [](int x) { return x < 0 ? 0 : (x > 255 ? 255 : x); };
+  return Rgb8{clamp8((yy + CVR * v) >> SHIFT), clamp8((yy + CVG * v + CUG * u) >> SHIFT),
+              clamp8((yy + CUB * u) >> SHIFT)};
+}
+
+// pixel (y, x) of YUV 4:2:0 image n (SRC 2 / 3): one Y load and one chroma load (NV12: one
+// 2-byte load; I420: the U and V bytes of the same 2 x 2 block)
+template <int SRC>
+__device__ __forceinline__ Rgb8 yuv420_px(const void* frames, size_t n, int y, int x, int H, int W) {
+  static_assert(SRC == kSrcI420 || SRC == kSrcNV12, "yuv420_px: YUV 4:2:0 formats only");
+  const size_t plane = (size_t)H * W;
+  const unsigned char* img = static_cast<const unsigned char*>(frames) + n * (plane + plane / 2);
+  const int Y = img[(size_t)y * W + x];
+  int U, V;
+  if (SRC == kSrcNV12) {
+    // (H * W is a multiple of 4 and the pair offset is even: the 16-bit load is aligned)
+    const unsigned short uv =
+        *reinterpret_cast<const unsigned short*>(img + plane + (size_t)(y >> 1) * W + (x & ~1));
+    U = uv & 0xff; V = uv >> 8;
+  } else {
+    const size_t c = plane + (size_t)(y >> 1) * (W >> 1) + (x >> 1);
+    U = img[c]; V = img[c + plane / 4];
+  }
+  return yuv_to_rgb8(Y, U, V);
+}
+
+// the three channels (r, g, b) of one pixel as the uint8 path scales them; YUV: one conversion
+// for all three channels
+template <int SRC>
+__device__ __forceinline__ void frame_px3(const void* frames, size_t n, int y, int x, int H, int W, float v[3]) {
+  if constexpr (SRC == kSrcI420 || SRC == kSrcNV12) {
+    const Rgb8 p = yuv420_px<SRC>(frames, n, y, x, H, W);
+    const float k = __fdiv_rn(1.f, 255.f);
+    v[0] = __fmul_rn((float)p.r, k); v[1] = __fmul_rn((float)p.g, k); v[2] = __fmul_rn((float)p.b, k);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = frame_px<SRC>(frames, n, c, y, x, H, W);
+  }
 }
 
 // pixel (oy, ox) of the S x S resized + normalised image n: torchvision tensor resize (bilinear,
@@ -35,10 +92,22 @@ __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, i
   const float lx1 = fminf(fmaxf(__fsub_rn(rx, (float)x0), 0.f), 1.f), lx0 = __fsub_rn(1.f, lx1);
   const float mv[3] = {mean.x, mean.y, mean.z}, sv[3] = {stdv.x, stdv.y, stdv.z};
   float r[3];
+  // YUV: each of the four taps is converted once for all three channels (the per-channel arithmetic
+  // below is that of the uint8 path, so the result equals SRC 1 on the converted bytes bit for bit)
+  float q00[3], q01[3], q10[3], q11[3];
+  if constexpr (SRC == kSrcI420 || SRC == kSrcNV12) {
+    frame_px3<SRC>(frames, n, y0, x0, H, W, q00); frame_px3<SRC>(frames, n, y0, x1, H, W, q01);
+    frame_px3<SRC>(frames, n, y1, x0, H, W, q10); frame_px3<SRC>(frames, n, y1, x1, H, W, q11);
+  }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const float p00 = frame_px<SRC>(frames, n, c, y0, x0, H, W), p01 = frame_px<SRC>(frames, n, c, y0, x1, H, W);
-    const float p10 = frame_px<SRC>(frames, n, c, y1, x0, H, W), p11 = frame_px<SRC>(frames, n, c, y1, x1, H, W);
+    float p00, p01, p10, p11;
+    if constexpr (SRC == kSrcI420 || SRC == kSrcNV12) {
+      p00 = q00[c]; p01 = q01[c]; p10 = q10[c]; p11 = q11[c];
+    } else {
+      p00 = frame_px<SRC>(frames, n, c, y0, x0, H, W); p01 = frame_px<SRC>(frames, n, c, y0, x1, H, W);
+      p10 = frame_px<SRC>(frames, n, c, y1, x0, H, W); p11 = frame_px<SRC>(frames, n, c, y1, x1, H, W);
+    }
     const float a = __fmaf_rn(p00, lx0, __fmul_rn(p01, lx1));
     const float b = __fmaf_rn(p10, lx0, __fmul_rn(p11, lx1));
     const float v = __fmaf_rn(a, ly0, __fmul_rn(b, ly1));
@@ -58,10 +127,18 @@ __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int
   const float mv[3] = {mean.x, mean.y, mean.z}, sv[3] = {stdv.x, stdv.y, stdv.z};
   float r[3];
   const bool ok = ix >= 0 && ix < W && iy >= 0 && iy < H;
+  if constexpr (SRC == kSrcI420 || SRC == kSrcNV12) {
+    // (outside the frame: 0 before the normalisation, as for the other formats -- not the conversion of Y = U = V = 0)
+    float q[3] = {0.f, 0.f, 0.f};
+    if (ok) frame_px3<SRC>(frames, n, iy, ix, H, W, q);
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float v = ok ? frame_px<SRC>(frames, n, c, iy, ix, H, W) : 0.f;
-    r[c] = __fdiv_rn(__fsub_rn(v, mv[c]), sv[c]);
+    for (int c = 0; c < 3; ++c) r[c] = __fdiv_rn(__fsub_rn(q[c], mv[c]), sv[c]);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float v = ok ? frame_px<SRC>(frames, n, c, iy, ix, H, W) : 0.f;
+      r[c] = __fdiv_rn(__fsub_rn(v, mv[c]), sv[c]);
+    }
   }
   return make_float4(r[0], r[1], r[2], 0.f);
 }
@@ -71,7 +148,7 @@ struct StemSource {
   int mode = 0;               // 0: the plan's own input tensor; 1: resize of the frames; 2: crop of the frames
   const void* frames = nullptr;
   const void* const* frames_cell = nullptr;    // graph replays: the frame pointer of the current call
-  int src_u8 = 0;
+  int fmt = 0;                                 // frame format: SRC of preprocess.h (kSrc*)
   const int* center_hm = nullptr;              // crop: [T][C][2]
   int Cloc = 0, C = 0, cam0 = 0;               // crop: image n = (t, local camera)
   int H = 0, W = 0;                            // frame size

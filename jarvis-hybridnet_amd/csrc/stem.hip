@@ -198,8 +198,16 @@ int launch_stem_conv_src(const StemSource& src, const Act& x, const float* w_dev
       hipLaunchKernelGGL((stem_conv_kernel<M, U, 16>), grid, dim3(256), (M == 1 && U == 0) ? pad_f32 : 0, s, x.p,       \
                          w_dev, y.p, stats, x.H, x.W, sa);                                                              \
   } while (0)
-  if (src.mode == 1) { if (src.src_u8) JH_STEM(1, 1); else JH_STEM(1, 0); }
-  else { if (src.src_u8) JH_STEM(2, 1); else JH_STEM(2, 0); }
+  JH_REQUIRE(src.fmt >= kSrcRgbF32 && src.fmt <= kSrcNV12, "frame format");
+#define JH_STEM_FMT(M)                                     \
+  switch (src.fmt) {                                       \
+    case kSrcRgbF32: JH_STEM(M, kSrcRgbF32); break;        \
+    case kSrcBgrU8: JH_STEM(M, kSrcBgrU8); break;          \
+    case kSrcI420: JH_STEM(M, kSrcI420); break;            \
+    default: JH_STEM(M, kSrcNV12); break;                  \
+  }
+  if (src.mode == 1) { JH_STEM_FMT(1) } else { JH_STEM_FMT(2) }
+#undef JH_STEM_FMT
 #undef JH_STEM
   JH_CHECK_HIP(hipGetLastError());
   return 0;

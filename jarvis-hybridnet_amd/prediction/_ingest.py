@@ -255,6 +255,34 @@ def host_outputs(ring, slot, outs):
     return host
 
 
+def driver_format(frame_format, frame_spec, ndim):
+    """The drivers' frame_format argument checked: True for the YUV 4:2:0 formats, False for 'bgr' (the frames'
+    dtype then decides between uint8 BGR and fp32 RGB, as without the argument); ValueError for anything else and
+    for a YUV `frame_spec` that is no ((..., 3H/2, W), uint8) with H and W even."""
+    from .. import _native as N
+    if frame_format not in N.FRAME_FORMATS:
+        raise ValueError("frame_format must be one of %s, got %r" % (sorted(N.FRAME_FORMATS), frame_format))
+    yuv = frame_format in N.YUV_FORMATS
+    if yuv and frame_spec is not None:
+        shape, dtype = tuple(frame_spec[0]), frame_spec[1]
+        if len(shape) != ndim or dtype != torch.uint8:
+            raise ValueError("frame_spec of %s frames must be (%s, torch.uint8); got %r" % (
+                frame_format, "(C, 3H/2, W)" if ndim == 3 else "(3H/2, W)", frame_spec))
+        N.yuv_frame_hw(shape)
+    return yuv
+
+
+def check_driver_frames(frames, frame_format, ndim):
+    """One YUV 4:2:0 frame (set) handed to a driver: `ndim`-d uint8 (..., 3H/2, W) with H, W even, or ValueError
+    (the bytes would be misread)."""
+    from .. import _native as N
+    dtype = frames.dtype if torch.is_tensor(frames) else torch.from_numpy(np.empty(0, frames.dtype)).dtype
+    if len(frames.shape) != ndim or dtype != torch.uint8:
+        raise ValueError("%s frames must be uint8 %s; got %s %s" % (
+            frame_format, "(C, 3H/2, W)" if ndim == 3 else "(3H/2, W)", dtype, tuple(frames.shape)))
+    N.yuv_frame_hw(frames.shape)
+
+
 def pipeline_for(owner, frames, time_batch, streams, submit, emit, frame_spec=None):
     """The pipeline for frame sets shaped like `frames` (or like `frame_spec` = (shape, torch dtype) when
     `frames` is a fill callable), cached on `owner` (the predictor) so that its pinned buffers are re-used by

@@ -24,16 +24,25 @@ class _Native2D:
             img_h, img_w, batch, 0, 0, 1, (ctypes.c_float * 3)(*cfg.DATASET.MEAN),
             (ctypes.c_float * 3)(*cfg.DATASET.STD), N.precision_id(precision))
         self.T, self.J = batch, cfg.KEYPOINTDETECT.NUM_JOINTS
+        self.H, self.W = img_h, img_w
         self.handle = ctypes.c_void_p()
         pc, pk = N.Params(center_state), N.Params(kp_state)
         N.check(N.lib().jh_predictor2d_create(pc.handle, pk.handle, ctypes.byref(c),
                                               ctypes.byref(self.handle)))
 
-    def forward(self, frames):
+    def forward(self, frames, frame_format=None):
         dev = frames.device
         pts = torch.empty((self.T, self.J, 2), device=dev, dtype=torch.int32)
         conf = torch.empty((self.T, self.J), device=dev)
         valid = torch.empty((self.T,), device=dev, dtype=torch.int32)
+        if frame_format in N.YUV_FORMATS:
+            if tuple(frames.shape) != (self.T, self.H * 3 // 2, self.W) or frames.dtype != torch.uint8 \
+                    or not frames.is_contiguous():
+                raise RuntimeError("%s frames %s, expected contiguous uint8 %s" % (
+                    frame_format, (frames.dtype, tuple(frames.shape)), (self.T, self.H * 3 // 2, self.W)))
+            N.check(N.lib().jh_predictor2d_forward_yuv(self.handle, N.ptr(frames), N.FRAME_FORMATS[frame_format],
+                                                       N.ptr(pts), N.ptr(conf), N.ptr(valid), N.stream()))
+            return pts, conf, valid
         fn = N.lib().jh_predictor2d_forward_u8 if frames.dtype == torch.uint8 else \
             N.lib().jh_predictor2d_forward
         N.check(fn(self.handle, N.ptr(frames), N.ptr(pts), N.ptr(conf), N.ptr(valid), N.stream()))
@@ -82,9 +91,31 @@ class JarvisPredictor2D(nn.Module):
             return None, None
         return pts[0].long(), conf[0]
 
-    def forward_batch(self, imgs):
+    def forward_yuv(self, img, frame_format):
+        """img (3H/2,W) or (1,3H/2,W) uint8 YUV 4:2:0, frame_format 'i420' / 'nv12' (H, W even; see
+        JarvisPredictor3D.forward_yuv) -> (points2D (J,2) int64 pixels, confidences (J,)) or (None, None)."""
+        from .jarvis3D import _yuv_frames
+        if torch.is_tensor(img) and img.dim() == 2:
+            img = img.unsqueeze(0)
+        x = _yuv_frames(img, frame_format, 3)
+        H, W = N.yuv_frame_hw(x.shape)
+        pts, conf, valid = self.native(H, W, x.shape[0]).forward(x, frame_format)
+        if int(valid[0].item()) == 0:
+            return None, None
+        return pts[0].long(), conf[0]
+
+    def forward_batch(self, imgs, frame_format=None):
         """imgs (T,3,H,W) fp32 RGB or (T,H,W,3) uint8 BGR, independent images ->
-        points2D (T,J,2) int32, confidences (T,J), valid (T) int32; no host sync."""
+        points2D (T,J,2) int32, confidences (T,J), valid (T) int32; no host sync.  frame_format 'i420' / 'nv12':
+        imgs (T,3H/2,W) uint8 YUV 4:2:0; 'bgr': uint8 BGR required; None: the dtype decides."""
+        frame_format = N.frame_format(frame_format)
+        if frame_format in N.YUV_FORMATS:
+            from .jarvis3D import _yuv_frames
+            x = _yuv_frames(imgs, frame_format, 3)
+            H, W = N.yuv_frame_hw(x.shape)
+            return self.native(H, W, x.shape[0]).forward(x, frame_format)
+        if frame_format == "bgr" and imgs.dtype != torch.uint8:
+            raise ValueError("frame_format 'bgr' needs uint8 (T,H,W,3) frames; got dtype %s" % imgs.dtype)
         if imgs.dtype == torch.uint8:
             x = N.dev(imgs, torch.uint8)
             return self.native(x.shape[1], x.shape[2], x.shape[0]).forward(x)

@@ -156,10 +156,37 @@ class JarvisPredictor3D(nn.Module):
             return None, None
         return points, conf
 
-    def forward_batch(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients):
+    def forward_yuv(self, frames, frame_format, cameraMatrices, intrinsicMatrices, distortionCoefficients):
+        """frames (C,3H/2,W) uint8 YUV 4:2:0 as video decoders produce them natively, frame_format 'i420'
+        (FFmpeg yuv420p: Y, U, V planes) or 'nv12' (Y plane, interleaved UV plane); H and W even.  Same result,
+        bit for bit, as forward_uint8 on the BGR bytes of cv2.cvtColor(COLOR_YUV2BGR_I420 / _NV12) of each
+        image (BT.601 limited range); the conversion runs inside the resize / crop kernels.
+        -> (points3D (1,J,3), confidences (1,J)) or (None, None)."""
+        x = _yuv_frames(frames, frame_format, 3)
+        check_native_seam(self)
+        H, W = N.yuv_frame_hw(x.shape)
+        pr = self.native(H, W)
+        pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
+        points, conf, valid = pr.forward(x.unsqueeze(0), frame_format=frame_format)
+        if int(valid[0].item()) == 0:
+            return None, None
+        return points, conf
+
+    def forward_batch(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None):
         """Throughput form: imgs (T,C,3,H,W) fp32 RGB or (T,C,H,W,3) uint8 BGR,
         independent time steps -> points (T,J,3), confidences (T,J), valid (T) int32;
-        no host synchronisation."""
+        no host synchronisation.  frame_format 'i420' / 'nv12': imgs (T,C,3H/2,W) uint8 YUV 4:2:0 (see
+        forward_yuv); 'bgr': uint8 BGR required; None: the dtype decides."""
+        frame_format = N.frame_format(frame_format)
+        if frame_format in N.YUV_FORMATS:
+            x = _yuv_frames(imgs, frame_format, 4)
+            check_native_seam(self)
+            H, W = N.yuv_frame_hw(x.shape)
+            pr = self.native(H, W, time_batch=x.shape[0])
+            pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
+            return pr.forward(x, frame_format=frame_format)
+        if frame_format == "bgr" and imgs.dtype != torch.uint8:
+            raise ValueError("frame_format 'bgr' needs uint8 (T,C,H,W,3) frames; got dtype %s" % imgs.dtype)
         check_native_seam(self)
         if imgs.dtype == torch.uint8:
             x = N.dev(imgs, torch.uint8)
@@ -170,3 +197,15 @@ class JarvisPredictor3D(nn.Module):
         pr = self.native(x.shape[3], x.shape[4], time_batch=x.shape[0])
         pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
         return pr.forward(x)
+
+
+def _yuv_frames(frames, frame_format, ndim):
+    """YUV 4:2:0 frames of the public API checked (format, dtype, rank, even H and W) and made a contiguous CUDA
+    tensor; ValueError for what would be misread."""
+    if frame_format not in N.YUV_FORMATS:
+        raise ValueError("frame_format must be one of %s, got %r" % (list(N.YUV_FORMATS), frame_format))
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != ndim:
+        raise ValueError("%s frames must be a %d-d uint8 tensor (..., 3H/2, W); got %s" % (
+            frame_format, ndim, (frames.dtype, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)))
+    N.yuv_frame_hw(frames.shape)
+    return N.dev(frames, torch.uint8)

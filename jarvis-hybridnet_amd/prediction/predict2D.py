@@ -54,7 +54,7 @@ def frame_row(points2D, confidences, num_joints):
 
 
 def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch=1,
-                     csv_name="data2D.csv", frame_spec=None):
+                     csv_name="data2D.csv", frame_spec=None, frame_format="bgr"):
     """Run `predictor` (JarvisPredictor2D) over an iterable of frames -- (H,W,3) uint8 BGR arrays
     / tensors exactly as cv2 delivers them, or (3,H,W) fp32 RGB -- and write `csv_name`
     (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -67,8 +67,13 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
     time_batch > 1 groups that many consecutive frames into one launch sequence
     (`forward_batch`); rows are written in frame order and are the same as with
     time_batch = 1.  A short last group is padded with its last frame and the padding rows
-    are dropped."""
-    from ._ingest import host_outputs, pipeline_for
+    are dropped.
+
+    frame_format 'i420' / 'nv12': the frames are (3H/2,W) uint8 YUV 4:2:0 (H, W even; fill callables with
+    `frame_spec=((3H/2,W), torch.uint8)`), see predict3D_frames.  Anything but 'bgr' (the default), 'i420' and
+    'nv12' raises ValueError."""
+    from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
+    yuv = driver_format(frame_format, frame_spec, 2)
     from .predict3D import _as_host
     os.makedirs(output_dir, exist_ok=True)
     if params is not None:
@@ -95,7 +100,7 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
         def submit(x, slot):
             # the reference driver's own conversion of uint8 frames (predict2D.py:93-94) is what the
             # uint8 entry point fuses into the resize / crop kernels
-            res = predictor.forward_batch(x)
+            res = predictor.forward_batch(x, frame_format=frame_format) if yuv else predictor.forward_batch(x)
             ev = None
             if x.is_cuda:
                 res = host_outputs(ring, slot, res)
@@ -108,6 +113,8 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
             for frame in frames:
                 if not callable(frame):
                     frame = frame if torch.is_tensor(frame) and frame.is_cuda else _as_host(frame)
+                    if yuv:
+                        check_driver_frames(frame, frame_format, 2)
                     k = (frame.dtype, tuple(frame.shape), torch.is_tensor(frame))
                 else:
                     k = key if key is not None else ("fill",)

@@ -13,6 +13,8 @@ import re
 
 import torch
 
+from .. import _native as N
+
 _PLAIN = re.compile(r"^[A-Za-z0-9_./\\][A-Za-z0-9_./\\ +=,@%-]*$")
 _RESERVED = {"", "~", "null", "true", "false", "yes", "no", "on", "off", "y", "n"}
 
@@ -65,7 +67,7 @@ def frame_row(points3D, confidences, num_joints):
 
 def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                      distortionCoefficients, cfg, output_dir, params=None, time_batch=1, streams=1,
-                     frame_spec=None):
+                     frame_spec=None, frame_format="bgr"):
     """Run `predictor` over an iterable of multi-view frame sets -- (C,H,W,3) uint8 BGR
     arrays / tensors exactly as cv2 delivers them, or (C,3,H,W) fp32 RGB -- and write
     data3D.csv (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -92,8 +94,14 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     Retained memory: the predictor keeps ONE ingest pipeline (streams + 2 pinned host buffers and as many HBM
     buffers of a whole time batch, e.g. 7.5 GB + 7.5 GB at 12 x 1280 x 1024 uint8, T = 32, 3 streams) for the next
     call with the same frame format; a call with another format / time batch / stream count replaces it, an
-    aborted call drops it, `_ingest.release_ingest_buffers(predictor)` frees it."""
-    from ._ingest import host_outputs, pipeline_for
+    aborted call drops it, `_ingest.release_ingest_buffers(predictor)` frees it.
+
+    frame_format 'i420' / 'nv12': the frame sets are (C,3H/2,W) uint8 YUV 4:2:0 as video decoders produce them
+    (FFmpeg yuv420p / hardware NV12; H and W even; fill callables with `frame_spec=((C,3H/2,W), torch.uint8)`): half
+    the bytes of BGR to stage and upload, converted inside the resize / crop kernels (JarvisPredictor3D.forward_yuv).
+    The default 'bgr' is the behaviour described above.  Anything else raises ValueError."""
+    from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
+    yuv = driver_format(frame_format, frame_spec, 3)
     os.makedirs(output_dir, exist_ok=True)
     if params is not None:
         params.output_dir = output_dir
@@ -118,13 +126,19 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
 
         def submit(x, slot):
             if hasattr(predictor, "native_streams"):
-                h, w = (x.shape[2], x.shape[3]) if x.dtype == torch.uint8 else (x.shape[3], x.shape[4])
+                if yuv:
+                    h, w = N.yuv_frame_hw(x.shape)
+                else:
+                    h, w = (x.shape[2], x.shape[3]) if x.dtype == torch.uint8 else (x.shape[3], x.shape[4])
                 msp = predictor.native_streams(h, w, time_batch, streams)
                 msp.set_calibration(*calib)
                 # results leave for pinned host memory on the forward's own stream (behind it, before its event)
-                res = msp.forward(x, then=lambda outs: host_outputs(ring, slot, outs))
+                res = msp.forward(x, then=lambda outs: host_outputs(ring, slot, outs),
+                                  frame_format=frame_format if yuv else None)
                 return res, msp.last_event
-            res = predictor.forward_batch(x, *calib)           # any object with the batch interface
+            # any object with the batch interface
+            res = predictor.forward_batch(x, *calib, frame_format=frame_format) if yuv else \
+                predictor.forward_batch(x, *calib)
             ev = None
             if x.is_cuda:
                 res = host_outputs(ring, slot, res)
@@ -137,6 +151,8 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             for frames in frame_sets:
                 if not callable(frames):
                     frames = frames if torch.is_tensor(frames) and frames.is_cuda else _as_host(frames)
+                    if yuv:
+                        check_driver_frames(frames, frame_format, 3)
                     k = (frames.dtype, tuple(frames.shape), torch.is_tensor(frames))
                 else:
                     k = key if key is not None else ("fill",)

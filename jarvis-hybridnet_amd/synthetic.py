@@ -173,3 +173,34 @@ def smooth_heatmaps(num_cameras, num_joints, size, seed):
             a = 60.0 + 190.0 * torch.rand(1, generator=g).item()
             out[c, j] = a * torch.exp(-((xx - cx) ** 2 + (yy - cy) ** 2) / (2 * s * s))
     return out + torch.rand(out.shape, generator=g) * 2.0
+
+
+def pack_yuv420(y, u, v, fmt):
+    """Planes Y (..., H, W), U and V (..., H/2, W/2) uint8 -> (..., 3H/2, W) uint8 in the layout `fmt`:
+    'i420' = Y, then U, then V; 'nv12' = Y, then one interleaved plane, U first."""
+    y, u, v = np.asarray(y, np.uint8), np.asarray(u, np.uint8), np.asarray(v, np.uint8)
+    lead, (H, W) = y.shape[:-2], y.shape[-2:]
+    if fmt == "i420":
+        chroma = np.concatenate([u.reshape(lead + (-1,)), v.reshape(lead + (-1,))], -1).reshape(lead + (H // 2, W))
+    elif fmt == "nv12":
+        chroma = np.stack([u, v], -1).reshape(lead + (H // 2, W))
+    else:
+        raise ValueError("fmt must be 'i420' or 'nv12', got %r" % (fmt,))
+    return np.ascontiguousarray(np.concatenate([y, chroma], -2))
+
+
+def bgr_to_yuv420(bgr, fmt):
+    """uint8 BGR (..., H, W, 3), H and W even -> YUV 4:2:0 (..., 3H/2, W) in the layout `fmt`: a forward BT.601
+    limited-range transform with 2 x 2 averaged chroma (test data; only the inverse, the conversion the kernels
+    apply, is a contract)."""
+    x = np.asarray(bgr, np.float32)
+    b, g, r = x[..., 0], x[..., 1], x[..., 2]
+    y = 16.0 + 0.256788 * r + 0.504129 * g + 0.097906 * b
+    u = 128.0 - 0.148223 * r - 0.290993 * g + 0.439216 * b
+    v = 128.0 + 0.439216 * r - 0.367788 * g - 0.071427 * b
+
+    def pool(p):
+        return 0.25 * (p[..., 0::2, 0::2] + p[..., 0::2, 1::2] + p[..., 1::2, 0::2] + p[..., 1::2, 1::2])
+
+    q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)  # noqa: E731
+    return pack_yuv420(q(y), q(pool(u)), q(pool(v)), fmt)

@@ -1,6 +1,10 @@
 """Where the time of the predict3D_frames ingest pipeline goes on this host: memcpy into pinned memory by N
 threads, pinned host -> HBM bandwidth, and the driver with (a) numpy frame sets, (b) in-place fill callables
-that write nothing (the pipeline without the host copy).  Run on the GPU box."""
+that write nothing (the pipeline without the host copy).  Run on the GPU box.
+
+--format bgr,i420,nv12 (default bgr): the driver timings for each listed frame format in one run, on the same
+seeded frame sets (YUV 4:2:0: the BGR sets through synthetic.bgr_to_yuv420), with the bytes per frame set."""
+import argparse
 import os
 import sys
 import time
@@ -14,6 +18,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from jarvis_hybridnet_amd import synthetic as S  # noqa: E402
 from jarvis_hybridnet_amd.prediction._ingest import usable_cores  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--format", default="bgr", help="comma-separated frame formats of the driver timings: bgr, i420, nv12")
+args = ap.parse_args()
+FORMATS = args.format.split(",")
+for f in FORMATS:
+    if f not in ("bgr", "i420", "nv12"):
+        ap.error("unknown frame format %r" % f)
 
 C, H, W, J, T, K = 12, 1024, 1280, 23, 32, 3
 print("usable cores", usable_cores(), "affinity", len(os.sched_getaffinity(0)))
@@ -60,15 +72,22 @@ cal = [t.cuda() for t in calib]
 sets = [(S.blob_frames(calib, W, H, J, 52 + i)[0].permute(0, 2, 3, 1)[..., [2, 1, 0]] * 255).round().to(torch.uint8).numpy()
         for i in range(8)]
 out = "/dev/shm/jh_probe"
-spec = ((C, H, W, 3), torch.uint8)
-for name, gen in (("numpy frame sets", lambda n: (sets[i % 8] for i in range(n))),
-                  ("fill callables (no host copy)", lambda n: ((lambda dst: None) for i in range(n)))):
-    predict3D_frames(jp, gen(T * K), *cal, cfg, out, time_batch=T, streams=K, frame_spec=spec)
-    torch.cuda.synchronize()
-    n = T * K * 8
-    t0 = time.perf_counter()
-    predict3D_frames(jp, gen(n), *cal, cfg, out, time_batch=T, streams=K, frame_spec=spec)
-    dt = time.perf_counter() - t0
-    st = next(iter(jp._ingest_cache.values())).stats
-    print("predict3D_frames, %s: %.0f frames/s; per batch ms: %s" % (
-        name, n / dt, {k: round(1e3 * v / st["batches"], 2) for k, v in st.items() if k != "batches"}))
+for fmt in FORMATS:
+    if fmt == "bgr":
+        fsets, spec = sets, ((C, H, W, 3), torch.uint8)
+    else:
+        fsets = [S.bgr_to_yuv420(a, fmt) for a in sets]
+        spec = ((C, H * 3 // 2, W), torch.uint8)
+    nbytes = fsets[0].nbytes
+    for name, gen in (("numpy frame sets", lambda n: (fsets[i % 8] for i in range(n))),
+                      ("fill callables (no host copy)", lambda n: ((lambda dst: None) for i in range(n)))):
+        predict3D_frames(jp, gen(T * K), *cal, cfg, out, time_batch=T, streams=K, frame_spec=spec, frame_format=fmt)
+        torch.cuda.synchronize()
+        n = T * K * 8
+        t0 = time.perf_counter()
+        predict3D_frames(jp, gen(n), *cal, cfg, out, time_batch=T, streams=K, frame_spec=spec, frame_format=fmt)
+        dt = time.perf_counter() - t0
+        st = next(iter(jp._ingest_cache.values())).stats
+        print("predict3D_frames [%s, %d B per frame set], %s: %.0f frames/s (%.1f GB/s of frames); per batch ms: %s" % (
+            fmt, nbytes, name, n / dt, n * nbytes / dt / 1e9,
+            {k: round(1e3 * v / st["batches"], 2) for k, v in st.items() if k != "batches"}))
