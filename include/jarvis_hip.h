@@ -248,6 +248,37 @@ int jh_predictor_forward_yuv(jh_predictor* pr, const uint8_t* frames_dev, int fo
 int jh_predictor_debug(jh_predictor* pr, float* center3d_f_dev, int32_t* center3d_i_dev,
                        int32_t* center_hm_dev, float* det_dev, void* stream);
 
+/* Per-frame camera masks (ABI v4, additive).  mask_dev: (T, num_cameras) bytes on the device, nonzero = the
+ * camera takes part in frame t; NULL = all cameras, i.e. exactly the unmasked entry point.  Frame t is computed
+ * as the reference computes it for the cameras with mask[t][c] != 0 alone, in their original order (its
+ * `cameras_to_use` subset, utils/reprojection.py): a masked camera adds nothing to the triangulation, is not
+ * counted among the detecting cameras, and is left out of the mean over cameras of the voxel grid, which divides
+ * by the number of unmasked cameras.  valid[t] = 0 when fewer than two unmasked cameras detect (maxval > 50).
+ * The frame slot of a masked camera may hold anything (stale bytes, NaN): its 2D networks still run, per image,
+ * and nothing of them reaches a result.
+ * jh_predictor_forward_masked: jh_predictor_forward / _u8 / _yuv by format code (JH_FRAME_*).  The mask is copied
+ * into a buffer the predictor owns (T * num_cameras bytes, beside two T-int32 count buffers), so the caller's buffer
+ * is free once the stream has passed the call, and a graph-replaying predictor keeps replaying: it captures one
+ * further graph per frame format for the masked form.
+ * The staged pair, for cam_lo = 0, cam_n = num_cameras (what the masked forward runs between stage 1, which has no
+ * camera sum, and the results): jh_predictor_stage_keypoints_masked is jh_predictor_stage_keypoints / _u8 by format
+ * code (JH_FRAME_RGB_F32 / JH_FRAME_BGR_U8) with the masked triangulation -- it decides valid[] and the centres --
+ * and jh_predictor_stage_3d_masked is jh_predictor_stage_3d with the masked gather (rows t0 .. t0+T3-1 of the
+ * mask).  Give both the SAME mask: stage 3 after an unmasked stage 2 would average other cameras than the centre
+ * was triangulated from.  These two read mask_dev in place: keep it alive and unchanged until the stream has
+ * passed the call. */
+int jh_predictor_forward_masked(jh_predictor* pr, const void* frames_dev, int format, const uint8_t* mask_dev,
+                                float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
+int jh_predictor_stage_keypoints_masked(jh_predictor* pr, const void* frames_dev, int format,
+                                        const float* det_all_dev, const uint8_t* mask_dev, float* heat_dev,
+                                        void* stream);
+int jh_predictor_stage_3d_masked(jh_predictor* pr, const float* heat_all_dev, int t0, const uint8_t* mask_dev,
+                                 float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
+/* Counts of the last MASKED forward / masked stage 2, for parity tests: n_active (T) int32 = unmasked cameras per frame (the
+ * divisor of the mean over cameras), num_cams_detect (T) int32 = those of them with maxval > 50.  Any pointer may
+ * be NULL.  Unmasked calls do not update them. */
+int jh_predictor_debug_mask(jh_predictor* pr, int32_t* n_active_dev, int32_t* num_cams_detect_dev, void* stream);
+
 /* HybridNetBackbone.forward: crops (T,C,3,B,B) normalised NCHW dev, center_hm
  * (T,C,2) int32, center3d (T,3) int32 -> heatmap_final (T,J,Gh,Gh,Gh) optional,
  * heatmaps_padded (T,C,J,hs,hs) optional, points (T,J,3), conf (T,J). */

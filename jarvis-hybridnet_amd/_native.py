@@ -105,6 +105,13 @@ _SIGS = {
     "jh_predictor_stage_keypoints_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_forward_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_forward_yuv": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_predictor_forward_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
+    "jh_predictor_stage_keypoints_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p]),
+    "jh_predictor_stage_3d_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]),
+    "jh_predictor_debug_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor2d_create": (c_int, [c_void_p, c_void_p, ctypes.POINTER(PredictorConfig),
                                       ctypes.POINTER(c_void_p)]),
     "jh_predictor2d_destroy": (None, [c_void_p]),
@@ -171,6 +178,24 @@ def yuv_frame_hw(shape):
     if rows <= 0 or rows % 3 or w <= 0 or w % 2:
         raise ValueError("a YUV 4:2:0 image is (3H/2, W) bytes with H and W even; got (%d, %d)" % (rows, w))
     return rows // 3 * 2, w
+
+
+def camera_mask(mask, shape, what="camera_mask"):
+    """A camera_mask argument checked and made a contiguous uint8 CPU or device tensor of `shape` with values
+    0 / 1: None stays None; a bool or integer tensor, or a sequence of bools / integers, nonzero = use the camera.
+    A floating dtype or another shape raises ValueError."""
+    if mask is None:
+        return None
+    if not torch.is_tensor(mask):
+        try:
+            mask = torch.as_tensor(mask)
+        except Exception as e:                              # noqa: BLE001 -- ragged / non-numeric sequences
+            raise ValueError("%s must be a bool or integer tensor or sequence of shape %s: %s" % (what, tuple(shape), e))
+    if mask.dtype.is_floating_point or mask.dtype.is_complex:
+        raise ValueError("%s must be bool or integer (nonzero = use the camera); got dtype %s" % (what, mask.dtype))
+    if tuple(mask.shape) != tuple(shape):
+        raise ValueError("%s must have shape %s; got %s" % (what, tuple(shape), tuple(mask.shape)))
+    return (mask != 0).to(torch.uint8).contiguous()
 
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x3_wide": 2}

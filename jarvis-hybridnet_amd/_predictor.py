@@ -58,17 +58,28 @@ class NativePredictor:
             self.handle, N.ptr(N.dev(cam)), N.ptr(N.dev(intr)), N.ptr(N.dev(dist)), N.stream()))
 
     # ---- single-GPU forward ----------------------------------------------
-    def forward(self, frames, out=None, frame_format=None):
+    def forward(self, frames, out=None, frame_format=None, camera_mask=None):
         """frames (T,C,3,H,W) fp32 RGB, or (T,C,H,W,3) uint8 BGR as decoded, or with frame_format 'i420' / 'nv12'
         (T,C,3H/2,W) uint8 YUV 4:2:0 -> points (T,J,3), conf (T,J), valid (T) int32.  frame_format None: the
-        dtype decides between fp32 RGB and uint8 BGR; 'bgr' requires uint8 BGR."""
+        dtype decides between fp32 RGB and uint8 BGR; 'bgr' requires uint8 BGR.
+        camera_mask (T,C) bool / integer, host or device: frame t uses the cameras with a nonzero entry only
+        (jh_predictor_forward_masked); None: all cameras, the unmasked entry points."""
         frame_format = N.frame_format(frame_format)
+        camera_mask = N.camera_mask(camera_mask, (self.T, self.C))
         self._check_frames(frames, self.Cloc, frame_format)
         dev = frames.device
         if out is None:
             out = (torch.empty((self.T, self.J, 3), device=dev),
                    torch.empty((self.T, self.J), device=dev),
                    torch.empty((self.T,), device=dev, dtype=torch.int32))
+        if camera_mask is not None:
+            fmt = N.FRAME_FORMATS[frame_format] if frame_format in N.YUV_FORMATS else int(frames.dtype == torch.uint8)
+            mask = camera_mask.to(dev, non_blocking=True)       # (copied by the call: free once it is enqueued)
+            N.check(N.lib().jh_predictor_forward_masked(self.handle, N.ptr(frames), fmt, N.ptr(mask), N.ptr(out[0]),
+                                                        N.ptr(out[1]), N.ptr(out[2]), N.stream()))
+            if mask.is_cuda:
+                mask.record_stream(torch.cuda.current_stream())
+            return out
         if frame_format in N.YUV_FORMATS:
             N.check(N.lib().jh_predictor_forward_yuv(self.handle, N.ptr(frames), N.FRAME_FORMATS[frame_format],
                                                      N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.stream()))
@@ -112,13 +123,33 @@ class NativePredictor:
             N.lib().jh_predictor_stage_center
         N.check(fn(self.handle, N.ptr(frames), N.ptr(det), N.stream()))
 
-    def stage_keypoints(self, frames, det_all, heat):
+    def stage_keypoints(self, frames, det_all, heat, camera_mask=None):
+        """camera_mask: a (T,C) uint8 DEVICE tensor (kept alive by the caller until the stream has passed the call;
+        all cameras local) for the masked triangulation; give stage_3d the same one."""
         self._check_frames(frames, self.Cloc)
+        if camera_mask is not None:
+            mask = self._device_mask(camera_mask)
+            N.check(N.lib().jh_predictor_stage_keypoints_masked(
+                self.handle, N.ptr(frames), int(frames.dtype == torch.uint8), N.ptr(det_all), N.ptr(mask), N.ptr(heat),
+                N.stream()))
+            return
         fn = N.lib().jh_predictor_stage_keypoints_u8 if frames.dtype == torch.uint8 else \
             N.lib().jh_predictor_stage_keypoints
         N.check(fn(self.handle, N.ptr(frames), N.ptr(det_all), N.ptr(heat), N.stream()))
 
-    def stage_3d(self, heat_all, t0, points, conf, valid):
+    def _device_mask(self, camera_mask):
+        if not (torch.is_tensor(camera_mask) and camera_mask.is_cuda and camera_mask.dtype == torch.uint8
+                and camera_mask.is_contiguous() and tuple(camera_mask.shape) == (self.T, self.C)):
+            raise ValueError("the staged calls take camera_mask as a contiguous (%d, %d) uint8 device tensor"
+                             % (self.T, self.C))
+        return camera_mask
+
+    def stage_3d(self, heat_all, t0, points, conf, valid, camera_mask=None):
+        if camera_mask is not None:
+            mask = self._device_mask(camera_mask)
+            N.check(N.lib().jh_predictor_stage_3d_masked(self.handle, N.ptr(heat_all), t0, N.ptr(mask), N.ptr(points),
+                                                         N.ptr(conf), N.ptr(valid), N.stream()))
+            return
         N.check(N.lib().jh_predictor_stage_3d(self.handle, N.ptr(heat_all), t0, N.ptr(points),
                                               N.ptr(conf), N.ptr(valid), N.stream()))
 
@@ -144,6 +175,14 @@ class NativePredictor:
         N.check(N.lib().jh_predictor_debug(self.handle, N.ptr(c3f), N.ptr(c3i), N.ptr(chm),
                                            N.ptr(det), N.stream()))
         return dict(center3d=c3f, center3d_int=c3i, center_hm=chm, det=det)
+
+    def debug_mask(self, device):
+        """Counts of the last MASKED forward: n_active (T) unmasked cameras, num_cams_detect (T) those of them with
+        maxval > 50."""
+        n_act = torch.empty((self.T,), device=device, dtype=torch.int32)
+        n_det = torch.empty((self.T,), device=device, dtype=torch.int32)
+        N.check(N.lib().jh_predictor_debug_mask(self.handle, N.ptr(n_act), N.ptr(n_det), N.stream()))
+        return dict(n_active=n_act, num_cams_detect=n_det)
 
     def hybridnet_forward(self, crops, center_hm, center3d, want_final=True, want_padded=True):
         dev = crops.device
@@ -204,11 +243,12 @@ class MultiStreamPredictor:
                     t.record_stream(s)
         self._calib = key
 
-    def forward(self, frames, out=None, then=None, frame_format=None):
+    def forward(self, frames, out=None, then=None, frame_format=None, camera_mask=None):
         """`then(outputs)`, when given, runs inside the batch's stream context right behind the forward and
         before its event is recorded (the drivers enqueue the device->host copy of the results there); its
-        return value replaces the outputs.  frame_format: as NativePredictor.forward."""
+        return value replaces the outputs.  frame_format, camera_mask: as NativePredictor.forward."""
         frame_format = N.frame_format(frame_format)
+        camera_mask = N.camera_mask(camera_mask, (self.preds[0].T, self.preds[0].C))
         self.preds[0]._check_frames(frames, self.preds[0].Cloc, frame_format)     # before any stream work
         i = self._next
         self._next = (i + 1) % len(self.preds)
@@ -222,7 +262,7 @@ class MultiStreamPredictor:
         for t in (out or ()):
             t.record_stream(s)
         with torch.cuda.stream(s):
-            res = self.preds[i].forward(frames, out, frame_format=frame_format)
+            res = self.preds[i].forward(frames, out, frame_format=frame_format, camera_mask=camera_mask)
             if then is not None:
                 res = then(res)
             ev = torch.cuda.Event(enable_timing=self.timing)

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include "nets.h"
 #include "bifpn_node.h"
+#include "camera_mask.h"
 
 namespace jh {
 static thread_local std::string g_err;
@@ -312,7 +313,15 @@ struct jh_predictor {
   const void* const* cur_cell = nullptr;     // non-null only while the forward is being captured
   float *g_points = nullptr, *g_conf = nullptr;
   hipStream_t gstream = nullptr;             // capture stream (the caller's may be the null stream)
-  hipGraphExec_t gexec[4] = {nullptr, nullptr, nullptr, nullptr};   // one per frame format (kSrc*, preprocess.h)
+  // one per frame format (kSrc*, preprocess.h); [4 + fmt]: the masked form of that format
+  hipGraphExec_t gexec[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // Camera mask (camera_mask.h).  mask_buf [T][C]: the predictor's copy of the current call's mask -- the masked
+  // kernels (and a captured graph of them) read this buffer, so the mask may change from call to call.  mask_cur:
+  // the mask of the call under way, nullptr = no mask (the plain kernels).  n_active / n_detect [T]: written by
+  // the masked triangulation.
+  unsigned char* mask_buf = nullptr;
+  const unsigned char* mask_cur = nullptr;
+  int *n_active = nullptr, *n_detect = nullptr;
   ~jh_predictor() {
     for (auto& e : gexec) if (e) (void)hipGraphExecDestroy(e);
     if (gstream) (void)hipStreamDestroy(gstream);
@@ -323,10 +332,18 @@ struct jh_predictor {
              hipStream_t s, const HeatLayout* layout = nullptr) {
     const double g3 = (double)G * G * G;
     // algorithmic traffic of the gather: every heatmap byte once in, the volume once out
+    if (mask_cur) {
+      // (algorithmic traffic as for all cameras: an upper bound, the unmasked cameras' heatmaps are what is read)
+      JH_PROF("reproject_gather_masked", 0.0, 4.0 * T3 * ((double)C * Hh * Hh * J + g3 * J),
+              launch_reproject_masked(cam, intr, dist, c3i_cur() + t0 * 3, chm_cur() + t0 * C * 2, heat_all, coarse,
+                                      v2v->input.p, nullptr, T3, C, G, cfg.grid_spacing, hs, Jp,
+                                      /*heat_pad=*/0, /*div255=*/1, mask_cur + (size_t)t0 * C, s, layout));
+    } else {
     JH_PROF("reproject_gather", 0.0, 4.0 * T3 * ((double)C * Hh * Hh * J + g3 * J),
             launch_reproject(cam, intr, dist, c3i_cur() + t0 * 3, chm_cur() + t0 * C * 2, heat_all, coarse,
                              v2v->input.p, nullptr, T3, C, G, cfg.grid_spacing, hs, Jp,
                              /*heat_pad=*/0, /*div255=*/1, s, layout));
+    }
     if (v2v->run(s)) return 1;
     JH_PROF("softargmax", 0.0, 4.0 * T3 * (g3 / 8) * J,
             launch_softargmax(v2v->output.p, c3i_cur() + t0 * 3, sa_partial, sa_max, points, conf,
@@ -400,6 +417,12 @@ int jh_predictor_create(const jh_params* center_params, const jh_params* hybrid_
     pr->sa_max = reinterpret_cast<int*>(reinterpret_cast<char*>(pr->sa_partial) + pb);
   }
   for (int k = 0; k < 2; ++k) JH_CHECK_HIP(hipMemset(pr->valid_[k], 0, (size_t)T * sizeof(int)));
+  if (m.get(reinterpret_cast<void**>(&pr->mask_buf), (size_t)T * C)) return 1;
+  if (m.get(reinterpret_cast<void**>(&pr->n_active), (size_t)T * sizeof(int))) return 1;
+  if (m.get(reinterpret_cast<void**>(&pr->n_detect), (size_t)T * sizeof(int))) return 1;
+  JH_CHECK_HIP(hipMemset(pr->mask_buf, 1, (size_t)T * C));
+  JH_CHECK_HIP(hipMemset(pr->n_active, 0, (size_t)T * sizeof(int)));
+  JH_CHECK_HIP(hipMemset(pr->n_detect, 0, (size_t)T * sizeof(int)));
   // graph replay: by default for the single-frame-set call (T = 1), where the forward is
   // launch-bound; JH_GRAPH=1 / 0 forces it on / off for every time batch
   const int knob = JH_ENV_KNOB("JH_GRAPH");
@@ -501,9 +524,16 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, int fm
   // preds * (downsampling_scale * 2), jarvis3D.py:138-141,158-160
   const float sx2 = (float)((double)c.img_w / (double)c.center_size) * 2.f;
   const float sy2 = (float)((double)c.img_h / (double)c.center_size) * 2.f;
+  if (pr->mask_cur) {
+    JH_PROF("triangulate_masked", 0.0, 0.0,
+            launch_triangulate_masked(det_all_dev, pr->cam, pr->intr, pr->dist, pr->c3f, pr->c3i_cur(),
+                                      pr->chm_cur(), pr->valid_cur(), pr->T, pr->C, sx2, sy2, 255.f, pr->B / 2,
+                                      c.img_w, c.img_h, pr->mask_cur, pr->n_active, pr->n_detect, s));
+  } else {
   JH_PROF("triangulate", 0.0, 0.0,
           launch_triangulate(det_all_dev, pr->cam, pr->intr, pr->dist, pr->c3f, pr->c3i_cur(), pr->chm_cur(),
                              pr->valid_cur(), pr->T, pr->C, sx2, sy2, 255.f, pr->B / 2, c.img_w, c.img_h, s));
+  }
   if (det_all_dev != pr->det_all)
     JH_CHECK_HIP(hipMemcpyAsync(pr->det_all, det_all_dev, (size_t)pr->T * pr->C * 3 * sizeof(float),
                                 hipMemcpyDeviceToDevice, s));
@@ -589,7 +619,7 @@ static int forward_eager(jh_predictor* pr, const void* frames_dev, int fmt, floa
 // copies into them), weights are immutable for the life of a predictor: nothing to invalidate.
 static int forward_graph(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
                          float* conf_dev, int32_t* valid_dev, hipStream_t s) {
-  hipGraphExec_t& exec = pr->gexec[fmt];
+  hipGraphExec_t& exec = pr->gexec[fmt + (pr->mask_cur ? 4 : 0)];
   if (!exec) {
     hipGraph_t g = nullptr;
     if (!pr->gstream) JH_CHECK_HIP(hipStreamCreateWithFlags(&pr->gstream, hipStreamNonBlocking));
@@ -615,8 +645,25 @@ static int forward_graph(jh_predictor* pr, const void* frames_dev, int fmt, floa
   return 0;
 }
 
+static int forward_unmasked(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
+                            float* conf_dev, int32_t* valid_dev, void* stream);
+
+// mask_dev != nullptr: the masked kernels, reading the predictor's copy of the mask (made here, on the caller's
+// stream, outside any graph of the predictor's own: the captured launches keep pointing at mask_buf)
 static int forward_impl(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
-                        float* conf_dev, int32_t* valid_dev, void* stream) {
+                        float* conf_dev, int32_t* valid_dev, void* stream,
+                        const unsigned char* mask_dev = nullptr) {
+  if (!mask_dev) return forward_unmasked(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, stream);
+  JH_CHECK_HIP(hipMemcpyAsync(pr->mask_buf, mask_dev, (size_t)pr->T * pr->C, hipMemcpyDeviceToDevice,
+                              static_cast<hipStream_t>(stream)));
+  pr->mask_cur = pr->mask_buf;
+  const int rc = forward_unmasked(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, stream);
+  pr->mask_cur = nullptr;
+  return rc;
+}
+
+static int forward_unmasked(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
+                            float* conf_dev, int32_t* valid_dev, void* stream) {
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
   JH_REQUIRE(pr->T3 == pr->T, "forward needs time_batch_3d == time_batch");
   JH_REQUIRE(frames_dev && points_dev && conf_dev, "null frame / output pointer");
@@ -644,6 +691,46 @@ int jh_predictor_forward_yuv(jh_predictor* pr, const uint8_t* frames_dev, int fo
              "JH_FRAME_I420 or JH_FRAME_NV12");
   JH_REQUIRE(pr && pr->cfg.img_h % 2 == 0 && pr->cfg.img_w % 2 == 0, "YUV 4:2:0 frames need an even height and width");
   return forward_impl(pr, frames_dev, format, points_dev, conf_dev, valid_dev, stream);
+}
+
+int jh_predictor_forward_masked(jh_predictor* pr, const void* frames_dev, int format, const uint8_t* mask_dev,
+                                float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
+  JH_REQUIRE(pr, "bad argument");
+  JH_REQUIRE(format >= JH_FRAME_RGB_F32 && format <= JH_FRAME_NV12, "jh_predictor_forward_masked: unknown frame format");
+  if (format == JH_FRAME_I420 || format == JH_FRAME_NV12)
+    JH_REQUIRE(pr->cfg.img_h % 2 == 0 && pr->cfg.img_w % 2 == 0, "YUV 4:2:0 frames need an even height and width");
+  return forward_impl(pr, frames_dev, format, points_dev, conf_dev, valid_dev, stream, mask_dev);
+}
+
+int jh_predictor_stage_keypoints_masked(jh_predictor* pr, const void* frames_dev, int format,
+                                        const float* det_all_dev, const uint8_t* mask_dev, float* heat_dev,
+                                        void* stream) {
+  JH_REQUIRE(pr && mask_dev, "bad argument");
+  JH_REQUIRE(format == JH_FRAME_RGB_F32 || format == JH_FRAME_BGR_U8, "masked stage 2: fp32 RGB or uint8 BGR frames");
+  JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "masked stage 2 needs all cameras local");
+  pr->mask_cur = mask_dev;
+  const int rc = stage_keypoints_impl(pr, frames_dev, format, det_all_dev, heat_dev, stream, 1, true);
+  pr->mask_cur = nullptr;
+  return rc;
+}
+
+int jh_predictor_stage_3d_masked(jh_predictor* pr, const float* heat_all_dev, int t0, const uint8_t* mask_dev,
+                                 float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
+  JH_REQUIRE(pr && mask_dev, "bad argument");
+  JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "masked stage 3 needs all cameras local");
+  pr->mask_cur = mask_dev;
+  const int rc = jh_predictor_stage_3d(pr, heat_all_dev, t0, points_dev, conf_dev, valid_dev, stream);
+  pr->mask_cur = nullptr;
+  return rc;
+}
+
+int jh_predictor_debug_mask(jh_predictor* pr, int32_t* n_active_dev, int32_t* num_cams_detect_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(pr, "bad argument");
+  const size_t T = pr->T;
+  if (n_active_dev) JH_CHECK_HIP(hipMemcpyAsync(n_active_dev, pr->n_active, T * sizeof(int), hipMemcpyDeviceToDevice, s));
+  if (num_cams_detect_dev) JH_CHECK_HIP(hipMemcpyAsync(num_cams_detect_dev, pr->n_detect, T * sizeof(int), hipMemcpyDeviceToDevice, s));
+  return 0;
 }
 
 int jh_predictor_debug(jh_predictor* pr, float* center3d_f_dev, int32_t* center3d_i_dev,

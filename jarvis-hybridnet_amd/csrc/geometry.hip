@@ -13,6 +13,7 @@
 //                      jarvis/hybridnet/model.py:73-88
 #include "jh_common.h"
 #include "preprocess.h"
+#include "camera_mask.h"
 
 namespace jh {
 
@@ -325,25 +326,37 @@ __device__ __forceinline__ void project_one(const float* M, const float* K, cons
 // One 64-thread block per frame t.  det: [T][C][3] (x, y, raw maxval).
 // Outputs: center3d_f [T][3] float, center3d_i [T][3] int (truncated),
 // center_hm [T][C][2] int (truncated + clamped crop centres), valid [T].
-__global__ __launch_bounds__(64) void triangulate_kernel(
+// MASK (camera_mask.h): camera c of frame t takes part iff mask[t][c] != 0.  A masked camera's term of A^T A is an
+// exact 0.0 -- SELECTED, not multiplied: its detection may be NaN -- and s + 0.0 == s, so the centre has the bits
+// of a run over the unmasked cameras alone; it is not counted either.  Its crop centre is still written (the
+// clamped projection of the centre: in range whatever its frame held).
+template <bool MASK>
+__device__ __forceinline__ void triangulate_body(
     const float* __restrict__ det, const float* __restrict__ cam, const float* __restrict__ intr,
     const float* __restrict__ dist, float* __restrict__ center3d_f, int* __restrict__ center3d_i,
     int* __restrict__ center_hm, int* __restrict__ valid, int C, float sx2, float sy2, float wdiv,
-    int hw, int W, int H) {
+    int hw, int W, int H, const unsigned char* __restrict__ mask, int* __restrict__ n_active,
+    int* __restrict__ n_detect) {
   __shared__ double ata[16];
   __shared__ double contrib[64][17];            // per-camera terms of A^T A (summed in camera order)
   __shared__ float ctr[3];
   __shared__ int cnt;
+  __shared__ int act;
   const int t = blockIdx.x, c = threadIdx.x;
-  if (c == 0) cnt = 0;
+  if (c == 0) { cnt = 0; if constexpr (MASK) act = 0; }
   __syncthreads();
   if (c < C) {
+    bool live = true;
+    if constexpr (MASK) {
+      live = mask[(size_t)t * C + c] != 0;
+      if (live) atomicAdd(&act, 1);
+    }
     const float* d = det + ((size_t)t * C + c) * 3;
     const float* K = intr + c * 9;
     const float* M = cam + c * 12;
     const float cx = K[6], cy = K[7], fx = K[0], fy = K[4];
     const float k1 = dist[c * 5 + 0], k2 = dist[c * 5 + 1];
-    if (d[2] > 50.f) atomicAdd(&cnt, 1);
+    if (live && d[2] > 50.f) atomicAdd(&cnt, 1);
     const float wgt = __fdiv_rn(d[2], wdiv);
     // undistort the detection (single-step inverse), reprojection.py:71-78
     float u = __fsub_rn(__fmul_rn(d[0], sx2), cx);
@@ -364,7 +377,10 @@ __global__ __launch_bounds__(64) void triangulate_kernel(
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        contrib[c][i * 4 + j] = (double)r0[i] * (double)r0[j] + (double)r1[i] * (double)r1[j];
+      {
+        const double term = (double)r0[i] * (double)r0[j] + (double)r1[i] * (double)r1[j];
+        contrib[c][i * 4 + j] = live ? term : 0.0;
+      }
   }
   __syncthreads();
   if (c < 16) {                                 // fixed order: the result does not depend on timing
@@ -385,6 +401,7 @@ __global__ __launch_bounds__(64) void triangulate_kernel(
       center3d_i[t * 3 + k] = (int)f;          // .int() truncates, jarvis3D.py:183
     }
     valid[t] = cnt >= 2 ? 1 : 0;
+    if constexpr (MASK) { n_active[t] = act; n_detect[t] = cnt; }
   }
   __syncthreads();
   if (c < C) {
@@ -396,6 +413,37 @@ __global__ __launch_bounds__(64) void triangulate_kernel(
     center_hm[((size_t)t * C + c) * 2 + 0] = iu;
     center_hm[((size_t)t * C + c) * 2 + 1] = iv;
   }
+}
+
+__global__ __launch_bounds__(64) void triangulate_kernel(
+    const float* __restrict__ det, const float* __restrict__ cam, const float* __restrict__ intr,
+    const float* __restrict__ dist, float* __restrict__ center3d_f, int* __restrict__ center3d_i,
+    int* __restrict__ center_hm, int* __restrict__ valid, int C, float sx2, float sy2, float wdiv,
+    int hw, int W, int H) {
+  triangulate_body<false>(det, cam, intr, dist, center3d_f, center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H,
+                          nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(64) void triangulate_masked_kernel(
+    const float* __restrict__ det, const float* __restrict__ cam, const float* __restrict__ intr,
+    const float* __restrict__ dist, float* __restrict__ center3d_f, int* __restrict__ center3d_i,
+    int* __restrict__ center_hm, int* __restrict__ valid, int C, float sx2, float sy2, float wdiv,
+    int hw, int W, int H, const unsigned char* __restrict__ mask, int* __restrict__ n_active,
+    int* __restrict__ n_detect) {
+  triangulate_body<true>(det, cam, intr, dist, center3d_f, center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H,
+                         mask, n_active, n_detect);
+}
+
+int launch_triangulate_masked(const float* det, const float* cam, const float* intr, const float* dist,
+                              float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C,
+                              float sx2, float sy2, float wdiv, int hw, int W, int H,
+                              const unsigned char* mask, int* n_active, int* n_detect, hipStream_t s) {
+  JH_REQUIRE(C <= 64, "at most 64 cameras");
+  JH_REQUIRE(mask && n_active && n_detect, "camera mask");
+  hipLaunchKernelGGL(triangulate_masked_kernel, dim3(T), dim3(64), 0, s, det, cam, intr, dist, center3d_f,
+                     center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H, mask, n_active, n_detect);
+  JH_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 int launch_triangulate(const float* det, const float* cam, const float* intr, const float* dist,

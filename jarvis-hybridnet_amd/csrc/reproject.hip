@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <atomic>
 #include "jh_common.h"
+#include "camera_mask.h"
 
 namespace jh {
 
@@ -114,11 +115,14 @@ __device__ __forceinline__ rp2 lerp_ref2(rp2 p0, rp2 p1, float w0, float w1) {
 // memory parallelism, hides the latency here.
 constexpr int kCamBatch = 1;
 
-template <int Q>
-__global__ __launch_bounds__(256) void repro_gather_kernel(
+// MASK (camera_mask.h): cameras with mask[t][c] == 0 are skipped -- their heatmaps are never loaded -- and the mean
+// divides by the number of cameras left.
+template <int Q, bool MASK>
+__device__ __forceinline__ void repro_gather_body(
     const float2* __restrict__ coarse, const float* __restrict__ heat, float* __restrict__ vol,
     int* __restrict__ idx_out, int C, int G, int hs, int Jp, int heat_pad, int div255, int ci_n,
-    int cj_n, FastDiv fgh, FastDiv frows, FastDiv fcjn, FastDiv fbpp, HeatLayout lay) {
+    int cj_n, FastDiv fgh, FastDiv frows, FastDiv fcjn, FastDiv fbpp, HeatLayout lay,
+    const unsigned char* __restrict__ mask) {
   extern __shared__ __attribute__((aligned(16))) float2 ctab[];   // [C][ci_n][cj_n][Gh]
   const BlockId bid = xcd_block();             // consecutive planes share heatmap regions
   const int t = bid.y;
@@ -185,6 +189,9 @@ __global__ __launch_bounds__(256) void repro_gather_kernel(
         const_cast<float*>(heat_t + (size_t)cblk * lay.block_stride + (size_t)cloc * (plane_bytes >> 2)), 0,
         plane_bytes, 0x00020000);
     if (++cloc == lay.cams_per_block) { cloc = 0; ++cblk; }
+    if constexpr (MASK) {
+      if (mask[(size_t)t * C + cb] == 0) continue;            // (uniform)
+    }
     int src[kCamBatch];
 #pragma unroll
     for (int cc = 0; cc < kCamBatch; ++cc) {
@@ -238,11 +245,24 @@ __global__ __launch_bounds__(256) void repro_gather_kernel(
   // 2^32 inputs for c = 3 ... 16, 18, 20, 24, 32 and 255: identical bits for every |x| >= 1e-37 (below
   // that, where the quotient is denormal, it can differ in the last denormal bit).  3 instead of 11
   // instructions per division; the epilogue was 21 % of the kernel's vector instructions.
-  const float fc = (float)C;
+  // MASK: the divisor is the frame's number of unmasked cameras, any integer in 1 .. 64 -- outside the set the
+  // reciprocal form was checked for -- so the mean is an IEEE division there (bit-equal to the reciprocal form
+  // wherever that one is exact).
+  int n_cam = C;
+  if constexpr (MASK) {
+    n_cam = 0;
+    for (int c = 0; c < C; ++c) n_cam += mask[(size_t)t * C + c] != 0;
+    n_cam = max(n_cam, 1);                                   // (no camera at all: the sums are 0, the volume too)
+  }
+  const float fc = (float)n_cam;
   const float rfc = __fdiv_rn(1.f, fc), r255 = __fdiv_rn(1.f, 255.f);
   auto divc = [](float x, float c, float rc) __attribute__((always_inline)) {
     const float q = __fmul_rn(x, rc);
     return __fmaf_rn(__fmaf_rn(-q, c, x), rc, q);
+  };
+  auto mean = [&](float x) __attribute__((always_inline)) {
+    if constexpr (MASK) return __fdiv_rn(x, fc);
+    else return divc(x, fc, rfc);
   };
 #pragma unroll
   for (int q = 0; q < Q; ++q) {
@@ -250,8 +270,8 @@ __global__ __launch_bounds__(256) void repro_gather_kernel(
     const int vsrc = item / Q, quad = item % Q;
     if (wave_vox0 + vsrc < vox_end) {
       float4 r;
-      r.x = divc(acc[q].x, fc, rfc); r.y = divc(acc[q].y, fc, rfc);
-      r.z = divc(acc[q].z, fc, rfc); r.w = divc(acc[q].w, fc, rfc);
+      r.x = mean(acc[q].x); r.y = mean(acc[q].y);
+      r.z = mean(acc[q].z); r.w = mean(acc[q].w);
       if (div255) {
         r.x = divc(r.x, 255.f, r255); r.y = divc(r.y, 255.f, r255);
         r.z = divc(r.z, 255.f, r255); r.w = divc(r.w, 255.f, r255);
@@ -259,6 +279,25 @@ __global__ __launch_bounds__(256) void repro_gather_kernel(
       *reinterpret_cast<float4*>(vol + ((size_t)t * nvox + wave_vox0 + vsrc) * Jp + quad * 4) = r;
     }
   }
+}
+
+template <int Q>
+__global__ __launch_bounds__(256) void repro_gather_kernel(
+    const float2* __restrict__ coarse, const float* __restrict__ heat, float* __restrict__ vol,
+    int* __restrict__ idx_out, int C, int G, int hs, int Jp, int heat_pad, int div255, int ci_n,
+    int cj_n, FastDiv fgh, FastDiv frows, FastDiv fcjn, FastDiv fbpp, HeatLayout lay) {
+  repro_gather_body<Q, false>(coarse, heat, vol, idx_out, C, G, hs, Jp, heat_pad, div255, ci_n, cj_n, fgh, frows, fcjn,
+                              fbpp, lay, nullptr);
+}
+
+template <int Q>
+__global__ __launch_bounds__(256) void repro_gather_masked_kernel(
+    const float2* __restrict__ coarse, const float* __restrict__ heat, float* __restrict__ vol,
+    int* __restrict__ idx_out, int C, int G, int hs, int Jp, int heat_pad, int div255, int ci_n,
+    int cj_n, FastDiv fgh, FastDiv frows, FastDiv fcjn, FastDiv fbpp, HeatLayout lay,
+    const unsigned char* __restrict__ mask) {
+  repro_gather_body<Q, true>(coarse, heat, vol, idx_out, C, G, hs, Jp, heat_pad, div255, ci_n, cj_n, fgh, frows, fcjn,
+                             fbpp, lay, mask);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -325,8 +364,11 @@ __device__ __forceinline__ void lds_read_quads(cube_f4 (&h)[Q], unsigned addr) {
   }
 }
 
-template <int Q, int CI, int NT>
-__global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
+// MASK (camera_mask.h): the camera loop walks the frame's unmasked cameras only -- position n of the walk is camera
+// cam(n), kept four deep in scalar registers from the wave's ballot over the mask row; the double buffers alternate by
+// POSITION, memory is addressed by CAMERA.  Nothing of a masked camera is requested: no table, no patch DMA, no tap.
+template <int Q, int CI, int NT, bool MASK>
+__device__ __forceinline__ void repro_cube_body(const CubeArgs a, const unsigned char* mask) {
   // voxels per thread: a wave's group g = w * VPT + v is the i-plane g % CI and the j-rows 4 (g / CI) .. + 3 of the
   // cube, 16 k each -- j-row groups vary slowest over the waves, so in a cube that is ragged along j (72 = 4.5 x 16)
   // the waves without a voxel inside the grid are spread evenly over the SIMDs and skip the tap arithmetic
@@ -368,6 +410,20 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
   const int plane_bytes = Hh * Hh * JPB;
   const size_t nvox = (size_t)G * G * G, nvox_c = (size_t)Gh * Gh * Gh;
   const float* heat_t = a.heat + (size_t)t * a.lay.frame_stride;
+  // cameras of the walk: Cn of them; cm0 .. cm3 = the cameras at positions c .. c + 3 of the loop below (past the end:
+  // a camera that exists, its data is requested by nobody)
+  int Cn = C, cm0 = 0, cm1 = 1, cm2 = 2, cm3 = 3;
+  unsigned long long cam_rest = 0;
+  auto cam_pop = [&](int fallback) __attribute__((always_inline)) {
+    int r = fallback;
+    if (cam_rest) { r = __builtin_ctzll(cam_rest); cam_rest &= cam_rest - 1; }
+    return r;
+  };
+  if constexpr (MASK) {
+    cam_rest = __builtin_amdgcn_ballot_w64(lane < C && mask[(size_t)t * C + min(lane, C - 1)] != 0);
+    Cn = __builtin_popcountll(cam_rest);
+    cm0 = cam_pop(0); cm1 = cam_pop(cm0); cm2 = cam_pop(cm1); cm3 = cam_pop(cm2);
+  }
 
   if (tid < JPB / 4) reinterpret_cast<float*>(smem + kZeroOff)[tid] = 0.f;
 
@@ -412,8 +468,8 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
 #pragma unroll
   for (int e = 0; e < TPT; ++e)
     if (e * NT + tid < NTAB) {
-      tpre[0][e] = a.coarse[(size_t)(t * C) * nvox_c + ctab_src[e]];
-      if (C > 1) tpre[1][e] = a.coarse[(size_t)(t * C + 1) * nvox_c + ctab_src[e]];
+      tpre[0][e] = a.coarse[(size_t)(t * C + (MASK ? cm0 : 0)) * nvox_c + ctab_src[e]];
+      if (Cn > 1) tpre[1][e] = a.coarse[(size_t)(t * C + (MASK ? cm1 : 1)) * nvox_c + ctab_src[e]];
     }
   // ---- boxes of ALL cameras, once per cube (prologue; wave w takes cameras w, w + waves, ...): lane
   // n & 7 interpolates the cube's n-th corner VOXEL from the coarse field in global memory (the field is
@@ -493,7 +549,7 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
   auto tap_wait = [&](TapRaw& r) __attribute__((always_inline)) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r.t0), "+v"(r.t1), "+v"(r.t2), "+v"(r.t3));
   };
-  auto tap_finish = [&](int c, const Geo& g, int v, const TapRaw& r) __attribute__((always_inline)) -> int {
+  auto tap_finish = [&](int c, int cam, const Geo& g, int v, const TapRaw& r) __attribute__((always_inline)) -> int {
     const rp2 p000 = (rp2){r.t0[0], r.t0[1]}, p001 = (rp2){r.t0[2], r.t0[3]};
     const rp2 p010 = (rp2){r.t1[0], r.t1[1]}, p011 = (rp2){r.t1[2], r.t1[3]};
     const rp2 p100 = (rp2){r.t2[0], r.t2[1]}, p101 = (rp2){r.t2[2], r.t2[3]};
@@ -509,7 +565,7 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
       asm volatile("" : "+v"(ln));
       const int gi = w * VPT + v, il = gi % CI, jl = ((gi / CI) << 2) + (ln >> 4);
       if (J0 + jl < G && K0 + (ln & 15) < G)
-        a.idx_out[((size_t)(t * C + c)) * nvox + ((size_t)(I0 + il) * G + (J0 + jl)) * G + K0 + (ln & 15)] =
+        a.idx_out[((size_t)(t * C + cam)) * nvox + ((size_t)(I0 + il) * G + (J0 + jl)) * G + K0 + (ln & 15)] =
             iv * hs + iu;
     }
     const int hx = iu - 1 + a.heat_pad, hy = iv - 1 + a.heat_pad;
@@ -523,13 +579,13 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
     }
     return o;
   };
-  auto tap_offsets = [&](int c, const Geo& g, int* off) __attribute__((always_inline)) {
+  auto tap_offsets = [&](int c, int cam, const Geo& g, int* off) __attribute__((always_inline)) {
 #pragma unroll
     for (int v = 0; v < VPT; ++v) {
       TapRaw r;
       tap_request(c, v, r);
       tap_wait(r);
-      off[v] = tap_finish(c, g, v, r);
+      off[v] = tap_finish(c, cam, g, v, r);
     }
   };
   // patch of camera c -> LDS buffer c & 1.  LDS slot s (16 bytes) of a patch row = quad s % SPX of staged pixel
@@ -575,17 +631,21 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
   for (int e = 0; e < TPT; ++e)
     if (e * NT + tid < NTAB) {
       ctab[e * NT + tid] = tpre[0][e];
-      if (C > 1) ctab[NTAB + e * NT + tid] = tpre[1][e];
+      if (Cn > 1) ctab[NTAB + e * NT + tid] = tpre[1][e];
     }
   __syncthreads();
-  Geo gc = geometry(box(0));
+  Geo gc = geometry(box(MASK ? cm0 : 0));
   CamPos cam_c{0, 0};                                  // camera c of the loop below
-  if (!gc.big) load_patch(0, cam_c, gc);
-  int4 box_n = box(1);                                // (a box is fetched one camera ahead of its use)
+  if constexpr (MASK)
+    for (int i = 0; i < cm0; ++i) cam_c = cam_next(cam_c);
+  // (MASK, a frame without cameras: the epilogue parks its results in the patch buffers and no loop iteration would
+  //  have waited for this DMA)
+  if (!gc.big && (!MASK || Cn > 0)) load_patch(0, cam_c, gc);
+  int4 box_n = box(MASK ? cm1 : 1);                   // (a box is fetched one camera ahead of its use)
   int off_c[VPT];
   // (uniform per wave: does any of this wave's j-row groups lie inside the grid?)
   const bool wave_in = J0 + 4 * ((w * VPT) / CI) < G;
-  if (wave_in) tap_offsets(0, gc, off_c);
+  if (wave_in) tap_offsets(0, MASK ? cm0 : 0, gc, off_c);
   __syncthreads();
 
   rp2 acc[VPT][Q][2];                                 // (channel pairs: v_pk_add_f32, half the additions' instructions)
@@ -598,9 +658,9 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
 #pragma unroll
   for (int e = 0; e < TPT; ++e) {
     tnext[e] = make_float2(0.f, 0.f);
-    if (2 < C && e * NT + tid < NTAB) tnext[e] = a.coarse[(size_t)(t * C + 2) * nvox_c + ctab_src[e]];
+    if (2 < Cn && e * NT + tid < NTAB) tnext[e] = a.coarse[(size_t)(t * C + (MASK ? cm2 : 2)) * nvox_c + ctab_src[e]];
   }
-  for (int c = 0; c < ((a.abl & 32) ? 1 : C); ++c) {
+  for (int c = 0; c < ((a.abl & 32) ? (MASK ? min(1, Cn) : 1) : Cn); ++c) {
     // (the table entry requested in the previous iteration is taken over BEFORE this iteration's DMA is issued: vector
     //  memory operations return in order, and the number of DMA instructions is not a compile-time constant -- a wait for
     //  the entry placed after them would be a wait for all of them)
@@ -612,11 +672,13 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
     }
     // camera c+1: box, patch in flight into the other buffer; camera c+2: table entry in flight
     Geo gn = gc;
-    const bool more = c + 1 < C;
-    const CamPos cam_n = cam_next(cam_c);
+    const bool more = c + 1 < Cn;
+    CamPos cam_n = cam_next(cam_c);
+    if constexpr (MASK)
+      for (int i = cm0 + 1; i < cm1; ++i) cam_n = cam_next(cam_n);
     if (more) {
       if (!(a.abl & 64)) gn = geometry(box_n);
-      box_n = box(c + 2);
+      box_n = box(MASK ? cm2 : c + 2);
       if (!gn.big && !(a.abl & 1)) load_patch(c + 1, cam_n, gn);
     }
     // table of camera c+3 requested now, committed at the END OF THE NEXT iteration (as camera (c+1)+2): a table entry
@@ -625,7 +687,7 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
     // without these loads.)
 #pragma unroll
     for (int e = 0; e < TPT; ++e)
-      if (c + 3 < C && e * NT + tid < NTAB && !(a.abl & 16)) tnext[e] = a.coarse[(size_t)(t * C + c + 3) * nvox_c + ctab_src[e]];
+      if (c + 3 < Cn && e * NT + tid < NTAB && !(a.abl & 16)) tnext[e] = a.coarse[(size_t)(t * C + (MASK ? cm3 : c + 3)) * nvox_c + ctab_src[e]];
     // gather camera c: every lane reads the Q quads of its own voxels' pixels
     const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cam_base(cam_c)), 0,
                                                                            plane_bytes, 0x00020000);
@@ -663,11 +725,11 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
     //  copies of this body it takes the kernel from 116 to 128 registers with 50 spills; (2) per voxel, the table reads
     //  of camera c+1 and the pixel reads of camera c under ONE wait: 128 registers with 10 spills at 24 channels, 0.81
     //  against 0.68 ms; without spills, at 32 channels, 1.22 against 1.23 ms)
-    if (more && !(a.abl & 4) && wave_in) tap_offsets(c + 1, gn, off_c);          // (reads table (c+1) & 1; off_c of camera c is spent)
+    if (more && !(a.abl & 4) && wave_in) tap_offsets(c + 1, MASK ? cm1 : c + 1, gn, off_c);          // (reads table (c+1) & 1; off_c of camera c is spent)
     // table of camera c+2 over the table of camera c (read for the last time one iteration ago)
 #pragma unroll
     for (int e = 0; e < TPT; ++e)
-      if (c + 2 < C && e * NT + tid < NTAB) ctab[(c & 1) * NTAB + e * NT + tid] = tv[e];
+      if (c + 2 < Cn && e * NT + tid < NTAB) ctab[(c & 1) * NTAB + e * NT + tid] = tv[e];
     // one barrier per camera: patch c+1 has landed (vmcnt) and is visible, table c+2 is visible, and
     // nobody still reads patch c, whose buffer the next iteration's prefetch overwrites
     // patch c+1 (this wave's rows of it) has landed: the DMA is waited for HERE, after the step's arithmetic
@@ -675,10 +737,12 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
     if (!(a.abl & 128)) __syncthreads();
     gc = gn;
     cam_c = cam_n;
+    if constexpr (MASK) { cm0 = cm1; cm1 = cm2; cm2 = cm3; cm3 = cam_pop(cm3); }
   }
 
   // ---- mean over cameras, / 255 (see repro_gather_kernel); a lane stores its voxels' Jp channels ----
-  const float fc = (float)C;
+  // (MASK: the divisor is any integer in 1 .. 64, so the mean is an IEEE division, see repro_gather_body)
+  const float fc = (float)(MASK ? max(Cn, 1) : C);
   const float rfc = __fdiv_rn(1.f, fc), r255 = __fdiv_rn(1.f, 255.f);
   // (packed: q = x rc, r = fma(-q, c, x), q' = fma(r, rc, q) on channel pairs)
   auto divc2 = [](rp2 x, float cc, float rc) __attribute__((always_inline)) {
@@ -698,7 +762,14 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
   for (int v = 0; v < VPT; ++v) {
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-      rp2 lo = divc2(acc[v][q][0], fc, rfc), hi = divc2(acc[v][q][1], fc, rfc);
+      rp2 lo, hi;
+      if constexpr (MASK) {
+        lo = (rp2){__fdiv_rn(acc[v][q][0][0], fc), __fdiv_rn(acc[v][q][0][1], fc)};
+        hi = (rp2){__fdiv_rn(acc[v][q][1][0], fc), __fdiv_rn(acc[v][q][1][1], fc)};
+      } else {
+        lo = divc2(acc[v][q][0], fc, rfc);
+        hi = divc2(acc[v][q][1], fc, rfc);
+      }
       if (a.div255) {
         lo = divc2(lo, 255.f, r255);
         hi = divc2(hi, 255.f, r255);
@@ -723,7 +794,32 @@ __global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
 }
 
 template <int Q, int CI, int NT>
-static int launch_cube(const CubeArgs& a, int T, hipStream_t s) {
+__global__ __launch_bounds__(NT) void repro_cube_kernel(CubeArgs a) {
+  repro_cube_body<Q, CI, NT, false>(a, nullptr);
+}
+
+template <int Q, int CI, int NT>
+__global__ __launch_bounds__(NT) void repro_cube_masked_kernel(CubeArgs a, const unsigned char* __restrict__ mask) {
+  repro_cube_body<Q, CI, NT, true>(a, mask);
+}
+
+template <int Q, int CI, int NT>
+static int launch_cube(const CubeArgs& a, int T, hipStream_t s, const unsigned char* mask = nullptr) {
+  const int cubes = (a.G / CI) * ((a.G + kCubeJ - 1) / kCubeJ) * ((a.G + kCubeK - 1) / kCubeK);
+  if (mask) {
+    auto mkern = repro_cube_masked_kernel<Q, CI, NT>;
+    static std::atomic<bool> mbig[64];               // (as below: the attribute belongs to the current device)
+    int dv = 0;
+    JH_CHECK_HIP(hipGetDevice(&dv));
+    if (dv < 0 || dv >= 64 || !mbig[dv].load(std::memory_order_acquire)) {
+      JH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mkern),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      if (dv >= 0 && dv < 64) mbig[dv].store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(mkern, dim3(cubes, T), dim3(NT), (size_t)kCubePatchOff(CI) + 2 * a.patch_bytes, s, a, mask);
+    JH_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
   auto kern = repro_cube_kernel<Q, CI, NT>;
   // the attribute belongs to the CURRENT device: one flag per device (a process may drive several GPUs, and
   // two host threads may build predictors at the same time -- setting it twice is harmless)
@@ -735,16 +831,16 @@ static int launch_cube(const CubeArgs& a, int T, hipStream_t s) {
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (devid >= 0 && devid < 64) big[devid].store(true, std::memory_order_release);
   }
-  const int cubes = (a.G / CI) * ((a.G + kCubeJ - 1) / kCubeJ) * ((a.G + kCubeK - 1) / kCubeK);
   hipLaunchKernelGGL(kern, dim3(cubes, T), dim3(NT), (size_t)kCubePatchOff(CI) + 2 * a.patch_bytes, s, a);
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
-int launch_reproject(const float* cam, const float* intr, const float* dist, const int* center3d,
-                     const int* center_hm, const float* heat, float2* coarse, float* vol,
-                     int* idx_out, int T, int C, int G, float spacing, int hs, int Jp,
-                     int heat_pad, int div255, hipStream_t s, const HeatLayout* layout) {
+static int reproject_impl(const float* cam, const float* intr, const float* dist, const int* center3d,
+                          const int* center_hm, const float* heat, float2* coarse, float* vol,
+                          int* idx_out, int T, int C, int G, float spacing, int hs, int Jp,
+                          int heat_pad, int div255, hipStream_t s, const HeatLayout* layout,
+                          const unsigned char* mask) {
   const int Gh = G / 2;
   const int Hst = hs - 2 + 2 * heat_pad;
   HeatLayout lay;                        // default: dense (T, C, Hh, Hh, Jp)
@@ -772,28 +868,28 @@ int launch_reproject(const float* cam, const float* intr, const float* dist, con
     // (test knob: a smaller limit sends boxes to the per-lane global-memory path, which must give the same bits)
     if (getenv("JH_REPRO_PATCH_KB")) ca.patch_limit = std::min(ca.patch_bytes, std::max(1, atoi(getenv("JH_REPRO_PATCH_KB"))) * 1024);
     switch (Q) {
-      case 2: return launch_cube<2, 8, 1024>(ca, T, s);
-      case 4: return launch_cube<4, 8, 512>(ca, T, s);
+      case 2: return launch_cube<2, 8, 1024>(ca, T, s, mask);
+      case 4: return launch_cube<4, 8, 512>(ca, T, s, mask);
       case 6:
         if (JH_ENV_KNOB("JH_REPRO_CI4") > 0) {
           // experiment (round 6): 4-voxel-thick cubes on 512 threads with HALF the patch buffers -- two workgroups per
           // CU that cover each other's per-camera barriers; boxes over the limit take the per-lane global path
           ca.patch_bytes = ((80 * 1024 - kCubePatchOff(4)) / 2) & ~1023;
           ca.patch_limit = std::min(ca.patch_limit, ca.patch_bytes);
-          return launch_cube<6, 4, 512>(ca, T, s);
+          return launch_cube<6, 4, 512>(ca, T, s, mask);
         }
-        return JH_ENV_KNOB("JH_REPRO_NT") == 512 ? launch_cube<6, 8, 512>(ca, T, s)
-                                                 : launch_cube<6, 8, 1024>(ca, T, s);
+        return JH_ENV_KNOB("JH_REPRO_NT") == 512 ? launch_cube<6, 8, 512>(ca, T, s, mask)
+                                                 : launch_cube<6, 8, 1024>(ca, T, s, mask);
       // 32 channels: 4-voxel-thick cubes, one voxel per lane (configs[4]: 1.37 against 1.48 ms per 8 frames
       // for the 8-thick cube on 512 threads, 1.52 for the voxel-row kernel)
       case 8:
         if (JH_ENV_KNOB("JH_REPRO_CI4") > 0) {       // (the same experiment at 32 channels: configs[4])
           ca.patch_bytes = ((80 * 1024 - kCubePatchOff(4)) / 2) & ~1023;
           ca.patch_limit = std::min(ca.patch_limit, ca.patch_bytes);
-          return launch_cube<8, 4, 512>(ca, T, s);
+          return launch_cube<8, 4, 512>(ca, T, s, mask);
         }
-        return JH_ENV_KNOB("JH_REPRO_Q8") == 0 ? launch_cube<8, 8, 512>(ca, T, s)
-                                               : launch_cube<8, 4, 1024>(ca, T, s);
+        return JH_ENV_KNOB("JH_REPRO_Q8") == 0 ? launch_cube<8, 8, 512>(ca, T, s, mask)
+                                               : launch_cube<8, 4, 1024>(ca, T, s, mask);
       default: break;
     }
   }
@@ -807,6 +903,11 @@ int launch_reproject(const float* cam, const float* intr, const float* dist, con
   JH_REQUIRE(lds <= 64 * 1024, "coarse table tile does not fit LDS");
 #define JH_RG(QV)                                                                              \
   case QV:                                                                                     \
+    if (mask)                                                                                  \
+      hipLaunchKernelGGL(repro_gather_masked_kernel<QV>, grid, dim3(256), lds, s, coarse, heat, vol, \
+                         idx_out, C, G, hs, Jp, heat_pad, div255, ci_n, cj_n, make_fastdiv(Gh), \
+                         make_fastdiv(ci_n * cj_n), make_fastdiv(cj_n), make_fastdiv(bpp), lay, mask); \
+    else                                                                                       \
     hipLaunchKernelGGL(repro_gather_kernel<QV>, grid, dim3(256), lds, s, coarse, heat, vol,    \
                        idx_out, C, G, hs, Jp, heat_pad, div255, ci_n, cj_n, make_fastdiv(Gh),   \
                        make_fastdiv(ci_n * cj_n), make_fastdiv(cj_n), make_fastdiv(bpp), lay); \
@@ -818,6 +919,24 @@ int launch_reproject(const float* cam, const float* intr, const float* dist, con
 #undef JH_RG
   JH_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+int launch_reproject(const float* cam, const float* intr, const float* dist, const int* center3d,
+                     const int* center_hm, const float* heat, float2* coarse, float* vol,
+                     int* idx_out, int T, int C, int G, float spacing, int hs, int Jp,
+                     int heat_pad, int div255, hipStream_t s, const HeatLayout* layout) {
+  return reproject_impl(cam, intr, dist, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs, Jp,
+                        heat_pad, div255, s, layout, nullptr);
+}
+
+int launch_reproject_masked(const float* cam, const float* intr, const float* dist, const int* center3d,
+                            const int* center_hm, const float* heat, float2* coarse, float* vol, int* idx_out,
+                            int T, int C, int G, float spacing, int hs, int Jp, int heat_pad, int div255,
+                            const unsigned char* mask, hipStream_t s, const HeatLayout* layout) {
+  JH_REQUIRE(mask, "camera mask");
+  JH_REQUIRE(C <= 64, "at most 64 cameras");
+  return reproject_impl(cam, intr, dist, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs, Jp,
+                        heat_pad, div255, s, layout, mask);
 }
 
 }  // namespace jh

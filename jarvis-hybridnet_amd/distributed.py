@@ -124,9 +124,9 @@ class ShardedPredictor:
             ev.record()
             self.trace.append((label, ev))
 
-    def step(self, frames_local, frame_format=None):
-        """frames_local (T, Cloc, 3, H, W) -> points (T,J,3), conf (T,J), valid (T)."""
-        self.submit(frames_local, frame_format)
+    def step(self, frames_local, frame_format=None, camera_mask=None):
+        """frames_local (T, Cloc, 3, H, W) -> points (T,J,3), conf (T,J), valid (T).  camera_mask: None only."""
+        self.submit(frames_local, frame_format, camera_mask)
         return self.flush()
 
     # ---- pipelined form: the bulk exchange of time batch i runs under the CenterDetect
@@ -134,9 +134,13 @@ class ShardedPredictor:
     # centres the 3D stage of batch i still needs).  Order of one submit():
     #     stage_center(i+1) || exchange(i)  ->  stage_3d(i) [second stream] || stage_keypoints(i+1)
     #     -> exchange(i+1) started asynchronously once stage_3d(i) has let go of the receive buffer
-    def submit(self, frames_local, frame_format=None):
+    def submit(self, frames_local, frame_format=None, camera_mask=None):
         """Start time batch i+1; returns the results of batch i (None on the first call).  frame_format: None or
-        'bgr' only -- the camera-sharded stages take fp32 RGB or uint8 BGR frames, not YUV 4:2:0."""
+        'bgr' only -- the camera-sharded stages take fp32 RGB or uint8 BGR frames, not YUV 4:2:0.  camera_mask: None
+        only -- per-frame camera masks are a single-GPU feature."""
+        if camera_mask is not None:
+            raise ValueError("the camera-sharded path does not take a camera_mask: use "
+                             "JarvisPredictor3D.forward_batch(..., camera_mask=...) on one GPU")
         if frame_format not in (None, "bgr"):
             raise ValueError("the camera-sharded path takes fp32 RGB or uint8 BGR frames only, not frame_format=%r: "
                              "use JarvisPredictor3D.forward_batch(..., frame_format=%r) on one GPU or convert the "

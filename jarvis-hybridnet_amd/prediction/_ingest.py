@@ -55,7 +55,11 @@ class FramePipeline:
     HOST tensors when the event fires (an asynchronous device->host copy into pinned memory enqueued
     behind the forward on ITS stream, see `host_outputs`; `slot` < `slots` names the buffer set to use):
     a synchronous `.cpu()` from the calling thread queues behind the multi-gigabyte upload in flight
-    (measured: 25 ms per batch at configs[2])."""
+    (measured: 25 ms per batch at configs[2]).
+
+    Camera masks: `push(frames, mask)` with a (C,) uint8 mask per frame set.  The masks of a time batch are kept as
+    one small (T, C) host tensor per batch (a short last batch repeats its last row, like its frames) and handed
+    to `submit(x, slot, mask)`; a run that never pushes a mask calls `submit(x, slot)` as before."""
 
     def __init__(self, frame_shape, dtype, time_batch, streams, submit, emit, device, copy_threads=None):
         self.T, self.submit, self.emit = int(time_batch), submit, emit
@@ -86,6 +90,7 @@ class FramePipeline:
         self.quiesce()
         self.submit, self.emit = submit, emit
         self.group, self.fill, self.jobs = 0, 0, []
+        self.masks = []                         # mask rows of the batch being filled (None entries: no mask)
         self.inflight = []                      # (outputs, event, n_real) of submitted batches
         self.frames_in = 0
         # where the calling thread spends its time (seconds): waiting for the pool's copies, enqueueing upload +
@@ -121,11 +126,12 @@ class FramePipeline:
         else:
             self.jobs.append(self.pool.submit(np.copyto, dst, src))
 
-    def push(self, frames):
+    def push(self, frames, mask=None):
         """One decoded frame set: a numpy array / CPU tensor of `frame_shape` (copied into the staging
         buffer by the pool), or a callable `fill(dst)` that decodes straight into the numpy view `dst` of
         the pinned buffer (the reference's `read_images(cap, slice, imgs_orig)` pattern: no copy at all;
-        it runs on a pool thread)."""
+        it runs on a pool thread).  mask: this frame set's (C,) camera mask, or None."""
+        self.masks.append(mask)
         slot = self.group % self.slots
         dst = self.host_np[slot][self.fill]
         if callable(frames):
@@ -161,10 +167,10 @@ class FramePipeline:
                 self.dev[slot].copy_(self.host[slot], non_blocking=True)
                 self.uploaded[slot].record(self.copy_stream)
             cur.wait_event(self.uploaded[slot])
-            outs, ev = self.submit(self.dev[slot], slot)
+            outs, ev = self._submit(self.dev[slot], slot)
             self.consumed[slot] = ev
         else:
-            outs, ev = self.submit(self.host[slot], slot)
+            outs, ev = self._submit(self.host[slot], slot)
         t2 = time.perf_counter()
         self.stats["fill_wait"] += t1 - t0
         self.stats["submit"] += t2 - t1
@@ -176,6 +182,10 @@ class FramePipeline:
         # drain above ran before this batch was appended), so that batch's forward (and with it the upload before
         # it) has completed before a pool thread overwrites the host buffer
         assert len(self.inflight) <= self.slots - 1
+
+    def _submit(self, x, slot):
+        mask, self.masks = batch_mask(self.masks, self.T), []
+        return self.submit(x, slot) if mask is None else self.submit(x, slot, mask)
 
     # ---- rows ----------------------------------------------------------------------------------------
     def drain(self, keep=0):
@@ -206,13 +216,14 @@ class DevicePipeline:
 
     def __init__(self, time_batch, submit, emit, streams=1):
         self.T, self.submit, self.emit = int(time_batch), submit, emit
-        self.group, self.frames_in = [], 0
+        self.group, self.frames_in, self.masks = [], 0, []
         self.keep = max(0, int(streams) - 1)    # batches left in flight behind the one just submitted
         self.slots = self.keep + 1              # output-ring slots: one per batch that can be in flight
         self.n, self.inflight = 0, []
 
-    def push(self, frames):
+    def push(self, frames, mask=None):
         self.group.append(frames)
+        self.masks.append(mask)
         self.frames_in += 1
         if len(self.group) == self.T:
             self._launch()
@@ -223,7 +234,8 @@ class DevicePipeline:
         self.group = []
         # the slot's previous batch has been emitted: at most `keep` batches are in flight at this point
         self.drain(self.keep)
-        outs, ev = self.submit(x, self.n % self.slots)
+        mask, self.masks = batch_mask(self.masks, self.T), []
+        outs, ev = self.submit(x, self.n % self.slots) if mask is None else self.submit(x, self.n % self.slots, mask)
         self.n += 1
         self.inflight.append((outs, ev, real))
 
@@ -239,6 +251,16 @@ class DevicePipeline:
             self._launch()
         self.drain(0)
         return self.frames_in
+
+
+def batch_mask(rows, time_batch):
+    """The (time_batch, C) uint8 camera mask of one time batch from its frame sets' rows ((C,) tensors, or None =
+    all cameras), a short batch padded with its last row like its frames; None when no frame set carried a mask."""
+    if all(r is None for r in rows):
+        return None
+    width = next(r for r in rows if r is not None).numel()
+    rows = [torch.ones(width, dtype=torch.uint8) if r is None else r.cpu() for r in rows]
+    return torch.stack(rows + [rows[-1]] * (time_batch - len(rows)))
 
 
 def host_outputs(ring, slot, outs):

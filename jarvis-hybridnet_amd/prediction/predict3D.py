@@ -67,7 +67,7 @@ def frame_row(points3D, confidences, num_joints):
 
 def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                      distortionCoefficients, cfg, output_dir, params=None, time_batch=1, streams=1,
-                     frame_spec=None, frame_format="bgr"):
+                     frame_spec=None, frame_format="bgr", camera_mask=None):
     """Run `predictor` over an iterable of multi-view frame sets -- (C,H,W,3) uint8 BGR
     arrays / tensors exactly as cv2 delivers them, or (C,3,H,W) fp32 RGB -- and write
     data3D.csv (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -99,9 +99,24 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     frame_format 'i420' / 'nv12': the frame sets are (C,3H/2,W) uint8 YUV 4:2:0 as video decoders produce them
     (FFmpeg yuv420p / hardware NV12; H and W even; fill callables with `frame_spec=((C,3H/2,W), torch.uint8)`): half
     the bytes of BGR to stage and upload, converted inside the resize / crop kernels (JarvisPredictor3D.forward_yuv).
-    The default 'bgr' is the behaviour described above.  Anything else raises ValueError."""
+    The default 'bgr' is the behaviour described above.  Anything else raises ValueError.
+
+    camera_mask: a (C,) bool / integer mask for the whole run (the reference's `cameras_to_use` subset: the rows
+    are those of a predictor built for the unmasked cameras alone, fed their frames and calibration), or an iterable
+    that yields one (C,) mask -- or None for all cameras -- per frame set, consumed in step with `frame_sets` (a
+    camera that dropped a frame: mask it for that frame set; whatever its slot holds is ignored).  A frame set with
+    fewer than two cameras left gives a 'NaN' row, like one in which fewer than two cameras detect.  A mask of the
+    wrong shape or of a floating dtype, and a mask iterable that ends before the frame sets do, or after, raise
+    ValueError.  The CSV and info.yaml formats do not change."""
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
     yuv = driver_format(frame_format, frame_spec, 3)
+    run_mask, mask_iter = None, None
+    if camera_mask is not None:
+        C = cfg.HYBRIDNET.NUM_CAMERAS
+        if _is_single_mask(camera_mask):
+            run_mask = N.camera_mask(camera_mask, (C,)).cpu()
+        else:
+            mask_iter = iter(camera_mask)
     os.makedirs(output_dir, exist_ok=True)
     if params is not None:
         params.output_dir = output_dir
@@ -124,7 +139,8 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
 
         ring = {}                                               # pinned host copies of the outputs, per slot
 
-        def submit(x, slot):
+        def submit(x, slot, mask=None):
+            kw = {} if mask is None else {"camera_mask": mask}
             if hasattr(predictor, "native_streams"):
                 if yuv:
                     h, w = N.yuv_frame_hw(x.shape)
@@ -134,11 +150,11 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                 msp.set_calibration(*calib)
                 # results leave for pinned host memory on the forward's own stream (behind it, before its event)
                 res = msp.forward(x, then=lambda outs: host_outputs(ring, slot, outs),
-                                  frame_format=frame_format if yuv else None)
+                                  frame_format=frame_format if yuv else None, **kw)
                 return res, msp.last_event
             # any object with the batch interface
-            res = predictor.forward_batch(x, *calib, frame_format=frame_format) if yuv else \
-                predictor.forward_batch(x, *calib)
+            res = predictor.forward_batch(x, *calib, frame_format=frame_format, **kw) if yuv else \
+                predictor.forward_batch(x, *calib, **kw)
             ev = None
             if x.is_cuda:
                 res = host_outputs(ring, slot, res)
@@ -147,8 +163,15 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             return res, ev
 
         pipe, key = None, None
+        _end = object()
         try:
             for frames in frame_sets:
+                mask = run_mask
+                if mask_iter is not None:
+                    mask = next(mask_iter, _end)
+                    if mask is _end:
+                        raise ValueError("camera_mask yielded fewer masks than there are frame sets")
+                    mask = None if mask is None else N.camera_mask(mask, (C,)).cpu()
                 if not callable(frames):
                     frames = frames if torch.is_tensor(frames) and frames.is_cuda else _as_host(frames)
                     if yuv:
@@ -160,7 +183,9 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                     if pipe is not None:
                         n += pipe.finish()
                     pipe, key = pipeline_for(predictor, frames, time_batch, streams, submit, emit, frame_spec), k
-                pipe.push(frames)
+                pipe.push(frames) if mask is None else pipe.push(frames, mask)
+            if mask_iter is not None and next(mask_iter, _end) is not _end:
+                raise ValueError("camera_mask yielded more masks than there are frame sets")
             if pipe is not None:
                 n += pipe.finish()
         except BaseException:
@@ -170,6 +195,19 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             release_ingest_buffers(predictor)
             raise
     return n
+
+
+def _is_single_mask(camera_mask):
+    """The drivers' camera_mask argument: ONE mask for the whole run when it is a 1-d tensor, a 1-d numpy array, or a
+    list / tuple whose elements are all plain scalars (bool, int, float, numpy scalars; an empty one too: it then
+    fails the shape check); anything else -- a list of masks / Nones, a 2-d tensor, a generator -- is an iterable of
+    one mask per frame set."""
+    import numpy as np
+    if torch.is_tensor(camera_mask) or isinstance(camera_mask, np.ndarray):
+        return camera_mask.ndim == 1
+    if isinstance(camera_mask, (list, tuple)):
+        return all(isinstance(v, (bool, int, float, np.generic)) for v in camera_mask)
+    return False
 
 
 def _as_host(frames):
