@@ -16,13 +16,12 @@ struct NodeArgs {
   const float* bias;       // [cout_p16]
   float* y;                // raw output [N][H][W][cout_p]
   double* stats;           // [N][cout_p][2]
-  int N, H, W, Cp, cout_p, cout_p16, cf;
+  int N, H, W, Cp, cout_p, cout_p16, cf;   // cf = channels per halo chunk (multiple of 4)
   int blds = 0;            // pointwise weights staged in LDS behind the operand tile
   int alias = 0;           // operand tile written over the halo tile (single channel chunk)
   float* y_pool = nullptr; // row-streaming form, two inputs: also the 2x2-max-pooled raw output [N][H/2][W/2][cout_p]
   int rows = -1;           // row-streaming form (bifpn_rows.hip): 1 wherever the shape allows, 0 never, -1 by launch size,
                            // 2 = the workgroup form with 8-row segments (wide pyramids, time batches below 8)
-  int abl = 0;             // ablation bits for timing experiments (0 in production)   // cf = channels per halo chunk (multiple of 4)
 };
 
 

@@ -88,13 +88,6 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
 
   const int nk8 = Cp >> 3, nb = CP ? kNodeNRG : (a.cout_p16 >> 4);      // (CP: the launcher checks cout_p16)
   const float2* wl = reinterpret_cast<const float2*>(a.pw) + lane;
-  if (a.abl & 16) {             // experiment: de-phase the first generation of workgroups
-    const unsigned L = blockIdx.x + gridDim.x * blockIdx.y;
-    if (L < 768u) {
-      const int k = (L >> 3) % 3;
-      for (int i = 0; i < k * (a.abl >> 8); ++i) __builtin_amdgcn_s_sleep(127);
-    }
-  }
 
   // 1 + 2. statistics -> mean / rstd, fused halo tile -> depthwise -> operand tile
   if constexpr (ONE) {
@@ -216,11 +209,11 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
             lo = __builtin_elementwise_fma((nf2){v[u][k][0], v[u][k][1]}, ak[k][0], lo);
             hi = __builtin_elementwise_fma((nf2){v[u][k][2], v[u][k][3]}, ak[k][1], hi);
           }
-          if (!(a.abl & 1) && a.act == ACT_SILU) {
+          if (a.act == ACT_SILU) {
             // x * sigmoid(x) with the hardware exp2 / reciprocal (about 1e-7 relative error)
             lo = (nf2){silu_fast(lo.x), silu_fast(lo.y)};
             hi = (nf2){silu_fast(hi.x), silu_fast(hi.y)};
-          } else if (!(a.abl & 1) && a.act == ACT_RELU) {
+          } else if (a.act == ACT_RELU) {
             lo = __builtin_elementwise_max(lo, (nf2){0.f, 0.f});
             hi = __builtin_elementwise_max(hi, (nf2){0.f, 0.f});
           }
@@ -245,7 +238,7 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
     // one round) and walks it tap row by tap row: 3 weight + 6 data quads per row feed 12
     // FMAs x 4 channels, i.e. 6.75 instead of 18 LDS quads per output quad.  All reads of the
     // halo tile precede the barrier, all writes of the aliased operand tile follow it.
-    const bool dact = cact && !(a.abl & 2);
+    constexpr bool dact = cact;
     const bool bact = a.blds && tid * 8 < nk8 * nb * 128;
     const int sty = slot >> 2, stx = (slot & 3) * 4;
     nf2 dlo[4], dhi[4];                          // packed fp32 FMAs: two channels per instruction
@@ -351,10 +344,8 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
                 r.z = __fadd_rn(r.z, __fmul_rn(wk, x.z)); r.w = __fadd_rn(r.w, __fmul_rn(wk, x.w));
               }
             }
-            if (!(a.abl & 1)) {
-              r.x = node_act(r.x, a.act); r.y = node_act(r.y, a.act);
-              r.z = node_act(r.z, a.act); r.w = node_act(r.w, a.act);
-            }
+            r.x = node_act(r.x, a.act); r.y = node_act(r.y, a.act);
+            r.z = node_act(r.z, a.act); r.w = node_act(r.w, a.act);
           }
           *reinterpret_cast<float4*>(Ft + pix * SF + c4 * 4) = r;
         }
@@ -365,7 +356,7 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
       // operand rows <= 2r+1 (stride SA <= 18 * SF / 16 floats) only overwrite halo rows
       // <= 2r+1, which no later round reads; the barrier orders this round's reads
       // before its writes.
-      const int ditems = (a.abl & 2) ? 0 : 32 * q;
+      const int ditems = 32 * q;
       const bool bact = a.blds && tid * 8 < nk8 * nb * 128;
 #pragma unroll 1
       for (int r = 0; r < kNodeTY / 2; ++r) {
@@ -397,7 +388,6 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
   }
 
   // 3. pointwise convolution on the matrix cores: wave w owns pixels 16w .. 16w+15
-  if (a.abl & 4) return;
   const float2* A2 = reinterpret_cast<const float2*>(At);
   const int SA2 = SA >> 1;
   const int abase = (wave * 16 + mrow) * SA2 + kq;
@@ -445,8 +435,7 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
         for (int nr = 0; nr < kNodeNRG; ++nr)
           acc[0][nr] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac.y, bc[nr].y, acc[0][nr], 0, 0, 0);
       }
-    } else if (!a.alias && kNodePY * kNodePX * SF >= nk8 * kNodeNRG * 128 && nk8 * kNodeNRG * 32 <= 6 * NT &&
-               !(a.abl & 32)) {
+    } else if (!a.alias && kNodePY * kNodePX * SF >= nk8 * kNodeNRG * 128 && nk8 * kNodeNRG * 32 <= 6 * NT) {
       // Wide pyramids (88 / 160 channels; round 4): the weights of this group of column blocks go through the dead
       // halo tile in ONE cooperative copy (all its loads in flight at once) instead of one L2 round trip per
       // channel step -- with 8 MFMAs per step and two waves per SIMD the two-deep register prefetch below covers
@@ -512,10 +501,8 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
       }
     }
     __syncthreads();          // the scratch may be the (dead) halo tile
-    if (!(a.abl & 8)) {
-      if (full_tile) conv_epilogue<1, kNodeNRG, kNodeTY, kNodeTX, 8, true>(acc, e, red, nb0, 0, oy0, ox0, tid);
-      else conv_epilogue<1, kNodeNRG, kNodeTY, kNodeTX, 8>(acc, e, red, nb0, 0, oy0, ox0, tid);
-    }
+    if (full_tile) conv_epilogue<1, kNodeNRG, kNodeTY, kNodeTX, 8, true>(acc, e, red, nb0, 0, oy0, ox0, tid);
+    else conv_epilogue<1, kNodeNRG, kNodeTY, kNodeTX, 8>(acc, e, red, nb0, 0, oy0, ox0, tid);
     __syncthreads();
   }
 }
@@ -538,7 +525,7 @@ static int launch_node_one(const NodeArgs& a, size_t lds, hipStream_t s) {
 template <int NIN, int M0, int M1, int M2>
 static int launch_node_variant(const NodeArgs& a, size_t lds, hipStream_t s) {
   // the small model's pyramid (56 channels, one MFMA group of 4 column blocks, weights in LDS)
-  if (a.alias && a.blds && a.Cp == 56 && a.cf == 56 && a.cout_p16 == 16 * kNodeNRG && JH_ENV_KNOB("JH_NODE_CP") != 0)
+  if (a.alias && a.blds && a.Cp == 56 && a.cf == 56 && a.cout_p16 == 16 * kNodeNRG)
     return launch_node_one<NIN, M0, M1, M2, true, 56>(a, lds, s);
   if (a.alias) return launch_node_one<NIN, M0, M1, M2, true>(a, lds, s);
   return launch_node_one<NIN, M0, M1, M2, false>(a, lds, s);
@@ -550,7 +537,6 @@ int launch_bifpn_rows(const NodeArgs& a, hipStream_t s);
 int launch_bifpn_node(const NodeArgs& args, hipStream_t s) {
   if (bifpn_rows_eligible(args)) return launch_bifpn_rows(args, s);      // csrc/bifpn_rows.hip
   NodeArgs a = args;
-  if (JH_ENV_KNOB("JH_NODE_ABL") >= 0) a.abl = JH_ENV_KNOB("JH_NODE_ABL");   // timing experiments only
   const size_t head = ((size_t)3 * a.Cp * 2 + (size_t)9 * a.Cp) * sizeof(float);
   const size_t at_bytes = (size_t)128 * (a.Cp + 4) * sizeof(float);
   const size_t red = (size_t)8 * kNodeNRG * 16 * 2 * sizeof(double);   // conv_epilogue: fp64 partials
@@ -559,17 +545,14 @@ int launch_bifpn_node(const NodeArgs& args, hipStream_t s) {
   // (3 workgroups per CU for the 56-channel pyramid of the small model)
   const size_t b_bytes = (size_t)(a.Cp / 8) * (a.cout_p16 / 16) * 128 * sizeof(float);
   a.blds = (b_bytes <= 16 * 1024) ? 1 : 0;        // 512 threads x 32 bytes
-  if (JH_ENV_KNOB("JH_NODE_NOBLDS") > 0) a.blds = 0;
   size_t lds = head + std::max(halo_px * a.Cp, at_bytes + (a.blds ? b_bytes : red));
   a.cf = a.Cp;
   a.alias = 1;
-  const bool na = JH_ENV_KNOB("JH_NODE_NOALIAS") > 0;
-  if (a.Cp > 64 || a.Cp < 32 || lds > 54 * 1024 || na) {
+  if (a.Cp > 64 || a.Cp < 32 || lds > 54 * 1024) {
     // fallback: separate operand tile, halo chunked to the LDS budget
     a.alias = 0;
     a.blds = 0;
     size_t budget = 78 * 1024;
-    if (JH_ENV_KNOB("JH_NODE_LDS_KB") > 0) budget = (size_t)JH_ENV_KNOB("JH_NODE_LDS_KB") * 1024;
     const size_t fixed = head + at_bytes;
     if (fixed + halo_px * 12 > budget) budget = 156 * 1024;
     int cf = std::min(a.Cp, 64);          // the depthwise rounds handle <= 16 channel quads

@@ -357,7 +357,7 @@ void bifpn_rows_kernel(const NodeArgs a, int seg_rows, int strips) {
 
 // Which nodes take the row-streaming form: the 56-channel (small model) or 88-channel (medium) pyramid with as many
 // output column blocks as the input has, no max-pooled input, level at least 32 pixels wide and a multiple of 16
-// (JH_NODE_ROWS=0: never; JH_NODE_ROWS88=0: not at 88 channels).
+// (JH_NODE_ROWS=0: never).
 bool bifpn_rows_wg_shape_ok(const NodeArgs& a);                 // csrc/bifpn_rows_wg.hip
 int launch_bifpn_rows_wg(const NodeArgs& a, hipStream_t s);
 bool bifpn_rows_ps_ok(const NodeArgs& a, int seg_rows, int strips, int segs);      // csrc/bifpn_rows_ps.hip
@@ -366,21 +366,19 @@ int launch_bifpn_rows_ps(const NodeArgs& a, int seg_rows, int strips, int segs, 
 // 88 channels, time-batch class >= 8, a level whose width is no multiple of 16 (or below 16): the one-wave / pair forms
 // need whole 16-pixel strips, the tile kernel's path for more than 64 channels is slow whatever the level -- the
 // workgroup form masks the last strip's pixels past the row end.  The reference's DEFAULT geometry (320-pixel images:
-// levels 80 / 40 / 20 / 10 / 5) has four of its five levels here.  A function of the node only.  JH_NODE_ROWS88_RAGGED=0: off.
+// levels 80 / 40 / 20 / 10 / 5) has four of its five levels here.  A function of the node only.
 bool bifpn_rows_ragged88(const NodeArgs& a) {
-  return a.Cp == 88 && a.rows == 1 && (a.W % 16 != 0 || a.W < 16) && JH_ENV_KNOB("JH_NODE_ROWS88_RAGGED") != 0;
+  return a.Cp == 88 && a.rows == 1 && (a.W % 16 != 0 || a.W < 16);
 }
 
 bool bifpn_rows_eligible(const NodeArgs& a) {
   if (JH_ENV_KNOB("JH_NODE_ROWS") == 0 || a.rows == 0) return false;
-  // (160 channels, the large model: the workgroup form, csrc/bifpn_rows_wg.hip; JH_NODE_ROWS160=0: tile form.
+  // (160 channels, the large model: the workgroup form, csrc/bifpn_rows_wg.hip.
   //  a.rows == 2 -- the wide pyramids at time batches below 8 -- is the same form with 8-row segments, also at 88
   //  channels, where one wave per strip is the faster form at bench scale but far too slow per row for a few images)
-  if (a.rows == 2 && JH_ENV_KNOB("JH_NODE_ROWS_LAT") == 0) return false;
-  const bool wg = (a.Cp == 160 || (a.Cp == 88 && (a.rows == 2 || bifpn_rows_ragged88(a)))) &&
-                  JH_ENV_KNOB("JH_NODE_ROWS160") != 0 && bifpn_rows_wg_shape_ok(a);
+  const bool wg = (a.Cp == 160 || (a.Cp == 88 && (a.rows == 2 || bifpn_rows_ragged88(a)))) && bifpn_rows_wg_shape_ok(a);
   if (a.rows == 2 && !wg) return false;
-  if (a.Cp != 56 && !(a.Cp == 88 && JH_ENV_KNOB("JH_NODE_ROWS88") != 0) && !wg) return false;
+  if (a.Cp != 56 && a.Cp != 88 && !wg) return false;
   // (88 / 160 channels: also the 16-pixel-wide level -- one strip per image -- because the tile kernel's path for more
   //  than 64 channels is slow there, 0.10 ms per launch against 0.05; at 56 channels the tile kernel wins below 32 pixels)
   if (a.cout_p16 != (a.Cp + 15) / 16 * 16 || a.mode[0] != FUSE_SAME) return false;
@@ -393,8 +391,7 @@ bool bifpn_rows_eligible(const NodeArgs& a) {
   }
   if (a.rows < 0) {
     // (one wave per workgroup walking >= 10 rows: below ~2048 strips the chip is not filled and the tile form wins)
-    const int min_wg = JH_ENV_KNOB("JH_NODE_ROWS_MINWG") > 0 ? JH_ENV_KNOB("JH_NODE_ROWS_MINWG") : 2048;
-    if (((a.W + 15) / 16) * ((a.H + 7) / 8) * a.N < min_wg) return false;
+    if (((a.W + 15) / 16) * ((a.H + 7) / 8) * a.N < 2048) return false;
   }
   const bool up2_ok = a.W % 2 == 0 && a.H % 2 == 0, up4_ok = a.W % 4 == 0 && a.H % 4 == 0;
   if (a.n_in == 2) return (a.mode[1] == FUSE_UP2 && up2_ok) || (wg && a.mode[1] == FUSE_SAME);
@@ -410,13 +407,12 @@ static int launch_rows_rc(const NodeArgs& a, hipStream_t s) {
   // carries (bit-equal results for any number of cameras per rank).  Measured at 384 images (P3 two-input node:
   // 8 rows 240 us, 16: 205, 32: 191; P4: 8: 74, 16: 66, 32: 71; three-input head: 16: 221, 32: 223; three
   // same-level inputs at P4: 8: 116, 16: 99): half the image height, 16 / 8 rows for the head.
-  int seg_rows = JH_ENV_KNOB("JH_NODE_SEG") > 0 ? JH_ENV_KNOB("JH_NODE_SEG")
-                 : (a.n_in == 2 || a.mode[1] == FUSE_SAME ? std::max(8, a.H / 2) : (a.H >= 64 ? 16 : 8));
+  int seg_rows = a.n_in == 2 || a.mode[1] == FUSE_SAME ? std::max(8, a.H / 2) : (a.H >= 64 ? 16 : 8);
   // (88 channels, producer / consumer pairs: four items per 512-thread workgroup, so fewer and longer segments fill the
   //  chip better -- measured at 384 images: 32-row segments at the 32-pixel levels 0.155 -> 0.140 / 0.188 -> 0.167 ms,
   //  the three-input head at 64 pixels 0.445 -> 0.397 with 32 rows instead of 16; the 16-pixel levels keep 8 rows: 0.051
   //  against 0.078 with one segment per image)
-  if (RC == 88 && JH_ENV_KNOB("JH_NODE_SEG") <= 0 && a.H >= 32) {
+  if (RC == 88 && a.H >= 32) {
     seg_rows = 32;
     // (the pairs of a workgroup must walk the same number of rows: a level that is no multiple of 32 -- 80 x 80 in the
     //  reference's DEFAULT 320-pixel geometry -- takes its largest even divisor up to 40 that leaves two segments; with

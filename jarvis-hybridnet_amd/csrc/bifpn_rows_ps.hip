@@ -236,17 +236,15 @@ __global__ __launch_bounds__(kPsPairs * 128) void bifpn_rows_ps_kernel(const Nod
         }
       }
     };
-    // REPACK 1: both phases in two passes; 2: the fusion in two passes, the depthwise in one (three inputs: the second
-    // pass's depthwise weights do not fit the registers next to 21 loads in flight)
+    // REPACK: both phases in two passes (two inputs; with three, the second pass's depthwise weights do not fit the
+    // registers next to 21 loads in flight)
     constexpr int QA = REPACK ? 16 : kRQ;          // quads of the first pass; the second takes the rest
     constexpr int QT = REPACK ? kRQ - 16 : kRQ;    // (not used without REPACK)
-    constexpr int kDSL1 = 64 / kRQ >= 8 ? 8 : (64 / kRQ >= 4 ? 4 : (64 / kRQ >= 2 ? 2 : 1));
     constexpr int NSLA = 64 / QA, NSLB = 64 / QT;
     constexpr int DSLA = NSLA >= 8 ? 8 : (NSLA >= 4 ? 4 : (NSLA >= 2 ? 2 : 1));
     constexpr int DSLB = NSLB >= 8 ? 8 : (NSLB >= 4 ? 4 : (NSLB >= 2 ? 2 : 1));
     auto pa = pass(std::integral_constant<int, 0>{}, std::integral_constant<int, QA>{});
     auto pb = pass(std::integral_constant<int, REPACK ? 16 : 0>{}, std::integral_constant<int, QT>{});
-    auto pd = pass(std::integral_constant<int, 0>{}, std::integral_constant<int, kRQ>{});   // (REPACK 2: its depthwise)
     __builtin_amdgcn_s_waitcnt(0);                 // (the preamble's loads: see bifpn_rows.hip)
     int slot = (y_begin + 3) % 3;                  // slot of row yf = y_begin - 1: (yf + 1) % 3
     auto row = [&](int yf, auto next_all_c, auto out_c) __attribute__((always_inline)) {
@@ -262,12 +260,8 @@ __global__ __launch_bounds__(kPsPairs * 128) void bifpn_rows_ps_kernel(const Nod
       // operand block of this output row: by row parity (next_all_c is true in the half of the unrolled loop that
       // produces the EVEN output rows)
       constexpr int kBuf = decltype(next_all_c)::value ? 0 : kOpB;
-      if (REPACK == 2) {
-        depthwise(pd, std::integral_constant<int, 16 / kDSL1>{}, s_top, kBuf);
-      } else {
-        depthwise(pa, std::integral_constant<int, 16 / DSLA>{}, s_top, kBuf);
-        if (REPACK) depthwise(pb, std::integral_constant<int, 16 / DSLB>{}, s_top, kBuf);
-      }
+      depthwise(pa, std::integral_constant<int, 16 / DSLA>{}, s_top, kBuf);
+      if (REPACK) depthwise(pb, std::integral_constant<int, 16 / DSLB>{}, s_top, kBuf);
       ps_barrier();                                  // this row's operand block is complete; the consumer has left
     };                                               // the other block (it read it before arriving here)
     if (y_begin - 1 >= 0) {
@@ -392,7 +386,6 @@ __global__ __launch_bounds__(kPsPairs * 128) void bifpn_rows_ps_kernel(const Nod
 // Is this launch one for the producer / consumer form?  (Decided by the caller's segmentation: every pair of a
 // workgroup must walk the same number of rows, and the items must fill whole workgroups.)
 bool bifpn_rows_ps_ok(const NodeArgs& a, int seg_rows, int strips, int segs) {
-  if (JH_ENV_KNOB("JH_NODE_PS") == 0) return false;
   if (a.Cp != 88 || a.cout_p != 88) return false;
   if (a.H % seg_rows != 0 || seg_rows % 2 != 0) return false;
   return ((long)strips * segs * a.N) % kPsPairs == 0;
@@ -402,20 +395,13 @@ int launch_bifpn_rows_ps(const NodeArgs& a, int seg_rows, int strips, int segs, 
   constexpr int RC = 88;
   const size_t lds = PsGeo<RC>::lds_bytes();
   const dim3 grid((unsigned)((long)strips * segs * a.N / kPsPairs)), block(kPsPairs * 128);
+  // REPACK for the two-input nodes only (384 images: P3 0.432 -> 0.397 ms, def320's 80-pixel level 0.350 -> 0.322).
+  // Three inputs stay on the one pass: fully repacked the producer holds 21 loads of a row in flight -- 256 registers +
+  // 72..128 B of scratch; with only the fusion repacked the eight P4 nodes of medium took 2.418 against 2.378 ms (both
+  // forms were removed after that measurement).
 #define JH_PS(NIN, M1, M2, ACT, POOL)                                                                            \
   do {                                                                                                           \
-    /* (two-input nodes, 384 images: P3 0.432 -> 0.397 ms, def320's 80-pixel level 0.350 -> 0.322.  Three inputs  \
-       stay on the one pass: fully repacked the producer holds 21 loads of a row in flight -- 256 registers +   \
-       72..128 B of scratch; with only the fusion repacked (2) the eight P4 nodes of medium take 2.418 against   \
-       2.378 ms.  JH_NODE_PS_REPACK=0: off, 2 / 3: those two forms for three inputs) */                          \
-    if (JH_ENV_KNOB("JH_NODE_PS_REPACK") == 0 || (NIN == 3 && JH_ENV_KNOB("JH_NODE_PS_REPACK") < 2))             \
-      JH_PS_(NIN, M1, M2, ACT, POOL, 0);                                                                         \
-    else if (NIN == 3 && JH_ENV_KNOB("JH_NODE_PS_REPACK") == 2) JH_PS_(NIN, M1, M2, ACT, POOL, 2);               \
-    else JH_PS_(NIN, M1, M2, ACT, POOL, 1);                                                                      \
-  } while (0)
-#define JH_PS_(NIN, M1, M2, ACT, POOL, REPACK)                                                                   \
-  do {                                                                                                           \
-    auto kern = bifpn_rows_ps_kernel<RC, NIN, M1, M2, ACT, POOL, REPACK>;                                        \
+    auto kern = bifpn_rows_ps_kernel<RC, NIN, M1, M2, ACT, POOL, (NIN == 2 ? 1 : 0)>;                            \
     static bool big = false;                                                                                     \
     if (!big) {                                                                                                  \
       JH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                      \
@@ -440,7 +426,6 @@ int launch_bifpn_rows_ps(const NodeArgs& a, int seg_rows, int strips, int segs, 
     else JH_REQUIRE(false, "producer / consumer node: activation");
   }
 #undef JH_PS
-#undef JH_PS_
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -434,7 +434,7 @@ bool bifpn_rows_wg_shape_ok(const NodeArgs& a) {
   return (a.Cp == 160 || a.Cp == 88) && a.cout_p == a.Cp && a.cout_p16 == (a.Cp + 15) / 16 * 16;
 }
 
-template <int RC, bool KSPLIT>
+template <int RC>
 static int launch_rows_wg_rc(const NodeArgs& a, hipStream_t s) {
   const int strips = (a.W + 15) / 16;
   // Rows per workgroup: a function of the node and of the predictor's time-batch CLASS only (the float partial sums
@@ -443,8 +443,7 @@ static int launch_rows_wg_rc(const NodeArgs& a, hipStream_t s) {
   // latency chain of its rows): short segments -- measured per node with one 12-camera frame set, 88 / 160 channels,
   // us: 64-row levels 16 rows 33 / 62 (8: 41 / 72, 4: 50 / 79, 32: 53 / 103); 32-row levels 4 rows 18 / 29 (8: 22 / 38,
   // 2: 26 / 42); 16 rows and below 2 rows 13 / 21 (4: 15 / 26, 8: 21 / 37).
-  int seg_rows = JH_ENV_KNOB("JH_NODE_SEG") > 0 ? JH_ENV_KNOB("JH_NODE_SEG")
-                 : a.rows == 2 ? (a.H >= 64 ? 16 : (a.H >= 32 ? 4 : 2))
+  int seg_rows = a.rows == 2 ? (a.H >= 64 ? 16 : (a.H >= 32 ? 4 : 2))
                  : (a.n_in == 2 || a.mode[1] == FUSE_SAME ? std::max(8, a.H / 2) : (a.H >= 64 ? 16 : 8));
   // (time-batch class >= 8, levels of 32 pixels and more: ONE segment per strip -- the workgroup's prologue (its waves'
   //  weight slices, the statistics' fp64 arithmetic, two warm-up rows) is paid once per 64 rows instead of per 16 or 32:
@@ -452,7 +451,7 @@ static int launch_rows_wg_rc(const NodeArgs& a, hipStream_t s) {
   //  0.389; the 16-pixel levels keep 8 rows, 0.106 against 0.112 with 16)
   //  (88 channels on a ragged level -- bifpn_rows_ragged88 -- keep half-image segments: 192 images x 3 strips of a 40-pixel
   //  level are 576 workgroups on 512 slots with one segment per strip)
-  if (a.rows != 2 && JH_ENV_KNOB("JH_NODE_SEG") <= 0 && a.H >= 32 && !bifpn_rows_ragged88(a)) seg_rows = a.H;
+  if (a.rows != 2 && a.H >= 32 && !bifpn_rows_ragged88(a)) seg_rows = a.H;
   seg_rows = (seg_rows + 1) & ~1;
   if (seg_rows > a.H) seg_rows = a.H;
   const int segs = (a.H + seg_rows - 1) / seg_rows;
@@ -460,7 +459,7 @@ static int launch_rows_wg_rc(const NodeArgs& a, hipStream_t s) {
   const dim3 grid(strips * segs, a.N), block((RowWgGeo<RC>::NW + RowWgGeo<RC>::NH) * 64);
 #define JH_ROWS(NIN, M1, M2, ACT, POOL)                                                                            \
   do {                                                                                                             \
-    auto kern = bifpn_rows_wg_kernel<RC, NIN, M1, M2, ACT, POOL, KSPLIT>;                                          \
+    auto kern = bifpn_rows_wg_kernel<RC, NIN, M1, M2, ACT, POOL, true>;                                            \
     static bool big = false;                                                                                       \
     if (!big && lds > 64 * 1024) {                                                                                 \
       JH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                        \
@@ -494,10 +493,8 @@ static int launch_rows_wg_rc(const NodeArgs& a, hipStream_t s) {
 }
 
 int launch_bifpn_rows_wg(const NodeArgs& a, hipStream_t s) {
-  // (JH_NODE_WG_KSPLIT=0: the helper waves only fuse pixels 16, 17 -- the form whose bits equal the helper-less kernel's)
-  const bool ks = JH_ENV_KNOB("JH_NODE_WG_KSPLIT") != 0;
-  if (a.Cp == 88) return ks ? launch_rows_wg_rc<88, true>(a, s) : launch_rows_wg_rc<88, false>(a, s);
-  return ks ? launch_rows_wg_rc<160, true>(a, s) : launch_rows_wg_rc<160, false>(a, s);
+  if (a.Cp == 88) return launch_rows_wg_rc<88>(a, s);
+  return launch_rows_wg_rc<160>(a, s);
 }
 
 }  // namespace jh

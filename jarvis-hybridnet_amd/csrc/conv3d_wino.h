@@ -39,11 +39,6 @@ inline WinoTiling wino_tiling(int D, int H, int W, int tz) {
   g.nB = sy ? (W + 15) / 16 : 0;
   g.slabs = (D + tz - 1) / tz;
   g.shaped = sx || sy;
-  // JH_WINO_SHAPES: 0 = never (the plain grid of 4 x 4 blocks), 2 = always (measurement: the shaped kernels on a volume
-  // that has no strips)
-  const int knob = JH_ENV_KNOB("JH_WINO_SHAPES");
-  if (knob == 0) g.shaped = 0;
-  if (knob == 2) g.shaped = 1;
   return g;
 }
 inline int wino_blocks_per_slab(const WinoTiling& g) { return g.n44x * g.n44y + g.nR + g.nB; }
@@ -58,7 +53,6 @@ struct WinoArgs {
   int in_act;
   double* stats;           // [N][cout_p][2] or nullptr
   int N, D, H, W, cin_p, cout_p, cout_p16;
-  int abl;                 // experiment knob (JH_WS_ABL), 0 in production
   long long* dbg;          // per-phase cycle sums of workgroup 0 (JH_WINO_DBG), nullptr in production
   WinoTiling tiling;       // block shapes of a z-slice (filled by launch_conv3d_wino)
   const int* shape_tab;    // tiling.shaped: the loader's per-shape patch tables, [3][kWinoShapeWords] (device)

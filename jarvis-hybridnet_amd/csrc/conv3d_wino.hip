@@ -31,13 +31,12 @@ namespace jh {
 constexpr int kWSV = 12;                                    // V row stride (floats): b64 reads of
                                                             // 16 tiles hit 64 distinct banks
 
-// kWTZ = z-slices per workgroup: 4 (48 accumulator tiles per wave, one workgroup per CU) or
-// 2 (24 tiles, <= 256 registers and 62 KB of LDS: two workgroups per CU, so one's patch
-// staging, input transform and epilogue run under the other's MFMAs).
+// kWTZ = z-slices per workgroup (48 accumulator tiles per wave, one workgroup per CU).
+constexpr int kWTZ = 4;
 // SH: the launch tiles its z-slices with the block shapes of conv3d_wino.h (an extent with a remainder of 1..4 voxels);
 // !SH is the plain grid of 8 x 8-voxel blocks, and every shape expression below folds to that constant.
-template <int NR, int kWTZ, bool SH = false>
-__global__ __launch_bounds__(256, (kWTZ == 2 ? 2 : 1)) void conv3d_wino_kernel(const WinoArgs a) {
+template <int NR, bool SH = false>
+__global__ __launch_bounds__(256, 1) void conv3d_wino_kernel(const WinoArgs a) {
   constexpr int kWPZ = kWTZ + 2;
   constexpr int kWNP = kWPZ * (SH ? 108 : kWPY * kWPX);     // 600 / 400 patch pixels (648 / 432 with 18 x 6 patches)
   extern __shared__ __attribute__((aligned(16))) float lds_all[];
@@ -243,11 +242,8 @@ __global__ __launch_bounds__(256, (kWTZ == 2 ? 2 : 1)) void conv3d_wino_kernel(c
   // channels (mrow & ~3) .. + 3.
   float* yb = a.y + (size_t)n * a.D * a.H * a.W * a.cout_p;
   const int jq = lane & 3;
-  // kWTZ = 4: wave w finishes z-slice w (both x phases); kWTZ = 2: z-slice w & 1, x phase w >> 1
-  constexpr int OXN = (kWTZ == 4) ? 2 : 1;
-  const int mr_own = (kWTZ == 4) ? wave : (wave & 1);
-  const int ox_first = (kWTZ == 4) ? 0 : (wave >> 1);
-  const int oz = z0 + mr_own;
+  static_assert(kWTZ == 4, "wave w finishes z-slice w (both x phases)");
+  const int oz = z0 + wave;
   float s1[NR], s2[NR];
 #pragma unroll
   for (int nr = 0; nr < NR; ++nr) {
@@ -256,11 +252,10 @@ __global__ __launch_bounds__(256, (kWTZ == 2 ? 2 : 1)) void conv3d_wino_kernel(c
     const float bvl = (a.bias && ch < a.cout_p16) ? a.bias[ch] : 0.f;
     s1[nr] = 0.f; s2[nr] = 0.f;
 #pragma unroll
-    for (int oxi = 0; oxi < OXN; ++oxi) {
-      const int ox = ox_first + oxi;
+    for (int ox = 0; ox < 2; ++ox) {
       float4 p[4];
 #pragma unroll
-      for (int w = 0; w < 4; ++w) p[w] = X4[(((w * 2 + ox) * kWTZ + mr_own) * NR + nr) * 64 + lane];
+      for (int w = 0; w < 4; ++w) p[w] = X4[(((w * 2 + ox) * kWTZ + wave) * NR + nr) * 64 + lane];
 #pragma unroll
       for (int oy = 0; oy < 2; ++oy) {
         float v[4];
@@ -325,9 +320,9 @@ __global__ __launch_bounds__(256, (kWTZ == 2 ? 2 : 1)) void conv3d_wino_kernel(c
   }
 }
 
-template <int NR, int TZ, bool SH = false>
+template <int NR, bool SH = false>
 static int launch_wino_nr(const WinoArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  auto kern = conv3d_wino_kernel<NR, TZ, SH>;
+  auto kern = conv3d_wino_kernel<NR, SH>;
   static bool big = false;
   if (!big) {
     JH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -383,10 +378,8 @@ int pack_wino_weights(int cin, int cout, const float* w, const float* b, ConvWei
 
 // variant: 4 = persistent wave-specialised form (conv3d_wino_pw.hip; the default -- it falls
 // back to variant 0 for launches with fewer than two tiles per CU or fewer than three channel
-// passes), 0 = one role per workgroup, 4 z-slices (JH_WINO_PW=0), 1 = the same with 2 z-slices
-// (JH_WINO_TZ=2)
+// passes), 0 = one role per workgroup (JH_WINO_PW=0)
 int wino_variant_from_env() {
-  if (const char* e = getenv("JH_WINO_TZ")) { if (atoi(e) == 2) return 1; }
   if (const char* e = getenv("JH_WINO_PW")) { if (atoi(e) == 0) return 0; }
   return 4;
 }
@@ -431,9 +424,9 @@ int launch_conv3d_wino(const ConvWeights& w, const Act& x, const Act& y, double*
   a.N = x.N; a.D = x.D; a.H = x.H; a.W = x.W; a.cin_p = x.Cp; a.cout_p = y.Cp; a.cout_p16 = w.cout_p16;
   const int nb = w.cout_p16 / 16;
   const int nr_full = (nb % 3 == 0) ? 3 : ((nb % 2 == 0) ? 2 : (nb == 1 ? 1 : 3));
-  // (2 z-slices per workgroup measure the same as 4: the second resident workgroup only pays for
-  // the doubled per-workgroup prologue / epilogue; kept as an experiment knob)
-  const int tz = variant == 1 ? 2 : 4;
+  // (2 z-slices per workgroup, two workgroups per CU, measured the same as 4: the second resident workgroup
+  // only pays for the doubled per-workgroup prologue / epilogue; that variant was removed)
+  constexpr int tz = kWTZ;
   // block shapes of a z-slice (conv3d_wino.h): a function of the volume only -- the persistent and the one-role kernel
   // tile a launch the same way, so their per-block fp32 partial sums of the statistics agree bit for bit
   a.tiling = wino_tiling(x.D, x.H, x.W, tz);
@@ -466,8 +459,7 @@ int launch_conv3d_wino(const ConvWeights& w, const Act& x, const Act& y, double*
   // third of the MFMAs.  (nr only partitions the output channels: the fp32 partial sums of the statistics --
   // per channel over a tile's voxels -- and every output value are the same bits for any nr.)
   int nr_l = nr_full;
-  if (JH_ENV_KNOB("JH_WINO_NR_SPLIT") != 0)
-    while (nr_l > 1 && (long)blocks * ((nb + nr_l - 1) / nr_l) * x.N <= 128) --nr_l;
+  while (nr_l > 1 && (long)blocks * ((nb + nr_l - 1) / nr_l) * x.N <= 128) --nr_l;
   const int nr = nr_l;
   dim3 grid(blocks, (nb + nr - 1) / nr, x.N);
   const size_t xbytes = (size_t)4 * 2 * tz * nr * 4 * 64 * sizeof(float);
@@ -475,9 +467,8 @@ int launch_conv3d_wino(const ConvWeights& w, const Act& x, const Act& y, double*
   if (lds < xbytes) lds = xbytes;
   lds += (a.in_stats ? (size_t)2 * a.cin_p : 0) * sizeof(float);
   JH_REQUIRE(lds <= 160 * 1024, "wino LDS");
-#define JH_WINO_CASE(NRV)                                                                               \
-  if (nr == NRV && sh) return tz == 4 ? launch_wino_nr<NRV, 4, true>(a, grid, lds, s) : launch_wino_nr<NRV, 2, true>(a, grid, lds, s); \
-  if (nr == NRV) return tz == 4 ? launch_wino_nr<NRV, 4>(a, grid, lds, s) : launch_wino_nr<NRV, 2>(a, grid, lds, s);
+#define JH_WINO_CASE(NRV) \
+  if (nr == NRV) return sh ? launch_wino_nr<NRV, true>(a, grid, lds, s) : launch_wino_nr<NRV>(a, grid, lds, s);
   JH_WINO_CASE(3) JH_WINO_CASE(2) JH_WINO_CASE(1)
 #undef JH_WINO_CASE
   JH_REQUIRE(false, "wino NR");

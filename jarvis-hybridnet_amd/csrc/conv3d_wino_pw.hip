@@ -65,7 +65,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define JH_T(slot) do { if (DBG && dbg_on) { const long long _t = __builtin_readcyclecounter(); dbg_acc[slot] += _t - dbg_t; dbg_t = _t; } } while (0)
 }  // namespace
 
-template <int NR, int ABL, bool DBG, bool SH = false>
+template <int NR, bool DBG, bool SH = false>
 __global__ __launch_bounds__(512) void conv3d_wino_pw_kernel(const WinoArgs a, int tiles_sp,
                                                              int total_tiles) {
   constexpr int kPNP = pw_pnp(SH), kPRS = pw_prs(SH);
@@ -448,7 +448,7 @@ __global__ __launch_bounds__(512) void conv3d_wino_pw_kernel(const WinoArgs a, i
         if (has_next) nxt = decode(k + 1);
         for (int p = 0; p < P; ++p) {
           JH_T(7);
-          if (p == 0 && k > 0 && ABL != 1) finish_half(prev, 1);
+          if (p == 0 && k > 0) finish_half(prev, 1);
           JH_T(0);
           if constexpr (LOADER) {
             // pf holds pass g+2 (requested one pass ago)
@@ -456,14 +456,14 @@ __global__ __launch_bounds__(512) void conv3d_wino_pw_kernel(const WinoArgs a, i
               pm = pinv;
               if (nxt.n != cur.n) norm_table(nxt.n);        // all commits of this tile are done
             }
-            if ((p + 2 < P || has_next) && ABL != 2)
+            if (p + 2 < P || has_next)
               commit(pm, (p + 2 < P ? p + 2 : p + 2 - P) * 8, (g + p) & 1 ? R1 : R0);
             JH_T(1);
             if (p == P - 3 && has_next) set_patch(nxt);
-            if ((p + 3 < P || has_next) && ABL != 2) issue((p + 3 < P ? p + 3 : p + 3 - P) * 8);
+            if (p + 3 < P || has_next) issue((p + 3 < P ? p + 3 : p + 3 - P) * 8);
             JH_T(2);
           } else {
-            if ((p + 1 < P || has_next) && ABL != 2)
+            if (p + 1 < P || has_next)
               transform((g + p + 1) & 1 ? R1 : R0, V + ((g + p + 1) & 1) * kPVSZ, p + 1 < P ? cur.lc : nxt.lc);
             JH_T(4);
           }
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(512) void conv3d_wino_pw_kernel(const WinoArgs a, i
         wg_barrier();                                       // Bd1: dump(ox 0) complete
         read_dump(D);
         wg_barrier();                                       // Bd2: ... and read
-        if (ABL != 1) finish_half(cur, 0);
+        finish_half(cur, 0);
         wg_barrier();                                       // Bd3: dump(ox 1) complete
         read_dump(D);
         wg_barrier();                                       // Bd4: every staging wave has read it (the
@@ -548,7 +548,6 @@ __global__ __launch_bounds__(512) void conv3d_wino_pw_kernel(const WinoArgs a, i
         const int nf = fi < 3 ? f + 1 : wave * 4, nk = fi < 3 ? p : pnx;
 #pragma unroll
         for (int dz = 0; dz < 3; ++dz) {
-          if (ABL != 3) {
 #pragma unroll
           for (int mr = 0; mr < kPTZ; ++mr)
 #pragma unroll
@@ -559,10 +558,6 @@ __global__ __launch_bounds__(512) void conv3d_wino_pw_kernel(const WinoArgs a, i
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr)
               acc[fi][mr][nr] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mr + dz].y, b[dz][nr].y, acc[fi][mr][nr], 0, 0, 0);
-          } else {
-#pragma unroll
-            for (int nr = 0; nr < NR; ++nr) acc[fi][dz][nr][0] += av[dz].x * b[dz][nr].x + av[dz + 3].y * b[dz][nr].y;
-          }
           __builtin_amdgcn_sched_barrier(0);
           load_b(b[dz], nf, dz, nk);
           if (fi < 3) {
@@ -630,9 +625,9 @@ __global__ __launch_bounds__(512) void conv3d_wino_pw_kernel(const WinoArgs a, i
   __syncthreads();                                          // Bf
 }
 
-template <int NR, int ABL = 0, bool DBG = false, bool SH = false>
+template <int NR, bool DBG = false, bool SH = false>
 static int launch_pw_nr(const WinoArgs& a, int grid, size_t lds, int tiles_sp, int total, hipStream_t s) {
-  auto kern = conv3d_wino_pw_kernel<NR, ABL, DBG, SH>;
+  auto kern = conv3d_wino_pw_kernel<NR, DBG, SH>;
   static bool big = false;
   if (!big) {
     JH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -682,17 +677,13 @@ int launch_conv3d_wino_pw(const WinoArgs& a, int nr, hipStream_t s) {
   JH_REQUIRE((size_t)4 * kPTZ * nr * 64 * 4 <= (size_t)kPVSZ, "wino (persistent) dump buffer");
   const size_t lds = (size_t)(2 * pw_prs(sh) + 2 * kPVSZ + 4 * nr * 16 * 2 + 2 * a.cin_p) * sizeof(float);
   JH_REQUIRE(lds <= 160 * 1024, "wino (persistent) LDS");
-  if (sh) {       // (the volumes with remainder strips: no experiment variants)
+  if (sh) {       // (the volumes with remainder strips)
     JH_REQUIRE(a.shape_tab != nullptr, "wino (persistent) shape tables");
-    if (nr == 3) return launch_pw_nr<3, 0, false, true>(a, cus, lds, tiles_sp, (int)total, s);
-    if (nr == 2) return launch_pw_nr<2, 0, false, true>(a, cus, lds, tiles_sp, (int)total, s);
-    return launch_pw_nr<1, 0, false, true>(a, cus, lds, tiles_sp, (int)total, s);
+    if (nr == 3) return launch_pw_nr<3, false, true>(a, cus, lds, tiles_sp, (int)total, s);
+    if (nr == 2) return launch_pw_nr<2, false, true>(a, cus, lds, tiles_sp, (int)total, s);
+    return launch_pw_nr<1, false, true>(a, cus, lds, tiles_sp, (int)total, s);
   }
-  const int abl = JH_ENV_KNOB("JH_WS_ABL");
-  if (nr == 3 && abl == 1) return launch_pw_nr<3, 1>(a, cus, lds, tiles_sp, (int)total, s);
-  if (nr == 3 && abl == 2) return launch_pw_nr<3, 2>(a, cus, lds, tiles_sp, (int)total, s);
-  if (nr == 3 && abl == 3) return launch_pw_nr<3, 3>(a, cus, lds, tiles_sp, (int)total, s);
-  if (nr == 3 && JH_ENV_KNOB("JH_WINO_DBG") > 0) return launch_pw_nr<3, 0, true>(a, cus, lds, tiles_sp, (int)total, s);
+  if (nr == 3 && JH_ENV_KNOB("JH_WINO_DBG") > 0) return launch_pw_nr<3, true>(a, cus, lds, tiles_sp, (int)total, s);
   if (nr == 3) return launch_pw_nr<3>(a, cus, lds, tiles_sp, (int)total, s);
   if (nr == 2) return launch_pw_nr<2>(a, cus, lds, tiles_sp, (int)total, s);
   return launch_pw_nr<1>(a, cus, lds, tiles_sp, (int)total, s);

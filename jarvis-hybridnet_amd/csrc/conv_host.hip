@@ -71,7 +71,7 @@ int pack_conv_weights(const ConvDesc& d, const float* w, const float* b, bool tr
   // kernels that read both operands 16 bytes at a time want two 8-channel steps per lane word
   const bool paired = d.nd == 2 && d.ostride > 1 && deconv4_eligible(cin_p, cout_p16);
   // stride-2 3D convs: two taps per 16-byte weight word (conv_mfma.h, TAPPAIR)
-  const bool tap_paired = d.nd == 3 && d.k == 3 && d.stride == 2 && d.ostride == 1 && JH_ENV_KNOB("JH_CONV_TAPPAIR") != 0;
+  const bool tap_paired = d.nd == 3 && d.k == 3 && d.stride == 2 && d.ostride == 1;
   if (tap_paired) packed.assign((size_t)((ntap + 1) / 2) * nk8 * nb * 256, 0.f);
   // geometry of the source tensor
   int skd, sk;   // source kernel extents
@@ -138,20 +138,12 @@ void free_conv_weights(ConvWeights* w) {
 // a 480- / 672-channel operand five / seven times: 0.266 -> 0.189 ms for 672 -> 112 at 384 images.)  nr only partitions
 // the output channels: outputs and statistics are the same bits for any nr.
 static int pick_nr(int nb, int taps, bool heavy_staging, long units) {
-  if (JH_ENV_KNOB("JH_CONV_NR_RULE") == 0) {     // the old rule: least padding, larger nr first
-    int best = 1, best_waste = 1 << 30;
-    for (int nr = 4; nr >= 1; --nr) {
-      const int waste = (nb + nr - 1) / nr * nr - nb;
-      if (waste < best_waste) { best_waste = waste; best = nr; }
-    }
-    return best;
-  }
   const double stage = (heavy_staging ? 1.5 : 0.5) / (double)taps;
   // A launch of fewer workgroups than the chip holds (`units` = tiles x images: a single frame set has 24 tiles at the
   // 16-pixel levels) is as slow as ONE workgroup: stage + nr, so the narrow groups win until the chip is full.  One
   // frame set, us per launch: k5 s2 16 -> 96 28.8 -> 21.4, k3 40 -> 240 20.7 -> 15.7; single-frame latency small / small
-  // 2.06 -> 2.00 ms, medium 3.59 -> 3.40, large 6.29 -> 6.17.  JH_CONV_NR_FILL=0: off (the throughput rule alone).
-  const long slots = JH_ENV_KNOB("JH_CONV_NR_FILL") >= 0 ? std::max(1, JH_ENV_KNOB("JH_CONV_NR_FILL")) : 512;
+  // 2.06 -> 2.00 ms, medium 3.59 -> 3.40, large 6.29 -> 6.17.
+  const long slots = 512;
   int best = 1;
   double best_cost = 1e30;
   for (int nr = 4; nr >= 1; --nr) {
@@ -202,23 +194,21 @@ int launch_conv(const ConvDesc& d, const ConvWeights& w, const Act& x, const Act
     const int rc = launch_deconv4_fused(a, s);
     if (rc >= 0) return rc;
   }
-  JH_REQUIRE(!a.paired || (a.paired == 2 && d.nd == 3 && d.k == 3 && d.stride == 2),
+  JH_REQUIRE((a.paired == 2) == (d.nd == 3 && d.k == 3 && d.stride == 2 && d.ostride == 1) && a.paired != 1,
              "paired weight layout without a kernel that reads it");
   if (conv_pw_direct_eligible(d, a)) return launch_conv_pw_direct(a, s);
   if (d.nd == 2) {
     const int small = (a.Wout <= 8) ? 1 : 0;
     // 16 x 16 tiles for high-resolution layers with few input channels
-    int big = (a.Wout >= 64 && a.Hout >= 64 && w.cin_p <= 32 && d.ostride == 1 && d.stride == 1 &&
+    const int big = (a.Wout >= 64 && a.Hout >= 64 && w.cin_p <= 32 && d.ostride == 1 && d.stride == 1 &&
                (d.k == 1 || d.k == 3)) ? 1 : 0;   // (measured: stride-2 layers do not gain)
-    if (JH_ENV_KNOB("JH_CONV2D_BIG") == 0) big = 0;
     if (big) return conv_launch_2d_big(a, d.k, d.stride, nr, budget, s);
     // Pointwise layers on images that do not tile into 8 x 16 (the reference's DEFAULT 320-pixel geometry: 20 x 20 at
     // stride 16 fills 52 % of its 3 x 2 tiles, 10 x 10 39 %): a 1 x 1 convolution has no neighbourhood, so the image
     // is handed over as one row of H * W pixels and cut into 1 x 128 tiles (20 x 20: 78 %, 40 x 40: 96 %).  A function
-    // of the layer's shape only (the tiling is part of the fused statistics' fp32 arithmetic).  JH_CONV_K1_FLAT=0: off.
+    // of the layer's shape only (the tiling is part of the fused statistics' fp32 arithmetic).
     if (d.k == 1 && d.stride == 1 && d.ostride == 1 && d.nphase == 1 && (a.Wout % 16 != 0 || a.Hout % 8 != 0) &&
-        a.Hout * a.Wout >= 96 && a.Hin == a.Hout && a.Win == a.Wout && a.Hy == a.Hout && a.Wy == a.Wout &&
-        JH_ENV_KNOB("JH_CONV_K1_FLAT") != 0) {
+        a.Hout * a.Wout >= 96 && a.Hin == a.Hout && a.Win == a.Wout && a.Hy == a.Hout && a.Wy == a.Wout) {
       ConvArgs f = a;
       f.Win = f.Wout = f.Wy = a.Hout * a.Wout;
       f.Hin = f.Hout = f.Hy = 1;
@@ -226,15 +216,15 @@ int launch_conv(const ConvDesc& d, const ConvWeights& w, const Act& x, const Act
     }
     if (d.k == 1 && d.stride == 1) return conv_launch_2d_k1(a, nr, small, budget, s);
     if (d.k == 2 && d.stride == 1) return conv_launch_2d_k2(a, nr, small, budget, s);
-    // (a function of the layer's shape only, like every tile choice: JH_CONV_W20=0 switches it off)
+    // (a function of the layer's shape only, like every tile choice)
     // (time-batch class >= 8 only: one tile per image leaves a 12-image launch with a sixth of the workgroups -- measured
     //  on one frame set of the default geometry: 80 -> 480 @ 20 94 us against 63)
     if (d.k == 3 && d.stride == 1 && d.ostride == 1 && a.Wout > 16 && a.Wout <= 20 && a.Hout <= 22 &&
-        !d.latency_class && JH_ENV_KNOB("JH_CONV_W20") != 0)
+        !d.latency_class)
       return conv_launch_2d_k3_w20(a, nr, std::max(budget, (size_t)64 * 1024), s);
     // (the same for the other layers of the default geometry that leave the 8 x 16 tiles half empty: 5 x 5 on 40-pixel
-    //  rows, 3 x 3 stride 2 onto 20 x 20; JH_CONV_W40=0 switches both off)
-    if (!d.latency_class && d.ostride == 1 && JH_ENV_KNOB("JH_CONV_W40") != 0) {
+    //  rows, 3 x 3 stride 2 onto 20 x 20)
+    if (!d.latency_class && d.ostride == 1) {
       if (d.k == 5 && d.stride <= 2 && a.Wout > 32 && a.Wout <= 40)
         return conv_launch_2d_k5_w40(a, d.stride, nr, std::max(budget, (size_t)64 * 1024), s);
       if (d.k == 3 && d.stride == 2 && a.Wout > 16 && a.Wout <= 20 && a.Hout <= 22)
@@ -257,7 +247,6 @@ int launch_conv(const ConvDesc& d, const ConvWeights& w, const Act& x, const Act
     // 256-voxel tiles (4 row blocks per wave: half the weight traffic per MFMA, 2.5x
     // instead of 3.4x halo) for volumes of at least 32^3 outputs
     if (!small && d.k == 3 && d.stride == 1 && tiles_big >= 256) small = 2;
-    if (JH_ENV_KNOB("JH_CONV3D_TILE") >= 0) { const int v = JH_ENV_KNOB("JH_CONV3D_TILE"); if (!small || v == 1) small = v; }
     if (d.k == 1 && d.stride == 1) return conv_launch_3d_k1(a, nr, small, budget, s);
     if (d.k == 2 && d.stride == 2) return conv_launch_3d_k2s2(a, nr, small, budget, s);
     if (d.k == 3 && d.stride <= 2) return conv_launch_3d_k3(a, d.stride, nr, small, budget, s);

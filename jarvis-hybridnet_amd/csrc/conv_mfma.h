@@ -397,7 +397,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
   // BREG: kernels whose whole weight set of a channel pass is small (1x1 convs, narrow 3x3
   // layers) fetch it into registers at the top of the pass, so the round trip to L2 runs under
   // the patch commit and the barriers instead of in front of every tap.
-  // (the stride-2 3D family always takes the plain loop: it has a tap-paired weight form there)
+  // (the stride-2 3D family always takes the plain loop: its weights are tap-paired there)
   constexpr bool TAPPAIR = ND == 3 && K == 3 && STRIDE == 2;
   constexpr bool PIPE = (G::NT > 1) && (MR * NR * KC8 >= 12) && !TAPPAIR;
   constexpr bool BREG = !PIPE && (G::NT == 1 ? KC8 * NR <= 16 : G::NT * KC8 * NR <= 9);   // (measured)
@@ -597,61 +597,56 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
 #pragma unroll
       for (int k8 = 0; k8 < KC8; ++k8)
         koff[k8] = min((c0 >> 3) + k8, nkc8_total - 1) * nb16_total * 64;
-      bool done = false;
       if constexpr (TAPPAIR) {
-        if (a.paired == 2) {
-          // Tap-paired weights ([tap pair][channel step][column block][lane][4]: x, y = even tap, z, w =
-          // odd tap; the 28th tap is zero): one 16-byte load per (pair, step, column block) instead of
-          // two 8-byte ones.  This layer issues 3 weight loads + 1 LDS read per 6 MFMAs, and a memory
-          // instruction costs about one MFMA whatever its width (tools/mfma_valu_coissue.hip).
-          // Per accumulator the order of the products is the unpaired loop's: bit-identical.
-          done = true;
-          constexpr int NP = (G::NT + 1) / 2;
-          typedef unsigned int wu4 __attribute__((ext_vector_type(4)));
-          auto wload4 = [&](int idx4, int nr) __attribute__((always_inline)) -> float4 {
-            const wu4 v = __builtin_amdgcn_raw_buffer_load_b128(wrs, wvo[nr] * 2, idx4 * 16, 0);
-            return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-          };
-          float4 b4[KC8][NR];
+        // Tap-paired weights, the only layout of this family ([tap pair][channel step][column block][lane][4]:
+        // x, y = even tap, z, w = odd tap; the 28th tap is zero): one 16-byte load per (pair, step, column block) instead of
+        // two 8-byte ones.  This layer issues 3 weight loads + 1 LDS read per 6 MFMAs, and a memory
+        // instruction costs about one MFMA whatever its width (tools/mfma_valu_coissue.hip).
+        // Per accumulator the order of the products is the unpaired loop's: bit-identical.
+        constexpr int NP = (G::NT + 1) / 2;
+        typedef unsigned int wu4 __attribute__((ext_vector_type(4)));
+        auto wload4 = [&](int idx4, int nr) __attribute__((always_inline)) -> float4 {
+          const wu4 v = __builtin_amdgcn_raw_buffer_load_b128(wrs, wvo[nr] * 2, idx4 * 16, 0);
+          return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+        };
+        float4 b4[KC8][NR];
+#pragma unroll
+        for (int k8 = 0; k8 < KC8; ++k8)
+#pragma unroll
+          for (int nr = 0; nr < NR; ++nr) b4[k8][nr] = wload4(koff[k8], nr);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          constexpr int KHW = G::KH * G::KW;
+          const int t0 = 2 * p, t1 = min(2 * p + 1, G::NT - 1);       // (tap 27 re-reads tap 26: weights 0)
+          const int o0 = (((t0 / KHW) * G::PY + (t0 / G::KW) % G::KH) * G::PX + t0 % G::KW) * S2;
+          const int o1 = (((t1 / KHW) * G::PY + (t1 / G::KW) % G::KH) * G::PX + t1 % G::KW) * S2;
+          float2 a0[KC8][MR], a1[KC8][MR];
+          float4 bc[KC8][NR];
 #pragma unroll
           for (int k8 = 0; k8 < KC8; ++k8)
 #pragma unroll
-            for (int nr = 0; nr < NR; ++nr) b4[k8][nr] = wload4(koff[k8], nr);
+            for (int mr = 0; mr < MR; ++mr) {
+              a0[k8][mr] = lds2[abase[mr] + o0 + k8 * 4];
+              a1[k8][mr] = lds2[abase[mr] + o1 + k8 * 4];
+            }
+          const int wn = min(p + 1, NP - 1) * tap_stride;
 #pragma unroll
-          for (int p = 0; p < NP; ++p) {
-            constexpr int KHW = G::KH * G::KW;
-            const int t0 = 2 * p, t1 = min(2 * p + 1, G::NT - 1);       // (tap 27 re-reads tap 26: weights 0)
-            const int o0 = (((t0 / KHW) * G::PY + (t0 / G::KW) % G::KH) * G::PX + t0 % G::KW) * S2;
-            const int o1 = (((t1 / KHW) * G::PY + (t1 / G::KW) % G::KH) * G::PX + t1 % G::KW) * S2;
-            float2 a0[KC8][MR], a1[KC8][MR];
-            float4 bc[KC8][NR];
+          for (int k8 = 0; k8 < KC8; ++k8)
 #pragma unroll
-            for (int k8 = 0; k8 < KC8; ++k8)
-#pragma unroll
-              for (int mr = 0; mr < MR; ++mr) {
-                a0[k8][mr] = lds2[abase[mr] + o0 + k8 * 4];
-                a1[k8][mr] = lds2[abase[mr] + o1 + k8 * 4];
-              }
-            const int wn = min(p + 1, NP - 1) * tap_stride;
-#pragma unroll
-            for (int k8 = 0; k8 < KC8; ++k8)
-#pragma unroll
-              for (int nr = 0; nr < NR; ++nr) {
-                bc[k8][nr] = b4[k8][nr];
-                b4[k8][nr] = wload4(wn + koff[k8], nr);
-              }
+            for (int nr = 0; nr < NR; ++nr) {
+              bc[k8][nr] = b4[k8][nr];
+              b4[k8][nr] = wload4(wn + koff[k8], nr);
+            }
 #define JH_TP_STEP(AV, AC, BC)                                                                              \
   _Pragma("unroll") for (int mr = 0; mr < MR; ++mr) _Pragma("unroll") for (int nr = 0; nr < NR; ++nr)     \
     acc[mr][nr] = __builtin_amdgcn_mfma_f32_16x16x4f32(AV[k8][mr].AC, bc[k8][nr].BC, acc[mr][nr], 0, 0, 0);
 #pragma unroll
-            for (int k8 = 0; k8 < KC8; ++k8) { JH_TP_STEP(a0, x, x) JH_TP_STEP(a0, y, y) }
+          for (int k8 = 0; k8 < KC8; ++k8) { JH_TP_STEP(a0, x, x) JH_TP_STEP(a0, y, y) }
 #pragma unroll
-            for (int k8 = 0; k8 < KC8; ++k8) { JH_TP_STEP(a1, x, z) JH_TP_STEP(a1, y, w) }
+          for (int k8 = 0; k8 < KC8; ++k8) { JH_TP_STEP(a1, x, z) JH_TP_STEP(a1, y, w) }
 #undef JH_TP_STEP
-          }
         }
-      }
-      if (!done) {
+      } else {
       float2 bn[KC8][NR];
 #pragma unroll
       for (int k8 = 0; k8 < KC8; ++k8)
@@ -757,9 +752,7 @@ template <int ND, int K, int STRIDE, int TZ, int TY, int TX>
 int launch_conv_geom(const ConvArgs& a, int nr, size_t lds_budget, hipStream_t s) {
   using G = ConvGeom<ND, K, STRIDE, TZ, TY, TX>;
   ConvArgs b = a;
-  if (JH_ENV_KNOB("JH_CONV_LDS_KB") > 0) lds_budget = (size_t)JH_ENV_KNOB("JH_CONV_LDS_KB") * 1024;
-  int kc8 = pick_kc8(b.cin_p, &G::lds_bytes, lds_budget);
-  if (JH_ENV_KNOB("JH_CONV_KC8") > 0) kc8 = JH_ENV_KNOB("JH_CONV_KC8");
+  const int kc8 = pick_kc8(b.cin_p, &G::lds_bytes, lds_budget);
   b.kc = kc8 * 8;
   const int tiles = ((b.Dout + TZ - 1) / TZ) * ((b.Hout + TY - 1) / TY) * ((b.Wout + TX - 1) / TX);
   const int nb = b.cout_p16 / 16;
@@ -768,8 +761,7 @@ int launch_conv_geom(const ConvArgs& a, int nr, size_t lds_budget, hipStream_t s
   // nr only partitions the output channels, so outputs and the per-channel fp32 partials of the fused statistics
   // are the same bits for any nr (test_time_batch_at_bench_scale_tile_nodes_bit_equal compares a 12-image call,
   // which takes this path, with a 192-image one, which does not).
-  if (JH_ENV_KNOB("JH_CONV_NR_SPLIT") != 0)
-    while (nr > 1 && (long)tiles * ((nb + nr - 1) / nr) * b.N * b.nphase <= 128) --nr;
+  while (nr > 1 && (long)tiles * ((nb + nr - 1) / nr) * b.N * b.nphase <= 128) --nr;
   dim3 grid(tiles, (nb + nr - 1) / nr, b.N * b.nphase);
 #define JH_CONV_CASE(NRV, KV) \
   if (nr == NRV && kc8 == KV) return launch_conv_inst<ND, K, STRIDE, TZ, TY, TX, NRV, KV>(b, grid, s);
@@ -782,7 +774,6 @@ int launch_conv_geom(const ConvArgs& a, int nr, size_t lds_budget, hipStream_t s
 
 // few-channel pointwise layers straight from registers (csrc/conv_pw_direct.hip)
 bool conv_pw_direct_eligible(const ConvDesc& d, const ConvArgs& a);
-bool conv_pw_direct_shape_ok(int cin_p, int cout_p16, int pixels);
 int launch_conv_pw_direct(const ConvArgs& a, hipStream_t s);
 
 // ConvTranspose2d k4 s2 p1 with the four parities in one workgroup (csrc/deconv4.hip); -1: not its layer

@@ -233,19 +233,11 @@ __global__ __launch_bounds__(256) void conv_pw_direct_kernel(const ConvArgs a, i
 }  // namespace
 
 // Layers this kernel takes: plain 1 x 1 convolutions with at most 48 input channels and 1 or 4 column blocks of output
-// channels on images of a multiple of 16 pixels, gate (if any) given as a tensor.  JH_CONV_PW_DIRECT=0: never.
+// channels on images of a multiple of 16 pixels, gate (if any) given as a tensor.
 // The shape part of the decision.  Which kernel runs must not depend on the batch (the two kernels group the statistics'
 // partial sums differently): this kernel therefore takes the squeeze-excite gate in BOTH forms the plan uses -- a tensor,
 // or the recipe the general kernel evaluates in its prologue for small batches.
-bool conv_pw_direct_shape_ok(int cin_p, int cout_p16, int pixels) {
-  if (JH_ENV_KNOB("JH_CONV_PW_DIRECT") == 0) return false;
-  const int nb = cout_p16 / 16;
-  if (cin_p > 48 || (nb != 1 && nb != 4)) return false;
-  return pixels % 16 == 0 && pixels >= (nb == 1 ? 1024 : 4096);
-}
-
 bool conv_pw_direct_eligible(const ConvDesc& d, const ConvArgs& a) {
-  if (JH_ENV_KNOB("JH_CONV_PW_DIRECT") == 0) return false;
   if (d.nd != 2 || d.k != 1 || d.stride != 1 || d.ostride != 1 || d.nphase != 1 || a.paired) return false;
   if (a.se.pool && (a.se.C > 64 || a.se.S > 64)) return false;
   if (a.cin_p > 48 || a.in_px != a.cin_p) return false;

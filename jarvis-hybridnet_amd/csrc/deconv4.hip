@@ -15,7 +15,7 @@
 // i.e. a quarter of the staging work and 9 instead of 16 A-operand reads per channel step for
 // the same 16 (parity, tap) MFMA groups.  Per parity the taps are visited in the order of the
 // general kernel and the per-workgroup statistics cover the same pixels, so outputs and fused
-// statistics are bit-identical to it (JH_DECONV_FUSED=0 selects the general kernel).
+// statistics are bit-identical to it.
 //
 // Operand layout ("paired"): in an fp32 MFMA stream every LDS read costs ~24 cycles and every
 // global load ~36 cycles of issue whatever its width (tools/mfma_valu_coissue.hip), against 32 per
@@ -287,13 +287,13 @@ static int launch_deconv4_tr(const ConvArgs& a, hipStream_t s) {
 
 template <int NRP, int KC8>
 static int launch_deconv4_inst(const ConvArgs& a, hipStream_t s) {
-  if (!a.stats && JH_ENV_KNOB("JH_CONV_TR") != 0) return launch_deconv4_tr<NRP, KC8, true>(a, s);
+  if (!a.stats) return launch_deconv4_tr<NRP, KC8, true>(a, s);
   return launch_deconv4_tr<NRP, KC8, false>(a, s);
 }
 
 // Layers this kernel takes (their weights are then packed in the paired layout)
 bool deconv4_eligible(int cin_p, int cout_p16) {
-  return cout_p16 <= 32 && cin_p % 16 == 0 && JH_ENV_KNOB("JH_DECONV_FUSED") != 0;
+  return cout_p16 <= 32 && cin_p % 16 == 0;
 }
 
 // Returns -1 when the layer is not this kernel's (the caller then takes the general path).

@@ -172,12 +172,11 @@ int launch_norm_apply(const Act& x, const double* stats, double eps, int act, co
   int iters = 8;
   while ((P + rows * iters - 1) / (rows * iters) > 64 && iters < 64) iters *= 2;
   // ... and at least `min_block_kb` of the tensor per block (the caller's choice -- plans of the time-batch class >= 8
-  // ask for 64 KB; JH_NORM_MINKB overrides): a block's prologue turns the statistics of ALL its channels into mean / rstd
+  // ask for 64 KB): a block's prologue turns the statistics of ALL its channels into mean / rstd
   // with fp64 arithmetic; with 480 channels and 16 pixels per block that was most of its life (small/small kernel time
   // 16.46 -> 16.31 ms per batch, medium 38.69 -> 38.19).  Single frame sets keep the small blocks: 12 images have to
   // spread over 256 CUs (2.059 against 2.090 ms per forward).
-  const int min_kb = JH_ENV_KNOB("JH_NORM_MINKB") >= 0 ? JH_ENV_KNOB("JH_NORM_MINKB") : min_block_kb;
-  while ((long)rows * iters * x.Cp * 4 < (long)min_kb * 1024 && iters < 64 && rows * iters < P) iters *= 2;
+  while ((long)rows * iters * x.Cp * 4 < (long)min_block_kb * 1024 && iters < 64 && rows * iters < P) iters *= 2;
   const int ppb = rows * iters;
   dim3 grid((P + ppb - 1) / ppb, x.N);
   const size_t sm = ((pool ? (size_t)rows * q * 4 : 0) + (stats ? (size_t)2 * x.Cp : 0)) * sizeof(float);
@@ -454,14 +453,14 @@ __global__ __launch_bounds__(256) void depthwise_lds_kernel(
 }
 
 bool depthwise_can_pool(int H, int W) {
-  return (H <= 16 && W <= 16) || (H <= 20 && W <= 20 && JH_ENV_KNOB("JH_DW_T20") != 0);
+  return H <= 20 && W <= 20;
 }
 
 int launch_depthwise(const Act& x, const float* w, int k, float* y, double* stats, hipStream_t s, double* pool) {
   JH_REQUIRE(x.D == 1, "depthwise is 2D only");
   JH_REQUIRE(k == 3 || k == 5, "depthwise kernel size must be 3 or 5");
   // tile side: a function of the image only (16, or 20 for images 17 .. 20 pixels wide / high: one tile instead of four)
-  const int tt = (std::max(x.H, x.W) > 16 && std::max(x.H, x.W) <= 20 && JH_ENV_KNOB("JH_DW_T20") != 0) ? 20 : 16;
+  const int tt = (std::max(x.H, x.W) > 16 && std::max(x.H, x.W) <= 20) ? 20 : 16;
   const int tiles = ((x.H + tt - 1) / tt) * ((x.W + tt - 1) / tt);
   if (pool) {
     // fused squeeze-excite pooled sums: one tile per image, channel chunk 16 (the form does not depend on the batch)
@@ -479,19 +478,19 @@ int launch_depthwise(const Act& x, const float* w, int k, float* y, double* stat
     JH_CHECK_HIP(hipGetLastError());
     return 0;
   }
-  // Channel chunk per workgroup: 16 (33.6 KB of LDS at k = 5: four workgroups per CU) unless JH_DW_CC=32 (60.8 KB,
-  // two per CU: the round-2 form).  The kernel is latency-bound; the chunk is part of no sum (statistics are
-  // per channel), so the choice does not depend on anything but the knob.
-  const int cc = (JH_ENV_KNOB("JH_DW_CC") == 32 && tt == 16) ? 32 : 16;
+  // Channel chunk per workgroup: 16 (33.6 KB of LDS at k = 5: four workgroups per CU; the round-2 form, 32 channels
+  // = 60.8 KB = two per CU, was removed).  The kernel is latency-bound; the chunk is part of no sum (statistics are
+  // per channel).
+  constexpr int cc = 16;
   dim3 grid(tiles, (x.Cp + cc - 1) / cc, x.N);
   const int ht = tt + k - 1;
   size_t lds = (size_t)(ht * ht * (cc + 4) + k * k * cc) * sizeof(float);
   const size_t red = (size_t)((256 / (cc / 4)) * (cc / 4) * 8 + (cc / 4) * 8 * 8) * sizeof(double);
   if (lds < red) lds = red;
-#define JH_DW(K, CC, TTV) hipLaunchKernelGGL((depthwise_lds_kernel<K, CC, false, TTV>), grid, dim3(256), lds, s, x.p, w, y, stats, x.H, x.W, x.Cp)
-  if (tt == 20) { if (k == 3) JH_DW(3, 16, 20); else JH_DW(5, 16, 20); }
-  else if (k == 3) { if (cc == 32) JH_DW(3, 32, 16); else JH_DW(3, 16, 16); }
-  else { if (cc == 32) JH_DW(5, 32, 16); else JH_DW(5, 16, 16); }
+#define JH_DW(K, TTV) hipLaunchKernelGGL((depthwise_lds_kernel<K, cc, false, TTV>), grid, dim3(256), lds, s, x.p, w, y, stats, x.H, x.W, x.Cp)
+  if (tt == 20) { if (k == 3) JH_DW(3, 20); else JH_DW(5, 20); }
+  else if (k == 3) JH_DW(3, 16);
+  else JH_DW(5, 16);
 #undef JH_DW
   JH_CHECK_HIP(hipGetLastError());
   return 0;

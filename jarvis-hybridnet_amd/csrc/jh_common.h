@@ -18,7 +18,7 @@ namespace jh {
 
 constexpr int kWave = 64;
 
-// Experiment knobs (JH_* environment variables) are launch-path constants: each is read ONCE per
+// Knobs (JH_* environment variables) are launch-path constants: each is read ONCE per
 // process (first use), not on every launch.  -1 = unset.
 #define JH_ENV_KNOB(name) ([]() -> int { static const int v = [] { const char* e = getenv(name); return e ? atoi(e) : -1; }(); return v; }())
 
@@ -173,8 +173,6 @@ struct InNorm {
   float inv = 0.f;
   int act = 0;
 };
-// which few-channel 1 x 1 layers the direct register kernel takes, by shape (csrc/conv_pw_direct.hip)
-bool conv_pw_direct_shape_ok(int cin_p, int cout_p16, int pixels);
 int launch_conv(const ConvDesc& d, const ConvWeights& w, const Act& x, const Act& y,
                 const float* gate, double* stats, hipStream_t s, const InNorm* in = nullptr,
                 const SeGate* se = nullptr);

@@ -40,9 +40,6 @@ int Profiler::finish() {
 Plan::~Plan() {
   for (void* p : owned_) (void)hipFree(p);
   for (auto& c : convs_) free_conv_weights(&c);
-  if (ev_fork_) (void)hipEventDestroy(ev_fork_);
-  if (ev_join_) (void)hipEventDestroy(ev_join_);
-  if (side_) (void)hipStreamDestroy(side_);
 }
 
 int Plan::alloc(void** p, size_t bytes) {
@@ -68,13 +65,6 @@ size_t Plan::scratch(size_t doubles) {
 
 int Plan::finish() {
   if (arena_doubles_ == 0) arena_doubles_ = 8;
-  bool branch = false;
-  for (const auto& op : ops_) branch = branch || op.lane != 0;
-  if (branch) {       // (created here, at build time: run() may be inside a stream capture)
-    JH_CHECK_HIP(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
-    JH_CHECK_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-    JH_CHECK_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-  }
   return alloc(reinterpret_cast<void**>(&arena_), arena_doubles_ * sizeof(double));
 }
 
@@ -89,33 +79,11 @@ void set_precision_mode(int m) { g_precision = m; }
 int Plan::run(hipStream_t s) {
   if (launch_zero(arena_, arena_doubles_ * sizeof(double), s)) return 1;
   Profiler& pf = profiler();
-  // (profiled passes time every kernel alone: no side branch then)
-  const bool fork = side_ != nullptr && !pf.on;
-  bool side_busy = false;
-  auto join = [&]() {
-    JH_CHECK_HIP(hipEventRecord(ev_join_, side_));
-    JH_CHECK_HIP(hipStreamWaitEvent(s, ev_join_, 0));
-    side_busy = false;
-    return 0;
-  };
   for (auto& op : ops_) {
-    hipStream_t os = s;
-    if (fork) {
-      if (op.join && side_busy && join()) return 1;
-      if (op.lane != 0) {
-        if (!side_busy) {                    // the branch starts behind everything launched so far
-          JH_CHECK_HIP(hipEventRecord(ev_fork_, s));
-          JH_CHECK_HIP(hipStreamWaitEvent(side_, ev_fork_, 0));
-          side_busy = true;
-        }
-        os = side_;
-      }
-    }
-    if (pf.on) pf.begin(op.name, op.flops, op.bytes, os);
-    if (op.fn(os)) return 1;
-    if (pf.on) pf.end(os);
+    if (pf.on) pf.begin(op.name, op.flops, op.bytes, s);
+    if (op.fn(s)) return 1;
+    if (pf.on) pf.end(s);
   }
-  if (side_busy && join()) return 1;
   return 0;
 }
 
@@ -327,7 +295,7 @@ int EffTrackPlan::mbconv(const ParamMap& pm, const std::string& p, int stage, in
     float* wd = nullptr;
     if (upload(wt, &wd)) return 1;
     st1 = scratch((size_t)raw.N * raw.Cp * kStatW);
-    pooled = depthwise_can_pool(Ho, Wo) && JH_ENV_KNOB("JH_DW_POOL") != 0;
+    pooled = depthwise_can_pool(Ho, Wo);
     push(std::string("depthwise_k") + std::to_string(k) + (pooled ? "pool" : ""), 2.0 * raw.N * raw.pixels() * mid * k * k,
          8.0 * raw.N * raw.pixels() * mid, [this, e, wd, k, raw, st1, pool, pooled](hipStream_t s) {
       return launch_depthwise(e, wd, k, raw.p, sc(st1), s, pooled ? sc(pool) : nullptr);
@@ -353,10 +321,8 @@ int EffTrackPlan::mbconv(const ParamMap& pm, const std::string& p, int stage, in
   // connected layers per image -- is computed by the project convolution's own prologue from the pooled
   // sums, with the arithmetic of se_gate_kernel, bit for bit: 14 launches less per forward.  At bench
   // scale the serial prologue in every project-conv workgroup costs more than the launches (1950-1969
-  // against 1973-1985 frames/s), so large batches keep the stand-alone se_gate launch.  JH_SE_FUSE=0 / 1
-  // forces either form.
-  const int se_knob = JH_ENV_KNOB("JH_SE_FUSE");
-  const bool se_fused = se_knob >= 0 ? se_knob != 0 : raw.N <= 32;
+  // against 1973-1985 frames/s), so large batches keep the stand-alone se_gate launch.
+  const bool se_fused = raw.N <= 32;
   SeGate seg;
   seg.wr = dwr; seg.br = dbr; seg.we = dwe; seg.be = dbe; seg.C = mid; seg.S = squeeze; seg.inv_hw = inv_hw;
   if (!se_fused) {
@@ -501,34 +467,32 @@ int EffTrackPlan::build(const ParamMap& pm, const std::string& pre, int size, in
   if (new_act(N, 1, H / 2, W / 2, stem, &x.a)) return 1;
   size_t st = 0;
   const std::string bb = pre + "backbone_net.model.";
-  if ((stem == 16 || stem == 32) && JH_ENV_KNOB("JH_STEM_MFMA") <= 0) {
-    // the 3 -> 16 (small) / 3 -> 32 (medium, large) stem runs on the vector ALUs (csrc/stem.hip): K = 27 is
-    // too little matrix work per workgroup for the MFMA kernel, and the pre-processing fuses into it
-    const float* wh = nullptr;
-    if (get(pm, bb + "_conv_stem.weight", (size_t)stem * 27, &wh)) return 1;
-    std::vector<float> packed(27 * stem);
-    pack_stem_weights(wh, packed.data(), stem);
-    float* wd = nullptr;
-    if (upload(packed, &wd)) return 1;
-    st = scratch((size_t)N * stem * kStatW);
-    const Act xin = input, xo = x.a;
-    const double opix = (double)N * xo.pixels();
-    // (named by FAMILY: this layer runs on the vector ALUs and is HBM-bound on the frame rows it fetches; its
-    //  algorithmic bytes depend on what feeds it -- set_stem_traffic() -- so bench.py prices it against HBM)
-    stem_op_ = (int)ops_.size();
-    stem_ch_ = stem;
-    push("stem_conv_k3s2_3x" + std::to_string(stem) + "@" + std::to_string(xo.W), 2.0 * opix * 27 * stem,
-         4.0 * ((double)N * xin.pixels() * 3 + opix * stem + 27 * stem),
-         [this, xin, xo, wd, st](hipStream_t s) {
-           if (stem_src.mode) return launch_stem_conv_src(stem_src, xin, wd, xo, sc(st), s);
-           return launch_stem_conv(xin, wd, xo, sc(st), s);
-         });
-    // JH_STEM_FUSE=0: the stand-alone resize / crop kernels feed the stem instead (read at plan build time, so a
-    // process may build plans of both forms)
-    const char* fuse = getenv("JH_STEM_FUSE");
-    stem_fusable = !(fuse && atoi(fuse) == 0);
-  } else if (add_conv(pm, conv_desc(2, 3, 2, 1, 3, stem), bb + "_conv_stem.weight", "", false, input, x.a,
-                      nullptr, true, &st)) return 1;
+  JH_REQUIRE(stem == 16 || stem == 32, "stem channels");
+  // the 3 -> 16 (small) / 3 -> 32 (medium, large) stem runs on the vector ALUs (csrc/stem.hip): K = 27 is
+  // too little matrix work per workgroup for the MFMA kernel, and the pre-processing fuses into it
+  const float* wh = nullptr;
+  if (get(pm, bb + "_conv_stem.weight", (size_t)stem * 27, &wh)) return 1;
+  std::vector<float> packed(27 * stem);
+  pack_stem_weights(wh, packed.data(), stem);
+  float* wd = nullptr;
+  if (upload(packed, &wd)) return 1;
+  st = scratch((size_t)N * stem * kStatW);
+  const Act xin = input, xo = x.a;
+  const double opix = (double)N * xo.pixels();
+  // (named by FAMILY: this layer runs on the vector ALUs and is HBM-bound on the frame rows it fetches; its
+  //  algorithmic bytes depend on what feeds it -- set_stem_traffic() -- so bench.py prices it against HBM)
+  stem_op_ = (int)ops_.size();
+  stem_ch_ = stem;
+  push("stem_conv_k3s2_3x" + std::to_string(stem) + "@" + std::to_string(xo.W), 2.0 * opix * 27 * stem,
+       4.0 * ((double)N * xin.pixels() * 3 + opix * stem + 27 * stem),
+       [this, xin, xo, wd, st](hipStream_t s) {
+         if (stem_src.mode) return launch_stem_conv_src(stem_src, xin, wd, xo, sc(st), s);
+         return launch_stem_conv(xin, wd, xo, sc(st), s);
+       });
+  // JH_STEM_FUSE=0: the stand-alone resize / crop kernels feed the stem instead (read at plan build time, so a
+  // process may build plans of both forms)
+  const char* fuse = getenv("JH_STEM_FUSE");
+  stem_fusable = !(fuse && atoi(fuse) == 0);
   // the stem's InstanceNorm + swish is applied by the first block's conv on load
   x.st = (long)st;
   x.inv = 1.f / (float)((H / 2) * (W / 2));
@@ -695,32 +659,23 @@ int V2VPlan::build(const ParamMap& pm, const std::string& pre, int J, int T, int
                pre + "front_layers.0.block.0.bias", false, input, f0, nullptr, true, &st)) return 1;
   // The stage-entry tensors (f0, e0, u0) stay RAW: their InstanceNorm + ReLU is applied on load by the two
   // readers, the residual block's first convolution and its closing relu(IN(conv2) + x) pass
-  // (JH_V2V_ENTRY_NORM=1: materialise them as rounds 1-2 did).
-  const bool lazy = JH_ENV_KNOB("JH_V2V_ENTRY_NORM") <= 0;
-  if (!lazy) add_norm(f0, st, ACT_RELU, nullptr, nullptr, f0.p, -1);
-  if (res_block(pm, pre + "front_layers.1.", 2 * J, f0, nullptr, &f1, lazy ? (long)st : -1)) return 1;
+  // (rounds 1-2 materialised them with a pass of their own).
+  if (res_block(pm, pre + "front_layers.1.", 2 * J, f0, nullptr, &f1, (long)st)) return 1;
   const std::string e = pre + "encoder_decoder.";
-  // skip_res1 (three launches) depends on f1 only and is read again by decoder_res1's closing pass, so it can run as a
-  // side branch next to encoder_pool1 .. decoder_upsample1 (Plan::run forks a second stream; statistics and activations
-  // of the two chains are disjoint).  Measured on the single-frame forward, where the V2V stage is a chain of 47-us
-  // launches: 2.089 ms with the branch against 2.059 without (medium 3.68 / 3.59) -- each of these kernels already
-  // spreads over the chip, the two chains only take turns.  Opt-in: JH_V2V_FORK=1.
-  const bool fork = T < 8 && JH_ENV_KNOB("JH_V2V_FORK") == 1;
-  if (fork) lane_ = 1;
+  // skip_res1 (three launches) depends on f1 only and is read again by decoder_res1's closing pass.  Running it as a
+  // side branch on a second stream next to encoder_pool1 .. decoder_upsample1 was measured on the single-frame forward,
+  // where the V2V stage is a chain of 47-us launches: 2.089 ms with the branch against 2.059 without (medium 3.68 /
+  // 3.59) -- each of these kernels already spreads over the chip, the two chains only take turns.  The side-stream
+  // machinery was removed after that measurement: a plan is one chain on the caller's stream.
   if (res_block(pm, e + "skip_res1.", 2 * J, f1, nullptr, &skip)) return 1;
-  lane_ = 0;
   if (new_act(T, Gq, Gq, Gq, 4 * J, &e0)) return 1;
   if (add_conv(pm, conv_desc(3, 2, 2, 0, 2 * J, 4 * J), e + "encoder_pool1.block.0.weight",
                e + "encoder_pool1.block.0.bias", false, f1, e0, nullptr, true, &st)) return 1;
-  if (!lazy) add_norm(e0, st, ACT_RELU, nullptr, nullptr, e0.p, -1);
-  if (res_block(pm, e + "mid_res.", 4 * J, e0, nullptr, &e1, lazy ? (long)st : -1)) return 1;
+  if (res_block(pm, e + "mid_res.", 4 * J, e0, nullptr, &e1, (long)st)) return 1;
   if (new_act(T, Gh, Gh, Gh, 2 * J, &u0)) return 1;
   if (add_conv(pm, deconv3d_k2s2_desc(4 * J, 2 * J), e + "decoder_upsample1.block.0.weight",
                e + "decoder_upsample1.block.0.bias", true, e1, u0, nullptr, true, &st)) return 1;
-  if (!lazy) add_norm(u0, st, ACT_RELU, nullptr, nullptr, u0.p, -1);
-  // (decoder_res1's first two launches do not read `skip`, its closing pass does: the join sits in front of the block)
-  if (fork) join_next_ = true;
-  if (res_block(pm, e + "decoder_res1.", 2 * J, u0, skip.p, &d1, lazy ? (long)st : -1)) return 1;   // ... + res1
+  if (res_block(pm, e + "decoder_res1.", 2 * J, u0, skip.p, &d1, (long)st)) return 1;   // ... + res1
   if (new_act(T, Gh, Gh, Gh, J, &output)) return 1;
   if (add_conv(pm, conv_desc(3, 1, 1, 0, 2 * J, J), pre + "output_layer.weight",
                pre + "output_layer.bias", false, d1, output, nullptr, false, nullptr)) return 1;

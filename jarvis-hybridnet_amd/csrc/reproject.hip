@@ -334,8 +334,6 @@ struct CubeArgs {
   int C, G, hs, heat_pad, div255, patch_bytes;   // patch_bytes: size of each of the two LDS patch buffers
   int patch_limit;                               // largest box that is staged (<= patch_bytes; test knob)
   HeatLayout lay;
-  int abl;       // JH_REPRO_ABL bit mask (timing experiments only): 1 no patch loads, 2 no LDS gather,
-                 // 4 no tap interpolation after camera 0, 8 no stores, 16 no table prefetch
 };
 
 // raw LDS reads of Q consecutive 16-byte words (see repro_cube_kernel: invisible to the compiler's wait-count pass)
@@ -660,7 +658,7 @@ __device__ __forceinline__ void repro_cube_body(const CubeArgs a, const unsigned
     tnext[e] = make_float2(0.f, 0.f);
     if (2 < Cn && e * NT + tid < NTAB) tnext[e] = a.coarse[(size_t)(t * C + (MASK ? cm2 : 2)) * nvox_c + ctab_src[e]];
   }
-  for (int c = 0; c < ((a.abl & 32) ? (MASK ? min(1, Cn) : 1) : Cn); ++c) {
+  for (int c = 0; c < Cn; ++c) {
     // (the table entry requested in the previous iteration is taken over BEFORE this iteration's DMA is issued: vector
     //  memory operations return in order, and the number of DMA instructions is not a compile-time constant -- a wait for
     //  the entry placed after them would be a wait for all of them)
@@ -677,9 +675,9 @@ __device__ __forceinline__ void repro_cube_body(const CubeArgs a, const unsigned
     if constexpr (MASK)
       for (int i = cm0 + 1; i < cm1; ++i) cam_n = cam_next(cam_n);
     if (more) {
-      if (!(a.abl & 64)) gn = geometry(box_n);
+      gn = geometry(box_n);
       box_n = box(MASK ? cm2 : c + 2);
-      if (!gn.big && !(a.abl & 1)) load_patch(c + 1, cam_n, gn);
+      if (!gn.big) load_patch(c + 1, cam_n, gn);
     }
     // table of camera c+3 requested now, committed at the END OF THE NEXT iteration (as camera (c+1)+2): a table entry
     // has two iterations to arrive.  (Requested and committed inside one iteration, its round trip was the floor under
@@ -687,11 +685,11 @@ __device__ __forceinline__ void repro_cube_body(const CubeArgs a, const unsigned
     // without these loads.)
 #pragma unroll
     for (int e = 0; e < TPT; ++e)
-      if (c + 3 < Cn && e * NT + tid < NTAB && !(a.abl & 16)) tnext[e] = a.coarse[(size_t)(t * C + (MASK ? cm3 : c + 3)) * nvox_c + ctab_src[e]];
+      if (c + 3 < Cn && e * NT + tid < NTAB) tnext[e] = a.coarse[(size_t)(t * C + (MASK ? cm3 : c + 3)) * nvox_c + ctab_src[e]];
     // gather camera c: every lane reads the Q quads of its own voxels' pixels
     const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cam_base(cam_c)), 0,
                                                                            plane_bytes, 0x00020000);
-    if (!(a.abl & 2) && wave_in)
+    if (wave_in)
 #pragma unroll
     for (int v = 0; v < VPT; ++v) {
       const int o = off_c[v] >= 0 ? off_c[v] : kZeroOff;
@@ -703,6 +701,9 @@ __device__ __forceinline__ void repro_cube_body(const CubeArgs a, const unsigned
         acc[v][q][1] += __builtin_shufflevector(h[q], h[q], 2, 3);
       }
     }
+    // (scheduling fence: the gather above and the fallback below sit under the same `wave_in`; scheduled as ONE region
+    //  the 24-channel kernel goes from 118 registers to 128 with 16 spills)
+    __builtin_amdgcn_sched_barrier(0);
     // taps that are not in LDS (a box over the LDS budget; never seen otherwise): from global memory.
     // Those lanes added the zero pixel above, so the camera order of the sum is unchanged.
     if (wave_in)
@@ -725,7 +726,7 @@ __device__ __forceinline__ void repro_cube_body(const CubeArgs a, const unsigned
     //  copies of this body it takes the kernel from 116 to 128 registers with 50 spills; (2) per voxel, the table reads
     //  of camera c+1 and the pixel reads of camera c under ONE wait: 128 registers with 10 spills at 24 channels, 0.81
     //  against 0.68 ms; without spills, at 32 channels, 1.22 against 1.23 ms)
-    if (more && !(a.abl & 4) && wave_in) tap_offsets(c + 1, MASK ? cm1 : c + 1, gn, off_c);          // (reads table (c+1) & 1; off_c of camera c is spent)
+    if (more && wave_in) tap_offsets(c + 1, MASK ? cm1 : c + 1, gn, off_c);          // (reads table (c+1) & 1; off_c of camera c is spent)
     // table of camera c+2 over the table of camera c (read for the last time one iteration ago)
 #pragma unroll
     for (int e = 0; e < TPT; ++e)
@@ -734,7 +735,7 @@ __device__ __forceinline__ void repro_cube_body(const CubeArgs a, const unsigned
     // nobody still reads patch c, whose buffer the next iteration's prefetch overwrites
     // patch c+1 (this wave's rows of it) has landed: the DMA is waited for HERE, after the step's arithmetic
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!(a.abl & 128)) __syncthreads();
+    __syncthreads();
     gc = gn;
     cam_c = cam_n;
     if constexpr (MASK) { cm0 = cm1; cm1 = cm2; cm2 = cm3; cm3 = cam_pop(cm3); }
@@ -787,7 +788,7 @@ __device__ __forceinline__ void repro_cube_body(const CubeArgs a, const unsigned
       const size_t vox0 = ((size_t)(I0 + il) * G + (J0 + jl)) * G + K0;
       const float4 r = *reinterpret_cast<const float4*>(park + ch * 16);
       // (ragged last cubes: rows j >= G and, inside a run, voxels k >= G are not part of the grid)
-      if (!(a.abl & 8) && J0 + jl < G && K0 + within / Q < G)
+      if (J0 + jl < G && K0 + within / Q < G)
         *reinterpret_cast<float4*>(a.vol + ((size_t)t * nvox + vox0) * (JPB / 4) + within * 4) = r;
     }
   }
@@ -803,27 +804,12 @@ __global__ __launch_bounds__(NT) void repro_cube_masked_kernel(CubeArgs a, const
   repro_cube_body<Q, CI, NT, true>(a, mask);
 }
 
-template <int Q, int CI, int NT>
-static int launch_cube(const CubeArgs& a, int T, hipStream_t s, const unsigned char* mask = nullptr) {
-  const int cubes = (a.G / CI) * ((a.G + kCubeJ - 1) / kCubeJ) * ((a.G + kCubeK - 1) / kCubeK);
-  if (mask) {
-    auto mkern = repro_cube_masked_kernel<Q, CI, NT>;
-    static std::atomic<bool> mbig[64];               // (as below: the attribute belongs to the current device)
-    int dv = 0;
-    JH_CHECK_HIP(hipGetDevice(&dv));
-    if (dv < 0 || dv >= 64 || !mbig[dv].load(std::memory_order_acquire)) {
-      JH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mkern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      if (dv >= 0 && dv < 64) mbig[dv].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(mkern, dim3(cubes, T), dim3(NT), (size_t)kCubePatchOff(CI) + 2 * a.patch_bytes, s, a, mask);
-    JH_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  auto kern = repro_cube_kernel<Q, CI, NT>;
-  // the attribute belongs to the CURRENT device: one flag per device (a process may drive several GPUs, and
-  // two host threads may build predictors at the same time -- setting it twice is harmless)
-  static std::atomic<bool> big[64];
+// One cube kernel (plain or masked) with its 160 KB of dynamic LDS.  The attribute belongs to the CURRENT device: one
+// flag per kernel and device in `big` (a process may drive several GPUs, and two host threads may build predictors at
+// the same time -- setting it twice is harmless)
+template <typename... KArgs, typename... Args>
+static int launch_cube_kernel(void (*kern)(KArgs...), std::atomic<bool> (&big)[64], dim3 grid, int nt, size_t lds,
+                              hipStream_t s, Args... args) {
   int devid = 0;
   JH_CHECK_HIP(hipGetDevice(&devid));
   if (devid < 0 || devid >= 64 || !big[devid].load(std::memory_order_acquire)) {
@@ -831,9 +817,19 @@ static int launch_cube(const CubeArgs& a, int T, hipStream_t s, const unsigned c
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (devid >= 0 && devid < 64) big[devid].store(true, std::memory_order_release);
   }
-  hipLaunchKernelGGL(kern, dim3(cubes, T), dim3(NT), (size_t)kCubePatchOff(CI) + 2 * a.patch_bytes, s, a);
+  hipLaunchKernelGGL(kern, grid, dim3(nt), lds, s, args...);
   JH_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+template <int Q, int CI, int NT>
+static int launch_cube(const CubeArgs& a, int T, hipStream_t s, const unsigned char* mask = nullptr) {
+  const int cubes = (a.G / CI) * ((a.G + kCubeJ - 1) / kCubeJ) * ((a.G + kCubeK - 1) / kCubeK);
+  const dim3 grid(cubes, T);
+  const size_t lds = (size_t)kCubePatchOff(CI) + 2 * a.patch_bytes;
+  static std::atomic<bool> big[64], mbig[64];
+  return mask ? launch_cube_kernel(repro_cube_masked_kernel<Q, CI, NT>, mbig, grid, NT, lds, s, a, mask)
+              : launch_cube_kernel(repro_cube_kernel<Q, CI, NT>, big, grid, NT, lds, s, a);
 }
 
 static int reproject_impl(const float* cam, const float* intr, const float* dist, const int* center3d,
@@ -860,8 +856,7 @@ static int reproject_impl(const float* cam, const float* intr, const float* dist
   // 32 channels (JH_REPRO_CUBE=0: the voxel-row form below; JH_REPRO_CUBE=16: only grids that are multiples of 16)
   if (G % 8 == 0 && G >= 16 && Jp <= 32 && JH_ENV_KNOB("JH_REPRO_CUBE") != 0 &&
       (G % 16 == 0 || JH_ENV_KNOB("JH_REPRO_CUBE") != 16)) {
-    CubeArgs ca{coarse, heat, vol, idx_out, C, G, hs, heat_pad, div255, 0, 0, lay, 0};
-    ca.abl = std::max(0, JH_ENV_KNOB("JH_REPRO_ABL"));
+    CubeArgs ca{coarse, heat, vol, idx_out, C, G, hs, heat_pad, div255, 0, 0, lay};
     const int Q = Jp / 4;
     ca.patch_bytes = ((160 * 1024 - kCubePatchOff(8)) / 2) & ~1023;     // two patch buffers (CI <= 8)
     ca.patch_limit = ca.patch_bytes;
@@ -870,26 +865,10 @@ static int reproject_impl(const float* cam, const float* intr, const float* dist
     switch (Q) {
       case 2: return launch_cube<2, 8, 1024>(ca, T, s, mask);
       case 4: return launch_cube<4, 8, 512>(ca, T, s, mask);
-      case 6:
-        if (JH_ENV_KNOB("JH_REPRO_CI4") > 0) {
-          // experiment (round 6): 4-voxel-thick cubes on 512 threads with HALF the patch buffers -- two workgroups per
-          // CU that cover each other's per-camera barriers; boxes over the limit take the per-lane global path
-          ca.patch_bytes = ((80 * 1024 - kCubePatchOff(4)) / 2) & ~1023;
-          ca.patch_limit = std::min(ca.patch_limit, ca.patch_bytes);
-          return launch_cube<6, 4, 512>(ca, T, s, mask);
-        }
-        return JH_ENV_KNOB("JH_REPRO_NT") == 512 ? launch_cube<6, 8, 512>(ca, T, s, mask)
-                                                 : launch_cube<6, 8, 1024>(ca, T, s, mask);
+      case 6: return launch_cube<6, 8, 1024>(ca, T, s, mask);
       // 32 channels: 4-voxel-thick cubes, one voxel per lane (configs[4]: 1.37 against 1.48 ms per 8 frames
       // for the 8-thick cube on 512 threads, 1.52 for the voxel-row kernel)
-      case 8:
-        if (JH_ENV_KNOB("JH_REPRO_CI4") > 0) {       // (the same experiment at 32 channels: configs[4])
-          ca.patch_bytes = ((80 * 1024 - kCubePatchOff(4)) / 2) & ~1023;
-          ca.patch_limit = std::min(ca.patch_limit, ca.patch_bytes);
-          return launch_cube<8, 4, 512>(ca, T, s, mask);
-        }
-        return JH_ENV_KNOB("JH_REPRO_Q8") == 0 ? launch_cube<8, 8, 512>(ca, T, s, mask)
-                                               : launch_cube<8, 4, 1024>(ca, T, s, mask);
+      case 8: return launch_cube<8, 4, 1024>(ca, T, s, mask);
       default: break;
     }
   }
@@ -901,17 +880,14 @@ static int reproject_impl(const float* cam, const float* intr, const float* dist
   const int cj_n = (256 >= G * G) ? Gh : std::min(Gh, ((256 + G - 1) / G + 1) / 2 + 2);
   const size_t lds = (size_t)C * ci_n * cj_n * Gh * sizeof(float2);
   JH_REQUIRE(lds <= 64 * 1024, "coarse table tile does not fit LDS");
-#define JH_RG(QV)                                                                              \
-  case QV:                                                                                     \
-    if (mask)                                                                                  \
-      hipLaunchKernelGGL(repro_gather_masked_kernel<QV>, grid, dim3(256), lds, s, coarse, heat, vol, \
-                         idx_out, C, G, hs, Jp, heat_pad, div255, ci_n, cj_n, make_fastdiv(Gh), \
-                         make_fastdiv(ci_n * cj_n), make_fastdiv(cj_n), make_fastdiv(bpp), lay, mask); \
-    else                                                                                       \
-    hipLaunchKernelGGL(repro_gather_kernel<QV>, grid, dim3(256), lds, s, coarse, heat, vol,    \
-                       idx_out, C, G, hs, Jp, heat_pad, div255, ci_n, cj_n, make_fastdiv(Gh),   \
-                       make_fastdiv(ci_n * cj_n), make_fastdiv(cj_n), make_fastdiv(bpp), lay); \
-    break;
+  // (the masked kernel takes the mask as one more argument behind the plain kernel's)
+  auto launch_rows = [&](auto kern, auto... mask_arg) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, coarse, heat, vol, idx_out, C, G, hs, Jp, heat_pad, div255, ci_n,
+                       cj_n, make_fastdiv(Gh), make_fastdiv(ci_n * cj_n), make_fastdiv(cj_n), make_fastdiv(bpp), lay,
+                       mask_arg...);
+  };
+#define JH_RG(QV) \
+  case QV: mask ? launch_rows(repro_gather_masked_kernel<QV>, mask) : launch_rows(repro_gather_kernel<QV>); break;
   switch (Jp / 4) {
     JH_RG(2) JH_RG(4) JH_RG(6) JH_RG(8) JH_RG(10) JH_RG(12) JH_RG(14) JH_RG(16)
     default: JH_REQUIRE(false, "unsupported joint count");

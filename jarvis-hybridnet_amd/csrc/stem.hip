@@ -189,7 +189,7 @@ int launch_stem_conv_src(const StemSource& src, const Act& x, const float* w_dev
   // (the fp32 resize form is bound by HBM on the frames it reads -- 2 of every 4 rows of 1280 x 1024 x 3 floats --
   //  and loses locality with more workgroups in flight: 654 -> 711 us at eight per CU; 16 KB of unused dynamic LDS
   //  keep it at four.  The other forms are latency-bound and want the eight.)
-  const size_t pad_f32 = JH_ENV_KNOB("JH_STEM_PAD_KB") >= 0 ? (size_t)JH_ENV_KNOB("JH_STEM_PAD_KB") * 1024 : 16384;
+  const size_t pad_f32 = 16384;
 #define JH_STEM(M, U)                                                                                                   \
   do {                                                                                                                  \
     if (y.Cp == 32)                                                                                                     \
