@@ -279,6 +279,36 @@ int jh_predictor_stage_3d_masked(jh_predictor* pr, const float* heat_all_dev, in
  * be NULL.  Unmasked calls do not update them. */
 int jh_predictor_debug_mask(jh_predictor* pr, int32_t* n_active_dev, int32_t* num_cams_detect_dev, void* stream);
 
+/* Per-camera 2D views of a 3D result (ABI v4, additive; new design: the reference gets 2D keypoints only from a
+ * second pass over every video, JarvisPredictor2D, jarvis/prediction/jarvis2D.py).  For the frames t0 .. t0+T3-1
+ * whose 3D result is points_dev (T3,J,3): call after the forward / stage-3 call that produced it, on the same stream.
+ * heat_all_dev NULL = the heat maps of the last whole-path forward (the predictor's own buffer; all cameras local);
+ * otherwise (T3,C,B/2,B/2,Jp) as for jh_predictor_stage_3d.  mask_dev: the (T,C) mask that forward was given (rows
+ * t0 .. t0+T3-1 are read, in place: keep it alive until the stream has passed the call), or NULL.  Reads the crop
+ * centres / validity set that stage 3 read.  Outputs, with m the flat index y*(B/2) + x of the maximum of joint j's
+ * heat map (the lowest index among equal maxima, as torch.argmax on the CPU):
+ *   used (T3,C) uint8        valid[t] && (mask == NULL || mask[t][c] != 0)
+ *   points2d (T3,C,J,2) int32  (m % (B/2), m / (B/2)) * 2 + centerHM[t][c] - B/2: full-frame pixels (jarvis2D.py:143-149,
+ *                            the expression of jh_predictor2d_forward); -1 for a camera that is not used
+ *   conf2d (T3,C,J)          min(max, 255) / 255 (jarvis2D.py:147-148); 0 for a camera that is not used
+ *   reproj (T3,C,J,2)        ReprojectionTool.reprojectPoint of points[t][j] in camera c (utils/reprojection.py:49-61),
+ *                            the bits of jh_reproject_point, for EVERY camera of a valid frame -- a masked camera's
+ *                            calibration is known: where the joint should be in the camera that dropped the frame --;
+ *                            NaN for a frame that is not valid
+ *   err (T3,C,J)             sqrt(dx*dx + dy*dy), dx = u - (float)x2d, dy = v - (float)y2d, each operation rounded
+ *                            once in fp32; NaN for a camera that is not used
+ * Nothing of the heat map of a camera that is not used reaches an output (it may hold anything).
+ * These are HybridNet's own 2D detections, on the crop around the projection of the TRIANGULATED centre;
+ * JarvisPredictor2D crops around each camera's own centre detection.  The two agree wherever the crops cover the
+ * subject; they are not bit-equal.
+ * The (max, index) workspace of the scan is allocated by the first call of a predictor -- never by
+ * jh_predictor_create, so jh_predictor_device_bytes and the memory of a predictor that never asks for 2D views are
+ * unchanged -- and that first call must not be made inside a stream capture.  Plain launches, also on a
+ * graph-replaying predictor: the call runs behind the replay and the captured graphs are untouched. */
+int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, const float* points_dev,
+                         const uint8_t* mask_dev, int32_t* points2d_dev, float* conf2d_dev, float* reproj_dev,
+                         float* err_dev, uint8_t* used_dev, void* stream);
+
 /* HybridNetBackbone.forward: crops (T,C,3,B,B) normalised NCHW dev, center_hm
  * (T,C,2) int32, center3d (T,3) int32 -> heatmap_final (T,J,Gh,Gh,Gh) optional,
  * heatmaps_padded (T,C,J,hs,hs) optional, points (T,J,3), conf (T,J). */
@@ -339,6 +369,15 @@ int jh_op_depthwise_pool(int k, int c, const float* w_host, const float* x_dev, 
  * JH_FRAME_I420 / JH_FRAME_NV12 -> out_bgr (n,h,w,3) uint8 BGR (device pointers; h, w even). */
 int jh_op_yuv420_to_bgr(const uint8_t* frames_dev, int format, int n, int h, int w, uint8_t* out_bgr_dev,
                         void* stream);
+
+/* The scan of jh_predictor_views2d on its own: the argmax of every joint's heat map in ONE pass over the buffer (each
+ * byte read once; jh_predictor2d_forward's per-joint kernel reads the image once per joint).  heat (n,hh,wh,jp)
+ * channel-last dev, jp a multiple of 8 up to 256, channels j..jp-1 ignored -> idx (n,j) int32 flat index
+ * y*wh + x of the maximum (the lowest among equal maxima; NaN never wins), max (n,j).  workspace_dev: >=
+ * jh_joint_argmax_all_workspace_bytes(n, hh, wh, jp) bytes, 256-byte aligned (0 for a shape the scan does not take). */
+int64_t jh_joint_argmax_all_workspace_bytes(int n, int hh, int wh, int jp);
+int jh_op_joint_argmax_all(const float* heat_dev, int n, int hh, int wh, int j, int jp, int32_t* idx_dev,
+                           float* max_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
 
 /* One fused BiFPN node (jarvis/efficienttrack/model.py:301-353 fusion expressions + :223-232
  * SeparableConvBlock.forward, without its trailing InstanceNorm):

@@ -112,6 +112,10 @@ _SIGS = {
     "jh_predictor_stage_3d_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p]),
     "jh_predictor_debug_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_predictor_views2d": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 8),
+    "jh_joint_argmax_all_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "jh_op_joint_argmax_all": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_int64, c_void_p]),
     "jh_predictor2d_create": (c_int, [c_void_p, c_void_p, ctypes.POINTER(PredictorConfig),
                                       ctypes.POINTER(c_void_p)]),
     "jh_predictor2d_destroy": (None, [c_void_p]),

@@ -1,10 +1,18 @@
 """Python handle of the native predictor (jh_predictor_* in include/jarvis_hip.h)."""
+import collections
 import ctypes
 
 import torch
 
 from . import _native as N
 from . import arch
+
+
+# Per-camera 2D views of a 3D result (jh_predictor_views2d, include/jarvis_hip.h): points2D (T,C,J,2) int32 full-frame
+# pixels, confidences2D (T,C,J), reprojections (T,C,J,2) of the 3D keypoints, errors (T,C,J) = their distance to
+# points2D in pixels, used (T,C) uint8.  A camera that is not used (masked, or an invalid frame) has points2D -1,
+# confidences2D 0, errors NaN; an invalid frame has NaN reprojections too.
+Views2D = collections.namedtuple("Views2D", "points2D confidences2D reprojections errors used")
 
 
 class NativePredictor:
@@ -167,6 +175,36 @@ class NativePredictor:
             self.handle, N.ptr(heat_blocks), n_blocks, frames_per_block, t_off, t0, N.ptr(points),
             N.ptr(conf), N.ptr(valid), N.stream()))
 
+    def views2d(self, points, heat=None, t0=0, camera_mask=None, out=None):
+        """Per-camera 2D views of the frames t0 .. t0+T3-1 whose 3D keypoints are `points` (T3,J,3): call right
+        after the forward / stage_3d that produced them, on the same stream -> Views2D of device tensors.
+        heat None: the heat maps of the last forward(); otherwise the (T3,C,B/2,B/2,Jp) tensor stage_3d was given.
+        camera_mask: the (T,C) mask that forward / those stages were given (host or device), or None.
+        These are HybridNet's own 2D detections, on the crop around the projection of the triangulated centre;
+        JarvisPredictor2D crops around each camera's own centre detection, so the two are not bit-equal."""
+        dev, T3 = points.device, self.T3
+        if not (points.is_cuda and points.is_contiguous() and points.dtype == torch.float32
+                and tuple(points.shape) == (T3, self.J, 3)):
+            raise ValueError("points must be the contiguous (%d, %d, 3) float32 device tensor of the 3D stage" % (T3, self.J))
+        if heat is not None and not (heat.is_cuda and heat.is_contiguous() and heat.dtype == torch.float32 and
+                                     tuple(heat.shape) == (T3, self.C, self.Hh, self.Hh, self.Jp)):
+            raise ValueError("heat must be a contiguous (%d, %d, %d, %d, %d) float32 device tensor"
+                             % (T3, self.C, self.Hh, self.Hh, self.Jp))
+        mask = N.camera_mask(camera_mask, (self.T, self.C))
+        if mask is not None:
+            mask = mask.to(dev, non_blocking=True)
+        if out is None:
+            out = Views2D(torch.empty((T3, self.C, self.J, 2), device=dev, dtype=torch.int32),
+                          torch.empty((T3, self.C, self.J), device=dev),
+                          torch.empty((T3, self.C, self.J, 2), device=dev),
+                          torch.empty((T3, self.C, self.J), device=dev),
+                          torch.empty((T3, self.C), device=dev, dtype=torch.uint8))
+        N.check(N.lib().jh_predictor_views2d(self.handle, N.ptr(heat), int(t0), N.ptr(points), N.ptr(mask),
+                                             *(N.ptr(t) for t in out), N.stream()))
+        if mask is not None:
+            mask.record_stream(torch.cuda.current_stream())     # (read in place by the enqueued kernel)
+        return Views2D(*out)
+
     def debug(self, device):
         c3f = torch.empty((self.T, 3), device=device)
         c3i = torch.empty((self.T, 3), device=device, dtype=torch.int32)
@@ -243,8 +281,10 @@ class MultiStreamPredictor:
                     t.record_stream(s)
         self._calib = key
 
-    def forward(self, frames, out=None, then=None, frame_format=None, camera_mask=None):
-        """`then(outputs)`, when given, runs inside the batch's stream context right behind the forward and
+    def forward(self, frames, out=None, then=None, frame_format=None, camera_mask=None, return_2d=False):
+        """return_2d: the five tensors of NativePredictor.views2d for this batch are appended to the outputs
+        (points, conf, valid, points2D, confidences2D, reprojections, errors, used).
+        `then(outputs)`, when given, runs inside the batch's stream context right behind the forward and
         before its event is recorded (the drivers enqueue the device->host copy of the results there); its
         return value replaces the outputs.  frame_format, camera_mask: as NativePredictor.forward."""
         frame_format = N.frame_format(frame_format)
@@ -263,6 +303,8 @@ class MultiStreamPredictor:
             t.record_stream(s)
         with torch.cuda.stream(s):
             res = self.preds[i].forward(frames, out, frame_format=frame_format, camera_mask=camera_mask)
+            if return_2d:
+                res = tuple(res) + tuple(self.preds[i].views2d(res[0], camera_mask=camera_mask))
             if then is not None:
                 res = then(res)
             ev = torch.cuda.Event(enable_timing=self.timing)

@@ -6,6 +6,7 @@
 #include "nets.h"
 #include "bifpn_node.h"
 #include "camera_mask.h"
+#include "views2d.h"
 
 namespace jh {
 static thread_local std::string g_err;
@@ -322,6 +323,10 @@ struct jh_predictor {
   unsigned char* mask_buf = nullptr;
   const unsigned char* mask_cur = nullptr;
   int *n_active = nullptr, *n_detect = nullptr;
+  // (max, index) partials of the all-joint argmax behind jh_predictor_views2d, [T3 * C][slices][Jp] each: allocated
+  // by the first such call, so a predictor that never asks for 2D views owns what it always did
+  float* v2d_max = nullptr;
+  int* v2d_idx = nullptr;
   ~jh_predictor() {
     for (auto& e : gexec) if (e) (void)hipGraphExecDestroy(e);
     if (gstream) (void)hipStreamDestroy(gstream);
@@ -733,6 +738,41 @@ int jh_predictor_debug_mask(jh_predictor* pr, int32_t* n_active_dev, int32_t* nu
   return 0;
 }
 
+int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, const float* points_dev,
+                         const uint8_t* mask_dev, int32_t* points2d_dev, float* conf2d_dev, float* reproj_dev,
+                         float* err_dev, uint8_t* used_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(pr && points_dev && points2d_dev && conf2d_dev && reproj_dev && err_dev && used_dev,
+             "null pointer");
+  JH_REQUIRE(t0 >= 0 && t0 + pr->T3 <= pr->T, "frame range of the 2D views");
+  const int N = pr->T3 * pr->C;
+  if (!heat_all_dev) {
+    JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "the predictor's own heat maps hold all cameras only when "
+               "all cameras are local");
+    heat_all_dev = pr->kp->heat.p + (size_t)t0 * pr->C * pr->Hh * pr->Hh * pr->Jp;
+  }
+  if (!pr->v2d_max) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s, &cs);
+    JH_REQUIRE(cs == hipStreamCaptureStatusNone, "the first jh_predictor_views2d call of a predictor allocates its "
+               "workspace: make it outside a stream capture");
+    const size_t n = joint_argmax_all_partials(N, pr->Hh, pr->Hh, pr->Jp);
+    if (pr->mem.get(reinterpret_cast<void**>(&pr->v2d_max), n * sizeof(float))) return 1;
+    if (pr->mem.get(reinterpret_cast<void**>(&pr->v2d_idx), n * sizeof(int))) return 1;
+  }
+  const double bytes = 4.0 * N * pr->Hh * pr->Hh * pr->Jp;
+  JH_PROF("joint_argmax_all", 0.0, bytes,
+          launch_joint_argmax_all(heat_all_dev, pr->v2d_max, pr->v2d_idx, N, pr->Hh, pr->Hh, pr->J, pr->Jp, s));
+  // (the merge reads the partials of every slice and writes 24 B per (frame, camera, joint))
+  const int slices = joint_argmax_all_shape(N, pr->Hh, pr->Hh, pr->Jp).slices;
+  JH_PROF("views2d_final", 0.0, 8.0 * N * slices * pr->Jp + 24.0 * N * pr->J,
+          launch_views2d_final(pr->v2d_max, pr->v2d_idx, pr->chm_cur() + (size_t)t0 * pr->C * 2, pr->valid_cur() + t0,
+                               mask_dev ? mask_dev + (size_t)t0 * pr->C : nullptr, points_dev, pr->cam, pr->intr,
+                               pr->dist, points2d_dev, conf2d_dev, reproj_dev, err_dev, used_dev, pr->T3, pr->C,
+                               pr->J, pr->Jp, pr->Hh, pr->Hh, pr->B / 2, s));
+  return 0;
+}
+
 int jh_predictor_debug(jh_predictor* pr, float* center3d_f_dev, int32_t* center3d_i_dev,
                        int32_t* center_hm_dev, float* det_dev, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1020,6 +1060,41 @@ int jh_op_depthwise_pool(int k, int c, const float* w_host, const float* x_dev, 
       out[(size_t)i * c + ch] = (float)((q[0] + q[1]) + q[2]);
     }
   JH_CHECK_HIP(hipMemcpy(pool_dev, out.data(), out.size() * sizeof(float), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// The all-joint argmax on its own (csrc/geometry.hip): the (max, index) partials live in the caller's workspace.
+static size_t carve_joint_argmax_all(Carver& c, int n, int hh, int wh, int jp, float** pmax, int** pidx) {
+  const size_t k = joint_argmax_all_partials(n, hh, wh, jp);
+  *pmax = c.take<float>(k);
+  *pidx = c.take<int>(k);
+  return c.off;
+}
+
+int64_t jh_joint_argmax_all_workspace_bytes(int n, int hh, int wh, int jp) {
+  if (n < 1 || hh < 1 || wh < 1 || jp < 8 || jp % 8 || jp > 256) return 0;
+  Carver c(nullptr, 0);
+  float* pmax;
+  int* pidx;
+  return (int64_t)carve_joint_argmax_all(c, n, hh, wh, jp, &pmax, &pidx);
+}
+
+int jh_op_joint_argmax_all(const float* heat_dev, int n, int hh, int wh, int j, int jp, int32_t* idx_dev,
+                           float* max_dev, void* workspace_dev, int64_t workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(heat_dev && idx_dev && max_dev, "null pointer");
+  JH_REQUIRE(n >= 1 && hh >= 1 && wh >= 1 && jp >= 8 && jp % 8 == 0 && jp <= 256 && j >= 1 && j <= jp,
+             "jh_op_joint_argmax_all: shape");
+  JH_REQUIRE(workspace_dev && workspace_bytes >= 0, "workspace (see jh_joint_argmax_all_workspace_bytes)");
+  Carver c(workspace_dev, (size_t)workspace_bytes);
+  float* pmax;
+  int* pidx;
+  carve_joint_argmax_all(c, n, hh, wh, jp, &pmax, &pidx);
+  JH_REQUIRE(c.fits(), "workspace smaller than jh_joint_argmax_all_workspace_bytes()");
+  const double bytes = 4.0 * n * hh * wh * jp;
+  JH_PROF("joint_argmax_all", 0.0, bytes, launch_joint_argmax_all(heat_dev, pmax, pidx, n, hh, wh, j, jp, s));
+  if (launch_joint_argmax_all_combine(pmax, pidx, idx_dev, max_dev, n, hh, wh, j, jp, s)) return 1;
+  JH_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }
 

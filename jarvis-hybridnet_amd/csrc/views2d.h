@@ -1,0 +1,24 @@
+// Per-camera 2D views of the 3D predictor (jh_predictor_views2d): the all-joint argmax in one pass over
+// [N][Hh*Wh][Jp] channel-last heat maps and the kernels that merge its slices (csrc/geometry.hip).
+#pragma once
+#include "jh_common.h"
+
+namespace jh {
+
+// How the scan cuts a shape: threads per block, pixels per slice, slices per image.
+struct ScanShape { int threads = 0, ppb = 0, slices = 0; };
+ScanShape joint_argmax_all_shape(int N, int Hh, int Wh, int Jp);
+// elements of each of the two partial arrays (max: float, index: int) the scan writes: [N][slices][Jp]
+size_t joint_argmax_all_partials(int N, int Hh, int Wh, int Jp);
+int launch_joint_argmax_all(const float* heat, float* pmax, int* pidx, int N, int Hh, int Wh, int J, int Jp,
+                            hipStream_t s);
+// partials -> idx / maxv [N][J] (the scan's own result, for the unit test)
+int launch_joint_argmax_all_combine(const float* pmax, const int* pidx, int* idx, float* maxv, int N, int Hh,
+                                    int Wh, int J, int Jp, hipStream_t s);
+// partials + crop centres, validity, mask and 3D points of T frames -> the five outputs of jh_predictor_views2d
+int launch_views2d_final(const float* pmax, const int* pidx, const int* center_hm, const int* valid,
+                         const unsigned char* mask, const float* pts3d, const float* cam, const float* intr,
+                         const float* dist, int* points2d, float* conf2d, float* reproj, float* err,
+                         unsigned char* used, int T, int C, int J, int Jp, int Hh, int Wh, int hw, hipStream_t s);
+
+}  // namespace jh

@@ -133,8 +133,12 @@ class JarvisPredictor3D(nn.Module):
         m = N.camera_mask(camera_mask, (self.num_cameras,))
         return None if m is None else m.unsqueeze(0)
 
-    def forward(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None):
+    def forward(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None,
+                return_2d=False):
         """imgs (C,3,H,W) RGB in [0,1] -> (points3D (1,J,3), confidences (1,J)) or (None, None).
+        return_2d: a third element, the per-camera `Views2D` of this frame set (leading dimension 1: 2D keypoints of
+        every camera from the heat maps this forward computed anyway, the reprojections of the 3D keypoints and
+        their distance in pixels; see _single), or (None, None, None).
         camera_mask (C,) bool / integer tensor or sequence, host or device: the frame is computed as the reference
         computes it for the cameras with a nonzero entry alone, in their order (its `cameras_to_use` subset); what
         the other cameras' slots of `imgs` hold does not matter.  Fewer than two cameras left, or fewer than two of
@@ -147,53 +151,62 @@ class JarvisPredictor3D(nn.Module):
         x = N.dev(imgs)
         pr = self.native(x.shape[2], x.shape[3])
         pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-        points, conf, valid = pr.forward(x.unsqueeze(0), camera_mask=mask)
-        if int(valid[0].item()) == 0:               # jarvis3D.py:157,187-190
-            return None, None
-        return points, conf
+        return self._single(pr, pr.forward(x.unsqueeze(0), camera_mask=mask), mask, return_2d)
 
-    def forward_uint8(self, imgs_bgr, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None):
+    @staticmethod
+    def _single(pr, res, mask, return_2d):
+        """The single-frame forms' return value: (points3D, confidences[, Views2D]), every element None when fewer
+        than two cameras saw the subject (jarvis3D.py:157,187-190).  The 2D views are enqueued behind the forward,
+        before the one host synchronisation (reading the validity flag).
+        Views2D are HybridNet's own 2D detections, on the crop around the projection of the TRIANGULATED centre;
+        JarvisPredictor2D crops around each camera's own centre detection.  The two agree wherever the crops cover
+        the subject; they are not bit-equal."""
+        points, conf, valid = res
+        views = pr.views2d(points, camera_mask=mask) if return_2d else None
+        if int(valid[0].item()) == 0:
+            return (None, None, None) if return_2d else (None, None)
+        return (points, conf, views) if return_2d else (points, conf)
+
+    def forward_uint8(self, imgs_bgr, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None,
+                      return_2d=False):
         """imgs_bgr (C,H,W,3) uint8 BGR exactly as the video decoder delivers them
         (predict3D.py:72-78).  Same result as forward() on
         `imgs_bgr.float().permute(0,3,1,2)[:, [2,1,0]] / 255.` (predict3D.py:79-80); the
-        conversion runs inside the resize / crop kernels.  camera_mask: as forward()."""
+        conversion runs inside the resize / crop kernels.  camera_mask, return_2d: as forward()."""
         mask = self._frame_mask(camera_mask)
         check_native_seam(self)
         x = N.dev(imgs_bgr, torch.uint8)
         pr = self.native(x.shape[1], x.shape[2])
         pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-        points, conf, valid = pr.forward(x.unsqueeze(0), camera_mask=mask)
-        if int(valid[0].item()) == 0:
-            return None, None
-        return points, conf
+        return self._single(pr, pr.forward(x.unsqueeze(0), camera_mask=mask), mask, return_2d)
 
     def forward_yuv(self, frames, frame_format, cameraMatrices, intrinsicMatrices, distortionCoefficients,
-                    camera_mask=None):
+                    camera_mask=None, return_2d=False):
         """frames (C,3H/2,W) uint8 YUV 4:2:0 as video decoders produce them natively, frame_format 'i420'
         (FFmpeg yuv420p: Y, U, V planes) or 'nv12' (Y plane, interleaved UV plane); H and W even.  Same result,
         bit for bit, as forward_uint8 on the BGR bytes of cv2.cvtColor(COLOR_YUV2BGR_I420 / _NV12) of each
         image (BT.601 limited range); the conversion runs inside the resize / crop kernels.
-        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask: as forward()."""
+        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d: as forward()."""
         mask = self._frame_mask(camera_mask)
         x = _yuv_frames(frames, frame_format, 3)
         check_native_seam(self)
         H, W = N.yuv_frame_hw(x.shape)
         pr = self.native(H, W)
         pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-        points, conf, valid = pr.forward(x.unsqueeze(0), frame_format=frame_format, camera_mask=mask)
-        if int(valid[0].item()) == 0:
-            return None, None
-        return points, conf
+        return self._single(pr, pr.forward(x.unsqueeze(0), frame_format=frame_format, camera_mask=mask), mask,
+                            return_2d)
 
     def forward_batch(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
-                      camera_mask=None):
+                      camera_mask=None, return_2d=False):
         """Throughput form: imgs (T,C,3,H,W) fp32 RGB or (T,C,H,W,3) uint8 BGR,
         independent time steps -> points (T,J,3), confidences (T,J), valid (T) int32;
         no host synchronisation.  frame_format 'i420' / 'nv12': imgs (T,C,3H/2,W) uint8 YUV 4:2:0 (see
         forward_yuv); 'bgr': uint8 BGR required; None: the dtype decides.
         camera_mask (T,C) bool / integer, host or device: row t names the cameras frame set t uses (see forward());
         a row with fewer than two cameras gives valid[t] = 0.  Rows are independent: a frame set's result depends on
-        its own mask row only.  None: all cameras."""
+        its own mask row only.  None: all cameras.
+        return_2d: the per-camera `Views2D` of the batch (leading dimension T; see forward()) follows `valid`:
+        (points, confidences, valid, views).  Rows of invalid frames: used 0, points2D -1, NaN reprojections."""
         frame_format = N.frame_format(frame_format)
         if camera_mask is not None:
             if not torch.is_tensor(imgs) or imgs.dim() < 1:
@@ -205,7 +218,8 @@ class JarvisPredictor3D(nn.Module):
             H, W = N.yuv_frame_hw(x.shape)
             pr = self.native(H, W, time_batch=x.shape[0])
             pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-            return pr.forward(x, frame_format=frame_format, camera_mask=camera_mask)
+            return self._batch(pr, pr.forward(x, frame_format=frame_format, camera_mask=camera_mask), camera_mask,
+                               return_2d)
         if frame_format == "bgr" and imgs.dtype != torch.uint8:
             raise ValueError("frame_format 'bgr' needs uint8 (T,C,H,W,3) frames; got dtype %s" % imgs.dtype)
         check_native_seam(self)
@@ -213,11 +227,15 @@ class JarvisPredictor3D(nn.Module):
             x = N.dev(imgs, torch.uint8)
             pr = self.native(x.shape[2], x.shape[3], time_batch=x.shape[0])
             pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-            return pr.forward(x, camera_mask=camera_mask)
+            return self._batch(pr, pr.forward(x, camera_mask=camera_mask), camera_mask, return_2d)
         x = N.dev(imgs)
         pr = self.native(x.shape[3], x.shape[4], time_batch=x.shape[0])
         pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-        return pr.forward(x, camera_mask=camera_mask)
+        return self._batch(pr, pr.forward(x, camera_mask=camera_mask), camera_mask, return_2d)
+
+    @staticmethod
+    def _batch(pr, res, mask, return_2d):
+        return tuple(res) + (pr.views2d(res[0], camera_mask=mask),) if return_2d else res
 
 
 def _yuv_frames(frames, frame_format, ndim):

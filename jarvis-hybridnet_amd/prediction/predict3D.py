@@ -65,9 +65,34 @@ def frame_row(points3D, confidences, num_joints):
     return row
 
 
+def views2d_row(points2D, confidences2D, used, num_joints):
+    """One row of a camera's data2D_<name>.csv from its slice of a frame set's `Views2D`: points2D (J,2),
+    confidences2D (J): predict2D.frame_row of the same numbers ([x, y, confidence] per joint), or 'NaN' x 3J when
+    the camera is not used in that frame set (masked, or the frame set is invalid)."""
+    from .predict2D import frame_row as frame_row_2d
+    if not int(used):
+        return frame_row_2d(None, None, num_joints)
+    return frame_row_2d(points2D.long(), confidences2D, num_joints)
+
+
+def reprojection_error_row(errors):
+    """One row of reprojection_error.csv: the (C,J) reprojection errors of a frame set in pixels, camera-major,
+    as numpy float32 elements (the element type of the confidences in the other files); 'NaN' where the error is
+    undefined (a camera that is not used in the frame set)."""
+    import math
+    return ["NaN" if math.isnan(v) else v for v in errors.detach().cpu().float().reshape(-1).numpy()]
+
+
+def create_header_reprojection_error(writer, cfg, camera_names):
+    """Two header rows: every camera name once per joint, then the joint names once per camera."""
+    names = list(cfg.KEYPOINT_NAMES)
+    writer.writerow(list(itertools.chain.from_iterable(itertools.repeat(c, len(names)) for c in camera_names)))
+    writer.writerow(names * len(camera_names))
+
+
 def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                      distortionCoefficients, cfg, output_dir, params=None, time_batch=1, streams=1,
-                     frame_spec=None, frame_format="bgr", camera_mask=None):
+                     frame_spec=None, frame_format="bgr", camera_mask=None, output_2d=False, camera_names=None):
     """Run `predictor` over an iterable of multi-view frame sets -- (C,H,W,3) uint8 BGR
     arrays / tensors exactly as cv2 delivers them, or (C,3,H,W) fp32 RGB -- and write
     data3D.csv (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -107,7 +132,19 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     camera that dropped a frame: mask it for that frame set; whatever its slot holds is ignored).  A frame set with
     fewer than two cameras left gives a 'NaN' row, like one in which fewer than two cameras detect.  A mask of the
     wrong shape or of a floating dtype, and a mask iterable that ends before the frame sets do, or after, raise
-    ValueError.  The CSV and info.yaml formats do not change."""
+    ValueError.  The CSV and info.yaml formats do not change.
+
+    output_2d: also write, beside data3D.csv (which, like info.yaml, is byte-identical with and without the option),
+    the per-camera 2D views of every frame set (JarvisPredictor3D.forward(..., return_2d=True): no second pass over
+    the videos): `data2D_<name>.csv` per camera in the format of the predict2D driver (rows of predict2D.frame_row,
+    the header of predict2D.create_header when data3D.csv gets its header; 'NaN' x 3J where the camera is not used:
+    masked in that frame set, or the frame set is invalid) and `reprojection_error.csv`, one row per frame set of
+    C * J distances in pixels between a camera's 2D keypoint and the projection of the 3D keypoint, camera-major,
+    'NaN' where undefined, under a camera-name row and a joint-name row.  camera_names: C names, default
+    Camera_0 ...  These 2D keypoints are HybridNet's own detections, on the crop around the projection of the
+    TRIANGULATED centre; the predict2D driver (JarvisPredictor2D) crops around each camera's own centre detection.
+    The two agree wherever the crops cover the subject; they are not bit-equal."""
+    import contextlib
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
     yuv = driver_format(frame_format, frame_spec, 3)
     run_mask, mask_iter = None, None
@@ -125,22 +162,47 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     calib = (cameraMatrices, intrinsicMatrices, distortionCoefficients)
     time_batch, streams = max(1, int(time_batch)), max(1, int(streams))
     n = 0
-    with open(os.path.join(output_dir, "data3D.csv"), "w", newline="") as f:
-        writer = csv.writer(f, delimiter=",", quotechar='"', quoting=csv.QUOTE_MINIMAL)
+    if output_2d:
+        num_cams = cfg.HYBRIDNET.NUM_CAMERAS
+        camera_names = ["Camera_%d" % i for i in range(num_cams)] if camera_names is None else list(camera_names)
+        if len(camera_names) != num_cams or len(set(camera_names)) != num_cams:
+            raise ValueError("camera_names must be %d distinct names, got %r" % (num_cams, camera_names))
+    with contextlib.ExitStack() as files:
+        def open_csv(name):
+            f = files.enter_context(open(os.path.join(output_dir, name), "w", newline=""))
+            return csv.writer(f, delimiter=",", quotechar='"', quoting=csv.QUOTE_MINIMAL)
+
+        writer = open_csv("data3D.csv")
         names = getattr(cfg, "KEYPOINT_NAMES", [])
         if len(names) == J:
             create_header(writer, cfg)
+        writers_2d, writer_err = [], None
+        if output_2d:
+            from .predict2D import create_header as create_header_2d
+            writers_2d = [open_csv("data2D_%s.csv" % name) for name in camera_names]
+            writer_err = open_csv("reprojection_error.csv")
+            if len(names) == J:
+                for w in writers_2d:
+                    create_header_2d(w, cfg)
+                create_header_reprojection_error(writer_err, cfg, camera_names)
 
         def emit(outs, real):
-            pts, conf, valid = outs
+            pts, conf, valid = outs[:3]
             for t in range(real):
                 ok = int(valid[t]) != 0
                 writer.writerow(frame_row(pts[t] if ok else None, conf[t] if ok else None, J))
+                if output_2d:
+                    p2d, c2d, _, err, used = outs[3:]
+                    for c, w in enumerate(writers_2d):
+                        w.writerow(views2d_row(p2d[t, c], c2d[t, c], used[t, c], J))
+                    writer_err.writerow(reprojection_error_row(err[t]))
 
         ring = {}                                               # pinned host copies of the outputs, per slot
 
         def submit(x, slot, mask=None):
             kw = {} if mask is None else {"camera_mask": mask}
+            if output_2d:
+                kw["return_2d"] = True
             if hasattr(predictor, "native_streams"):
                 if yuv:
                     h, w = N.yuv_frame_hw(x.shape)
@@ -155,6 +217,8 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             # any object with the batch interface
             res = predictor.forward_batch(x, *calib, frame_format=frame_format, **kw) if yuv else \
                 predictor.forward_batch(x, *calib, **kw)
+            if output_2d:
+                res = tuple(res[:3]) + tuple(res[3])           # (points, conf, valid, Views2D) -> eight tensors
             ev = None
             if x.is_cuda:
                 res = host_outputs(ring, slot, res)
