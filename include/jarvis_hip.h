@@ -243,6 +243,51 @@ int jh_predictor_forward_u8(jh_predictor* pr, const uint8_t* frames_dev, float* 
 int jh_predictor_forward_yuv(jh_predictor* pr, const uint8_t* frames_dev, int format, float* points_dev,
                              float* conf_dev, int32_t* valid_dev, void* stream);
 
+/* Described YUV 4:2:0 surfaces (ABI v4, additive): what decoders really hand out, read in place.  A jh_yuv_surface
+ * says where the three planes of ONE image lie inside a buffer of `image_stride` bytes and how its colour is coded;
+ * frames are (T,cam_n) such images back to back (the 2D predictor: (T)), image n = t * cam_n + c at byte
+ * n * image_stride.  Pitched decoder surfaces (row pitch above the width, chroma after pitch * aligned height),
+ * FFmpeg AVFrames copied plane by plane with their linesize, and the four plane orders are values of the fields:
+ *   I420: u_offset < v_offset, c_step 1;   YV12: v_offset < u_offset, c_step 1;
+ *   NV12: v_offset == u_offset + 1, c_step 2;   NV21: u_offset == v_offset + 1, c_step 2.
+ * Bytes of an image that belong to no plane (pitch padding, rows between the planes, the gap up to image_stride) may
+ * hold anything: they are never read.
+ * Conversion: u = U - 128, v = V - 128, yy = max(0, Y - Y0) * CY + 2^19, then
+ *   R = clamp8((yy + CVR v) >> 20), G = clamp8((yy + CVG v + CUG u) >> 20), B = clamp8((yy + CUB u) >> 20)
+ * in int32, the chroma of pixel (y, x) that of block (y/2, x/2), with (Y0, CY, CVR, CUB, CUG, CVG) =
+ *   BT.601 limited  (16, 1220542, 1673527, 2116026, -409993, -852492)   -- OpenCV's literals: the bits of _forward_yuv
+ *   BT.601 full     ( 0, 1048576, 1470104, 1858077, -360853, -748826)
+ *   BT.709 limited  (16, 1220945, 1879825, 2215014, -223607, -558796)
+ *   BT.709 full     ( 0, 1048576, 1651297, 1945738, -196424, -490864)
+ * (the last three: round(x * 2^20) of the real matrix, within 0.51 of it everywhere).  The bytes then take the
+ * uint8 path unchanged: the result equals, bit for bit, jh_predictor_forward_u8 on the converted frames.
+ * jh_yuv_surface_check (no GPU needed) is the validation every entry point applies: h, w even and positive;
+ * c_step 1 or 2; y_pitch >= w, c_pitch >= (w/2) * c_step; offsets >= 0; for c_step 2, |u_offset - v_offset| == 1
+ * with min(u_offset, v_offset) and c_pitch even; every plane ends at or before image_stride; matrix and range
+ * known; reserved 0.  Returns 0, or nonzero with jh_last_error() set.
+ * jh_predictor_forward_surface: jh_predictor_forward_yuv through a description; mask_dev as in
+ * jh_predictor_forward_masked, or NULL.  A graph-replaying predictor keeps one captured graph for this form (and
+ * one for its masked form); a recording has one layout, so a call whose description differs from the recorded one
+ * records again. */
+#define JH_YUV_BT601 0
+#define JH_YUV_BT709 1
+#define JH_YUV_LIMITED 0
+#define JH_YUV_FULL 1
+typedef struct jh_yuv_surface {
+  int64_t image_stride;        /* bytes from image n to image n+1 (n = t * cameras + c) */
+  int64_t y_offset, y_pitch;   /* Y(y, x)  at y_offset + y * y_pitch + x */
+  int64_t u_offset, v_offset;  /* U / V of block (y/2, x/2) at *_offset + (y/2) * c_pitch + (x/2) * c_step */
+  int64_t c_pitch;
+  int32_t c_step;              /* 1: planar (I420, YV12); 2: semi-planar (NV12, NV21) */
+  int32_t matrix;              /* JH_YUV_BT601 = 0, JH_YUV_BT709 = 1 */
+  int32_t range;               /* JH_YUV_LIMITED = 0, JH_YUV_FULL = 1 */
+  int32_t reserved;            /* 0 */
+} jh_yuv_surface;
+int jh_yuv_surface_check(const jh_yuv_surface* surface, int h, int w);
+int jh_predictor_forward_surface(jh_predictor* pr, const uint8_t* frames_dev, const jh_yuv_surface* surface,
+                                 const uint8_t* mask_dev, float* points_dev, float* conf_dev, int32_t* valid_dev,
+                                 void* stream);
+
 /* Integer path of the last call, for parity tests: center3d float (T,3),
  * center3d int (T,3), center_hm (T,C,2), det (T,C,3).  Any pointer may be NULL. */
 int jh_predictor_debug(jh_predictor* pr, float* center3d_f_dev, int32_t* center3d_i_dev,
@@ -336,6 +381,9 @@ int jh_predictor2d_forward_u8(jh_predictor2d* pr, const uint8_t* frames_dev, int
 /* frames (T,3H/2,W) YUV 4:2:0, format JH_FRAME_I420 or JH_FRAME_NV12 (as jh_predictor_forward_yuv). */
 int jh_predictor2d_forward_yuv(jh_predictor2d* pr, const uint8_t* frames_dev, int format, int32_t* points_dev,
                                float* conf_dev, int32_t* valid_dev, void* stream);
+/* frames (T) images of a described surface (as jh_predictor_forward_surface). */
+int jh_predictor2d_forward_surface(jh_predictor2d* pr, const uint8_t* frames_dev, const jh_yuv_surface* surface,
+                                   int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
 
 /* ---- per-launch timing (HIP events on the launch stream; used by bench.py for
  * the roofline figures).  begin() switches recording on for every kernel the
@@ -369,6 +417,10 @@ int jh_op_depthwise_pool(int k, int c, const float* w_host, const float* x_dev, 
  * JH_FRAME_I420 / JH_FRAME_NV12 -> out_bgr (n,h,w,3) uint8 BGR (device pointers; h, w even). */
 int jh_op_yuv420_to_bgr(const uint8_t* frames_dev, int format, int n, int h, int w, uint8_t* out_bgr_dev,
                         void* stream);
+/* The same for images of a described surface (jh_yuv_surface above): frames n * image_stride bytes -> out_bgr
+ * (n,h,w,3) uint8 BGR. */
+int jh_op_yuv_surface_to_bgr(const uint8_t* frames_dev, const jh_yuv_surface* surface, int n, int h, int w,
+                             uint8_t* out_bgr_dev, void* stream);
 
 /* The scan of jh_predictor_views2d on its own: the argmax of every joint's heat map in ONE pass over the buffer (each
  * byte read once; jh_predictor2d_forward's per-joint kernel reads the image once per joint).  heat (n,hh,wh,jp)

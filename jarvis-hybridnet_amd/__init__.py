@@ -8,3 +8,5 @@ live in `csrc/` and are reached through the C ABI declared in
 entry point raises if the library cannot be loaded.
 """
 __version__ = "0.1.0"
+
+from .yuv_surface import YuvSurface  # noqa: E402,F401 -- pure Python: importing the package still loads no library

@@ -31,6 +31,16 @@ class PredictorConfig(ctypes.Structure):
                 ("precision", ctypes.c_int32)]
 
 
+class YuvSurfaceStruct(ctypes.Structure):
+    """jh_yuv_surface of include/jarvis_hip.h (built by yuv_surface.YuvSurface.struct())."""
+    _fields_ = [("image_stride", ctypes.c_int64), ("y_offset", ctypes.c_int64), ("y_pitch", ctypes.c_int64),
+                ("u_offset", ctypes.c_int64), ("v_offset", ctypes.c_int64), ("c_pitch", ctypes.c_int64),
+                ("c_step", ctypes.c_int32), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(YuvSurfaceStruct) == 64
+
 ABI_VERSION = 4                      # JH_ABI_VERSION of include/jarvis_hip.h
 # sizeof(jh_predictor_config): statically asserted on the C side (tests/abi_smoke.c) and here
 assert ctypes.sizeof(PredictorConfig) == 84
@@ -105,6 +115,13 @@ _SIGS = {
     "jh_predictor_stage_keypoints_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_forward_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_forward_yuv": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_yuv_surface_check": (c_int, [ctypes.POINTER(YuvSurfaceStruct), c_int, c_int]),
+    "jh_predictor_forward_surface": (c_int, [c_void_p, c_void_p, ctypes.POINTER(YuvSurfaceStruct), c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
+    "jh_predictor2d_forward_surface": (c_int, [c_void_p, c_void_p, ctypes.POINTER(YuvSurfaceStruct), c_void_p,
+                                               c_void_p, c_void_p, c_void_p]),
+    "jh_op_yuv_surface_to_bgr": (c_int, [c_void_p, ctypes.POINTER(YuvSurfaceStruct), c_int, c_int, c_int, c_void_p,
+                                         c_void_p]),
     "jh_predictor_forward_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p]),
     "jh_predictor_stage_keypoints_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
@@ -182,6 +199,32 @@ def yuv_frame_hw(shape):
     if rows <= 0 or rows % 3 or w <= 0 or w % 2:
         raise ValueError("a YUV 4:2:0 image is (3H/2, W) bytes with H and W even; got (%d, %d)" % (rows, w))
     return rows // 3 * 2, w
+
+
+def frame_layout(layout, frame_format, lead, hw=None, frames=None):
+    """A frame_layout argument checked, before anything reaches the GPU: None stays None; otherwise a
+    yuv_surface.YuvSurface, not combined with frame_format 'i420' / 'nv12' (the layout says where the planes are),
+    of the frame size `hw` when that is given, and `frames` (when given) a uint8 tensor of shape
+    lead + (image_stride,) -- `lead` a tuple whose None entries match any size.  ValueError otherwise."""
+    if layout is None:
+        return None
+    from .yuv_surface import YuvSurface
+    if not isinstance(layout, YuvSurface):
+        raise ValueError("frame_layout must be a YuvSurface or None, got %r" % (type(layout).__name__,))
+    if frame_format in YUV_FORMATS:
+        raise ValueError("frame_layout describes the planes itself: do not combine it with frame_format=%r"
+                         % (frame_format,))
+    if hw is not None and (layout.height, layout.width) != tuple(hw):
+        raise ValueError("frame_layout is %d x %d; this predictor is %d x %d" % (layout.height, layout.width, *hw))
+    if frames is not None:
+        want = tuple(lead) + (layout.image_stride,)
+        ok = torch.is_tensor(frames) and frames.dtype == torch.uint8 and frames.dim() == len(want) and all(
+            w is None or int(g) == w for g, w in zip(frames.shape, want))
+        if not ok:
+            raise ValueError("frames of a YuvSurface must be uint8 %s (image_stride bytes per image); got %s" % (
+                tuple("*" if w is None else w for w in want),
+                (frames.dtype, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames).__name__))
+    return layout
 
 
 def camera_mask(mask, shape, what="camera_mask"):

@@ -66,20 +66,32 @@ class NativePredictor:
             self.handle, N.ptr(N.dev(cam)), N.ptr(N.dev(intr)), N.ptr(N.dev(dist)), N.stream()))
 
     # ---- single-GPU forward ----------------------------------------------
-    def forward(self, frames, out=None, frame_format=None, camera_mask=None):
+    def forward(self, frames, out=None, frame_format=None, camera_mask=None, frame_layout=None):
         """frames (T,C,3,H,W) fp32 RGB, or (T,C,H,W,3) uint8 BGR as decoded, or with frame_format 'i420' / 'nv12'
         (T,C,3H/2,W) uint8 YUV 4:2:0 -> points (T,J,3), conf (T,J), valid (T) int32.  frame_format None: the
         dtype decides between fp32 RGB and uint8 BGR; 'bgr' requires uint8 BGR.
         camera_mask (T,C) bool / integer, host or device: frame t uses the cameras with a nonzero entry only
-        (jh_predictor_forward_masked); None: all cameras, the unmasked entry points."""
+        (jh_predictor_forward_masked); None: all cameras, the unmasked entry points.
+        frame_layout: a YuvSurface -- frames (T,C,image_stride) uint8, each image a YUV 4:2:0 surface read through
+        that description (jh_predictor_forward_surface); not together with frame_format 'i420' / 'nv12'."""
         frame_format = N.frame_format(frame_format)
         camera_mask = N.camera_mask(camera_mask, (self.T, self.C))
-        self._check_frames(frames, self.Cloc, frame_format)
+        frame_layout = N.frame_layout(frame_layout, frame_format, (self.T, self.Cloc), (self.cfg.img_h, self.cfg.img_w),
+                                      frames)
+        self._check_frames(frames, self.Cloc, frame_format, frame_layout)
         dev = frames.device
         if out is None:
             out = (torch.empty((self.T, self.J, 3), device=dev),
                    torch.empty((self.T, self.J), device=dev),
                    torch.empty((self.T,), device=dev, dtype=torch.int32))
+        if frame_layout is not None:
+            mask = None if camera_mask is None else camera_mask.to(dev, non_blocking=True)
+            surf = frame_layout.struct()                        # (read during the call only)
+            N.check(N.lib().jh_predictor_forward_surface(self.handle, N.ptr(frames), surf, N.ptr(mask), N.ptr(out[0]),
+                                                         N.ptr(out[1]), N.ptr(out[2]), N.stream()))
+            if mask is not None and mask.is_cuda:
+                mask.record_stream(torch.cuda.current_stream())
+            return out
         if camera_mask is not None:
             fmt = N.FRAME_FORMATS[frame_format] if frame_format in N.YUV_FORMATS else int(frames.dtype == torch.uint8)
             mask = camera_mask.to(dev, non_blocking=True)       # (copied by the call: free once it is enqueued)
@@ -98,11 +110,13 @@ class NativePredictor:
                    N.stream()))
         return out
 
-    def _check_frames(self, frames, cams, frame_format=None):
+    def _check_frames(self, frames, cams, frame_format=None, frame_layout=None):
         """Raw pointers cross the C ABI: refuse anything whose bytes would be misread."""
         H, W = self.cfg.img_h, self.cfg.img_w
         if not (torch.is_tensor(frames) and frames.is_cuda and frames.is_contiguous()):
             raise RuntimeError("frames must be a contiguous CUDA (HIP) tensor")
+        if frame_layout is not None:
+            return                                   # (dtype and shape: _native.frame_layout, a ValueError)
         if frame_format in N.YUV_FORMATS:
             if H % 2 or W % 2:
                 raise ValueError("YUV 4:2:0 frames need an even height and width; this predictor is %d x %d" % (H, W))
@@ -281,15 +295,18 @@ class MultiStreamPredictor:
                     t.record_stream(s)
         self._calib = key
 
-    def forward(self, frames, out=None, then=None, frame_format=None, camera_mask=None, return_2d=False):
+    def forward(self, frames, out=None, then=None, frame_format=None, camera_mask=None, return_2d=False,
+                frame_layout=None):
         """return_2d: the five tensors of NativePredictor.views2d for this batch are appended to the outputs
         (points, conf, valid, points2D, confidences2D, reprojections, errors, used).
         `then(outputs)`, when given, runs inside the batch's stream context right behind the forward and
         before its event is recorded (the drivers enqueue the device->host copy of the results there); its
-        return value replaces the outputs.  frame_format, camera_mask: as NativePredictor.forward."""
+        return value replaces the outputs.  frame_format, camera_mask, frame_layout: as NativePredictor.forward."""
         frame_format = N.frame_format(frame_format)
-        camera_mask = N.camera_mask(camera_mask, (self.preds[0].T, self.preds[0].C))
-        self.preds[0]._check_frames(frames, self.preds[0].Cloc, frame_format)     # before any stream work
+        p0 = self.preds[0]
+        camera_mask = N.camera_mask(camera_mask, (p0.T, p0.C))
+        frame_layout = N.frame_layout(frame_layout, frame_format, (p0.T, p0.Cloc), (p0.cfg.img_h, p0.cfg.img_w), frames)
+        p0._check_frames(frames, p0.Cloc, frame_format, frame_layout)              # before any stream work
         i = self._next
         self._next = (i + 1) % len(self.preds)
         s = self.streams[i]
@@ -302,7 +319,8 @@ class MultiStreamPredictor:
         for t in (out or ()):
             t.record_stream(s)
         with torch.cuda.stream(s):
-            res = self.preds[i].forward(frames, out, frame_format=frame_format, camera_mask=camera_mask)
+            res = self.preds[i].forward(frames, out, frame_format=frame_format, camera_mask=camera_mask,
+                                        frame_layout=frame_layout)
             if return_2d:
                 res = tuple(res) + tuple(self.preds[i].views2d(res[0], camera_mask=camera_mask))
             if then is not None:

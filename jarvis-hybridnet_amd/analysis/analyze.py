@@ -20,11 +20,15 @@ from ..utils.reprojection import load_reprojection_tools
 
 
 def analyze_frames(predictor, samples, reproTools, output_dir, num_joints, progress_bar=None,
-                   num_frame_sets=None):
+                   num_frame_sets=None, frame_layout=None):
     """samples: iterable of batch-1 collated Dataset3D analysis samples
     `[imgs (1,C,H,W,3), keypoints3D (1,J,3), ..., dataset_name [str], file_name [str]]`
     (dataset3D.py:248-258 behind a DataLoader(batch_size=1), analyze.py:46-51).
+    frame_layout: a YuvSurface -- imgs is (1,C,image_stride) uint8, one described YUV 4:2:0 surface per camera
+    (JarvisPredictor3D.forward_surface).
     Returns (number of frame sets seen, number predicted)."""
+    from .. import _native as N
+    N.frame_layout(frame_layout, None, ())
     pointsNet, pointsGT, filenames = [], [], []
     seen = 0
     for item, sample in enumerate(samples):
@@ -36,10 +40,13 @@ def analyze_frames(predictor, samples, reproTools, output_dir, num_joints, progr
         dataset_name = sample[-2][0]
         reproTool = reproTools[dataset_name]
         file_name = sample[-1][0]
-        imgs = imgs_orig.cuda().float().permute(0, 3, 1, 2)          # analyze.py:66
-        points3D_net, _ = predictor(imgs.contiguous(), reproTool.cameraMatrices.cuda(),
-                                    reproTool.intrinsicMatrices.cuda(),
-                                    reproTool.distortionCoefficients.cuda())
+        calib = (reproTool.cameraMatrices.cuda(), reproTool.intrinsicMatrices.cuda(),
+                 reproTool.distortionCoefficients.cuda())
+        if frame_layout is not None:
+            points3D_net, _ = predictor.forward_surface(imgs_orig.cuda(), frame_layout, *calib)
+        else:
+            imgs = imgs_orig.cuda().float().permute(0, 3, 1, 2)          # analyze.py:66
+            points3D_net, _ = predictor(imgs.contiguous(), *calib)
         if points3D_net is not None:
             pointsNet.append(points3D_net[0].cpu().detach().numpy())
             pointsGT.append(keypoints3D)

@@ -282,6 +282,50 @@ int jh_reconstruct_point(const float* points2d_dev, const float* maxvals_dev, in
 // bytes of frame data per source pixel of a frame format (kSrc*): fp32 RGB 12, uint8 BGR 3, YUV 4:2:0 1.5
 static double frame_px_bytes(int fmt) { return fmt == kSrcRgbF32 ? 12.0 : fmt == kSrcBgrU8 ? 3.0 : 1.5; }
 
+// The one validation of a described YUV 4:2:0 surface of h x w images (include/jarvis_hip.h): every surface entry
+// point and jh_yuv_surface_check.  Host arithmetic only.  (__int128: a plane's end may not wrap for any int64 field.)
+static int yuv_surface_check(const jh_yuv_surface* sp, int h, int w) {
+  JH_REQUIRE(sp, "null jh_yuv_surface");
+  const jh_yuv_surface& q = *sp;
+  JH_REQUIRE(h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0, "YUV 4:2:0 frames need an even, positive height and width");
+  JH_REQUIRE(q.c_step == 1 || q.c_step == 2, "jh_yuv_surface.c_step must be 1 (planar) or 2 (semi-planar)");
+  JH_REQUIRE(q.y_pitch >= w, "jh_yuv_surface.y_pitch is smaller than the width");
+  JH_REQUIRE(q.c_pitch >= (int64_t)(w / 2) * q.c_step, "jh_yuv_surface.c_pitch is smaller than a chroma row");
+  JH_REQUIRE(q.y_offset >= 0 && q.u_offset >= 0 && q.v_offset >= 0 && q.image_stride >= 0,
+             "jh_yuv_surface offsets must not be negative");
+  if (q.c_step == 2) {
+    JH_REQUIRE(q.u_offset - q.v_offset == 1 || q.v_offset - q.u_offset == 1,
+               "jh_yuv_surface: semi-planar U and V are neighbouring bytes");
+    JH_REQUIRE((q.u_offset < q.v_offset ? q.u_offset : q.v_offset) % 2 == 0 && q.c_pitch % 2 == 0,
+               "jh_yuv_surface: a semi-planar chroma pair starts at an even offset and c_pitch is even");
+  }
+  const __int128 y_end = (__int128)q.y_offset + (__int128)(h - 1) * q.y_pitch + w;
+  const __int128 c_span = (__int128)(h / 2 - 1) * q.c_pitch + (__int128)(w / 2 - 1) * q.c_step + 1;
+  JH_REQUIRE(y_end <= q.image_stride && q.u_offset + c_span <= q.image_stride && q.v_offset + c_span <= q.image_stride,
+             "jh_yuv_surface: a plane ends beyond image_stride");
+  JH_REQUIRE(q.matrix == JH_YUV_BT601 || q.matrix == JH_YUV_BT709, "jh_yuv_surface.matrix: unknown");
+  JH_REQUIRE(q.range == JH_YUV_LIMITED || q.range == JH_YUV_FULL, "jh_yuv_surface.range: unknown");
+  JH_REQUIRE(q.reserved == 0, "jh_yuv_surface.reserved must be 0");
+  return 0;
+}
+
+// a checked description as the kernels take it (preprocess.h): the layout and the constants of its (matrix, range)
+static YuvSurface yuv_surface_args(const jh_yuv_surface& q) {
+  // {Y0, CY, CVR, CUB, CUG, CVG}: BT.601 limited = OpenCV's literals (yuv_to_rgb8); the others round(x * 2^20) of
+  // the float64 matrix (include/jarvis_hip.h)
+  static const int k[2][2][6] = {{{16, 1220542, 1673527, 2116026, -409993, -852492},
+                                  {0, 1048576, 1470104, 1858077, -360853, -748826}},
+                                 {{16, 1220945, 1879825, 2215014, -223607, -558796},
+                                  {0, 1048576, 1651297, 1945738, -196424, -490864}}};
+  const int* c = k[q.matrix][q.range];
+  YuvSurface a;
+  a.image_stride = q.image_stride; a.y_offset = q.y_offset; a.y_pitch = q.y_pitch;
+  a.u_offset = q.u_offset; a.v_offset = q.v_offset; a.c_pitch = q.c_pitch; a.c_step = q.c_step;
+  a.pair = q.c_step == 2 && q.image_stride % 2 == 0;
+  a.y0 = c[0]; a.cy = c[1]; a.cvr = c[2]; a.cub = c[3]; a.cug = c[4]; a.cvg = c[5];
+  return a;
+}
+
 static_assert(JH_FRAME_RGB_F32 == kSrcRgbF32 && JH_FRAME_BGR_U8 == kSrcBgrU8 && JH_FRAME_I420 == kSrcI420 &&
                   JH_FRAME_NV12 == kSrcNV12, "frame format codes of the C ABI are preprocess.h's SRC");
 
@@ -314,8 +358,14 @@ struct jh_predictor {
   const void* const* cur_cell = nullptr;     // non-null only while the forward is being captured
   float *g_points = nullptr, *g_conf = nullptr;
   hipStream_t gstream = nullptr;             // capture stream (the caller's may be the null stream)
-  // one per frame format (kSrc*, preprocess.h); [4 + fmt]: the masked form of that format
-  hipGraphExec_t gexec[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // one per frame format (kSrc*, preprocess.h); [kGraphFmts + fmt]: the masked form of that format
+  static constexpr int kGraphFmts = kSrcYuvSurface + 1;
+  hipGraphExec_t gexec[2 * kGraphFmts] = {};
+  // Described surfaces (kSrcYuvSurface).  ysurf: the description of the call under way, as the kernels take it.
+  // A launch carries it by value, so a recording has ONE layout: gsurf[plain / masked] is the description its graph
+  // was captured with, and a call with another one records again (forward_graph).
+  YuvSurface ysurf;
+  jh_yuv_surface gsurf[2] = {};
   // Camera mask (camera_mask.h).  mask_buf [T][C]: the predictor's copy of the current call's mask -- the masked
   // kernels (and a captured graph of them) read this buffer, so the mask may change from call to call.  mask_cur:
   // the mask of the call under way, nullptr = no mask (the plain kernels).  n_active / n_detect [T]: written by
@@ -485,7 +535,7 @@ static int stage_center_impl(jh_predictor* pr, const void* frames_dev, int fmt, 
   if (pr->center->stem_fusable) {
     // resize + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->center->stem_src;
-    src.mode = 1; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.fmt = fmt;
+    src.mode = 1; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.fmt = fmt; src.yuv = pr->ysurf;
     src.H = pr->cfg.img_h; src.W = pr->cfg.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = pr->cfg.mean[i]; src.stdv[i] = pr->cfg.std[i]; }
     // algorithmic bytes of the fused launch: the four bilinear taps of every network-input pixel (frame_px_bytes
@@ -494,7 +544,7 @@ static int stage_center_impl(jh_predictor* pr, const void* frames_dev, int fmt, 
   } else {
     JH_PROF("preprocess_resize", 0.0, (double)N * S * S * (4.0 * frame_px_bytes(fmt) + 3 * 4),
             launch_preprocess_resize(frames_dev, fmt, pr->center->input.p, N, pr->cfg.img_h,
-                                     pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, pr->cur_cell));
+                                     pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, pr->cur_cell, &pr->ysurf));
   }
   if (pr->center->run(s)) return 1;
   const Act& h = pr->center->heat;
@@ -545,7 +595,7 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, int fm
   if (pr->kp->stem_fusable) {
     // crop + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->kp->stem_src;
-    src.mode = 2; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.fmt = fmt;
+    src.mode = 2; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.fmt = fmt; src.yuv = pr->ysurf;
     src.center_hm = pr->chm_cur(); src.Cloc = pr->Cloc; src.C = pr->C; src.cam0 = c.cam_lo;
     src.H = c.img_h; src.W = c.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = c.mean[i]; src.stdv[i] = c.std[i]; }
@@ -553,7 +603,7 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, int fm
   } else {
     JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->Cloc * pr->B * pr->B * (frame_px_bytes(fmt) + 12.0),
             launch_preprocess_crop(frames_dev, fmt, pr->chm_cur(), pr->kp->input.p, pr->T, pr->Cloc, pr->C,
-                                   c.cam_lo, c.img_h, c.img_w, pr->B, c.mean, c.std, s, pr->cur_cell));
+                                   c.cam_lo, c.img_h, c.img_w, pr->B, c.mean, c.std, s, pr->cur_cell, &pr->ysurf));
   }
   if (pr->kp->run(s)) return 1;
   if (heat_dev && heat_dev != pr->kp->heat.p)
@@ -623,8 +673,19 @@ static int forward_eager(jh_predictor* pr, const void* frames_dev, int fmt, floa
 // submissions instead of ~150.  Calibration lives in the predictor's buffers (set_calibration
 // copies into them), weights are immutable for the life of a predictor: nothing to invalidate.
 static int forward_graph(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
-                         float* conf_dev, int32_t* valid_dev, hipStream_t s) {
-  hipGraphExec_t& exec = pr->gexec[fmt + (pr->mask_cur ? 4 : 0)];
+                         float* conf_dev, int32_t* valid_dev, hipStream_t s, const jh_yuv_surface* surface) {
+  hipGraphExec_t& exec = pr->gexec[fmt + (pr->mask_cur ? jh_predictor::kGraphFmts : 0)];
+  if (fmt == kSrcYuvSurface) {
+    // the recorded launches hold the description they were captured with: another layout records again (rare: a
+    // stream keeps its layout; the replay in flight is waited for before its executable graph goes)
+    jh_yuv_surface& rec = pr->gsurf[pr->mask_cur ? 1 : 0];
+    if (exec && memcmp(&rec, surface, sizeof(rec)) != 0) {
+      JH_CHECK_HIP(hipStreamSynchronize(s));
+      (void)hipGraphExecDestroy(exec);
+      exec = nullptr;
+    }
+    rec = *surface;
+  }
   if (!exec) {
     hipGraph_t g = nullptr;
     if (!pr->gstream) JH_CHECK_HIP(hipStreamCreateWithFlags(&pr->gstream, hipStreamNonBlocking));
@@ -651,27 +712,29 @@ static int forward_graph(jh_predictor* pr, const void* frames_dev, int fmt, floa
 }
 
 static int forward_unmasked(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
-                            float* conf_dev, int32_t* valid_dev, void* stream);
+                            float* conf_dev, int32_t* valid_dev, void* stream, const jh_yuv_surface* surface);
 
 // mask_dev != nullptr: the masked kernels, reading the predictor's copy of the mask (made here, on the caller's
 // stream, outside any graph of the predictor's own: the captured launches keep pointing at mask_buf)
 static int forward_impl(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
                         float* conf_dev, int32_t* valid_dev, void* stream,
-                        const unsigned char* mask_dev = nullptr) {
-  if (!mask_dev) return forward_unmasked(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, stream);
+                        const unsigned char* mask_dev = nullptr, const jh_yuv_surface* surface = nullptr) {
+  if (!mask_dev) return forward_unmasked(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, stream, surface);
   JH_CHECK_HIP(hipMemcpyAsync(pr->mask_buf, mask_dev, (size_t)pr->T * pr->C, hipMemcpyDeviceToDevice,
                               static_cast<hipStream_t>(stream)));
   pr->mask_cur = pr->mask_buf;
-  const int rc = forward_unmasked(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, stream);
+  const int rc = forward_unmasked(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, stream, surface);
   pr->mask_cur = nullptr;
   return rc;
 }
 
 static int forward_unmasked(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
-                            float* conf_dev, int32_t* valid_dev, void* stream) {
+                            float* conf_dev, int32_t* valid_dev, void* stream, const jh_yuv_surface* surface) {
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
   JH_REQUIRE(pr->T3 == pr->T, "forward needs time_batch_3d == time_batch");
   JH_REQUIRE(frames_dev && points_dev && conf_dev, "null frame / output pointer");
+  JH_REQUIRE((fmt == kSrcYuvSurface) == (surface != nullptr), "a described surface comes with its own frame format");
+  if (surface) pr->ysurf = yuv_surface_args(*surface);
   pr->slot = 0;                               // (the whole-path forward and its captured graph: centre set 0)
   // per-launch profiling needs the launches one by one; a caller that is itself capturing this
   // stream gets the plain launches too (its graph then holds them)
@@ -679,7 +742,8 @@ static int forward_unmasked(jh_predictor* pr, const void* frames_dev, int fmt, f
   if (pr->use_graph && !profiler().on) (void)hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs);
   if (!pr->use_graph || profiler().on || cs != hipStreamCaptureStatusNone)
     return forward_eager(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, stream);
-  return forward_graph(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, static_cast<hipStream_t>(stream));
+  return forward_graph(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, static_cast<hipStream_t>(stream),
+                       surface);
 }
 int jh_predictor_forward(jh_predictor* pr, const float* frames_dev, float* points_dev,
                          float* conf_dev, int32_t* valid_dev, void* stream) {
@@ -696,6 +760,16 @@ int jh_predictor_forward_yuv(jh_predictor* pr, const uint8_t* frames_dev, int fo
              "JH_FRAME_I420 or JH_FRAME_NV12");
   JH_REQUIRE(pr && pr->cfg.img_h % 2 == 0 && pr->cfg.img_w % 2 == 0, "YUV 4:2:0 frames need an even height and width");
   return forward_impl(pr, frames_dev, format, points_dev, conf_dev, valid_dev, stream);
+}
+
+int jh_yuv_surface_check(const jh_yuv_surface* surface, int h, int w) { return yuv_surface_check(surface, h, w); }
+
+int jh_predictor_forward_surface(jh_predictor* pr, const uint8_t* frames_dev, const jh_yuv_surface* surface,
+                                 const uint8_t* mask_dev, float* points_dev, float* conf_dev, int32_t* valid_dev,
+                                 void* stream) {
+  JH_REQUIRE(pr, "bad argument");
+  if (yuv_surface_check(surface, pr->cfg.img_h, pr->cfg.img_w)) return 1;
+  return forward_impl(pr, frames_dev, kSrcYuvSurface, points_dev, conf_dev, valid_dev, stream, mask_dev, surface);
 }
 
 int jh_predictor_forward_masked(jh_predictor* pr, const void* frames_dev, int format, const uint8_t* mask_dev,
@@ -851,7 +925,7 @@ int jh_predictor2d_create(const jh_params* center_params, const jh_params* kp_pa
 void jh_predictor2d_destroy(jh_predictor2d* pr) { delete pr; }
 
 static int forward2d_impl(jh_predictor2d* pr, const void* frames, int fmt, int32_t* points_dev,
-                          float* conf_dev, int32_t* valid_dev, void* stream) {
+                          float* conf_dev, int32_t* valid_dev, void* stream, const YuvSurface* surface = nullptr) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const auto& c = pr->cfg;
   const int S = c.center_size;
@@ -859,7 +933,7 @@ static int forward2d_impl(jh_predictor2d* pr, const void* frames, int fmt, int32
   // (These counts used to be a flat 24 B per pixel for every format: fp32 resize is 60, uint8 crop 15.)
   JH_PROF("preprocess_resize", 0.0, (double)pr->T * S * S * (4.0 * frame_px_bytes(fmt) + 12.0),
           launch_preprocess_resize(frames, fmt, pr->center->input.p, pr->T, c.img_h, c.img_w, S,
-                                   c.mean, c.std, s));
+                                   c.mean, c.std, s, nullptr, surface));
   if (pr->center->run(s)) return 1;
   const Act& h = pr->center->heat;
   JH_PROF("center_argmax", 0.0, 4.0 * pr->T * h.H * h.W,
@@ -870,7 +944,7 @@ static int forward2d_impl(jh_predictor2d* pr, const void* frames, int fmt, int32
     return 1;
   JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->B * pr->B * (frame_px_bytes(fmt) + 12.0),
           launch_preprocess_crop(frames, fmt, pr->chm, pr->kp->input.p, pr->T, 1, 1, 0, c.img_h,
-                                 c.img_w, pr->B, c.mean, c.std, s));
+                                 c.img_w, pr->B, c.mean, c.std, s, nullptr, surface));
   if (pr->kp->run(s)) return 1;
   const Act& k = pr->kp->heat;
   JH_PROF("joint_argmax", 0.0, 4.0 * pr->T * k.H * k.W * pr->J,
@@ -897,6 +971,14 @@ int jh_predictor2d_forward_yuv(jh_predictor2d* pr, const uint8_t* frames_dev, in
              "JH_FRAME_I420 or JH_FRAME_NV12");
   JH_REQUIRE(pr && pr->cfg.img_h % 2 == 0 && pr->cfg.img_w % 2 == 0, "YUV 4:2:0 frames need an even height and width");
   return forward2d_impl(pr, frames_dev, format, points_dev, conf_dev, valid_dev, stream);
+}
+
+int jh_predictor2d_forward_surface(jh_predictor2d* pr, const uint8_t* frames_dev, const jh_yuv_surface* surface,
+                                   int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
+  JH_REQUIRE(pr && frames_dev, "bad argument");
+  if (yuv_surface_check(surface, pr->cfg.img_h, pr->cfg.img_w)) return 1;
+  const YuvSurface ys = yuv_surface_args(*surface);
+  return forward2d_impl(pr, frames_dev, kSrcYuvSurface, points_dev, conf_dev, valid_dev, stream, &ys);
 }
 
 // ------------------------------------------------------------------- profiling
@@ -1022,6 +1104,16 @@ int jh_op_yuv420_to_bgr(const uint8_t* frames_dev, int format, int n, int h, int
   JH_REQUIRE(format == JH_FRAME_I420 || format == JH_FRAME_NV12, "jh_op_yuv420_to_bgr: format must be "
              "JH_FRAME_I420 or JH_FRAME_NV12");
   if (launch_yuv420_to_bgr(frames_dev, format, out_bgr_dev, n, h, w, s)) return 1;
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int jh_op_yuv_surface_to_bgr(const uint8_t* frames_dev, const jh_yuv_surface* surface, int n, int h, int w,
+                             uint8_t* out_bgr_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(frames_dev && out_bgr_dev && n >= 1, "null frame / output pointer");
+  if (yuv_surface_check(surface, h, w)) return 1;
+  if (launch_yuv_surface_to_bgr(frames_dev, yuv_surface_args(*surface), out_bgr_dev, n, h, w, s)) return 1;
   JH_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }

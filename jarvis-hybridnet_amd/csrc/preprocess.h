@@ -16,7 +16,11 @@ namespace jh {
 // SRC = 3 (NV12): the Y plane, then one interleaved [H/2][W/2][2] plane, U first.
 // A YUV pixel is converted to the BGR bytes cv2.cvtColor(COLOR_YUV2BGR_I420 / _NV12) gives
 // (yuv420_px) and those bytes enter the uint8 arithmetic unchanged.
-enum { kSrcRgbF32 = 0, kSrcBgrU8 = 1, kSrcI420 = 2, kSrcNV12 = 3 };
+// SRC = 4 (a described YUV 4:2:0 surface, jh_yuv_surface of include/jarvis_hip.h): plane offsets, pitches, the
+// chroma order and step, and the colour matrix / range come with the launch (YuvSurface below), so pitched decoder
+// surfaces, YV12 / NV21 and BT.709 / full-range streams are read in place (yuv_surface_px).
+enum { kSrcRgbF32 = 0, kSrcBgrU8 = 1, kSrcI420 = 2, kSrcNV12 = 3, kSrcYuvSurface = 4 };
+template <int SRC> constexpr bool kIsYuv = SRC == kSrcI420 || SRC == kSrcNV12 || SRC == kSrcYuvSurface;
 
 template <int SRC>
 __device__ __forceinline__ float frame_px(const void* frames, size_t n, int c, int y, int x, int H,
@@ -65,12 +69,56 @@ __device__ __forceinline__ Rgb8 yuv420_px(const void* frames, size_t n, int y, i
   return yuv_to_rgb8(Y, U, V);
 }
 
+// A described surface as the kernels take it: the layout of a jh_yuv_surface the host has checked
+// (jh_yuv_surface_check) and the fixed-point constants of its (matrix, range).  Passed BY VALUE in the kernel
+// arguments: every field is wave-uniform and stays in scalar registers.
+struct YuvSurface {
+  long long image_stride = 0, y_offset = 0, y_pitch = 0, u_offset = 0, v_offset = 0, c_pitch = 0;
+  int c_step = 1;
+  int pair = 0;                // c_step == 2 and image_stride even: U, V of a block in one aligned 2-byte load
+  int y0 = 16, cy = 0, cvr = 0, cub = 0, cug = 0, cvg = 0;
+};
+
+// yuv_to_rgb8 with the constants of the surface's (matrix, range): the same scheme, int32 throughout (every
+// partial sum of the four constant rows stays below 2^30, tests/test_yuv_surface_cpu.py)
+__host__ __device__ __forceinline__ Rgb8 yuv_to_rgb8(int Y, int U, int V, const YuvSurface& s) {
+  constexpr int SHIFT = 20, HALF = 1 << (SHIFT - 1);
+  const int u = U - 128, v = V - 128;
+  const int yy = (Y > s.y0 ? Y - s.y0 : 0) * s.cy + HALF;
+  const auto clamp8 = [](int x) { return x < 0 ? 0 : (x > 255 ? 255 : x); };
+  return Rgb8{clamp8((yy + s.cvr * v) >> SHIFT), clamp8((yy + s.cvg * v + s.cug * u) >> SHIFT),
+              clamp8((yy + s.cub * u) >> SHIFT)};
+}
+
+// pixel (y, x) of image n of a described surface (SRC 4): one Y load and, for the 2 x 2 block's chroma, one
+// 2-byte load (semi-planar, when the pair is 2-byte aligned: a wave-uniform choice) or the U and the V byte.
+// 64-bit offsets: image_stride * n passes 2^31 at batch scale.  Only plane bytes are ever addressed.
+__device__ __forceinline__ Rgb8 yuv_surface_px(const void* frames, size_t n, int y, int x, const YuvSurface& s) {
+  const unsigned char* img = static_cast<const unsigned char*>(frames) + (long long)n * s.image_stride;
+  const int Y = img[s.y_offset + (long long)y * s.y_pitch + x];
+  const long long crow = (long long)(y >> 1) * s.c_pitch;
+  int U, V;
+  if (s.pair && !(reinterpret_cast<uintptr_t>(frames) & 1)) {
+    const bool u_first = s.u_offset < s.v_offset;
+    const unsigned short uv = *reinterpret_cast<const unsigned short*>(
+        img + (u_first ? s.u_offset : s.v_offset) + crow + (x & ~1));
+    U = u_first ? uv & 0xff : uv >> 8; V = u_first ? uv >> 8 : uv & 0xff;
+  } else {
+    const long long c = crow + (long long)(x >> 1) * s.c_step;
+    U = img[s.u_offset + c]; V = img[s.v_offset + c];
+  }
+  return yuv_to_rgb8(Y, U, V, s);
+}
+
 // the three channels (r, g, b) of one pixel as the uint8 path scales them; YUV: one conversion
-// for all three channels
+// for all three channels (ys: the surface of SRC 4, unused by the other formats)
 template <int SRC>
-__device__ __forceinline__ void frame_px3(const void* frames, size_t n, int y, int x, int H, int W, float v[3]) {
-  if constexpr (SRC == kSrcI420 || SRC == kSrcNV12) {
-    const Rgb8 p = yuv420_px<SRC>(frames, n, y, x, H, W);
+__device__ __forceinline__ void frame_px3(const void* frames, size_t n, int y, int x, int H, int W,
+                                          const YuvSurface& ys, float v[3]) {
+  if constexpr (kIsYuv<SRC>) {
+    Rgb8 p;
+    if constexpr (SRC == kSrcYuvSurface) p = yuv_surface_px(frames, n, y, x, ys);
+    else p = yuv420_px<SRC>(frames, n, y, x, H, W);
     const float k = __fdiv_rn(1.f, 255.f);
     v[0] = __fmul_rn((float)p.r, k); v[1] = __fmul_rn((float)p.g, k); v[2] = __fmul_rn((float)p.b, k);
   } else {
@@ -83,7 +131,7 @@ __device__ __forceinline__ void frame_px3(const void* frames, size_t n, int y, i
 // align_corners = False, no antialias), then (x - mean) / std; (r, g, b, 0)
 template <int SRC>
 __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, int ox, int H, int W, float sy,
-                                            float sx, float3 mean, float3 stdv) {
+                                            float sx, float3 mean, float3 stdv, const YuvSurface& ys) {
   float ry = fmaxf(__fsub_rn(__fmul_rn(sy, __fadd_rn((float)oy, 0.5f)), 0.5f), 0.f);
   float rx = fmaxf(__fsub_rn(__fmul_rn(sx, __fadd_rn((float)ox, 0.5f)), 0.5f), 0.f);
   int y0 = min((int)floorf(ry), H - 1), x0 = min((int)floorf(rx), W - 1);
@@ -95,14 +143,14 @@ __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, i
   // YUV: each of the four taps is converted once for all three channels (the per-channel arithmetic
   // below is that of the uint8 path, so the result equals SRC 1 on the converted bytes bit for bit)
   float q00[3], q01[3], q10[3], q11[3];
-  if constexpr (SRC == kSrcI420 || SRC == kSrcNV12) {
-    frame_px3<SRC>(frames, n, y0, x0, H, W, q00); frame_px3<SRC>(frames, n, y0, x1, H, W, q01);
-    frame_px3<SRC>(frames, n, y1, x0, H, W, q10); frame_px3<SRC>(frames, n, y1, x1, H, W, q11);
+  if constexpr (kIsYuv<SRC>) {
+    frame_px3<SRC>(frames, n, y0, x0, H, W, ys, q00); frame_px3<SRC>(frames, n, y0, x1, H, W, ys, q01);
+    frame_px3<SRC>(frames, n, y1, x0, H, W, ys, q10); frame_px3<SRC>(frames, n, y1, x1, H, W, ys, q11);
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     float p00, p01, p10, p11;
-    if constexpr (SRC == kSrcI420 || SRC == kSrcNV12) {
+    if constexpr (kIsYuv<SRC>) {
       p00 = q00[c]; p01 = q01[c]; p10 = q10[c]; p11 = q11[c];
     } else {
       p00 = frame_px<SRC>(frames, n, c, y0, x0, H, W); p01 = frame_px<SRC>(frames, n, c, y0, x1, H, W);
@@ -121,16 +169,16 @@ __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, i
 // crop centre is clamped; kept for safety as the stand-alone kernel has it)
 template <int SRC>
 __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int cy, int oy, int ox, int H,
-                                          int W, int B, float3 mean, float3 stdv) {
+                                          int W, int B, float3 mean, float3 stdv, const YuvSurface& ys) {
   const int hw = B / 2;
   const int ix = cx - hw + ox, iy = cy - hw + oy;
   const float mv[3] = {mean.x, mean.y, mean.z}, sv[3] = {stdv.x, stdv.y, stdv.z};
   float r[3];
   const bool ok = ix >= 0 && ix < W && iy >= 0 && iy < H;
-  if constexpr (SRC == kSrcI420 || SRC == kSrcNV12) {
+  if constexpr (kIsYuv<SRC>) {
     // (outside the frame: 0 before the normalisation, as for the other formats -- not the conversion of Y = U = V = 0)
     float q[3] = {0.f, 0.f, 0.f};
-    if (ok) frame_px3<SRC>(frames, n, iy, ix, H, W, q);
+    if (ok) frame_px3<SRC>(frames, n, iy, ix, H, W, ys, q);
 #pragma unroll
     for (int c = 0; c < 3; ++c) r[c] = __fdiv_rn(__fsub_rn(q[c], mv[c]), sv[c]);
   } else {
@@ -149,6 +197,7 @@ struct StemSource {
   const void* frames = nullptr;
   const void* const* frames_cell = nullptr;    // graph replays: the frame pointer of the current call
   int fmt = 0;                                 // frame format: SRC of preprocess.h (kSrc*)
+  YuvSurface yuv;                              // fmt == kSrcYuvSurface: the surface the frames are read through
   const int* center_hm = nullptr;              // crop: [T][C][2]
   int Cloc = 0, C = 0, cam0 = 0;               // crop: image n = (t, local camera)
   int H = 0, W = 0;                            // frame size

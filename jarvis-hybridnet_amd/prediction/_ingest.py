@@ -277,13 +277,21 @@ def host_outputs(ring, slot, outs):
     return host
 
 
-def driver_format(frame_format, frame_spec, ndim):
+def driver_format(frame_format, frame_spec, ndim, frame_layout=None):
     """The drivers' frame_format argument checked: True for the YUV 4:2:0 formats, False for 'bgr' (the frames'
     dtype then decides between uint8 BGR and fp32 RGB, as without the argument); ValueError for anything else and
-    for a YUV `frame_spec` that is no ((..., 3H/2, W), uint8) with H and W even."""
+    for a YUV `frame_spec` that is no ((..., 3H/2, W), uint8) with H and W even.  frame_layout (a YuvSurface, or
+    None) is checked with it: not together with 'i420' / 'nv12', and its `frame_spec` is ((..., image_stride), uint8)
+    with one dimension less."""
     from .. import _native as N
     if frame_format not in N.FRAME_FORMATS:
         raise ValueError("frame_format must be one of %s, got %r" % (sorted(N.FRAME_FORMATS), frame_format))
+    if N.frame_layout(frame_layout, frame_format, ()) is not None and frame_spec is not None:
+        shape, dtype = tuple(frame_spec[0]), frame_spec[1]
+        if len(shape) != ndim - 1 or dtype != torch.uint8 or shape[-1] != frame_layout.image_stride:
+            raise ValueError("frame_spec of YuvSurface frames must be (%s, torch.uint8) with image_stride = %d; got %r"
+                             % ("(C, image_stride)" if ndim == 3 else "(image_stride,)", frame_layout.image_stride,
+                                frame_spec))
     yuv = frame_format in N.YUV_FORMATS
     if yuv and frame_spec is not None:
         shape, dtype = tuple(frame_spec[0]), frame_spec[1]
@@ -294,21 +302,28 @@ def driver_format(frame_format, frame_spec, ndim):
     return yuv
 
 
-def check_driver_frames(frames, frame_format, ndim):
+def check_driver_frames(frames, frame_format, ndim, frame_layout=None):
     """One YUV 4:2:0 frame (set) handed to a driver: `ndim`-d uint8 (..., 3H/2, W) with H, W even, or ValueError
-    (the bytes would be misread)."""
+    (the bytes would be misread).  With a frame_layout: (ndim - 1)-d uint8 (..., image_stride)."""
     from .. import _native as N
     dtype = frames.dtype if torch.is_tensor(frames) else torch.from_numpy(np.empty(0, frames.dtype)).dtype
+    if frame_layout is not None:
+        if len(frames.shape) != ndim - 1 or dtype != torch.uint8 or frames.shape[-1] != frame_layout.image_stride:
+            raise ValueError("YuvSurface frames must be uint8 %s with image_stride = %d; got %s %s" % (
+                "(C, image_stride)" if ndim == 3 else "(image_stride,)", frame_layout.image_stride, dtype,
+                tuple(frames.shape)))
+        return
     if len(frames.shape) != ndim or dtype != torch.uint8:
         raise ValueError("%s frames must be uint8 %s; got %s %s" % (
             frame_format, "(C, 3H/2, W)" if ndim == 3 else "(3H/2, W)", dtype, tuple(frames.shape)))
     N.yuv_frame_hw(frames.shape)
 
 
-def pipeline_for(owner, frames, time_batch, streams, submit, emit, frame_spec=None):
+def pipeline_for(owner, frames, time_batch, streams, submit, emit, frame_spec=None, frame_layout=None):
     """The pipeline for frame sets shaped like `frames` (or like `frame_spec` = (shape, torch dtype) when
     `frames` is a fill callable), cached on `owner` (the predictor) so that its pinned buffers are re-used by
-    later driver calls."""
+    later driver calls.  frame_layout: the YuvSurface of the run, part of the cache key (the staging buffers are
+    (C, image_stride) bytes of THAT layout)."""
     if torch.is_tensor(frames) and frames.is_cuda:
         return DevicePipeline(time_batch, submit, emit, streams)
     if callable(frames):
@@ -320,7 +335,7 @@ def pipeline_for(owner, frames, time_batch, streams, submit, emit, frame_spec=No
         shape, dtype = tuple(a.shape), torch.from_numpy(np.empty(0, a.dtype)).dtype
     device = "cuda" if torch.cuda.is_available() else None
     cache = owner.__dict__.setdefault("_ingest_cache", {})
-    key = (shape, dtype, int(time_batch), int(streams), device)
+    key = (shape, dtype, int(time_batch), int(streams), device, frame_layout)
     pipe = cache.get(key)
     if pipe is None:
         # ONE cached pipeline per predictor: another frame format / time batch / stream count replaces it (an entry

@@ -30,11 +30,18 @@ class _Native2D:
         N.check(N.lib().jh_predictor2d_create(pc.handle, pk.handle, ctypes.byref(c),
                                               ctypes.byref(self.handle)))
 
-    def forward(self, frames, frame_format=None):
+    def forward(self, frames, frame_format=None, frame_layout=None):
         dev = frames.device
         pts = torch.empty((self.T, self.J, 2), device=dev, dtype=torch.int32)
         conf = torch.empty((self.T, self.J), device=dev)
         valid = torch.empty((self.T,), device=dev, dtype=torch.int32)
+        if frame_layout is not None:
+            N.frame_layout(frame_layout, frame_format, (self.T,), (self.H, self.W), frames)
+            if not (frames.is_cuda and frames.is_contiguous()):
+                raise RuntimeError("frames must be a contiguous CUDA (HIP) tensor")
+            N.check(N.lib().jh_predictor2d_forward_surface(self.handle, N.ptr(frames), frame_layout.struct(),
+                                                           N.ptr(pts), N.ptr(conf), N.ptr(valid), N.stream()))
+            return pts, conf, valid
         if frame_format in N.YUV_FORMATS:
             if tuple(frames.shape) != (self.T, self.H * 3 // 2, self.W) or frames.dtype != torch.uint8 \
                     or not frames.is_contiguous():
@@ -82,9 +89,11 @@ class JarvisPredictor2D(nn.Module):
                                           batch, self.precision)
         return self._native[key]
 
-    def forward(self, img):
+    def forward(self, img, frame_layout=None):
         """img (1,3,H,W) RGB in [0,1] -> (points2D (J,2) int64 pixels, confidences (J,))
-        or (None, None)."""
+        or (None, None).  frame_layout: a YuvSurface -- img is forward_surface's."""
+        if frame_layout is not None:
+            return self.forward_surface(img, frame_layout)
         x = N.dev(img)
         pts, conf, valid = self.native(x.shape[2], x.shape[3], x.shape[0]).forward(x)
         if int(valid[0].item()) == 0:               # jarvis2D.py:121,150-153
@@ -104,11 +113,28 @@ class JarvisPredictor2D(nn.Module):
             return None, None
         return pts[0].long(), conf[0]
 
-    def forward_batch(self, imgs, frame_format=None):
+    def forward_surface(self, img, surface):
+        """img (image_stride,) or (1,image_stride) uint8: one YUV 4:2:0 image read through the YuvSurface `surface`
+        (see JarvisPredictor3D.forward_surface) -> (points2D (J,2) int64 pixels, confidences (J,)) or (None, None)."""
+        from .jarvis3D import _need_surface
+        if torch.is_tensor(img) and img.dim() == 1:
+            img = img.unsqueeze(0)
+        N.frame_layout(_need_surface(surface), None, (1,), None, img)
+        x = N.dev(img, torch.uint8)
+        pts, conf, valid = self.native(surface.height, surface.width, 1).forward(x, frame_layout=surface)
+        if int(valid[0].item()) == 0:
+            return None, None
+        return pts[0].long(), conf[0]
+
+    def forward_batch(self, imgs, frame_format=None, frame_layout=None):
         """imgs (T,3,H,W) fp32 RGB or (T,H,W,3) uint8 BGR, independent images ->
         points2D (T,J,2) int32, confidences (T,J), valid (T) int32; no host sync.  frame_format 'i420' / 'nv12':
-        imgs (T,3H/2,W) uint8 YUV 4:2:0; 'bgr': uint8 BGR required; None: the dtype decides."""
+        imgs (T,3H/2,W) uint8 YUV 4:2:0; 'bgr': uint8 BGR required; None: the dtype decides.  frame_layout: a
+        YuvSurface -- imgs (T,image_stride) uint8 (forward_surface); not together with 'i420' / 'nv12'."""
         frame_format = N.frame_format(frame_format)
+        if N.frame_layout(frame_layout, frame_format, (None,), None, imgs) is not None:
+            x = N.dev(imgs, torch.uint8)
+            return self.native(frame_layout.height, frame_layout.width, x.shape[0]).forward(x, frame_layout=frame_layout)
         if frame_format in N.YUV_FORMATS:
             from .jarvis3D import _yuv_frames
             x = _yuv_frames(imgs, frame_format, 3)

@@ -196,8 +196,23 @@ class JarvisPredictor3D(nn.Module):
         return self._single(pr, pr.forward(x.unsqueeze(0), frame_format=frame_format, camera_mask=mask), mask,
                             return_2d)
 
+    def forward_surface(self, frames, surface, cameraMatrices, intrinsicMatrices, distortionCoefficients,
+                        camera_mask=None, return_2d=False):
+        """frames (C,image_stride) uint8: one YUV 4:2:0 image per camera, read in place through the YuvSurface
+        `surface` (pitched decoder surfaces, I420 / YV12 / NV12 / NV21, BT.601 / BT.709, limited / full range).
+        Same result, bit for bit, as forward_uint8 on the BGR bytes the surface's conversion gives
+        (include/jarvis_hip.h); bytes outside the planes are never read.
+        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d: as forward()."""
+        mask = self._frame_mask(camera_mask)
+        N.frame_layout(_need_surface(surface), None, (self.num_cameras,), None, frames)
+        check_native_seam(self)
+        x = N.dev(frames, torch.uint8)
+        pr = self.native(surface.height, surface.width)
+        pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
+        return self._single(pr, pr.forward(x.unsqueeze(0), camera_mask=mask, frame_layout=surface), mask, return_2d)
+
     def forward_batch(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
-                      camera_mask=None, return_2d=False):
+                      camera_mask=None, return_2d=False, frame_layout=None):
         """Throughput form: imgs (T,C,3,H,W) fp32 RGB or (T,C,H,W,3) uint8 BGR,
         independent time steps -> points (T,J,3), confidences (T,J), valid (T) int32;
         no host synchronisation.  frame_format 'i420' / 'nv12': imgs (T,C,3H/2,W) uint8 YUV 4:2:0 (see
@@ -206,12 +221,22 @@ class JarvisPredictor3D(nn.Module):
         a row with fewer than two cameras gives valid[t] = 0.  Rows are independent: a frame set's result depends on
         its own mask row only.  None: all cameras.
         return_2d: the per-camera `Views2D` of the batch (leading dimension T; see forward()) follows `valid`:
-        (points, confidences, valid, views).  Rows of invalid frames: used 0, points2D -1, NaN reprojections."""
+        (points, confidences, valid, views).  Rows of invalid frames: used 0, points2D -1, NaN reprojections.
+        frame_layout: a YuvSurface -- imgs (T,C,image_stride) uint8, see forward_surface; not together with
+        frame_format 'i420' / 'nv12'."""
         frame_format = N.frame_format(frame_format)
+        frame_layout = N.frame_layout(frame_layout, frame_format, (None, self.num_cameras), None, imgs)
         if camera_mask is not None:
             if not torch.is_tensor(imgs) or imgs.dim() < 1:
                 raise ValueError("imgs must be a tensor of time steps")
             camera_mask = N.camera_mask(camera_mask, (imgs.shape[0], self.num_cameras))
+        if frame_layout is not None:
+            check_native_seam(self)
+            x = N.dev(imgs, torch.uint8)
+            pr = self.native(frame_layout.height, frame_layout.width, time_batch=x.shape[0])
+            pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
+            return self._batch(pr, pr.forward(x, camera_mask=camera_mask, frame_layout=frame_layout), camera_mask,
+                               return_2d)
         if frame_format in N.YUV_FORMATS:
             x = _yuv_frames(imgs, frame_format, 4)
             check_native_seam(self)
@@ -236,6 +261,14 @@ class JarvisPredictor3D(nn.Module):
     @staticmethod
     def _batch(pr, res, mask, return_2d):
         return tuple(res) + (pr.views2d(res[0], camera_mask=mask),) if return_2d else res
+
+
+def _need_surface(surface):
+    """The direct forms' `surface` argument: a YuvSurface, not None."""
+    from ..yuv_surface import YuvSurface
+    if not isinstance(surface, YuvSurface):
+        raise ValueError("surface must be a YuvSurface, got %r" % (type(surface).__name__,))
+    return surface
 
 
 def _yuv_frames(frames, frame_format, ndim):

@@ -54,7 +54,7 @@ def frame_row(points2D, confidences, num_joints):
 
 
 def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch=1,
-                     csv_name="data2D.csv", frame_spec=None, frame_format="bgr"):
+                     csv_name="data2D.csv", frame_spec=None, frame_format="bgr", frame_layout=None):
     """Run `predictor` (JarvisPredictor2D) over an iterable of frames -- (H,W,3) uint8 BGR arrays
     / tensors exactly as cv2 delivers them, or (3,H,W) fp32 RGB -- and write `csv_name`
     (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -71,9 +71,12 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
 
     frame_format 'i420' / 'nv12': the frames are (3H/2,W) uint8 YUV 4:2:0 (H, W even; fill callables with
     `frame_spec=((3H/2,W), torch.uint8)`), see predict3D_frames.  Anything but 'bgr' (the default), 'i420' and
-    'nv12' raises ValueError."""
+    'nv12' raises ValueError.
+
+    frame_layout: a YuvSurface -- the frames are (image_stride,) uint8 described YUV 4:2:0 surfaces (fill callables
+    with `frame_spec=((image_stride,), torch.uint8)`), see predict3D_frames; not together with 'i420' / 'nv12'."""
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
-    yuv = driver_format(frame_format, frame_spec, 2)
+    yuv = driver_format(frame_format, frame_spec, 2, frame_layout)
     from .predict3D import _as_host
     os.makedirs(output_dir, exist_ok=True)
     if params is not None:
@@ -100,7 +103,10 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
         def submit(x, slot):
             # the reference driver's own conversion of uint8 frames (predict2D.py:93-94) is what the
             # uint8 entry point fuses into the resize / crop kernels
-            res = predictor.forward_batch(x, frame_format=frame_format) if yuv else predictor.forward_batch(x)
+            if frame_layout is not None:
+                res = predictor.forward_batch(x, frame_layout=frame_layout)
+            else:
+                res = predictor.forward_batch(x, frame_format=frame_format) if yuv else predictor.forward_batch(x)
             ev = None
             if x.is_cuda:
                 res = host_outputs(ring, slot, res)
@@ -113,15 +119,16 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
             for frame in frames:
                 if not callable(frame):
                     frame = frame if torch.is_tensor(frame) and frame.is_cuda else _as_host(frame)
-                    if yuv:
-                        check_driver_frames(frame, frame_format, 2)
+                    if yuv or frame_layout is not None:
+                        check_driver_frames(frame, frame_format, 2, frame_layout)
                     k = (frame.dtype, tuple(frame.shape), torch.is_tensor(frame))
                 else:
                     k = key if key is not None else ("fill",)
                 if pipe is None or k != key:
                     if pipe is not None:
                         n += pipe.finish()
-                    pipe, key = pipeline_for(predictor, frame, time_batch, 1, submit, emit, frame_spec), k
+                    pipe, key = pipeline_for(predictor, frame, time_batch, 1, submit, emit, frame_spec,
+                                             frame_layout), k
                 pipe.push(frame)
             if pipe is not None:
                 n += pipe.finish()
@@ -132,14 +139,16 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
     return n
 
 
-def predict2D_recordings(predictor, recordings, cfg, output_dir, params=None, time_batch=1):
+def predict2D_recordings(predictor, recordings, cfg, output_dir, params=None, time_batch=1, frame_layout=None):
     """`recordings`: {recording path: iterable of frames}.  One CSV per recording, named as the
     reference names them: `data2D.csv` for a single file, `<video>_data2D.csv` per video of a
-    directory (predict2D.py:49-68).  Returns {csv file name: number of frames}."""
+    directory (predict2D.py:49-68).  Returns {csv file name: number of frames}.  frame_layout: the YuvSurface of
+    every recording's frames (predict2D_frames), or None."""
+    kw = {} if frame_layout is None else {"frame_layout": frame_layout}
     multiple = len(recordings) > 1 or bool(getattr(params, "multiple_videos", False))
     done = {}
     for i, (path, frames) in enumerate(recordings.items()):
         name = csv_filename(path, multiple)
         done[name] = predict2D_frames(predictor, frames, cfg, output_dir, params if i == 0 else None,
-                                      time_batch, name)
+                                      time_batch, name, **kw)
     return done

@@ -92,7 +92,8 @@ def create_header_reprojection_error(writer, cfg, camera_names):
 
 def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                      distortionCoefficients, cfg, output_dir, params=None, time_batch=1, streams=1,
-                     frame_spec=None, frame_format="bgr", camera_mask=None, output_2d=False, camera_names=None):
+                     frame_spec=None, frame_format="bgr", camera_mask=None, output_2d=False, camera_names=None,
+                     frame_layout=None):
     """Run `predictor` over an iterable of multi-view frame sets -- (C,H,W,3) uint8 BGR
     arrays / tensors exactly as cv2 delivers them, or (C,3,H,W) fp32 RGB -- and write
     data3D.csv (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -126,6 +127,12 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     the bytes of BGR to stage and upload, converted inside the resize / crop kernels (JarvisPredictor3D.forward_yuv).
     The default 'bgr' is the behaviour described above.  Anything else raises ValueError.
 
+    frame_layout: a YuvSurface -- the frame sets are (C, image_stride) uint8, one described YUV 4:2:0 surface per
+    camera (pitched decoder output, I420 / YV12 / NV12 / NV21, BT.601 / BT.709, limited / full range; fill callables
+    with `frame_spec=((C, image_stride), torch.uint8)`; device-resident frame sets likewise), read in place
+    (JarvisPredictor3D.forward_surface).  Not together with frame_format 'i420' / 'nv12': ValueError.  The
+    predictor is given `frame_layout=` only when it is set here.
+
     camera_mask: a (C,) bool / integer mask for the whole run (the reference's `cameras_to_use` subset: the rows
     are those of a predictor built for the unmasked cameras alone, fed their frames and calibration), or an iterable
     that yields one (C,) mask -- or None for all cameras -- per frame set, consumed in step with `frame_sets` (a
@@ -146,7 +153,7 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     The two agree wherever the crops cover the subject; they are not bit-equal."""
     import contextlib
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
-    yuv = driver_format(frame_format, frame_spec, 3)
+    yuv = driver_format(frame_format, frame_spec, 3, frame_layout)
     run_mask, mask_iter = None, None
     if camera_mask is not None:
         C = cfg.HYBRIDNET.NUM_CAMERAS
@@ -203,8 +210,12 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             kw = {} if mask is None else {"camera_mask": mask}
             if output_2d:
                 kw["return_2d"] = True
+            if frame_layout is not None:
+                kw["frame_layout"] = frame_layout
             if hasattr(predictor, "native_streams"):
-                if yuv:
+                if frame_layout is not None:
+                    h, w = frame_layout.height, frame_layout.width
+                elif yuv:
                     h, w = N.yuv_frame_hw(x.shape)
                 else:
                     h, w = (x.shape[2], x.shape[3]) if x.dtype == torch.uint8 else (x.shape[3], x.shape[4])
@@ -238,15 +249,16 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                     mask = None if mask is None else N.camera_mask(mask, (C,)).cpu()
                 if not callable(frames):
                     frames = frames if torch.is_tensor(frames) and frames.is_cuda else _as_host(frames)
-                    if yuv:
-                        check_driver_frames(frames, frame_format, 3)
+                    if yuv or frame_layout is not None:
+                        check_driver_frames(frames, frame_format, 3, frame_layout)
                     k = (frames.dtype, tuple(frames.shape), torch.is_tensor(frames))
                 else:
                     k = key if key is not None else ("fill",)
                 if pipe is None or k != key:                        # first frame set, or a new frame format
                     if pipe is not None:
                         n += pipe.finish()
-                    pipe, key = pipeline_for(predictor, frames, time_batch, streams, submit, emit, frame_spec), k
+                    pipe, key = pipeline_for(predictor, frames, time_batch, streams, submit, emit, frame_spec,
+                                             frame_layout), k
                 pipe.push(frames) if mask is None else pipe.push(frames, mask)
             if mask_iter is not None and next(mask_iter, _end) is not _end:
                 raise ValueError("camera_mask yielded more masks than there are frame sets")

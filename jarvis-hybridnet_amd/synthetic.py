@@ -204,3 +204,46 @@ def bgr_to_yuv420(bgr, fmt):
 
     q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)  # noqa: E731
     return pack_yuv420(q(y), q(pool(u)), q(pool(v)), fmt)
+
+
+def pack_yuv_surface(y, u, v, surface, fill=0):
+    """Planes Y (..., H, W), U and V (..., H/2, W/2) uint8 -> (..., image_stride) uint8 laid out as the YuvSurface
+    `surface` describes; every byte that belongs to no plane (pitch padding, the rows between the planes, the gap up
+    to image_stride) is `fill`."""
+    y, u, v = np.asarray(y, np.uint8), np.asarray(u, np.uint8), np.asarray(v, np.uint8)
+    s, lead = surface, y.shape[:-2]
+    H, W = s.height, s.width
+    if y.shape[-2:] != (H, W) or u.shape != lead + (H // 2, W // 2) or v.shape != u.shape:
+        raise ValueError("planes %s / %s / %s do not fit a %d x %d surface" % (y.shape, u.shape, v.shape, H, W))
+    out = np.full(lead + (s.image_stride,), fill, np.uint8)
+
+    def put(plane, offset, pitch, step):
+        rows, cols = plane.shape[-2:]
+        idx = offset + np.arange(rows)[:, None] * pitch + np.arange(cols)[None, :] * step
+        out[..., idx.reshape(-1)] = plane.reshape(lead + (-1,))
+
+    put(y, s.y_offset, s.y_pitch, 1)
+    put(u, s.u_offset, s.c_pitch, s.c_step)
+    put(v, s.v_offset, s.c_pitch, s.c_step)
+    return out
+
+
+def bgr_to_yuv(bgr, matrix="bt601", range="limited"):
+    """uint8 BGR (..., H, W, 3), H and W even -> planes (Y (..., H, W), U, V (..., H/2, W/2)) uint8: the forward
+    transform of `matrix` ('bt601' | 'bt709') and `range` ('limited' | 'full') in float64, rounded and clamped, with
+    2 x 2 chroma means (test data: a frame decoded with the matching matrix looks like the original; only the
+    inverse is a contract)."""
+    kr, kb = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}[matrix]
+    sy, sc, y0 = {"limited": (219.0 / 255.0, 224.0 / 255.0, 16.0), "full": (1.0, 1.0, 0.0)}[range]
+    x = np.asarray(bgr, np.float64)
+    b, g, r = x[..., 0], x[..., 1], x[..., 2]
+    luma = kr * r + (1.0 - kr - kb) * g + kb * b
+    y = y0 + sy * luma
+    u = 128.0 + sc * (b - luma) / (2.0 * (1.0 - kb))
+    v = 128.0 + sc * (r - luma) / (2.0 * (1.0 - kr))
+
+    def pool(p):
+        return 0.25 * (p[..., 0::2, 0::2] + p[..., 0::2, 1::2] + p[..., 1::2, 0::2] + p[..., 1::2, 1::2])
+
+    q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)  # noqa: E731
+    return q(y), q(pool(u)), q(pool(v))
