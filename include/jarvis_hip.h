@@ -288,6 +288,47 @@ int jh_predictor_forward_surface(jh_predictor* pr, const uint8_t* frames_dev, co
                                  const uint8_t* mask_dev, float* points_dev, float* conf_dev, int32_t* valid_dev,
                                  void* stream);
 
+/* Raw sensor frames (ABI v4, additive): one byte per pixel as a machine-vision camera (GenICam Mono8, BayerRG8 and
+ * its siblings) delivers it, a third of the bytes of uint8 BGR, demosaiced inside the resize / crop kernels.  A
+ * jh_sensor_surface says where ONE h x w image lies inside `image_stride` bytes: raw(y, x) at
+ * offset + y * pitch + x; frames are (T,cam_n) such images back to back (the 2D predictor: (T)).  Bytes that are no
+ * sample (pitch padding, the bytes before `offset`, the gap up to image_stride) may hold anything: never read.
+ * `pattern` names the top-left 2 x 2 cell:
+ *   JH_SENSOR_MONO: one grey byte per pixel, R = G = B = the byte;
+ *   JH_SENSOR_RGGB (R G / G B): red at (even y, even x);   JH_SENSOR_BGGR (B G / G R): blue at (even y, even x);
+ *   JH_SENSOR_GRBG (G R / B G): red at (even y, odd x);    JH_SENSOR_GBRG (G B / R G): blue at (even y, odd x).
+ * Bilinear demosaic, integer arithmetic.  Interior pixel (1 <= y <= h-2, 1 <= x <= w-2), N S E W and NW NE SW SE its
+ * neighbouring bytes:
+ *   at a red or blue site: its own colour is the byte, green = (N + S + E + W + 2) >> 2, the opposite colour
+ *     = (NW + NE + SW + SE + 2) >> 2;
+ *   at a green site: green is the byte, the colour whose samples lie left and right = (W + E + 1) >> 1, the colour
+ *     whose samples lie above and below = (N + S + 1) >> 1.
+ * A border pixel (y in {0, h-1} or x in {0, w-1}) takes the RGB of the interior pixel (clamp(y, 1, h-2),
+ * clamp(x, 1, w-2)): clamp first, then demosaic, so no byte outside the h x w samples is addressed.  No white
+ * balance, gamma or colour correction: the bytes are taken as the camera delivers them.  The (R, G, B) bytes then
+ * take the uint8 path unchanged: the result equals, bit for bit, jh_predictor_forward_u8 on the converted frames.
+ * jh_sensor_surface_check (no GPU needed) is the validation every entry point applies: h, w positive; pattern
+ * known; for a Bayer pattern h, w even and >= 4; pitch >= w; offset >= 0; offset + (h-1) * pitch + w <=
+ * image_stride; reserved 0.  Returns 0, or nonzero with jh_last_error() set.
+ * jh_predictor_forward_sensor: mask_dev as in jh_predictor_forward_masked, or NULL; jh_predictor_views2d follows it
+ * as it follows any forward.  A graph-replaying predictor keeps one captured graph for this form (and one for its
+ * masked form); a call whose description differs from the recorded one records again. */
+#define JH_SENSOR_MONO 0
+#define JH_SENSOR_RGGB 1
+#define JH_SENSOR_BGGR 2
+#define JH_SENSOR_GRBG 3
+#define JH_SENSOR_GBRG 4
+typedef struct jh_sensor_surface {
+  int64_t image_stride;        /* bytes from image n to image n+1 (n = t * cameras + c) */
+  int64_t offset, pitch;       /* raw(y, x) at offset + y * pitch + x */
+  int32_t pattern;             /* JH_SENSOR_* */
+  int32_t reserved;            /* 0 */
+} jh_sensor_surface;
+int jh_sensor_surface_check(const jh_sensor_surface* surface, int h, int w);
+int jh_predictor_forward_sensor(jh_predictor* pr, const uint8_t* frames_dev, const jh_sensor_surface* surface,
+                                const uint8_t* mask_dev, float* points_dev, float* conf_dev, int32_t* valid_dev,
+                                void* stream);
+
 /* Integer path of the last call, for parity tests: center3d float (T,3),
  * center3d int (T,3), center_hm (T,C,2), det (T,C,3).  Any pointer may be NULL. */
 int jh_predictor_debug(jh_predictor* pr, float* center3d_f_dev, int32_t* center3d_i_dev,
@@ -384,6 +425,9 @@ int jh_predictor2d_forward_yuv(jh_predictor2d* pr, const uint8_t* frames_dev, in
 /* frames (T) images of a described surface (as jh_predictor_forward_surface). */
 int jh_predictor2d_forward_surface(jh_predictor2d* pr, const uint8_t* frames_dev, const jh_yuv_surface* surface,
                                    int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
+/* frames (T) raw sensor images (as jh_predictor_forward_sensor). */
+int jh_predictor2d_forward_sensor(jh_predictor2d* pr, const uint8_t* frames_dev, const jh_sensor_surface* surface,
+                                  int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
 
 /* ---- per-launch timing (HIP events on the launch stream; used by bench.py for
  * the roofline figures).  begin() switches recording on for every kernel the
@@ -421,6 +465,9 @@ int jh_op_yuv420_to_bgr(const uint8_t* frames_dev, int format, int n, int h, int
  * (n,h,w,3) uint8 BGR. */
 int jh_op_yuv_surface_to_bgr(const uint8_t* frames_dev, const jh_yuv_surface* surface, int n, int h, int w,
                              uint8_t* out_bgr_dev, void* stream);
+/* The demosaic on its own (jh_sensor_surface above): frames n * image_stride bytes -> out_bgr (n,h,w,3) uint8 BGR. */
+int jh_op_sensor_to_bgr(const uint8_t* frames_dev, const jh_sensor_surface* surface, int n, int h, int w,
+                        uint8_t* out_bgr_dev, void* stream);
 
 /* The scan of jh_predictor_views2d on its own: the argmax of every joint's heat map in ONE pass over the buffer (each
  * byte read once; jh_predictor2d_forward's per-joint kernel reads the image once per joint).  heat (n,hh,wh,jp)

@@ -41,6 +41,15 @@ class YuvSurfaceStruct(ctypes.Structure):
 
 assert ctypes.sizeof(YuvSurfaceStruct) == 64
 
+
+class SensorSurfaceStruct(ctypes.Structure):
+    """jh_sensor_surface of include/jarvis_hip.h (built by sensor_surface.SensorSurface.struct())."""
+    _fields_ = [("image_stride", ctypes.c_int64), ("offset", ctypes.c_int64), ("pitch", ctypes.c_int64),
+                ("pattern", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(SensorSurfaceStruct) == 32
+
 ABI_VERSION = 4                      # JH_ABI_VERSION of include/jarvis_hip.h
 # sizeof(jh_predictor_config): statically asserted on the C side (tests/abi_smoke.c) and here
 assert ctypes.sizeof(PredictorConfig) == 84
@@ -122,6 +131,13 @@ _SIGS = {
                                                c_void_p, c_void_p, c_void_p]),
     "jh_op_yuv_surface_to_bgr": (c_int, [c_void_p, ctypes.POINTER(YuvSurfaceStruct), c_int, c_int, c_int, c_void_p,
                                          c_void_p]),
+    "jh_sensor_surface_check": (c_int, [ctypes.POINTER(SensorSurfaceStruct), c_int, c_int]),
+    "jh_predictor_forward_sensor": (c_int, [c_void_p, c_void_p, ctypes.POINTER(SensorSurfaceStruct), c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p]),
+    "jh_predictor2d_forward_sensor": (c_int, [c_void_p, c_void_p, ctypes.POINTER(SensorSurfaceStruct), c_void_p,
+                                              c_void_p, c_void_p, c_void_p]),
+    "jh_op_sensor_to_bgr": (c_int, [c_void_p, ctypes.POINTER(SensorSurfaceStruct), c_int, c_int, c_int, c_void_p,
+                                    c_void_p]),
     "jh_predictor_forward_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p]),
     "jh_predictor_stage_keypoints_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
@@ -203,16 +219,17 @@ def yuv_frame_hw(shape):
 
 def frame_layout(layout, frame_format, lead, hw=None, frames=None):
     """A frame_layout argument checked, before anything reaches the GPU: None stays None; otherwise a
-    yuv_surface.YuvSurface, not combined with frame_format 'i420' / 'nv12' (the layout says where the planes are),
-    of the frame size `hw` when that is given, and `frames` (when given) a uint8 tensor of shape
-    lead + (image_stride,) -- `lead` a tuple whose None entries match any size.  ValueError otherwise."""
+    yuv_surface.YuvSurface or a sensor_surface.SensorSurface, not combined with frame_format 'i420' / 'nv12' (the
+    layout says what the bytes are), of the frame size `hw` when that is given, and `frames` (when given) a uint8
+    tensor of shape lead + (image_stride,) -- `lead` a tuple whose None entries match any size.  ValueError
+    otherwise."""
     if layout is None:
         return None
-    from .yuv_surface import YuvSurface
-    if not isinstance(layout, YuvSurface):
-        raise ValueError("frame_layout must be a YuvSurface or None, got %r" % (type(layout).__name__,))
+    if not is_frame_layout(layout):
+        raise ValueError("frame_layout must be a YuvSurface or a SensorSurface or None, got %r"
+                         % (type(layout).__name__,))
     if frame_format in YUV_FORMATS:
-        raise ValueError("frame_layout describes the planes itself: do not combine it with frame_format=%r"
+        raise ValueError("frame_layout describes the bytes itself: do not combine it with frame_format=%r"
                          % (frame_format,))
     if hw is not None and (layout.height, layout.width) != tuple(hw):
         raise ValueError("frame_layout is %d x %d; this predictor is %d x %d" % (layout.height, layout.width, *hw))
@@ -221,10 +238,27 @@ def frame_layout(layout, frame_format, lead, hw=None, frames=None):
         ok = torch.is_tensor(frames) and frames.dtype == torch.uint8 and frames.dim() == len(want) and all(
             w is None or int(g) == w for g, w in zip(frames.shape, want))
         if not ok:
-            raise ValueError("frames of a YuvSurface must be uint8 %s (image_stride bytes per image); got %s" % (
-                tuple("*" if w is None else w for w in want),
+            raise ValueError("frames of a %s must be uint8 %s (image_stride bytes per image); got %s" % (
+                type(layout).__name__, tuple("*" if w is None else w for w in want),
                 (frames.dtype, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames).__name__))
     return layout
+
+
+def is_frame_layout(layout):
+    """True for the two descriptions frame_layout= takes: a YuvSurface or a SensorSurface."""
+    from .sensor_surface import SensorSurface
+    from .yuv_surface import YuvSurface
+    return isinstance(layout, (YuvSurface, SensorSurface))
+
+
+def layout_entry(layout, which):
+    """The entry point of the library that reads frames through `layout`: which = 'forward' (the 3D predictor),
+    'forward2d' (the 2D predictor) or 'to_bgr' (the conversion on its own)."""
+    from .sensor_surface import SensorSurface
+    sensor = isinstance(layout, SensorSurface)
+    return getattr(lib(), {"forward": ("jh_predictor_forward_surface", "jh_predictor_forward_sensor"),
+                           "forward2d": ("jh_predictor2d_forward_surface", "jh_predictor2d_forward_sensor"),
+                           "to_bgr": ("jh_op_yuv_surface_to_bgr", "jh_op_sensor_to_bgr")}[which][int(sensor)])
 
 
 def camera_mask(mask, shape, what="camera_mask"):

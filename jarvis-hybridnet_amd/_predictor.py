@@ -73,7 +73,8 @@ class NativePredictor:
         camera_mask (T,C) bool / integer, host or device: frame t uses the cameras with a nonzero entry only
         (jh_predictor_forward_masked); None: all cameras, the unmasked entry points.
         frame_layout: a YuvSurface -- frames (T,C,image_stride) uint8, each image a YUV 4:2:0 surface read through
-        that description (jh_predictor_forward_surface); not together with frame_format 'i420' / 'nv12'."""
+        that description (jh_predictor_forward_surface) --, or a SensorSurface -- each image a raw Mono8 / Bayer
+        sensor image (jh_predictor_forward_sensor); not together with frame_format 'i420' / 'nv12'."""
         frame_format = N.frame_format(frame_format)
         camera_mask = N.camera_mask(camera_mask, (self.T, self.C))
         frame_layout = N.frame_layout(frame_layout, frame_format, (self.T, self.Cloc), (self.cfg.img_h, self.cfg.img_w),
@@ -87,8 +88,8 @@ class NativePredictor:
         if frame_layout is not None:
             mask = None if camera_mask is None else camera_mask.to(dev, non_blocking=True)
             surf = frame_layout.struct()                        # (read during the call only)
-            N.check(N.lib().jh_predictor_forward_surface(self.handle, N.ptr(frames), surf, N.ptr(mask), N.ptr(out[0]),
-                                                         N.ptr(out[1]), N.ptr(out[2]), N.stream()))
+            N.check(N.layout_entry(frame_layout, "forward")(self.handle, N.ptr(frames), surf, N.ptr(mask),
+                                                            N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.stream()))
             if mask is not None and mask.is_cuda:
                 mask.record_stream(torch.cuda.current_stream())
             return out

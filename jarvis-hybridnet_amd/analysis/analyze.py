@@ -25,7 +25,7 @@ def analyze_frames(predictor, samples, reproTools, output_dir, num_joints, progr
     `[imgs (1,C,H,W,3), keypoints3D (1,J,3), ..., dataset_name [str], file_name [str]]`
     (dataset3D.py:248-258 behind a DataLoader(batch_size=1), analyze.py:46-51).
     frame_layout: a YuvSurface -- imgs is (1,C,image_stride) uint8, one described YUV 4:2:0 surface per camera
-    (JarvisPredictor3D.forward_surface).
+    (JarvisPredictor3D.forward_surface); a SensorSurface likewise (one raw sensor image per camera).
     Returns (number of frame sets seen, number predicted)."""
     from .. import _native as N
     N.frame_layout(frame_layout, None, ())

@@ -279,8 +279,11 @@ int jh_reconstruct_point(const float* points2d_dev, const float* maxvals_dev, in
     if (_pf.on) _pf.end(s);                                    \
   } while (0)
 
-// bytes of frame data per source pixel of a frame format (kSrc*): fp32 RGB 12, uint8 BGR 3, YUV 4:2:0 1.5
-static double frame_px_bytes(int fmt) { return fmt == kSrcRgbF32 ? 12.0 : fmt == kSrcBgrU8 ? 3.0 : 1.5; }
+// bytes of frame data per source pixel of a frame format (kSrc*): fp32 RGB 12, uint8 BGR 3, YUV 4:2:0 1.5,
+// raw sensor 1
+static double frame_px_bytes(int fmt) {
+  return fmt == kSrcRgbF32 ? 12.0 : fmt == kSrcBgrU8 ? 3.0 : fmt == kSrcSensor ? 1.0 : 1.5;
+}
 
 // The one validation of a described YUV 4:2:0 surface of h x w images (include/jarvis_hip.h): every surface entry
 // point and jh_yuv_surface_check.  Host arithmetic only.  (__int128: a plane's end may not wrap for any int64 field.)
@@ -326,6 +329,31 @@ static YuvSurface yuv_surface_args(const jh_yuv_surface& q) {
   return a;
 }
 
+// The one validation of a raw sensor surface of h x w images (include/jarvis_hip.h): every sensor entry point and
+// jh_sensor_surface_check.  Host arithmetic only.
+static int sensor_surface_check(const jh_sensor_surface* sp, int h, int w) {
+  JH_REQUIRE(sp, "null jh_sensor_surface");
+  const jh_sensor_surface& q = *sp;
+  JH_REQUIRE(h > 0 && w > 0, "raw sensor frames need a positive height and width");
+  JH_REQUIRE(q.pattern >= JH_SENSOR_MONO && q.pattern <= JH_SENSOR_GBRG, "jh_sensor_surface.pattern: unknown");
+  if (q.pattern != JH_SENSOR_MONO)
+    JH_REQUIRE(h % 2 == 0 && w % 2 == 0 && h >= 4 && w >= 4,
+               "Bayer frames need an even height and width of at least 4");
+  JH_REQUIRE(q.pitch >= w, "jh_sensor_surface.pitch is smaller than the width");
+  JH_REQUIRE(q.offset >= 0, "jh_sensor_surface.offset must not be negative");
+  JH_REQUIRE((__int128)q.offset + (__int128)(h - 1) * q.pitch + w <= q.image_stride,
+             "jh_sensor_surface: the image ends beyond image_stride");
+  JH_REQUIRE(q.reserved == 0, "jh_sensor_surface.reserved must be 0");
+  return 0;
+}
+
+// a checked description as the kernels take it (preprocess.h)
+static SensorSurface sensor_surface_args(const jh_sensor_surface& q, int h, int w) {
+  SensorSurface a;
+  a.image_stride = q.image_stride; a.offset = q.offset; a.pitch = q.pitch; a.pattern = q.pattern; a.h = h; a.w = w;
+  return a;
+}
+
 static_assert(JH_FRAME_RGB_F32 == kSrcRgbF32 && JH_FRAME_BGR_U8 == kSrcBgrU8 && JH_FRAME_I420 == kSrcI420 &&
                   JH_FRAME_NV12 == kSrcNV12, "frame format codes of the C ABI are preprocess.h's SRC");
 
@@ -359,13 +387,16 @@ struct jh_predictor {
   float *g_points = nullptr, *g_conf = nullptr;
   hipStream_t gstream = nullptr;             // capture stream (the caller's may be the null stream)
   // one per frame format (kSrc*, preprocess.h); [kGraphFmts + fmt]: the masked form of that format
-  static constexpr int kGraphFmts = kSrcYuvSurface + 1;
+  static constexpr int kGraphFmts = kSrcSensor + 1;
   hipGraphExec_t gexec[2 * kGraphFmts] = {};
   // Described surfaces (kSrcYuvSurface).  ysurf: the description of the call under way, as the kernels take it.
   // A launch carries it by value, so a recording has ONE layout: gsurf[plain / masked] is the description its graph
   // was captured with, and a call with another one records again (forward_graph).
   YuvSurface ysurf;
   jh_yuv_surface gsurf[2] = {};
+  // Raw sensor surfaces (kSrcSensor), likewise: ssurf is set by jh_predictor_forward_sensor before the forward,
+  // gsens[plain / masked] is the description the graph of that form was captured with.
+  SensorSurface ssurf, gsens[2];
   // Camera mask (camera_mask.h).  mask_buf [T][C]: the predictor's copy of the current call's mask -- the masked
   // kernels (and a captured graph of them) read this buffer, so the mask may change from call to call.  mask_cur:
   // the mask of the call under way, nullptr = no mask (the plain kernels).  n_active / n_detect [T]: written by
@@ -536,6 +567,7 @@ static int stage_center_impl(jh_predictor* pr, const void* frames_dev, int fmt, 
     // resize + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->center->stem_src;
     src.mode = 1; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.fmt = fmt; src.yuv = pr->ysurf;
+    src.sensor = pr->ssurf;
     src.H = pr->cfg.img_h; src.W = pr->cfg.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = pr->cfg.mean[i]; src.stdv[i] = pr->cfg.std[i]; }
     // algorithmic bytes of the fused launch: the four bilinear taps of every network-input pixel (frame_px_bytes
@@ -544,7 +576,8 @@ static int stage_center_impl(jh_predictor* pr, const void* frames_dev, int fmt, 
   } else {
     JH_PROF("preprocess_resize", 0.0, (double)N * S * S * (4.0 * frame_px_bytes(fmt) + 3 * 4),
             launch_preprocess_resize(frames_dev, fmt, pr->center->input.p, N, pr->cfg.img_h,
-                                     pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, pr->cur_cell, &pr->ysurf));
+                                     pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, pr->cur_cell, &pr->ysurf,
+                                     &pr->ssurf));
   }
   if (pr->center->run(s)) return 1;
   const Act& h = pr->center->heat;
@@ -596,6 +629,7 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, int fm
     // crop + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->kp->stem_src;
     src.mode = 2; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.fmt = fmt; src.yuv = pr->ysurf;
+    src.sensor = pr->ssurf;
     src.center_hm = pr->chm_cur(); src.Cloc = pr->Cloc; src.C = pr->C; src.cam0 = c.cam_lo;
     src.H = c.img_h; src.W = c.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = c.mean[i]; src.stdv[i] = c.std[i]; }
@@ -603,7 +637,8 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, int fm
   } else {
     JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->Cloc * pr->B * pr->B * (frame_px_bytes(fmt) + 12.0),
             launch_preprocess_crop(frames_dev, fmt, pr->chm_cur(), pr->kp->input.p, pr->T, pr->Cloc, pr->C,
-                                   c.cam_lo, c.img_h, c.img_w, pr->B, c.mean, c.std, s, pr->cur_cell, &pr->ysurf));
+                                   c.cam_lo, c.img_h, c.img_w, pr->B, c.mean, c.std, s, pr->cur_cell, &pr->ysurf,
+                                   &pr->ssurf));
   }
   if (pr->kp->run(s)) return 1;
   if (heat_dev && heat_dev != pr->kp->heat.p)
@@ -685,6 +720,15 @@ static int forward_graph(jh_predictor* pr, const void* frames_dev, int fmt, floa
       exec = nullptr;
     }
     rec = *surface;
+  }
+  if (fmt == kSrcSensor) {                    // (the same for a raw sensor surface)
+    SensorSurface& rec = pr->gsens[pr->mask_cur ? 1 : 0];
+    if (exec && memcmp(&rec, &pr->ssurf, sizeof(rec)) != 0) {
+      JH_CHECK_HIP(hipStreamSynchronize(s));
+      (void)hipGraphExecDestroy(exec);
+      exec = nullptr;
+    }
+    rec = pr->ssurf;
   }
   if (!exec) {
     hipGraph_t g = nullptr;
@@ -770,6 +814,19 @@ int jh_predictor_forward_surface(jh_predictor* pr, const uint8_t* frames_dev, co
   JH_REQUIRE(pr, "bad argument");
   if (yuv_surface_check(surface, pr->cfg.img_h, pr->cfg.img_w)) return 1;
   return forward_impl(pr, frames_dev, kSrcYuvSurface, points_dev, conf_dev, valid_dev, stream, mask_dev, surface);
+}
+
+int jh_sensor_surface_check(const jh_sensor_surface* surface, int h, int w) {
+  return sensor_surface_check(surface, h, w);
+}
+
+int jh_predictor_forward_sensor(jh_predictor* pr, const uint8_t* frames_dev, const jh_sensor_surface* surface,
+                                const uint8_t* mask_dev, float* points_dev, float* conf_dev, int32_t* valid_dev,
+                                void* stream) {
+  JH_REQUIRE(pr, "bad argument");
+  if (sensor_surface_check(surface, pr->cfg.img_h, pr->cfg.img_w)) return 1;
+  pr->ssurf = sensor_surface_args(*surface, pr->cfg.img_h, pr->cfg.img_w);
+  return forward_impl(pr, frames_dev, kSrcSensor, points_dev, conf_dev, valid_dev, stream, mask_dev);
 }
 
 int jh_predictor_forward_masked(jh_predictor* pr, const void* frames_dev, int format, const uint8_t* mask_dev,
@@ -925,7 +982,8 @@ int jh_predictor2d_create(const jh_params* center_params, const jh_params* kp_pa
 void jh_predictor2d_destroy(jh_predictor2d* pr) { delete pr; }
 
 static int forward2d_impl(jh_predictor2d* pr, const void* frames, int fmt, int32_t* points_dev,
-                          float* conf_dev, int32_t* valid_dev, void* stream, const YuvSurface* surface = nullptr) {
+                          float* conf_dev, int32_t* valid_dev, void* stream, const YuvSurface* surface = nullptr,
+                          const SensorSurface* sensor = nullptr) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const auto& c = pr->cfg;
   const int S = c.center_size;
@@ -933,7 +991,7 @@ static int forward2d_impl(jh_predictor2d* pr, const void* frames, int fmt, int32
   // (These counts used to be a flat 24 B per pixel for every format: fp32 resize is 60, uint8 crop 15.)
   JH_PROF("preprocess_resize", 0.0, (double)pr->T * S * S * (4.0 * frame_px_bytes(fmt) + 12.0),
           launch_preprocess_resize(frames, fmt, pr->center->input.p, pr->T, c.img_h, c.img_w, S,
-                                   c.mean, c.std, s, nullptr, surface));
+                                   c.mean, c.std, s, nullptr, surface, sensor));
   if (pr->center->run(s)) return 1;
   const Act& h = pr->center->heat;
   JH_PROF("center_argmax", 0.0, 4.0 * pr->T * h.H * h.W,
@@ -944,7 +1002,7 @@ static int forward2d_impl(jh_predictor2d* pr, const void* frames, int fmt, int32
     return 1;
   JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->B * pr->B * (frame_px_bytes(fmt) + 12.0),
           launch_preprocess_crop(frames, fmt, pr->chm, pr->kp->input.p, pr->T, 1, 1, 0, c.img_h,
-                                 c.img_w, pr->B, c.mean, c.std, s, nullptr, surface));
+                                 c.img_w, pr->B, c.mean, c.std, s, nullptr, surface, sensor));
   if (pr->kp->run(s)) return 1;
   const Act& k = pr->kp->heat;
   JH_PROF("joint_argmax", 0.0, 4.0 * pr->T * k.H * k.W * pr->J,
@@ -979,6 +1037,14 @@ int jh_predictor2d_forward_surface(jh_predictor2d* pr, const uint8_t* frames_dev
   if (yuv_surface_check(surface, pr->cfg.img_h, pr->cfg.img_w)) return 1;
   const YuvSurface ys = yuv_surface_args(*surface);
   return forward2d_impl(pr, frames_dev, kSrcYuvSurface, points_dev, conf_dev, valid_dev, stream, &ys);
+}
+
+int jh_predictor2d_forward_sensor(jh_predictor2d* pr, const uint8_t* frames_dev, const jh_sensor_surface* surface,
+                                  int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
+  JH_REQUIRE(pr && frames_dev, "bad argument");
+  if (sensor_surface_check(surface, pr->cfg.img_h, pr->cfg.img_w)) return 1;
+  const SensorSurface ss = sensor_surface_args(*surface, pr->cfg.img_h, pr->cfg.img_w);
+  return forward2d_impl(pr, frames_dev, kSrcSensor, points_dev, conf_dev, valid_dev, stream, nullptr, &ss);
 }
 
 // ------------------------------------------------------------------- profiling
@@ -1114,6 +1180,16 @@ int jh_op_yuv_surface_to_bgr(const uint8_t* frames_dev, const jh_yuv_surface* su
   JH_REQUIRE(frames_dev && out_bgr_dev && n >= 1, "null frame / output pointer");
   if (yuv_surface_check(surface, h, w)) return 1;
   if (launch_yuv_surface_to_bgr(frames_dev, yuv_surface_args(*surface), out_bgr_dev, n, h, w, s)) return 1;
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int jh_op_sensor_to_bgr(const uint8_t* frames_dev, const jh_sensor_surface* surface, int n, int h, int w,
+                        uint8_t* out_bgr_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(frames_dev && out_bgr_dev && n >= 1, "null frame / output pointer");
+  if (sensor_surface_check(surface, h, w)) return 1;
+  if (launch_sensor_to_bgr(frames_dev, sensor_surface_args(*surface, h, w), out_bgr_dev, n, h, w, s)) return 1;
   JH_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -19,8 +19,13 @@ namespace jh {
 // SRC = 4 (a described YUV 4:2:0 surface, jh_yuv_surface of include/jarvis_hip.h): plane offsets, pitches, the
 // chroma order and step, and the colour matrix / range come with the launch (YuvSurface below), so pitched decoder
 // surfaces, YV12 / NV21 and BT.709 / full-range streams are read in place (yuv_surface_px).
-enum { kSrcRgbF32 = 0, kSrcBgrU8 = 1, kSrcI420 = 2, kSrcNV12 = 3, kSrcYuvSurface = 4 };
+// SRC = 5 (a raw sensor image, jh_sensor_surface of include/jarvis_hip.h): one byte per pixel as a machine-vision
+// camera delivers it, Mono8 or an 8-bit Bayer mosaic, demosaiced per fetched pixel (sensor_px); the (R, G, B) bytes
+// enter the uint8 arithmetic unchanged, as the YUV forms' bytes do.
+enum { kSrcRgbF32 = 0, kSrcBgrU8 = 1, kSrcI420 = 2, kSrcNV12 = 3, kSrcYuvSurface = 4, kSrcSensor = 5 };
 template <int SRC> constexpr bool kIsYuv = SRC == kSrcI420 || SRC == kSrcNV12 || SRC == kSrcYuvSurface;
+// the forms whose pixel is converted once to (R, G, B) bytes for all three channels
+template <int SRC> constexpr bool kIsRgb8 = kIsYuv<SRC> || SRC == kSrcSensor;
 
 template <int SRC>
 __device__ __forceinline__ float frame_px(const void* frames, size_t n, int c, int y, int x, int H,
@@ -110,14 +115,53 @@ __device__ __forceinline__ Rgb8 yuv_surface_px(const void* frames, size_t n, int
   return yuv_to_rgb8(Y, U, V, s);
 }
 
-// the three channels (r, g, b) of one pixel as the uint8 path scales them; YUV: one conversion
-// for all three channels (ys: the surface of SRC 4, unused by the other formats)
+// A raw sensor surface as the kernels take it: the layout of a jh_sensor_surface the host has checked
+// (jh_sensor_surface_check) with the image size.  Passed BY VALUE in the kernel arguments, next to YuvSurface: every
+// field is wave-uniform and stays in scalar registers.
+struct SensorSurface {
+  long long image_stride = 0, offset = 0, pitch = 0;
+  int pattern = 0;             // JH_SENSOR_*: 0 mono, 1 rggb, 2 bggr, 3 grbg, 4 gbrg
+  int h = 0, w = 0;            // Bayer: even and >= 4, so the clamp below has an interior to clamp to
+  int reserved = 0;            // (no padding bytes: a recording's description is compared bytewise)
+};
+
+// pixel (y, x) of raw image n (SRC 5).  mono: the byte, three times.  Bayer: the bilinear demosaic defined in
+// include/jarvis_hip.h -- a border pixel takes the RGB of the interior pixel it clamps to, so the 3 x 3 neighbourhood
+// never leaves the h x w samples; then, by the parity of the site against the pattern, a green site reads 5 bytes
+// (itself, W E, N S) and a red or blue site 9.  64-bit offsets, as yuv_surface_px.
+__device__ __forceinline__ Rgb8 sensor_px(const void* frames, size_t n, int y, int x, const SensorSurface& s) {
+  const unsigned char* img = static_cast<const unsigned char*>(frames) + (long long)n * s.image_stride + s.offset;
+  if (s.pattern == 0) {
+    const int v = img[(long long)y * s.pitch + x];
+    return Rgb8{v, v, v};
+  }
+  y = min(max(y, 1), s.h - 2);
+  x = min(max(x, 1), s.w - 2);
+  const unsigned char* c = img + (long long)y * s.pitch + x;
+  const long long p = s.pitch;
+  // red sits at (ry, rx) of the top-left cell: rggb (0,0), bggr (1,1), grbg (0,1), gbrg (1,0)
+  const int ry = s.pattern == 2 || s.pattern == 4, rx = s.pattern == 2 || s.pattern == 3;
+  const int py = (y & 1) ^ ry, px = (x & 1) ^ rx;       // (0,0): red site, (1,1): blue site, else green
+  const int own = c[0];
+  if (py == px) {
+    const int g = (c[-p] + c[p] + c[1] + c[-1] + 2) >> 2;
+    const int opp = (c[-p - 1] + c[-p + 1] + c[p - 1] + c[p + 1] + 2) >> 2;
+    return py == 0 ? Rgb8{own, g, opp} : Rgb8{opp, g, own};
+  }
+  const int lr = (c[-1] + c[1] + 1) >> 1, ab = (c[-p] + c[p] + 1) >> 1;
+  // a green site of a red row (py == 0) has red left and right, blue above and below; of a blue row the reverse
+  return py == 0 ? Rgb8{lr, own, ab} : Rgb8{ab, own, lr};
+}
+
+// the three channels (r, g, b) of one pixel as the uint8 path scales them; YUV and raw sensor forms: one conversion
+// for all three channels (ys / ss: the surface of SRC 4 / SRC 5, unused by the other formats)
 template <int SRC>
 __device__ __forceinline__ void frame_px3(const void* frames, size_t n, int y, int x, int H, int W,
-                                          const YuvSurface& ys, float v[3]) {
-  if constexpr (kIsYuv<SRC>) {
+                                          const YuvSurface& ys, const SensorSurface& ss, float v[3]) {
+  if constexpr (kIsRgb8<SRC>) {
     Rgb8 p;
-    if constexpr (SRC == kSrcYuvSurface) p = yuv_surface_px(frames, n, y, x, ys);
+    if constexpr (SRC == kSrcSensor) p = sensor_px(frames, n, y, x, ss);
+    else if constexpr (SRC == kSrcYuvSurface) p = yuv_surface_px(frames, n, y, x, ys);
     else p = yuv420_px<SRC>(frames, n, y, x, H, W);
     const float k = __fdiv_rn(1.f, 255.f);
     v[0] = __fmul_rn((float)p.r, k); v[1] = __fmul_rn((float)p.g, k); v[2] = __fmul_rn((float)p.b, k);
@@ -131,7 +175,8 @@ __device__ __forceinline__ void frame_px3(const void* frames, size_t n, int y, i
 // align_corners = False, no antialias), then (x - mean) / std; (r, g, b, 0)
 template <int SRC>
 __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, int ox, int H, int W, float sy,
-                                            float sx, float3 mean, float3 stdv, const YuvSurface& ys) {
+                                            float sx, float3 mean, float3 stdv, const YuvSurface& ys,
+                                            const SensorSurface& ss) {
   float ry = fmaxf(__fsub_rn(__fmul_rn(sy, __fadd_rn((float)oy, 0.5f)), 0.5f), 0.f);
   float rx = fmaxf(__fsub_rn(__fmul_rn(sx, __fadd_rn((float)ox, 0.5f)), 0.5f), 0.f);
   int y0 = min((int)floorf(ry), H - 1), x0 = min((int)floorf(rx), W - 1);
@@ -143,14 +188,14 @@ __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, i
   // YUV: each of the four taps is converted once for all three channels (the per-channel arithmetic
   // below is that of the uint8 path, so the result equals SRC 1 on the converted bytes bit for bit)
   float q00[3], q01[3], q10[3], q11[3];
-  if constexpr (kIsYuv<SRC>) {
-    frame_px3<SRC>(frames, n, y0, x0, H, W, ys, q00); frame_px3<SRC>(frames, n, y0, x1, H, W, ys, q01);
-    frame_px3<SRC>(frames, n, y1, x0, H, W, ys, q10); frame_px3<SRC>(frames, n, y1, x1, H, W, ys, q11);
+  if constexpr (kIsRgb8<SRC>) {
+    frame_px3<SRC>(frames, n, y0, x0, H, W, ys, ss, q00); frame_px3<SRC>(frames, n, y0, x1, H, W, ys, ss, q01);
+    frame_px3<SRC>(frames, n, y1, x0, H, W, ys, ss, q10); frame_px3<SRC>(frames, n, y1, x1, H, W, ys, ss, q11);
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     float p00, p01, p10, p11;
-    if constexpr (kIsYuv<SRC>) {
+    if constexpr (kIsRgb8<SRC>) {
       p00 = q00[c]; p01 = q01[c]; p10 = q10[c]; p11 = q11[c];
     } else {
       p00 = frame_px<SRC>(frames, n, c, y0, x0, H, W); p01 = frame_px<SRC>(frames, n, c, y0, x1, H, W);
@@ -169,16 +214,17 @@ __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, i
 // crop centre is clamped; kept for safety as the stand-alone kernel has it)
 template <int SRC>
 __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int cy, int oy, int ox, int H,
-                                          int W, int B, float3 mean, float3 stdv, const YuvSurface& ys) {
+                                          int W, int B, float3 mean, float3 stdv, const YuvSurface& ys,
+                                          const SensorSurface& ss) {
   const int hw = B / 2;
   const int ix = cx - hw + ox, iy = cy - hw + oy;
   const float mv[3] = {mean.x, mean.y, mean.z}, sv[3] = {stdv.x, stdv.y, stdv.z};
   float r[3];
   const bool ok = ix >= 0 && ix < W && iy >= 0 && iy < H;
-  if constexpr (kIsYuv<SRC>) {
+  if constexpr (kIsRgb8<SRC>) {
     // (outside the frame: 0 before the normalisation, as for the other formats -- not the conversion of Y = U = V = 0)
     float q[3] = {0.f, 0.f, 0.f};
-    if (ok) frame_px3<SRC>(frames, n, iy, ix, H, W, ys, q);
+    if (ok) frame_px3<SRC>(frames, n, iy, ix, H, W, ys, ss, q);
 #pragma unroll
     for (int c = 0; c < 3; ++c) r[c] = __fdiv_rn(__fsub_rn(q[c], mv[c]), sv[c]);
   } else {
@@ -198,6 +244,7 @@ struct StemSource {
   const void* const* frames_cell = nullptr;    // graph replays: the frame pointer of the current call
   int fmt = 0;                                 // frame format: SRC of preprocess.h (kSrc*)
   YuvSurface yuv;                              // fmt == kSrcYuvSurface: the surface the frames are read through
+  SensorSurface sensor;                        // fmt == kSrcSensor: the raw surface the frames are read through
   const int* center_hm = nullptr;              // crop: [T][C][2]
   int Cloc = 0, C = 0, cam0 = 0;               // crop: image n = (t, local camera)
   int H = 0, W = 0;                            // frame size

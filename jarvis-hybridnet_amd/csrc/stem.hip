@@ -39,6 +39,7 @@ struct StemSrcArgs {           // MODE != 0: the frames this launch pre-processe
   float sy, sx;
   float3 mean, stdv;
   YuvSurface yuv;              // SRC == kSrcYuvSurface: the described surface (uniform: scalar registers)
+  SensorSurface sensor;        // SRC == kSrcSensor: the raw sensor surface (likewise)
 };
 
 template <int MODE, int SRC, int CO = 16>
@@ -83,8 +84,10 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
       // (the convolution's zero padding lies outside the pre-processed image: zeros, not normalised zeros)
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (ok)
-        v = MODE == 1 ? resize_px<SRC>(frames, n, iy, ix, sa.FH, sa.FW, sa.sy, sa.sx, sa.mean, sa.stdv, sa.yuv)
-                      : crop_px<SRC>(frames, n, ccx, ccy, iy, ix, sa.FH, sa.FW, H, sa.mean, sa.stdv, sa.yuv);
+        v = MODE == 1 ? resize_px<SRC>(frames, n, iy, ix, sa.FH, sa.FW, sa.sy, sa.sx, sa.mean, sa.stdv, sa.yuv,
+                                       sa.sensor)
+                      : crop_px<SRC>(frames, n, ccx, ccy, iy, ix, sa.FH, sa.FW, H, sa.mean, sa.stdv, sa.yuv,
+                                     sa.sensor);
       patch[i] = v;
     }
   }
@@ -185,7 +188,7 @@ int launch_stem_conv_src(const StemSource& src, const Act& x, const float* w_dev
   sa.sy = (float)src.H / (float)x.H; sa.sx = (float)src.W / (float)x.W;        // (as launch_preprocess_resize)
   sa.mean = make_float3(src.mean[0], src.mean[1], src.mean[2]);
   sa.stdv = make_float3(src.stdv[0], src.stdv[1], src.stdv[2]);
-  sa.yuv = src.yuv;
+  sa.yuv = src.yuv; sa.sensor = src.sensor;
   const int tiles = ((y.H + kStT - 1) / kStT) * ((y.W + kStT - 1) / kStT);
   const dim3 grid(tiles, x.N);
   // (the fp32 resize form is bound by HBM on the frames it reads -- 2 of every 4 rows of 1280 x 1024 x 3 floats --
@@ -200,14 +203,15 @@ int launch_stem_conv_src(const StemSource& src, const Act& x, const float* w_dev
       hipLaunchKernelGGL((stem_conv_kernel<M, U, 16>), grid, dim3(256), (M == 1 && U == 0) ? pad_f32 : 0, s, x.p,       \
                          w_dev, y.p, stats, x.H, x.W, sa);                                                              \
   } while (0)
-  JH_REQUIRE(src.fmt >= kSrcRgbF32 && src.fmt <= kSrcYuvSurface, "frame format");
+  JH_REQUIRE(src.fmt >= kSrcRgbF32 && src.fmt <= kSrcSensor, "frame format");
 #define JH_STEM_FMT(M)                                     \
   switch (src.fmt) {                                       \
     case kSrcRgbF32: JH_STEM(M, kSrcRgbF32); break;        \
     case kSrcBgrU8: JH_STEM(M, kSrcBgrU8); break;          \
     case kSrcI420: JH_STEM(M, kSrcI420); break;            \
     case kSrcNV12: JH_STEM(M, kSrcNV12); break;            \
-    default: JH_STEM(M, kSrcYuvSurface); break;            \
+    case kSrcYuvSurface: JH_STEM(M, kSrcYuvSurface); break; \
+    default: JH_STEM(M, kSrcSensor); break;                \
   }
   if (src.mode == 1) { JH_STEM_FMT(1) } else { JH_STEM_FMT(2) }
 #undef JH_STEM_FMT

@@ -139,7 +139,7 @@ class ShardedPredictor:
         """Start time batch i+1; returns the results of batch i (None on the first call).  frame_format: None or
         'bgr' only -- the camera-sharded stages take fp32 RGB or uint8 BGR frames, not YUV 4:2:0.  camera_mask: None
         only -- per-frame camera masks are a single-GPU feature.  return_2d: False only -- so are the per-camera 2D views.
-        frame_layout: None only -- so are described YUV surfaces."""
+        frame_layout: None only -- so are described YUV surfaces and raw sensor surfaces."""
         if frame_layout is not None:
             raise ValueError("the camera-sharded path does not take a frame_layout (it would misread the surfaces "
                              "as BGR): use JarvisPredictor3D.forward_batch(..., frame_layout=...) on one GPU")

@@ -280,8 +280,8 @@ def host_outputs(ring, slot, outs):
 def driver_format(frame_format, frame_spec, ndim, frame_layout=None):
     """The drivers' frame_format argument checked: True for the YUV 4:2:0 formats, False for 'bgr' (the frames'
     dtype then decides between uint8 BGR and fp32 RGB, as without the argument); ValueError for anything else and
-    for a YUV `frame_spec` that is no ((..., 3H/2, W), uint8) with H and W even.  frame_layout (a YuvSurface, or
-    None) is checked with it: not together with 'i420' / 'nv12', and its `frame_spec` is ((..., image_stride), uint8)
+    for a YUV `frame_spec` that is no ((..., 3H/2, W), uint8) with H and W even.  frame_layout (a YuvSurface, a
+    SensorSurface, or None) is checked with it: not together with 'i420' / 'nv12', and its `frame_spec` is ((..., image_stride), uint8)
     with one dimension less."""
     from .. import _native as N
     if frame_format not in N.FRAME_FORMATS:
@@ -289,9 +289,9 @@ def driver_format(frame_format, frame_spec, ndim, frame_layout=None):
     if N.frame_layout(frame_layout, frame_format, ()) is not None and frame_spec is not None:
         shape, dtype = tuple(frame_spec[0]), frame_spec[1]
         if len(shape) != ndim - 1 or dtype != torch.uint8 or shape[-1] != frame_layout.image_stride:
-            raise ValueError("frame_spec of YuvSurface frames must be (%s, torch.uint8) with image_stride = %d; got %r"
-                             % ("(C, image_stride)" if ndim == 3 else "(image_stride,)", frame_layout.image_stride,
-                                frame_spec))
+            raise ValueError("frame_spec of %s frames must be (%s, torch.uint8) with image_stride = %d; got %r"
+                             % (type(frame_layout).__name__, "(C, image_stride)" if ndim == 3 else "(image_stride,)",
+                                frame_layout.image_stride, frame_spec))
     yuv = frame_format in N.YUV_FORMATS
     if yuv and frame_spec is not None:
         shape, dtype = tuple(frame_spec[0]), frame_spec[1]
@@ -309,8 +309,8 @@ def check_driver_frames(frames, frame_format, ndim, frame_layout=None):
     dtype = frames.dtype if torch.is_tensor(frames) else torch.from_numpy(np.empty(0, frames.dtype)).dtype
     if frame_layout is not None:
         if len(frames.shape) != ndim - 1 or dtype != torch.uint8 or frames.shape[-1] != frame_layout.image_stride:
-            raise ValueError("YuvSurface frames must be uint8 %s with image_stride = %d; got %s %s" % (
-                "(C, image_stride)" if ndim == 3 else "(image_stride,)", frame_layout.image_stride, dtype,
+            raise ValueError("%s frames must be uint8 %s with image_stride = %d; got %s %s" % (
+                type(frame_layout).__name__, "(C, image_stride)" if ndim == 3 else "(image_stride,)", frame_layout.image_stride, dtype,
                 tuple(frames.shape)))
         return
     if len(frames.shape) != ndim or dtype != torch.uint8:
@@ -322,7 +322,7 @@ def check_driver_frames(frames, frame_format, ndim, frame_layout=None):
 def pipeline_for(owner, frames, time_batch, streams, submit, emit, frame_spec=None, frame_layout=None):
     """The pipeline for frame sets shaped like `frames` (or like `frame_spec` = (shape, torch dtype) when
     `frames` is a fill callable), cached on `owner` (the predictor) so that its pinned buffers are re-used by
-    later driver calls.  frame_layout: the YuvSurface of the run, part of the cache key (the staging buffers are
+    later driver calls.  frame_layout: the YuvSurface / SensorSurface of the run, part of the cache key (the staging buffers are
     (C, image_stride) bytes of THAT layout)."""
     if torch.is_tensor(frames) and frames.is_cuda:
         return DevicePipeline(time_batch, submit, emit, streams)

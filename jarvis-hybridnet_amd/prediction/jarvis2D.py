@@ -39,8 +39,8 @@ class _Native2D:
             N.frame_layout(frame_layout, frame_format, (self.T,), (self.H, self.W), frames)
             if not (frames.is_cuda and frames.is_contiguous()):
                 raise RuntimeError("frames must be a contiguous CUDA (HIP) tensor")
-            N.check(N.lib().jh_predictor2d_forward_surface(self.handle, N.ptr(frames), frame_layout.struct(),
-                                                           N.ptr(pts), N.ptr(conf), N.ptr(valid), N.stream()))
+            N.check(N.layout_entry(frame_layout, "forward2d")(self.handle, N.ptr(frames), frame_layout.struct(),
+                                                              N.ptr(pts), N.ptr(conf), N.ptr(valid), N.stream()))
             return pts, conf, valid
         if frame_format in N.YUV_FORMATS:
             if tuple(frames.shape) != (self.T, self.H * 3 // 2, self.W) or frames.dtype != torch.uint8 \
@@ -91,7 +91,7 @@ class JarvisPredictor2D(nn.Module):
 
     def forward(self, img, frame_layout=None):
         """img (1,3,H,W) RGB in [0,1] -> (points2D (J,2) int64 pixels, confidences (J,))
-        or (None, None).  frame_layout: a YuvSurface -- img is forward_surface's."""
+        or (None, None).  frame_layout: a YuvSurface or a SensorSurface -- img is forward_surface's."""
         if frame_layout is not None:
             return self.forward_surface(img, frame_layout)
         x = N.dev(img)
@@ -114,8 +114,9 @@ class JarvisPredictor2D(nn.Module):
         return pts[0].long(), conf[0]
 
     def forward_surface(self, img, surface):
-        """img (image_stride,) or (1,image_stride) uint8: one YUV 4:2:0 image read through the YuvSurface `surface`
-        (see JarvisPredictor3D.forward_surface) -> (points2D (J,2) int64 pixels, confidences (J,)) or (None, None)."""
+        """img (image_stride,) or (1,image_stride) uint8: one YUV 4:2:0 image read through the YuvSurface `surface`,
+        or one raw Mono8 / Bayer image read through the SensorSurface `surface` (see
+        JarvisPredictor3D.forward_surface) -> (points2D (J,2) int64 pixels, confidences (J,)) or (None, None)."""
         from .jarvis3D import _need_surface
         if torch.is_tensor(img) and img.dim() == 1:
             img = img.unsqueeze(0)
@@ -130,7 +131,7 @@ class JarvisPredictor2D(nn.Module):
         """imgs (T,3,H,W) fp32 RGB or (T,H,W,3) uint8 BGR, independent images ->
         points2D (T,J,2) int32, confidences (T,J), valid (T) int32; no host sync.  frame_format 'i420' / 'nv12':
         imgs (T,3H/2,W) uint8 YUV 4:2:0; 'bgr': uint8 BGR required; None: the dtype decides.  frame_layout: a
-        YuvSurface -- imgs (T,image_stride) uint8 (forward_surface); not together with 'i420' / 'nv12'."""
+        YuvSurface or a SensorSurface -- imgs (T,image_stride) uint8 (forward_surface); not together with 'i420' / 'nv12'."""
         frame_format = N.frame_format(frame_format)
         if N.frame_layout(frame_layout, frame_format, (None,), None, imgs) is not None:
             x = N.dev(imgs, torch.uint8)

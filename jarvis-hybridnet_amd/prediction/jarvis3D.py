@@ -199,7 +199,9 @@ class JarvisPredictor3D(nn.Module):
     def forward_surface(self, frames, surface, cameraMatrices, intrinsicMatrices, distortionCoefficients,
                         camera_mask=None, return_2d=False):
         """frames (C,image_stride) uint8: one YUV 4:2:0 image per camera, read in place through the YuvSurface
-        `surface` (pitched decoder surfaces, I420 / YV12 / NV12 / NV21, BT.601 / BT.709, limited / full range).
+        `surface` (pitched decoder surfaces, I420 / YV12 / NV12 / NV21, BT.601 / BT.709, limited / full range), or one
+        raw sensor image per camera through the SensorSurface `surface` (Mono8, or an 8-bit Bayer mosaic demosaiced
+        bilinearly on the GPU; pitched buffers with a header in front likewise).
         Same result, bit for bit, as forward_uint8 on the BGR bytes the surface's conversion gives
         (include/jarvis_hip.h); bytes outside the planes are never read.
         -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d: as forward()."""
@@ -222,8 +224,8 @@ class JarvisPredictor3D(nn.Module):
         its own mask row only.  None: all cameras.
         return_2d: the per-camera `Views2D` of the batch (leading dimension T; see forward()) follows `valid`:
         (points, confidences, valid, views).  Rows of invalid frames: used 0, points2D -1, NaN reprojections.
-        frame_layout: a YuvSurface -- imgs (T,C,image_stride) uint8, see forward_surface; not together with
-        frame_format 'i420' / 'nv12'."""
+        frame_layout: a YuvSurface or a SensorSurface -- imgs (T,C,image_stride) uint8, see forward_surface; not
+        together with frame_format 'i420' / 'nv12'."""
         frame_format = N.frame_format(frame_format)
         frame_layout = N.frame_layout(frame_layout, frame_format, (None, self.num_cameras), None, imgs)
         if camera_mask is not None:
@@ -264,10 +266,9 @@ class JarvisPredictor3D(nn.Module):
 
 
 def _need_surface(surface):
-    """The direct forms' `surface` argument: a YuvSurface, not None."""
-    from ..yuv_surface import YuvSurface
-    if not isinstance(surface, YuvSurface):
-        raise ValueError("surface must be a YuvSurface, got %r" % (type(surface).__name__,))
+    """The direct forms' `surface` argument: a YuvSurface or a SensorSurface, not None."""
+    if not N.is_frame_layout(surface):
+        raise ValueError("surface must be a YuvSurface or a SensorSurface, got %r" % (type(surface).__name__,))
     return surface
 
 

@@ -74,7 +74,8 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
     'nv12' raises ValueError.
 
     frame_layout: a YuvSurface -- the frames are (image_stride,) uint8 described YUV 4:2:0 surfaces (fill callables
-    with `frame_spec=((image_stride,), torch.uint8)`), see predict3D_frames; not together with 'i420' / 'nv12'."""
+    with `frame_spec=((image_stride,), torch.uint8)`) --, or a SensorSurface -- (image_stride,) uint8 raw Mono8 /
+    Bayer sensor images --, see predict3D_frames; not together with 'i420' / 'nv12'."""
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
     yuv = driver_format(frame_format, frame_spec, 2, frame_layout)
     from .predict3D import _as_host
@@ -142,7 +143,7 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
 def predict2D_recordings(predictor, recordings, cfg, output_dir, params=None, time_batch=1, frame_layout=None):
     """`recordings`: {recording path: iterable of frames}.  One CSV per recording, named as the
     reference names them: `data2D.csv` for a single file, `<video>_data2D.csv` per video of a
-    directory (predict2D.py:49-68).  Returns {csv file name: number of frames}.  frame_layout: the YuvSurface of
+    directory (predict2D.py:49-68).  Returns {csv file name: number of frames}.  frame_layout: the YuvSurface or SensorSurface of
     every recording's frames (predict2D_frames), or None."""
     kw = {} if frame_layout is None else {"frame_layout": frame_layout}
     multiple = len(recordings) > 1 or bool(getattr(params, "multiple_videos", False))

@@ -247,3 +247,68 @@ def bgr_to_yuv(bgr, matrix="bt601", range="limited"):
 
     q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)  # noqa: E731
     return q(y), q(pool(u)), q(pool(v))
+
+
+# red site (row parity, column parity) of a Bayer pattern's top-left 2 x 2 cell; blue sits diagonally opposite
+_BAYER_RED = {"rggb": (0, 0), "bggr": (1, 1), "grbg": (0, 1), "gbrg": (1, 0)}
+
+
+def mosaic(bgr, pattern):
+    """uint8 BGR (..., H, W, 3) -> the raw (..., H, W) uint8 image a sensor with the colour filter `pattern` stores:
+    'mono' keeps the green channel, a Bayer pattern ('rggb' | 'bggr' | 'grbg' | 'gbrg') the one sample of each
+    pixel's site (test data: the inverse, sensor_to_bgr, is the contract)."""
+    x = np.asarray(bgr, np.uint8)
+    if pattern == "mono":
+        return np.ascontiguousarray(x[..., 1])
+    ry, rx = _BAYER_RED[pattern]
+    raw = np.ascontiguousarray(x[..., 1])                        # green everywhere, then the red and blue sites
+    raw[..., ry::2, rx::2] = x[..., ry::2, rx::2, 2]
+    raw[..., 1 - ry::2, 1 - rx::2] = x[..., 1 - ry::2, 1 - rx::2, 0]
+    return raw
+
+
+def sensor_to_bgr(raw, pattern):
+    """The numpy reference of the sensor conversion (include/jarvis_hip.h), in int32: raw (..., H, W) uint8 ->
+    (..., H, W, 3) uint8 BGR.  'mono': the byte three times.  Bayer: every pixel is first clamped to the interior
+    (1..H-2, 1..W-2) and the clamped pixel demosaiced -- at a red or blue site green = (N+S+E+W+2) >> 2 and the
+    opposite colour = (NW+NE+SW+SE+2) >> 2, at a green site the left/right colour = (W+E+1) >> 1 and the above/below
+    colour = (N+S+1) >> 1."""
+    raw = np.asarray(raw, np.uint8)
+    if pattern == "mono":
+        return np.repeat(raw[..., None], 3, axis=-1)
+    ry, rx = _BAYER_RED[pattern]
+    H, W = raw.shape[-2:]
+    if H < 4 or W < 4 or H % 2 or W % 2:
+        raise ValueError("Bayer frames need an even height and width of at least 4; got %d x %d" % (H, W))
+    r32 = raw.astype(np.int32)
+    y = np.clip(np.arange(H), 1, H - 2)[:, None]
+    x = np.clip(np.arange(W), 1, W - 2)[None, :]
+
+    def at(dy, dx):
+        return r32[..., y + dy, x + dx]
+
+    own = at(0, 0)
+    cross = (at(-1, 0) + at(1, 0) + at(0, 1) + at(0, -1) + 2) >> 2
+    diag = (at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1) + 2) >> 2
+    lr = (at(0, -1) + at(0, 1) + 1) >> 1
+    ab = (at(-1, 0) + at(1, 0) + 1) >> 1
+    py, px = (y & 1) ^ ry, (x & 1) ^ rx                          # (0, 0): red site, (1, 1): blue site, else green
+    red_site, blue_site = (py == 0) & (px == 0), (py == 1) & (px == 1)
+    green_red_row = (py == 0) & (px == 1)                        # red left and right, blue above and below
+    g = np.where(red_site | blue_site, cross, own)
+    r = np.where(red_site, own, np.where(blue_site, diag, np.where(green_red_row, lr, ab)))
+    b = np.where(blue_site, own, np.where(red_site, diag, np.where(green_red_row, ab, lr)))
+    return np.stack([b, g, r], axis=-1).astype(np.uint8)
+
+
+def pack_sensor_surface(raw, surface, fill=0):
+    """raw (..., H, W) uint8 -> (..., image_stride) uint8 laid out as the SensorSurface `surface` describes; every
+    byte that is no sample (the bytes before `offset`, pitch padding, the gap up to image_stride) is `fill`."""
+    raw = np.asarray(raw, np.uint8)
+    s, lead = surface, raw.shape[:-2]
+    if raw.shape[-2:] != (s.height, s.width):
+        raise ValueError("raw %s does not fit a %d x %d surface" % (raw.shape, s.height, s.width))
+    out = np.full(lead + (s.image_stride,), fill, np.uint8)
+    idx = s.offset + np.arange(s.height)[:, None] * s.pitch + np.arange(s.width)[None, :]
+    out[..., idx.reshape(-1)] = raw.reshape(lead + (-1,))
+    return out
