@@ -251,14 +251,23 @@ def is_frame_layout(layout):
     return isinstance(layout, (YuvSurface, SensorSurface))
 
 
-def layout_entry(layout, which):
-    """The entry point of the library that reads frames through `layout`: which = 'forward' (the 3D predictor),
-    'forward2d' (the 2D predictor) or 'to_bgr' (the conversion on its own)."""
-    from .sensor_surface import SensorSurface
-    sensor = isinstance(layout, SensorSurface)
-    return getattr(lib(), {"forward": ("jh_predictor_forward_surface", "jh_predictor_forward_sensor"),
-                           "forward2d": ("jh_predictor2d_forward_surface", "jh_predictor2d_forward_sensor"),
-                           "to_bgr": ("jh_op_yuv_surface_to_bgr", "jh_op_sensor_to_bgr")}[which][int(sensor)])
+def forward_entry(which, frames, frame_format=None, layout=None, mask=None):
+    """The whole-path entry point of the library for a call's frames, and the arguments that say what they are:
+    (fn, fmt_args), called as fn(handle, ptr(frames), *fmt_args, <outputs>, stream).  which = 'jh_predictor' (3D,
+    whose masked and described entry points take the device mask pointer, NULL for none) or 'jh_predictor2d' (no
+    masks).  layout: a checked frame_layout (its struct is kept alive by fmt_args); otherwise frame_format 'i420' /
+    'nv12', or the dtype decides between uint8 BGR and fp32 RGB."""
+    if layout is not None:
+        from .sensor_surface import SensorSurface
+        kind = "sensor" if isinstance(layout, SensorSurface) else "surface"
+        return (getattr(lib(), "%s_forward_%s" % (which, kind)),
+                (layout.struct(),) + ((ptr(mask),) if which == "jh_predictor" else ()))
+    fmt = FRAME_FORMATS[frame_format] if frame_format in YUV_FORMATS else int(frames.dtype == torch.uint8)
+    if mask is not None:
+        return lib().jh_predictor_forward_masked, (fmt, ptr(mask))
+    if frame_format in YUV_FORMATS:
+        return getattr(lib(), which + "_forward_yuv"), (fmt,)
+    return getattr(lib(), which + ("_forward_u8" if fmt else "_forward")), ()
 
 
 def camera_mask(mask, shape, what="camera_mask"):

@@ -85,30 +85,11 @@ class NativePredictor:
             out = (torch.empty((self.T, self.J, 3), device=dev),
                    torch.empty((self.T, self.J), device=dev),
                    torch.empty((self.T,), device=dev, dtype=torch.int32))
-        if frame_layout is not None:
-            mask = None if camera_mask is None else camera_mask.to(dev, non_blocking=True)
-            surf = frame_layout.struct()                        # (read during the call only)
-            N.check(N.layout_entry(frame_layout, "forward")(self.handle, N.ptr(frames), surf, N.ptr(mask),
-                                                            N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.stream()))
-            if mask is not None and mask.is_cuda:
-                mask.record_stream(torch.cuda.current_stream())
-            return out
-        if camera_mask is not None:
-            fmt = N.FRAME_FORMATS[frame_format] if frame_format in N.YUV_FORMATS else int(frames.dtype == torch.uint8)
-            mask = camera_mask.to(dev, non_blocking=True)       # (copied by the call: free once it is enqueued)
-            N.check(N.lib().jh_predictor_forward_masked(self.handle, N.ptr(frames), fmt, N.ptr(mask), N.ptr(out[0]),
-                                                        N.ptr(out[1]), N.ptr(out[2]), N.stream()))
-            if mask.is_cuda:
-                mask.record_stream(torch.cuda.current_stream())
-            return out
-        if frame_format in N.YUV_FORMATS:
-            N.check(N.lib().jh_predictor_forward_yuv(self.handle, N.ptr(frames), N.FRAME_FORMATS[frame_format],
-                                                     N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.stream()))
-            return out
-        fn = N.lib().jh_predictor_forward_u8 if frames.dtype == torch.uint8 else \
-            N.lib().jh_predictor_forward
-        N.check(fn(self.handle, N.ptr(frames), N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]),
-                   N.stream()))
+        mask = None if camera_mask is None else camera_mask.to(dev, non_blocking=True)   # (copied by the call)
+        fn, fmt_args = N.forward_entry("jh_predictor", frames, frame_format, frame_layout, mask)
+        N.check(fn(self.handle, N.ptr(frames), *fmt_args, N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.stream()))
+        if mask is not None and mask.is_cuda:
+            mask.record_stream(torch.cuda.current_stream())     # (free once the call is enqueued)
         return out
 
     def _check_frames(self, frames, cams, frame_format=None, frame_layout=None):

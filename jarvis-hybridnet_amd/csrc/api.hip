@@ -279,12 +279,6 @@ int jh_reconstruct_point(const float* points2d_dev, const float* maxvals_dev, in
     if (_pf.on) _pf.end(s);                                    \
   } while (0)
 
-// bytes of frame data per source pixel of a frame format (kSrc*): fp32 RGB 12, uint8 BGR 3, YUV 4:2:0 1.5,
-// raw sensor 1
-static double frame_px_bytes(int fmt) {
-  return fmt == kSrcRgbF32 ? 12.0 : fmt == kSrcBgrU8 ? 3.0 : fmt == kSrcSensor ? 1.0 : 1.5;
-}
-
 // The one validation of a described YUV 4:2:0 surface of h x w images (include/jarvis_hip.h): every surface entry
 // point and jh_yuv_surface_check.  Host arithmetic only.  (__int128: a plane's end may not wrap for any int64 field.)
 static int yuv_surface_check(const jh_yuv_surface* sp, int h, int w) {
@@ -312,8 +306,11 @@ static int yuv_surface_check(const jh_yuv_surface* sp, int h, int w) {
   return 0;
 }
 
-// a checked description as the kernels take it (preprocess.h): the layout and the constants of its (matrix, range)
-static YuvSurface yuv_surface_args(const jh_yuv_surface& q) {
+// FrameSource of a described YUV 4:2:0 surface of h x w images: the check above, then the description as the kernels
+// take it (preprocess.h) -- the layout and the constants of its (matrix, range)
+static int frame_source(const jh_yuv_surface* sp, int h, int w, FrameSource* out) {
+  if (yuv_surface_check(sp, h, w)) return 1;
+  const jh_yuv_surface& q = *sp;
   // {Y0, CY, CVR, CUB, CUG, CVG}: BT.601 limited = OpenCV's literals (yuv_to_rgb8); the others round(x * 2^20) of
   // the float64 matrix (include/jarvis_hip.h)
   static const int k[2][2][6] = {{{16, 1220542, 1673527, 2116026, -409993, -852492},
@@ -321,12 +318,13 @@ static YuvSurface yuv_surface_args(const jh_yuv_surface& q) {
                                  {{16, 1220945, 1879825, 2215014, -223607, -558796},
                                   {0, 1048576, 1651297, 1945738, -196424, -490864}}};
   const int* c = k[q.matrix][q.range];
-  YuvSurface a;
+  SrcDesc<kSrcYuvSurface> a;
   a.image_stride = q.image_stride; a.y_offset = q.y_offset; a.y_pitch = q.y_pitch;
   a.u_offset = q.u_offset; a.v_offset = q.v_offset; a.c_pitch = q.c_pitch; a.c_step = q.c_step;
   a.pair = q.c_step == 2 && q.image_stride % 2 == 0;
   a.y0 = c[0]; a.cy = c[1]; a.cvr = c[2]; a.cub = c[3]; a.cug = c[4]; a.cvg = c[5];
-  return a;
+  out->fmt = kSrcYuvSurface; out->desc = a;
+  return 0;
 }
 
 // The one validation of a raw sensor surface of h x w images (include/jarvis_hip.h): every sensor entry point and
@@ -347,15 +345,32 @@ static int sensor_surface_check(const jh_sensor_surface* sp, int h, int w) {
   return 0;
 }
 
-// a checked description as the kernels take it (preprocess.h)
-static SensorSurface sensor_surface_args(const jh_sensor_surface& q, int h, int w) {
-  SensorSurface a;
+// FrameSource of a raw sensor surface of h x w images: the check above, then the description as the kernels take it
+static int frame_source(const jh_sensor_surface* sp, int h, int w, FrameSource* out) {
+  if (sensor_surface_check(sp, h, w)) return 1;
+  const jh_sensor_surface& q = *sp;
+  SrcDesc<kSrcSensor> a;
   a.image_stride = q.image_stride; a.offset = q.offset; a.pitch = q.pitch; a.pattern = q.pattern; a.h = h; a.w = w;
-  return a;
+  out->fmt = kSrcSensor; out->desc = a;
+  return 0;
 }
 
 static_assert(JH_FRAME_RGB_F32 == kSrcRgbF32 && JH_FRAME_BGR_U8 == kSrcBgrU8 && JH_FRAME_I420 == kSrcI420 &&
                   JH_FRAME_NV12 == kSrcNV12, "frame format codes of the C ABI are preprocess.h's SRC");
+
+// FrameSource of h x w frames in one of the four fixed formats (JH_FRAME_*), whose layout follows from (h, w)
+static FrameSource fixed_source(int format) {        // (fp32 RGB / uint8 BGR: any size, nothing to validate)
+  FrameSource fs;
+  fs.fmt = format;
+  return fs;
+}
+static int frame_source(int format, int h, int w, FrameSource* out) {
+  JH_REQUIRE(format >= JH_FRAME_RGB_F32 && format <= JH_FRAME_NV12, "frame format");
+  if (format == JH_FRAME_I420 || format == JH_FRAME_NV12)
+    JH_REQUIRE(h % 2 == 0 && w % 2 == 0, "YUV 4:2:0 frames need an even height and width");
+  *out = fixed_source(format);
+  return 0;
+}
 
 struct jh_predictor {
   jh_predictor_config cfg{};
@@ -386,17 +401,12 @@ struct jh_predictor {
   const void* const* cur_cell = nullptr;     // non-null only while the forward is being captured
   float *g_points = nullptr, *g_conf = nullptr;
   hipStream_t gstream = nullptr;             // capture stream (the caller's may be the null stream)
-  // one per frame format (kSrc*, preprocess.h); [kGraphFmts + fmt]: the masked form of that format
+  // One slot per frame format (kSrc*, preprocess.h); [kGraphFmts + fmt]: the masked form of that format.  A launch
+  // carries its source's description by value, so a recording has ONE source: the slot keeps the FrameSource its
+  // graph was captured with, and a call with another one records again (forward_graph).
   static constexpr int kGraphFmts = kSrcSensor + 1;
-  hipGraphExec_t gexec[2 * kGraphFmts] = {};
-  // Described surfaces (kSrcYuvSurface).  ysurf: the description of the call under way, as the kernels take it.
-  // A launch carries it by value, so a recording has ONE layout: gsurf[plain / masked] is the description its graph
-  // was captured with, and a call with another one records again (forward_graph).
-  YuvSurface ysurf;
-  jh_yuv_surface gsurf[2] = {};
-  // Raw sensor surfaces (kSrcSensor), likewise: ssurf is set by jh_predictor_forward_sensor before the forward,
-  // gsens[plain / masked] is the description the graph of that form was captured with.
-  SensorSurface ssurf, gsens[2];
+  struct GraphSlot { hipGraphExec_t exec = nullptr; FrameSource src; };
+  GraphSlot gslot[2 * kGraphFmts];
   // Camera mask (camera_mask.h).  mask_buf [T][C]: the predictor's copy of the current call's mask -- the masked
   // kernels (and a captured graph of them) read this buffer, so the mask may change from call to call.  mask_cur:
   // the mask of the call under way, nullptr = no mask (the plain kernels).  n_active / n_detect [T]: written by
@@ -409,7 +419,7 @@ struct jh_predictor {
   float* v2d_max = nullptr;
   int* v2d_idx = nullptr;
   ~jh_predictor() {
-    for (auto& e : gexec) if (e) (void)hipGraphExecDestroy(e);
+    for (auto& g : gslot) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (gstream) (void)hipStreamDestroy(gstream);
   }
 
@@ -558,7 +568,7 @@ int jh_predictor_set_calibration(jh_predictor* pr, const float* cam_dev, const f
   return 0;
 }
 
-static int stage_center_impl(jh_predictor* pr, const void* frames_dev, int fmt, float* det_dev,
+static int stage_center_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* det_dev,
                              void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   JH_REQUIRE(pr->center, "predictor was created without CenterDetect weights");
@@ -566,18 +576,16 @@ static int stage_center_impl(jh_predictor* pr, const void* frames_dev, int fmt, 
   if (pr->center->stem_fusable) {
     // resize + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->center->stem_src;
-    src.mode = 1; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.fmt = fmt; src.yuv = pr->ysurf;
-    src.sensor = pr->ssurf;
+    src.mode = 1; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.source = fs;
     src.H = pr->cfg.img_h; src.W = pr->cfg.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = pr->cfg.mean[i]; src.stdv[i] = pr->cfg.std[i]; }
-    // algorithmic bytes of the fused launch: the four bilinear taps of every network-input pixel (frame_px_bytes
+    // algorithmic bytes of the fused launch: the four bilinear taps of every network-input pixel (px_bytes
     // each) + the stem's output at half resolution (16 or 32 channels = 16 or 32 B per input pixel)
-    pr->center->set_stem_traffic((double)N * S * S * (4.0 * frame_px_bytes(fmt) + pr->center->stem_channels()));
+    pr->center->set_stem_traffic((double)N * S * S * (4.0 * fs.px_bytes() + pr->center->stem_channels()));
   } else {
-    JH_PROF("preprocess_resize", 0.0, (double)N * S * S * (4.0 * frame_px_bytes(fmt) + 3 * 4),
-            launch_preprocess_resize(frames_dev, fmt, pr->center->input.p, N, pr->cfg.img_h,
-                                     pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, pr->cur_cell, &pr->ysurf,
-                                     &pr->ssurf));
+    JH_PROF("preprocess_resize", 0.0, (double)N * S * S * (4.0 * fs.px_bytes() + 3 * 4),
+            launch_preprocess_resize(frames_dev, fs, pr->center->input.p, N, pr->cfg.img_h,
+                                     pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, pr->cur_cell));
   }
   if (pr->center->run(s)) return 1;
   const Act& h = pr->center->heat;
@@ -588,14 +596,14 @@ static int stage_center_impl(jh_predictor* pr, const void* frames_dev, int fmt, 
 
 int jh_predictor_stage_center(jh_predictor* pr, const float* frames_dev, float* det_dev,
                               void* stream) {
-  return stage_center_impl(pr, frames_dev, 0, det_dev, stream);
+  return stage_center_impl(pr, frames_dev, fixed_source(kSrcRgbF32), det_dev, stream);
 }
 int jh_predictor_stage_center_u8(jh_predictor* pr, const uint8_t* frames_dev, float* det_dev,
                                  void* stream) {
-  return stage_center_impl(pr, frames_dev, 1, det_dev, stream);
+  return stage_center_impl(pr, frames_dev, fixed_source(kSrcBgrU8), det_dev, stream);
 }
 
-static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, int fmt,
+static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs,
                                 const float* det_all_dev, float* heat_dev, void* stream,
                                 int det_blocks = 1, bool next_centre_set = false) {
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -628,17 +636,15 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, int fm
   if (pr->kp->stem_fusable) {
     // crop + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->kp->stem_src;
-    src.mode = 2; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.fmt = fmt; src.yuv = pr->ysurf;
-    src.sensor = pr->ssurf;
+    src.mode = 2; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.source = fs;
     src.center_hm = pr->chm_cur(); src.Cloc = pr->Cloc; src.C = pr->C; src.cam0 = c.cam_lo;
     src.H = c.img_h; src.W = c.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = c.mean[i]; src.stdv[i] = c.std[i]; }
-    pr->kp->set_stem_traffic((double)pr->T * pr->Cloc * pr->B * pr->B * (frame_px_bytes(fmt) + pr->kp->stem_channels()));
+    pr->kp->set_stem_traffic((double)pr->T * pr->Cloc * pr->B * pr->B * (fs.px_bytes() + pr->kp->stem_channels()));
   } else {
-    JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->Cloc * pr->B * pr->B * (frame_px_bytes(fmt) + 12.0),
-            launch_preprocess_crop(frames_dev, fmt, pr->chm_cur(), pr->kp->input.p, pr->T, pr->Cloc, pr->C,
-                                   c.cam_lo, c.img_h, c.img_w, pr->B, c.mean, c.std, s, pr->cur_cell, &pr->ysurf,
-                                   &pr->ssurf));
+    JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->Cloc * pr->B * pr->B * (fs.px_bytes() + 12.0),
+            launch_preprocess_crop(frames_dev, fs, pr->chm_cur(), pr->kp->input.p, pr->T, pr->Cloc, pr->C,
+                                   c.cam_lo, c.img_h, c.img_w, pr->B, c.mean, c.std, s, pr->cur_cell));
   }
   if (pr->kp->run(s)) return 1;
   if (heat_dev && heat_dev != pr->kp->heat.p)
@@ -649,18 +655,19 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, int fm
 
 int jh_predictor_stage_keypoints(jh_predictor* pr, const float* frames_dev,
                                  const float* det_all_dev, float* heat_dev, void* stream) {
-  return stage_keypoints_impl(pr, frames_dev, 0, det_all_dev, heat_dev, stream, 1, true);
+  return stage_keypoints_impl(pr, frames_dev, fixed_source(kSrcRgbF32), det_all_dev, heat_dev, stream, 1, true);
 }
 int jh_predictor_stage_keypoints_u8(jh_predictor* pr, const uint8_t* frames_dev,
                                     const float* det_all_dev, float* heat_dev, void* stream) {
-  return stage_keypoints_impl(pr, frames_dev, 1, det_all_dev, heat_dev, stream, 1, true);
+  return stage_keypoints_impl(pr, frames_dev, fixed_source(kSrcBgrU8), det_all_dev, heat_dev, stream, 1, true);
 }
 
 int jh_predictor_stage_keypoints_gathered(jh_predictor* pr, const void* frames_dev, int frames_u8,
                                           const float* det_gathered_dev, int n_blocks, float* heat_dev,
                                           void* stream) {
   JH_REQUIRE(n_blocks >= 1, "block count");
-  return stage_keypoints_impl(pr, frames_dev, frames_u8 != 0, det_gathered_dev, heat_dev, stream, n_blocks, true);
+  return stage_keypoints_impl(pr, frames_dev, fixed_source(frames_u8 ? kSrcBgrU8 : kSrcRgbF32), det_gathered_dev, heat_dev,
+                              stream, n_blocks, true);
 }
 
 int jh_predictor_stage_3d(jh_predictor* pr, const float* heat_all_dev, int t0, float* points_dev,
@@ -694,10 +701,10 @@ int jh_predictor_stage_3d_blocks(jh_predictor* pr, const float* heat_blocks_dev,
   return 0;
 }
 
-static int forward_eager(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
+static int forward_eager(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
                          float* conf_dev, int32_t* valid_dev, void* stream) {
-  if (stage_center_impl(pr, frames_dev, fmt, pr->det_all, stream)) return 1;
-  if (stage_keypoints_impl(pr, frames_dev, fmt, pr->det_all, nullptr, stream)) return 1;
+  if (stage_center_impl(pr, frames_dev, fs, pr->det_all, stream)) return 1;
+  if (stage_keypoints_impl(pr, frames_dev, fs, pr->det_all, nullptr, stream)) return 1;
   return jh_predictor_stage_3d(pr, pr->kp->heat.p, 0, points_dev, conf_dev, valid_dev, stream);
 }
 
@@ -707,47 +714,36 @@ static int forward_eager(jh_predictor* pr, const void* frames_dev, int fmt, floa
 // graph serves every later call: set the cell, launch the graph, copy the results out -- three
 // submissions instead of ~150.  Calibration lives in the predictor's buffers (set_calibration
 // copies into them), weights are immutable for the life of a predictor: nothing to invalidate.
-static int forward_graph(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
-                         float* conf_dev, int32_t* valid_dev, hipStream_t s, const jh_yuv_surface* surface) {
-  hipGraphExec_t& exec = pr->gexec[fmt + (pr->mask_cur ? jh_predictor::kGraphFmts : 0)];
-  if (fmt == kSrcYuvSurface) {
-    // the recorded launches hold the description they were captured with: another layout records again (rare: a
-    // stream keeps its layout; the replay in flight is waited for before its executable graph goes)
-    jh_yuv_surface& rec = pr->gsurf[pr->mask_cur ? 1 : 0];
-    if (exec && memcmp(&rec, surface, sizeof(rec)) != 0) {
-      JH_CHECK_HIP(hipStreamSynchronize(s));
-      (void)hipGraphExecDestroy(exec);
-      exec = nullptr;
-    }
-    rec = *surface;
+static int forward_graph(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
+                         float* conf_dev, int32_t* valid_dev, hipStream_t s) {
+  jh_predictor::GraphSlot& slot = pr->gslot[fs.fmt + (pr->mask_cur ? jh_predictor::kGraphFmts : 0)];
+  // the recorded launches hold the description they were captured with: another one records again (rare: a stream
+  // keeps its layout, and a fixed format has nothing to differ in; the replay in flight is waited for before its
+  // executable graph goes)
+  if (slot.exec && slot.src != fs) {
+    JH_CHECK_HIP(hipStreamSynchronize(s));
+    (void)hipGraphExecDestroy(slot.exec);
+    slot.exec = nullptr;
   }
-  if (fmt == kSrcSensor) {                    // (the same for a raw sensor surface)
-    SensorSurface& rec = pr->gsens[pr->mask_cur ? 1 : 0];
-    if (exec && memcmp(&rec, &pr->ssurf, sizeof(rec)) != 0) {
-      JH_CHECK_HIP(hipStreamSynchronize(s));
-      (void)hipGraphExecDestroy(exec);
-      exec = nullptr;
-    }
-    rec = pr->ssurf;
-  }
-  if (!exec) {
+  if (!slot.exec) {
     hipGraph_t g = nullptr;
     if (!pr->gstream) JH_CHECK_HIP(hipStreamCreateWithFlags(&pr->gstream, hipStreamNonBlocking));
     JH_CHECK_HIP(hipStreamBeginCapture(pr->gstream, hipStreamCaptureModeRelaxed));
     pr->cur_cell = pr->frames_cell;
-    const int rc = forward_eager(pr, nullptr, fmt, pr->g_points, pr->g_conf, nullptr, pr->gstream);
+    const int rc = forward_eager(pr, nullptr, fs, pr->g_points, pr->g_conf, nullptr, pr->gstream);
     pr->cur_cell = nullptr;
     const hipError_t e = hipStreamEndCapture(pr->gstream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return 1; }
     JH_CHECK_HIP(e);
-    const hipError_t ei = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+    const hipError_t ei = hipGraphInstantiate(&slot.exec, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
-    if (ei != hipSuccess) exec = nullptr;
+    if (ei != hipSuccess) slot.exec = nullptr;
     JH_CHECK_HIP(ei);
+    slot.src = fs;
   }
   hipLaunchKernelGGL(set_cell_kernel, dim3(1), dim3(1), 0, s, pr->frames_cell, frames_dev);
   JH_CHECK_HIP(hipGetLastError());
-  JH_CHECK_HIP(hipGraphLaunch(exec, s));
+  JH_CHECK_HIP(hipGraphLaunch(slot.exec, s));
   const int n_pts = pr->T * pr->J * 3;
   hipLaunchKernelGGL(copy_out_kernel, dim3((n_pts + 255) / 256), dim3(256), 0, s, pr->g_points, pr->g_conf,
                      pr->valid_[0], points_dev, conf_dev, valid_dev, n_pts, pr->T * pr->J, pr->T);
@@ -755,55 +751,51 @@ static int forward_graph(jh_predictor* pr, const void* frames_dev, int fmt, floa
   return 0;
 }
 
-static int forward_unmasked(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
-                            float* conf_dev, int32_t* valid_dev, void* stream, const jh_yuv_surface* surface);
-
-// mask_dev != nullptr: the masked kernels, reading the predictor's copy of the mask (made here, on the caller's
-// stream, outside any graph of the predictor's own: the captured launches keep pointing at mask_buf)
-static int forward_impl(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
-                        float* conf_dev, int32_t* valid_dev, void* stream,
-                        const unsigned char* mask_dev = nullptr, const jh_yuv_surface* surface = nullptr) {
-  if (!mask_dev) return forward_unmasked(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, stream, surface);
-  JH_CHECK_HIP(hipMemcpyAsync(pr->mask_buf, mask_dev, (size_t)pr->T * pr->C, hipMemcpyDeviceToDevice,
-                              static_cast<hipStream_t>(stream)));
-  pr->mask_cur = pr->mask_buf;
-  const int rc = forward_unmasked(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, stream, surface);
-  pr->mask_cur = nullptr;
-  return rc;
-}
-
-static int forward_unmasked(jh_predictor* pr, const void* frames_dev, int fmt, float* points_dev,
-                            float* conf_dev, int32_t* valid_dev, void* stream, const jh_yuv_surface* surface) {
+static int forward_unmasked(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
+                            float* conf_dev, int32_t* valid_dev, void* stream) {
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
   JH_REQUIRE(pr->T3 == pr->T, "forward needs time_batch_3d == time_batch");
   JH_REQUIRE(frames_dev && points_dev && conf_dev, "null frame / output pointer");
-  JH_REQUIRE((fmt == kSrcYuvSurface) == (surface != nullptr), "a described surface comes with its own frame format");
-  if (surface) pr->ysurf = yuv_surface_args(*surface);
   pr->slot = 0;                               // (the whole-path forward and its captured graph: centre set 0)
   // per-launch profiling needs the launches one by one; a caller that is itself capturing this
   // stream gets the plain launches too (its graph then holds them)
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (pr->use_graph && !profiler().on) (void)hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs);
   if (!pr->use_graph || profiler().on || cs != hipStreamCaptureStatusNone)
-    return forward_eager(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, stream);
-  return forward_graph(pr, frames_dev, fmt, points_dev, conf_dev, valid_dev, static_cast<hipStream_t>(stream),
-                       surface);
+    return forward_eager(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
+  return forward_graph(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, static_cast<hipStream_t>(stream));
+}
+
+// mask_dev != nullptr: the masked kernels, reading the predictor's copy of the mask (made here, on the caller's
+// stream, outside any graph of the predictor's own: the captured launches keep pointing at mask_buf)
+static int forward_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
+                        float* conf_dev, int32_t* valid_dev, void* stream,
+                        const unsigned char* mask_dev = nullptr) {
+  if (!mask_dev) return forward_unmasked(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
+  JH_CHECK_HIP(hipMemcpyAsync(pr->mask_buf, mask_dev, (size_t)pr->T * pr->C, hipMemcpyDeviceToDevice,
+                              static_cast<hipStream_t>(stream)));
+  pr->mask_cur = pr->mask_buf;
+  const int rc = forward_unmasked(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
+  pr->mask_cur = nullptr;
+  return rc;
 }
 int jh_predictor_forward(jh_predictor* pr, const float* frames_dev, float* points_dev,
                          float* conf_dev, int32_t* valid_dev, void* stream) {
-  return forward_impl(pr, frames_dev, 0, points_dev, conf_dev, valid_dev, stream);
+  return forward_impl(pr, frames_dev, fixed_source(kSrcRgbF32), points_dev, conf_dev, valid_dev, stream);
 }
 int jh_predictor_forward_u8(jh_predictor* pr, const uint8_t* frames_dev, float* points_dev,
                             float* conf_dev, int32_t* valid_dev, void* stream) {
-  return forward_impl(pr, frames_dev, 1, points_dev, conf_dev, valid_dev, stream);
+  return forward_impl(pr, frames_dev, fixed_source(kSrcBgrU8), points_dev, conf_dev, valid_dev, stream);
 }
 
 int jh_predictor_forward_yuv(jh_predictor* pr, const uint8_t* frames_dev, int format, float* points_dev,
                              float* conf_dev, int32_t* valid_dev, void* stream) {
   JH_REQUIRE(format == JH_FRAME_I420 || format == JH_FRAME_NV12, "jh_predictor_forward_yuv: format must be "
              "JH_FRAME_I420 or JH_FRAME_NV12");
-  JH_REQUIRE(pr && pr->cfg.img_h % 2 == 0 && pr->cfg.img_w % 2 == 0, "YUV 4:2:0 frames need an even height and width");
-  return forward_impl(pr, frames_dev, format, points_dev, conf_dev, valid_dev, stream);
+  JH_REQUIRE(pr, "bad argument");
+  FrameSource fs;
+  if (frame_source(format, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
+  return forward_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
 }
 
 int jh_yuv_surface_check(const jh_yuv_surface* surface, int h, int w) { return yuv_surface_check(surface, h, w); }
@@ -812,8 +804,9 @@ int jh_predictor_forward_surface(jh_predictor* pr, const uint8_t* frames_dev, co
                                  const uint8_t* mask_dev, float* points_dev, float* conf_dev, int32_t* valid_dev,
                                  void* stream) {
   JH_REQUIRE(pr, "bad argument");
-  if (yuv_surface_check(surface, pr->cfg.img_h, pr->cfg.img_w)) return 1;
-  return forward_impl(pr, frames_dev, kSrcYuvSurface, points_dev, conf_dev, valid_dev, stream, mask_dev, surface);
+  FrameSource fs;
+  if (frame_source(surface, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
+  return forward_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream, mask_dev);
 }
 
 int jh_sensor_surface_check(const jh_sensor_surface* surface, int h, int w) {
@@ -824,18 +817,18 @@ int jh_predictor_forward_sensor(jh_predictor* pr, const uint8_t* frames_dev, con
                                 const uint8_t* mask_dev, float* points_dev, float* conf_dev, int32_t* valid_dev,
                                 void* stream) {
   JH_REQUIRE(pr, "bad argument");
-  if (sensor_surface_check(surface, pr->cfg.img_h, pr->cfg.img_w)) return 1;
-  pr->ssurf = sensor_surface_args(*surface, pr->cfg.img_h, pr->cfg.img_w);
-  return forward_impl(pr, frames_dev, kSrcSensor, points_dev, conf_dev, valid_dev, stream, mask_dev);
+  FrameSource fs;
+  if (frame_source(surface, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
+  return forward_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream, mask_dev);
 }
 
 int jh_predictor_forward_masked(jh_predictor* pr, const void* frames_dev, int format, const uint8_t* mask_dev,
                                 float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
   JH_REQUIRE(pr, "bad argument");
   JH_REQUIRE(format >= JH_FRAME_RGB_F32 && format <= JH_FRAME_NV12, "jh_predictor_forward_masked: unknown frame format");
-  if (format == JH_FRAME_I420 || format == JH_FRAME_NV12)
-    JH_REQUIRE(pr->cfg.img_h % 2 == 0 && pr->cfg.img_w % 2 == 0, "YUV 4:2:0 frames need an even height and width");
-  return forward_impl(pr, frames_dev, format, points_dev, conf_dev, valid_dev, stream, mask_dev);
+  FrameSource fs;
+  if (frame_source(format, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
+  return forward_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream, mask_dev);
 }
 
 int jh_predictor_stage_keypoints_masked(jh_predictor* pr, const void* frames_dev, int format,
@@ -845,7 +838,7 @@ int jh_predictor_stage_keypoints_masked(jh_predictor* pr, const void* frames_dev
   JH_REQUIRE(format == JH_FRAME_RGB_F32 || format == JH_FRAME_BGR_U8, "masked stage 2: fp32 RGB or uint8 BGR frames");
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "masked stage 2 needs all cameras local");
   pr->mask_cur = mask_dev;
-  const int rc = stage_keypoints_impl(pr, frames_dev, format, det_all_dev, heat_dev, stream, 1, true);
+  const int rc = stage_keypoints_impl(pr, frames_dev, fixed_source(format), det_all_dev, heat_dev, stream, 1, true);
   pr->mask_cur = nullptr;
   return rc;
 }
@@ -981,17 +974,16 @@ int jh_predictor2d_create(const jh_params* center_params, const jh_params* kp_pa
 
 void jh_predictor2d_destroy(jh_predictor2d* pr) { delete pr; }
 
-static int forward2d_impl(jh_predictor2d* pr, const void* frames, int fmt, int32_t* points_dev,
-                          float* conf_dev, int32_t* valid_dev, void* stream, const YuvSurface* surface = nullptr,
-                          const SensorSurface* sensor = nullptr) {
+static int forward2d_impl(jh_predictor2d* pr, const void* frames, const FrameSource& fs, int32_t* points_dev,
+                          float* conf_dev, int32_t* valid_dev, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const auto& c = pr->cfg;
   const int S = c.center_size;
   // algorithmic bytes as in the 3D stages: four taps (resize) or one pixel (crop) of frame data + the float4 written.
   // (These counts used to be a flat 24 B per pixel for every format: fp32 resize is 60, uint8 crop 15.)
-  JH_PROF("preprocess_resize", 0.0, (double)pr->T * S * S * (4.0 * frame_px_bytes(fmt) + 12.0),
-          launch_preprocess_resize(frames, fmt, pr->center->input.p, pr->T, c.img_h, c.img_w, S,
-                                   c.mean, c.std, s, nullptr, surface, sensor));
+  JH_PROF("preprocess_resize", 0.0, (double)pr->T * S * S * (4.0 * fs.px_bytes() + 12.0),
+          launch_preprocess_resize(frames, fs, pr->center->input.p, pr->T, c.img_h, c.img_w, S,
+                                   c.mean, c.std, s));
   if (pr->center->run(s)) return 1;
   const Act& h = pr->center->heat;
   JH_PROF("center_argmax", 0.0, 4.0 * pr->T * h.H * h.W,
@@ -1000,9 +992,9 @@ static int forward2d_impl(jh_predictor2d* pr, const void* frames, int fmt, int32
   const float sx = (float)c.img_w / (float)S, sy = (float)c.img_h / (float)S;
   if (launch_center2d(pr->det, pr->chm, pr->valid, pr->T, sx, sy, pr->B / 2, c.img_w, c.img_h, s))
     return 1;
-  JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->B * pr->B * (frame_px_bytes(fmt) + 12.0),
-          launch_preprocess_crop(frames, fmt, pr->chm, pr->kp->input.p, pr->T, 1, 1, 0, c.img_h,
-                                 c.img_w, pr->B, c.mean, c.std, s, nullptr, surface, sensor));
+  JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->B * pr->B * (fs.px_bytes() + 12.0),
+          launch_preprocess_crop(frames, fs, pr->chm, pr->kp->input.p, pr->T, 1, 1, 0, c.img_h,
+                                 c.img_w, pr->B, c.mean, c.std, s));
   if (pr->kp->run(s)) return 1;
   const Act& k = pr->kp->heat;
   JH_PROF("joint_argmax", 0.0, 4.0 * pr->T * k.H * k.W * pr->J,
@@ -1016,35 +1008,37 @@ static int forward2d_impl(jh_predictor2d* pr, const void* frames, int fmt, int32
 
 int jh_predictor2d_forward(jh_predictor2d* pr, const float* frames_dev, int32_t* points_dev,
                            float* conf_dev, int32_t* valid_dev, void* stream) {
-  return forward2d_impl(pr, frames_dev, 0, points_dev, conf_dev, valid_dev, stream);
+  return forward2d_impl(pr, frames_dev, fixed_source(kSrcRgbF32), points_dev, conf_dev, valid_dev, stream);
 }
 int jh_predictor2d_forward_u8(jh_predictor2d* pr, const uint8_t* frames_dev, int32_t* points_dev,
                               float* conf_dev, int32_t* valid_dev, void* stream) {
-  return forward2d_impl(pr, frames_dev, 1, points_dev, conf_dev, valid_dev, stream);
+  return forward2d_impl(pr, frames_dev, fixed_source(kSrcBgrU8), points_dev, conf_dev, valid_dev, stream);
 }
 
 int jh_predictor2d_forward_yuv(jh_predictor2d* pr, const uint8_t* frames_dev, int format, int32_t* points_dev,
                                float* conf_dev, int32_t* valid_dev, void* stream) {
   JH_REQUIRE(format == JH_FRAME_I420 || format == JH_FRAME_NV12, "jh_predictor2d_forward_yuv: format must be "
              "JH_FRAME_I420 or JH_FRAME_NV12");
-  JH_REQUIRE(pr && pr->cfg.img_h % 2 == 0 && pr->cfg.img_w % 2 == 0, "YUV 4:2:0 frames need an even height and width");
-  return forward2d_impl(pr, frames_dev, format, points_dev, conf_dev, valid_dev, stream);
+  JH_REQUIRE(pr, "bad argument");
+  FrameSource fs;
+  if (frame_source(format, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
+  return forward2d_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
 }
 
 int jh_predictor2d_forward_surface(jh_predictor2d* pr, const uint8_t* frames_dev, const jh_yuv_surface* surface,
                                    int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
   JH_REQUIRE(pr && frames_dev, "bad argument");
-  if (yuv_surface_check(surface, pr->cfg.img_h, pr->cfg.img_w)) return 1;
-  const YuvSurface ys = yuv_surface_args(*surface);
-  return forward2d_impl(pr, frames_dev, kSrcYuvSurface, points_dev, conf_dev, valid_dev, stream, &ys);
+  FrameSource fs;
+  if (frame_source(surface, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
+  return forward2d_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
 }
 
 int jh_predictor2d_forward_sensor(jh_predictor2d* pr, const uint8_t* frames_dev, const jh_sensor_surface* surface,
                                   int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
   JH_REQUIRE(pr && frames_dev, "bad argument");
-  if (sensor_surface_check(surface, pr->cfg.img_h, pr->cfg.img_w)) return 1;
-  const SensorSurface ss = sensor_surface_args(*surface, pr->cfg.img_h, pr->cfg.img_w);
-  return forward2d_impl(pr, frames_dev, kSrcSensor, points_dev, conf_dev, valid_dev, stream, nullptr, &ss);
+  FrameSource fs;
+  if (frame_source(surface, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
+  return forward2d_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
 }
 
 // ------------------------------------------------------------------- profiling
@@ -1169,7 +1163,8 @@ int jh_op_yuv420_to_bgr(const uint8_t* frames_dev, int format, int n, int h, int
   JH_REQUIRE(frames_dev && out_bgr_dev, "null frame / output pointer");
   JH_REQUIRE(format == JH_FRAME_I420 || format == JH_FRAME_NV12, "jh_op_yuv420_to_bgr: format must be "
              "JH_FRAME_I420 or JH_FRAME_NV12");
-  if (launch_yuv420_to_bgr(frames_dev, format, out_bgr_dev, n, h, w, s)) return 1;
+  FrameSource fs;
+  if (frame_source(format, h, w, &fs) || launch_frames_to_bgr(frames_dev, fs, out_bgr_dev, n, h, w, s)) return 1;
   JH_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }
@@ -1178,8 +1173,8 @@ int jh_op_yuv_surface_to_bgr(const uint8_t* frames_dev, const jh_yuv_surface* su
                              uint8_t* out_bgr_dev, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   JH_REQUIRE(frames_dev && out_bgr_dev && n >= 1, "null frame / output pointer");
-  if (yuv_surface_check(surface, h, w)) return 1;
-  if (launch_yuv_surface_to_bgr(frames_dev, yuv_surface_args(*surface), out_bgr_dev, n, h, w, s)) return 1;
+  FrameSource fs;
+  if (frame_source(surface, h, w, &fs) || launch_frames_to_bgr(frames_dev, fs, out_bgr_dev, n, h, w, s)) return 1;
   JH_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }
@@ -1188,8 +1183,8 @@ int jh_op_sensor_to_bgr(const uint8_t* frames_dev, const jh_sensor_surface* surf
                         uint8_t* out_bgr_dev, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   JH_REQUIRE(frames_dev && out_bgr_dev && n >= 1, "null frame / output pointer");
-  if (sensor_surface_check(surface, h, w)) return 1;
-  if (launch_sensor_to_bgr(frames_dev, sensor_surface_args(*surface, h, w), out_bgr_dev, n, h, w, s)) return 1;
+  FrameSource fs;
+  if (frame_source(surface, h, w, &fs) || launch_frames_to_bgr(frames_dev, fs, out_bgr_dev, n, h, w, s)) return 1;
   JH_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -25,8 +25,7 @@ namespace jh {
 template <int SRC>
 __global__ __launch_bounds__(256) void preprocess_resize_kernel(
     const void* __restrict__ frames, float* __restrict__ out, int N, int H, int W, int S,
-    float sy, float sx, float3 mean, float3 stdv, const void* const* __restrict__ frames_cell, YuvSurface ys,
-    SensorSurface ss) {
+    float sy, float sx, float3 mean, float3 stdv, const void* const* __restrict__ frames_cell, SrcDesc<SRC> d) {
   // graph replays: the frame pointer of THIS call is read from a device cell (a captured launch
   // would otherwise keep the pointer of the call it was captured on)
   if (frames_cell) frames = *frames_cell;
@@ -34,34 +33,23 @@ __global__ __launch_bounds__(256) void preprocess_resize_kernel(
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (size_t)gridDim.x * blockDim.x) {
     const int ox = (int)(i % S), oy = (int)((i / S) % S), n = (int)(i / ((size_t)S * S));
-    *reinterpret_cast<float4*>(out + i * 4) = resize_px<SRC>(frames, n, oy, ox, H, W, sy, sx, mean, stdv, ys, ss);
+    *reinterpret_cast<float4*>(out + i * 4) = resize_px<SRC>(frames, n, oy, ox, H, W, sy, sx, mean, stdv, d);
   }
 }
 
-int launch_preprocess_resize(const void* frames, int fmt, float* out, int N, int H, int W, int S,
+int launch_preprocess_resize(const void* frames, const FrameSource& src, float* out, int N, int H, int W, int S,
                              const float* mean, const float* stdv, hipStream_t s,
-                             const void* const* frames_cell, const YuvSurface* surface,
-                             const SensorSurface* sensor) {
+                             const void* const* frames_cell) {
   const size_t total = (size_t)N * S * S;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 8192) blocks = 8192;
   const float3 m = make_float3(mean[0], mean[1], mean[2]), sd = make_float3(stdv[0], stdv[1], stdv[2]);
-  JH_REQUIRE(fmt >= kSrcRgbF32 && fmt <= kSrcSensor && (fmt != kSrcYuvSurface || surface) &&
-                 (fmt != kSrcSensor || sensor), "frame format");
-  const YuvSurface ys = surface ? *surface : YuvSurface{};
-  const SensorSurface ss = sensor ? *sensor : SensorSurface{};
-#define JH_RESIZE(F)                                                                                         \
-  hipLaunchKernelGGL(preprocess_resize_kernel<F>, dim3(blocks), dim3(256), 0, s, frames, out, N, H, W, S,    \
-                     (float)H / (float)S, (float)W / (float)S, m, sd, frames_cell, ys, ss)
-  switch (fmt) {
-    case kSrcRgbF32: JH_RESIZE(kSrcRgbF32); break;
-    case kSrcBgrU8: JH_RESIZE(kSrcBgrU8); break;
-    case kSrcI420: JH_RESIZE(kSrcI420); break;
-    case kSrcNV12: JH_RESIZE(kSrcNV12); break;
-    case kSrcYuvSurface: JH_RESIZE(kSrcYuvSurface); break;
-    default: JH_RESIZE(kSrcSensor); break;
-  }
-#undef JH_RESIZE
+  if (dispatch_src(src, [&](auto tag, const auto& d) {
+        hipLaunchKernelGGL(preprocess_resize_kernel<decltype(tag)::value>, dim3(blocks), dim3(256), 0, s, frames, out,
+                           N, H, W, S, (float)H / (float)S, (float)W / (float)S, m, sd, frames_cell, d);
+        return 0;
+      }))
+    return 1;
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -71,7 +59,7 @@ template <int SRC>
 __global__ __launch_bounds__(256) void preprocess_crop_kernel(
     const void* __restrict__ frames, const int* __restrict__ center_hm, float* __restrict__ out,
     int T, int Cloc, int C, int cam0, int H, int W, int B, float3 mean, float3 stdv,
-    const void* const* __restrict__ frames_cell, YuvSurface ys, SensorSurface ss) {
+    const void* const* __restrict__ frames_cell, SrcDesc<SRC> d) {
   if (frames_cell) frames = *frames_cell;
   const size_t total = (size_t)T * Cloc * B * B;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -80,119 +68,65 @@ __global__ __launch_bounds__(256) void preprocess_crop_kernel(
     const int n = (int)(i / ((size_t)B * B));
     const int t = n / Cloc, cl = n % Cloc;
     const int cx = center_hm[(t * C + cam0 + cl) * 2 + 0], cy = center_hm[(t * C + cam0 + cl) * 2 + 1];
-    *reinterpret_cast<float4*>(out + i * 4) = crop_px<SRC>(frames, n, cx, cy, oy, ox, H, W, B, mean, stdv, ys,
-                                                            ss);
+    *reinterpret_cast<float4*>(out + i * 4) = crop_px<SRC>(frames, n, cx, cy, oy, ox, H, W, B, mean, stdv, d);
   }
 }
 
-int launch_preprocess_crop(const void* frames, int fmt, const int* center_hm, float* out, int T,
+int launch_preprocess_crop(const void* frames, const FrameSource& src, const int* center_hm, float* out, int T,
                            int Cloc, int C, int cam0, int H, int W, int B, const float* mean,
-                           const float* stdv, hipStream_t s, const void* const* frames_cell,
-                           const YuvSurface* surface, const SensorSurface* sensor) {
+                           const float* stdv, hipStream_t s, const void* const* frames_cell) {
   const size_t total = (size_t)T * Cloc * B * B;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 8192) blocks = 8192;
   const float3 m = make_float3(mean[0], mean[1], mean[2]), sd = make_float3(stdv[0], stdv[1], stdv[2]);
-  JH_REQUIRE(fmt >= kSrcRgbF32 && fmt <= kSrcSensor && (fmt != kSrcYuvSurface || surface) &&
-                 (fmt != kSrcSensor || sensor), "frame format");
-  const YuvSurface ys = surface ? *surface : YuvSurface{};
-  const SensorSurface ss = sensor ? *sensor : SensorSurface{};
-#define JH_CROP(F)                                                                                            \
-  hipLaunchKernelGGL(preprocess_crop_kernel<F>, dim3(blocks), dim3(256), 0, s, frames, center_hm, out, T, Cloc, \
-                     C, cam0, H, W, B, m, sd, frames_cell, ys, ss)
-  switch (fmt) {
-    case kSrcRgbF32: JH_CROP(kSrcRgbF32); break;
-    case kSrcBgrU8: JH_CROP(kSrcBgrU8); break;
-    case kSrcI420: JH_CROP(kSrcI420); break;
-    case kSrcNV12: JH_CROP(kSrcNV12); break;
-    case kSrcYuvSurface: JH_CROP(kSrcYuvSurface); break;
-    default: JH_CROP(kSrcSensor); break;
-  }
-#undef JH_CROP
+  if (dispatch_src(src, [&](auto tag, const auto& d) {
+        hipLaunchKernelGGL(preprocess_crop_kernel<decltype(tag)::value>, dim3(blocks), dim3(256), 0, s, frames,
+                           center_hm, out, T, Cloc, C, cam0, H, W, B, m, sd, frames_cell, d);
+        return 0;
+      }))
+    return 1;
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
-// YUV 4:2:0 (SRC 2 / 3) -> [N][H][W][3] uint8 BGR through the conversion the resize / crop use (yuv420_px): the
-// unit-test form of that device function.  One thread per output pixel.
+// A YUV 4:2:0 or raw sensor form (SRC 2 .. 5) -> [N][H][W][3] uint8 BGR through the pixel function the resize / crop
+// use (rgb8_px): the unit-test form of yuv420_px, yuv_surface_px and sensor_px.  One thread per output pixel; only
+// plane bytes resp. the H x W samples are read.
 template <int SRC>
-__global__ __launch_bounds__(256) void yuv420_to_bgr_kernel(const void* __restrict__ frames,
-                                                            unsigned char* __restrict__ out, int N, int H, int W) {
-  const size_t total = (size_t)N * H * W;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (size_t)gridDim.x * blockDim.x) {
-    const int x = (int)(i % W), y = (int)((i / W) % H);
-    const size_t n = i / ((size_t)H * W);
-    const Rgb8 p = yuv420_px<SRC>(frames, n, y, x, H, W);
-    out[i * 3 + 0] = (unsigned char)p.b;
-    out[i * 3 + 1] = (unsigned char)p.g;
-    out[i * 3 + 2] = (unsigned char)p.r;
-  }
-}
-
-int launch_yuv420_to_bgr(const void* frames, int fmt, unsigned char* out, int N, int H, int W, hipStream_t s) {
-  JH_REQUIRE(fmt == kSrcI420 || fmt == kSrcNV12, "YUV 4:2:0 format");
-  JH_REQUIRE(N >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "YUV 4:2:0 frames need an even height and width");
-  const size_t total = (size_t)N * H * W;
-  int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  if (fmt == kSrcI420)
-    hipLaunchKernelGGL(yuv420_to_bgr_kernel<kSrcI420>, dim3(blocks), dim3(256), 0, s, frames, out, N, H, W);
-  else
-    hipLaunchKernelGGL(yuv420_to_bgr_kernel<kSrcNV12>, dim3(blocks), dim3(256), 0, s, frames, out, N, H, W);
-  JH_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// A described YUV 4:2:0 surface (SRC 4) -> [N][H][W][3] uint8 BGR through yuv_surface_px: the unit-test form of
-// that device function.  One thread per output pixel; only plane bytes are read.
-__global__ __launch_bounds__(256) void yuv_surface_to_bgr_kernel(const void* __restrict__ frames,
-                                                                 unsigned char* __restrict__ out, int N, int H, int W,
-                                                                 YuvSurface ys) {
-  const size_t total = (size_t)N * H * W;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (size_t)gridDim.x * blockDim.x) {
-    const int x = (int)(i % W), y = (int)((i / W) % H);
-    const size_t n = i / ((size_t)H * W);
-    const Rgb8 p = yuv_surface_px(frames, n, y, x, ys);
-    out[i * 3 + 0] = (unsigned char)p.b;
-    out[i * 3 + 1] = (unsigned char)p.g;
-    out[i * 3 + 2] = (unsigned char)p.r;
-  }
-}
-
-int launch_yuv_surface_to_bgr(const void* frames, const YuvSurface& ys, unsigned char* out, int N, int H, int W,
-                              hipStream_t s) {
-  JH_REQUIRE(N >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "YUV 4:2:0 frames need an even height and width");
-  const size_t total = (size_t)N * H * W;
-  int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(yuv_surface_to_bgr_kernel, dim3(blocks), dim3(256), 0, s, frames, out, N, H, W, ys);
-  JH_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// A raw sensor surface (SRC 5) -> [N][H][W][3] uint8 BGR through sensor_px: the unit-test form of that device
-// function.  One thread per output pixel; only the H x W samples are read (ss.h, ss.w are H, W).
-__global__ __launch_bounds__(256) void sensor_to_bgr_kernel(const void* __restrict__ frames,
+__global__ __launch_bounds__(256) void frames_to_bgr_kernel(const void* __restrict__ frames,
                                                             unsigned char* __restrict__ out, int N, int H, int W,
-                                                            SensorSurface ss) {
+                                                            SrcDesc<SRC> d) {
   const size_t total = (size_t)N * H * W;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (size_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % W), y = (int)((i / W) % H);
     const size_t n = i / ((size_t)H * W);
-    const Rgb8 p = sensor_px(frames, n, y, x, ss);
+    const Rgb8 p = rgb8_px<SRC>(frames, n, y, x, H, W, d);
     out[i * 3 + 0] = (unsigned char)p.b;
     out[i * 3 + 1] = (unsigned char)p.g;
     out[i * 3 + 2] = (unsigned char)p.r;
   }
 }
 
-int launch_sensor_to_bgr(const void* frames, const SensorSurface& ss, unsigned char* out, int N, int H, int W,
+int launch_frames_to_bgr(const void* frames, const FrameSource& src, unsigned char* out, int N, int H, int W,
                          hipStream_t s) {
-  JH_REQUIRE(N >= 1 && H >= 1 && W >= 1 && ss.h == H && ss.w == W, "raw sensor frames: image size");
   const size_t total = (size_t)N * H * W;
-  int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(sensor_to_bgr_kernel, dim3(blocks), dim3(256), 0, s, frames, out, N, H, W, ss);
+  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  if (dispatch_src(src, [&](auto tag, const auto& d) {
+        constexpr int SRC = decltype(tag)::value;
+        if constexpr (!kIsRgb8<SRC>) {
+          JH_REQUIRE(kIsRgb8<SRC>, "YUV 4:2:0 format");
+        } else {
+          if constexpr (SRC == kSrcSensor)
+            JH_REQUIRE(N >= 1 && H >= 1 && W >= 1 && d.h == H && d.w == W, "raw sensor frames: image size");
+          else
+            JH_REQUIRE(N >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0,
+                       "YUV 4:2:0 frames need an even height and width");
+          hipLaunchKernelGGL(frames_to_bgr_kernel<SRC>, dim3(blocks), dim3(256), 0, s, frames, out, N, H, W, d);
+        }
+        return 0;
+      }))
+    return 1;
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -19,18 +19,13 @@ int launch_reproject(const float* cam, const float* intr, const float* dist, con
                      const int* center_hm, const float* heat, float2* coarse, float* vol,
                      int* idx_out, int T, int C, int G, float spacing, int hs, int Jp,
                      int heat_pad, int div255, hipStream_t s, const HeatLayout* layout = nullptr);
-int launch_preprocess_resize(const void* frames, int fmt, float* out, int N, int H, int W, int S,
+int launch_preprocess_resize(const void* frames, const FrameSource& src, float* out, int N, int H, int W, int S,
                              const float* mean, const float* stdv, hipStream_t s,
-                             const void* const* frames_cell = nullptr, const YuvSurface* surface = nullptr,
-                             const SensorSurface* sensor = nullptr);
-int launch_preprocess_crop(const void* frames, int fmt, const int* center_hm, float* out, int T,
+                             const void* const* frames_cell = nullptr);
+int launch_preprocess_crop(const void* frames, const FrameSource& src, const int* center_hm, float* out, int T,
                            int Cloc, int C, int cam0, int H, int W, int B, const float* mean,
-                           const float* stdv, hipStream_t s, const void* const* frames_cell = nullptr,
-                           const YuvSurface* surface = nullptr, const SensorSurface* sensor = nullptr);
-int launch_yuv420_to_bgr(const void* frames, int fmt, unsigned char* out, int N, int H, int W, hipStream_t s);
-int launch_yuv_surface_to_bgr(const void* frames, const YuvSurface& ys, unsigned char* out, int N, int H, int W,
-                              hipStream_t s);
-int launch_sensor_to_bgr(const void* frames, const SensorSurface& ss, unsigned char* out, int N, int H, int W,
+                           const float* stdv, hipStream_t s, const void* const* frames_cell = nullptr);
+int launch_frames_to_bgr(const void* frames, const FrameSource& src, unsigned char* out, int N, int H, int W,
                          hipStream_t s);
 int launch_center_argmax(const float* heat, float* det, int N, int Hh, int Wh, int Cp,
                          hipStream_t s);

@@ -2,26 +2,41 @@
 // normalise, :168-178 crop + normalise), shared by the stand-alone kernels (geometry.hip) and the stem
 // convolution that applies it while staging its input patch (stem.hip): ONE definition, so the fused
 // and the unfused path produce the same bits.
+//
+// The frames come in one of six SOURCE FORMS (SRC, the kSrc* codes; 0 .. 3 are JH_FRAME_* of include/jarvis_hip.h):
+//   0 kSrcRgbF32      [N][3][H][W] fp32 RGB in [0,1] (the API input of JarvisPredictor3D.forward);
+//   1 kSrcBgrU8       [N][H][W][3] uint8 BGR as the video decoder delivers it, converted like predict3D.py:79-80
+//                     (`.float()...[:, [2,1,0]] / 255.`) on the fly, so the 4x larger fp32 frame never exists;
+//   2 kSrcI420        YUV 4:2:0, one contiguous [3H/2][W] byte image per camera (H, W even): the Y plane [H][W],
+//                     then U [H/2][W/2], then V [H/2][W/2];
+//   3 kSrcNV12        the Y plane, then one interleaved [H/2][W/2][2] plane, U first.  A YUV pixel is converted to
+//                     the BGR bytes cv2.cvtColor(COLOR_YUV2BGR_I420 / _NV12) gives (yuv420_px) and those bytes enter
+//                     the uint8 arithmetic unchanged; layout and constants are compile-time immediates;
+//   4 kSrcYuvSurface  a described YUV 4:2:0 surface (jh_yuv_surface): plane offsets, pitches, the chroma order and
+//                     step, and the colour matrix / range come with the launch (YuvSurface), so pitched decoder
+//                     surfaces, YV12 / NV21 and BT.709 / full-range streams are read in place (yuv_surface_px);
+//   5 kSrcSensor      a raw sensor image (jh_sensor_surface): one byte per pixel, Mono8 or an 8-bit Bayer mosaic,
+//                     demosaiced per fetched pixel (sensor_px); the (R, G, B) bytes enter the uint8 arithmetic
+//                     unchanged, as the YUV forms' bytes do.
+//
+// A source form is four local things, and a new one adds exactly these:
+//   1. its description: a specialisation of SrcDesc<SRC> (what a kernel of that form takes BY VALUE -- wave-uniform,
+//      so it stays in scalar registers; a form that needs none keeps the empty primary template) with a field-wise
+//      operator==, and its alternative in FrameSource::desc;
+//   2. its pixel function, selected in rgb8_px<SRC> (a form delivering (R, G, B) bytes) or frame_px<SRC>;
+//   3. its row in dispatch_src, the one place a run-time format code becomes a template argument: the resize, the
+//      crop, the fused stem and the to-BGR launchers all instantiate through it;
+//   4. its host constructor in api.hip (frame_source), which validates what the caller gave and builds the FrameSource
+//      every layer below takes.
+// Nothing else names a form: the kernels, StemSource and the predictor's graph slots carry a SrcDesc<SRC> resp. a
+// FrameSource whatever it holds.
 #pragma once
+#include <type_traits>
+#include <variant>
 #include "jh_common.h"
 
 namespace jh {
 
-// Four frame formats: SRC = 0: [N][3][H][W] fp32 RGB in [0,1] (the API input of
-// JarvisPredictor3D.forward); SRC = 1: [N][H][W][3] uint8 BGR as the video decoder
-// delivers it, converted like predict3D.py:79-80 (`.float()...[:, [2,1,0]] / 255.`) on
-// the fly, so the 4x larger fp32 frame never exists; SRC = 2 / 3: YUV 4:2:0 as decoders
-// produce it natively, one contiguous [3H/2][W] byte image per camera (H, W even):
-// SRC = 2 (I420): the Y plane [H][W], then U [H/2][W/2], then V [H/2][W/2];
-// SRC = 3 (NV12): the Y plane, then one interleaved [H/2][W/2][2] plane, U first.
-// A YUV pixel is converted to the BGR bytes cv2.cvtColor(COLOR_YUV2BGR_I420 / _NV12) gives
-// (yuv420_px) and those bytes enter the uint8 arithmetic unchanged.
-// SRC = 4 (a described YUV 4:2:0 surface, jh_yuv_surface of include/jarvis_hip.h): plane offsets, pitches, the
-// chroma order and step, and the colour matrix / range come with the launch (YuvSurface below), so pitched decoder
-// surfaces, YV12 / NV21 and BT.709 / full-range streams are read in place (yuv_surface_px).
-// SRC = 5 (a raw sensor image, jh_sensor_surface of include/jarvis_hip.h): one byte per pixel as a machine-vision
-// camera delivers it, Mono8 or an 8-bit Bayer mosaic, demosaiced per fetched pixel (sensor_px); the (R, G, B) bytes
-// enter the uint8 arithmetic unchanged, as the YUV forms' bytes do.
 enum { kSrcRgbF32 = 0, kSrcBgrU8 = 1, kSrcI420 = 2, kSrcNV12 = 3, kSrcYuvSurface = 4, kSrcSensor = 5 };
 template <int SRC> constexpr bool kIsYuv = SRC == kSrcI420 || SRC == kSrcNV12 || SRC == kSrcYuvSurface;
 // the forms whose pixel is converted once to (R, G, B) bytes for all three channels
@@ -82,6 +97,11 @@ struct YuvSurface {
   int c_step = 1;
   int pair = 0;                // c_step == 2 and image_stride even: U, V of a block in one aligned 2-byte load
   int y0 = 16, cy = 0, cvr = 0, cub = 0, cug = 0, cvg = 0;
+  bool operator==(const YuvSurface& o) const {
+    return image_stride == o.image_stride && y_offset == o.y_offset && y_pitch == o.y_pitch &&
+           u_offset == o.u_offset && v_offset == o.v_offset && c_pitch == o.c_pitch && c_step == o.c_step &&
+           pair == o.pair && y0 == o.y0 && cy == o.cy && cvr == o.cvr && cub == o.cub && cug == o.cug && cvg == o.cvg;
+  }
 };
 
 // yuv_to_rgb8 with the constants of the surface's (matrix, range): the same scheme, int32 throughout (every
@@ -116,13 +136,16 @@ __device__ __forceinline__ Rgb8 yuv_surface_px(const void* frames, size_t n, int
 }
 
 // A raw sensor surface as the kernels take it: the layout of a jh_sensor_surface the host has checked
-// (jh_sensor_surface_check) with the image size.  Passed BY VALUE in the kernel arguments, next to YuvSurface: every
+// (jh_sensor_surface_check) with the image size.  Passed BY VALUE in the kernel arguments, as YuvSurface is: every
 // field is wave-uniform and stays in scalar registers.
 struct SensorSurface {
   long long image_stride = 0, offset = 0, pitch = 0;
   int pattern = 0;             // JH_SENSOR_*: 0 mono, 1 rggb, 2 bggr, 3 grbg, 4 gbrg
   int h = 0, w = 0;            // Bayer: even and >= 4, so the clamp below has an interior to clamp to
-  int reserved = 0;            // (no padding bytes: a recording's description is compared bytewise)
+  bool operator==(const SensorSurface& o) const {
+    return image_stride == o.image_stride && offset == o.offset && pitch == o.pitch && pattern == o.pattern &&
+           h == o.h && w == o.w;
+  }
 };
 
 // pixel (y, x) of raw image n (SRC 5).  mono: the byte, three times.  Bayer: the bilinear demosaic defined in
@@ -153,16 +176,31 @@ __device__ __forceinline__ Rgb8 sensor_px(const void* frames, size_t n, int y, i
   return py == 0 ? Rgb8{lr, own, ab} : Rgb8{ab, own, lr};
 }
 
+// The description a kernel of source form SRC takes by value: the surface of the two described forms, nothing (an
+// empty class) for the four whose layout follows from (H, W).
+template <int SRC> struct SrcDesc {
+  bool operator==(const SrcDesc&) const { return true; }
+};
+template <> struct SrcDesc<kSrcYuvSurface> : YuvSurface {};
+template <> struct SrcDesc<kSrcSensor> : SensorSurface {};
+
+// pixel (y, x) of image n as (R, G, B) bytes: the forms that convert once for all three channels
+template <int SRC>
+__device__ __forceinline__ Rgb8 rgb8_px(const void* frames, size_t n, int y, int x, int H, int W,
+                                        const SrcDesc<SRC>& d) {
+  static_assert(kIsRgb8<SRC>, "rgb8_px: YUV and raw sensor formats only");
+  if constexpr (SRC == kSrcSensor) return sensor_px(frames, n, y, x, d);
+  else if constexpr (SRC == kSrcYuvSurface) return yuv_surface_px(frames, n, y, x, d);
+  else return yuv420_px<SRC>(frames, n, y, x, H, W);
+}
+
 // the three channels (r, g, b) of one pixel as the uint8 path scales them; YUV and raw sensor forms: one conversion
-// for all three channels (ys / ss: the surface of SRC 4 / SRC 5, unused by the other formats)
+// for all three channels
 template <int SRC>
 __device__ __forceinline__ void frame_px3(const void* frames, size_t n, int y, int x, int H, int W,
-                                          const YuvSurface& ys, const SensorSurface& ss, float v[3]) {
+                                          const SrcDesc<SRC>& d, float v[3]) {
   if constexpr (kIsRgb8<SRC>) {
-    Rgb8 p;
-    if constexpr (SRC == kSrcSensor) p = sensor_px(frames, n, y, x, ss);
-    else if constexpr (SRC == kSrcYuvSurface) p = yuv_surface_px(frames, n, y, x, ys);
-    else p = yuv420_px<SRC>(frames, n, y, x, H, W);
+    const Rgb8 p = rgb8_px<SRC>(frames, n, y, x, H, W, d);
     const float k = __fdiv_rn(1.f, 255.f);
     v[0] = __fmul_rn((float)p.r, k); v[1] = __fmul_rn((float)p.g, k); v[2] = __fmul_rn((float)p.b, k);
   } else {
@@ -175,8 +213,7 @@ __device__ __forceinline__ void frame_px3(const void* frames, size_t n, int y, i
 // align_corners = False, no antialias), then (x - mean) / std; (r, g, b, 0)
 template <int SRC>
 __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, int ox, int H, int W, float sy,
-                                            float sx, float3 mean, float3 stdv, const YuvSurface& ys,
-                                            const SensorSurface& ss) {
+                                            float sx, float3 mean, float3 stdv, const SrcDesc<SRC>& d) {
   float ry = fmaxf(__fsub_rn(__fmul_rn(sy, __fadd_rn((float)oy, 0.5f)), 0.5f), 0.f);
   float rx = fmaxf(__fsub_rn(__fmul_rn(sx, __fadd_rn((float)ox, 0.5f)), 0.5f), 0.f);
   int y0 = min((int)floorf(ry), H - 1), x0 = min((int)floorf(rx), W - 1);
@@ -189,8 +226,8 @@ __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, i
   // below is that of the uint8 path, so the result equals SRC 1 on the converted bytes bit for bit)
   float q00[3], q01[3], q10[3], q11[3];
   if constexpr (kIsRgb8<SRC>) {
-    frame_px3<SRC>(frames, n, y0, x0, H, W, ys, ss, q00); frame_px3<SRC>(frames, n, y0, x1, H, W, ys, ss, q01);
-    frame_px3<SRC>(frames, n, y1, x0, H, W, ys, ss, q10); frame_px3<SRC>(frames, n, y1, x1, H, W, ys, ss, q11);
+    frame_px3<SRC>(frames, n, y0, x0, H, W, d, q00); frame_px3<SRC>(frames, n, y0, x1, H, W, d, q01);
+    frame_px3<SRC>(frames, n, y1, x0, H, W, d, q10); frame_px3<SRC>(frames, n, y1, x1, H, W, d, q11);
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -214,8 +251,7 @@ __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, i
 // crop centre is clamped; kept for safety as the stand-alone kernel has it)
 template <int SRC>
 __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int cy, int oy, int ox, int H,
-                                          int W, int B, float3 mean, float3 stdv, const YuvSurface& ys,
-                                          const SensorSurface& ss) {
+                                          int W, int B, float3 mean, float3 stdv, const SrcDesc<SRC>& d) {
   const int hw = B / 2;
   const int ix = cx - hw + ox, iy = cy - hw + oy;
   const float mv[3] = {mean.x, mean.y, mean.z}, sv[3] = {stdv.x, stdv.y, stdv.z};
@@ -224,7 +260,7 @@ __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int
   if constexpr (kIsRgb8<SRC>) {
     // (outside the frame: 0 before the normalisation, as for the other formats -- not the conversion of Y = U = V = 0)
     float q[3] = {0.f, 0.f, 0.f};
-    if (ok) frame_px3<SRC>(frames, n, iy, ix, H, W, ys, ss, q);
+    if (ok) frame_px3<SRC>(frames, n, iy, ix, H, W, d, q);
 #pragma unroll
     for (int c = 0; c < 3; ++c) r[c] = __fdiv_rn(__fsub_rn(q[c], mv[c]), sv[c]);
   } else {
@@ -237,14 +273,53 @@ __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int
   return make_float4(r[0], r[1], r[2], 0.f);
 }
 
+// ---------------------------------------------------------------------------------------------------- host side
+// Where a call's frames come from: the format code and the description that format has.  Built (and validated) by the
+// frame_source constructors of api.hip; everything between the C entry point and a kernel launch takes this.
+struct FrameSource {
+  int fmt = kSrcRgbF32;                                                                  // kSrc*
+  std::variant<std::monostate, SrcDesc<kSrcYuvSurface>, SrcDesc<kSrcSensor>> desc;       // monostate: fmt needs none
+  bool operator==(const FrameSource& o) const { return fmt == o.fmt && desc == o.desc; }
+  bool operator!=(const FrameSource& o) const { return !(*this == o); }
+  // bytes of frame data per source pixel: fp32 RGB 12, uint8 BGR 3, YUV 4:2:0 1.5, raw sensor 1
+  double px_bytes() const {
+    return fmt == kSrcRgbF32 ? 12.0 : fmt == kSrcBgrU8 ? 3.0 : fmt == kSrcSensor ? 1.0 : 1.5;
+  }
+};
+
+// The one place a run-time format code becomes a template argument: f(SrcTag<SRC>{}, const SrcDesc<SRC>&) -> int
+// for the form src holds; an unknown code, or a described form without its description, is an error.
+template <int SRC> using SrcTag = std::integral_constant<int, SRC>;
+template <class F>
+int dispatch_src(const FrameSource& src, F&& f) {
+  const auto row = [&](auto tag) -> int {
+    constexpr int SRC = decltype(tag)::value;
+    if constexpr (std::is_empty_v<SrcDesc<SRC>>) {
+      return f(tag, SrcDesc<SRC>{});
+    } else {
+      const SrcDesc<SRC>* d = std::get_if<SrcDesc<SRC>>(&src.desc);
+      JH_REQUIRE(d, "a described surface comes with its own frame format");
+      return f(tag, *d);
+    }
+  };
+  switch (src.fmt) {
+    case kSrcRgbF32: return row(SrcTag<kSrcRgbF32>{});
+    case kSrcBgrU8: return row(SrcTag<kSrcBgrU8>{});
+    case kSrcI420: return row(SrcTag<kSrcI420>{});
+    case kSrcNV12: return row(SrcTag<kSrcNV12>{});
+    case kSrcYuvSurface: return row(SrcTag<kSrcYuvSurface>{});
+    case kSrcSensor: return row(SrcTag<kSrcSensor>{});
+  }
+  set_error("requirement failed: src.fmt is no kSrc* code (frame format)");
+  return 1;
+}
+
 // What the stem convolution reads when the pre-processing is fused into its patch staging.
 struct StemSource {
   int mode = 0;               // 0: the plan's own input tensor; 1: resize of the frames; 2: crop of the frames
   const void* frames = nullptr;
   const void* const* frames_cell = nullptr;    // graph replays: the frame pointer of the current call
-  int fmt = 0;                                 // frame format: SRC of preprocess.h (kSrc*)
-  YuvSurface yuv;                              // fmt == kSrcYuvSurface: the surface the frames are read through
-  SensorSurface sensor;                        // fmt == kSrcSensor: the raw surface the frames are read through
+  FrameSource source;                          // the form of the frames and its description
   const int* center_hm = nullptr;              // crop: [T][C][2]
   int Cloc = 0, C = 0, cam0 = 0;               // crop: image n = (t, local camera)
   int H = 0, W = 0;                            // frame size

@@ -31,6 +31,7 @@ typedef float sf2 __attribute__((ext_vector_type(2)));
 typedef float sf4 __attribute__((ext_vector_type(4)));
 }  // namespace
 
+template <int SRC>
 struct StemSrcArgs {           // MODE != 0: the frames this launch pre-processes on the fly
   const void* frames;
   const void* const* frames_cell;
@@ -38,15 +39,14 @@ struct StemSrcArgs {           // MODE != 0: the frames this launch pre-processe
   int Cloc, C, cam0, FH, FW;
   float sy, sx;
   float3 mean, stdv;
-  YuvSurface yuv;              // SRC == kSrcYuvSurface: the described surface (uniform: scalar registers)
-  SensorSurface sensor;        // SRC == kSrcSensor: the raw sensor surface (likewise)
+  SrcDesc<SRC> desc;           // the form's description (uniform: scalar registers); MODE == 0: the empty one
 };
 
 template <int MODE, int SRC, int CO = 16>
 __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict__ x,
                                                         const float* __restrict__ w /* [9][3][CO] */,
                                                         float* __restrict__ y, double* __restrict__ stats,
-                                                        int H, int W, StemSrcArgs sa) {
+                                                        int H, int W, StemSrcArgs<SRC> sa) {
   static_assert(CO == 16 || CO == 32, "stem output channels");
   // (the statistics scratch lies over the patch, which is dead once every thread has its 16 sums: 19.5 instead of
   //  35.8 KB of LDS = twice the workgroups per CU; the kernel is bound by the latency of its patch loads)
@@ -84,10 +84,8 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
       // (the convolution's zero padding lies outside the pre-processed image: zeros, not normalised zeros)
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (ok)
-        v = MODE == 1 ? resize_px<SRC>(frames, n, iy, ix, sa.FH, sa.FW, sa.sy, sa.sx, sa.mean, sa.stdv, sa.yuv,
-                                       sa.sensor)
-                      : crop_px<SRC>(frames, n, ccx, ccy, iy, ix, sa.FH, sa.FW, H, sa.mean, sa.stdv, sa.yuv,
-                                     sa.sensor);
+        v = MODE == 1 ? resize_px<SRC>(frames, n, iy, ix, sa.FH, sa.FW, sa.sy, sa.sx, sa.mean, sa.stdv, sa.desc)
+                      : crop_px<SRC>(frames, n, ccx, ccy, iy, ix, sa.FH, sa.FW, H, sa.mean, sa.stdv, sa.desc);
       patch[i] = v;
     }
   }
@@ -167,10 +165,10 @@ int launch_stem_conv(const Act& x, const float* w_dev, const Act& y, double* sta
   const int tiles = ((y.H + kStT - 1) / kStT) * ((y.W + kStT - 1) / kStT);
   if (y.Cp == 32)
     hipLaunchKernelGGL((stem_conv_kernel<0, 0, 32>), dim3(tiles, x.N), dim3(256), 0, s, x.p, w_dev, y.p, stats, x.H,
-                       x.W, StemSrcArgs{});
+                       x.W, StemSrcArgs<0>{});
   else
     hipLaunchKernelGGL((stem_conv_kernel<0, 0, 16>), dim3(tiles, x.N), dim3(256), 0, s, x.p, w_dev, y.p, stats, x.H,
-                       x.W, StemSrcArgs{});
+                       x.W, StemSrcArgs<0>{});
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -182,40 +180,33 @@ int launch_stem_conv_src(const StemSource& src, const Act& x, const float* w_dev
   JH_REQUIRE(src.mode == 1 || src.mode == 2, "stem source mode");
   JH_REQUIRE(x.Cp == 4 && (y.Cp == 16 || y.Cp == 32) && x.D == 1 && y.H * 2 == x.H && y.W * 2 == x.W && x.N == y.N &&
                  x.H == x.W, "stem convolution shapes");
-  StemSrcArgs sa{};
-  sa.frames = src.frames; sa.frames_cell = src.frames_cell; sa.center_hm = src.center_hm;
-  sa.Cloc = src.Cloc; sa.C = src.C; sa.cam0 = src.cam0; sa.FH = src.H; sa.FW = src.W;
-  sa.sy = (float)src.H / (float)x.H; sa.sx = (float)src.W / (float)x.W;        // (as launch_preprocess_resize)
-  sa.mean = make_float3(src.mean[0], src.mean[1], src.mean[2]);
-  sa.stdv = make_float3(src.stdv[0], src.stdv[1], src.stdv[2]);
-  sa.yuv = src.yuv; sa.sensor = src.sensor;
   const int tiles = ((y.H + kStT - 1) / kStT) * ((y.W + kStT - 1) / kStT);
   const dim3 grid(tiles, x.N);
   // (the fp32 resize form is bound by HBM on the frames it reads -- 2 of every 4 rows of 1280 x 1024 x 3 floats --
   //  and loses locality with more workgroups in flight: 654 -> 711 us at eight per CU; 16 KB of unused dynamic LDS
   //  keep it at four.  The other forms are latency-bound and want the eight.)
   const size_t pad_f32 = 16384;
-#define JH_STEM(M, U)                                                                                                   \
-  do {                                                                                                                  \
-    if (y.Cp == 32)                                                                                                     \
-      hipLaunchKernelGGL((stem_conv_kernel<M, U, 32>), grid, dim3(256), 0, s, x.p, w_dev, y.p, stats, x.H, x.W, sa);    \
-    else                                                                                                                \
-      hipLaunchKernelGGL((stem_conv_kernel<M, U, 16>), grid, dim3(256), (M == 1 && U == 0) ? pad_f32 : 0, s, x.p,       \
-                         w_dev, y.p, stats, x.H, x.W, sa);                                                              \
-  } while (0)
-  JH_REQUIRE(src.fmt >= kSrcRgbF32 && src.fmt <= kSrcSensor, "frame format");
-#define JH_STEM_FMT(M)                                     \
-  switch (src.fmt) {                                       \
-    case kSrcRgbF32: JH_STEM(M, kSrcRgbF32); break;        \
-    case kSrcBgrU8: JH_STEM(M, kSrcBgrU8); break;          \
-    case kSrcI420: JH_STEM(M, kSrcI420); break;            \
-    case kSrcNV12: JH_STEM(M, kSrcNV12); break;            \
-    case kSrcYuvSurface: JH_STEM(M, kSrcYuvSurface); break; \
-    default: JH_STEM(M, kSrcSensor); break;                \
-  }
-  if (src.mode == 1) { JH_STEM_FMT(1) } else { JH_STEM_FMT(2) }
-#undef JH_STEM_FMT
-#undef JH_STEM
+  const auto launch = [&](auto mode, auto tag, const auto& d) {
+    constexpr int M = decltype(mode)::value, U = decltype(tag)::value;
+    StemSrcArgs<U> sa{};
+    sa.frames = src.frames; sa.frames_cell = src.frames_cell; sa.center_hm = src.center_hm;
+    sa.Cloc = src.Cloc; sa.C = src.C; sa.cam0 = src.cam0; sa.FH = src.H; sa.FW = src.W;
+    sa.sy = (float)src.H / (float)x.H; sa.sx = (float)src.W / (float)x.W;      // (as launch_preprocess_resize)
+    sa.mean = make_float3(src.mean[0], src.mean[1], src.mean[2]);
+    sa.stdv = make_float3(src.stdv[0], src.stdv[1], src.stdv[2]);
+    sa.desc = d;
+    if (y.Cp == 32)
+      hipLaunchKernelGGL((stem_conv_kernel<M, U, 32>), grid, dim3(256), 0, s, x.p, w_dev, y.p, stats, x.H, x.W, sa);
+    else
+      hipLaunchKernelGGL((stem_conv_kernel<M, U, 16>), grid, dim3(256), (M == 1 && U == 0) ? pad_f32 : 0, s, x.p,
+                         w_dev, y.p, stats, x.H, x.W, sa);
+    return 0;
+  };
+  if (dispatch_src(src.source, [&](auto tag, const auto& d) {
+        return src.mode == 1 ? launch(std::integral_constant<int, 1>{}, tag, d)
+                             : launch(std::integral_constant<int, 2>{}, tag, d);
+      }))
+    return 1;
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }

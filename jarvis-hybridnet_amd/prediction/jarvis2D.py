@@ -39,20 +39,13 @@ class _Native2D:
             N.frame_layout(frame_layout, frame_format, (self.T,), (self.H, self.W), frames)
             if not (frames.is_cuda and frames.is_contiguous()):
                 raise RuntimeError("frames must be a contiguous CUDA (HIP) tensor")
-            N.check(N.layout_entry(frame_layout, "forward2d")(self.handle, N.ptr(frames), frame_layout.struct(),
-                                                              N.ptr(pts), N.ptr(conf), N.ptr(valid), N.stream()))
-            return pts, conf, valid
-        if frame_format in N.YUV_FORMATS:
+        elif frame_format in N.YUV_FORMATS:
             if tuple(frames.shape) != (self.T, self.H * 3 // 2, self.W) or frames.dtype != torch.uint8 \
                     or not frames.is_contiguous():
                 raise RuntimeError("%s frames %s, expected contiguous uint8 %s" % (
                     frame_format, (frames.dtype, tuple(frames.shape)), (self.T, self.H * 3 // 2, self.W)))
-            N.check(N.lib().jh_predictor2d_forward_yuv(self.handle, N.ptr(frames), N.FRAME_FORMATS[frame_format],
-                                                       N.ptr(pts), N.ptr(conf), N.ptr(valid), N.stream()))
-            return pts, conf, valid
-        fn = N.lib().jh_predictor2d_forward_u8 if frames.dtype == torch.uint8 else \
-            N.lib().jh_predictor2d_forward
-        N.check(fn(self.handle, N.ptr(frames), N.ptr(pts), N.ptr(conf), N.ptr(valid), N.stream()))
+        fn, fmt_args = N.forward_entry("jh_predictor2d", frames, frame_format, frame_layout)
+        N.check(fn(self.handle, N.ptr(frames), *fmt_args, N.ptr(pts), N.ptr(conf), N.ptr(valid), N.stream()))
         return pts, conf, valid
 
     def close(self):
