@@ -395,6 +395,43 @@ int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, co
                          const uint8_t* mask_dev, int32_t* points2d_dev, float* conf2d_dev, float* reproj_dev,
                          float* err_dev, uint8_t* used_dev, void* stream);
 
+/* Per-image frame pointers (ABI v4, additive): every camera's buffer read where its producer left it.  The entry
+ * points above take ONE base pointer with all T * num_cameras images at one constant distance; twelve decoder sessions
+ * or frame-grabber rings deliver twelve unrelated device pointers.  Here a call says where EACH image is.
+ * images_host: a HOST array of n_images = T * num_cameras device pointers (the 2D predictor: T), index t * C + c, each
+ * pointing at ONE image in the layout `format` gives a single image:
+ *   JH_FRAME_RGB_F32 (3,H,W) fp32, 4-byte aligned;   JH_FRAME_BGR_U8 (H,W,3) uint8;
+ *   JH_FRAME_I420 / JH_FRAME_NV12 (3H/2,W) uint8;
+ *   JH_FRAME_SURFACE: one image of the jh_yuv_surface `yuv`;   JH_FRAME_SENSOR: one image of the jh_sensor_surface
+ *   `sensor`.  Give exactly the description the format needs and NULL for the other (both NULL for the first four).
+ *   Of a description, image_stride keeps only its role as the extent every plane must end within.
+ * The byte forms may start at ANY address.  The one wider load of the fetch, the 2-byte chroma pair of NV12 and of
+ * semi-planar surfaces, is taken from an image at an even address; an image at an odd address reads the pair as two
+ * bytes (the kernels test the image's own pointer; nothing is demanded of the caller).
+ * Duplicate pointers are allowed.  Every entry, a masked camera's too, points at readable memory of one image: its 2D
+ * networks run, per image, and nothing of them reaches a result.
+ * The array is free again when the call returns: the pointers travel as kernel arguments (chunks of up to 256) into a
+ * table the predictor owns, on `stream` -- no staging buffer, no host synchronisation.  The launches read that table,
+ * so a graph-replaying predictor keeps replaying ONE recording per format while the pointers change from call to
+ * call.  The per-image form has graph slots of its OWN (per format, unmasked and masked): per-image and contiguous
+ * calls of one format may alternate freely and never re-record each other; as everywhere, a described call whose
+ * description differs from the recorded one records again.  Like the mask buffer the table belongs to the predictor:
+ * calls of one predictor go to one stream, or are ordered by the caller.
+ * The table (n_images pointers) is allocated by the first such call of a predictor -- never by *_create, so
+ * jh_predictor_device_bytes and the memory of a predictor that never uses it are unchanged -- and that first call
+ * must not be made inside a stream capture.
+ * Validation (non-zero with jh_last_error() set, nothing enqueued): n_images == T * num_cameras (2D: T); no NULL
+ * entry; fp32 images 4-byte aligned; exactly the description the format needs; the description passes
+ * jh_yuv_surface_check / jh_sensor_surface_check.
+ * Results: bit for bit those of the contiguous entry point of the format on the same images.  mask_dev as in
+ * jh_predictor_forward_masked, or NULL; jh_predictor_views2d follows the call as it follows any forward.
+ * Whole-path forwards only: the staged entry points (jh_predictor_stage_*) take one base pointer. */
+#define JH_FRAME_SURFACE  4   /* needs yuv    */
+#define JH_FRAME_SENSOR   5   /* needs sensor */
+int jh_predictor_forward_images(jh_predictor* pr, const void* const* images_host, int n_images, int format,
+                                const jh_yuv_surface* yuv, const jh_sensor_surface* sensor, const uint8_t* mask_dev,
+                                float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
+
 /* HybridNetBackbone.forward: crops (T,C,3,B,B) normalised NCHW dev, center_hm
  * (T,C,2) int32, center3d (T,3) int32 -> heatmap_final (T,J,Gh,Gh,Gh) optional,
  * heatmaps_padded (T,C,J,hs,hs) optional, points (T,J,3), conf (T,J). */
@@ -427,6 +464,11 @@ int jh_predictor2d_forward_surface(jh_predictor2d* pr, const uint8_t* frames_dev
                                    int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
 /* frames (T) raw sensor images (as jh_predictor_forward_sensor). */
 int jh_predictor2d_forward_sensor(jh_predictor2d* pr, const uint8_t* frames_dev, const jh_sensor_surface* surface,
+                                  int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
+
+/* images_host: T device pointers, one image each (as jh_predictor_forward_images, which see). */
+int jh_predictor2d_forward_images(jh_predictor2d* pr, const void* const* images_host, int n_images, int format,
+                                  const jh_yuv_surface* yuv, const jh_sensor_surface* sensor,
                                   int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
 
 /* ---- per-launch timing (HIP events on the launch stream; used by bench.py for

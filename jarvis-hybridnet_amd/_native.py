@@ -140,6 +140,12 @@ _SIGS = {
                                     c_void_p]),
     "jh_predictor_forward_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p]),
+    "jh_predictor_forward_images": (c_int, [c_void_p, ctypes.POINTER(c_void_p), c_int, c_int,
+                                            ctypes.POINTER(YuvSurfaceStruct), ctypes.POINTER(SensorSurfaceStruct),
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_predictor2d_forward_images": (c_int, [c_void_p, ctypes.POINTER(c_void_p), c_int, c_int,
+                                              ctypes.POINTER(YuvSurfaceStruct), ctypes.POINTER(SensorSurfaceStruct),
+                                              c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_stage_keypoints_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                                     c_void_p]),
     "jh_predictor_stage_3d_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -268,6 +274,73 @@ def forward_entry(which, frames, frame_format=None, layout=None, mask=None):
     if frame_format in YUV_FORMATS:
         return getattr(lib(), which + "_forward_yuv"), (fmt,)
     return getattr(lib(), which + ("_forward_u8" if fmt else "_forward")), ()
+
+
+FRAME_RGB_F32, FRAME_SURFACE, FRAME_SENSOR = 0, 4, 5      # JH_FRAME_* beside FRAME_FORMATS
+_checked_format, _checked_layout = frame_format, frame_layout   # (frame_images' arguments carry the public names)
+
+
+def frame_images(images, count, frame_format=None, frame_layout=None):
+    """The images of a per-image call (forward_images) checked, before anything reaches the GPU: `images` a sequence
+    of `count` tensors, each ONE image -- fp32 (3,H,W); uint8 (H,W,3); with frame_format 'i420' / 'nv12' uint8
+    (3H/2,W); with frame_layout a 1-D uint8 tensor of at least image_stride bytes -- all of one shape, dtype and
+    device, contiguous and on the GPU.  Nothing is copied: the tensors are read where they lie.
+    -> (format code JH_FRAME_*, (H, W), the checked layout or None).  ValueError for what does not fit the call
+    (count, mixed images, shapes, frame_layout with 'i420' / 'nv12'), RuntimeError for a CPU or a non-contiguous
+    tensor, as the contiguous forms raise them."""
+    frame_format = _checked_format(frame_format)
+    frame_layout = _checked_layout(frame_layout, frame_format, ())
+    if not isinstance(images, (list, tuple)) or len(images) != count:
+        raise ValueError("expected a sequence of %d images (one tensor per image); got %s" % (
+            count, len(images) if isinstance(images, (list, tuple)) else type(images).__name__))
+    for i, t in enumerate(images):
+        if not torch.is_tensor(t):
+            raise ValueError("image %d is a %s, not a tensor" % (i, type(t).__name__))
+        if (t.shape, t.dtype, t.device) != (images[0].shape, images[0].dtype, images[0].device):
+            raise ValueError("the images of a call have one shape, dtype and device: image %d is %s, image 0 is %s" % (
+                i, (t.dtype, tuple(t.shape), str(t.device)),
+                (images[0].dtype, tuple(images[0].shape), str(images[0].device))))
+    t = images[0]
+    if frame_layout is not None:
+        if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < frame_layout.image_stride:
+            raise ValueError("an image of a %s must be 1-D uint8 of at least image_stride = %d bytes; got %s" % (
+                type(frame_layout).__name__, frame_layout.image_stride, (t.dtype, tuple(t.shape))))
+        from .sensor_surface import SensorSurface
+        fmt = FRAME_SENSOR if isinstance(frame_layout, SensorSurface) else FRAME_SURFACE
+        hw = (frame_layout.height, frame_layout.width)
+    elif frame_format in YUV_FORMATS:
+        if t.dtype != torch.uint8 or t.dim() != 2:
+            raise ValueError("a %s image must be uint8 (3H/2, W); got %s" % (frame_format, (t.dtype, tuple(t.shape))))
+        fmt, hw = FRAME_FORMATS[frame_format], yuv_frame_hw(t.shape)
+    elif t.dtype == torch.uint8:
+        if t.dim() != 3 or t.shape[2] != 3:
+            hint = " (YUV 4:2:0 images: pass frame_format='i420' or 'nv12')" if t.dim() == 2 else ""
+            raise ValueError("a uint8 BGR image must be (H, W, 3); got %s%s" % (tuple(t.shape), hint))
+        fmt, hw = FRAME_FORMATS["bgr"], (int(t.shape[0]), int(t.shape[1]))
+    elif t.dtype == torch.float32 and frame_format is None:
+        if t.dim() != 3 or t.shape[0] != 3:
+            raise ValueError("an fp32 RGB image must be (3, H, W); got %s" % (tuple(t.shape),))
+        fmt, hw = FRAME_RGB_F32, (int(t.shape[1]), int(t.shape[2]))
+    else:
+        raise ValueError("an image must be float32 RGB (3,H,W) or uint8; frame_format 'bgr' needs uint8; got dtype %s"
+                         % (t.dtype,))
+    for i, t in enumerate(images):
+        if not t.is_contiguous():
+            raise RuntimeError("image %d is not contiguous: the kernels read it in place" % i)
+        if not t.is_cuda:
+            raise RuntimeError("jarvis_hybridnet_amd needs CUDA (HIP) tensors; image %d is a CPU tensor" % i)
+    return fmt, hw, frame_layout
+
+
+def image_table(images):
+    """The host array of device pointers jh_predictor*_forward_images takes (free again when the call returns)."""
+    return (c_void_p * len(images))(*(t.data_ptr() for t in images))
+
+
+def layout_args(fmt, layout):
+    """(yuv, sensor) of jh_predictor*_forward_images: the struct the format needs, NULL for the other."""
+    s = layout.struct() if layout is not None else None
+    return (s if fmt == FRAME_SURFACE else None, s if fmt == FRAME_SENSOR else None)
 
 
 def camera_mask(mask, shape, what="camera_mask"):

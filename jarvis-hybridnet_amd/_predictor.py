@@ -92,6 +92,26 @@ class NativePredictor:
             mask.record_stream(torch.cuda.current_stream())     # (free once the call is enqueued)
         return out
 
+    def forward_images(self, images, fmt, layout=None, out=None, camera_mask=None):
+        """forward() on T * C separately placed images: `images` the flat list (index t * C + c) that
+        _native.frame_images has checked, fmt / layout what it returned (jh_predictor_forward_images).  The images are
+        read where they lie; nothing is gathered."""
+        if len(images) != self.T * self.C:
+            raise ValueError("expected %d images (time_batch * num_cameras), got %d" % (self.T * self.C, len(images)))
+        camera_mask = N.camera_mask(camera_mask, (self.T, self.C))
+        dev = images[0].device
+        if out is None:
+            out = (torch.empty((self.T, self.J, 3), device=dev),
+                   torch.empty((self.T, self.J), device=dev),
+                   torch.empty((self.T,), device=dev, dtype=torch.int32))
+        mask = None if camera_mask is None else camera_mask.to(dev, non_blocking=True)   # (copied by the call)
+        N.check(N.lib().jh_predictor_forward_images(
+            self.handle, N.image_table(images), len(images), fmt, *N.layout_args(fmt, layout), N.ptr(mask),
+            N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.stream()))
+        if mask is not None and mask.is_cuda:
+            mask.record_stream(torch.cuda.current_stream())
+        return out
+
     def _check_frames(self, frames, cams, frame_format=None, frame_layout=None):
         """Raw pointers cross the C ABI: refuse anything whose bytes would be misread."""
         H, W = self.cfg.img_h, self.cfg.img_w

@@ -106,6 +106,14 @@ __global__ void det_unblock_kernel(const float* __restrict__ src, float* __restr
 
 // graph replays: this call's frame pointer into the device cell the captured kernels read it from
 __global__ void set_cell_kernel(const void** cell, const void* value) { *cell = value; }
+// per-image frames: up to kPtrChunk pointers of this call's table travel as kernel arguments into the predictor's
+// device table -- no staging buffer, nothing the host has to keep alive or wait for
+constexpr int kPtrChunk = 256;
+struct PtrChunk { const void* p[kPtrChunk]; };
+__global__ __launch_bounds__(kPtrChunk) void set_table_kernel(const void** table, int count, PtrChunk c) {
+  const int i = threadIdx.x;
+  if (i < count) table[i] = c.p[i];
+}
 // ... and the results out of the predictor's own buffers into this call's output tensors
 __global__ void copy_out_kernel(const float* __restrict__ gp, const float* __restrict__ gc,
                                 const int* __restrict__ gv, float* __restrict__ points,
@@ -372,6 +380,61 @@ static int frame_source(int format, int h, int w, FrameSource* out) {
   return 0;
 }
 
+static_assert(JH_FRAME_SURFACE == kSrcYuvSurface && JH_FRAME_SENSOR == kSrcSensor,
+              "frame format codes of the C ABI are preprocess.h's SRC");
+
+// FrameSource of a per-image call (jh_predictor_forward_images / jh_predictor2d_forward_images): `format` with exactly
+// the description it needs, checked as the contiguous entry points check it.  image_stride of a description is here
+// only the extent every plane ends within; every image is image 0 of its own pointer, so a semi-planar surface takes
+// the 2-byte chroma load whatever the parity of that extent (the kernel looks at the image's own base).
+static int images_source(int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor, int h, int w,
+                         FrameSource* out) {
+  JH_REQUIRE(format >= JH_FRAME_RGB_F32 && format <= JH_FRAME_SENSOR, "forward_images: unknown frame format");
+  JH_REQUIRE((yuv != nullptr) == (format == JH_FRAME_SURFACE),
+             "forward_images: JH_FRAME_SURFACE, and no other format, comes with a jh_yuv_surface");
+  JH_REQUIRE((sensor != nullptr) == (format == JH_FRAME_SENSOR),
+             "forward_images: JH_FRAME_SENSOR, and no other format, comes with a jh_sensor_surface");
+  if (format == JH_FRAME_SURFACE) {
+    if (frame_source(yuv, h, w, out)) return 1;
+    auto& d = std::get<SrcDesc<kSrcYuvSurface>>(out->desc);
+    d.pair = d.c_step == 2;
+  } else if (format == JH_FRAME_SENSOR) {
+    if (frame_source(sensor, h, w, out)) return 1;
+  } else if (frame_source(format, h, w, out)) {
+    return 1;
+  }
+  out->per_image = true;
+  return 0;
+}
+
+// The host table of a per-image call checked and sent into the predictor's device table (allocated by the first such
+// call of a predictor, never inside a stream capture) on the caller's stream.
+static int upload_images(Scratch& mem, const void*** table, const void* const* images_host, int n_images, int want,
+                         int format, hipStream_t s) {
+  JH_REQUIRE(images_host, "forward_images: null image table");
+  JH_REQUIRE(n_images == want, "forward_images: n_images must be time_batch * num_cameras (2D predictor: time_batch)");
+  for (int i = 0; i < n_images; ++i) {
+    JH_REQUIRE(images_host[i], "forward_images: a null image pointer");
+    JH_REQUIRE(format != JH_FRAME_RGB_F32 || reinterpret_cast<uintptr_t>(images_host[i]) % 4 == 0,
+               "forward_images: an fp32 image that is not 4-byte aligned");
+  }
+  if (!*table) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s, &cs);
+    JH_REQUIRE(cs == hipStreamCaptureStatusNone, "the first forward_images call of a predictor allocates its pointer "
+               "table: make it outside a stream capture");
+    if (mem.get(reinterpret_cast<void**>(table), (size_t)want * sizeof(void*))) return 1;
+  }
+  for (int off = 0; off < n_images; off += kPtrChunk) {
+    PtrChunk c{};
+    const int count = n_images - off < kPtrChunk ? n_images - off : kPtrChunk;
+    for (int i = 0; i < count; ++i) c.p[i] = images_host[off + i];
+    hipLaunchKernelGGL(set_table_kernel, dim3(1), dim3(kPtrChunk), 0, s, *table + off, count, c);
+  }
+  JH_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 struct jh_predictor {
   jh_predictor_config cfg{};
   int T3 = 0;
@@ -399,14 +462,21 @@ struct jh_predictor {
   int use_graph = 0;
   const void** frames_cell = nullptr;        // device: the frame pointer of the current call
   const void* const* cur_cell = nullptr;     // non-null only while the forward is being captured
+  // per-image frames (jh_predictor_forward_images): [T * C] device pointers, written on the caller's stream before
+  // every such forward; the launches, captured or not, read this table.  Allocated by the first such call.
+  const void** frames_table = nullptr;
+  // what a launch of source fs reads its frame pointer(s) through
+  const void* const* cell_for(const FrameSource& fs) const { return fs.per_image ? frames_table : cur_cell; }
   float *g_points = nullptr, *g_conf = nullptr;
   hipStream_t gstream = nullptr;             // capture stream (the caller's may be the null stream)
-  // One slot per frame format (kSrc*, preprocess.h); [kGraphFmts + fmt]: the masked form of that format.  A launch
+  // One slot per frame format (kSrc*, preprocess.h); [kGraphFmts + fmt]: the masked form of that format;
+  // [2 * kGraphFmts + ...]: the same again for the per-image form, which has slots of its OWN -- a stream of
+  // per-image calls and a stream of contiguous calls of one format never re-record each other.  A launch
   // carries its source's description by value, so a recording has ONE source: the slot keeps the FrameSource its
   // graph was captured with, and a call with another one records again (forward_graph).
   static constexpr int kGraphFmts = kSrcSensor + 1;
   struct GraphSlot { hipGraphExec_t exec = nullptr; FrameSource src; };
-  GraphSlot gslot[2 * kGraphFmts];
+  GraphSlot gslot[4 * kGraphFmts];
   // Camera mask (camera_mask.h).  mask_buf [T][C]: the predictor's copy of the current call's mask -- the masked
   // kernels (and a captured graph of them) read this buffer, so the mask may change from call to call.  mask_cur:
   // the mask of the call under way, nullptr = no mask (the plain kernels).  n_active / n_detect [T]: written by
@@ -576,7 +646,7 @@ static int stage_center_impl(jh_predictor* pr, const void* frames_dev, const Fra
   if (pr->center->stem_fusable) {
     // resize + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->center->stem_src;
-    src.mode = 1; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.source = fs;
+    src.mode = 1; src.frames = frames_dev; src.frames_cell = pr->cell_for(fs); src.source = fs;
     src.H = pr->cfg.img_h; src.W = pr->cfg.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = pr->cfg.mean[i]; src.stdv[i] = pr->cfg.std[i]; }
     // algorithmic bytes of the fused launch: the four bilinear taps of every network-input pixel (px_bytes
@@ -585,7 +655,7 @@ static int stage_center_impl(jh_predictor* pr, const void* frames_dev, const Fra
   } else {
     JH_PROF("preprocess_resize", 0.0, (double)N * S * S * (4.0 * fs.px_bytes() + 3 * 4),
             launch_preprocess_resize(frames_dev, fs, pr->center->input.p, N, pr->cfg.img_h,
-                                     pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, pr->cur_cell));
+                                     pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, pr->cell_for(fs)));
   }
   if (pr->center->run(s)) return 1;
   const Act& h = pr->center->heat;
@@ -636,7 +706,7 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, const 
   if (pr->kp->stem_fusable) {
     // crop + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->kp->stem_src;
-    src.mode = 2; src.frames = frames_dev; src.frames_cell = pr->cur_cell; src.source = fs;
+    src.mode = 2; src.frames = frames_dev; src.frames_cell = pr->cell_for(fs); src.source = fs;
     src.center_hm = pr->chm_cur(); src.Cloc = pr->Cloc; src.C = pr->C; src.cam0 = c.cam_lo;
     src.H = c.img_h; src.W = c.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = c.mean[i]; src.stdv[i] = c.std[i]; }
@@ -644,7 +714,7 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, const 
   } else {
     JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->Cloc * pr->B * pr->B * (fs.px_bytes() + 12.0),
             launch_preprocess_crop(frames_dev, fs, pr->chm_cur(), pr->kp->input.p, pr->T, pr->Cloc, pr->C,
-                                   c.cam_lo, c.img_h, c.img_w, pr->B, c.mean, c.std, s, pr->cur_cell));
+                                   c.cam_lo, c.img_h, c.img_w, pr->B, c.mean, c.std, s, pr->cell_for(fs)));
   }
   if (pr->kp->run(s)) return 1;
   if (heat_dev && heat_dev != pr->kp->heat.p)
@@ -716,7 +786,8 @@ static int forward_eager(jh_predictor* pr, const void* frames_dev, const FrameSo
 // copies into them), weights are immutable for the life of a predictor: nothing to invalidate.
 static int forward_graph(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
                          float* conf_dev, int32_t* valid_dev, hipStream_t s) {
-  jh_predictor::GraphSlot& slot = pr->gslot[fs.fmt + (pr->mask_cur ? jh_predictor::kGraphFmts : 0)];
+  jh_predictor::GraphSlot& slot = pr->gslot[fs.fmt + (pr->mask_cur ? jh_predictor::kGraphFmts : 0) +
+                                            (fs.per_image ? 2 * jh_predictor::kGraphFmts : 0)];
   // the recorded launches hold the description they were captured with: another one records again (rare: a stream
   // keeps its layout, and a fixed format has nothing to differ in; the replay in flight is waited for before its
   // executable graph goes)
@@ -741,7 +812,8 @@ static int forward_graph(jh_predictor* pr, const void* frames_dev, const FrameSo
     JH_CHECK_HIP(ei);
     slot.src = fs;
   }
-  hipLaunchKernelGGL(set_cell_kernel, dim3(1), dim3(1), 0, s, pr->frames_cell, frames_dev);
+  // (per-image: the recording reads frames_table, which this call's pointers have already been sent into)
+  if (!fs.per_image) hipLaunchKernelGGL(set_cell_kernel, dim3(1), dim3(1), 0, s, pr->frames_cell, frames_dev);
   JH_CHECK_HIP(hipGetLastError());
   JH_CHECK_HIP(hipGraphLaunch(slot.exec, s));
   const int n_pts = pr->T * pr->J * 3;
@@ -829,6 +901,19 @@ int jh_predictor_forward_masked(jh_predictor* pr, const void* frames_dev, int fo
   FrameSource fs;
   if (frame_source(format, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
   return forward_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream, mask_dev);
+}
+
+int jh_predictor_forward_images(jh_predictor* pr, const void* const* images_host, int n_images, int format,
+                                const jh_yuv_surface* yuv, const jh_sensor_surface* sensor, const uint8_t* mask_dev,
+                                float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
+  JH_REQUIRE(pr, "bad argument");
+  JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
+  FrameSource fs;
+  if (images_source(format, yuv, sensor, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
+  if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T * pr->C, format,
+                    static_cast<hipStream_t>(stream))) return 1;
+  // (the launches read the table: `frames` itself is not dereferenced)
+  return forward_impl(pr, pr->frames_table, fs, points_dev, conf_dev, valid_dev, stream, mask_dev);
 }
 
 int jh_predictor_stage_keypoints_masked(jh_predictor* pr, const void* frames_dev, int format,
@@ -941,6 +1026,7 @@ struct jh_predictor2d {
   Scratch mem;
   float* det = nullptr;
   int *chm = nullptr, *valid = nullptr;
+  const void** frames_table = nullptr;       // per-image frames: [T] device pointers (jh_predictor2d_forward_images)
 };
 
 extern "C" {
@@ -983,7 +1069,7 @@ static int forward2d_impl(jh_predictor2d* pr, const void* frames, const FrameSou
   // (These counts used to be a flat 24 B per pixel for every format: fp32 resize is 60, uint8 crop 15.)
   JH_PROF("preprocess_resize", 0.0, (double)pr->T * S * S * (4.0 * fs.px_bytes() + 12.0),
           launch_preprocess_resize(frames, fs, pr->center->input.p, pr->T, c.img_h, c.img_w, S,
-                                   c.mean, c.std, s));
+                                   c.mean, c.std, s, fs.per_image ? pr->frames_table : nullptr));
   if (pr->center->run(s)) return 1;
   const Act& h = pr->center->heat;
   JH_PROF("center_argmax", 0.0, 4.0 * pr->T * h.H * h.W,
@@ -994,7 +1080,7 @@ static int forward2d_impl(jh_predictor2d* pr, const void* frames, const FrameSou
     return 1;
   JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->B * pr->B * (fs.px_bytes() + 12.0),
           launch_preprocess_crop(frames, fs, pr->chm, pr->kp->input.p, pr->T, 1, 1, 0, c.img_h,
-                                 c.img_w, pr->B, c.mean, c.std, s));
+                                 c.img_w, pr->B, c.mean, c.std, s, fs.per_image ? pr->frames_table : nullptr));
   if (pr->kp->run(s)) return 1;
   const Act& k = pr->kp->heat;
   JH_PROF("joint_argmax", 0.0, 4.0 * pr->T * k.H * k.W * pr->J,
@@ -1039,6 +1125,17 @@ int jh_predictor2d_forward_sensor(jh_predictor2d* pr, const uint8_t* frames_dev,
   FrameSource fs;
   if (frame_source(surface, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
   return forward2d_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
+}
+
+int jh_predictor2d_forward_images(jh_predictor2d* pr, const void* const* images_host, int n_images, int format,
+                                  const jh_yuv_surface* yuv, const jh_sensor_surface* sensor,
+                                  int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
+  JH_REQUIRE(pr && points_dev && conf_dev, "bad argument");
+  FrameSource fs;
+  if (images_source(format, yuv, sensor, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
+  if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T, format,
+                    static_cast<hipStream_t>(stream))) return 1;
+  return forward2d_impl(pr, pr->frames_table, fs, points_dev, conf_dev, valid_dev, stream);
 }
 
 // ------------------------------------------------------------------- profiling

@@ -25,15 +25,19 @@ namespace jh {
 template <int SRC>
 __global__ __launch_bounds__(256) void preprocess_resize_kernel(
     const void* __restrict__ frames, float* __restrict__ out, int N, int H, int W, int S,
-    float sy, float sx, float3 mean, float3 stdv, const void* const* __restrict__ frames_cell, SrcDesc<SRC> d) {
+    float sy, float sx, float3 mean, float3 stdv, const void* const* __restrict__ frames_cell, int per_image,
+    SrcDesc<SRC> d) {
   // graph replays: the frame pointer of THIS call is read from a device cell (a captured launch
-  // would otherwise keep the pointer of the call it was captured on)
-  if (frames_cell) frames = *frames_cell;
+  // would otherwise keep the pointer of the call it was captured on); per_image: the cell is a table of N image
+  // pointers and n varies inside the loop, so the entry is read per iteration (image_base)
+  if (frames_cell && !per_image) frames = *frames_cell;
   const size_t total = (size_t)N * S * S;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (size_t)gridDim.x * blockDim.x) {
-    const int ox = (int)(i % S), oy = (int)((i / S) % S), n = (int)(i / ((size_t)S * S));
-    *reinterpret_cast<float4*>(out + i * 4) = resize_px<SRC>(frames, n, oy, ox, H, W, sy, sx, mean, stdv, d);
+    const int ox = (int)(i % S), oy = (int)((i / S) % S);
+    int n = (int)(i / ((size_t)S * S));
+    const void* base = image_base(frames, frames_cell, per_image, n);
+    *reinterpret_cast<float4*>(out + i * 4) = resize_px<SRC>(base, n, oy, ox, H, W, sy, sx, mean, stdv, d);
   }
 }
 
@@ -44,9 +48,11 @@ int launch_preprocess_resize(const void* frames, const FrameSource& src, float* 
   int blocks = (int)((total + 255) / 256);
   if (blocks > 8192) blocks = 8192;
   const float3 m = make_float3(mean[0], mean[1], mean[2]), sd = make_float3(stdv[0], stdv[1], stdv[2]);
+  JH_REQUIRE(!src.per_image || frames_cell, "per-image frames come with their pointer table");
   if (dispatch_src(src, [&](auto tag, const auto& d) {
         hipLaunchKernelGGL(preprocess_resize_kernel<decltype(tag)::value>, dim3(blocks), dim3(256), 0, s, frames, out,
-                           N, H, W, S, (float)H / (float)S, (float)W / (float)S, m, sd, frames_cell, d);
+                           N, H, W, S, (float)H / (float)S, (float)W / (float)S, m, sd, frames_cell,
+                           (int)src.per_image, d);
         return 0;
       }))
     return 1;
@@ -59,16 +65,17 @@ template <int SRC>
 __global__ __launch_bounds__(256) void preprocess_crop_kernel(
     const void* __restrict__ frames, const int* __restrict__ center_hm, float* __restrict__ out,
     int T, int Cloc, int C, int cam0, int H, int W, int B, float3 mean, float3 stdv,
-    const void* const* __restrict__ frames_cell, SrcDesc<SRC> d) {
-  if (frames_cell) frames = *frames_cell;
+    const void* const* __restrict__ frames_cell, int per_image, SrcDesc<SRC> d) {
+  if (frames_cell && !per_image) frames = *frames_cell;
   const size_t total = (size_t)T * Cloc * B * B;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (size_t)gridDim.x * blockDim.x) {
     const int ox = (int)(i % B), oy = (int)((i / B) % B);
-    const int n = (int)(i / ((size_t)B * B));
+    int n = (int)(i / ((size_t)B * B));
     const int t = n / Cloc, cl = n % Cloc;
     const int cx = center_hm[(t * C + cam0 + cl) * 2 + 0], cy = center_hm[(t * C + cam0 + cl) * 2 + 1];
-    *reinterpret_cast<float4*>(out + i * 4) = crop_px<SRC>(frames, n, cx, cy, oy, ox, H, W, B, mean, stdv, d);
+    const void* base = image_base(frames, frames_cell, per_image, n);
+    *reinterpret_cast<float4*>(out + i * 4) = crop_px<SRC>(base, n, cx, cy, oy, ox, H, W, B, mean, stdv, d);
   }
 }
 
@@ -79,9 +86,10 @@ int launch_preprocess_crop(const void* frames, const FrameSource& src, const int
   int blocks = (int)((total + 255) / 256);
   if (blocks > 8192) blocks = 8192;
   const float3 m = make_float3(mean[0], mean[1], mean[2]), sd = make_float3(stdv[0], stdv[1], stdv[2]);
+  JH_REQUIRE(!src.per_image || frames_cell, "per-image frames come with their pointer table");
   if (dispatch_src(src, [&](auto tag, const auto& d) {
         hipLaunchKernelGGL(preprocess_crop_kernel<decltype(tag)::value>, dim3(blocks), dim3(256), 0, s, frames,
-                           center_hm, out, T, Cloc, C, cam0, H, W, B, m, sd, frames_cell, d);
+                           center_hm, out, T, Cloc, C, cam0, H, W, B, m, sd, frames_cell, (int)src.per_image, d);
         return 0;
       }))
     return 1;
@@ -112,6 +120,7 @@ int launch_frames_to_bgr(const void* frames, const FrameSource& src, unsigned ch
                          hipStream_t s) {
   const size_t total = (size_t)N * H * W;
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  JH_REQUIRE(!src.per_image, "the to-BGR helper reads contiguous frames");
   if (dispatch_src(src, [&](auto tag, const auto& d) {
         constexpr int SRC = decltype(tag)::value;
         if constexpr (!kIsRgb8<SRC>) {

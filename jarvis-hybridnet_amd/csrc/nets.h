@@ -19,6 +19,8 @@ int launch_reproject(const float* cam, const float* intr, const float* dist, con
                      const int* center_hm, const float* heat, float2* coarse, float* vol,
                      int* idx_out, int T, int C, int G, float spacing, int hs, int Jp,
                      int heat_pad, int div255, hipStream_t s, const HeatLayout* layout = nullptr);
+// (frames_cell: the one-pointer cell of a graph replay, or nullptr; with src.per_image the table of N image pointers,
+//  which must then be given -- preprocess.h: image_base)
 int launch_preprocess_resize(const void* frames, const FrameSource& src, float* out, int N, int H, int W, int S,
                              const float* mean, const float* stdv, hipStream_t s,
                              const void* const* frames_cell = nullptr);

@@ -30,6 +30,15 @@
 //      every layer below takes.
 // Nothing else names a form: the kernels, StemSource and the predictor's graph slots carry a SrcDesc<SRC> resp. a
 // FrameSource whatever it holds.
+//
+// WHERE the images of a launch lie is independent of their form (image_base below): at `frames + n * stride` of one
+// base pointer -- given with the launch, or read from a one-pointer device cell under graph replay --, or PER IMAGE,
+// image n at table[n] of a device table of N pointers (jh_predictor_forward_images: every camera's buffer where its
+// producer left it).  The per-image flag is wave-uniform launch data; with it set the pixel functions below get
+// (table[n], image 0), otherwise (base, n): their arithmetic is the same either way.
+// Alignment under a table: fp32 images are 4-byte aligned (checked on the host); the byte forms may start at ANY
+// address -- the one wider load there is, the 2-byte chroma pair of NV12 and of semi-planar surfaces, is taken only
+// from an even image base, and an image at an odd address reads the pair as two bytes (yuv420_px, yuv_surface_px).
 #pragma once
 #include <type_traits>
 #include <variant>
@@ -41,6 +50,16 @@ enum { kSrcRgbF32 = 0, kSrcBgrU8 = 1, kSrcI420 = 2, kSrcNV12 = 3, kSrcYuvSurface
 template <int SRC> constexpr bool kIsYuv = SRC == kSrcI420 || SRC == kSrcNV12 || SRC == kSrcYuvSurface;
 // the forms whose pixel is converted once to (R, G, B) bytes for all three channels
 template <int SRC> constexpr bool kIsRgb8 = kIsYuv<SRC> || SRC == kSrcSensor;
+
+// The base pointer and the index under which the pixel functions find image n of a launch (see the head of this file).
+// cell: the one-pointer cell of a graph replay (or nullptr: `frames` is the base), or with per_image the table.
+__device__ __forceinline__ const void* image_base(const void* frames, const void* const* cell, int per_image, int& n) {
+  if (per_image) {
+    frames = cell[n];
+    n = 0;
+  }
+  return frames;
+}
 
 template <int SRC>
 __device__ __forceinline__ float frame_px(const void* frames, size_t n, int c, int y, int x, int H,
@@ -69,7 +88,7 @@ __host__ __device__ __forceinline__ Rgb8 yuv_to_rgb8(int Y, int U, int V) {
 }
 
 // pixel (y, x) of YUV 4:2:0 image n (SRC 2 / 3): one Y load and one chroma load (NV12: one
-// 2-byte load; I420: the U and V bytes of the same 2 x 2 block)
+// 2-byte load, or the two bytes when the base is odd; I420: the U and V bytes of the same 2 x 2 block)
 template <int SRC>
 __device__ __forceinline__ Rgb8 yuv420_px(const void* frames, size_t n, int y, int x, int H, int W) {
   static_assert(SRC == kSrcI420 || SRC == kSrcNV12, "yuv420_px: YUV 4:2:0 formats only");
@@ -78,10 +97,15 @@ __device__ __forceinline__ Rgb8 yuv420_px(const void* frames, size_t n, int y, i
   const int Y = img[(size_t)y * W + x];
   int U, V;
   if (SRC == kSrcNV12) {
-    // (H * W is a multiple of 4 and the pair offset is even: the 16-bit load is aligned)
-    const unsigned short uv =
-        *reinterpret_cast<const unsigned short*>(img + plane + (size_t)(y >> 1) * W + (x & ~1));
-    U = uv & 0xff; V = uv >> 8;
+    // (an image is H * W * 3 / 2 bytes, a multiple of 2, and the pair offset is even: with an even base the 16-bit
+    //  load is aligned.  An odd base -- one image of a per-image table -- takes the two bytes.)
+    const unsigned char* pair = img + plane + (size_t)(y >> 1) * W + (x & ~1);
+    if (!(reinterpret_cast<uintptr_t>(frames) & 1)) {
+      const unsigned short uv = *reinterpret_cast<const unsigned short*>(pair);
+      U = uv & 0xff; V = uv >> 8;
+    } else {
+      U = pair[0]; V = pair[1];
+    }
   } else {
     const size_t c = plane + (size_t)(y >> 1) * (W >> 1) + (x >> 1);
     U = img[c]; V = img[c + plane / 4];
@@ -95,7 +119,8 @@ __device__ __forceinline__ Rgb8 yuv420_px(const void* frames, size_t n, int y, i
 struct YuvSurface {
   long long image_stride = 0, y_offset = 0, y_pitch = 0, u_offset = 0, v_offset = 0, c_pitch = 0;
   int c_step = 1;
-  int pair = 0;                // c_step == 2 and image_stride even: U, V of a block in one aligned 2-byte load
+  int pair = 0;                // c_step == 2 and image_stride even (per image: c_step == 2; every image is image 0 of
+                               // its own base): U, V of a block in one 2-byte load, aligned when the base is even
   int y0 = 16, cy = 0, cvr = 0, cub = 0, cug = 0, cvg = 0;
   bool operator==(const YuvSurface& o) const {
     return image_stride == o.image_stride && y_offset == o.y_offset && y_pitch == o.y_pitch &&
@@ -116,7 +141,8 @@ __host__ __device__ __forceinline__ Rgb8 yuv_to_rgb8(int Y, int U, int V, const 
 }
 
 // pixel (y, x) of image n of a described surface (SRC 4): one Y load and, for the 2 x 2 block's chroma, one
-// 2-byte load (semi-planar, when the pair is 2-byte aligned: a wave-uniform choice) or the U and the V byte.
+// 2-byte load (semi-planar, when the pair is 2-byte aligned: with `pair` every image has the parity of `frames`, which
+// per image is the image's own base) or the U and the V byte.
 // 64-bit offsets: image_stride * n passes 2^31 at batch scale.  Only plane bytes are ever addressed.
 __device__ __forceinline__ Rgb8 yuv_surface_px(const void* frames, size_t n, int y, int x, const YuvSurface& s) {
   const unsigned char* img = static_cast<const unsigned char*>(frames) + (long long)n * s.image_stride;
@@ -279,7 +305,8 @@ __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int
 struct FrameSource {
   int fmt = kSrcRgbF32;                                                                  // kSrc*
   std::variant<std::monostate, SrcDesc<kSrcYuvSurface>, SrcDesc<kSrcSensor>> desc;       // monostate: fmt needs none
-  bool operator==(const FrameSource& o) const { return fmt == o.fmt && desc == o.desc; }
+  bool per_image = false;      // the launches read a table of one device pointer per image instead of one base
+  bool operator==(const FrameSource& o) const { return fmt == o.fmt && desc == o.desc && per_image == o.per_image; }
   bool operator!=(const FrameSource& o) const { return !(*this == o); }
   // bytes of frame data per source pixel: fp32 RGB 12, uint8 BGR 3, YUV 4:2:0 1.5, raw sensor 1
   double px_bytes() const {
@@ -318,7 +345,8 @@ int dispatch_src(const FrameSource& src, F&& f) {
 struct StemSource {
   int mode = 0;               // 0: the plan's own input tensor; 1: resize of the frames; 2: crop of the frames
   const void* frames = nullptr;
-  const void* const* frames_cell = nullptr;    // graph replays: the frame pointer of the current call
+  const void* const* frames_cell = nullptr;    // graph replays: the frame pointer of the current call; with
+                                               // source.per_image: the table of N image pointers (always set)
   FrameSource source;                          // the form of the frames and its description
   const int* center_hm = nullptr;              // crop: [T][C][2]
   int Cloc = 0, C = 0, cam0 = 0;               // crop: image n = (t, local camera)

@@ -34,9 +34,10 @@ typedef float sf4 __attribute__((ext_vector_type(4)));
 template <int SRC>
 struct StemSrcArgs {           // MODE != 0: the frames this launch pre-processes on the fly
   const void* frames;
-  const void* const* frames_cell;
+  const void* const* frames_cell;   // the cell of a graph replay, or (per_image) the table of N image pointers
   const int* center_hm;
   int Cloc, C, cam0, FH, FW;
+  int per_image;
   float sy, sx;
   float3 mean, stdv;
   SrcDesc<SRC> desc;           // the form's description (uniform: scalar registers); MODE == 0: the empty one
@@ -63,9 +64,12 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(x + (size_t)n * H * W * 4), 0, H * W * 16, 0x00020000);
   const void* frames = sa.frames;
+  int ni = n;                  // the image as the pixel functions index it: n of the base, or 0 of its own pointer
   int ccx = 0, ccy = 0;
   if (MODE != 0) {
-    if (sa.frames_cell) frames = *sa.frames_cell;
+    // (n is workgroup-uniform: the table entry, like the cell, is one scalar load)
+    if (sa.per_image) frames = image_base(frames, sa.frames_cell, 1, ni);
+    else if (sa.frames_cell) frames = *sa.frames_cell;
     if (MODE == 2) {
       const int t = n / sa.Cloc, cl = n - t * sa.Cloc;
       ccx = sa.center_hm[(t * sa.C + sa.cam0 + cl) * 2 + 0];
@@ -84,8 +88,8 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
       // (the convolution's zero padding lies outside the pre-processed image: zeros, not normalised zeros)
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (ok)
-        v = MODE == 1 ? resize_px<SRC>(frames, n, iy, ix, sa.FH, sa.FW, sa.sy, sa.sx, sa.mean, sa.stdv, sa.desc)
-                      : crop_px<SRC>(frames, n, ccx, ccy, iy, ix, sa.FH, sa.FW, H, sa.mean, sa.stdv, sa.desc);
+        v = MODE == 1 ? resize_px<SRC>(frames, ni, iy, ix, sa.FH, sa.FW, sa.sy, sa.sx, sa.mean, sa.stdv, sa.desc)
+                      : crop_px<SRC>(frames, ni, ccx, ccy, iy, ix, sa.FH, sa.FW, H, sa.mean, sa.stdv, sa.desc);
       patch[i] = v;
     }
   }
@@ -178,6 +182,7 @@ int launch_stem_conv(const Act& x, const float* w_dev, const Act& y, double* sta
 int launch_stem_conv_src(const StemSource& src, const Act& x, const float* w_dev, const Act& y, double* stats,
                          hipStream_t s) {
   JH_REQUIRE(src.mode == 1 || src.mode == 2, "stem source mode");
+  JH_REQUIRE(!src.source.per_image || src.frames_cell, "per-image frames come with their pointer table");
   JH_REQUIRE(x.Cp == 4 && (y.Cp == 16 || y.Cp == 32) && x.D == 1 && y.H * 2 == x.H && y.W * 2 == x.W && x.N == y.N &&
                  x.H == x.W, "stem convolution shapes");
   const int tiles = ((y.H + kStT - 1) / kStT) * ((y.W + kStT - 1) / kStT);
@@ -191,6 +196,7 @@ int launch_stem_conv_src(const StemSource& src, const Act& x, const float* w_dev
     StemSrcArgs<U> sa{};
     sa.frames = src.frames; sa.frames_cell = src.frames_cell; sa.center_hm = src.center_hm;
     sa.Cloc = src.Cloc; sa.C = src.C; sa.cam0 = src.cam0; sa.FH = src.H; sa.FW = src.W;
+    sa.per_image = src.source.per_image;
     sa.sy = (float)src.H / (float)x.H; sa.sx = (float)src.W / (float)x.W;      // (as launch_preprocess_resize)
     sa.mean = make_float3(src.mean[0], src.mean[1], src.mean[2]);
     sa.stdv = make_float3(src.stdv[0], src.stdv[1], src.stdv[2]);

@@ -48,6 +48,17 @@ class _Native2D:
         N.check(fn(self.handle, N.ptr(frames), *fmt_args, N.ptr(pts), N.ptr(conf), N.ptr(valid), N.stream()))
         return pts, conf, valid
 
+    def forward_images(self, images, fmt, layout=None):
+        """forward() on T separately placed images (checked by _native.frame_images): jh_predictor2d_forward_images."""
+        dev = images[0].device
+        pts = torch.empty((self.T, self.J, 2), device=dev, dtype=torch.int32)
+        conf = torch.empty((self.T, self.J), device=dev)
+        valid = torch.empty((self.T,), device=dev, dtype=torch.int32)
+        N.check(N.lib().jh_predictor2d_forward_images(
+            self.handle, N.image_table(images), len(images), fmt, *N.layout_args(fmt, layout), N.ptr(pts), N.ptr(conf),
+            N.ptr(valid), N.stream()))
+        return pts, conf, valid
+
     def close(self):
         if getattr(self, "handle", None) and N is not None and N._lib is not None:
             N.lib().jh_predictor2d_destroy(self.handle)
@@ -141,3 +152,14 @@ class JarvisPredictor2D(nn.Module):
             return self.native(x.shape[1], x.shape[2], x.shape[0]).forward(x)
         x = N.dev(imgs)
         return self.native(x.shape[2], x.shape[3], x.shape[0]).forward(x)
+
+    def forward_images(self, images, frame_format=None, frame_layout=None):
+        """forward_batch on T images that lie where their producers left them: `images` a sequence of T tensors, each
+        ONE image -- fp32 (3,H,W); uint8 (H,W,3); 'i420' / 'nv12': uint8 (3H/2,W); frame_layout: 1-D uint8 of at least
+        image_stride bytes (see JarvisPredictor3D.forward_images) -> what forward_batch returns for their stack, bit
+        for bit; no host sync."""
+        if not isinstance(images, (list, tuple)) or len(images) == 0:
+            raise ValueError("images must be a non-empty sequence of tensors, one per image")
+        images = list(images)
+        fmt, (H, W), layout = N.frame_images(images, len(images), frame_format, frame_layout)
+        return self.native(H, W, len(images)).forward_images(images, fmt, layout)

@@ -260,6 +260,36 @@ class JarvisPredictor3D(nn.Module):
         pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
         return self._batch(pr, pr.forward(x, camera_mask=camera_mask), camera_mask, return_2d)
 
+    def forward_images(self, images, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
+                       frame_layout=None, camera_mask=None, return_2d=False):
+        """forward_batch on images that lie where their producers left them: `images` a sequence of C tensors (one
+        frame set) or a sequence of T such sequences, each tensor ONE image -- fp32 (3,H,W); uint8 (H,W,3);
+        frame_format 'i420' / 'nv12': uint8 (3H/2,W); frame_layout (a YuvSurface or a SensorSurface): 1-D uint8 of at
+        least image_stride bytes.  All of one shape, dtype and device, contiguous, on the GPU; any address (views
+        into a decoder's surface pool included), the same tensor may appear more than once, and a masked camera's
+        entry is still an image.  Nothing is gathered: the kernels read every image through its own pointer
+        (jh_predictor_forward_images).
+        -> what forward_batch returns for the (T,C,...) stack of the same images, bit for bit; no host
+        synchronisation.  camera_mask (T,C), return_2d: as forward_batch."""
+        if isinstance(images, (list, tuple)) and len(images) > 0 and torch.is_tensor(images[0]):
+            images = [images]
+        if not isinstance(images, (list, tuple)) or len(images) == 0:
+            raise ValueError("images must be a sequence of %d tensors or a sequence of such sequences"
+                             % self.num_cameras)
+        for t, frame_set in enumerate(images):
+            if not isinstance(frame_set, (list, tuple)) or len(frame_set) != self.num_cameras:
+                raise ValueError("frame set %d: expected a sequence of %d images (one per camera), got %s" % (
+                    t, self.num_cameras,
+                    len(frame_set) if isinstance(frame_set, (list, tuple)) else type(frame_set).__name__))
+        T = len(images)
+        flat = [img for frame_set in images for img in frame_set]
+        fmt, (H, W), layout = N.frame_images(flat, T * self.num_cameras, frame_format, frame_layout)
+        camera_mask = N.camera_mask(camera_mask, (T, self.num_cameras))
+        check_native_seam(self)
+        pr = self.native(H, W, time_batch=T)
+        pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
+        return self._batch(pr, pr.forward_images(flat, fmt, layout, camera_mask=camera_mask), camera_mask, return_2d)
+
     @staticmethod
     def _batch(pr, res, mask, return_2d):
         return tuple(res) + (pr.views2d(res[0], camera_mask=mask),) if return_2d else res
