@@ -5,7 +5,9 @@ fails, a RuntimeError is raised.  PyTorch is used only as the owner of device
 memory and streams -- every pointer crossing this boundary is a raw address.
 """
 import ctypes
+import math
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -200,38 +202,57 @@ def lib():
     return _lib
 
 
-# frame_format names of the Python API -> JH_FRAME_* of include/jarvis_hip.h.  'bgr': uint8 BGR (H,W,3) images as
-# cv2 delivers them; 'i420' / 'nv12': YUV 4:2:0, one contiguous (3H/2, W) uint8 image per camera, H and W even.
-FRAME_FORMATS = {"bgr": 1, "i420": 2, "nv12": 3}
+# JH_FRAME_* of include/jarvis_hip.h.  'rgb': fp32 RGB (3,H,W) images; 'bgr': uint8 BGR (H,W,3) images as cv2 delivers
+# them; 'i420' / 'nv12': YUV 4:2:0, one contiguous (3H/2, W) uint8 image per camera, H and W even; 'surface' / 'sensor':
+# image_stride bytes per image, read through a YuvSurface / a SensorSurface.
+FRAME_CODES = {"rgb": 0, "bgr": 1, "i420": 2, "nv12": 3, "surface": 4, "sensor": 5}
+FRAME_FORMATS = {k: FRAME_CODES[k] for k in ("bgr", "i420", "nv12")}       # the names a frame_format argument takes
 YUV_FORMATS = ("i420", "nv12")
+FRAME_SURFACE, FRAME_SENSOR = FRAME_CODES["surface"], FRAME_CODES["sensor"]
 
 
-def frame_format(name):
-    """A frame_format argument checked: None (the frame tensor's dtype decides, the behaviour without the argument)
-    or one of FRAME_FORMATS; anything else raises ValueError."""
-    if name is not None and name not in FRAME_FORMATS:
-        raise ValueError("frame_format must be one of %s or None, got %r" % (sorted(FRAME_FORMATS), name))
+class Frames(NamedTuple):
+    """What the frames of one call are, checked once and carried to the ctypes call: fmt the JH_FRAME_* code, height
+    and width of a frame, layout the checked YuvSurface / SensorSurface or None, lead the leading shape ((T, C) of a
+    3D call, (T,) of a 2D one), and the bytes: `data`, one contiguous device tensor of shape lead + (one image), or
+    `images`, the flat list of prod(lead) separately placed device tensors.  Built by describe_frames and
+    frame_images alone (describe_shape gives one without bytes)."""
+    fmt: int
+    height: int
+    width: int
+    layout: object
+    lead: tuple
+    data: object = None
+    images: object = None
+
+    @property
+    def device(self):
+        return self.data.device if self.images is None else self.images[0].device
+
+
+def yuv_format(name):
+    """The frame_format of the forms that take YUV 4:2:0 frames only (forward_yuv): 'i420' or 'nv12'."""
+    if name not in YUV_FORMATS:
+        raise ValueError("frame_format must be one of %s, got %r" % (list(YUV_FORMATS), name))
     return name
 
 
-def yuv_frame_hw(shape):
-    """(rows, W) of a YUV 4:2:0 image -> (H, W).  rows = 3H/2 with H and W even: ValueError otherwise (an odd
-    frame height leaves rows that are no multiple of 3)."""
-    rows, w = int(shape[-2]), int(shape[-1])
-    if rows <= 0 or rows % 3 or w <= 0 or w % 2:
-        raise ValueError("a YUV 4:2:0 image is (3H/2, W) bytes with H and W even; got (%d, %d)" % (rows, w))
-    return rows // 3 * 2, w
+def surface(layout):
+    """The `surface` argument of the forms that take described frames only (forward_surface): not None."""
+    if layout is None:
+        raise ValueError("surface must be a YuvSurface or a SensorSurface, got None")
+    return layout
 
 
-def frame_layout(layout, frame_format, lead, hw=None, frames=None):
-    """A frame_layout argument checked, before anything reaches the GPU: None stays None; otherwise a
-    yuv_surface.YuvSurface or a sensor_surface.SensorSurface, not combined with frame_format 'i420' / 'nv12' (the
-    layout says what the bytes are), of the frame size `hw` when that is given, and `frames` (when given) a uint8
-    tensor of shape lead + (image_stride,) -- `lead` a tuple whose None entries match any size.  ValueError
-    otherwise."""
+def check_layout(layout, frame_format=None, hw=None):
+    """A frame_layout argument checked: None stays None; otherwise a yuv_surface.YuvSurface or a
+    sensor_surface.SensorSurface, not combined with frame_format 'i420' / 'nv12' (the layout says what the bytes
+    are) and of the frame size `hw` when that is given.  ValueError otherwise."""
     if layout is None:
         return None
-    if not is_frame_layout(layout):
+    from .sensor_surface import SensorSurface
+    from .yuv_surface import YuvSurface
+    if not isinstance(layout, (YuvSurface, SensorSurface)):
         raise ValueError("frame_layout must be a YuvSurface or a SensorSurface or None, got %r"
                          % (type(layout).__name__,))
     if frame_format in YUV_FORMATS:
@@ -239,58 +260,101 @@ def frame_layout(layout, frame_format, lead, hw=None, frames=None):
                          % (frame_format,))
     if hw is not None and (layout.height, layout.width) != tuple(hw):
         raise ValueError("frame_layout is %d x %d; this predictor is %d x %d" % (layout.height, layout.width, *hw))
-    if frames is not None:
-        want = tuple(lead) + (layout.image_stride,)
-        ok = torch.is_tensor(frames) and frames.dtype == torch.uint8 and frames.dim() == len(want) and all(
-            w is None or int(g) == w for g, w in zip(frames.shape, want))
-        if not ok:
-            raise ValueError("frames of a %s must be uint8 %s (image_stride bytes per image); got %s" % (
-                type(layout).__name__, tuple("*" if w is None else w for w in want),
-                (frames.dtype, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames).__name__))
     return layout
 
 
-def is_frame_layout(layout):
-    """True for the two descriptions frame_layout= takes: a YuvSurface or a SensorSurface."""
-    from .sensor_surface import SensorSurface
-    from .yuv_surface import YuvSurface
-    return isinstance(layout, (YuvSurface, SensorSurface))
-
-
-def forward_entry(which, frames, frame_format=None, layout=None, mask=None):
-    """The whole-path entry point of the library for a call's frames, and the arguments that say what they are:
-    (fn, fmt_args), called as fn(handle, ptr(frames), *fmt_args, <outputs>, stream).  which = 'jh_predictor' (3D,
-    whose masked and described entry points take the device mask pointer, NULL for none) or 'jh_predictor2d' (no
-    masks).  layout: a checked frame_layout (its struct is kept alive by fmt_args); otherwise frame_format 'i420' /
-    'nv12', or the dtype decides between uint8 BGR and fp32 RGB."""
+def describe_shape(shape, dtype, lead, frame_format=None, frame_layout=None, hw=None, error=ValueError,
+                   in_place=False, at_least=False):
+    """THE rules of what frames are, on a shape and a dtype alone (no tensor, no device) -> Frames without bytes.
+    lead: the leading dimensions, None entries match any size.  After them one image is
+      frame_layout (a YuvSurface / SensorSurface)  uint8 (image_stride,); with at_least, image_stride bytes or more
+      frame_format 'i420' / 'nv12'                  uint8 (3H/2, W), H and W even
+      dtype uint8                                   BGR (H, W, 3)
+      otherwise                                     fp32 RGB (3, H, W); frame_format 'bgr' refuses it
+    hw: the fixed (H, W) of a predictor the frames are for; None: the shape says it.
+    in_place: the bytes are read as they are, so fp32 means float32; otherwise any other dtype is taken for frames
+    that the caller converts to float32.
+    An unknown frame_format, a bad frame_layout and a YUV size that cannot be are ValueErrors; a dtype or shape that
+    does not fit raises `error` for the fixed formats (the public predictors, the drivers and frame_images say
+    ValueError, NativePredictor always said RuntimeError) and ValueError for a frame_layout.
+    shape None: what was given is no tensor (dtype: its type's name)."""
+    if frame_format is not None and frame_format not in FRAME_FORMATS:
+        raise ValueError("frame_format must be one of %s or None, got %r" % (sorted(FRAME_FORMATS), frame_format))
+    layout = check_layout(frame_layout, frame_format, hw)
+    H, W = hw if hw is not None else ("H", "W")
+    hint = ""
     if layout is not None:
         from .sensor_surface import SensorSurface
-        kind = "sensor" if isinstance(layout, SensorSurface) else "surface"
-        return (getattr(lib(), "%s_forward_%s" % (which, kind)),
-                (layout.struct(),) + ((ptr(mask),) if which == "jh_predictor" else ()))
-    fmt = FRAME_FORMATS[frame_format] if frame_format in YUV_FORMATS else int(frames.dtype == torch.uint8)
-    if mask is not None:
-        return lib().jh_predictor_forward_masked, (fmt, ptr(mask))
-    if frame_format in YUV_FORMATS:
-        return getattr(lib(), which + "_forward_yuv"), (fmt,)
-    return getattr(lib(), which + ("_forward_u8" if fmt else "_forward")), ()
+        kind, error = "sensor" if isinstance(layout, SensorSurface) else "surface", ValueError
+        what = "frames of a %s (%simage_stride = %d bytes per image)" % (
+            type(layout).__name__, "at least " if at_least else "", layout.image_stride)
+        want, tail = torch.uint8, ("image_stride" if at_least else layout.image_stride,)
+        H, W = layout.height, layout.width
+    elif frame_format in YUV_FORMATS:
+        if hw is not None and (H % 2 or W % 2):
+            raise ValueError("YUV 4:2:0 frames need an even height and width; this predictor is %d x %d" % (H, W))
+        kind, what, want = frame_format, "%s frames" % frame_format, torch.uint8
+        tail = (H * 3 // 2, W) if hw is not None else ("3H/2", "W")
+    elif dtype == torch.uint8:
+        kind, what, want, tail = "bgr", "uint8 BGR frames", torch.uint8, (H, W, 3)
+        if shape is not None and len(shape) == len(lead) + 2:
+            hint = " (YUV 4:2:0 frames: pass frame_format='i420' or 'nv12')"
+    elif frame_format == "bgr":
+        raise error("frame_format 'bgr' needs uint8 %s frames; got dtype %s" % (_shape_text(lead, (H, W, 3)), dtype))
+    elif dtype == torch.float32 or (not in_place and isinstance(dtype, torch.dtype)):
+        kind, what, want, tail = "rgb", "fp32 RGB frames", dtype, (3, H, W)
+    else:
+        raise error("frames must be float32 RGB %s or uint8 BGR %s; got dtype %s"
+                    % (_shape_text(lead, (3, H, W)), _shape_text(lead, (H, W, 3)), dtype))
+    full = tuple(lead) + tail
+    fits = shape is not None and dtype == want and len(shape) == len(full) and all(
+        not isinstance(w, int) or int(g) == w for g, w in zip(shape, full))
+    if fits and at_least and layout is not None:
+        fits = int(shape[-1]) >= layout.image_stride
+    if not fits:
+        raise error("%s must be %s of shape %s; got %s%s" % (
+            what, "uint8" if want == torch.uint8 else "float32", _shape_text(lead, tail),
+            dtype if shape is None else "dtype %s, shape %s" % (dtype, tuple(shape)), hint))
+    if kind in YUV_FORMATS and hw is None:
+        rows, W = int(shape[-2]), int(shape[-1])
+        if rows <= 0 or rows % 3 or W <= 0 or W % 2:
+            raise ValueError("a YUV 4:2:0 image is (3H/2, W) bytes with H and W even; got (%d, %d)" % (rows, W))
+        H = rows // 3 * 2
+    elif hw is None and layout is None:
+        H, W = (int(shape[-3]), int(shape[-2])) if kind == "bgr" else (int(shape[-2]), int(shape[-1]))
+    return Frames(FRAME_CODES[kind], H, W, layout, tuple(int(n) for n in shape[:len(lead)]))
 
 
-FRAME_RGB_F32, FRAME_SURFACE, FRAME_SENSOR = 0, 4, 5      # JH_FRAME_* beside FRAME_FORMATS
-_checked_format, _checked_layout = frame_format, frame_layout   # (frame_images' arguments carry the public names)
+def _shape_text(lead, tail):
+    """(2, *, H, W, 3): a wanted shape for an error message, * for a leading dimension of any size."""
+    return "(%s)" % ", ".join("*" if n is None else str(n) for n in tuple(lead) + tuple(tail))
+
+
+def describe_frames(frames, lead, frame_format=None, frame_layout=None, hw=None, error=ValueError, in_place=False):
+    """The frames of a call in one tensor, checked -> Frames with `data`.  The rules are describe_shape's (lead,
+    frame_format, frame_layout, hw, error and in_place as there) and need no device; the device comes last:
+    in_place: `frames` itself must be a contiguous device tensor (RuntimeError otherwise); else it is made one
+    (_native.dev: uint8 stays uint8, the fp32 form is converted to float32; RuntimeError for a CPU tensor)."""
+    shape, dtype = (frames.shape, frames.dtype) if torch.is_tensor(frames) else (None, type(frames).__name__)
+    d = describe_shape(shape, dtype, lead, frame_format, frame_layout, hw, error, in_place)
+    if not in_place:
+        return d._replace(data=dev(frames, torch.uint8 if d.fmt else torch.float32))
+    if not (frames.is_cuda and frames.is_contiguous()):
+        raise RuntimeError("frames must be a contiguous CUDA (HIP) tensor")
+    return d._replace(data=frames)
 
 
 def frame_images(images, count, frame_format=None, frame_layout=None):
-    """The images of a per-image call (forward_images) checked, before anything reaches the GPU: `images` a sequence
-    of `count` tensors, each ONE image -- fp32 (3,H,W); uint8 (H,W,3); with frame_format 'i420' / 'nv12' uint8
+    """The images of a per-image call (forward_images) checked -> Frames with `images`.  `images`: a sequence of
+    `count` tensors (count an int, or the leading shape (T, C) whose product it is), each ONE image as describe_shape
+    has it with no leading dimension -- fp32 (3,H,W); uint8 (H,W,3); with frame_format 'i420' / 'nv12' uint8
     (3H/2,W); with frame_layout a 1-D uint8 tensor of at least image_stride bytes -- all of one shape, dtype and
     device, contiguous and on the GPU.  Nothing is copied: the tensors are read where they lie.
-    -> (format code JH_FRAME_*, (H, W), the checked layout or None).  ValueError for what does not fit the call
-    (count, mixed images, shapes, frame_layout with 'i420' / 'nv12'), RuntimeError for a CPU or a non-contiguous
-    tensor, as the contiguous forms raise them."""
-    frame_format = _checked_format(frame_format)
-    frame_layout = _checked_layout(frame_layout, frame_format, ())
-    if not isinstance(images, (list, tuple)) or len(images) != count:
+    ValueError for what does not fit the call (count, mixed images, shapes, frame_layout with 'i420' / 'nv12'),
+    RuntimeError for a CPU or a non-contiguous tensor, as the contiguous forms raise them."""
+    lead = (count,) if isinstance(count, int) else tuple(count)
+    count = math.prod(lead)
+    if not isinstance(images, (list, tuple)) or len(images) != count or not images:
         raise ValueError("expected a sequence of %d images (one tensor per image); got %s" % (
             count, len(images) if isinstance(images, (list, tuple)) else type(images).__name__))
     for i, t in enumerate(images):
@@ -300,47 +364,50 @@ def frame_images(images, count, frame_format=None, frame_layout=None):
             raise ValueError("the images of a call have one shape, dtype and device: image %d is %s, image 0 is %s" % (
                 i, (t.dtype, tuple(t.shape), str(t.device)),
                 (images[0].dtype, tuple(images[0].shape), str(images[0].device))))
-    t = images[0]
-    if frame_layout is not None:
-        if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < frame_layout.image_stride:
-            raise ValueError("an image of a %s must be 1-D uint8 of at least image_stride = %d bytes; got %s" % (
-                type(frame_layout).__name__, frame_layout.image_stride, (t.dtype, tuple(t.shape))))
-        from .sensor_surface import SensorSurface
-        fmt = FRAME_SENSOR if isinstance(frame_layout, SensorSurface) else FRAME_SURFACE
-        hw = (frame_layout.height, frame_layout.width)
-    elif frame_format in YUV_FORMATS:
-        if t.dtype != torch.uint8 or t.dim() != 2:
-            raise ValueError("a %s image must be uint8 (3H/2, W); got %s" % (frame_format, (t.dtype, tuple(t.shape))))
-        fmt, hw = FRAME_FORMATS[frame_format], yuv_frame_hw(t.shape)
-    elif t.dtype == torch.uint8:
-        if t.dim() != 3 or t.shape[2] != 3:
-            hint = " (YUV 4:2:0 images: pass frame_format='i420' or 'nv12')" if t.dim() == 2 else ""
-            raise ValueError("a uint8 BGR image must be (H, W, 3); got %s%s" % (tuple(t.shape), hint))
-        fmt, hw = FRAME_FORMATS["bgr"], (int(t.shape[0]), int(t.shape[1]))
-    elif t.dtype == torch.float32 and frame_format is None:
-        if t.dim() != 3 or t.shape[0] != 3:
-            raise ValueError("an fp32 RGB image must be (3, H, W); got %s" % (tuple(t.shape),))
-        fmt, hw = FRAME_RGB_F32, (int(t.shape[1]), int(t.shape[2]))
-    else:
-        raise ValueError("an image must be float32 RGB (3,H,W) or uint8; frame_format 'bgr' needs uint8; got dtype %s"
-                         % (t.dtype,))
+    d = describe_shape(images[0].shape, images[0].dtype, (), frame_format, frame_layout, in_place=True, at_least=True)
     for i, t in enumerate(images):
         if not t.is_contiguous():
             raise RuntimeError("image %d is not contiguous: the kernels read it in place" % i)
         if not t.is_cuda:
             raise RuntimeError("jarvis_hybridnet_amd needs CUDA (HIP) tensors; image %d is a CPU tensor" % i)
-    return fmt, hw, frame_layout
+    return d._replace(lead=lead, images=list(images))
 
 
-def image_table(images):
-    """The host array of device pointers jh_predictor*_forward_images takes (free again when the call returns)."""
-    return (c_void_p * len(images))(*(t.data_ptr() for t in images))
+def forward_symbol(which, fmt, masked=False, per_image=False):
+    """The whole-path entry point of the library for a call's frames, by name.  which: 'jh_predictor' (3D) or
+    'jh_predictor2d' (which takes no masks); fmt: the JH_FRAME_* code; masked: a camera mask is given; per_image: the
+    frames are separately placed images.  Per-image frames of any format have one entry point, so have described
+    surfaces and sensor images (their 3D forms take the mask, NULL for none); a mask on the fixed formats goes
+    through the 3D predictor's masked entry point; otherwise every fixed format has its own."""
+    if per_image:
+        return which + "_forward_images"
+    if fmt in (FRAME_SURFACE, FRAME_SENSOR):
+        return which + ("_forward_surface" if fmt == FRAME_SURFACE else "_forward_sensor")
+    if masked:
+        return which + "_forward_masked"
+    return which + ("_forward", "_forward_u8", "_forward_yuv", "_forward_yuv")[fmt]
 
 
-def layout_args(fmt, layout):
-    """(yuv, sensor) of jh_predictor*_forward_images: the struct the format needs, NULL for the other."""
-    s = layout.struct() if layout is not None else None
-    return (s if fmt == FRAME_SURFACE else None, s if fmt == FRAME_SENSOR else None)
+def call_forward(which, handle, frames, mask, outs):
+    """THE call into the library for the whole forward: `frames` a Frames with its bytes, mask the (T,C) uint8
+    device mask or None, outs the output tensors; on the current stream.  The arguments that say what the frames
+    are follow the entry point (include/jarvis_hip.h); a layout's struct lives until the call returns."""
+    masks = which == "jh_predictor"
+    if mask is not None and not masks:
+        raise ValueError("%s takes no camera mask" % which)
+    name = forward_symbol(which, frames.fmt, mask is not None, frames.images is not None)
+    struct = frames.layout.struct() if frames.layout is not None else None
+    if frames.images is not None:
+        table = (c_void_p * len(frames.images))(*(t.data_ptr() for t in frames.images))
+        args = (table, len(frames.images), frames.fmt, struct if frames.fmt == FRAME_SURFACE else None,
+                struct if frames.fmt == FRAME_SENSOR else None) + ((ptr(mask),) if masks else ())
+    elif struct is not None:
+        args = (ptr(frames.data), struct) + ((ptr(mask),) if masks else ())
+    elif mask is not None:
+        args = (ptr(frames.data), frames.fmt, ptr(mask))
+    else:
+        args = (ptr(frames.data),) + ((frames.fmt,) if frames.fmt >= FRAME_CODES["i420"] else ())
+    check(getattr(lib(), name)(handle, *args, *(ptr(t) for t in outs), stream()))
 
 
 def camera_mask(mask, shape, what="camera_mask"):

@@ -75,74 +75,40 @@ class NativePredictor:
         frame_layout: a YuvSurface -- frames (T,C,image_stride) uint8, each image a YUV 4:2:0 surface read through
         that description (jh_predictor_forward_surface) --, or a SensorSurface -- each image a raw Mono8 / Bayer
         sensor image (jh_predictor_forward_sensor); not together with frame_format 'i420' / 'nv12'."""
-        frame_format = N.frame_format(frame_format)
-        camera_mask = N.camera_mask(camera_mask, (self.T, self.C))
-        frame_layout = N.frame_layout(frame_layout, frame_format, (self.T, self.Cloc), (self.cfg.img_h, self.cfg.img_w),
-                                      frames)
-        self._check_frames(frames, self.Cloc, frame_format, frame_layout)
+        return self._forward(self._describe(frames, frame_format, frame_layout), out,
+                             N.camera_mask(camera_mask, (self.T, self.C)))
+
+    def forward_images(self, frames, out=None, camera_mask=None):
+        """forward() on T * C separately placed images: `frames` what _native.frame_images made of the flat list
+        (index t * C + c) (jh_predictor_forward_images).  The images are read where they lie; nothing is gathered."""
+        if len(frames.images) != self.T * self.C:
+            raise ValueError("expected %d images (time_batch * num_cameras), got %d" % (self.T * self.C,
+                                                                                         len(frames.images)))
+        return self._forward(frames, out, N.camera_mask(camera_mask, (self.T, self.C)))
+
+    def _describe(self, frames, frame_format=None, frame_layout=None):
+        """Raw pointers cross the C ABI: refuse anything whose bytes would be misread (_native.describe_frames for
+        this predictor's time batch, local cameras and frame size; the frames are read in place)."""
+        return N.describe_frames(frames, (self.T, self.Cloc), frame_format, frame_layout,
+                                 (self.cfg.img_h, self.cfg.img_w), error=RuntimeError, in_place=True)
+
+    def _forward(self, frames, out, mask):
+        """The forward of checked frames (a _native.Frames) with a checked mask (_native.camera_mask) or None."""
         dev = frames.device
         if out is None:
             out = (torch.empty((self.T, self.J, 3), device=dev),
                    torch.empty((self.T, self.J), device=dev),
                    torch.empty((self.T,), device=dev, dtype=torch.int32))
-        mask = None if camera_mask is None else camera_mask.to(dev, non_blocking=True)   # (copied by the call)
-        fn, fmt_args = N.forward_entry("jh_predictor", frames, frame_format, frame_layout, mask)
-        N.check(fn(self.handle, N.ptr(frames), *fmt_args, N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.stream()))
+        if mask is not None:
+            mask = mask.to(dev, non_blocking=True)                # (copied by the call)
+        N.call_forward("jh_predictor", self.handle, frames, mask, out)
         if mask is not None and mask.is_cuda:
             mask.record_stream(torch.cuda.current_stream())     # (free once the call is enqueued)
         return out
 
-    def forward_images(self, images, fmt, layout=None, out=None, camera_mask=None):
-        """forward() on T * C separately placed images: `images` the flat list (index t * C + c) that
-        _native.frame_images has checked, fmt / layout what it returned (jh_predictor_forward_images).  The images are
-        read where they lie; nothing is gathered."""
-        if len(images) != self.T * self.C:
-            raise ValueError("expected %d images (time_batch * num_cameras), got %d" % (self.T * self.C, len(images)))
-        camera_mask = N.camera_mask(camera_mask, (self.T, self.C))
-        dev = images[0].device
-        if out is None:
-            out = (torch.empty((self.T, self.J, 3), device=dev),
-                   torch.empty((self.T, self.J), device=dev),
-                   torch.empty((self.T,), device=dev, dtype=torch.int32))
-        mask = None if camera_mask is None else camera_mask.to(dev, non_blocking=True)   # (copied by the call)
-        N.check(N.lib().jh_predictor_forward_images(
-            self.handle, N.image_table(images), len(images), fmt, *N.layout_args(fmt, layout), N.ptr(mask),
-            N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.stream()))
-        if mask is not None and mask.is_cuda:
-            mask.record_stream(torch.cuda.current_stream())
-        return out
-
-    def _check_frames(self, frames, cams, frame_format=None, frame_layout=None):
-        """Raw pointers cross the C ABI: refuse anything whose bytes would be misread."""
-        H, W = self.cfg.img_h, self.cfg.img_w
-        if not (torch.is_tensor(frames) and frames.is_cuda and frames.is_contiguous()):
-            raise RuntimeError("frames must be a contiguous CUDA (HIP) tensor")
-        if frame_layout is not None:
-            return                                   # (dtype and shape: _native.frame_layout, a ValueError)
-        if frame_format in N.YUV_FORMATS:
-            if H % 2 or W % 2:
-                raise ValueError("YUV 4:2:0 frames need an even height and width; this predictor is %d x %d" % (H, W))
-            if frames.dtype != torch.uint8:
-                raise RuntimeError("%s frames must be uint8 (T,C,3H/2,W); got dtype %s" % (frame_format, frames.dtype))
-            want = (self.T, cams, H * 3 // 2, W)
-        elif frame_format == "bgr" and frames.dtype != torch.uint8:
-            raise RuntimeError("frame_format 'bgr' needs uint8 (T,C,H,W,3) frames; got dtype %s" % frames.dtype)
-        elif frames.dtype == torch.uint8:
-            want = (self.T, cams, H, W, 3)
-        elif frames.dtype == torch.float32:
-            want = (self.T, cams, 3, H, W)
-        else:
-            raise RuntimeError("frames must be float32 RGB (T,C,3,H,W) or uint8 BGR (T,C,H,W,3); "
-                               "got dtype %s" % frames.dtype)
-        if tuple(frames.shape) != want:
-            hint = ""
-            if frames.dtype == torch.uint8 and frames.dim() == 4 and frame_format not in N.YUV_FORMATS:
-                hint = " (YUV 4:2:0 frames: pass frame_format='i420' or 'nv12')"
-            raise RuntimeError("frames shape %s, expected %s%s" % (tuple(frames.shape), want, hint))
-
     # ---- camera-sharded stages -------------------------------------------
     def stage_center(self, frames, det):
-        self._check_frames(frames, self.Cloc)
+        frames = self._describe(frames).data
         fn = N.lib().jh_predictor_stage_center_u8 if frames.dtype == torch.uint8 else \
             N.lib().jh_predictor_stage_center
         N.check(fn(self.handle, N.ptr(frames), N.ptr(det), N.stream()))
@@ -150,7 +116,7 @@ class NativePredictor:
     def stage_keypoints(self, frames, det_all, heat, camera_mask=None):
         """camera_mask: a (T,C) uint8 DEVICE tensor (kept alive by the caller until the stream has passed the call;
         all cameras local) for the masked triangulation; give stage_3d the same one."""
-        self._check_frames(frames, self.Cloc)
+        frames = self._describe(frames).data
         if camera_mask is not None:
             mask = self._device_mask(camera_mask)
             N.check(N.lib().jh_predictor_stage_keypoints_masked(
@@ -179,7 +145,7 @@ class NativePredictor:
 
     def stage_keypoints_gathered(self, frames, det_gathered, n_blocks, heat):
         """Stage 2 reading the all-gathered detections (n_blocks, T, C/n_blocks, 3) in place."""
-        self._check_frames(frames, self.Cloc)
+        frames = self._describe(frames).data
         N.check(N.lib().jh_predictor_stage_keypoints_gathered(
             self.handle, N.ptr(frames), int(frames.dtype == torch.uint8), N.ptr(det_gathered), n_blocks,
             N.ptr(heat), N.stream()))
@@ -304,11 +270,9 @@ class MultiStreamPredictor:
         `then(outputs)`, when given, runs inside the batch's stream context right behind the forward and
         before its event is recorded (the drivers enqueue the device->host copy of the results there); its
         return value replaces the outputs.  frame_format, camera_mask, frame_layout: as NativePredictor.forward."""
-        frame_format = N.frame_format(frame_format)
         p0 = self.preds[0]
+        described = p0._describe(frames, frame_format, frame_layout)               # before any stream work
         camera_mask = N.camera_mask(camera_mask, (p0.T, p0.C))
-        frame_layout = N.frame_layout(frame_layout, frame_format, (p0.T, p0.Cloc), (p0.cfg.img_h, p0.cfg.img_w), frames)
-        p0._check_frames(frames, p0.Cloc, frame_format, frame_layout)              # before any stream work
         i = self._next
         self._next = (i + 1) % len(self.preds)
         s = self.streams[i]
@@ -321,8 +285,7 @@ class MultiStreamPredictor:
         for t in (out or ()):
             t.record_stream(s)
         with torch.cuda.stream(s):
-            res = self.preds[i].forward(frames, out, frame_format=frame_format, camera_mask=camera_mask,
-                                        frame_layout=frame_layout)
+            res = self.preds[i]._forward(described, out, camera_mask)
             if return_2d:
                 res = tuple(res) + tuple(self.preds[i].views2d(res[0], camera_mask=camera_mask))
             if then is not None:

@@ -28,7 +28,7 @@ def analyze_frames(predictor, samples, reproTools, output_dir, num_joints, progr
     (JarvisPredictor3D.forward_surface); a SensorSurface likewise (one raw sensor image per camera).
     Returns (number of frame sets seen, number predicted)."""
     from .. import _native as N
-    N.frame_layout(frame_layout, None, ())
+    N.check_layout(frame_layout)
     pointsNet, pointsGT, filenames = [], [], []
     seen = 0
     for item, sample in enumerate(samples):

@@ -281,24 +281,16 @@ def driver_format(frame_format, frame_spec, ndim, frame_layout=None):
     """The drivers' frame_format argument checked: True for the YUV 4:2:0 formats, False for 'bgr' (the frames'
     dtype then decides between uint8 BGR and fp32 RGB, as without the argument); ValueError for anything else and
     for a YUV `frame_spec` that is no ((..., 3H/2, W), uint8) with H and W even.  frame_layout (a YuvSurface, a
-    SensorSurface, or None) is checked with it: not together with 'i420' / 'nv12', and its `frame_spec` is ((..., image_stride), uint8)
-    with one dimension less."""
+    SensorSurface, or None) is checked with it: not together with 'i420' / 'nv12', and its `frame_spec` is
+    ((..., image_stride), uint8) with one dimension less.  The shape rules are _native.describe_shape's."""
     from .. import _native as N
     if frame_format not in N.FRAME_FORMATS:
         raise ValueError("frame_format must be one of %s, got %r" % (sorted(N.FRAME_FORMATS), frame_format))
-    if N.frame_layout(frame_layout, frame_format, ()) is not None and frame_spec is not None:
-        shape, dtype = tuple(frame_spec[0]), frame_spec[1]
-        if len(shape) != ndim - 1 or dtype != torch.uint8 or shape[-1] != frame_layout.image_stride:
-            raise ValueError("frame_spec of %s frames must be (%s, torch.uint8) with image_stride = %d; got %r"
-                             % (type(frame_layout).__name__, "(C, image_stride)" if ndim == 3 else "(image_stride,)",
-                                frame_layout.image_stride, frame_spec))
     yuv = frame_format in N.YUV_FORMATS
-    if yuv and frame_spec is not None:
-        shape, dtype = tuple(frame_spec[0]), frame_spec[1]
-        if len(shape) != ndim or dtype != torch.uint8:
-            raise ValueError("frame_spec of %s frames must be (%s, torch.uint8); got %r" % (
-                frame_format, "(C, 3H/2, W)" if ndim == 3 else "(3H/2, W)", frame_spec))
-        N.yuv_frame_hw(shape)
+    if frame_spec is None:
+        N.check_layout(frame_layout, frame_format)
+    elif yuv or frame_layout is not None:
+        N.describe_shape(frame_spec[0], frame_spec[1], (None,) * (ndim - 2), frame_format, frame_layout)
     return yuv
 
 
@@ -307,16 +299,7 @@ def check_driver_frames(frames, frame_format, ndim, frame_layout=None):
     (the bytes would be misread).  With a frame_layout: (ndim - 1)-d uint8 (..., image_stride)."""
     from .. import _native as N
     dtype = frames.dtype if torch.is_tensor(frames) else torch.from_numpy(np.empty(0, frames.dtype)).dtype
-    if frame_layout is not None:
-        if len(frames.shape) != ndim - 1 or dtype != torch.uint8 or frames.shape[-1] != frame_layout.image_stride:
-            raise ValueError("%s frames must be uint8 %s with image_stride = %d; got %s %s" % (
-                type(frame_layout).__name__, "(C, image_stride)" if ndim == 3 else "(image_stride,)", frame_layout.image_stride, dtype,
-                tuple(frames.shape)))
-        return
-    if len(frames.shape) != ndim or dtype != torch.uint8:
-        raise ValueError("%s frames must be uint8 %s; got %s %s" % (
-            frame_format, "(C, 3H/2, W)" if ndim == 3 else "(3H/2, W)", dtype, tuple(frames.shape)))
-    N.yuv_frame_hw(frames.shape)
+    N.describe_shape(frames.shape, dtype, (None,) * (ndim - 2), frame_format, frame_layout)
 
 
 def pipeline_for(owner, frames, time_batch, streams, submit, emit, frame_spec=None, frame_layout=None):

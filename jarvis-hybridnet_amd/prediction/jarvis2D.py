@@ -5,6 +5,7 @@ Same constructor / forward signature and attributes (`centerDetect`,
 <= 40).  `forward` is one native call (jh_predictor2d_* in include/jarvis_hip.h).
 """
 import ctypes
+import math
 
 import torch
 import torch.nn as nn
@@ -13,6 +14,7 @@ from .. import _native as N
 from .. import arch
 from .._params import flat_state
 from ..efficienttrack.efficienttrack import EfficientTrack
+from .jarvis3D import precision_for_trt_mode
 
 
 class _Native2D:
@@ -30,33 +32,16 @@ class _Native2D:
         N.check(N.lib().jh_predictor2d_create(pc.handle, pk.handle, ctypes.byref(c),
                                               ctypes.byref(self.handle)))
 
-    def forward(self, frames, frame_format=None, frame_layout=None):
+    def _forward(self, frames):
+        """The forward of checked frames (a _native.Frames of T images of this predictor's size)."""
+        if (frames.height, frames.width, math.prod(frames.lead)) != (self.H, self.W, self.T):
+            raise RuntimeError("%d frames of %d x %d given to a predictor of %d frames of %d x %d" % (
+                math.prod(frames.lead), frames.height, frames.width, self.T, self.H, self.W))
         dev = frames.device
         pts = torch.empty((self.T, self.J, 2), device=dev, dtype=torch.int32)
         conf = torch.empty((self.T, self.J), device=dev)
         valid = torch.empty((self.T,), device=dev, dtype=torch.int32)
-        if frame_layout is not None:
-            N.frame_layout(frame_layout, frame_format, (self.T,), (self.H, self.W), frames)
-            if not (frames.is_cuda and frames.is_contiguous()):
-                raise RuntimeError("frames must be a contiguous CUDA (HIP) tensor")
-        elif frame_format in N.YUV_FORMATS:
-            if tuple(frames.shape) != (self.T, self.H * 3 // 2, self.W) or frames.dtype != torch.uint8 \
-                    or not frames.is_contiguous():
-                raise RuntimeError("%s frames %s, expected contiguous uint8 %s" % (
-                    frame_format, (frames.dtype, tuple(frames.shape)), (self.T, self.H * 3 // 2, self.W)))
-        fn, fmt_args = N.forward_entry("jh_predictor2d", frames, frame_format, frame_layout)
-        N.check(fn(self.handle, N.ptr(frames), *fmt_args, N.ptr(pts), N.ptr(conf), N.ptr(valid), N.stream()))
-        return pts, conf, valid
-
-    def forward_images(self, images, fmt, layout=None):
-        """forward() on T separately placed images (checked by _native.frame_images): jh_predictor2d_forward_images."""
-        dev = images[0].device
-        pts = torch.empty((self.T, self.J, 2), device=dev, dtype=torch.int32)
-        conf = torch.empty((self.T, self.J), device=dev)
-        valid = torch.empty((self.T,), device=dev, dtype=torch.int32)
-        N.check(N.lib().jh_predictor2d_forward_images(
-            self.handle, N.image_table(images), len(images), fmt, *N.layout_args(fmt, layout), N.ptr(pts), N.ptr(conf),
-            N.ptr(valid), N.stream()))
+        N.call_forward("jh_predictor2d", self.handle, frames, None, (pts, conf, valid))
         return pts, conf, valid
 
     def close(self):
@@ -73,7 +58,6 @@ class JarvisPredictor2D(nn.Module):
         super().__init__()
         # trt_mode 'new' / 'previous' (jarvis2D.py:39-43) select the reduced-precision mode bf16x3, see
         # jarvis3D.precision_for_trt_mode
-        from .jarvis3D import precision_for_trt_mode
         self.precision = precision_for_trt_mode(trt_mode, precision)
         self.trt_mode = trt_mode
         self.cfg = cfg
@@ -98,60 +82,44 @@ class JarvisPredictor2D(nn.Module):
         or (None, None).  frame_layout: a YuvSurface or a SensorSurface -- img is forward_surface's."""
         if frame_layout is not None:
             return self.forward_surface(img, frame_layout)
-        x = N.dev(img)
-        pts, conf, valid = self.native(x.shape[2], x.shape[3], x.shape[0]).forward(x)
-        if int(valid[0].item()) == 0:               # jarvis2D.py:121,150-153
+        frames = N.describe_frames(img, (None,))
+        return self._run(frames, True)
+
+    def _run(self, frames, single=False):
+        """The forward of checked frames (a _native.Frames) on the native predictor of their size and count; single:
+        the first image's (points2D int64, confidences), or (None, None) where nothing is detected
+        (jarvis2D.py:121,150-153)."""
+        pts, conf, valid = self.native(frames.height, frames.width, frames.lead[0])._forward(frames)
+        if not single:
+            return pts, conf, valid
+        if int(valid[0].item()) == 0:
             return None, None
         return pts[0].long(), conf[0]
 
     def forward_yuv(self, img, frame_format):
         """img (3H/2,W) or (1,3H/2,W) uint8 YUV 4:2:0, frame_format 'i420' / 'nv12' (H, W even; see
         JarvisPredictor3D.forward_yuv) -> (points2D (J,2) int64 pixels, confidences (J,)) or (None, None)."""
-        from .jarvis3D import _yuv_frames
         if torch.is_tensor(img) and img.dim() == 2:
             img = img.unsqueeze(0)
-        x = _yuv_frames(img, frame_format, 3)
-        H, W = N.yuv_frame_hw(x.shape)
-        pts, conf, valid = self.native(H, W, x.shape[0]).forward(x, frame_format)
-        if int(valid[0].item()) == 0:
-            return None, None
-        return pts[0].long(), conf[0]
+        frames = N.describe_frames(img, (None,), N.yuv_format(frame_format))
+        return self._run(frames, True)
 
     def forward_surface(self, img, surface):
         """img (image_stride,) or (1,image_stride) uint8: one YUV 4:2:0 image read through the YuvSurface `surface`,
         or one raw Mono8 / Bayer image read through the SensorSurface `surface` (see
         JarvisPredictor3D.forward_surface) -> (points2D (J,2) int64 pixels, confidences (J,)) or (None, None)."""
-        from .jarvis3D import _need_surface
         if torch.is_tensor(img) and img.dim() == 1:
             img = img.unsqueeze(0)
-        N.frame_layout(_need_surface(surface), None, (1,), None, img)
-        x = N.dev(img, torch.uint8)
-        pts, conf, valid = self.native(surface.height, surface.width, 1).forward(x, frame_layout=surface)
-        if int(valid[0].item()) == 0:
-            return None, None
-        return pts[0].long(), conf[0]
+        frames = N.describe_frames(img, (1,), None, N.surface(surface))
+        return self._run(frames, True)
 
     def forward_batch(self, imgs, frame_format=None, frame_layout=None):
         """imgs (T,3,H,W) fp32 RGB or (T,H,W,3) uint8 BGR, independent images ->
         points2D (T,J,2) int32, confidences (T,J), valid (T) int32; no host sync.  frame_format 'i420' / 'nv12':
         imgs (T,3H/2,W) uint8 YUV 4:2:0; 'bgr': uint8 BGR required; None: the dtype decides.  frame_layout: a
         YuvSurface or a SensorSurface -- imgs (T,image_stride) uint8 (forward_surface); not together with 'i420' / 'nv12'."""
-        frame_format = N.frame_format(frame_format)
-        if N.frame_layout(frame_layout, frame_format, (None,), None, imgs) is not None:
-            x = N.dev(imgs, torch.uint8)
-            return self.native(frame_layout.height, frame_layout.width, x.shape[0]).forward(x, frame_layout=frame_layout)
-        if frame_format in N.YUV_FORMATS:
-            from .jarvis3D import _yuv_frames
-            x = _yuv_frames(imgs, frame_format, 3)
-            H, W = N.yuv_frame_hw(x.shape)
-            return self.native(H, W, x.shape[0]).forward(x, frame_format)
-        if frame_format == "bgr" and imgs.dtype != torch.uint8:
-            raise ValueError("frame_format 'bgr' needs uint8 (T,H,W,3) frames; got dtype %s" % imgs.dtype)
-        if imgs.dtype == torch.uint8:
-            x = N.dev(imgs, torch.uint8)
-            return self.native(x.shape[1], x.shape[2], x.shape[0]).forward(x)
-        x = N.dev(imgs)
-        return self.native(x.shape[2], x.shape[3], x.shape[0]).forward(x)
+        frames = N.describe_frames(imgs, (None,), frame_format, frame_layout)
+        return self._run(frames)
 
     def forward_images(self, images, frame_format=None, frame_layout=None):
         """forward_batch on T images that lie where their producers left them: `images` a sequence of T tensors, each
@@ -160,6 +128,5 @@ class JarvisPredictor2D(nn.Module):
         for bit; no host sync."""
         if not isinstance(images, (list, tuple)) or len(images) == 0:
             raise ValueError("images must be a non-empty sequence of tensors, one per image")
-        images = list(images)
-        fmt, (H, W), layout = N.frame_images(images, len(images), frame_format, frame_layout)
-        return self.native(H, W, len(images)).forward_images(images, fmt, layout)
+        frames = N.frame_images(list(images), len(images), frame_format, frame_layout)
+        return self._run(frames)

@@ -144,14 +144,22 @@ class JarvisPredictor3D(nn.Module):
         the other cameras' slots of `imgs` hold does not matter.  Fewer than two cameras left, or fewer than two of
         them detecting: (None, None).  None: all cameras."""
         mask = self._frame_mask(camera_mask)
-        check_native_seam(self)
+        frames = N.describe_frames(imgs, (self.num_cameras,))
         self.reproTool.cameraMatrices = cameraMatrices
         self.reproTool.intrinsicMatrices = intrinsicMatrices
         self.reproTool.distortionCoefficients = distortionCoefficients
-        x = N.dev(imgs)
-        pr = self.native(x.shape[2], x.shape[3])
-        pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-        return self._single(pr, pr.forward(x.unsqueeze(0), camera_mask=mask), mask, return_2d)
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True)
+
+    def _run(self, frames, calib, mask, return_2d, single=False):
+        """The forward of checked frames (a _native.Frames; single: one frame set, lead (C,)) with a checked mask, on
+        the native predictor of their size: nothing of the predictor is touched before this."""
+        check_native_seam(self)
+        if single:
+            frames = frames._replace(lead=(1,) + frames.lead, data=frames.data.unsqueeze(0))
+        pr = self.native(frames.height, frames.width, time_batch=frames.lead[0])
+        pr.set_calibration(*calib)
+        res = pr._forward(frames, None, mask)
+        return self._single(pr, res, mask, return_2d) if single else self._batch(pr, res, mask, return_2d)
 
     @staticmethod
     def _single(pr, res, mask, return_2d):
@@ -174,11 +182,8 @@ class JarvisPredictor3D(nn.Module):
         `imgs_bgr.float().permute(0,3,1,2)[:, [2,1,0]] / 255.` (predict3D.py:79-80); the
         conversion runs inside the resize / crop kernels.  camera_mask, return_2d: as forward()."""
         mask = self._frame_mask(camera_mask)
-        check_native_seam(self)
-        x = N.dev(imgs_bgr, torch.uint8)
-        pr = self.native(x.shape[1], x.shape[2])
-        pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-        return self._single(pr, pr.forward(x.unsqueeze(0), camera_mask=mask), mask, return_2d)
+        frames = N.describe_frames(imgs_bgr, (self.num_cameras,), "bgr")
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True)
 
     def forward_yuv(self, frames, frame_format, cameraMatrices, intrinsicMatrices, distortionCoefficients,
                     camera_mask=None, return_2d=False):
@@ -188,13 +193,8 @@ class JarvisPredictor3D(nn.Module):
         image (BT.601 limited range); the conversion runs inside the resize / crop kernels.
         -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d: as forward()."""
         mask = self._frame_mask(camera_mask)
-        x = _yuv_frames(frames, frame_format, 3)
-        check_native_seam(self)
-        H, W = N.yuv_frame_hw(x.shape)
-        pr = self.native(H, W)
-        pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-        return self._single(pr, pr.forward(x.unsqueeze(0), frame_format=frame_format, camera_mask=mask), mask,
-                            return_2d)
+        frames = N.describe_frames(frames, (self.num_cameras,), N.yuv_format(frame_format))
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True)
 
     def forward_surface(self, frames, surface, cameraMatrices, intrinsicMatrices, distortionCoefficients,
                         camera_mask=None, return_2d=False):
@@ -206,12 +206,8 @@ class JarvisPredictor3D(nn.Module):
         (include/jarvis_hip.h); bytes outside the planes are never read.
         -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d: as forward()."""
         mask = self._frame_mask(camera_mask)
-        N.frame_layout(_need_surface(surface), None, (self.num_cameras,), None, frames)
-        check_native_seam(self)
-        x = N.dev(frames, torch.uint8)
-        pr = self.native(surface.height, surface.width)
-        pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-        return self._single(pr, pr.forward(x.unsqueeze(0), camera_mask=mask, frame_layout=surface), mask, return_2d)
+        frames = N.describe_frames(frames, (self.num_cameras,), None, N.surface(surface))
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True)
 
     def forward_batch(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
                       camera_mask=None, return_2d=False, frame_layout=None):
@@ -226,39 +222,12 @@ class JarvisPredictor3D(nn.Module):
         (points, confidences, valid, views).  Rows of invalid frames: used 0, points2D -1, NaN reprojections.
         frame_layout: a YuvSurface or a SensorSurface -- imgs (T,C,image_stride) uint8, see forward_surface; not
         together with frame_format 'i420' / 'nv12'."""
-        frame_format = N.frame_format(frame_format)
-        frame_layout = N.frame_layout(frame_layout, frame_format, (None, self.num_cameras), None, imgs)
         if camera_mask is not None:
             if not torch.is_tensor(imgs) or imgs.dim() < 1:
                 raise ValueError("imgs must be a tensor of time steps")
             camera_mask = N.camera_mask(camera_mask, (imgs.shape[0], self.num_cameras))
-        if frame_layout is not None:
-            check_native_seam(self)
-            x = N.dev(imgs, torch.uint8)
-            pr = self.native(frame_layout.height, frame_layout.width, time_batch=x.shape[0])
-            pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-            return self._batch(pr, pr.forward(x, camera_mask=camera_mask, frame_layout=frame_layout), camera_mask,
-                               return_2d)
-        if frame_format in N.YUV_FORMATS:
-            x = _yuv_frames(imgs, frame_format, 4)
-            check_native_seam(self)
-            H, W = N.yuv_frame_hw(x.shape)
-            pr = self.native(H, W, time_batch=x.shape[0])
-            pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-            return self._batch(pr, pr.forward(x, frame_format=frame_format, camera_mask=camera_mask), camera_mask,
-                               return_2d)
-        if frame_format == "bgr" and imgs.dtype != torch.uint8:
-            raise ValueError("frame_format 'bgr' needs uint8 (T,C,H,W,3) frames; got dtype %s" % imgs.dtype)
-        check_native_seam(self)
-        if imgs.dtype == torch.uint8:
-            x = N.dev(imgs, torch.uint8)
-            pr = self.native(x.shape[2], x.shape[3], time_batch=x.shape[0])
-            pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-            return self._batch(pr, pr.forward(x, camera_mask=camera_mask), camera_mask, return_2d)
-        x = N.dev(imgs)
-        pr = self.native(x.shape[3], x.shape[4], time_batch=x.shape[0])
-        pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-        return self._batch(pr, pr.forward(x, camera_mask=camera_mask), camera_mask, return_2d)
+        frames = N.describe_frames(imgs, (None, self.num_cameras), frame_format, frame_layout)
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d)
 
     def forward_images(self, images, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
                        frame_layout=None, camera_mask=None, return_2d=False):
@@ -283,32 +252,10 @@ class JarvisPredictor3D(nn.Module):
                     len(frame_set) if isinstance(frame_set, (list, tuple)) else type(frame_set).__name__))
         T = len(images)
         flat = [img for frame_set in images for img in frame_set]
-        fmt, (H, W), layout = N.frame_images(flat, T * self.num_cameras, frame_format, frame_layout)
+        frames = N.frame_images(flat, (T, self.num_cameras), frame_format, frame_layout)
         camera_mask = N.camera_mask(camera_mask, (T, self.num_cameras))
-        check_native_seam(self)
-        pr = self.native(H, W, time_batch=T)
-        pr.set_calibration(cameraMatrices, intrinsicMatrices, distortionCoefficients)
-        return self._batch(pr, pr.forward_images(flat, fmt, layout, camera_mask=camera_mask), camera_mask, return_2d)
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d)
 
     @staticmethod
     def _batch(pr, res, mask, return_2d):
         return tuple(res) + (pr.views2d(res[0], camera_mask=mask),) if return_2d else res
-
-
-def _need_surface(surface):
-    """The direct forms' `surface` argument: a YuvSurface or a SensorSurface, not None."""
-    if not N.is_frame_layout(surface):
-        raise ValueError("surface must be a YuvSurface or a SensorSurface, got %r" % (type(surface).__name__,))
-    return surface
-
-
-def _yuv_frames(frames, frame_format, ndim):
-    """YUV 4:2:0 frames of the public API checked (format, dtype, rank, even H and W) and made a contiguous CUDA
-    tensor; ValueError for what would be misread."""
-    if frame_format not in N.YUV_FORMATS:
-        raise ValueError("frame_format must be one of %s, got %r" % (list(N.YUV_FORMATS), frame_format))
-    if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != ndim:
-        raise ValueError("%s frames must be a %d-d uint8 tensor (..., 3H/2, W); got %s" % (
-            frame_format, ndim, (frames.dtype, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)))
-    N.yuv_frame_hw(frames.shape)
-    return N.dev(frames, torch.uint8)

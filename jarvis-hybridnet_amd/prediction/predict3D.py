@@ -215,13 +215,8 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             if frame_layout is not None:
                 kw["frame_layout"] = frame_layout
             if hasattr(predictor, "native_streams"):
-                if frame_layout is not None:
-                    h, w = frame_layout.height, frame_layout.width
-                elif yuv:
-                    h, w = N.yuv_frame_hw(x.shape)
-                else:
-                    h, w = (x.shape[2], x.shape[3]) if x.dtype == torch.uint8 else (x.shape[3], x.shape[4])
-                msp = predictor.native_streams(h, w, time_batch, streams)
+                d = N.describe_shape(x.shape, x.dtype, (time_batch, None), frame_format if yuv else None, frame_layout)
+                msp = predictor.native_streams(d.height, d.width, time_batch, streams)
                 msp.set_calibration(*calib)
                 # results leave for pinned host memory on the forward's own stream (behind it, before its event)
                 res = msp.forward(x, then=lambda outs: host_outputs(ring, slot, outs),

@@ -74,15 +74,25 @@ def test_frame_images_checks(no_native):
         N.frame_images([torch.zeros((H, W, 3))] * 3, 3)
 
 
-def test_layout_args_and_table():
+def test_layout_args_and_table(monkeypatch):
+    """(table, n, fmt, yuv, sensor) of jh_predictor*_forward_images as _native.call_forward hands them over: the
+    struct the format needs, NULL for the other, and the images' own addresses."""
+    seen = []
+    monkeypatch.setattr(N, "lib", lambda: type("L", (), {"__getattr__": lambda self, name: lambda *a: seen.append(a) or 0})())
+    monkeypatch.setattr(N, "stream", lambda: 0)
+
+    def layout_args(fmt, layout, imgs):
+        del seen[:]
+        N.call_forward("jh_predictor2d", None, N.Frames(fmt, H, W, layout, (len(imgs),), images=imgs), None, ())
+        assert seen[0][2:4] == (len(imgs), fmt)
+        return seen[0][1], seen[0][4:6]
     y, s = YuvSurface(H, W, "nv12"), SensorSurface(H, W, "mono")
-    a = N.layout_args(N.FRAME_SURFACE, y)
-    assert isinstance(a[0], N.YuvSurfaceStruct) and a[1] is None
-    a = N.layout_args(N.FRAME_SENSOR, s)
-    assert a[0] is None and isinstance(a[1], N.SensorSurfaceStruct)
-    assert N.layout_args(N.FRAME_FORMATS["bgr"], None) == (None, None)
     imgs = bgr(3)
-    tab = N.image_table(imgs)
+    tab, a = layout_args(N.FRAME_SURFACE, y, imgs)
+    assert isinstance(a[0], N.YuvSurfaceStruct) and a[1] is None
+    _, a = layout_args(N.FRAME_SENSOR, s, imgs)
+    assert a[0] is None and isinstance(a[1], N.SensorSurfaceStruct)
+    assert layout_args(N.FRAME_FORMATS["bgr"], None, imgs)[1] == (None, None)
     assert [tab[i] for i in range(3)] == [t.data_ptr() for t in imgs]
 
 

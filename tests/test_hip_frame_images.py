@@ -171,8 +171,8 @@ def test_stand_alone_kernels(rig, name, monkeypatch):
     pred = predictor(rig)
     every_form_equals_contiguous(rig, eager(eager(predictor(rig), 1), 2), pred, [name])
     views = scatter(list(rig["frames"][name][0]))
-    fmt, _, layout = N.frame_images(views, rig["C"], **how(name))
-    names = {r[0] for r in N.profile(lambda: pred.native(H, W).forward_images(views, fmt, layout))}
+    described = N.frame_images(views, rig["C"], **how(name))
+    names = {r[0] for r in N.profile(lambda: pred.native(H, W).forward_images(described))}
     assert {"preprocess_resize", "preprocess_crop"} <= names, "JH_STEM_FUSE=0 had no effect"
 
 
@@ -225,8 +225,7 @@ def test_graph_replay_follows_the_pointers(rig, name):
     for i, (kind, s, v, m) in enumerate(steps):
         if kind == "img":
             views = pools[s, v]
-            fmt, _, layout = N.frame_images(views, C, **fkw)
-            got = g.forward_images(views, fmt, layout, camera_mask=m)
+            got = g.forward_images(N.frame_images(views, C, **fkw), camera_mask=m)
         else:
             got = g.forward(contig[s], camera_mask=m, **fkw)
         same(got, want[s, m is not None], (i, kind, s, v, m is not None))

@@ -124,15 +124,18 @@ def test_matches_cv2_cvtcolor():
 
 def test_frame_format_names():
     from jarvis_hybridnet_amd import _native as N
-    assert N.frame_format(None) is None and N.frame_format("i420") == "i420"
+    def hw(shape, fmt="i420"):
+        d = N.describe_shape(shape, torch.uint8, (None,) * (len(shape) - 2), fmt)
+        return d.height, d.width
+    assert N.describe_shape((4, 6, 3), torch.uint8, (), None).fmt == 1 and hw((12, 10), "i420") == (8, 10)
     assert N.FRAME_FORMATS == {"bgr": 1, "i420": 2, "nv12": 3}
     for bad in ("I420", "yuv420p", "rgb", 2):
         with pytest.raises(ValueError):
-            N.frame_format(bad)
-    assert N.yuv_frame_hw((12, 10)) == (8, 10) and N.yuv_frame_hw((2, 3, 1536, 1280)) == (1024, 1280)
+            hw((12, 10), bad)
+    assert hw((12, 10)) == (8, 10) and hw((2, 3, 1536, 1280)) == (1024, 1280)
     for bad in ((7, 10), (12, 9), (0, 4)):
         with pytest.raises(ValueError):
-            N.yuv_frame_hw(bad)
+            hw(bad)
     # the C ABI's codes (include/jarvis_hip.h)
     import re
     root = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -251,7 +254,11 @@ def test_predictor_entry_points_refuse_bad_yuv_arguments():
     """The public forms validate format, dtype and shape before anything reaches the GPU (no GPU needed: the
     checks run first)."""
     from jarvis_hybridnet_amd.distributed import ShardedPredictor
-    from jarvis_hybridnet_amd.prediction.jarvis3D import _yuv_frames
+    from jarvis_hybridnet_amd import _native as N
+
+    def _yuv_frames(frames, frame_format, ndim):            # (forward_yuv's check of a (C, 3H/2, W) frame set)
+        assert ndim == 3
+        return N.describe_frames(frames, (2,), N.yuv_format(frame_format))
     ok = torch.zeros((2, 6, 4), dtype=torch.uint8)
     with pytest.raises(ValueError, match="frame_format"):
         _yuv_frames(ok, "bgr", 3)

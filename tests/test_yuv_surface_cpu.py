@@ -361,18 +361,21 @@ def test_entry_points_refuse_bad_layout_arguments():
     from jarvis_hybridnet_amd.distributed import ShardedPredictor
     s = YuvSurface(4, 6, "nv12")
     ok = torch.zeros((3, 2, s.image_stride), dtype=torch.uint8)
-    assert N.frame_layout(None, "nv12", ()) is None
-    assert N.frame_layout(s, None, (3, 2), (4, 6), ok) is s and N.frame_layout(s, "bgr", (None, 2), None, ok) is s
+    assert N.check_layout(None, "nv12") is None
+    def frame_layout(layout, fmt, lead, hw, frames):
+        return N.describe_frames(frames, lead, fmt, layout, hw)
+    assert N.describe_shape(ok.shape, ok.dtype, (3, 2), None, s, (4, 6)).layout is s
+    assert N.describe_shape(ok.shape, ok.dtype, (None, 2), "bgr", s).layout is s
     for fmt in ("i420", "nv12"):
         with pytest.raises(ValueError, match="frame_layout"):
-            N.frame_layout(s, fmt, (3, 2), (4, 6), ok)
+            frame_layout(s, fmt, (3, 2), (4, 6), ok)
     for bad in (ok.float(), ok[0], ok[..., :-1], torch.zeros((3, 1, s.image_stride), dtype=torch.uint8), ok.numpy()):
         with pytest.raises(ValueError):
-            N.frame_layout(s, None, (3, 2), (4, 6), bad)
+            frame_layout(s, None, (3, 2), (4, 6), bad)
     with pytest.raises(ValueError, match="4 x 6"):
-        N.frame_layout(s, None, (3, 2), (8, 6), ok)
+        frame_layout(s, None, (3, 2), (8, 6), ok)
     with pytest.raises(ValueError, match="YuvSurface"):
-        N.frame_layout(s.struct(), None, (3, 2), (4, 6), ok)
+        frame_layout(s.struct(), None, (3, 2), (4, 6), ok)
     with pytest.raises(ValueError, match="frame_layout"):
         ShardedPredictor.submit(NS(), ok, None, None, False, s)
     with pytest.raises(ValueError, match="camera-sharded"):
