@@ -161,6 +161,34 @@ int jh_predictor_precision(const jh_predictor* pr);    /* the resolved mode (nev
 /* calibration of all cameras (device pointers, copied). */
 int jh_predictor_set_calibration(jh_predictor* pr, const float* cam_dev, const float* intr_dev,
                                  const float* dist_dev, void* stream);
+/* Per-frame-set calibration (ABI v4, additive): one calibration PER FRAME SET of the time batch, as the reference
+ * passes one with every call (jarvis3D.py:127-133) and its validation analysis takes each sample's own
+ * (jarvis/analysis/analyze.py:54-96).
+ *   cam (T,C,4,3), intr (T,C,3,3), dist (T,C,1,5) dev, T = time_batch: row t is the calibration of frame set t, in the
+ *   layout of jh_predictor_set_calibration.  Rows of ALL T frame sets are given, also with time_batch_3d < T and
+ *   on a camera-sharded predictor (every rank triangulates all T frames; stage 3 and the 2D views of the frames
+ *   t0 .. read rows t0 ..).
+ * Lifetime: the rows are COPIED, on `stream`, into buffers the predictor owns (T times the shared ones).  The first such
+ * call of a predictor allocates them -- never jh_predictor_create, so jh_predictor_device_bytes and the memory of a
+ * predictor that never uses it are unchanged -- and that first call must not be made inside a stream capture.
+ * After it every entry point of this predictor reads row t for frame set t -- all forwards,
+ * jh_predictor_stage_keypoints*, jh_predictor_stage_3d* (_blocks, _masked), jh_predictor_views2d,
+ * jh_predictor_hybridnet_forward -- until
+ * jh_predictor_set_calibration returns it to the shared form; the two calls may alternate freely.  The stand-alone
+ * operators (jh_reproject_forward, jh_reconstruct_point, jh_reproject_point) take one calibration, as before.
+ * Graph replay: a recorded graph holds the buffers' addresses and the form.  A change of FORM (shared <-> per frame)
+ * between two forwards records again (the replay in flight is waited for before its executable graph goes), as a
+ * described surface whose description changes does; a change of VALUES within one form keeps replaying the one
+ * recording, because the values live in the predictor's buffers.
+ * Results: only the address of a frame set's 12 + 9 + 5 floats per camera differs between the forms -- the arithmetic
+ * is the same, operation for operation.  Row t of a batch under per-frame calibration therefore equals, BIT FOR BIT,
+ * row t of the same batch (same predictor, frames and mask row) run with calibration k(t) as the shared calibration:
+ * points, confidences, valid, the float and integer 3D centre, the crop centres, num_cams_detect and the five outputs
+ * of jh_predictor_views2d.  jh_predictor_set_calibration and everything that follows it keep the bits they had.
+ * Validation: pr and the three pointers non-NULL; otherwise non-zero with jh_last_error() set, nothing enqueued. */
+int jh_predictor_set_calibration_frames(jh_predictor* pr, const float* cam_dev /* (T,C,4,3) */,
+                                        const float* intr_dev /* (T,C,3,3) */, const float* dist_dev /* (T,C,1,5) */,
+                                        void* stream);
 
 /* Stage 1 (jarvis3D.py:135-155): resize + normalise + CenterDetect + argmax for
  * the owned cameras.  frames (T,cam_n,3,H,W) dev -> det (T,cam_n,3) = (x, y,

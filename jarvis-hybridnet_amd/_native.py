@@ -109,6 +109,7 @@ _SIGS = {
     "jh_predictor_device_bytes": (c_int64, [c_void_p]),
     "jh_predictor_precision": (c_int, [c_void_p]),
     "jh_predictor_set_calibration": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_predictor_set_calibration_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_stage_center": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_stage_keypoints": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_stage_3d": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
@@ -426,6 +427,40 @@ def camera_mask(mask, shape, what="camera_mask"):
     if tuple(mask.shape) != tuple(shape):
         raise ValueError("%s must have shape %s; got %s" % (what, tuple(shape), tuple(mask.shape)))
     return (mask != 0).to(torch.uint8).contiguous()
+
+
+_CALIB_TAILS = ((4, 3), (3, 3), (1, 5))       # cameraMatrices, intrinsicMatrices, distortionCoefficients per camera
+
+
+def calibration(calib, T, C):
+    """The calibration arguments of a batched call checked -> (form, cam, intr, dist), form "shared" or "frames".
+    calib: the three tensors (cameraMatrices, intrinsicMatrices, distortionCoefficients) in the reference's transposed
+    storage, either (C,4,3) / (C,3,3) / (C,1,5) -- one calibration shared by the T frame sets
+    (jh_predictor_set_calibration) -- or the same three with a leading T -- row t is the calibration of frame set t
+    (jh_predictor_set_calibration_frames).  The tensors are returned as given: no copy, no device, no dtype change.
+    ValueError for fewer or more than three tensors, a non-floating dtype, a wrong T or C, any other shape, and for
+    a mix of the two forms."""
+    if not isinstance(calib, (list, tuple)) or len(calib) != 3 or not all(torch.is_tensor(t) for t in calib):
+        raise ValueError("calibration is three tensors (cameraMatrices, intrinsicMatrices, distortionCoefficients); "
+                         "got %s" % ([type(t).__name__ for t in calib] if isinstance(calib, (list, tuple))
+                                     else type(calib).__name__))
+    names = ("cameraMatrices", "intrinsicMatrices", "distortionCoefficients")
+    forms = []
+    for name, t, tail in zip(names, calib, _CALIB_TAILS):
+        if not t.dtype.is_floating_point:
+            raise ValueError("%s must be a floating-point tensor; got dtype %s" % (name, t.dtype))
+        shape = tuple(int(n) for n in t.shape)
+        if shape == (C,) + tail:
+            forms.append("shared")
+        elif shape == (T, C) + tail:
+            forms.append("frames")
+        else:
+            raise ValueError("%s must have shape %s (shared by the frame sets) or %s (one per frame set); got %s"
+                             % (name, (C,) + tail, (T, C) + tail, shape))
+    if len(set(forms)) != 1:
+        raise ValueError("the three calibration tensors are either all per camera (C, ...) or all per frame set "
+                         "(T, C, ...); got %s" % ", ".join("%s: %s" % nf for nf in zip(names, forms)))
+    return (forms[0],) + tuple(calib)
 
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x3_wide": 2}

@@ -65,6 +65,18 @@ class NativePredictor:
         N.check(N.lib().jh_predictor_set_calibration(
             self.handle, N.ptr(N.dev(cam)), N.ptr(N.dev(intr)), N.ptr(N.dev(dist)), N.stream()))
 
+    def set_calibration_frames(self, cam, intr, dist):
+        """One calibration per frame set of the time batch: cam (T,C,4,3), intr (T,C,3,3), dist (T,C,1,5) device
+        tensors, row t for frame set t (jh_predictor_set_calibration_frames; copied on the current stream).  Every
+        later call of this predictor reads row t for frame set t until set_calibration() returns it to the shared
+        form.  Row t of a result equals, bit for bit, row t of the same batch under set_calibration(row t)."""
+        form, cam, intr, dist = N.calibration((cam, intr, dist), self.T, self.C)
+        if form != "frames":
+            raise ValueError("set_calibration_frames takes (%d, %d, 4, 3) / (%d, %d, 3, 3) / (%d, %d, 1, 5) tensors; "
+                             "got %s" % (self.T, self.C, self.T, self.C, self.T, self.C, tuple(cam.shape)))
+        N.check(N.lib().jh_predictor_set_calibration_frames(
+            self.handle, N.ptr(N.dev(cam)), N.ptr(N.dev(intr)), N.ptr(N.dev(dist)), N.stream()))
+
     # ---- single-GPU forward ----------------------------------------------
     def forward(self, frames, out=None, frame_format=None, camera_mask=None, frame_layout=None):
         """frames (T,C,3,H,W) fp32 RGB, or (T,C,H,W,3) uint8 BGR as decoded, or with frame_format 'i420' / 'nv12'
@@ -240,13 +252,26 @@ class MultiStreamPredictor:
         self.events = [None] * streams
         self._next = 0
         self._calib = None
+        self._calib_of = [None] * streams            # per predictor: (key, tensors) of the per-frame calibration it holds
 
     def set_calibration(self, *calib):
         """Calibration of every predictor, written on that predictor's OWN stream (so the copy
         is ordered against the forwards in flight there).  Setting the same tensors again is a
-        no-op: drivers may call this once per group of frames."""
-        key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in calib)
+        no-op: drivers may call this once per group of frames.
+        Per-frame form -- (T,C,4,3) / (T,C,3,3) / (T,C,1,5), row t for frame set t (_native.calibration) --: the
+        calibration of ONE batch, the one the next forward() enqueues.  It goes to the predictor that batch runs on
+        alone, on that predictor's stream, inside forward(); the batches in flight on the other streams keep theirs.
+        It stays in force for later forwards until another calibration is set (each predictor is given it when its
+        turn comes; one that holds these very tensors already is left alone)."""
+        p0 = self.preds[0]
+        # (the shared form is taken as it always was; what has a leading T is checked as the per-frame form)
+        form = N.calibration(calib, p0.T, p0.C)[0] if len(calib) == 3 and calib[0].dim() == 4 else "shared"
+        key = (form,) + tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in calib)
         if key == self._calib:
+            return
+        if form == "frames":
+            self._calib_refs = tuple(calib)          # (alive while keyed, as below)
+            self._calib = key
             return
         # the key is only meaningful while the keyed tensors are alive: a freed calibration's
         # address is handed out again by the caching allocator (same size, _version 0), and the
@@ -262,6 +287,20 @@ class MultiStreamPredictor:
                 if t.is_cuda:
                     t.record_stream(s)
         self._calib = key
+        self._calib_of = [None] * len(self.preds)
+
+    def _frames_calibration(self, i):
+        """Inside predictor i's stream context: its copy of the per-frame calibration in force, if it has not got it."""
+        if self._calib is None or self._calib[0] != "frames":
+            return
+        held = self._calib_of[i]
+        if held is not None and held[0] == self._calib:
+            return
+        self.preds[i].set_calibration_frames(*self._calib_refs)
+        for t in self._calib_refs:
+            if t.is_cuda:
+                t.record_stream(self.streams[i])
+        self._calib_of[i] = (self._calib, self._calib_refs)       # the tensors live as long as their key is compared
 
     def forward(self, frames, out=None, then=None, frame_format=None, camera_mask=None, return_2d=False,
                 frame_layout=None):
@@ -285,6 +324,7 @@ class MultiStreamPredictor:
         for t in (out or ()):
             t.record_stream(s)
         with torch.cuda.stream(s):
+            self._frames_calibration(i)
             res = self.preds[i]._forward(described, out, camera_mask)
             if return_2d:
                 res = tuple(res) + tuple(self.preds[i].views2d(res[0], camera_mask=camera_mask))

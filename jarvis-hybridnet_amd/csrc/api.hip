@@ -219,7 +219,7 @@ int jh_reproject_forward(const float* heatmaps_padded_dev, int cams, int joints,
   carve_reproject(c, cams, joints, hs, grid_size, &w);
   JH_REQUIRE(c.fits(), "workspace smaller than jh_reproject_workspace_bytes()");
   if (launch_to_channel_last(heatmaps_padded_dev, w.heat, s)) return 1;
-  if (launch_reproject(cam_dev, intr_dev, dist_dev, center3d_dev, center_hm_dev, w.heat.p, w.coarse,
+  if (launch_reproject(cam_dev, intr_dev, dist_dev, /*calib_fs=*/0, center3d_dev, center_hm_dev, w.heat.p, w.coarse,
                        w.vol.p, idx_dev, 1, cams, grid_size, grid_spacing, hs, w.heat.Cp,
                        /*heat_pad=*/1, /*div255=*/0, s)) return 1;
   return launch_from_channel_last(w.vol, vol_dev, s);
@@ -271,7 +271,7 @@ int jh_reconstruct_point(const float* points2d_dev, const float* maxvals_dev, in
   JH_REQUIRE(c.fits(), "workspace smaller than jh_reconstruct_workspace_bytes()");
   hipLaunchKernelGGL(pack_det_kernel, dim3(1), dim3(64), 0, s, points2d_dev, maxvals_dev, w.det, cams);
   JH_CHECK_HIP(hipGetLastError());
-  return launch_triangulate(w.det, cam_dev, intr_dev, dist_dev, point3d_dev, w.c3i, w.chm, w.valid, 1,
+  return launch_triangulate(w.det, cam_dev, intr_dev, dist_dev, /*calib_fs=*/0, point3d_dev, w.c3i, w.chm, w.valid, 1,
                             cams, 1.f, 1.f, 1.f, 0, 1 << 20, 1 << 20, s);
 }
 
@@ -443,6 +443,15 @@ struct jh_predictor {
   std::unique_ptr<V2VPlan> v2v;
   Scratch mem;
   float *cam = nullptr, *intr = nullptr, *dist = nullptr;
+  // Per-frame calibration (jh_predictor_set_calibration_frames): T rows of the three arrays above, allocated by the
+  // first such call.  calib_fs is the frame stride every launch that reads calibration is given: 0 -- all frames read
+  // cam / intr / dist --, or C -- frame t reads row t of cam_f / intr_f / dist_f.  A call that starts at frame t0
+  // (stage 3, views2d) passes the pointers of row t0, as it passes the centres' and the mask's.
+  float *cam_f = nullptr, *intr_f = nullptr, *dist_f = nullptr;
+  int calib_fs = 0;
+  const float* cam_at(int t0) const { return calib_fs ? cam_f + (size_t)t0 * calib_fs * 12 : cam; }
+  const float* intr_at(int t0) const { return calib_fs ? intr_f + (size_t)t0 * calib_fs * 9 : intr; }
+  const float* dist_at(int t0) const { return calib_fs ? dist_f + (size_t)t0 * calib_fs * 5 : dist; }
   float *det_all = nullptr, *c3f = nullptr;
   // Crop centres, truncated 3D centre and validity of a time batch: written by stage 2 (triangulation), read by
   // stage 3.  TWO sets: the staged entry points alternate between them, so that stage 3 of time batch i may run
@@ -473,9 +482,10 @@ struct jh_predictor {
   // [2 * kGraphFmts + ...]: the same again for the per-image form, which has slots of its OWN -- a stream of
   // per-image calls and a stream of contiguous calls of one format never re-record each other.  A launch
   // carries its source's description by value, so a recording has ONE source: the slot keeps the FrameSource its
-  // graph was captured with, and a call with another one records again (forward_graph).
+  // graph was captured with, and a call with another one records again (forward_graph).  The same holds for the
+  // calibration's form: a recording holds the pointers and the frame stride (calib_fs) it was captured with.
   static constexpr int kGraphFmts = kSrcSensor + 1;
-  struct GraphSlot { hipGraphExec_t exec = nullptr; FrameSource src; };
+  struct GraphSlot { hipGraphExec_t exec = nullptr; FrameSource src; int calib_fs = 0; };
   GraphSlot gslot[4 * kGraphFmts];
   // Camera mask (camera_mask.h).  mask_buf [T][C]: the predictor's copy of the current call's mask -- the masked
   // kernels (and a captured graph of them) read this buffer, so the mask may change from call to call.  mask_cur:
@@ -501,13 +511,15 @@ struct jh_predictor {
     if (mask_cur) {
       // (algorithmic traffic as for all cameras: an upper bound, the unmasked cameras' heatmaps are what is read)
       JH_PROF("reproject_gather_masked", 0.0, 4.0 * T3 * ((double)C * Hh * Hh * J + g3 * J),
-              launch_reproject_masked(cam, intr, dist, c3i_cur() + t0 * 3, chm_cur() + t0 * C * 2, heat_all, coarse,
-                                      v2v->input.p, nullptr, T3, C, G, cfg.grid_spacing, hs, Jp,
+              launch_reproject_masked(cam_at(t0), intr_at(t0), dist_at(t0), calib_fs, c3i_cur() + t0 * 3,
+                                      chm_cur() + t0 * C * 2, heat_all, coarse, v2v->input.p, nullptr, T3, C, G,
+                                      cfg.grid_spacing, hs, Jp,
                                       /*heat_pad=*/0, /*div255=*/1, mask_cur + (size_t)t0 * C, s, layout));
     } else {
     JH_PROF("reproject_gather", 0.0, 4.0 * T3 * ((double)C * Hh * Hh * J + g3 * J),
-            launch_reproject(cam, intr, dist, c3i_cur() + t0 * 3, chm_cur() + t0 * C * 2, heat_all, coarse,
-                             v2v->input.p, nullptr, T3, C, G, cfg.grid_spacing, hs, Jp,
+            launch_reproject(cam_at(t0), intr_at(t0), dist_at(t0), calib_fs, c3i_cur() + t0 * 3,
+                             chm_cur() + t0 * C * 2, heat_all, coarse, v2v->input.p, nullptr, T3, C, G,
+                             cfg.grid_spacing, hs, Jp,
                              /*heat_pad=*/0, /*div255=*/1, s, layout));
     }
     if (v2v->run(s)) return 1;
@@ -635,6 +647,32 @@ int jh_predictor_set_calibration(jh_predictor* pr, const float* cam_dev, const f
   JH_CHECK_HIP(hipMemcpyAsync(pr->cam, cam_dev, (size_t)pr->C * 12 * sizeof(float), hipMemcpyDeviceToDevice, s));
   JH_CHECK_HIP(hipMemcpyAsync(pr->intr, intr_dev, (size_t)pr->C * 9 * sizeof(float), hipMemcpyDeviceToDevice, s));
   JH_CHECK_HIP(hipMemcpyAsync(pr->dist, dist_dev, (size_t)pr->C * 5 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  pr->calib_fs = 0;                           // (back to the shared form, if the per-frame one was in use)
+  return 0;
+}
+
+int jh_predictor_set_calibration_frames(jh_predictor* pr, const float* cam_dev, const float* intr_dev,
+                                        const float* dist_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(pr, "jh_predictor_set_calibration_frames: null predictor");
+  JH_REQUIRE(cam_dev && intr_dev && dist_dev, "jh_predictor_set_calibration_frames: null calibration pointer");
+  const size_t rows = (size_t)pr->T * pr->C;
+  if (!pr->cam_f) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s, &cs);
+    JH_REQUIRE(cs == hipStreamCaptureStatusNone, "the first jh_predictor_set_calibration_frames call of a predictor "
+               "allocates its per-frame calibration: make it outside a stream capture");
+    // (one allocation: cam_f is set last, so a failure leaves the predictor as it was)
+    float* base = nullptr;
+    if (pr->mem.get(reinterpret_cast<void**>(&base), rows * 26 * sizeof(float))) return 1;
+    pr->intr_f = base + rows * 12;
+    pr->dist_f = base + rows * 21;
+    pr->cam_f = base;
+  }
+  JH_CHECK_HIP(hipMemcpyAsync(pr->cam_f, cam_dev, rows * 12 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  JH_CHECK_HIP(hipMemcpyAsync(pr->intr_f, intr_dev, rows * 9 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  JH_CHECK_HIP(hipMemcpyAsync(pr->dist_f, dist_dev, rows * 5 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  pr->calib_fs = pr->C;
   return 0;
 }
 
@@ -692,13 +730,15 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, const 
   const float sy2 = (float)((double)c.img_h / (double)c.center_size) * 2.f;
   if (pr->mask_cur) {
     JH_PROF("triangulate_masked", 0.0, 0.0,
-            launch_triangulate_masked(det_all_dev, pr->cam, pr->intr, pr->dist, pr->c3f, pr->c3i_cur(),
-                                      pr->chm_cur(), pr->valid_cur(), pr->T, pr->C, sx2, sy2, 255.f, pr->B / 2,
+            launch_triangulate_masked(det_all_dev, pr->cam_at(0), pr->intr_at(0), pr->dist_at(0), pr->calib_fs, pr->c3f,
+                                      pr->c3i_cur(), pr->chm_cur(), pr->valid_cur(), pr->T, pr->C, sx2, sy2, 255.f,
+                                      pr->B / 2,
                                       c.img_w, c.img_h, pr->mask_cur, pr->n_active, pr->n_detect, s));
   } else {
   JH_PROF("triangulate", 0.0, 0.0,
-          launch_triangulate(det_all_dev, pr->cam, pr->intr, pr->dist, pr->c3f, pr->c3i_cur(), pr->chm_cur(),
-                             pr->valid_cur(), pr->T, pr->C, sx2, sy2, 255.f, pr->B / 2, c.img_w, c.img_h, s));
+          launch_triangulate(det_all_dev, pr->cam_at(0), pr->intr_at(0), pr->dist_at(0), pr->calib_fs, pr->c3f,
+                             pr->c3i_cur(), pr->chm_cur(), pr->valid_cur(), pr->T, pr->C, sx2, sy2, 255.f, pr->B / 2,
+                             c.img_w, c.img_h, s));
   }
   if (det_all_dev != pr->det_all)
     JH_CHECK_HIP(hipMemcpyAsync(pr->det_all, det_all_dev, (size_t)pr->T * pr->C * 3 * sizeof(float),
@@ -790,8 +830,9 @@ static int forward_graph(jh_predictor* pr, const void* frames_dev, const FrameSo
                                             (fs.per_image ? 2 * jh_predictor::kGraphFmts : 0)];
   // the recorded launches hold the description they were captured with: another one records again (rare: a stream
   // keeps its layout, and a fixed format has nothing to differ in; the replay in flight is waited for before its
-  // executable graph goes)
-  if (slot.exec && slot.src != fs) {
+  // executable graph goes).  Likewise the calibration's form, shared or per frame: its pointers and frame stride are
+  // in the recording.  Its VALUES are not: they live in the predictor's buffers.
+  if (slot.exec && (slot.src != fs || slot.calib_fs != pr->calib_fs)) {
     JH_CHECK_HIP(hipStreamSynchronize(s));
     (void)hipGraphExecDestroy(slot.exec);
     slot.exec = nullptr;
@@ -811,6 +852,7 @@ static int forward_graph(jh_predictor* pr, const void* frames_dev, const FrameSo
     if (ei != hipSuccess) slot.exec = nullptr;
     JH_CHECK_HIP(ei);
     slot.src = fs;
+    slot.calib_fs = pr->calib_fs;
   }
   // (per-image: the recording reads frames_table, which this call's pointers have already been sent into)
   if (!fs.per_image) hipLaunchKernelGGL(set_cell_kernel, dim3(1), dim3(1), 0, s, pr->frames_cell, frames_dev);
@@ -976,8 +1018,9 @@ int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, co
   const int slices = joint_argmax_all_shape(N, pr->Hh, pr->Hh, pr->Jp).slices;
   JH_PROF("views2d_final", 0.0, 8.0 * N * slices * pr->Jp + 24.0 * N * pr->J,
           launch_views2d_final(pr->v2d_max, pr->v2d_idx, pr->chm_cur() + (size_t)t0 * pr->C * 2, pr->valid_cur() + t0,
-                               mask_dev ? mask_dev + (size_t)t0 * pr->C : nullptr, points_dev, pr->cam, pr->intr,
-                               pr->dist, points2d_dev, conf2d_dev, reproj_dev, err_dev, used_dev, pr->T3, pr->C,
+                               mask_dev ? mask_dev + (size_t)t0 * pr->C : nullptr, points_dev, pr->cam_at(t0),
+                               pr->intr_at(t0), pr->dist_at(t0), pr->calib_fs, points2d_dev, conf2d_dev, reproj_dev,
+                               err_dev, used_dev, pr->T3, pr->C,
                                pr->J, pr->Jp, pr->Hh, pr->Hh, pr->B / 2, s));
   return 0;
 }

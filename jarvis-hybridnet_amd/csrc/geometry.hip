@@ -344,10 +344,13 @@ __device__ __forceinline__ void project_one(const float* M, const float* K, cons
 // exact 0.0 -- SELECTED, not multiplied: its detection may be NaN -- and s + 0.0 == s, so the centre has the bits
 // of a run over the unmasked cameras alone; it is not counted either.  Its crop centre is still written (the
 // clamped projection of the centre: in range whatever its frame held).
+// fs: the calibration's frame stride in cameras -- frame t reads row t * fs + c of cam / intr / dist; 0: one calibration
+// shared by all frames, C: one per frame (jh_predictor_set_calibration_frames).  Only the address of the 26 floats
+// moves: the operations on them are the same.
 template <bool MASK>
 __device__ __forceinline__ void triangulate_body(
     const float* __restrict__ det, const float* __restrict__ cam, const float* __restrict__ intr,
-    const float* __restrict__ dist, float* __restrict__ center3d_f, int* __restrict__ center3d_i,
+    const float* __restrict__ dist, int fs, float* __restrict__ center3d_f, int* __restrict__ center3d_i,
     int* __restrict__ center_hm, int* __restrict__ valid, int C, float sx2, float sy2, float wdiv,
     int hw, int W, int H, const unsigned char* __restrict__ mask, int* __restrict__ n_active,
     int* __restrict__ n_detect) {
@@ -357,6 +360,7 @@ __device__ __forceinline__ void triangulate_body(
   __shared__ int cnt;
   __shared__ int act;
   const int t = blockIdx.x, c = threadIdx.x;
+  const size_t row = (size_t)t * fs + c;        // this camera's calibration
   if (c == 0) { cnt = 0; if constexpr (MASK) act = 0; }
   __syncthreads();
   if (c < C) {
@@ -366,10 +370,10 @@ __device__ __forceinline__ void triangulate_body(
       if (live) atomicAdd(&act, 1);
     }
     const float* d = det + ((size_t)t * C + c) * 3;
-    const float* K = intr + c * 9;
-    const float* M = cam + c * 12;
+    const float* K = intr + row * 9;
+    const float* M = cam + row * 12;
     const float cx = K[6], cy = K[7], fx = K[0], fy = K[4];
-    const float k1 = dist[c * 5 + 0], k2 = dist[c * 5 + 1];
+    const float k1 = dist[row * 5 + 0], k2 = dist[row * 5 + 1];
     if (live && d[2] > 50.f) atomicAdd(&cnt, 1);
     const float wgt = __fdiv_rn(d[2], wdiv);
     // undistort the detection (single-step inverse), reprojection.py:71-78
@@ -420,7 +424,7 @@ __device__ __forceinline__ void triangulate_body(
   __syncthreads();
   if (c < C) {
     float u, v;
-    project_one(cam + c * 12, intr + c * 9, dist + c * 5, ctr[0], ctr[1], ctr[2], &u, &v);
+    project_one(cam + row * 12, intr + row * 9, dist + row * 5, ctr[0], ctr[1], ctr[2], &u, &v);
     int iu = (int)u, iv = (int)v;
     iu = min(max(iu, hw), W - hw);             // jarvis3D.py:163-166
     iv = min(max(iv, hw), H - hw);
@@ -431,40 +435,42 @@ __device__ __forceinline__ void triangulate_body(
 
 __global__ __launch_bounds__(64) void triangulate_kernel(
     const float* __restrict__ det, const float* __restrict__ cam, const float* __restrict__ intr,
-    const float* __restrict__ dist, float* __restrict__ center3d_f, int* __restrict__ center3d_i,
+    const float* __restrict__ dist, int fs, float* __restrict__ center3d_f, int* __restrict__ center3d_i,
     int* __restrict__ center_hm, int* __restrict__ valid, int C, float sx2, float sy2, float wdiv,
     int hw, int W, int H) {
-  triangulate_body<false>(det, cam, intr, dist, center3d_f, center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H,
+  triangulate_body<false>(det, cam, intr, dist, fs, center3d_f, center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H,
                           nullptr, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(64) void triangulate_masked_kernel(
     const float* __restrict__ det, const float* __restrict__ cam, const float* __restrict__ intr,
-    const float* __restrict__ dist, float* __restrict__ center3d_f, int* __restrict__ center3d_i,
+    const float* __restrict__ dist, int fs, float* __restrict__ center3d_f, int* __restrict__ center3d_i,
     int* __restrict__ center_hm, int* __restrict__ valid, int C, float sx2, float sy2, float wdiv,
     int hw, int W, int H, const unsigned char* __restrict__ mask, int* __restrict__ n_active,
     int* __restrict__ n_detect) {
-  triangulate_body<true>(det, cam, intr, dist, center3d_f, center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H,
+  triangulate_body<true>(det, cam, intr, dist, fs, center3d_f, center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H,
                          mask, n_active, n_detect);
 }
 
-int launch_triangulate_masked(const float* det, const float* cam, const float* intr, const float* dist,
+int launch_triangulate_masked(const float* det, const float* cam, const float* intr, const float* dist, int calib_fs,
                               float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C,
                               float sx2, float sy2, float wdiv, int hw, int W, int H,
                               const unsigned char* mask, int* n_active, int* n_detect, hipStream_t s) {
   JH_REQUIRE(C <= 64, "at most 64 cameras");
   JH_REQUIRE(mask && n_active && n_detect, "camera mask");
-  hipLaunchKernelGGL(triangulate_masked_kernel, dim3(T), dim3(64), 0, s, det, cam, intr, dist, center3d_f,
+  JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
+  hipLaunchKernelGGL(triangulate_masked_kernel, dim3(T), dim3(64), 0, s, det, cam, intr, dist, calib_fs, center3d_f,
                      center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H, mask, n_active, n_detect);
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
-int launch_triangulate(const float* det, const float* cam, const float* intr, const float* dist,
+int launch_triangulate(const float* det, const float* cam, const float* intr, const float* dist, int calib_fs,
                        float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C,
                        float sx2, float sy2, float wdiv, int hw, int W, int H, hipStream_t s) {
   JH_REQUIRE(C <= 64, "at most 64 cameras");
-  hipLaunchKernelGGL(triangulate_kernel, dim3(T), dim3(64), 0, s, det, cam, intr, dist, center3d_f,
+  JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
+  hipLaunchKernelGGL(triangulate_kernel, dim3(T), dim3(64), 0, s, det, cam, intr, dist, calib_fs, center3d_f,
                      center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H);
   JH_CHECK_HIP(hipGetLastError());
   return 0;
@@ -599,7 +605,7 @@ __global__ void views2d_final_kernel(const float* __restrict__ pmax, const int* 
                                      const int* __restrict__ center_hm, const int* __restrict__ valid,
                                      const unsigned char* __restrict__ mask, const float* __restrict__ pts3d,
                                      const float* __restrict__ cam, const float* __restrict__ intr,
-                                     const float* __restrict__ dist, int* __restrict__ points2d,
+                                     const float* __restrict__ dist, int fs, int* __restrict__ points2d,
                                      float* __restrict__ conf2d, float* __restrict__ reproj, float* __restrict__ err,
                                      unsigned char* __restrict__ used, int C, int J, int Jp, int slices, int Hh,
                                      int Wh, int hw) {
@@ -613,7 +619,8 @@ __global__ void views2d_final_kernel(const float* __restrict__ pmax, const int* 
   float u = nan, v = nan;
   if (ok) {
     const float* p = pts3d + ((size_t)t * J + j) * 3;
-    project_one(cam + c * 12, intr + c * 9, dist + c * 5, p[0], p[1], p[2], &u, &v);
+    const size_t row = (size_t)t * fs + c;      // (fs: the calibration's frame stride, see triangulate_body)
+    project_one(cam + row * 12, intr + row * 9, dist + row * 5, p[0], p[1], p[2], &u, &v);
   }
   reproj[o * 2 + 0] = u;
   reproj[o * 2 + 1] = v;
@@ -686,13 +693,14 @@ int launch_joint_argmax_all_combine(const float* pmax, const int* pidx, int* idx
 
 int launch_views2d_final(const float* pmax, const int* pidx, const int* center_hm, const int* valid,
                          const unsigned char* mask, const float* pts3d, const float* cam, const float* intr,
-                         const float* dist, int* points2d, float* conf2d, float* reproj, float* err,
+                         const float* dist, int calib_fs, int* points2d, float* conf2d, float* reproj, float* err,
                          unsigned char* used, int T, int C, int J, int Jp, int Hh, int Wh, int hw, hipStream_t s) {
   if (check_scan_shape(T * C, Hh, Wh, J, Jp)) return 1;
+  JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
   const ScanShape sh = joint_argmax_all_shape(T * C, Hh, Wh, Jp);
   hipLaunchKernelGGL(views2d_final_kernel, dim3(T * C), dim3(round_up(J, kWave)), 0, s, pmax, pidx, center_hm,
-                     valid, mask, pts3d, cam, intr, dist, points2d, conf2d, reproj, err, used, C, J, Jp, sh.slices,
-                     Hh, Wh, hw);
+                     valid, mask, pts3d, cam, intr, dist, calib_fs, points2d, conf2d, reproj, err, used, C, J, Jp,
+                     sh.slices, Hh, Wh, hw);
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -15,7 +15,10 @@
 namespace jh {
 
 // kernels implemented in other translation units
-int launch_reproject(const float* cam, const float* intr, const float* dist, const int* center3d,
+// calib_fs: the frame stride of the calibration in cameras.  Frame t of a launch reads cam + (t * calib_fs + c) * 12,
+// intr + (t * calib_fs + c) * 9, dist + (t * calib_fs + c) * 5: 0 = one calibration (C rows) shared by all frames,
+// C = one per frame (T * C rows, jh_predictor_set_calibration_frames).  Nothing else differs between the two forms.
+int launch_reproject(const float* cam, const float* intr, const float* dist, int calib_fs, const int* center3d,
                      const int* center_hm, const float* heat, float2* coarse, float* vol,
                      int* idx_out, int T, int C, int G, float spacing, int hs, int Jp,
                      int heat_pad, int div255, hipStream_t s, const HeatLayout* layout = nullptr);
@@ -35,7 +38,7 @@ int launch_center2d(const float* det, int* center_hm, int* valid, int T, float s
                     int W, int H, hipStream_t s);
 int launch_joint_argmax(const float* heat, const int* center_hm, int* points, float* conf, int T,
                         int J, int Jp, int Hh, int Wh, int hw, hipStream_t s);
-int launch_triangulate(const float* det, const float* cam, const float* intr, const float* dist,
+int launch_triangulate(const float* det, const float* cam, const float* intr, const float* dist, int calib_fs,
                        float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C,
                        float sx2, float sy2, float wdiv, int hw, int W, int H, hipStream_t s);
 int launch_project_points(const float* pts, const float* cam, const float* intr, const float* dist,

@@ -38,6 +38,7 @@ struct ReproCalib {
   const float* cam;    // [C][4][3]
   const float* intr;   // [C][3][3]  (principal point in row 2)
   const float* dist;   // [C][5]
+  int fs;              // frame stride in cameras: frame t reads row t * fs + c (0: shared by all frames, C: per frame)
 };
 
 __global__ __launch_bounds__(256) void repro_coarse_kernel(
@@ -53,7 +54,8 @@ __global__ __launch_bounds__(256) void repro_coarse_kernel(
   const float gx = __fadd_rn(__fmul_rn(__fmul_rn((float)(i - half), spacing), 2.f), (float)center3d[t * 3 + 0]);
   const float gy = __fadd_rn(__fmul_rn(__fmul_rn((float)(j - half), spacing), 2.f), (float)center3d[t * 3 + 1]);
   const float gz = __fadd_rn(__fmul_rn(__fmul_rn((float)(k - half), spacing), 2.f), (float)center3d[t * 3 + 2]);
-  const float* M = cal.cam + c * 12;
+  const size_t row = (size_t)t * cal.fs + c;
+  const float* M = cal.cam + row * 12;
   float p[3];
 #pragma unroll
   for (int col = 0; col < 3; ++col) {
@@ -63,9 +65,9 @@ __global__ __launch_bounds__(256) void repro_coarse_kernel(
     a = __fmaf_rn(1.f, M[3 * 3 + col], a);
     p[col] = a;
   }
-  const float* K = cal.intr + c * 9;
+  const float* K = cal.intr + row * 9;
   const float cx = K[6], cy = K[7], fx = K[0], fy = K[4];
-  const float k1 = cal.dist[c * 5 + 0], k2 = cal.dist[c * 5 + 1];
+  const float k1 = cal.dist[row * 5 + 0], k2 = cal.dist[row * 5 + 1];
   float u = __fsub_rn(__fdiv_rn(p[0], p[2]), cx);
   float v = __fsub_rn(__fdiv_rn(p[1], p[2]), cy);
   const float a1 = __fdiv_rn(u, fx), a2 = __fdiv_rn(v, fy);
@@ -832,7 +834,7 @@ static int launch_cube(const CubeArgs& a, int T, hipStream_t s, const unsigned c
               : launch_cube_kernel(repro_cube_kernel<Q, CI, NT>, big, grid, NT, lds, s, a);
 }
 
-static int reproject_impl(const float* cam, const float* intr, const float* dist, const int* center3d,
+static int reproject_impl(const float* cam, const float* intr, const float* dist, int calib_fs, const int* center3d,
                           const int* center_hm, const float* heat, float2* coarse, float* vol,
                           int* idx_out, int T, int C, int G, float spacing, int hs, int Jp,
                           int heat_pad, int div255, hipStream_t s, const HeatLayout* layout,
@@ -847,7 +849,8 @@ static int reproject_impl(const float* cam, const float* intr, const float* dist
   JH_REQUIRE(lay.cams_per_block >= 1 && C % lay.cams_per_block == 0, "cameras per heatmap block");
   JH_REQUIRE(G % 2 == 0 && Jp % 8 == 0 && Jp <= 64, "reprojection shape");
   JH_REQUIRE((size_t)hs * hs * Jp * 4 < ((size_t)1 << 31), "one camera's heatmap exceeds 2 GB");
-  ReproCalib cal{cam, intr, dist};
+  JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
+  ReproCalib cal{cam, intr, dist, calib_fs};
   const int nvc = Gh * Gh * Gh;
   hipLaunchKernelGGL(repro_coarse_kernel, dim3((nvc + 255) / 256, C, T), dim3(256), 0, s, cal,
                      center3d, center_hm, coarse, C, Gh, spacing, hs);
@@ -897,22 +900,22 @@ static int reproject_impl(const float* cam, const float* intr, const float* dist
   return 0;
 }
 
-int launch_reproject(const float* cam, const float* intr, const float* dist, const int* center3d,
+int launch_reproject(const float* cam, const float* intr, const float* dist, int calib_fs, const int* center3d,
                      const int* center_hm, const float* heat, float2* coarse, float* vol,
                      int* idx_out, int T, int C, int G, float spacing, int hs, int Jp,
                      int heat_pad, int div255, hipStream_t s, const HeatLayout* layout) {
-  return reproject_impl(cam, intr, dist, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs, Jp,
-                        heat_pad, div255, s, layout, nullptr);
+  return reproject_impl(cam, intr, dist, calib_fs, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs,
+                        Jp, heat_pad, div255, s, layout, nullptr);
 }
 
-int launch_reproject_masked(const float* cam, const float* intr, const float* dist, const int* center3d,
+int launch_reproject_masked(const float* cam, const float* intr, const float* dist, int calib_fs, const int* center3d,
                             const int* center_hm, const float* heat, float2* coarse, float* vol, int* idx_out,
                             int T, int C, int G, float spacing, int hs, int Jp, int heat_pad, int div255,
                             const unsigned char* mask, hipStream_t s, const HeatLayout* layout) {
   JH_REQUIRE(mask, "camera mask");
   JH_REQUIRE(C <= 64, "at most 64 cameras");
-  return reproject_impl(cam, intr, dist, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs, Jp,
-                        heat_pad, div255, s, layout, mask);
+  return reproject_impl(cam, intr, dist, calib_fs, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs,
+                        Jp, heat_pad, div255, s, layout, mask);
 }
 
 }  // namespace jh

@@ -154,10 +154,14 @@ class JarvisPredictor3D(nn.Module):
         """The forward of checked frames (a _native.Frames; single: one frame set, lead (C,)) with a checked mask, on
         the native predictor of their size: nothing of the predictor is touched before this."""
         check_native_seam(self)
+        per_frame = False
         if single:
             frames = frames._replace(lead=(1,) + frames.lead, data=frames.data.unsqueeze(0))
+        else:
+            # the batched forms take one calibration for the batch, (C,...), or one per frame set, (T,C,...)
+            per_frame = N.calibration(tuple(calib), frames.lead[0], self.num_cameras)[0] == "frames"
         pr = self.native(frames.height, frames.width, time_batch=frames.lead[0])
-        pr.set_calibration(*calib)
+        (pr.set_calibration_frames if per_frame else pr.set_calibration)(*calib)
         res = pr._forward(frames, None, mask)
         return self._single(pr, res, mask, return_2d) if single else self._batch(pr, res, mask, return_2d)
 
@@ -221,7 +225,14 @@ class JarvisPredictor3D(nn.Module):
         return_2d: the per-camera `Views2D` of the batch (leading dimension T; see forward()) follows `valid`:
         (points, confidences, valid, views).  Rows of invalid frames: used 0, points2D -1, NaN reprojections.
         frame_layout: a YuvSurface or a SensorSurface -- imgs (T,C,image_stride) uint8, see forward_surface; not
-        together with frame_format 'i420' / 'nv12'."""
+        together with frame_format 'i420' / 'nv12'.
+        Calibration: cameraMatrices (C,4,3), intrinsicMatrices (C,3,3), distortionCoefficients (C,1,5) -- one
+        calibration shared by the T frame sets --, or the same three with a leading T -- (T,C,4,3) / (T,C,3,3) /
+        (T,C,1,5), row t the calibration of frame set t, as the reference's validation analysis gives every sample the
+        calibration of its own dataset (analysis/analyze.py).  All three in one form (ValueError otherwise).  Row t of
+        the result under per-frame calibration equals, bit for bit, row t of the same batch run with row t's
+        calibration shared; camera_mask and return_2d compose with either form (the reprojections of row t use row
+        t's calibration).  The single-frame forms (forward, forward_uint8, forward_yuv, forward_surface) take (C,...)."""
         if camera_mask is not None:
             if not torch.is_tensor(imgs) or imgs.dim() < 1:
                 raise ValueError("imgs must be a tensor of time steps")
@@ -239,7 +250,8 @@ class JarvisPredictor3D(nn.Module):
         entry is still an image.  Nothing is gathered: the kernels read every image through its own pointer
         (jh_predictor_forward_images).
         -> what forward_batch returns for the (T,C,...) stack of the same images, bit for bit; no host
-        synchronisation.  camera_mask (T,C), return_2d: as forward_batch."""
+        synchronisation.  camera_mask (T,C), return_2d: as forward_batch.  Calibration: shared (C,...) or one per frame
+        set (T,C,...), as forward_batch."""
         if isinstance(images, (list, tuple)) and len(images) > 0 and torch.is_tensor(images[0]):
             images = [images]
         if not isinstance(images, (list, tuple)) or len(images) == 0:
