@@ -190,6 +190,45 @@ int jh_predictor_set_calibration_frames(jh_predictor* pr, const float* cam_dev /
                                         const float* intr_dev /* (T,C,3,3) */, const float* dist_dev /* (T,C,1,5) */,
                                         void* stream);
 
+/* Caller-supplied 3D centres (ABI v4, additive; new design: the reference always detects, jarvis3D.py:135-166).  Stage 1
+ * only decides where the crops and the voxel cube go; a caller that knows where the subject is -- the centroid of the
+ * previous result when tracking, a fixed volume, an external detector, several subjects seen in the same frames (one
+ * centre per row of a jh_predictor_forward_images batch whose rows share their image pointers) -- gives the centres
+ * and stage 1 does not run: no resize, no CenterDetect, no centre arg-max, no triangulation.
+ *   centers (T,3) fp32 dev, T = time_batch: row t is the centre of frame set t in world millimetres; NULL returns the
+ *   predictor to detection.  The two may alternate freely, call by call.
+ * Lifetime: the rows are COPIED, on `stream`, into a buffer the predictor owns (T * 12 bytes).  The first such call of
+ * a predictor allocates it -- never jh_predictor_create, so jh_predictor_device_bytes and the memory of a predictor that
+ * never uses it are unchanged -- and that first call must not be made inside a stream capture.
+ * After it every whole-path forward of this predictor (jh_predictor_forward, _u8, _yuv, _surface, _sensor, _masked,
+ * _images) skips stage 1 and runs stage 2 from the centres, and every jh_predictor_stage_keypoints* call (_u8, _masked,
+ * _gathered) ignores its det argument, which may then be NULL; jh_predictor_stage_center* is not affected.  A
+ * predictor created with center_params == NULL runs centred whole-path forwards (without graph replay, which such a
+ * predictor does not have); its detected ones keep failing with "created without CenterDetect weights".
+ * For every frame set t:
+ *   center3d float = centers[t];  center3d int = (int)centers[t], truncation toward zero (center3D.int(),
+ *   jarvis3D.py:183);  center_hm[t][c] = clamp((int)reprojectPoint(centers[t])[c]) under the calibration in force
+ *   (shared or per frame set) -- the very operations that follow the triangulation of a detected call;
+ *   valid[t] = 1 iff the three coordinates are finite and |x| < 2^24 (no detection ran: there is no `> 50` gate) and,
+ *   under a camera mask, at least one camera of row t is unmasked.  jh_predictor_debug_mask then reports n_active as for
+ *   a detected masked call and num_cams_detect = 0.
+ *   An invalid row is computed as if its centre were (0,0,0): nothing that is not finite or not in range is converted
+ *   to an integer, a projection that is not finite or not representable takes the clamp's lower bound, and the row's
+ *   crops are in range.  Its points / confidences are unspecified, as for the invalid rows of a detected call.
+ * Everything downstream is the code of a detected call on those buffers: crop stem or crop kernel, KeypointDetect,
+ * reprojection gather (plain or masked), V2V, soft-argmax, jh_predictor_views2d.
+ * Graph replay: the centred forward has graph slots of its own, as the masked and the per-image forms have, so
+ * alternating centred and detected calls records each once; the centres' VALUES live in the predictor's buffer and may
+ * change from call to call under one recording.
+ * Results: a centred call whose centres are the float centres of a detected call (jh_predictor_debug's center3d of the
+ * same frames, calibration and mask) equals that call BIT FOR BIT in points, confidences, valid, the integer centre,
+ * the crop centres and the five outputs of jh_predictor_views2d, wherever the detected call is valid.  A predictor that
+ * is never given centres makes the launches it always made.
+ * jh_predictor_debug after a centred call reports the supplied center3d and the integers and crop centres derived
+ * from it; det is left as the last detected call wrote it.
+ * Validation: pr non-NULL; otherwise non-zero with jh_last_error() set, nothing enqueued. */
+int jh_predictor_set_centers(jh_predictor* pr, const float* centers_dev /* (T,3) or NULL */, void* stream);
+
 /* Stage 1 (jarvis3D.py:135-155): resize + normalise + CenterDetect + argmax for
  * the owned cameras.  frames (T,cam_n,3,H,W) dev -> det (T,cam_n,3) = (x, y,
  * raw maxval) dev. */
@@ -358,7 +397,9 @@ int jh_predictor_forward_sensor(jh_predictor* pr, const uint8_t* frames_dev, con
                                 void* stream);
 
 /* Integer path of the last call, for parity tests: center3d float (T,3),
- * center3d int (T,3), center_hm (T,C,2), det (T,C,3).  Any pointer may be NULL. */
+ * center3d int (T,3), center_hm (T,C,2), det (T,C,3).  Any pointer may be NULL.
+ * After a call from caller-supplied centres (jh_predictor_set_centers): center3d is the supplied centre, the integers
+ * and crop centres are derived from it, and det is what the last DETECTED call wrote. */
 int jh_predictor_debug(jh_predictor* pr, float* center3d_f_dev, int32_t* center3d_i_dev,
                        int32_t* center_hm_dev, float* det_dev, void* stream);
 

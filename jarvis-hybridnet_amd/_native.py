@@ -110,6 +110,7 @@ _SIGS = {
     "jh_predictor_precision": (c_int, [c_void_p]),
     "jh_predictor_set_calibration": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_set_calibration_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_predictor_set_centers": (c_int, [c_void_p, c_void_p, c_void_p]),
     "jh_predictor_stage_center": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_stage_keypoints": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_stage_3d": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
@@ -461,6 +462,30 @@ def calibration(calib, T, C):
         raise ValueError("the three calibration tensors are either all per camera (C, ...) or all per frame set "
                          "(T, C, ...); got %s" % ", ".join("%s: %s" % nf for nf in zip(names, forms)))
     return (forms[0],) + tuple(calib)
+
+
+def centers(value, T):
+    """A centers argument checked and made a contiguous fp32 tensor of shape (T,3), world millimetres, one row per
+    frame set (jh_predictor_set_centers): None stays None; a tensor, numpy array or sequence of shape (T,3) -- (3,) too
+    when T == 1 -- of any real numeric dtype.  The device is left alone (a device tensor computed from the previous
+    result costs no host synchronisation); values are not looked at -- a row that is not finite is an invalid row of
+    the result, not an error.  Anything else raises ValueError."""
+    if value is None:
+        return None
+    want = "(%d, 3)" % T + (" or (3,)" if T == 1 else "")
+    if not torch.is_tensor(value):
+        try:
+            value = torch.as_tensor(value)
+        except Exception as e:                              # noqa: BLE001 -- ragged / non-numeric sequences
+            raise ValueError("centers must be a real numeric tensor, array or sequence of shape %s: %s" % (want, e))
+    if value.dtype == torch.bool or value.dtype.is_complex:
+        raise ValueError("centers must have a real numeric dtype; got %s" % value.dtype)
+    shape = tuple(int(n) for n in value.shape)
+    if shape == (3,) and T == 1:
+        value = value.unsqueeze(0)
+    elif shape != (T, 3):
+        raise ValueError("centers must have shape %s (world millimetres, one row per frame set); got %s" % (want, shape))
+    return value.to(torch.float32).contiguous()
 
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x3_wide": 2}

@@ -43,6 +43,7 @@ class NativePredictor:
         self.precision = {v: k for k, v in N.PRECISIONS.items()}[N.lib().jh_predictor_precision(self.handle)]
         self.launches = N.lib().jh_predictor_launches(self.handle)
         self.device_bytes = N.lib().jh_predictor_device_bytes(self.handle)
+        self._centred = False                        # centres are in force (set_centers)
 
     def close(self):
         if getattr(self, "handle", None) and N is not None and N._lib is not None:
@@ -77,8 +78,28 @@ class NativePredictor:
         N.check(N.lib().jh_predictor_set_calibration_frames(
             self.handle, N.ptr(N.dev(cam)), N.ptr(N.dev(intr)), N.ptr(N.dev(dist)), N.stream()))
 
+    # ---- caller-supplied centres ------------------------------------------
+    def set_centers(self, centers):
+        """centers (T,3), world millimetres, host or device (_native.centers; (3,) too at time_batch 1): from now on
+        every forward of this predictor skips stage 1 -- resize, CenterDetect, arg-max, triangulation -- and puts the
+        crops and the voxel cube of frame set t where row t says (jh_predictor_set_centers; copied on the current
+        stream).  None: back to detection; a predictor that holds no centres is not called at all.
+        valid[t] = 1 iff row t is finite and below 2^24 in magnitude (and, under a camera mask, a camera of the row is
+        unmasked); there is no detection gate.  Centres taken from debug()["center3d"] of a detected call reproduce
+        that call bit for bit."""
+        centers = N.centers(centers, self.T)
+        if centers is None:
+            if self._centred:
+                N.check(N.lib().jh_predictor_set_centers(self.handle, None, N.stream()))
+                self._centred = False
+            return
+        dev = centers.to("cuda", non_blocking=True)
+        N.check(N.lib().jh_predictor_set_centers(self.handle, N.ptr(dev), N.stream()))
+        dev.record_stream(torch.cuda.current_stream())          # (copied by the call: free once it is enqueued)
+        self._centred = True
+
     # ---- single-GPU forward ----------------------------------------------
-    def forward(self, frames, out=None, frame_format=None, camera_mask=None, frame_layout=None):
+    def forward(self, frames, out=None, frame_format=None, camera_mask=None, frame_layout=None, centers=None):
         """frames (T,C,3,H,W) fp32 RGB, or (T,C,H,W,3) uint8 BGR as decoded, or with frame_format 'i420' / 'nv12'
         (T,C,3H/2,W) uint8 YUV 4:2:0 -> points (T,J,3), conf (T,J), valid (T) int32.  frame_format None: the
         dtype decides between fp32 RGB and uint8 BGR; 'bgr' requires uint8 BGR.
@@ -86,17 +107,19 @@ class NativePredictor:
         (jh_predictor_forward_masked); None: all cameras, the unmasked entry points.
         frame_layout: a YuvSurface -- frames (T,C,image_stride) uint8, each image a YUV 4:2:0 surface read through
         that description (jh_predictor_forward_surface) --, or a SensorSurface -- each image a raw Mono8 / Bayer
-        sensor image (jh_predictor_forward_sensor); not together with frame_format 'i420' / 'nv12'."""
+        sensor image (jh_predictor_forward_sensor); not together with frame_format 'i420' / 'nv12'.
+        centers (T,3): this call runs from these centres (set_centers); None: it detects -- centres set earlier are
+        cleared first."""
         return self._forward(self._describe(frames, frame_format, frame_layout), out,
-                             N.camera_mask(camera_mask, (self.T, self.C)))
+                             N.camera_mask(camera_mask, (self.T, self.C)), N.centers(centers, self.T))
 
-    def forward_images(self, frames, out=None, camera_mask=None):
+    def forward_images(self, frames, out=None, camera_mask=None, centers=None):
         """forward() on T * C separately placed images: `frames` what _native.frame_images made of the flat list
         (index t * C + c) (jh_predictor_forward_images).  The images are read where they lie; nothing is gathered."""
         if len(frames.images) != self.T * self.C:
             raise ValueError("expected %d images (time_batch * num_cameras), got %d" % (self.T * self.C,
                                                                                          len(frames.images)))
-        return self._forward(frames, out, N.camera_mask(camera_mask, (self.T, self.C)))
+        return self._forward(frames, out, N.camera_mask(camera_mask, (self.T, self.C)), N.centers(centers, self.T))
 
     def _describe(self, frames, frame_format=None, frame_layout=None):
         """Raw pointers cross the C ABI: refuse anything whose bytes would be misread (_native.describe_frames for
@@ -104,9 +127,12 @@ class NativePredictor:
         return N.describe_frames(frames, (self.T, self.Cloc), frame_format, frame_layout,
                                  (self.cfg.img_h, self.cfg.img_w), error=RuntimeError, in_place=True)
 
-    def _forward(self, frames, out, mask):
-        """The forward of checked frames (a _native.Frames) with a checked mask (_native.camera_mask) or None."""
+    def _forward(self, frames, out, mask, centers=None):
+        """The forward of checked frames (a _native.Frames) with a checked mask (_native.camera_mask) or None, and
+        checked centres (_native.centers) or None = detect."""
         dev = frames.device
+        if centers is not None or self._centred:
+            self.set_centers(centers)
         if out is None:
             out = (torch.empty((self.T, self.J, 3), device=dev),
                    torch.empty((self.T, self.J), device=dev),
@@ -127,7 +153,9 @@ class NativePredictor:
 
     def stage_keypoints(self, frames, det_all, heat, camera_mask=None):
         """camera_mask: a (T,C) uint8 DEVICE tensor (kept alive by the caller until the stream has passed the call;
-        all cameras local) for the masked triangulation; give stage_3d the same one."""
+        all cameras local) for the masked triangulation; give stage_3d the same one.
+        det_all may be None while centres are set (set_centers): stage 2 then takes them and reads no detection."""
+        self._need_det(det_all)
         frames = self._describe(frames).data
         if camera_mask is not None:
             mask = self._device_mask(camera_mask)
@@ -138,6 +166,10 @@ class NativePredictor:
         fn = N.lib().jh_predictor_stage_keypoints_u8 if frames.dtype == torch.uint8 else \
             N.lib().jh_predictor_stage_keypoints
         N.check(fn(self.handle, N.ptr(frames), N.ptr(det_all), N.ptr(heat), N.stream()))
+
+    def _need_det(self, det):
+        if det is None and not self._centred:
+            raise ValueError("stage 2 needs the detections of stage 1 (det_all) unless centres are set (set_centers)")
 
     def _device_mask(self, camera_mask):
         if not (torch.is_tensor(camera_mask) and camera_mask.is_cuda and camera_mask.dtype == torch.uint8
@@ -156,7 +188,9 @@ class NativePredictor:
                                               N.ptr(conf), N.ptr(valid), N.stream()))
 
     def stage_keypoints_gathered(self, frames, det_gathered, n_blocks, heat):
-        """Stage 2 reading the all-gathered detections (n_blocks, T, C/n_blocks, 3) in place."""
+        """Stage 2 reading the all-gathered detections (n_blocks, T, C/n_blocks, 3) in place (None while centres are
+        set, as stage_keypoints)."""
+        self._need_det(det_gathered)
         frames = self._describe(frames).data
         N.check(N.lib().jh_predictor_stage_keypoints_gathered(
             self.handle, N.ptr(frames), int(frames.dtype == torch.uint8), N.ptr(det_gathered), n_blocks,
@@ -303,15 +337,18 @@ class MultiStreamPredictor:
         self._calib_of[i] = (self._calib, self._calib_refs)       # the tensors live as long as their key is compared
 
     def forward(self, frames, out=None, then=None, frame_format=None, camera_mask=None, return_2d=False,
-                frame_layout=None):
+                frame_layout=None, centers=None):
         """return_2d: the five tensors of NativePredictor.views2d for this batch are appended to the outputs
         (points, conf, valid, points2D, confidences2D, reprojections, errors, used).
         `then(outputs)`, when given, runs inside the batch's stream context right behind the forward and
         before its event is recorded (the drivers enqueue the device->host copy of the results there); its
-        return value replaces the outputs.  frame_format, camera_mask, frame_layout: as NativePredictor.forward."""
+        return value replaces the outputs.  frame_format, camera_mask, frame_layout: as NativePredictor.forward.
+        centers (T,3): the centres of THIS batch (NativePredictor.set_centers), written on the stream of the predictor
+        the batch runs on; None: the batch detects."""
         p0 = self.preds[0]
         described = p0._describe(frames, frame_format, frame_layout)               # before any stream work
         camera_mask = N.camera_mask(camera_mask, (p0.T, p0.C))
+        centers = N.centers(centers, p0.T)
         i = self._next
         self._next = (i + 1) % len(self.preds)
         s = self.streams[i]
@@ -325,7 +362,7 @@ class MultiStreamPredictor:
             t.record_stream(s)
         with torch.cuda.stream(s):
             self._frames_calibration(i)
-            res = self.preds[i]._forward(described, out, camera_mask)
+            res = self.preds[i]._forward(described, out, camera_mask, centers)
             if return_2d:
                 res = tuple(res) + tuple(self.preds[i].views2d(res[0], camera_mask=camera_mask))
             if then is not None:

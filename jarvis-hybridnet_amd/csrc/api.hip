@@ -480,13 +480,15 @@ struct jh_predictor {
   hipStream_t gstream = nullptr;             // capture stream (the caller's may be the null stream)
   // One slot per frame format (kSrc*, preprocess.h); [kGraphFmts + fmt]: the masked form of that format;
   // [2 * kGraphFmts + ...]: the same again for the per-image form, which has slots of its OWN -- a stream of
-  // per-image calls and a stream of contiguous calls of one format never re-record each other.  A launch
+  // per-image calls and a stream of contiguous calls of one format never re-record each other; [4 * kGraphFmts + ...]:
+  // all of these again for the forward from caller-supplied centres (centers_on), which records no stage 1 -- a
+  // tracking loop that falls back to one detected call between centred ones never re-records.  A launch
   // carries its source's description by value, so a recording has ONE source: the slot keeps the FrameSource its
   // graph was captured with, and a call with another one records again (forward_graph).  The same holds for the
   // calibration's form: a recording holds the pointers and the frame stride (calib_fs) it was captured with.
   static constexpr int kGraphFmts = kSrcSensor + 1;
   struct GraphSlot { hipGraphExec_t exec = nullptr; FrameSource src; int calib_fs = 0; };
-  GraphSlot gslot[4 * kGraphFmts];
+  GraphSlot gslot[8 * kGraphFmts];
   // Camera mask (camera_mask.h).  mask_buf [T][C]: the predictor's copy of the current call's mask -- the masked
   // kernels (and a captured graph of them) read this buffer, so the mask may change from call to call.  mask_cur:
   // the mask of the call under way, nullptr = no mask (the plain kernels).  n_active / n_detect [T]: written by
@@ -494,6 +496,12 @@ struct jh_predictor {
   unsigned char* mask_buf = nullptr;
   const unsigned char* mask_cur = nullptr;
   int *n_active = nullptr, *n_detect = nullptr;
+  // Caller-supplied centres (jh_predictor_set_centers).  centers_buf [T][3]: the predictor's copy of the centres in
+  // force, allocated by the first such call -- the centred stage 2 (and a captured graph of it) reads this buffer, so
+  // the centres may change from call to call.  centers_on: stage 1 is skipped and stage 2 takes its centres from the
+  // buffer (launch_centers) instead of triangulating detections.
+  float* centers_buf = nullptr;
+  bool centers_on = false;
   // (max, index) partials of the all-joint argmax behind jh_predictor_views2d, [T3 * C][slices][Jp] each: allocated
   // by the first such call, so a predictor that never asks for 2D views owns what it always did
   float* v2d_max = nullptr;
@@ -676,6 +684,26 @@ int jh_predictor_set_calibration_frames(jh_predictor* pr, const float* cam_dev, 
   return 0;
 }
 
+int jh_predictor_set_centers(jh_predictor* pr, const float* centers_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(pr, "jh_predictor_set_centers: null predictor");
+  if (!centers_dev) {                         // (back to detection; the buffer stays for the next centred call)
+    pr->centers_on = false;
+    return 0;
+  }
+  if (!pr->centers_buf) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s, &cs);
+    JH_REQUIRE(cs == hipStreamCaptureStatusNone, "the first jh_predictor_set_centers call of a predictor allocates its "
+               "centre buffer: make it outside a stream capture");
+    if (pr->mem.get(reinterpret_cast<void**>(&pr->centers_buf), (size_t)pr->T * 3 * sizeof(float))) return 1;
+  }
+  JH_CHECK_HIP(hipMemcpyAsync(pr->centers_buf, centers_dev, (size_t)pr->T * 3 * sizeof(float), hipMemcpyDeviceToDevice,
+                              s));
+  pr->centers_on = true;
+  return 0;
+}
+
 static int stage_center_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* det_dev,
                              void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -717,6 +745,10 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, const 
   hipStream_t s = static_cast<hipStream_t>(stream);
   const auto& c = pr->cfg;
   if (next_centre_set) pr->slot ^= 1;        // (the staged API: the previous batch's stage 3 may still read the other set)
+  if (pr->centers_on) {                      // (no detections are read, none are kept: `det` may be NULL)
+    det_blocks = 1;
+    det_all_dev = pr->det_all;
+  }
   if (det_blocks > 1) {
     JH_REQUIRE(pr->C % det_blocks == 0, "cameras must divide evenly over the detection blocks");
     const int n = pr->T * pr->C * 3;
@@ -728,7 +760,13 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, const 
   // preds * (downsampling_scale * 2), jarvis3D.py:138-141,158-160
   const float sx2 = (float)((double)c.img_w / (double)c.center_size) * 2.f;
   const float sy2 = (float)((double)c.img_h / (double)c.center_size) * 2.f;
-  if (pr->mask_cur) {
+  if (pr->centers_on) {
+    // the centres of jh_predictor_set_centers in place of a triangulation; masked or not by the mask pointer
+    JH_PROF("centers", 0.0, 0.0,
+            launch_centers(pr->centers_buf, pr->cam_at(0), pr->intr_at(0), pr->dist_at(0), pr->calib_fs, pr->c3f,
+                           pr->c3i_cur(), pr->chm_cur(), pr->valid_cur(), pr->T, pr->C, pr->B / 2, c.img_w, c.img_h,
+                           pr->mask_cur, pr->n_active, pr->n_detect, s));
+  } else if (pr->mask_cur) {
     JH_PROF("triangulate_masked", 0.0, 0.0,
             launch_triangulate_masked(det_all_dev, pr->cam_at(0), pr->intr_at(0), pr->dist_at(0), pr->calib_fs, pr->c3f,
                                       pr->c3i_cur(), pr->chm_cur(), pr->valid_cur(), pr->T, pr->C, sx2, sy2, 255.f,
@@ -813,7 +851,8 @@ int jh_predictor_stage_3d_blocks(jh_predictor* pr, const float* heat_blocks_dev,
 
 static int forward_eager(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
                          float* conf_dev, int32_t* valid_dev, void* stream) {
-  if (stage_center_impl(pr, frames_dev, fs, pr->det_all, stream)) return 1;
+  // (centres supplied by the caller: stage 1 does not run at all)
+  if (!pr->centers_on && stage_center_impl(pr, frames_dev, fs, pr->det_all, stream)) return 1;
   if (stage_keypoints_impl(pr, frames_dev, fs, pr->det_all, nullptr, stream)) return 1;
   return jh_predictor_stage_3d(pr, pr->kp->heat.p, 0, points_dev, conf_dev, valid_dev, stream);
 }
@@ -827,7 +866,8 @@ static int forward_eager(jh_predictor* pr, const void* frames_dev, const FrameSo
 static int forward_graph(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
                          float* conf_dev, int32_t* valid_dev, hipStream_t s) {
   jh_predictor::GraphSlot& slot = pr->gslot[fs.fmt + (pr->mask_cur ? jh_predictor::kGraphFmts : 0) +
-                                            (fs.per_image ? 2 * jh_predictor::kGraphFmts : 0)];
+                                            (fs.per_image ? 2 * jh_predictor::kGraphFmts : 0) +
+                                            (pr->centers_on ? 4 * jh_predictor::kGraphFmts : 0)];
   // the recorded launches hold the description they were captured with: another one records again (rare: a stream
   // keeps its layout, and a fixed format has nothing to differ in; the replay in flight is waited for before its
   // executable graph goes).  Likewise the calibration's form, shared or per frame: its pointers and frame stride are

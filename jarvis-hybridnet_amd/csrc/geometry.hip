@@ -9,6 +9,7 @@
 //  triangulate         ReprojectionTool.reconstructPoint + reprojectPoint +
 //                      integer clamp, jarvis/utils/reprojection.py:49-90,
 //                      jarvis3D.py:157-166
+//  centers             the same integer path from a centre the caller supplies (no detection, no triangulation)
 //  softargmax          softplus + spatial soft-argmax + confidences,
 //                      jarvis/hybridnet/model.py:73-88
 //  joint_argmax_all    argmax of every joint's heat map in one pass + the per-camera 2D views of the 3D
@@ -337,6 +338,33 @@ __device__ __forceinline__ void project_one(const float* M, const float* K, cons
   *v = __fadd_rn(__fmul_rn(vv, dd), cy);
 }
 
+// Crop centre of one camera from the 3D centre (x, y, z): reprojectPoint, .int() and the clamps of
+// jarvis3D.py:161-166.  THE tail of the triangulation and of the caller-supplied centres (centers_kernel): one
+// function, so that a centre handed back to the library gives the crop centres its detection gave.  row: the camera's
+// calibration row (frame stride included); out: its two ints of center_hm.
+// GUARD (centers_kernel: the centre is the caller's, the projection may be anything): a projection that is not finite or
+// not below 2^31 in magnitude is not converted -- it takes the clamp's lower bound.  Without it the conversion is the
+// one the triangulation always made.
+template <bool GUARD>
+__device__ __forceinline__ void crop_centre(const float* __restrict__ cam, const float* __restrict__ intr,
+                                            const float* __restrict__ dist, size_t row, float x, float y, float z,
+                                            int hw, int W, int H, int* __restrict__ out) {
+  float u, v;
+  project_one(cam + row * 12, intr + row * 9, dist + row * 5, x, y, z, &u, &v);
+  int iu, iv;
+  if constexpr (GUARD) {
+    iu = fabsf(u) < 2147483648.f ? (int)u : hw;  // (NaN and inf compare false)
+    iv = fabsf(v) < 2147483648.f ? (int)v : hw;
+  } else {
+    iu = (int)u;
+    iv = (int)v;
+  }
+  iu = min(max(iu, hw), W - hw);               // jarvis3D.py:163-166
+  iv = min(max(iv, hw), H - hw);
+  out[0] = iu;
+  out[1] = iv;
+}
+
 // One 64-thread block per frame t.  det: [T][C][3] (x, y, raw maxval).
 // Outputs: center3d_f [T][3] float, center3d_i [T][3] int (truncated),
 // center_hm [T][C][2] int (truncated + clamped crop centres), valid [T].
@@ -422,15 +450,7 @@ __device__ __forceinline__ void triangulate_body(
     if constexpr (MASK) { n_active[t] = act; n_detect[t] = cnt; }
   }
   __syncthreads();
-  if (c < C) {
-    float u, v;
-    project_one(cam + row * 12, intr + row * 9, dist + row * 5, ctr[0], ctr[1], ctr[2], &u, &v);
-    int iu = (int)u, iv = (int)v;
-    iu = min(max(iu, hw), W - hw);             // jarvis3D.py:163-166
-    iv = min(max(iv, hw), H - hw);
-    center_hm[((size_t)t * C + c) * 2 + 0] = iu;
-    center_hm[((size_t)t * C + c) * 2 + 1] = iv;
-  }
+  if (c < C) crop_centre<false>(cam, intr, dist, row, ctr[0], ctr[1], ctr[2], hw, W, H, center_hm + ((size_t)t * C + c) * 2);
 }
 
 __global__ __launch_bounds__(64) void triangulate_kernel(
@@ -472,6 +492,64 @@ int launch_triangulate(const float* det, const float* cam, const float* intr, co
   JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
   hipLaunchKernelGGL(triangulate_kernel, dim3(T), dim3(64), 0, s, det, cam, intr, dist, calib_fs, center3d_f,
                      center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H);
+  JH_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------- caller-supplied centres
+// Stage 2 without stage 1 (jh_predictor_set_centers): the 3D centre of frame set t is centers[t] (world mm) instead of
+// a triangulated detection.  One 64-thread block per frame set, one lane per camera; writes what triangulate_body
+// writes, det excepted:
+//   center3d_f = the centre as given; center3d_i = (int)centre, truncation toward zero (jarvis3D.py:183);
+//   center_hm  = crop_centre() of it, the tail the triangulation runs;
+//   valid      = the three coordinates are finite and |x| < 2^24 (no detection ran: there is no `> 50` gate), and
+//                under a mask at least one camera of the row is unmasked; n_active as the masked triangulation counts
+//                it, n_detect = 0.
+// An invalid row is computed for the centre (0, 0, 0): nothing non-finite or out of range is ever converted to int,
+// and its crop centres are in range.
+template <bool MASK>
+__global__ __launch_bounds__(64) void centers_kernel(
+    const float* __restrict__ centers, const float* __restrict__ cam, const float* __restrict__ intr,
+    const float* __restrict__ dist, int fs, float* __restrict__ center3d_f, int* __restrict__ center3d_i,
+    int* __restrict__ center_hm, int* __restrict__ valid, int C, int hw, int W, int H,
+    const unsigned char* __restrict__ mask, int* __restrict__ n_active, int* __restrict__ n_detect) {
+  const int t = blockIdx.x, c = threadIdx.x;
+  const float gx = centers[t * 3 + 0], gy = centers[t * 3 + 1], gz = centers[t * 3 + 2];
+  // (NaN and inf compare false)
+  const bool ok = fabsf(gx) < 16777216.f && fabsf(gy) < 16777216.f && fabsf(gz) < 16777216.f;
+  const float x = ok ? gx : 0.f, y = ok ? gy : 0.f, z = ok ? gz : 0.f;
+  int act = 0;
+  if constexpr (MASK) act = __syncthreads_count(c < C && mask[(size_t)t * C + c] != 0);
+  if (c == 0) {
+    center3d_f[t * 3 + 0] = gx; center3d_f[t * 3 + 1] = gy; center3d_f[t * 3 + 2] = gz;
+    center3d_i[t * 3 + 0] = (int)x; center3d_i[t * 3 + 1] = (int)y; center3d_i[t * 3 + 2] = (int)z;
+    if constexpr (MASK) {
+      valid[t] = ok && act >= 1 ? 1 : 0;
+      n_active[t] = act;
+      n_detect[t] = 0;
+    } else {
+      valid[t] = ok ? 1 : 0;
+    }
+  }
+  if (c < C)
+    crop_centre<true>(cam, intr, dist, (size_t)t * fs + c, x, y, z, hw, W, H, center_hm + ((size_t)t * C + c) * 2);
+}
+
+// mask == nullptr: all cameras (n_active / n_detect are not touched, as by launch_triangulate)
+int launch_centers(const float* centers, const float* cam, const float* intr, const float* dist, int calib_fs,
+                   float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C, int hw, int W, int H,
+                   const unsigned char* mask, int* n_active, int* n_detect, hipStream_t s) {
+  JH_REQUIRE(C <= 64, "at most 64 cameras");
+  JH_REQUIRE(centers, "caller-supplied centres");
+  JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
+  if (mask) {
+    JH_REQUIRE(n_active && n_detect, "camera mask");
+    hipLaunchKernelGGL(centers_kernel<true>, dim3(T), dim3(64), 0, s, centers, cam, intr, dist, calib_fs, center3d_f,
+                       center3d_i, center_hm, valid, C, hw, W, H, mask, n_active, n_detect);
+  } else {
+    hipLaunchKernelGGL(centers_kernel<false>, dim3(T), dim3(64), 0, s, centers, cam, intr, dist, calib_fs, center3d_f,
+                       center3d_i, center_hm, valid, C, hw, W, H, nullptr, nullptr, nullptr);
+  }
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }

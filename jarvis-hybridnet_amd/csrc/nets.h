@@ -41,6 +41,11 @@ int launch_joint_argmax(const float* heat, const int* center_hm, int* points, fl
 int launch_triangulate(const float* det, const float* cam, const float* intr, const float* dist, int calib_fs,
                        float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C,
                        float sx2, float sy2, float wdiv, int hw, int W, int H, hipStream_t s);
+// Caller-supplied 3D centres (T,3) in place of the triangulation: the buffers launch_triangulate[_masked] writes, det
+// excepted (geometry.hip: centers_kernel).  mask: (T,C) bytes or nullptr = all cameras.
+int launch_centers(const float* centers, const float* cam, const float* intr, const float* dist, int calib_fs,
+                   float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C, int hw, int W, int H,
+                   const unsigned char* mask, int* n_active, int* n_detect, hipStream_t s);
 int launch_project_points(const float* pts, const float* cam, const float* intr, const float* dist,
                           float* uv, int P, int C, hipStream_t s);
 int launch_softargmax(const float* x, const int* center3d, double* partial, int* pmax,

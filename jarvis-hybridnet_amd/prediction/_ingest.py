@@ -59,7 +59,11 @@ class FramePipeline:
 
     Camera masks: `push(frames, mask)` with a (C,) uint8 mask per frame set.  The masks of a time batch are kept as
     one small (T, C) host tensor per batch (a short last batch repeats its last row, like its frames) and handed
-    to `submit(x, slot, mask)`; a run that never pushes a mask calls `submit(x, slot)` as before."""
+    to `submit(x, slot, mask)`; a run that never pushes a mask calls `submit(x, slot)` as before.
+
+    Caller-supplied centres: `push(frames, mask, center)` with a (3,) fp32 centre per frame set, kept and padded like
+    the masks (`batch_centers`) and handed to `submit(x, slot, mask, centers)`, mask None when no frame set of the
+    batch carried one; a run that never pushes a centre calls submit as above."""
 
     def __init__(self, frame_shape, dtype, time_batch, streams, submit, emit, device, copy_threads=None):
         self.T, self.submit, self.emit = int(time_batch), submit, emit
@@ -91,6 +95,7 @@ class FramePipeline:
         self.submit, self.emit = submit, emit
         self.group, self.fill, self.jobs = 0, 0, []
         self.masks = []                         # mask rows of the batch being filled (None entries: no mask)
+        self.centers = []                       # ... and its centres (None entries: none given)
         self.inflight = []                      # (outputs, event, n_real) of submitted batches
         self.frames_in = 0
         # where the calling thread spends its time (seconds): waiting for the pool's copies, enqueueing upload +
@@ -126,12 +131,14 @@ class FramePipeline:
         else:
             self.jobs.append(self.pool.submit(np.copyto, dst, src))
 
-    def push(self, frames, mask=None):
+    def push(self, frames, mask=None, center=None):
         """One decoded frame set: a numpy array / CPU tensor of `frame_shape` (copied into the staging
         buffer by the pool), or a callable `fill(dst)` that decodes straight into the numpy view `dst` of
         the pinned buffer (the reference's `read_images(cap, slice, imgs_orig)` pattern: no copy at all;
-        it runs on a pool thread).  mask: this frame set's (C,) camera mask, or None."""
+        it runs on a pool thread).  mask: this frame set's (C,) camera mask, or None; center: its (3,) centre, or
+        None."""
         self.masks.append(mask)
+        self.centers.append(center)
         slot = self.group % self.slots
         dst = self.host_np[slot][self.fill]
         if callable(frames):
@@ -185,7 +192,8 @@ class FramePipeline:
 
     def _submit(self, x, slot):
         mask, self.masks = batch_mask(self.masks, self.T), []
-        return self.submit(x, slot) if mask is None else self.submit(x, slot, mask)
+        centers, self.centers = batch_centers(self.centers, self.T), []
+        return submit_batch(self.submit, x, slot, mask, centers)
 
     # ---- rows ----------------------------------------------------------------------------------------
     def drain(self, keep=0):
@@ -216,14 +224,15 @@ class DevicePipeline:
 
     def __init__(self, time_batch, submit, emit, streams=1):
         self.T, self.submit, self.emit = int(time_batch), submit, emit
-        self.group, self.frames_in, self.masks = [], 0, []
+        self.group, self.frames_in, self.masks, self.centers = [], 0, [], []
         self.keep = max(0, int(streams) - 1)    # batches left in flight behind the one just submitted
         self.slots = self.keep + 1              # output-ring slots: one per batch that can be in flight
         self.n, self.inflight = 0, []
 
-    def push(self, frames, mask=None):
+    def push(self, frames, mask=None, center=None):
         self.group.append(frames)
         self.masks.append(mask)
+        self.centers.append(center)
         self.frames_in += 1
         if len(self.group) == self.T:
             self._launch()
@@ -235,7 +244,8 @@ class DevicePipeline:
         # the slot's previous batch has been emitted: at most `keep` batches are in flight at this point
         self.drain(self.keep)
         mask, self.masks = batch_mask(self.masks, self.T), []
-        outs, ev = self.submit(x, self.n % self.slots) if mask is None else self.submit(x, self.n % self.slots, mask)
+        centers, self.centers = batch_centers(self.centers, self.T), []
+        outs, ev = submit_batch(self.submit, x, self.n % self.slots, mask, centers)
         self.n += 1
         self.inflight.append((outs, ev, real))
 
@@ -261,6 +271,24 @@ def batch_mask(rows, time_batch):
     width = next(r for r in rows if r is not None).numel()
     rows = [torch.ones(width, dtype=torch.uint8) if r is None else r.cpu() for r in rows]
     return torch.stack(rows + [rows[-1]] * (time_batch - len(rows)))
+
+
+def batch_centers(rows, time_batch):
+    """The (time_batch, 3) fp32 centres of one time batch from its frame sets' rows ((3,) tensors), a short batch
+    padded with its last row like its frames; None when no frame set carried a centre.  A frame set without one
+    inside a batch that has some gets a NaN row: an invalid row of the result."""
+    if all(r is None for r in rows):
+        return None
+    rows = [torch.full((3,), float("nan")) if r is None else r.cpu() for r in rows]
+    return torch.stack(rows + [rows[-1]] * (time_batch - len(rows)))
+
+
+def submit_batch(submit, x, slot, mask, centers):
+    """The pipelines' call of `submit`: (x, slot), (x, slot, mask) or (x, slot, mask, centers) by what the batch
+    carries, so that a submit written before masks or centres existed is called as it always was."""
+    if centers is not None:
+        return submit(x, slot, mask, centers)
+    return submit(x, slot) if mask is None else submit(x, slot, mask)
 
 
 def host_outputs(ring, slot, outs):

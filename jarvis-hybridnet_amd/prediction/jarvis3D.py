@@ -134,7 +134,7 @@ class JarvisPredictor3D(nn.Module):
         return None if m is None else m.unsqueeze(0)
 
     def forward(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None,
-                return_2d=False):
+                return_2d=False, centers=None):
         """imgs (C,3,H,W) RGB in [0,1] -> (points3D (1,J,3), confidences (1,J)) or (None, None).
         return_2d: a third element, the per-camera `Views2D` of this frame set (leading dimension 1: 2D keypoints of
         every camera from the heat maps this forward computed anyway, the reprojections of the 3D keypoints and
@@ -142,17 +142,30 @@ class JarvisPredictor3D(nn.Module):
         camera_mask (C,) bool / integer tensor or sequence, host or device: the frame is computed as the reference
         computes it for the cameras with a nonzero entry alone, in their order (its `cameras_to_use` subset); what
         the other cameras' slots of `imgs` hold does not matter.  Fewer than two cameras left, or fewer than two of
-        them detecting: (None, None).  None: all cameras."""
+        them detecting: (None, None).  None: all cameras.
+        centers (3,) world millimetres, host or device: where the subject is -- the centroid of the previous result
+        when tracking, a fixed volume, another detector's answer.  Stage 1 (resize, CenterDetect, arg-max,
+        triangulation) then does not run: the crops and the voxel cube are placed around this centre, truncated and
+        projected as the reference truncates and projects its triangulated one (jarvis3D.py:161-166,183).  The frame is
+        valid iff the centre is finite and below 2^24 in magnitude (and, under camera_mask, a camera is left): there is
+        no detection gate, so (None, None) means an unusable centre.  A centre taken from a detected call of the same
+        frames, calibration and mask (native(...).debug("cuda")["center3d"]) gives that call's result bit for bit.
+        A device tensor computed from the previous result costs no host synchronisation.  None: detect, as always.
+        (weights_center_detect=None builds CenterDetect with its initial weights, as it always did; a predictor whose
+        every call brings centres never runs it.)"""
         mask = self._frame_mask(camera_mask)
+        centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(imgs, (self.num_cameras,))
         self.reproTool.cameraMatrices = cameraMatrices
         self.reproTool.intrinsicMatrices = intrinsicMatrices
         self.reproTool.distortionCoefficients = distortionCoefficients
-        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True)
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
+                         centers)
 
-    def _run(self, frames, calib, mask, return_2d, single=False):
-        """The forward of checked frames (a _native.Frames; single: one frame set, lead (C,)) with a checked mask, on
-        the native predictor of their size: nothing of the predictor is touched before this."""
+    def _run(self, frames, calib, mask, return_2d, single=False, centers=None):
+        """The forward of checked frames (a _native.Frames; single: one frame set, lead (C,)) with a checked mask and
+        checked centres (_native.centers for the frames' time batch, or None), on the native predictor of their size:
+        nothing of the predictor is touched before this."""
         check_native_seam(self)
         per_frame = False
         if single:
@@ -162,7 +175,7 @@ class JarvisPredictor3D(nn.Module):
             per_frame = N.calibration(tuple(calib), frames.lead[0], self.num_cameras)[0] == "frames"
         pr = self.native(frames.height, frames.width, time_batch=frames.lead[0])
         (pr.set_calibration_frames if per_frame else pr.set_calibration)(*calib)
-        res = pr._forward(frames, None, mask)
+        res = pr._forward(frames, None, mask, centers)
         return self._single(pr, res, mask, return_2d) if single else self._batch(pr, res, mask, return_2d)
 
     @staticmethod
@@ -180,41 +193,47 @@ class JarvisPredictor3D(nn.Module):
         return (points, conf, views) if return_2d else (points, conf)
 
     def forward_uint8(self, imgs_bgr, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None,
-                      return_2d=False):
+                      return_2d=False, centers=None):
         """imgs_bgr (C,H,W,3) uint8 BGR exactly as the video decoder delivers them
         (predict3D.py:72-78).  Same result as forward() on
         `imgs_bgr.float().permute(0,3,1,2)[:, [2,1,0]] / 255.` (predict3D.py:79-80); the
-        conversion runs inside the resize / crop kernels.  camera_mask, return_2d: as forward()."""
+        conversion runs inside the resize / crop kernels.  camera_mask, return_2d, centers: as forward()."""
         mask = self._frame_mask(camera_mask)
+        centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(imgs_bgr, (self.num_cameras,), "bgr")
-        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True)
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
+                         centers)
 
     def forward_yuv(self, frames, frame_format, cameraMatrices, intrinsicMatrices, distortionCoefficients,
-                    camera_mask=None, return_2d=False):
+                    camera_mask=None, return_2d=False, centers=None):
         """frames (C,3H/2,W) uint8 YUV 4:2:0 as video decoders produce them natively, frame_format 'i420'
         (FFmpeg yuv420p: Y, U, V planes) or 'nv12' (Y plane, interleaved UV plane); H and W even.  Same result,
         bit for bit, as forward_uint8 on the BGR bytes of cv2.cvtColor(COLOR_YUV2BGR_I420 / _NV12) of each
         image (BT.601 limited range); the conversion runs inside the resize / crop kernels.
-        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d: as forward()."""
+        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d, centers: as forward()."""
         mask = self._frame_mask(camera_mask)
+        centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(frames, (self.num_cameras,), N.yuv_format(frame_format))
-        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True)
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
+                         centers)
 
     def forward_surface(self, frames, surface, cameraMatrices, intrinsicMatrices, distortionCoefficients,
-                        camera_mask=None, return_2d=False):
+                        camera_mask=None, return_2d=False, centers=None):
         """frames (C,image_stride) uint8: one YUV 4:2:0 image per camera, read in place through the YuvSurface
         `surface` (pitched decoder surfaces, I420 / YV12 / NV12 / NV21, BT.601 / BT.709, limited / full range), or one
         raw sensor image per camera through the SensorSurface `surface` (Mono8, or an 8-bit Bayer mosaic demosaiced
         bilinearly on the GPU; pitched buffers with a header in front likewise).
         Same result, bit for bit, as forward_uint8 on the BGR bytes the surface's conversion gives
         (include/jarvis_hip.h); bytes outside the planes are never read.
-        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d: as forward()."""
+        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d, centers: as forward()."""
         mask = self._frame_mask(camera_mask)
+        centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(frames, (self.num_cameras,), None, N.surface(surface))
-        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True)
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
+                         centers)
 
     def forward_batch(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
-                      camera_mask=None, return_2d=False, frame_layout=None):
+                      camera_mask=None, return_2d=False, frame_layout=None, centers=None):
         """Throughput form: imgs (T,C,3,H,W) fp32 RGB or (T,C,H,W,3) uint8 BGR,
         independent time steps -> points (T,J,3), confidences (T,J), valid (T) int32;
         no host synchronisation.  frame_format 'i420' / 'nv12': imgs (T,C,3H/2,W) uint8 YUV 4:2:0 (see
@@ -232,16 +251,27 @@ class JarvisPredictor3D(nn.Module):
         calibration of its own dataset (analysis/analyze.py).  All three in one form (ValueError otherwise).  Row t of
         the result under per-frame calibration equals, bit for bit, row t of the same batch run with row t's
         calibration shared; camera_mask and return_2d compose with either form (the reprojections of row t use row
-        t's calibration).  The single-frame forms (forward, forward_uint8, forward_yuv, forward_surface) take (C,...)."""
+        t's calibration).  The single-frame forms (forward, forward_uint8, forward_yuv, forward_surface) take (C,...).
+        centers (T,3) world millimetres, host or device: row t is the centre of frame set t and stage 1 does not run
+        (see forward()).  valid[t] = 1 iff row t is finite and below 2^24 in magnitude (and, under camera_mask, a
+        camera of row t is left); rows are independent.  Centres taken from a detected run of the same batch
+        (native(...).debug("cuda")["center3d"]) give that run bit for bit -- points, confidences, valid and the 2D
+        views -- wherever it is valid.  It composes with camera_mask, return_2d, every frame format and per-frame-set
+        calibration (row t's centre is projected with row t's calibration).  None: detect."""
+        if centers is not None:
+            if not torch.is_tensor(imgs) or imgs.dim() < 1:
+                raise ValueError("imgs must be a tensor of time steps")
+            centers = N.centers(centers, imgs.shape[0])
         if camera_mask is not None:
             if not torch.is_tensor(imgs) or imgs.dim() < 1:
                 raise ValueError("imgs must be a tensor of time steps")
             camera_mask = N.camera_mask(camera_mask, (imgs.shape[0], self.num_cameras))
         frames = N.describe_frames(imgs, (None, self.num_cameras), frame_format, frame_layout)
-        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d)
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d,
+                         centers=centers)
 
     def forward_images(self, images, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
-                       frame_layout=None, camera_mask=None, return_2d=False):
+                       frame_layout=None, camera_mask=None, return_2d=False, centers=None):
         """forward_batch on images that lie where their producers left them: `images` a sequence of C tensors (one
         frame set) or a sequence of T such sequences, each tensor ONE image -- fp32 (3,H,W); uint8 (H,W,3);
         frame_format 'i420' / 'nv12': uint8 (3H/2,W); frame_layout (a YuvSurface or a SensorSurface): 1-D uint8 of at
@@ -251,7 +281,9 @@ class JarvisPredictor3D(nn.Module):
         (jh_predictor_forward_images).
         -> what forward_batch returns for the (T,C,...) stack of the same images, bit for bit; no host
         synchronisation.  camera_mask (T,C), return_2d: as forward_batch.  Calibration: shared (C,...) or one per frame
-        set (T,C,...), as forward_batch."""
+        set (T,C,...), as forward_batch.
+        centers (T,3): as forward_batch.  With the same images in several rows and one centre per row, the rows of a
+        batch are different subjects seen in the same frames (a detected batch finds the strongest one in every row)."""
         if isinstance(images, (list, tuple)) and len(images) > 0 and torch.is_tensor(images[0]):
             images = [images]
         if not isinstance(images, (list, tuple)) or len(images) == 0:
@@ -266,7 +298,8 @@ class JarvisPredictor3D(nn.Module):
         flat = [img for frame_set in images for img in frame_set]
         frames = N.frame_images(flat, (T, self.num_cameras), frame_format, frame_layout)
         camera_mask = N.camera_mask(camera_mask, (T, self.num_cameras))
-        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d)
+        return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d,
+                         centers=N.centers(centers, T))
 
     @staticmethod
     def _batch(pr, res, mask, return_2d):

@@ -93,7 +93,7 @@ def create_header_reprojection_error(writer, cfg, camera_names):
 def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                      distortionCoefficients, cfg, output_dir, params=None, time_batch=1, streams=1,
                      frame_spec=None, frame_format="bgr", camera_mask=None, output_2d=False, camera_names=None,
-                     frame_layout=None):
+                     frame_layout=None, centers=None):
     """Run `predictor` over an iterable of multi-view frame sets -- (C,H,W,3) uint8 BGR
     arrays / tensors exactly as cv2 delivers them, or (C,3,H,W) fp32 RGB -- and write
     data3D.csv (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -152,7 +152,16 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     'NaN' where undefined, under a camera-name row and a joint-name row.  camera_names: C names, default
     Camera_0 ...  These 2D keypoints are HybridNet's own detections, on the crop around the projection of the
     TRIANGULATED centre; the predict2D driver (JarvisPredictor2D) crops around each camera's own centre detection.
-    The two agree wherever the crops cover the subject; they are not bit-equal."""
+    The two agree wherever the crops cover the subject; they are not bit-equal.
+
+    centers: where the subject is, in world millimetres -- stage 1 (resize, CenterDetect, arg-max, triangulation) then
+    does not run (JarvisPredictor3D.forward_batch(..., centers=)).  One (3,) centre for the whole run (a fixed volume),
+    or an iterable that yields one (3,) centre -- or None -- per frame set, consumed in step with `frame_sets` exactly
+    as camera_mask is (a tracker's or another detector's answer per frame).  None, or a centre that is not finite,
+    gives that frame set a 'NaN' row; the rows of the others are those of a detected run that found these centres,
+    byte for byte.  A wrong shape, and an iterable that ends before the frame sets do, or after, raise ValueError.  The
+    padding rows of a short last group repeat the last centre.  It composes with camera_mask, output_2d, frame_format,
+    frame_layout, time_batch and streams; the CSV and info.yaml formats do not change."""
     import contextlib
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
     yuv = driver_format(frame_format, frame_spec, 3, frame_layout)
@@ -163,6 +172,12 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             run_mask = N.camera_mask(camera_mask, (C,)).cpu()
         else:
             mask_iter = iter(camera_mask)
+    run_center, center_iter = None, None
+    if centers is not None:
+        if _is_single_mask(centers):
+            run_center = _center(centers)
+        else:
+            center_iter = iter(centers)
     os.makedirs(output_dir, exist_ok=True)
     if params is not None:
         params.output_dir = output_dir
@@ -208,8 +223,10 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
 
         ring = {}                                               # pinned host copies of the outputs, per slot
 
-        def submit(x, slot, mask=None):
+        def submit(x, slot, mask=None, centers=None):
             kw = {} if mask is None else {"camera_mask": mask}
+            if centers is not None:
+                kw["centers"] = centers
             if output_2d:
                 kw["return_2d"] = True
             if frame_layout is not None:
@@ -244,6 +261,13 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                     if mask is _end:
                         raise ValueError("camera_mask yielded fewer masks than there are frame sets")
                     mask = None if mask is None else N.camera_mask(mask, (C,)).cpu()
+                center = run_center
+                if center_iter is not None:
+                    center = next(center_iter, _end)
+                    if center is _end:
+                        raise ValueError("centers yielded fewer centres than there are frame sets")
+                    # (None inside a centred run: a NaN centre, i.e. an invalid frame set -- rows do not mix forms)
+                    center = torch.full((3,), float("nan")) if center is None else _center(center)
                 if not callable(frames):
                     frames = frames if torch.is_tensor(frames) and frames.is_cuda else _as_host(frames)
                     if yuv or frame_layout is not None:
@@ -256,9 +280,14 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                         n += pipe.finish()
                     pipe, key = pipeline_for(predictor, frames, time_batch, streams, submit, emit, frame_spec,
                                              frame_layout), k
-                pipe.push(frames) if mask is None else pipe.push(frames, mask)
+                if center is not None:
+                    pipe.push(frames, mask, center)
+                else:
+                    pipe.push(frames) if mask is None else pipe.push(frames, mask)
             if mask_iter is not None and next(mask_iter, _end) is not _end:
                 raise ValueError("camera_mask yielded more masks than there are frame sets")
+            if center_iter is not None and next(center_iter, _end) is not _end:
+                raise ValueError("centers yielded more centres than there are frame sets")
             if pipe is not None:
                 n += pipe.finish()
         except BaseException:
@@ -281,6 +310,11 @@ def _is_single_mask(camera_mask):
     if isinstance(camera_mask, (list, tuple)):
         return all(isinstance(v, (bool, int, float, np.generic)) for v in camera_mask)
     return False
+
+
+def _center(value):
+    """One frame set's centre checked: a (3,) host fp32 tensor (_native.centers; ValueError for another shape)."""
+    return N.centers(value, 1)[0].cpu()
 
 
 def _as_host(frames):

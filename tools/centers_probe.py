@@ -1,0 +1,132 @@
+"""What caller-supplied centres buy (jh_predictor_set_centers: the 3D path without CenterDetect), on one GPU at BASELINE
+configs[2] (12 cameras 1280 x 1024, 23 keypoints, bbox 256, 64^3 grid), small models, fp32 frames resident in HBM as
+bench.py feeds them.  Detected forwards against centred ones whose centres are the detected run's own (so stage 2 and 3
+do the same work on the same crops), timed with HIP events after a warm-up, median of the passes:
+  1  time_batch 1 with graph replay (the tracking loop's call): milliseconds per frame set;
+  2  3 streams x 32 frame sets (MultiStreamPredictor, the throughput form bench.py measures): `frame_sets_per_s`, the
+     multi-view frames/s of bench.py, and `frames_per_s`, camera images per second (x C).
+The centres are passed with every call, as a tracking loop passes them: the copy into the predictor's buffer is part
+of what is timed.
+python tools/centers_probe.py [--passes 7] [--calls 50] [--steps 4] [--out profiles/r07_centers_probe.json]"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")))
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+from jarvis_hybridnet_amd import synthetic as S  # noqa: E402
+from jarvis_hybridnet_amd._predictor import MultiStreamPredictor, NativePredictor  # noqa: E402
+
+
+def median(v):
+    return sorted(v)[len(v) // 2]
+
+
+def timed(fn, passes):
+    """Median / min / max over `passes` of the HIP-event time of fn() in milliseconds; fn enqueues on the current
+    stream or makes it wait for what it enqueued elsewhere."""
+    ms = []
+    for _ in range(passes):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record()
+        fn()
+        t1.record()
+        t1.synchronize()
+        ms.append(t0.elapsed_time(t1))
+    return dict(ms=median(ms), ms_min=min(ms), ms_max=max(ms))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--time-batch", type=int, default=32)
+    ap.add_argument("--streams", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--passes", type=int, default=7)
+    ap.add_argument("--calls", type=int, default=50, help="time_batch 1: forwards per timed pass")
+    ap.add_argument("--steps", type=int, default=4, help="3 x 32: steps (one batch per stream) per timed pass")
+    ap.add_argument("--out", default=os.path.join("profiles", "r07_centers_probe.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("centers_probe: no GPU; a timing needs one")
+    c, T, K = bench.CONFIGS["cfg3"], a.time_batch, a.streams
+    H, W, C, J = c["H"], c["W"], c["C"], c["J"]
+    calib = S.ring_calibration(C, W, H, c["focal"])
+    calib_dev = [t.cuda() for t in calib]
+    sd_c = S.efficienttrack_weights("small", 1, c["seeds"][0])
+    sd_h = S.hybridnet_weights("small", J, c["seeds"][1])
+    base = torch.stack([S.blob_frames(calib, W, H, J, c["seeds"][2] + i)[0] for i in range(4)]).cuda()
+    x = base[torch.arange(T, device="cuda") % 4].contiguous()                     # (T,C,3,H,W) fp32
+
+    def make(frames):
+        return NativePredictor(sd_c, sd_h, num_cameras=C, num_joints=J, center_size=c["center"], bbox=c["bbox"],
+                               roi_cube_size=c["roi"], grid_spacing=c["spacing"], img_h=H, img_w=W, mean=S.MEAN,
+                               std=S.STD, time_batch=frames)
+    out = dict(config="cfg3", cameras=C, height=H, width=W, models="small", frames="fp32 RGB, resident",
+               passes=a.passes)
+
+    # ---- 1: time_batch 1, graph replay
+    p1 = make(1)
+    p1.set_calibration(*calib_dev)
+    assert p1.graph_replay
+    x1 = x[:1].contiguous()
+    res = p1.forward(x1)
+    k1 = p1.debug("cuda")["center3d"].clone()
+    torch.cuda.synchronize()
+    assert int(res[2][0]) == 1, "the probe's frame set must be a valid detection"
+    want = res[0].clone()
+    rows = {}
+    for name, centers in (("detected", None), ("centred", k1)):
+        def calls(n=a.calls):
+            for _ in range(n):
+                p1.forward(x1, res, centers=centers)
+        calls(10)
+        r = timed(calls, a.passes)
+        rows[name] = {k + "_per_frame_set": v / a.calls for k, v in r.items()}
+        torch.cuda.synchronize()
+        rows[name]["equals_detected_bits"] = bool(torch.equal(res[0], want))
+    rows["centred_vs_detected"] = rows["centred"]["ms_per_frame_set"] / rows["detected"]["ms_per_frame_set"]
+    out["time_batch_1_graph"] = dict(calls_per_pass=a.calls, **rows)
+
+    # ---- 2: K streams x T frame sets
+    msp = MultiStreamPredictor(lambda: make(T), streams=K)
+    msp.set_calibration(*calib_dev)
+    outs = [(torch.empty((T, J, 3), device="cuda"), torch.empty((T, J), device="cuda"),
+             torch.empty((T,), device="cuda", dtype=torch.int32)) for _ in range(K)]
+    msp.forward(x, outs[0])
+    msp.synchronize()
+    kT = msp.preds[0].debug("cuda")["center3d"].clone()
+    torch.cuda.synchronize()
+    valid = int(outs[0][2].sum())
+    want = outs[0][0].clone()
+    rows = {}
+    for name, centers in (("detected", None), ("centred", kT)):
+        def steps(n=a.steps):
+            for _ in range(n):
+                for i in range(K):
+                    msp.forward(x, outs[i], centers=centers)
+            cur = torch.cuda.current_stream()
+            for s in msp.streams:
+                cur.wait_stream(s)
+        steps(a.warmup)
+        r = timed(steps, a.passes)
+        sets = a.steps * K * T
+        rows[name] = dict(r, frame_sets_per_s=sets / (r["ms"] * 1e-3), frames_per_s=sets * C / (r["ms"] * 1e-3))
+        torch.cuda.synchronize()
+        rows[name]["equals_detected_bits"] = bool(torch.equal(outs[0][0], want))
+    rows["centred_vs_detected"] = rows["centred"]["frames_per_s"] / rows["detected"]["frames_per_s"]
+    out["streams_x_time_batch"] = dict(streams=K, time_batch=T, steps_per_pass=a.steps, valid_frame_sets=valid, **rows)
+
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
