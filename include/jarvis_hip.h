@@ -559,6 +559,10 @@ int jh_profile_get(int i, char* name, int name_cap, double* ms, double* flops, d
 int jh_op_conv(int nd, int kind, int k, int stride, int pad, int cin, int cout,
                const float* w_host, const float* b_host, const float* x_dev, int n, int d, int h,
                int w, const float* gate_dev, int norm_act, float* y_dev, void* stream);
+/* TEST-ONLY: launches of the window form of ConvTranspose2d k4 s2 p1 (layers without statistics and gate;
+ * JH_DECONV4_WINDOW=0 at weight-packing time selects the four-parity forms) by this process so far -- how a test tells
+ * which form ran.  Under hipGraph capture it counts captures, not replays. */
+long jh_deconv4_window_launches(void);
 /* depthwise k x k stride 1: x (N,C,H,W), w_host (C,1,k,k) -> y. */
 int jh_op_depthwise(int k, int c, const float* w_host, const float* x_dev, int n, int h, int w,
                     int norm_act, float* y_dev, void* stream);

@@ -169,6 +169,7 @@ _SIGS = {
     "jh_predictor_hybridnet_forward": (c_int, [c_void_p] * 9),
     "jh_op_conv": (c_int, [c_int] * 7 + [c_void_p, c_void_p, c_void_p] + [c_int] * 4 +
                    [c_void_p, c_int, c_void_p, c_void_p]),
+    "jh_deconv4_window_launches": (ctypes.c_long, []),
     "jh_op_depthwise": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                 c_void_p, c_void_p]),
     "jh_op_depthwise_pool": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,

@@ -1250,12 +1250,15 @@ int jh_profile_get(int i, char* name, int name_cap, double* ms, double* flops, d
 }
 
 // -------------------------------------------------------- single-operator tests
+long jh_deconv4_window_launches(void) { return deconv4_window_launches(); }
+
 int jh_op_conv(int nd, int kind, int k, int stride, int pad, int cin, int cout,
                const float* w_host, const float* b_host, const float* x_dev, int n, int d, int h,
                int w, const float* gate_dev, int norm_act, float* y_dev, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   ConvDesc desc = kind == 0 ? conv_desc(nd, k, stride, pad, cin, cout)
                             : (kind == 1 ? deconv2d_k4s2p1_desc(cin, cout) : deconv3d_k2s2_desc(cin, cout));
+  desc.plain_out = norm_act < 0 && !gate_dev;
   Scratch sc;
   Act x, y;
   if (nd == 2) d = 1;
@@ -1263,7 +1266,10 @@ int jh_op_conv(int nd, int kind, int k, int stride, int pad, int cin, int cout,
   int Do, Ho, Wo;
   conv_out_shape(desc, d, h, w, &Do, &Ho, &Wo);
   if (sc.act(n, Do, Ho, Wo, cout, &y)) return 1;
-  JH_CHECK_HIP(hipMemsetAsync(y.p, 0, y.bytes(), s));
+  // (a plain ConvTranspose2d -- no statistics, no InstanceNorm behind it -- starts from NaN instead: an output element
+  //  that no workgroup stores then reaches the caller as NaN; pad channels are not copied out.  The fill exists for the
+  //  exactly-once-stores check of tests/test_hip_deconv4_window.py)
+  JH_CHECK_HIP(hipMemsetAsync(y.p, kind == 1 && desc.plain_out ? 0xFF : 0, y.bytes(), s));
   // the same choice the V2V plan makes: 3x3x3 stride-1 convs run as Winograd (JH_WINO=0: direct)
   bool wino = kind == 0 && nd == 3 && k == 3 && stride == 1 && pad == 1 && !gate_dev;
   if (const char* e = getenv("JH_WINO")) wino = wino && atoi(e) != 0;

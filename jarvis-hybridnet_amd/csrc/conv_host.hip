@@ -69,10 +69,20 @@ int pack_conv_weights(const ConvDesc& d, const float* w, const float* b, bool tr
   const size_t phase_stride = (size_t)ntap * nk8 * nb * 128;
   std::vector<float> packed(phase_stride * d.nphase, 0.f);
   // kernels that read both operands 16 bytes at a time want two 8-channel steps per lane word
-  const bool paired = d.nd == 2 && d.ostride > 1 && deconv4_eligible(cin_p, cout_p16);
+  // ConvTranspose2d k4 s2 p1 without statistics and gate: the window form of csrc/deconv4.hip, one 2 x 2 convolution
+  // over the 4 cout_p columns (output sub-position, channel) of a window (JH_DECONV4_WINDOW=0: the four-parity forms)
+  const int cout_p = cpad(d.cout);
+  // (=2: also the layers of 8 column blocks in either form, cout 25..32 -- the measurement knob of DESIGN 3.8a)
+  int wmode = 1;
+  if (const char* e = getenv("JH_DECONV4_WINDOW")) wmode = atoi(e);
+  const bool window = d.nd == 2 && d.ostride > 1 && d.plain_out && wmode != 0 &&
+                      deconv4_window_eligible(cin_p, cout_p, wmode >= 2);
+  const int npair = (nk8 + 1) / 2, nbw = (4 * cout_p + 15) / 16;
+  const bool paired = !window && d.nd == 2 && d.ostride > 1 && deconv4_eligible(cin_p, cout_p16);
   // stride-2 3D convs: two taps per 16-byte weight word (conv_mfma.h, TAPPAIR)
   const bool tap_paired = d.nd == 3 && d.k == 3 && d.stride == 2 && d.ostride == 1;
   if (tap_paired) packed.assign((size_t)((ntap + 1) / 2) * nk8 * nb * 256, 0.f);
+  if (window) packed.assign((size_t)ntap * npair * nbw * 256, 0.f);
   // geometry of the source tensor
   int skd, sk;   // source kernel extents
   if (d.ostride > 1 && d.nd == 2) { skd = 1; sk = 4; }
@@ -101,6 +111,14 @@ int pack_conv_weights(const ConvDesc& d, const float* w, const float* b, bool tr
               const int lane = kq * 16 + nn;
               if (tap_paired)
                 packed[((((size_t)(tap / 2)) * nk8 + kc8) * nb + nbk) * 256 + lane * 4 + (tap & 1) * 2 + j] = v;
+              else if (window) {
+                // phase (py, px) is sub-position (1 - py, 1 - px) of the window: outputs (2 wy - 1, 2 wy) read the
+                // inputs {wy - 1, wy} with the taps of the odd / even parity
+                const int sub = (1 - d.phase[ph].ooff[1]) * 2 + (1 - d.phase[ph].ooff[2]);
+                const int col = sub * cout_p + co;
+                packed[(((size_t)tap * npair + kc8 / 2) * nbw + col / 16) * 256 + (kq * 16 + col % 16) * 4 +
+                       (kc8 & 1) * 2 + j] = v;
+              }
               else if (paired)
                 packed[ph * phase_stride + (((size_t)tap * (nk8 / 2) + kc8 / 2) * nb + nbk) * 256 + lane * 4 + (kc8 & 1) * 2 + j] = v;
               else
@@ -108,8 +126,8 @@ int pack_conv_weights(const ConvDesc& d, const float* w, const float* b, bool tr
             }
         }
   }
-  out->cin_p = cin_p; out->cout_p16 = cout_p16; out->paired = tap_paired ? 2 : (paired ? 1 : 0);
-  out->phase_stride = tap_paired ? packed.size() : phase_stride;
+  out->cin_p = cin_p; out->cout_p16 = cout_p16; out->paired = tap_paired ? 2 : (window ? 3 : (paired ? 1 : 0));
+  out->phase_stride = tap_paired ? packed.size() : (window ? packed.size() / d.nphase : phase_stride);
   JH_CHECK_HIP(hipMalloc(&out->w, packed.size() * sizeof(float)));
   JH_CHECK_HIP(hipMemcpy(out->w, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
   out->bias = nullptr;
@@ -189,7 +207,12 @@ int launch_conv(const ConvDesc& d, const ConvWeights& w, const Act& x, const Act
                          units);
   // LDS budget of the staged channel chunk (pick_kc8): 40 KB -- three to four workgroups per CU for the k5 / k4T
   // layers -- measured against 72 KB (two): k5s2 16->96 308 -> 287 us, head ConvTranspose 954 -> 928 us
-  const size_t budget = 40 * 1024;
+  const size_t budget = kConvLdsBudget;
+  if (a.paired == 3) {                                // packed for the window form: nothing else reads that layout
+    JH_REQUIRE(d.nd == 2 && d.ostride == 2 && d.k == 2 && !stats && !gate && !(se && se->pool),
+               "window-form weights on a layer with statistics or a gate");
+    return launch_deconv4_window(a, s);
+  }
   if (d.nd == 2 && d.ostride == 2 && d.k == 2) {      // all four parities from one staged patch
     const int rc = launch_deconv4_fused(a, s);
     if (rc >= 0) return rc;

@@ -708,6 +708,9 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
     conv_epilogue<MR, NR, TY, TX>(acc, e, lds, nb0, oz0, oy0, ox0, tid);
 }
 
+// LDS budget of the staged channel chunk (pick_kc8), see launch_conv
+constexpr size_t kConvLdsBudget = 40 * 1024;
+
 // Channels per LDS pass: the candidate (8..32) that wastes the fewest zero-padded
 // channels; ties go to the larger pass (fewer staging rounds).
 inline int pick_kc8(int cin_p, size_t (*lds_bytes)(int), size_t budget) {
@@ -779,6 +782,9 @@ int launch_conv_pw_direct(const ConvArgs& a, hipStream_t s);
 // ConvTranspose2d k4 s2 p1 with the four parities in one workgroup (csrc/deconv4.hip); -1: not its layer
 int launch_deconv4_fused(const ConvArgs& a, hipStream_t s);
 bool deconv4_eligible(int cin_p, int cout_p16);
+// ... and its window form for layers without statistics and gate (weights packed as ConvWeights::paired == 3)
+int launch_deconv4_window(const ConvArgs& a, hipStream_t s);
+bool deconv4_window_eligible(int cin_p, int cout_p, bool wide);
 
 // per-translation-unit entry points (one .hip file per kernel family so the
 // instantiations compile in parallel)

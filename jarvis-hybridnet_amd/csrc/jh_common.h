@@ -96,12 +96,16 @@ struct ConvDesc {
   int cin, cout;
   int latency_class;   // 1: the plan belongs to the single-frame-set class (time batch < 8): tile forms that trade
                        // workgroups for fill (the whole-image tile) stay off.  A function of the class, never of the batch.
+  int plain_out;       // 1: every launch of the layer runs without fused statistics and without a gate (set by whoever
+                       // packs the weights): a ConvTranspose2d k4 s2 p1 may then take the window form (csrc/deconv4.hip)
 };
 
 // Packed weights of one conv (all phases), see pack_conv_weights().
 struct ConvWeights {
   float* w = nullptr;      // [phase][tap][cin_p/8][cout_p16/16][64][2]; paired: [phase][tap][cin_p/16][cout_p16/16][64][4]
-  int paired = 0;          // two 8-channel steps per 16-byte lane word (kernels that read operands as b128)
+  int paired = 0;          // 1: two 8-channel steps per 16-byte lane word (kernels that read operands as b128);
+                           // 2: two taps per word (stride-2 3D convs); 3: the window form of ConvTranspose2d k4 s2 p1,
+                           // [window tap][ceil(cin_p/16)][ceil(4 cout_p/16)][64][4] with columns sub * cout_p + channel
   float* bias = nullptr;   // [cout_p16] or nullptr
   size_t phase_stride = 0; // floats
   int cin_p = 0, cout_p16 = 0;
@@ -154,7 +158,7 @@ struct ConvArgs {
   int in_px;             // floats per input pixel in memory: cin_p, or 4 for the 3-channel network
                          // input (one float4 per pixel; channels 4.. of the K padding read 0)
   int ostride, nphase;
-  int paired = 0;        // weights in the paired layout (ConvWeights::paired)
+  int paired = 0;        // layout of the weights (ConvWeights::paired)
   FastDiv fgx, fgy, ftx, fty;   // divisors: grid x / y, tiles per row / column (set by the launcher)
   size_t phase_stride;
   ConvPhase phase[8];
@@ -182,6 +186,8 @@ void conv_out_shape(const ConvDesc& d, int D, int H, int W, int* Do, int* Ho, in
 ConvDesc conv_desc(int nd, int k, int stride, int pad, int cin, int cout);
 ConvDesc deconv2d_k4s2p1_desc(int cin, int cout);
 ConvDesc deconv3d_k2s2_desc(int cin, int cout);
+// launches of the window form of ConvTranspose2d k4 s2 p1 (csrc/deconv4.hip) by this process so far (tests)
+long deconv4_window_launches();
 
 // ---------------------------------------------------------------- elementwise
 // y = act((x - mean) * rstd + r1) + r2  with per-(n,c) statistics from `stats`

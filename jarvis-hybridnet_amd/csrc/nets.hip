@@ -111,6 +111,7 @@ int Plan::add_conv(const ParamMap& pm, const ConvDesc& d, const std::string& wke
   const float *w = nullptr, *b = nullptr;
   ConvDesc dd = d;
   dd.latency_class = norm_block_kb == 0 ? 1 : 0;       // (the plan's time-batch class, set before build())
+  dd.plain_out = !want_stats && !gate && !se;
   if (get(pm, wkey, (size_t)d.cin * d.cout * taps, &w)) return 1;
   if (!bkey.empty() && get(pm, bkey, d.cout, &b)) return 1;
   // 3x3x3 stride-1 convs (the V2V residual blocks) run as Winograd F(2x2,3x3) x direct z
@@ -140,7 +141,7 @@ int Plan::add_conv(const ParamMap& pm, const ConvDesc& d, const std::string& wke
   } else if (wino) {
     if (pack_wino_weights(d.cin, d.cout, w, b, &cw)) return 1;
   } else {
-    if (pack_conv_weights(d, w, b, transposed, &cw)) return 1;
+    if (pack_conv_weights(dd, w, b, transposed, &cw)) return 1;
   }
   convs_.push_back(cw);
   bytes_ += cw.phase_stride * d.nphase * sizeof(float);

@@ -30,7 +30,8 @@ SPECS = {
     "bifpn_node_56x56@32": [("%bifpn_rows_kernel<56, 2, 1, 0, 2, false>%", "largest_grid"),
                             ("%bifpn_rows_kernel<56, 3, 0, 0, 2, false>%", "largest_grid")],
     "norm_apply": [("%norm_apply_kernel%", "all")],
-    "conv2d_k4s2T_64x23@128": [("%deconv4_fused_kernel%", "largest_grid")],
+    # (the window form by default, the four-parity kernel under JH_DECONV4_WINDOW=0: one of the two runs)
+    "conv2d_k4s2T_64x23@128": [("%deconv4_window_kernel%", "largest_grid"), ("%deconv4_fused_kernel%", "largest_grid")],
     "stem_conv_k3s2_3x16@128": [("%stem_conv_kernel<1,%", "largest_grid"), ("%stem_conv_kernel<2,%", "largest_grid")],
     "conv3d_k3s2_23x46@32": [("%conv_mfma_kernel<3, 3, 2,%", "largest_grid")],
     "conv2d_k3s1_16x16@128": [("%conv_mfma_kernel<2, 3, 1, 1, 16, 16, 1, 2>%", "largest_grid")],
