@@ -563,6 +563,37 @@ int jh_op_conv(int nd, int kind, int k, int stride, int pad, int cin, int cout,
  * JH_DECONV4_WINDOW=0 at weight-packing time selects the four-parity forms) by this process so far -- how a test tells
  * which form ran.  Under hipGraph capture it counts captures, not replays. */
 long jh_deconv4_window_launches(void);
+/* TEST-ONLY: the operand transform a consumer applies while it stages its input (csrc/jh_common.h: InNorm, SeGate),
+ * described from the host so that only the consumer is under test. */
+typedef struct jh_op_operand {
+  const double* in_sums_host; /* (n, cin, 2) sum and sum of squares per image and channel of x, or NULL: x is read as it
+                               * is.  InstanceNorm (eps 1e-5) + in_act are applied on load, 1 / pixels as a float */
+  int32_t in_act;             /* 0 none / 1 relu / 2 silu, behind that InstanceNorm */
+  int32_t latency_class;      /* ConvDesc::latency_class: 1 = the tile forms of the single-frame-set plans */
+  int32_t want_stats;         /* 1: the launch also accumulates the fused statistics of y (not returned); 0 and no gate:
+                               * a ConvTranspose2d k4 s2 p1 may take the window form */
+  int32_t se_c, se_s;         /* the squeeze-excite gate as the recipe (se_pool_host != NULL): channels (= cin), squeeze */
+  float se_inv_hw;            /* 1 / pixels the pooled sums were taken over */
+  const float *se_wr_host, *se_br_host, *se_we_host, *se_be_host; /* (se_s, se_c), (se_s), (se_c, se_s), (se_c) */
+  const double* se_pool_host; /* (n, se_c) pooled sums of the activated tensor */
+} jh_op_operand;
+/* jh_op_conv with the operand transform: y is always the RAW convolution output (no InstanceNorm behind it).  The gate
+ * is either gate_dev (n, cin) or the recipe in `operand`.  kind 1 with cout == 1, no bias, no statistics: the
+ * one-channel ConvTranspose2d kernel of the CenterDetect head. */
+int jh_op_conv_operand(int nd, int kind, int k, int stride, int pad, int cin, int cout,
+                       const float* w_host, const float* b_host, const float* x_dev, int n, int d, int h,
+                       int w, const float* gate_dev, const jh_op_operand* operand, float* y_dev, void* stream);
+/* The squeeze-excite gate kernel on its own: pooled sums (n, c) and the two layers' weights from the host ->
+ * gate_dev (n, c) = sigmoid(We silu(Wr (pool * inv_hw) + br) + be). */
+int jh_op_se_gate(const double* pool_host, int n, int c, int squeeze, float inv_hw, const float* wr_host,
+                  const float* br_host, const float* we_host, const float* be_host, float* gate_dev, void* stream);
+/* The InstanceNorm pass on its own, in place on a copy of x (n, c, [d,] h, w) as the plans run it:
+ * act((x - mean) * rstd + r1) + r2 with statistics sums_host (n, c, 2); r1_sums_host: r1 is raw, its
+ * InstanceNorm + ReLU is applied on load (act must be 1).  write_y: y_dev receives the result; want_pool: pool_host
+ * (n, c) doubles receive the sums of the result over the pixels.  min_block_kb: Plan::norm_block_kb (0 or 64). */
+int jh_op_norm_apply(const float* x_dev, int n, int c, int d, int h, int w, const double* sums_host, int act,
+                     const float* r1_dev, const double* r1_sums_host, const float* r2_dev, int write_y, int want_pool,
+                     int min_block_kb, float* y_dev, double* pool_host, void* stream);
 /* depthwise k x k stride 1: x (N,C,H,W), w_host (C,1,k,k) -> y. */
 int jh_op_depthwise(int k, int c, const float* w_host, const float* x_dev, int n, int h, int w,
                     int norm_act, float* y_dev, void* stream);

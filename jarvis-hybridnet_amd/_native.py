@@ -52,7 +52,17 @@ class SensorSurfaceStruct(ctypes.Structure):
 
 assert ctypes.sizeof(SensorSurfaceStruct) == 32
 
-ABI_VERSION = 4                      # JH_ABI_VERSION of include/jarvis_hip.h
+class OpOperand(ctypes.Structure):
+    """jh_op_operand of include/jarvis_hip.h (test entry jh_op_conv_operand): host pointers as raw addresses."""
+    _fields_ = [("in_sums_host", c_void_p), ("in_act", ctypes.c_int32), ("latency_class", ctypes.c_int32),
+                ("want_stats", ctypes.c_int32), ("se_c", ctypes.c_int32), ("se_s", ctypes.c_int32),
+                ("se_inv_hw", c_float), ("se_wr_host", c_void_p), ("se_br_host", c_void_p),
+                ("se_we_host", c_void_p), ("se_be_host", c_void_p), ("se_pool_host", c_void_p)]
+
+
+assert ctypes.sizeof(OpOperand) == 72
+
+ABI_VERSION = 4                    # JH_ABI_VERSION of include/jarvis_hip.h
 # sizeof(jh_predictor_config): statically asserted on the C side (tests/abi_smoke.c) and here
 assert ctypes.sizeof(PredictorConfig) == 84
 
@@ -170,6 +180,11 @@ _SIGS = {
     "jh_op_conv": (c_int, [c_int] * 7 + [c_void_p, c_void_p, c_void_p] + [c_int] * 4 +
                    [c_void_p, c_int, c_void_p, c_void_p]),
     "jh_deconv4_window_launches": (ctypes.c_long, []),
+    "jh_op_conv_operand": (c_int, [c_int] * 7 + [c_void_p, c_void_p, c_void_p] + [c_int] * 4 +
+                           [c_void_p, ctypes.POINTER(OpOperand), c_void_p, c_void_p]),
+    "jh_op_se_gate": (c_int, [c_void_p, c_int, c_int, c_int, c_float] + [c_void_p] * 6),
+    "jh_op_norm_apply": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                                           c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "jh_op_depthwise": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                 c_void_p, c_void_p]),
     "jh_op_depthwise_pool": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,

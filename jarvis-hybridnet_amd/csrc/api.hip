@@ -36,6 +36,14 @@ struct Scratch {
   }
 };
 
+// Host values -> a device buffer of the scratch (synchronous: the host side may be a local).
+template <typename T>
+int op_upload(Scratch& sc, const T* host, size_t count, T** dev) {
+  if (sc.get(reinterpret_cast<void**>(dev), count * sizeof(T))) return 1;
+  JH_CHECK_HIP(hipMemcpy(*dev, host, count * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+
 // Caller-provided workspace, carved into 256-byte aligned pieces.  With base == nullptr it
 // only measures (jh_*_workspace_bytes).
 struct Carver {
@@ -1252,13 +1260,49 @@ int jh_profile_get(int i, char* name, int name_cap, double* ms, double* flops, d
 // -------------------------------------------------------- single-operator tests
 long jh_deconv4_window_launches(void) { return deconv4_window_launches(); }
 
-int jh_op_conv(int nd, int kind, int k, int stride, int pad, int cin, int cout,
-               const float* w_host, const float* b_host, const float* x_dev, int n, int d, int h,
-               int w, const float* gate_dev, int norm_act, float* y_dev, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
+// Host (n, c, 2) sums / sums of squares -> [N][Cp][kStatW]: the whole value in the first limb of each (exact_read then
+// returns exactly the given double), pad channels zero.
+static int op_upload_stats(Scratch& sc, const double* sums_host, int n, int c, int Cp, double** dev) {
+  std::vector<double> st((size_t)n * Cp * kStatW, 0.0);
+  for (int b = 0; b < n; ++b)
+    for (int ch = 0; ch < c; ++ch) {
+      st[((size_t)b * Cp + ch) * kStatW] = sums_host[((size_t)b * c + ch) * 2];
+      st[((size_t)b * Cp + ch) * kStatW + kLimbs] = sums_host[((size_t)b * c + ch) * 2 + 1];
+    }
+  return op_upload(sc, st.data(), st.size(), dev);
+}
+
+// The squeeze-excite recipe from host values: pooled sums (n, C) -> [N][Cp][kLimbs] (first limb), weights as they are.
+static int op_upload_se(Scratch& sc, const double* pool_host, int n, int C, int Cp, int S, float inv_hw,
+                        const float* wr, const float* br, const float* we, const float* be, SeGate* out) {
+  JH_REQUIRE(pool_host && wr && br && we && be && C >= 1 && C <= Cp && S >= 1, "squeeze-excite recipe");
+  std::vector<double> pl((size_t)n * Cp * kLimbs, 0.0);
+  for (int b = 0; b < n; ++b)
+    for (int ch = 0; ch < C; ++ch) pl[((size_t)b * Cp + ch) * kLimbs] = pool_host[(size_t)b * C + ch];
+  double* pool = nullptr;
+  float *dwr = nullptr, *dbr = nullptr, *dwe = nullptr, *dbe = nullptr;
+  if (op_upload(sc, pl.data(), pl.size(), &pool) || op_upload(sc, wr, (size_t)S * C, &dwr) ||
+      op_upload(sc, br, (size_t)S, &dbr) || op_upload(sc, we, (size_t)C * S, &dwe) || op_upload(sc, be, (size_t)C, &dbe))
+    return 1;
+  out->pool = pool; out->wr = dwr; out->br = dbr; out->we = dwe; out->be = dbe;
+  out->C = C; out->S = S; out->inv_hw = inv_hw;
+  return 0;
+}
+
+// One convolution through the choices Plan::add_conv makes (Winograd, bf16x3 levels, JH_* knobs): the body of jh_op_conv
+// (opd == nullptr: operand as it is, optional norm_apply behind the conv) and of jh_op_conv_operand (opd: the operand
+// transform of the consumer -- InstanceNorm + activation from host statistics, gate tensor or recipe -- raw output).
+static int op_conv_body(int nd, int kind, int k, int stride, int pad, int cin, int cout, const float* w_host,
+                        const float* b_host, const float* x_dev, int n, int d, int h, int w, const float* gate_dev,
+                        int norm_act, const jh_op_operand* opd, float* y_dev, hipStream_t s, const char* who) {
+  struct Weights { ConvWeights cw; ~Weights() { free_conv_weights(&cw); } } wt;
+  ConvWeights& cw = wt.cw;
+  const bool recipe = opd && opd->se_pool_host;
+  const bool want_stats = opd ? opd->want_stats != 0 : norm_act >= 0;
   ConvDesc desc = kind == 0 ? conv_desc(nd, k, stride, pad, cin, cout)
                             : (kind == 1 ? deconv2d_k4s2p1_desc(cin, cout) : deconv3d_k2s2_desc(cin, cout));
-  desc.plain_out = norm_act < 0 && !gate_dev;
+  desc.latency_class = opd ? opd->latency_class : 0;
+  desc.plain_out = !want_stats && !gate_dev && !recipe;
   Scratch sc;
   Act x, y;
   if (nd == 2) d = 1;
@@ -1273,13 +1317,20 @@ int jh_op_conv(int nd, int kind, int k, int stride, int pad, int cin, int cout,
   // the same choice the V2V plan makes: 3x3x3 stride-1 convs run as Winograd (JH_WINO=0: direct)
   bool wino = kind == 0 && nd == 3 && k == 3 && stride == 1 && pad == 1 && !gate_dev;
   if (const char* e = getenv("JH_WINO")) wino = wino && atoi(e) != 0;
+  // the CenterDetect head, one output channel: the vector-ALU kernel (EffTrackPlan::build)
+  const bool c1 = opd && kind == 1 && cout == 1 && !b_host && !want_stats && !gate_dev && !recipe;
   const bool b3 = wino && precision_mode() >= 1;         // the same choices the plans make
-  const bool d4b = kind == 1 && !b_host && norm_act < 0 && !gate_dev && precision_mode() >= 1 &&
+  const bool d4b = !c1 && kind == 1 && !b_host && !want_stats && !gate_dev && !recipe && precision_mode() >= 1 &&
                    deconv4_bf16x3_eligible(cout);
-  const bool xb = kind == 0 && !wino && !gate_dev && conv_bf16x3_eligible(desc) && x.Cp == cpad(cin) &&
+  const bool xb = kind == 0 && !wino && !gate_dev && !recipe && conv_bf16x3_eligible(desc) && x.Cp == cpad(cin) &&
                   (precision_mode() == 2 || (precision_mode() == 1 && nd == 3));
-  ConvWeights cw;
-  if (xb) {
+  float* w_c1 = nullptr;
+  if (c1) {               // [16 taps][Cp], as EffTrackPlan::build repacks deconv1.weight
+    std::vector<float> t16((size_t)16 * x.Cp, 0.f);
+    for (int c = 0; c < cin; ++c)
+      for (int t = 0; t < 16; ++t) t16[(size_t)t * x.Cp + c] = w_host[(size_t)c * 16 + t];
+    if (op_upload(sc, t16.data(), t16.size(), &w_c1)) return 1;
+  } else if (xb) {
     if (pack_conv_bf16x3_weights(desc, w_host, b_host, &cw)) return 1;
   } else if (d4b) {
     if (pack_deconv4_bf16x3_weights(cin, cout, w_host, &cw)) return 1;
@@ -1292,30 +1343,110 @@ int jh_op_conv(int nd, int kind, int k, int stride, int pad, int cin, int cout,
   }
   double* stats = nullptr;
   float* gate_p = nullptr;
-  int rc = 0;
-  do {
-    if (norm_act >= 0) {
-      if ((rc = sc.get(reinterpret_cast<void**>(&stats), (size_t)n * y.Cp * kStatW * sizeof(double)))) break;
-      if (hipMemsetAsync(stats, 0, (size_t)n * y.Cp * kStatW * sizeof(double), s) != hipSuccess) { rc = 1; break; }
-    }
-    if (gate_dev) {   // (N,Cin) -> padded (N,Cin_p)
-      if ((rc = sc.get(reinterpret_cast<void**>(&gate_p), (size_t)n * x.Cp * sizeof(float)))) break;
-      if (hipMemsetAsync(gate_p, 0, (size_t)n * x.Cp * sizeof(float), s) != hipSuccess) { rc = 1; break; }
-      if (hipMemcpy2DAsync(gate_p, x.Cp * sizeof(float), gate_dev, cin * sizeof(float),
-                           cin * sizeof(float), n, hipMemcpyDeviceToDevice, s) != hipSuccess) { rc = 1; break; }
-    }
-    if ((rc = launch_to_channel_last(x_dev, x, s))) break;
-    if (xb) { if ((rc = launch_conv_bf16x3(desc, cw, x, y, stats, s, nullptr))) break; }
-    else if (d4b) { if ((rc = launch_deconv4_bf16x3(cw, x, y, s, nullptr))) break; }
-    else if (b3) { if ((rc = launch_conv3d_bf16x3(cw, x, y, stats, s, nullptr))) break; }
-    else if (wino) { if ((rc = launch_conv3d_wino(cw, x, y, stats, s, nullptr, wino_variant_from_env()))) break; }
-    else if ((rc = launch_conv(desc, cw, x, y, gate_p, stats, s))) break;
-    if (norm_act >= 0 && (rc = launch_norm_apply(y, stats, 1e-5, norm_act, nullptr, nullptr, y.p, nullptr, s))) break;
-    if ((rc = launch_from_channel_last(y, y_dev, s))) break;
-    if (hipStreamSynchronize(s) != hipSuccess) { set_error("stream sync failed in jh_op_conv"); rc = 1; }
-  } while (0);
-  free_conv_weights(&cw);
-  return rc;
+  if (want_stats) {
+    if (sc.get(reinterpret_cast<void**>(&stats), (size_t)n * y.Cp * kStatW * sizeof(double))) return 1;
+    JH_CHECK_HIP(hipMemsetAsync(stats, 0, (size_t)n * y.Cp * kStatW * sizeof(double), s));
+  }
+  if (gate_dev) {   // (N,Cin) -> padded (N,Cin_p)
+    if (sc.get(reinterpret_cast<void**>(&gate_p), (size_t)n * x.Cp * sizeof(float))) return 1;
+    JH_CHECK_HIP(hipMemsetAsync(gate_p, 0, (size_t)n * x.Cp * sizeof(float), s));
+    JH_CHECK_HIP(hipMemcpy2DAsync(gate_p, x.Cp * sizeof(float), gate_dev, cin * sizeof(float), cin * sizeof(float), n,
+                                  hipMemcpyDeviceToDevice, s));
+  }
+  InNorm in;
+  SeGate se;
+  if (opd && opd->in_sums_host) {
+    double* st = nullptr;
+    if (op_upload_stats(sc, opd->in_sums_host, n, cin, x.Cp, &st)) return 1;
+    in.stats = st; in.inv = 1.f / (float)x.pixels(); in.act = opd->in_act;
+  }
+  if (recipe) {
+    JH_REQUIRE(opd->se_c == cin, "the gate recipe has one gate per input channel");
+    if (op_upload_se(sc, opd->se_pool_host, n, opd->se_c, x.Cp, opd->se_s, opd->se_inv_hw, opd->se_wr_host,
+                     opd->se_br_host, opd->se_we_host, opd->se_be_host, &se)) return 1;
+  }
+  const InNorm* inp = in.stats ? &in : nullptr;
+  if (launch_to_channel_last(x_dev, x, s)) return 1;
+  if (c1) { if (launch_deconv_c1(x, in.stats, in.inv, in.act, w_c1, y, s)) return 1; }
+  else if (xb) { if (launch_conv_bf16x3(desc, cw, x, y, stats, s, inp)) return 1; }
+  else if (d4b) { if (launch_deconv4_bf16x3(cw, x, y, s, inp)) return 1; }
+  else if (b3) { if (launch_conv3d_bf16x3(cw, x, y, stats, s, inp)) return 1; }
+  else if (wino) { if (launch_conv3d_wino(cw, x, y, stats, s, inp, wino_variant_from_env())) return 1; }
+  else if (launch_conv(desc, cw, x, y, gate_p, stats, s, inp, recipe ? &se : nullptr)) return 1;
+  if (!opd && norm_act >= 0 && launch_norm_apply(y, stats, 1e-5, norm_act, nullptr, nullptr, y.p, nullptr, s)) return 1;
+  if (launch_from_channel_last(y, y_dev, s)) return 1;
+  if (hipStreamSynchronize(s) != hipSuccess) { set_error(std::string("stream sync failed in ") + who); return 1; }
+  return 0;
+}
+
+int jh_op_conv(int nd, int kind, int k, int stride, int pad, int cin, int cout,
+               const float* w_host, const float* b_host, const float* x_dev, int n, int d, int h,
+               int w, const float* gate_dev, int norm_act, float* y_dev, void* stream) {
+  return op_conv_body(nd, kind, k, stride, pad, cin, cout, w_host, b_host, x_dev, n, d, h, w, gate_dev, norm_act,
+                      nullptr, y_dev, static_cast<hipStream_t>(stream), "jh_op_conv");
+}
+
+int jh_op_conv_operand(int nd, int kind, int k, int stride, int pad, int cin, int cout,
+                       const float* w_host, const float* b_host, const float* x_dev, int n, int d, int h,
+                       int w, const float* gate_dev, const jh_op_operand* operand, float* y_dev, void* stream) {
+  JH_REQUIRE(operand && w_host && x_dev && y_dev && n >= 1, "bad argument");
+  JH_REQUIRE(operand->in_act >= ACT_NONE && operand->in_act <= ACT_SILU, "jh_op_conv_operand: in_act");
+  JH_REQUIRE(operand->latency_class == 0 || operand->latency_class == 1, "jh_op_conv_operand: latency_class");
+  JH_REQUIRE(!(gate_dev && operand->se_pool_host), "either a gate tensor or a gate recipe");
+  return op_conv_body(nd, kind, k, stride, pad, cin, cout, w_host, b_host, x_dev, n, d, h, w, gate_dev, -1, operand,
+                      y_dev, static_cast<hipStream_t>(stream), "jh_op_conv_operand");
+}
+
+// The squeeze-excite gate kernel on its own: host pooled sums (n, c) and weights -> gate_dev (n, c).
+int jh_op_se_gate(const double* pool_host, int n, int c, int squeeze, float inv_hw, const float* wr_host,
+                  const float* br_host, const float* we_host, const float* be_host, float* gate_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(gate_dev && n >= 1, "bad argument");
+  Scratch sc;
+  SeGate se;
+  const int Cp = cpad(c);
+  if (op_upload_se(sc, pool_host, n, c, Cp, squeeze, inv_hw, wr_host, br_host, we_host, be_host, &se)) return 1;
+  float* gate = nullptr;
+  if (sc.get(reinterpret_cast<void**>(&gate), (size_t)n * Cp * sizeof(float))) return 1;
+  if (launch_se_gate(se.pool, n, c, Cp, squeeze, inv_hw, se.wr, se.br, se.we, se.be, gate, s)) return 1;
+  JH_CHECK_HIP(hipMemcpy2DAsync(gate_dev, c * sizeof(float), gate, Cp * sizeof(float), c * sizeof(float), n,
+                                hipMemcpyDeviceToDevice, s));
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// norm_apply on its own, in place on x as the plans run it: statistics from the host, residual operands r1 (raw, with
+// its own statistics, when r1_sums_host is given) and r2; y_dev (write_y) and / or the pooled sums pool_host (n, c).
+int jh_op_norm_apply(const float* x_dev, int n, int c, int d, int h, int w, const double* sums_host, int act,
+                     const float* r1_dev, const double* r1_sums_host, const float* r2_dev, int write_y, int want_pool,
+                     int min_block_kb, float* y_dev, double* pool_host, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(x_dev && sums_host && n >= 1 && (!write_y || y_dev) && (!want_pool || pool_host), "bad argument");
+  Scratch sc;
+  Act x, r1, r2;
+  if (sc.act(n, d, h, w, c, &x) || launch_to_channel_last(x_dev, x, s)) return 1;
+  if (r1_dev && (sc.act(n, d, h, w, c, &r1) || launch_to_channel_last(r1_dev, r1, s))) return 1;
+  if (r2_dev && (sc.act(n, d, h, w, c, &r2) || launch_to_channel_last(r2_dev, r2, s))) return 1;
+  double *st = nullptr, *st1 = nullptr, *pool = nullptr;
+  if (op_upload_stats(sc, sums_host, n, c, x.Cp, &st)) return 1;
+  if (r1_sums_host && op_upload_stats(sc, r1_sums_host, n, c, x.Cp, &st1)) return 1;
+  const size_t npl = (size_t)n * x.Cp * kLimbs;
+  if (want_pool) {
+    if (sc.get(reinterpret_cast<void**>(&pool), npl * sizeof(double))) return 1;
+    JH_CHECK_HIP(hipMemsetAsync(pool, 0, npl * sizeof(double), s));
+  }
+  if (launch_norm_apply(x, st, 1e-5, act, r1.p, r2.p, write_y ? x.p : nullptr, pool, s, st1, min_block_kb)) return 1;
+  if (write_y && launch_from_channel_last(x, y_dev, s)) return 1;
+  std::vector<double> hp(want_pool ? npl : 0);
+  if (want_pool) JH_CHECK_HIP(hipMemcpyAsync(hp.data(), pool, npl * sizeof(double), hipMemcpyDeviceToHost, s));
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  if (want_pool)
+    for (int i = 0; i < n; ++i)
+      for (int ch = 0; ch < c; ++ch) {
+        const double* q = hp.data() + ((size_t)i * x.Cp + ch) * kLimbs;
+        pool_host[(size_t)i * c + ch] = (q[0] + q[1]) + q[2];
+      }
+  return 0;
 }
 
 int jh_op_depthwise(int k, int c, const float* w_host, const float* x_dev, int n, int h, int w,

@@ -202,19 +202,20 @@ def test_depthwise_fused_se_pool(k, c, H, W):
     assert e < 2e-5 and ep < 1e-4
 
 
-@pytest.mark.parametrize("cin,cout,N,G,in_norm", [(46, 46, 5, 32, 1), (92, 92, 20, 16, 0), (60, 60, 3, 48, 1)])
-def test_conv3d_winograd_persistent(cin, cout, N, G, in_norm, monkeypatch):
+@pytest.mark.parametrize("cin,cout,N,G,norm_behind", [(46, 46, 5, 32, 1), (92, 92, 20, 16, 0), (60, 60, 3, 48, 1)])
+def test_conv3d_winograd_persistent(cin, cout, N, G, norm_behind, monkeypatch):
     """The persistent wave-specialised Winograd kernel (csrc/conv3d_wino_pw.hip, the default for
     launches with at least two tiles per CU) against torch, on the V2V layer shapes: 46->46 @ 32^3
     and 92->92 @ 16^3 (J = 23), 60->60 @ 48^3 (J = 30: two column-block groups).  Odd image counts
-    give the workgroups unequal tile lists."""
+    give the workgroups unequal tile lists.  norm_behind: InstanceNorm + ReLU applied BEHIND the convolution, from its
+    fused statistics (the input is read as it is; the transform on load is tests/test_hip_operand.py's)."""
     g = torch.Generator().manual_seed(cin + N)
     x = torch.randn(N, cin, G, G, G, generator=g)
     w = torch.randn(cout, cin, 3, 3, 3, generator=g) / (cin * 27) ** 0.5
     b = torch.randn(cout, generator=g) * 0.1
-    y, ref = _conv(3, 0, 3, 1, 1, cin, cout, x, w, b, norm_act=1 if in_norm else -1)
+    y, ref = _conv(3, 0, 3, 1, 1, cin, cout, x, w, b, norm_act=1 if norm_behind else -1)
     monkeypatch.setenv("JH_WINO_PW", "0")
-    y0, _ = _conv(3, 0, 3, 1, 1, cin, cout, x, w, b, norm_act=1 if in_norm else -1)
+    y0, _ = _conv(3, 0, 3, 1, 1, cin, cout, x, w, b, norm_act=1 if norm_behind else -1)
     e, e0 = rel_err(y, ref), rel_err(y0, ref)
     report("conv3d_winograd_persistent", cin=cin, cout=cout, n=N, g=G, rel=e, rel_one_role=e0)
     assert e < 2e-4 and e0 < 2e-4
