@@ -464,6 +464,43 @@ int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, co
                          const uint8_t* mask_dev, int32_t* points2d_dev, float* conf2d_dev, float* reproj_dev,
                          float* err_dev, uint8_t* used_dev, void* stream);
 
+/* Per-joint 3D spread (ABI v4, additive; new design: the reference computes the mean of the normalised heat map and
+ * throws the rest away, hybridnet/model.py:73-88).  For frame set t and joint j, with x the V2V output on the Gh^3
+ * half grid, voxel (i, j, k) at flat index p = (i * Gh + j) * Gh + k, h = softplus(x) the weight the soft-argmax uses,
+ * S_0 = sum h, S_a = sum h * a, S_ab = sum h * a * b over a, b in (i, j, k), and s = 2 * grid_spacing:
+ *   mass (T,J)     S_0, the normaliser, from the fp64 sum rounded once (the float the points are divided by is the
+ *                  same sum from fp32 block sums: it agrees with mass to that summation's error, not to the bit)
+ *   cov (T,J,6)    cov_ab = (S_ab / S_0 - (S_a / S_0)(S_b / S_0)) * s^2 in mm^2, order xx, xy, xz, yy, yz, zz, the
+ *                  axes those of points[..., 0..2]; the ten sums are accumulated in fp64 (every product h * a * b is
+ *                  exact there) and added across workgroups order-independently, the expression is evaluated in fp64
+ *                  and rounded once: bit-reproducible from run to run
+ *   peak (T,J,3)   the voxel of the maximum of x -- of x, not of h: softplus is monotone and float ties of h would
+ *                  hide the index --, the lowest flat index among equal maxima, in millimetres by the points' own
+ *                  expression idx * grid_spacing * 2 - roi_cube_size / 2 + center3d with the integer voxel index as
+ *                  idx.  A joint whose peak and point disagree by more than the spread has a multi-modal map.
+ * jh_softargmax_spread: jh_softargmax with these three outputs; points and conf have the bits of jh_softargmax on
+ * the same input.  workspace_dev: >= jh_softargmax_spread_workspace_bytes(t, joints, gh) bytes.
+ * jh_predictor_set_spread(pr, on): from the next call on, the 3D stage of every entry point (the whole-path forwards,
+ * jh_predictor_stage_3d / _blocks / _masked, jh_predictor_hybridnet_forward) runs the spread form of the tail and
+ * writes rows t0 .. t0+T3-1 of the predictor's own (T,J,6), (T,J,3) and (T,J) buffers; points, conf and valid keep
+ * the bits they have with it off.  The buffers are allocated by the first enabling call -- never by
+ * jh_predictor_create, so jh_predictor_device_bytes, the memory and the launches of a predictor that never asks are
+ * unchanged; jh_predictor_device_bytes grows by them -- and that first call must not be made inside a stream capture.
+ * A graph-replaying predictor records the spread form in graph slots of its own: alternating calls with the spread on
+ * and off never re-record.
+ * jh_predictor_get_spread: the three buffers copied out (any pointer may be NULL), after a forward / stage-3 call, on
+ * the same stream.  Rows of a frame set that is not valid are NaN in all three. */
+int64_t jh_softargmax_spread_workspace_bytes(int t, int joints, int gh);
+int jh_softargmax_spread(const float* v2v_out_dev, int t, int joints, int gh, float grid_spacing,
+                         float roi_cube_size, const int32_t* center3d_dev, float* heatmap_final_dev,
+                         float* points_dev, float* conf_dev, float* cov_dev, float* peak_dev, float* mass_dev,
+                         void* workspace_dev, int64_t workspace_bytes, void* stream);
+int jh_predictor_set_spread(jh_predictor* pr, int on);
+int jh_predictor_get_spread(jh_predictor* pr, float* cov_dev, float* peak_dev, float* mass_dev, void* stream);
+/* The V2V output of the last 3D chunk, for parity tests: out (T3,J,Gh,Gh,Gh) NCDHW -- what jh_softargmax_spread
+ * takes. */
+int jh_predictor_debug_v2v(jh_predictor* pr, float* out_dev, void* stream);
+
 /* Per-image frame pointers (ABI v4, additive): every camera's buffer read where its producer left it.  The entry
  * points above take ONE base pointer with all T * num_cameras images at one constant distance; twelve decoder sessions
  * or frame-grabber rings deliver twelve unrelated device pointers.  Here a call says where EACH image is.

@@ -105,6 +105,12 @@ _SIGS = {
     "jh_softargmax_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "jh_softargmax": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "jh_softargmax_spread_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "jh_softargmax_spread": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "jh_predictor_set_spread": (c_int, [c_void_p, c_int]),
+    "jh_predictor_get_spread": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_predictor_debug_v2v": (c_int, [c_void_p, c_void_p, c_void_p]),
     "jh_reproject_point": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
     "jh_reconstruct_workspace_bytes": (c_int64, [c_int]),

@@ -6,6 +6,7 @@ import torch
 
 from . import _native as N
 from . import arch
+from .spread import Spread3D  # noqa: F401 -- the name the forwards return
 
 
 # Per-camera 2D views of a 3D result (jh_predictor_views2d, include/jarvis_hip.h): points2D (T,C,J,2) int32 full-frame
@@ -44,6 +45,7 @@ class NativePredictor:
         self.launches = N.lib().jh_predictor_launches(self.handle)
         self.device_bytes = N.lib().jh_predictor_device_bytes(self.handle)
         self._centred = False                        # centres are in force (set_centers)
+        self._spread = False                         # the 3D stage runs the spread form of its tail (set_spread)
 
     def close(self):
         if getattr(self, "handle", None) and N is not None and N._lib is not None:
@@ -98,8 +100,46 @@ class NativePredictor:
         dev.record_stream(torch.cuda.current_stream())          # (copied by the call: free once it is enqueued)
         self._centred = True
 
+    # ---- per-joint 3D spread ----------------------------------------------
+    def set_spread(self, on):
+        """From the next call on the 3D stage (forward and the staged calls alike) also leaves the per-joint spread
+        in the predictor's own buffers (jh_predictor_set_spread; the first enabling call allocates them: not inside a
+        stream capture); points, conf and valid keep their bits.  Read it with spread()."""
+        if bool(on) != self._spread:
+            N.check(N.lib().jh_predictor_set_spread(self.handle, int(bool(on))))
+            self._spread = bool(on)
+            self.device_bytes = N.lib().jh_predictor_device_bytes(self.handle)
+
+    def spread(self, out=None):
+        """The spread of the last forward / stage_3d made with the spread enabled -> Spread3D of device tensors, copied
+        on the current stream (jh_predictor_get_spread).  Enables the spread on first use, so before the staged calls
+        (stage_3d ...) whose spread is wanted call it, or set_spread(True), once; forward() and forward_images() set
+        the flag themselves, from their return_spread, on every call.  out: a Spread3D to write into."""
+        self.set_spread(True)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        cov6 = torch.empty((self.T, self.J, 6), device=dev)
+        peak = torch.empty((self.T, self.J, 3), device=dev) if out is None else out.peak
+        mass = torch.empty((self.T, self.J), device=dev) if out is None else out.mass
+        N.check(N.lib().jh_predictor_get_spread(self.handle, N.ptr(cov6), N.ptr(peak), N.ptr(mass), N.stream()))
+        # xx xy xz yy yz zz mirrored into the symmetric 3 x 3: slices, no index tensor (an index made from a list is a
+        # synchronous upload, which would stall every stream of a MultiStreamPredictor)
+        xx, xy, xz, yy, yz, zz = cov6.unbind(-1)
+        cov = torch.stack((xx, xy, xz, xy, yy, yz, xz, yz, zz), -1).reshape(self.T, self.J, 3, 3)
+        if out is not None:
+            out.cov.copy_(cov)
+            cov = out.cov
+        return Spread3D(cov, peak, mass)
+
+    def debug_v2v(self, device):
+        """The V2V output of the last 3D chunk, (T3,J,Gh,Gh,Gh): what the soft-argmax tail read (jh_predictor_debug_v2v)."""
+        Gh = int(self.cfg.roi_cube_size / self.cfg.grid_spacing) // 2
+        out = torch.empty((self.T3, self.J, Gh, Gh, Gh), device=device)
+        N.check(N.lib().jh_predictor_debug_v2v(self.handle, N.ptr(out), N.stream()))
+        return out
+
     # ---- single-GPU forward ----------------------------------------------
-    def forward(self, frames, out=None, frame_format=None, camera_mask=None, frame_layout=None, centers=None):
+    def forward(self, frames, out=None, frame_format=None, camera_mask=None, frame_layout=None, centers=None,
+                return_spread=False):
         """frames (T,C,3,H,W) fp32 RGB, or (T,C,H,W,3) uint8 BGR as decoded, or with frame_format 'i420' / 'nv12'
         (T,C,3H/2,W) uint8 YUV 4:2:0 -> points (T,J,3), conf (T,J), valid (T) int32.  frame_format None: the
         dtype decides between fp32 RGB and uint8 BGR; 'bgr' requires uint8 BGR.
@@ -109,17 +149,20 @@ class NativePredictor:
         that description (jh_predictor_forward_surface) --, or a SensorSurface -- each image a raw Mono8 / Bayer
         sensor image (jh_predictor_forward_sensor); not together with frame_format 'i420' / 'nv12'.
         centers (T,3): this call runs from these centres (set_centers); None: it detects -- centres set earlier are
-        cleared first."""
+        cleared first.
+        return_spread: the Spread3D of this call follows valid: (points, conf, valid, spread).  The flag is set before
+        the call (set_spread) and decides for this call alone; points, conf and valid keep their bits."""
         return self._forward(self._describe(frames, frame_format, frame_layout), out,
-                             N.camera_mask(camera_mask, (self.T, self.C)), N.centers(centers, self.T))
+                             N.camera_mask(camera_mask, (self.T, self.C)), N.centers(centers, self.T), return_spread)
 
-    def forward_images(self, frames, out=None, camera_mask=None, centers=None):
+    def forward_images(self, frames, out=None, camera_mask=None, centers=None, return_spread=False):
         """forward() on T * C separately placed images: `frames` what _native.frame_images made of the flat list
         (index t * C + c) (jh_predictor_forward_images).  The images are read where they lie; nothing is gathered."""
         if len(frames.images) != self.T * self.C:
             raise ValueError("expected %d images (time_batch * num_cameras), got %d" % (self.T * self.C,
                                                                                          len(frames.images)))
-        return self._forward(frames, out, N.camera_mask(camera_mask, (self.T, self.C)), N.centers(centers, self.T))
+        return self._forward(frames, out, N.camera_mask(camera_mask, (self.T, self.C)), N.centers(centers, self.T),
+                             return_spread)
 
     def _describe(self, frames, frame_format=None, frame_layout=None):
         """Raw pointers cross the C ABI: refuse anything whose bytes would be misread (_native.describe_frames for
@@ -127,10 +170,12 @@ class NativePredictor:
         return N.describe_frames(frames, (self.T, self.Cloc), frame_format, frame_layout,
                                  (self.cfg.img_h, self.cfg.img_w), error=RuntimeError, in_place=True)
 
-    def _forward(self, frames, out, mask, centers=None):
+    def _forward(self, frames, out, mask, centers=None, spread=False):
         """The forward of checked frames (a _native.Frames) with a checked mask (_native.camera_mask) or None, and
-        checked centres (_native.centers) or None = detect."""
+        checked centres (_native.centers) or None = detect.  spread: the call runs the spread form and its Spread3D
+        follows the three outputs."""
         dev = frames.device
+        self.set_spread(spread)
         if centers is not None or self._centred:
             self.set_centers(centers)
         if out is None:
@@ -142,7 +187,7 @@ class NativePredictor:
         N.call_forward("jh_predictor", self.handle, frames, mask, out)
         if mask is not None and mask.is_cuda:
             mask.record_stream(torch.cuda.current_stream())     # (free once the call is enqueued)
-        return out
+        return tuple(out) + (self.spread(),) if spread else out
 
     # ---- camera-sharded stages -------------------------------------------
     def stage_center(self, frames, det):
@@ -337,9 +382,10 @@ class MultiStreamPredictor:
         self._calib_of[i] = (self._calib, self._calib_refs)       # the tensors live as long as their key is compared
 
     def forward(self, frames, out=None, then=None, frame_format=None, camera_mask=None, return_2d=False,
-                frame_layout=None, centers=None):
+                frame_layout=None, centers=None, return_spread=False):
         """return_2d: the five tensors of NativePredictor.views2d for this batch are appended to the outputs
         (points, conf, valid, points2D, confidences2D, reprojections, errors, used).
+        return_spread: the three tensors of the batch's Spread3D (cov (T,J,3,3), peak, mass) are appended behind them.
         `then(outputs)`, when given, runs inside the batch's stream context right behind the forward and
         before its event is recorded (the drivers enqueue the device->host copy of the results there); its
         return value replaces the outputs.  frame_format, camera_mask, frame_layout: as NativePredictor.forward.
@@ -362,9 +408,13 @@ class MultiStreamPredictor:
             t.record_stream(s)
         with torch.cuda.stream(s):
             self._frames_calibration(i)
-            res = self.preds[i]._forward(described, out, camera_mask, centers)
+            res = self.preds[i]._forward(described, out, camera_mask, centers, return_spread)
+            if return_spread:
+                res, spread = res[:3], tuple(res[3])
             if return_2d:
                 res = tuple(res) + tuple(self.preds[i].views2d(res[0], camera_mask=camera_mask))
+            if return_spread:
+                res = tuple(res) + spread
             if then is not None:
                 res = then(res)
             ev = torch.cuda.Event(enable_timing=self.timing)

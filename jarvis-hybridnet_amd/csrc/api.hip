@@ -77,6 +77,13 @@ static size_t carve_softargmax(Carver& c, int t, int joints, int gh, SoftWs* w) 
   w->pmax = c.take<int>((size_t)t * w->x.Cp);
   return c.off;
 }
+// the spread form's sums and keys: one piece (launch_softargmax zeroes it with one launch)
+static size_t carve_spread(Carver& c, int t, int Jp, SoftargmaxSpread* sp) {
+  const size_t n = softargmax_spread_sums(t, Jp);
+  sp->sums = c.take<double>(n + (size_t)t * Jp);
+  sp->key = sp->sums ? reinterpret_cast<unsigned long long*>(sp->sums + n) : nullptr;
+  return c.off;
+}
 struct ReconWs { float* det; int *c3i, *chm, *valid; };
 static size_t carve_reconstruct(Carver& c, int cams, ReconWs* w) {
   w->det = c.take<float>((size_t)cams * 3);
@@ -252,6 +259,33 @@ int jh_softargmax(const float* v2v_out_dev, int t, int joints, int gh, float gri
   if (launch_to_channel_last(v2v_out_dev, w.x, s)) return 1;
   return launch_softargmax(w.x.p, center3d_dev, w.partial, w.pmax, points_dev, conf_dev,
                            heatmap_final_dev, t, joints, w.x.Cp, gh, grid_spacing, roi_cube_size, s);
+}
+
+int64_t jh_softargmax_spread_workspace_bytes(int t, int joints, int gh) {
+  Carver c(nullptr, 0);
+  SoftWs w;
+  SoftargmaxSpread sp;
+  carve_softargmax(c, t, joints, gh, &w);
+  return (int64_t)carve_spread(c, t, w.x.Cp, &sp);
+}
+
+int jh_softargmax_spread(const float* v2v_out_dev, int t, int joints, int gh, float grid_spacing,
+                         float roi_cube_size, const int32_t* center3d_dev, float* heatmap_final_dev,
+                         float* points_dev, float* conf_dev, float* cov_dev, float* peak_dev, float* mass_dev,
+                         void* workspace_dev, int64_t workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(workspace_dev && workspace_bytes >= 0, "workspace (see jh_softargmax_spread_workspace_bytes)");
+  JH_REQUIRE(cov_dev && peak_dev && mass_dev, "jh_softargmax_spread: null output pointer");
+  Carver c(workspace_dev, (size_t)workspace_bytes);
+  SoftWs w;
+  SoftargmaxSpread sp;
+  carve_softargmax(c, t, joints, gh, &w);
+  carve_spread(c, t, w.x.Cp, &sp);
+  JH_REQUIRE(c.fits(), "workspace smaller than jh_softargmax_spread_workspace_bytes()");
+  sp.cov = cov_dev; sp.peak = peak_dev; sp.mass = mass_dev;
+  if (launch_to_channel_last(v2v_out_dev, w.x, s)) return 1;
+  return launch_softargmax(w.x.p, center3d_dev, w.partial, w.pmax, points_dev, conf_dev,
+                           heatmap_final_dev, t, joints, w.x.Cp, gh, grid_spacing, roi_cube_size, s, &sp);
 }
 
 int jh_reproject_point(const float* points_dev, int npoints, int cams, const float* cam_dev,
@@ -490,13 +524,15 @@ struct jh_predictor {
   // [2 * kGraphFmts + ...]: the same again for the per-image form, which has slots of its OWN -- a stream of
   // per-image calls and a stream of contiguous calls of one format never re-record each other; [4 * kGraphFmts + ...]:
   // all of these again for the forward from caller-supplied centres (centers_on), which records no stage 1 -- a
-  // tracking loop that falls back to one detected call between centred ones never re-records.  A launch
+  // tracking loop that falls back to one detected call between centred ones never re-records; [8 * kGraphFmts + ...]:
+  // all sixteen again for the spread form of the tail (spread_on), which is another recording -- a loop that
+  // alternates spread-on and spread-off calls never re-records either.  A launch
   // carries its source's description by value, so a recording has ONE source: the slot keeps the FrameSource its
   // graph was captured with, and a call with another one records again (forward_graph).  The same holds for the
   // calibration's form: a recording holds the pointers and the frame stride (calib_fs) it was captured with.
   static constexpr int kGraphFmts = kSrcSensor + 1;
   struct GraphSlot { hipGraphExec_t exec = nullptr; FrameSource src; int calib_fs = 0; };
-  GraphSlot gslot[8 * kGraphFmts];
+  GraphSlot gslot[16 * kGraphFmts];
   // Camera mask (camera_mask.h).  mask_buf [T][C]: the predictor's copy of the current call's mask -- the masked
   // kernels (and a captured graph of them) read this buffer, so the mask may change from call to call.  mask_cur:
   // the mask of the call under way, nullptr = no mask (the plain kernels).  n_active / n_detect [T]: written by
@@ -514,6 +550,14 @@ struct jh_predictor {
   // by the first such call, so a predictor that never asks for 2D views owns what it always did
   float* v2d_max = nullptr;
   int* v2d_idx = nullptr;
+  // Per-joint 3D spread (jh_predictor_set_spread).  spread_on: run_3d launches the spread form of the soft-argmax tail,
+  // which writes rows t0 .. t0+T3-1 of sp_cov (T,J,6), sp_peak (T,J,3) and sp_mass (T,J); spread.sums / .key: its
+  // accumulators for one 3D chunk.  All of it ONE allocation of spread_bytes, made by the first enabling call: a
+  // predictor that never asks owns, and launches, what it always did.
+  bool spread_on = false;
+  SoftargmaxSpread spread;
+  float *sp_cov = nullptr, *sp_peak = nullptr, *sp_mass = nullptr;
+  size_t spread_bytes = 0;
   ~jh_predictor() {
     for (auto& g : gslot) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (gstream) (void)hipStreamDestroy(gstream);
@@ -539,6 +583,15 @@ struct jh_predictor {
                              /*heat_pad=*/0, /*div255=*/1, s, layout));
     }
     if (v2v->run(s)) return 1;
+    if (spread_on) {
+      SoftargmaxSpread sp = spread;
+      sp.valid = valid_cur() + t0;
+      sp.cov = sp_cov + (size_t)t0 * J * 6; sp.peak = sp_peak + (size_t)t0 * J * 3; sp.mass = sp_mass + (size_t)t0 * J;
+      JH_PROF("softargmax_spread", 0.0, 4.0 * T3 * (g3 / 8) * J,
+              launch_softargmax(v2v->output.p, c3i_cur() + t0 * 3, sa_partial, sa_max, points, conf,
+                                heatmap_final, T3, J, Jp, Gh, cfg.grid_spacing, cfg.roi_cube_size, s, &sp));
+      return 0;
+    }
     JH_PROF("softargmax", 0.0, 4.0 * T3 * (g3 / 8) * J,
             launch_softargmax(v2v->output.p, c3i_cur() + t0 * 3, sa_partial, sa_max, points, conf,
                               heatmap_final, T3, J, Jp, Gh, cfg.grid_spacing, cfg.roi_cube_size, s));
@@ -654,7 +707,7 @@ int jh_predictor_precision(const jh_predictor* pr) { return pr ? pr->cfg.precisi
 
 int64_t jh_predictor_device_bytes(const jh_predictor* pr) {
   return (int64_t)((pr->center ? pr->center->device_bytes() : 0) + pr->kp->device_bytes() +
-                   pr->v2v->device_bytes());
+                   pr->v2v->device_bytes() + pr->spread_bytes);
 }
 
 int jh_predictor_set_calibration(jh_predictor* pr, const float* cam_dev, const float* intr_dev,
@@ -710,6 +763,45 @@ int jh_predictor_set_centers(jh_predictor* pr, const float* centers_dev, void* s
                               s));
   pr->centers_on = true;
   return 0;
+}
+
+int jh_predictor_set_spread(jh_predictor* pr, int on) {
+  JH_REQUIRE(pr, "jh_predictor_set_spread: null predictor");
+  if (on && !pr->sp_cov) {
+    // (allocates and clears: not inside a stream capture -- the call has no stream to ask, the allocation itself
+    // fails there)
+    const size_t T = pr->T, J = pr->J, Jp = pr->Jp;
+    const size_t nsum = softargmax_spread_sums(pr->T3, pr->Jp), nkey = (size_t)pr->T3 * Jp;
+    const size_t bytes = (nsum + nkey) * sizeof(double) + T * J * 10 * sizeof(float);
+    char* base = nullptr;
+    if (pr->mem.get(reinterpret_cast<void**>(&base), bytes)) return 1;
+    JH_CHECK_HIP(hipMemset(base, 0, bytes));
+    pr->spread.sums = reinterpret_cast<double*>(base);
+    pr->spread.key = reinterpret_cast<unsigned long long*>(pr->spread.sums + nsum);
+    float* f = reinterpret_cast<float*>(pr->spread.key + nkey);
+    pr->sp_peak = f + T * J * 6;
+    pr->sp_mass = f + T * J * 9;
+    pr->sp_cov = f;
+    pr->spread_bytes = bytes;
+  }
+  pr->spread_on = on != 0;
+  return 0;
+}
+
+int jh_predictor_get_spread(jh_predictor* pr, float* cov_dev, float* peak_dev, float* mass_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(pr, "jh_predictor_get_spread: null predictor");
+  JH_REQUIRE(pr->sp_cov, "jh_predictor_get_spread: the spread was never enabled (jh_predictor_set_spread)");
+  const size_t n = (size_t)pr->T * pr->J * sizeof(float);
+  if (cov_dev) JH_CHECK_HIP(hipMemcpyAsync(cov_dev, pr->sp_cov, n * 6, hipMemcpyDeviceToDevice, s));
+  if (peak_dev) JH_CHECK_HIP(hipMemcpyAsync(peak_dev, pr->sp_peak, n * 3, hipMemcpyDeviceToDevice, s));
+  if (mass_dev) JH_CHECK_HIP(hipMemcpyAsync(mass_dev, pr->sp_mass, n, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+int jh_predictor_debug_v2v(jh_predictor* pr, float* out_dev, void* stream) {
+  JH_REQUIRE(pr && out_dev, "jh_predictor_debug_v2v: null pointer");
+  return launch_from_channel_last(pr->v2v->output, out_dev, static_cast<hipStream_t>(stream));
 }
 
 static int stage_center_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* det_dev,
@@ -875,7 +967,8 @@ static int forward_graph(jh_predictor* pr, const void* frames_dev, const FrameSo
                          float* conf_dev, int32_t* valid_dev, hipStream_t s) {
   jh_predictor::GraphSlot& slot = pr->gslot[fs.fmt + (pr->mask_cur ? jh_predictor::kGraphFmts : 0) +
                                             (fs.per_image ? 2 * jh_predictor::kGraphFmts : 0) +
-                                            (pr->centers_on ? 4 * jh_predictor::kGraphFmts : 0)];
+                                            (pr->centers_on ? 4 * jh_predictor::kGraphFmts : 0) +
+                                            (pr->spread_on ? 8 * jh_predictor::kGraphFmts : 0)];
   // the recorded launches hold the description they were captured with: another one records again (rare: a stream
   // keeps its layout, and a fixed format has nothing to differ in; the replay in flight is waited for before its
   // executable graph goes).  Likewise the calibration's form, shared or per frame: its pointers and frame stride are

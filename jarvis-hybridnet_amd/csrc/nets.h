@@ -48,9 +48,20 @@ int launch_centers(const float* centers, const float* cam, const float* intr, co
                    const unsigned char* mask, int* n_active, int* n_detect, hipStream_t s);
 int launch_project_points(const float* pts, const float* cam, const float* intr, const float* dist,
                           float* uv, int P, int C, hipStream_t s);
+// The spread form of the soft-argmax tail (geometry.hip): workspace and outputs of T frame sets.
+// sums: softargmax_spread_sums(T, Jp) doubles with T * Jp 64-bit keys right behind them (`key`), one allocation;
+// valid: [T] validity flags (rows of a frame set that is not valid are NaN) or nullptr = all valid;
+// cov [T][J][6] (xx, xy, xz, yy, yz, zz; mm^2), peak [T][J][3] (mm), mass [T][J].
+struct SoftargmaxSpread {
+  double* sums = nullptr;
+  unsigned long long* key = nullptr;
+  const int* valid = nullptr;
+  float *cov = nullptr, *peak = nullptr, *mass = nullptr;
+};
+size_t softargmax_spread_sums(int T, int Jp);
 int launch_softargmax(const float* x, const int* center3d, double* partial, int* pmax,
                       float* points, float* conf, float* heatmap_final, int T, int J, int Jp,
-                      int Gh, float spacing, float roi, hipStream_t s);
+                      int Gh, float spacing, float roi, hipStream_t s, const SoftargmaxSpread* spread = nullptr);
 
 typedef std::map<std::string, std::vector<float>> ParamMap;
 

@@ -124,10 +124,11 @@ class ShardedPredictor:
             ev.record()
             self.trace.append((label, ev))
 
-    def step(self, frames_local, frame_format=None, camera_mask=None, return_2d=False, frame_layout=None):
+    def step(self, frames_local, frame_format=None, camera_mask=None, return_2d=False, frame_layout=None,
+             return_spread=False):
         """frames_local (T, Cloc, 3, H, W) -> points (T,J,3), conf (T,J), valid (T).  camera_mask, frame_layout:
-        None only; return_2d: False only."""
-        self.submit(frames_local, frame_format, camera_mask, return_2d, frame_layout)
+        None only; return_2d, return_spread: False only."""
+        self.submit(frames_local, frame_format, camera_mask, return_2d, frame_layout, return_spread)
         return self.flush()
 
     # ---- pipelined form: the bulk exchange of time batch i runs under the CenterDetect
@@ -135,11 +136,16 @@ class ShardedPredictor:
     # centres the 3D stage of batch i still needs).  Order of one submit():
     #     stage_center(i+1) || exchange(i)  ->  stage_3d(i) [second stream] || stage_keypoints(i+1)
     #     -> exchange(i+1) started asynchronously once stage_3d(i) has let go of the receive buffer
-    def submit(self, frames_local, frame_format=None, camera_mask=None, return_2d=False, frame_layout=None):
+    def submit(self, frames_local, frame_format=None, camera_mask=None, return_2d=False, frame_layout=None,
+               return_spread=False):
         """Start time batch i+1; returns the results of batch i (None on the first call).  frame_format: None or
         'bgr' only -- the camera-sharded stages take fp32 RGB or uint8 BGR frames, not YUV 4:2:0.  camera_mask: None
         only -- per-frame camera masks are a single-GPU feature.  return_2d: False only -- so are the per-camera 2D views.
-        frame_layout: None only -- so are described YUV surfaces and raw sensor surfaces."""
+        frame_layout: None only -- so are described YUV surfaces and raw sensor surfaces.  return_spread: False only --
+        so is the per-joint 3D spread."""
+        if return_spread:
+            raise ValueError("the camera-sharded path does not return the per-joint 3D spread: use "
+                             "JarvisPredictor3D.forward_batch(..., return_spread=True) on one GPU")
         if frame_layout is not None:
             raise ValueError("the camera-sharded path does not take a frame_layout (it would misread the surfaces "
                              "as BGR): use JarvisPredictor3D.forward_batch(..., frame_layout=...) on one GPU")

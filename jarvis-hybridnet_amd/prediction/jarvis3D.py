@@ -134,7 +134,7 @@ class JarvisPredictor3D(nn.Module):
         return None if m is None else m.unsqueeze(0)
 
     def forward(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None,
-                return_2d=False, centers=None):
+                return_2d=False, centers=None, return_spread=False):
         """imgs (C,3,H,W) RGB in [0,1] -> (points3D (1,J,3), confidences (1,J)) or (None, None).
         return_2d: a third element, the per-camera `Views2D` of this frame set (leading dimension 1: 2D keypoints of
         every camera from the heat maps this forward computed anyway, the reprojections of the 3D keypoints and
@@ -152,7 +152,12 @@ class JarvisPredictor3D(nn.Module):
         frames, calibration and mask (native(...).debug("cuda")["center3d"]) gives that call's result bit for bit.
         A device tensor computed from the previous result costs no host synchronisation.  None: detect, as always.
         (weights_center_detect=None builds CenterDetect with its initial weights, as it always did; a predictor whose
-        every call brings centres never runs it.)"""
+        every call brings centres never runs it.)
+        return_spread: a further element behind Views2D, (points3D, confidences[, views][, spread]): the `Spread3D` of
+        the frame set (leading dimension 1), or None with the others.  Per joint, of the normalised heat map
+        softplus(V2V output) whose mean is the keypoint: cov (1,J,3,3) its covariance in mm^2 from fp64 sums, peak
+        (1,J,3) the voxel of its maximum in mm (the mode: |peak - point| beyond the spread means a multi-modal map),
+        mass (1,J) its sum.  points3D and confidences keep their bits."""
         mask = self._frame_mask(camera_mask)
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(imgs, (self.num_cameras,))
@@ -160,9 +165,9 @@ class JarvisPredictor3D(nn.Module):
         self.reproTool.intrinsicMatrices = intrinsicMatrices
         self.reproTool.distortionCoefficients = distortionCoefficients
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers)
+                         centers, return_spread)
 
-    def _run(self, frames, calib, mask, return_2d, single=False, centers=None):
+    def _run(self, frames, calib, mask, return_2d, single=False, centers=None, return_spread=False):
         """The forward of checked frames (a _native.Frames; single: one frame set, lead (C,)) with a checked mask and
         checked centres (_native.centers for the frames' time batch, or None), on the native predictor of their size:
         nothing of the predictor is touched before this."""
@@ -175,7 +180,8 @@ class JarvisPredictor3D(nn.Module):
             per_frame = N.calibration(tuple(calib), frames.lead[0], self.num_cameras)[0] == "frames"
         pr = self.native(frames.height, frames.width, time_batch=frames.lead[0])
         (pr.set_calibration_frames if per_frame else pr.set_calibration)(*calib)
-        res = pr._forward(frames, None, mask, centers)
+        # (return_spread decides for this call alone: the native predictor sets its flag, on or off, before it runs)
+        res = pr._forward(frames, None, mask, centers, *((True,) if return_spread else ()))
         return self._single(pr, res, mask, return_2d) if single else self._batch(pr, res, mask, return_2d)
 
     @staticmethod
@@ -186,54 +192,57 @@ class JarvisPredictor3D(nn.Module):
         Views2D are HybridNet's own 2D detections, on the crop around the projection of the TRIANGULATED centre;
         JarvisPredictor2D crops around each camera's own centre detection.  The two agree wherever the crops cover
         the subject; they are not bit-equal."""
-        points, conf, valid = res
-        views = pr.views2d(points, camera_mask=mask) if return_2d else None
+        points, conf, valid = res[:3]
+        extra = ((pr.views2d(points, camera_mask=mask),) if return_2d else ()) + tuple(res[3:])
         if int(valid[0].item()) == 0:
-            return (None, None, None) if return_2d else (None, None)
-        return (points, conf, views) if return_2d else (points, conf)
+            return (None, None) + (None,) * len(extra)
+        return (points, conf) + extra
 
     def forward_uint8(self, imgs_bgr, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None,
-                      return_2d=False, centers=None):
+                      return_2d=False, centers=None, return_spread=False):
         """imgs_bgr (C,H,W,3) uint8 BGR exactly as the video decoder delivers them
         (predict3D.py:72-78).  Same result as forward() on
         `imgs_bgr.float().permute(0,3,1,2)[:, [2,1,0]] / 255.` (predict3D.py:79-80); the
-        conversion runs inside the resize / crop kernels.  camera_mask, return_2d, centers: as forward()."""
+        conversion runs inside the resize / crop kernels.  camera_mask, return_2d, centers, return_spread: as
+        forward() -- the Spread3D (covariance in mm^2, peak voxel in mm and mass of every joint's heat map) comes last."""
         mask = self._frame_mask(camera_mask)
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(imgs_bgr, (self.num_cameras,), "bgr")
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers)
+                         centers, return_spread)
 
     def forward_yuv(self, frames, frame_format, cameraMatrices, intrinsicMatrices, distortionCoefficients,
-                    camera_mask=None, return_2d=False, centers=None):
+                    camera_mask=None, return_2d=False, centers=None, return_spread=False):
         """frames (C,3H/2,W) uint8 YUV 4:2:0 as video decoders produce them natively, frame_format 'i420'
         (FFmpeg yuv420p: Y, U, V planes) or 'nv12' (Y plane, interleaved UV plane); H and W even.  Same result,
         bit for bit, as forward_uint8 on the BGR bytes of cv2.cvtColor(COLOR_YUV2BGR_I420 / _NV12) of each
         image (BT.601 limited range); the conversion runs inside the resize / crop kernels.
-        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d, centers: as forward()."""
+        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d, centers, return_spread: as
+        forward() -- the Spread3D (covariance in mm^2, peak voxel in mm and mass of every joint's heat map) comes last."""
         mask = self._frame_mask(camera_mask)
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(frames, (self.num_cameras,), N.yuv_format(frame_format))
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers)
+                         centers, return_spread)
 
     def forward_surface(self, frames, surface, cameraMatrices, intrinsicMatrices, distortionCoefficients,
-                        camera_mask=None, return_2d=False, centers=None):
+                        camera_mask=None, return_2d=False, centers=None, return_spread=False):
         """frames (C,image_stride) uint8: one YUV 4:2:0 image per camera, read in place through the YuvSurface
         `surface` (pitched decoder surfaces, I420 / YV12 / NV12 / NV21, BT.601 / BT.709, limited / full range), or one
         raw sensor image per camera through the SensorSurface `surface` (Mono8, or an 8-bit Bayer mosaic demosaiced
         bilinearly on the GPU; pitched buffers with a header in front likewise).
         Same result, bit for bit, as forward_uint8 on the BGR bytes the surface's conversion gives
         (include/jarvis_hip.h); bytes outside the planes are never read.
-        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d, centers: as forward()."""
+        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d, centers, return_spread: as
+        forward() -- the Spread3D (covariance in mm^2, peak voxel in mm and mass of every joint's heat map) comes last."""
         mask = self._frame_mask(camera_mask)
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(frames, (self.num_cameras,), None, N.surface(surface))
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers)
+                         centers, return_spread)
 
     def forward_batch(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
-                      camera_mask=None, return_2d=False, frame_layout=None, centers=None):
+                      camera_mask=None, return_2d=False, frame_layout=None, centers=None, return_spread=False):
         """Throughput form: imgs (T,C,3,H,W) fp32 RGB or (T,C,H,W,3) uint8 BGR,
         independent time steps -> points (T,J,3), confidences (T,J), valid (T) int32;
         no host synchronisation.  frame_format 'i420' / 'nv12': imgs (T,C,3H/2,W) uint8 YUV 4:2:0 (see
@@ -257,7 +266,11 @@ class JarvisPredictor3D(nn.Module):
         camera of row t is left); rows are independent.  Centres taken from a detected run of the same batch
         (native(...).debug("cuda")["center3d"]) give that run bit for bit -- points, confidences, valid and the 2D
         views -- wherever it is valid.  It composes with camera_mask, return_2d, every frame format and per-frame-set
-        calibration (row t's centre is projected with row t's calibration).  None: detect."""
+        calibration (row t's centre is projected with row t's calibration).  None: detect.
+        return_spread: the `Spread3D` of the batch comes last, (points, confidences, valid[, views], spread): per joint
+        the covariance cov (T,J,3,3) in mm^2 of the normalised heat map softplus(V2V output) (fp64 sums, rounded once),
+        the voxel of its maximum peak (T,J,3) in mm and its sum mass (T,J); NaN rows where valid[t] = 0.  The other
+        outputs keep their bits; it composes with everything above."""
         if centers is not None:
             if not torch.is_tensor(imgs) or imgs.dim() < 1:
                 raise ValueError("imgs must be a tensor of time steps")
@@ -268,10 +281,11 @@ class JarvisPredictor3D(nn.Module):
             camera_mask = N.camera_mask(camera_mask, (imgs.shape[0], self.num_cameras))
         frames = N.describe_frames(imgs, (None, self.num_cameras), frame_format, frame_layout)
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d,
-                         centers=centers)
+                         centers=centers, return_spread=return_spread)
 
     def forward_images(self, images, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
-                       frame_layout=None, camera_mask=None, return_2d=False, centers=None):
+                       frame_layout=None, camera_mask=None, return_2d=False, centers=None,
+                       return_spread=False):
         """forward_batch on images that lie where their producers left them: `images` a sequence of C tensors (one
         frame set) or a sequence of T such sequences, each tensor ONE image -- fp32 (3,H,W); uint8 (H,W,3);
         frame_format 'i420' / 'nv12': uint8 (3H/2,W); frame_layout (a YuvSurface or a SensorSurface): 1-D uint8 of at
@@ -283,7 +297,9 @@ class JarvisPredictor3D(nn.Module):
         synchronisation.  camera_mask (T,C), return_2d: as forward_batch.  Calibration: shared (C,...) or one per frame
         set (T,C,...), as forward_batch.
         centers (T,3): as forward_batch.  With the same images in several rows and one centre per row, the rows of a
-        batch are different subjects seen in the same frames (a detected batch finds the strongest one in every row)."""
+        batch are different subjects seen in the same frames (a detected batch finds the strongest one in every row).
+        return_spread: as forward_batch -- the Spread3D of the batch (covariance in mm^2, peak voxel in mm and mass of
+        every joint's heat map) comes last."""
         if isinstance(images, (list, tuple)) and len(images) > 0 and torch.is_tensor(images[0]):
             images = [images]
         if not isinstance(images, (list, tuple)) or len(images) == 0:
@@ -299,8 +315,9 @@ class JarvisPredictor3D(nn.Module):
         frames = N.frame_images(flat, (T, self.num_cameras), frame_format, frame_layout)
         camera_mask = N.camera_mask(camera_mask, (T, self.num_cameras))
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d,
-                         centers=N.centers(centers, T))
+                         centers=N.centers(centers, T), return_spread=return_spread)
 
     @staticmethod
     def _batch(pr, res, mask, return_2d):
-        return tuple(res) + (pr.views2d(res[0], camera_mask=mask),) if return_2d else res
+        # (points, conf, valid[, views][, spread]): the Spread3D, when asked for, is res[3]
+        return tuple(res[:3]) + (pr.views2d(res[0], camera_mask=mask),) + tuple(res[3:]) if return_2d else res

@@ -65,6 +65,30 @@ def frame_row(points3D, confidences, num_joints):
     return row
 
 
+SPREAD_COLUMNS = ("cxx", "cxy", "cxz", "cyy", "cyz", "czz", "px", "py", "pz")
+
+
+def spread_row(cov, peak, num_joints):
+    """One row of spread3D.csv from a frame set's slice of a `Spread3D`: cov (J,3,3) mm^2, peak (J,3) mm ->
+    [cxx, cxy, cxz, cyy, cyz, czz, px, py, pz] per joint as numpy float32 elements (the element type of the
+    confidences in data3D.csv), or 'NaN' x 9J when the frame set is invalid (cov None)."""
+    if cov is None:
+        return ["NaN"] * (num_joints * len(SPREAD_COLUMNS))
+    cov = cov.detach().cpu().float().reshape(num_joints, 9).numpy()
+    peak = peak.detach().cpu().float().reshape(num_joints, 3).numpy()
+    row = []
+    for c, p in zip(cov, peak):
+        row = row + [c[0], c[1], c[2], c[4], c[5], c[8]] + list(p)
+    return row
+
+
+def create_header_spread(writer, cfg):
+    """Two header rows: every joint name nine times, then SPREAD_COLUMNS per joint."""
+    names = list(cfg.KEYPOINT_NAMES)
+    writer.writerow(list(itertools.chain.from_iterable(itertools.repeat(x, len(SPREAD_COLUMNS)) for x in names)))
+    writer.writerow(list(SPREAD_COLUMNS) * len(names))
+
+
 def views2d_row(points2D, confidences2D, used, num_joints):
     """One row of a camera's data2D_<name>.csv from its slice of a frame set's `Views2D`: points2D (J,2),
     confidences2D (J): predict2D.frame_row of the same numbers ([x, y, confidence] per joint), or 'NaN' x 3J when
@@ -93,7 +117,7 @@ def create_header_reprojection_error(writer, cfg, camera_names):
 def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                      distortionCoefficients, cfg, output_dir, params=None, time_batch=1, streams=1,
                      frame_spec=None, frame_format="bgr", camera_mask=None, output_2d=False, camera_names=None,
-                     frame_layout=None, centers=None):
+                     frame_layout=None, centers=None, output_spread=False):
     """Run `predictor` over an iterable of multi-view frame sets -- (C,H,W,3) uint8 BGR
     arrays / tensors exactly as cv2 delivers them, or (C,3,H,W) fp32 RGB -- and write
     data3D.csv (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -161,7 +185,13 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     gives that frame set a 'NaN' row; the rows of the others are those of a detected run that found these centres,
     byte for byte.  A wrong shape, and an iterable that ends before the frame sets do, or after, raise ValueError.  The
     padding rows of a short last group repeat the last centre.  It composes with camera_mask, output_2d, frame_format,
-    frame_layout, time_batch and streams; the CSV and info.yaml formats do not change."""
+    frame_layout, time_batch and streams; the CSV and info.yaml formats do not change.
+
+    output_spread: also write `spread3D.csv` beside data3D.csv (which, like info.yaml, is byte-identical with and
+    without the option): one row per frame set, per joint the six covariance entries of its 3D heat map in mm^2 and the
+    voxel of its maximum in mm -- cxx,cxy,cxz,cyy,cyz,czz,px,py,pz (JarvisPredictor3D.forward_batch(...,
+    return_spread=True); rows of spread_row, the header of create_header_spread when data3D.csv gets its header) --,
+    'NaN' x 9J for an invalid frame set.  It composes with time_batch, streams, camera_mask, centers and output_2d."""
     import contextlib
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
     yuv = driver_format(frame_format, frame_spec, 3, frame_layout)
@@ -209,14 +239,22 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                 for w in writers_2d:
                     create_header_2d(w, cfg)
                 create_header_reprojection_error(writer_err, cfg, camera_names)
+        writer_spread = None
+        if output_spread:
+            writer_spread = open_csv("spread3D.csv")
+            if len(names) == J:
+                create_header_spread(writer_spread, cfg)
 
         def emit(outs, real):
             pts, conf, valid = outs[:3]
             for t in range(real):
                 ok = int(valid[t]) != 0
                 writer.writerow(frame_row(pts[t] if ok else None, conf[t] if ok else None, J))
+                if output_spread:
+                    cov, peak = outs[-3], outs[-2]
+                    writer_spread.writerow(spread_row(cov[t] if ok else None, peak[t] if ok else None, J))
                 if output_2d:
-                    p2d, c2d, _, err, used = outs[3:]
+                    p2d, c2d, _, err, used = outs[3:8]
                     for c, w in enumerate(writers_2d):
                         w.writerow(views2d_row(p2d[t, c], c2d[t, c], used[t, c], J))
                     writer_err.writerow(reprojection_error_row(err[t]))
@@ -229,6 +267,8 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                 kw["centers"] = centers
             if output_2d:
                 kw["return_2d"] = True
+            if output_spread:
+                kw["return_spread"] = True
             if frame_layout is not None:
                 kw["frame_layout"] = frame_layout
             if hasattr(predictor, "native_streams"):
@@ -242,8 +282,10 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             # any object with the batch interface
             res = predictor.forward_batch(x, *calib, frame_format=frame_format, **kw) if yuv else \
                 predictor.forward_batch(x, *calib, **kw)
+            if output_spread:
+                res = tuple(res[:-1]) + tuple(res[-1])         # (..., Spread3D) -> its three tensors, last
             if output_2d:
-                res = tuple(res[:3]) + tuple(res[3])           # (points, conf, valid, Views2D) -> eight tensors
+                res = tuple(res[:3]) + tuple(res[3]) + tuple(res[4:])     # (points, conf, valid, Views2D, ...) -> tensors
             ev = None
             if x.is_cuda:
                 res = host_outputs(ring, slot, res)
