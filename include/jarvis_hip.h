@@ -592,7 +592,8 @@ int jh_profile_get(int i, char* name, int name_cap, double* ms, double* flops, d
  * ((Cout,Cin,k..) or, transposed, (Cin,Cout,k..)); kind 0 = conv (k, stride,
  * pad), 1 = ConvTranspose2d k4 s2 p1, 2 = ConvTranspose3d k2 s2.  When
  * norm_act >= 0 the InstanceNorm (+ activation 0 none / 1 relu / 2 silu) that
- * follows the conv in the networks is applied from the fused statistics. */
+ * follows the conv in the networks is applied from the fused statistics.  The layer takes the kernel form the network
+ * plans give it (jh_conv_form below, at the process-wide precision). */
 int jh_op_conv(int nd, int kind, int k, int stride, int pad, int cin, int cout,
                const float* w_host, const float* b_host, const float* x_dev, int n, int d, int h,
                int w, const float* gate_dev, int norm_act, float* y_dev, void* stream);
@@ -600,6 +601,14 @@ int jh_op_conv(int nd, int kind, int k, int stride, int pad, int cin, int cout,
  * JH_DECONV4_WINDOW=0 at weight-packing time selects the four-parity forms) by this process so far -- how a test tells
  * which form ran.  Under hipGraph capture it counts captures, not replays. */
 long jh_deconv4_window_launches(void);
+/* Which kernel form a convolution layer takes (no GPU needed; csrc/conv_layer.h): the layer as jh_op_conv describes it,
+ * used with / without bias, fused statistics and a gate (0 none, 1 tensor, 2 recipe) at precision 0 / 1 / 2
+ * (jh_predictor_config::precision); in_px: floats per input pixel in memory, 0 = cin rounded up to 8.  Reads JH_WINO,
+ * JH_WINO_PW and JH_DECONV4_WINDOW as they stand at the call, as making a layer does.  name receives "mfma" (+ "_paired"
+ * / "_tappair" / "_window": the weight layout), "wino", "wino_bf16x3", "conv_bf16x3", "deconv4_bf16x3" or "deconv_c1". */
+int jh_conv_form(int nd, int kind, int k, int stride, int pad, int cin, int cout, int has_bias,
+                 int want_stats, int gate /*0 none, 1 tensor, 2 recipe*/, int precision,
+                 int in_px /*0: cpad(cin)*/, char* name, int name_cap);
 /* TEST-ONLY: the operand transform a consumer applies while it stages its input (csrc/jh_common.h: InNorm, SeGate),
  * described from the host so that only the consumer is under test. */
 typedef struct jh_op_operand {

@@ -1353,6 +1353,22 @@ int jh_profile_get(int i, char* name, int name_cap, double* ms, double* flops, d
 // -------------------------------------------------------- single-operator tests
 long jh_deconv4_window_launches(void) { return deconv4_window_launches(); }
 
+int jh_conv_form(int nd, int kind, int k, int stride, int pad, int cin, int cout, int has_bias, int want_stats,
+                 int gate, int precision, int in_px, char* name, int name_cap) {
+  JH_REQUIRE((nd == 2 || nd == 3) && kind >= 0 && kind <= 2 && k >= 1 && stride >= 1 && pad >= 0 && cin >= 1 &&
+             cout >= 1 && gate >= 0 && gate <= 2 && precision >= 0 && precision <= 2 && in_px >= 0 && name &&
+             name_cap > 0, "jh_conv_form: bad argument");
+  ConvUse use;
+  use.desc = kind == 0 ? conv_desc(nd, k, stride, pad, cin, cout)
+                       : (kind == 1 ? deconv2d_k4s2p1_desc(cin, cout) : deconv3d_k2s2_desc(cin, cout));
+  use.transposed = kind != 0; use.has_bias = has_bias != 0; use.want_stats = want_stats != 0;
+  use.gate = static_cast<ConvGate>(gate);
+  use.precision = precision;
+  use.in_px = in_px;
+  snprintf(name, (size_t)name_cap, "%s", conv_choice_name(choose_conv(use)).c_str());
+  return 0;
+}
+
 // Host (n, c, 2) sums / sums of squares -> [N][Cp][kStatW]: the whole value in the first limb of each (exact_read then
 // returns exactly the given double), pad channels zero.
 static int op_upload_stats(Scratch& sc, const double* sums_host, int n, int c, int Cp, double** dev) {
@@ -1382,20 +1398,18 @@ static int op_upload_se(Scratch& sc, const double* pool_host, int n, int C, int 
   return 0;
 }
 
-// One convolution through the choices Plan::add_conv makes (Winograd, bf16x3 levels, JH_* knobs): the body of jh_op_conv
-// (opd == nullptr: operand as it is, optional norm_apply behind the conv) and of jh_op_conv_operand (opd: the operand
-// transform of the consumer -- InstanceNorm + activation from host statistics, gate tensor or recipe -- raw output).
+// One convolution as a ConvLayer (csrc/conv_layer.h), the way Plan::add_conv runs it (kernel form by choose_conv, at the
+// process-wide precision): the body of jh_op_conv (opd == nullptr: operand as it is, optional norm_apply behind the conv)
+// and of jh_op_conv_operand (opd: the operand transform of the consumer -- InstanceNorm + activation from host
+// statistics, gate tensor or recipe -- raw output).
 static int op_conv_body(int nd, int kind, int k, int stride, int pad, int cin, int cout, const float* w_host,
                         const float* b_host, const float* x_dev, int n, int d, int h, int w, const float* gate_dev,
                         int norm_act, const jh_op_operand* opd, float* y_dev, hipStream_t s, const char* who) {
-  struct Weights { ConvWeights cw; ~Weights() { free_conv_weights(&cw); } } wt;
-  ConvWeights& cw = wt.cw;
   const bool recipe = opd && opd->se_pool_host;
   const bool want_stats = opd ? opd->want_stats != 0 : norm_act >= 0;
-  ConvDesc desc = kind == 0 ? conv_desc(nd, k, stride, pad, cin, cout)
-                            : (kind == 1 ? deconv2d_k4s2p1_desc(cin, cout) : deconv3d_k2s2_desc(cin, cout));
-  desc.latency_class = opd ? opd->latency_class : 0;
-  desc.plain_out = !want_stats && !gate_dev && !recipe;
+  const bool plain_out = !want_stats && !gate_dev && !recipe;
+  const ConvDesc desc = kind == 0 ? conv_desc(nd, k, stride, pad, cin, cout)
+                                  : (kind == 1 ? deconv2d_k4s2p1_desc(cin, cout) : deconv3d_k2s2_desc(cin, cout));
   Scratch sc;
   Act x, y;
   if (nd == 2) d = 1;
@@ -1406,34 +1420,15 @@ static int op_conv_body(int nd, int kind, int k, int stride, int pad, int cin, i
   // (a plain ConvTranspose2d -- no statistics, no InstanceNorm behind it -- starts from NaN instead: an output element
   //  that no workgroup stores then reaches the caller as NaN; pad channels are not copied out.  The fill exists for the
   //  exactly-once-stores check of tests/test_hip_deconv4_window.py)
-  JH_CHECK_HIP(hipMemsetAsync(y.p, kind == 1 && desc.plain_out ? 0xFF : 0, y.bytes(), s));
-  // the same choice the V2V plan makes: 3x3x3 stride-1 convs run as Winograd (JH_WINO=0: direct)
-  bool wino = kind == 0 && nd == 3 && k == 3 && stride == 1 && pad == 1 && !gate_dev;
-  if (const char* e = getenv("JH_WINO")) wino = wino && atoi(e) != 0;
-  // the CenterDetect head, one output channel: the vector-ALU kernel (EffTrackPlan::build)
-  const bool c1 = opd && kind == 1 && cout == 1 && !b_host && !want_stats && !gate_dev && !recipe;
-  const bool b3 = wino && precision_mode() >= 1;         // the same choices the plans make
-  const bool d4b = !c1 && kind == 1 && !b_host && !want_stats && !gate_dev && !recipe && precision_mode() >= 1 &&
-                   deconv4_bf16x3_eligible(cout);
-  const bool xb = kind == 0 && !wino && !gate_dev && !recipe && conv_bf16x3_eligible(desc) && x.Cp == cpad(cin) &&
-                  (precision_mode() == 2 || (precision_mode() == 1 && nd == 3));
-  float* w_c1 = nullptr;
-  if (c1) {               // [16 taps][Cp], as EffTrackPlan::build repacks deconv1.weight
-    std::vector<float> t16((size_t)16 * x.Cp, 0.f);
-    for (int c = 0; c < cin; ++c)
-      for (int t = 0; t < 16; ++t) t16[(size_t)t * x.Cp + c] = w_host[(size_t)c * 16 + t];
-    if (op_upload(sc, t16.data(), t16.size(), &w_c1)) return 1;
-  } else if (xb) {
-    if (pack_conv_bf16x3_weights(desc, w_host, b_host, &cw)) return 1;
-  } else if (d4b) {
-    if (pack_deconv4_bf16x3_weights(cin, cout, w_host, &cw)) return 1;
-  } else if (b3) {
-    if (pack_bf16x3_weights(cin, cout, w_host, b_host, &cw)) return 1;
-  } else if (wino) {
-    if (pack_wino_weights(cin, cout, w_host, b_host, &cw)) return 1;
-  } else {
-    if (pack_conv_weights(desc, w_host, b_host, kind != 0, &cw)) return 1;
-  }
+  JH_CHECK_HIP(hipMemsetAsync(y.p, kind == 1 && plain_out ? 0xFF : 0, y.bytes(), s));
+  ConvUse use;
+  use.desc = desc; use.desc.latency_class = opd ? opd->latency_class : 0;
+  use.transposed = kind != 0; use.has_bias = b_host != nullptr; use.want_stats = want_stats;
+  use.gate = recipe ? ConvGate::Recipe : (gate_dev ? ConvGate::Tensor : ConvGate::None);
+  use.precision = precision_mode();
+  use.in_px = x.Cp;
+  ConvLayer layer;
+  if (make_conv_layer(use, w_host, b_host, y.D, y.H, y.W, &layer)) return 1;
   double* stats = nullptr;
   float* gate_p = nullptr;
   if (want_stats) {
@@ -1458,14 +1453,8 @@ static int op_conv_body(int nd, int kind, int k, int stride, int pad, int cin, i
     if (op_upload_se(sc, opd->se_pool_host, n, opd->se_c, x.Cp, opd->se_s, opd->se_inv_hw, opd->se_wr_host,
                      opd->se_br_host, opd->se_we_host, opd->se_be_host, &se)) return 1;
   }
-  const InNorm* inp = in.stats ? &in : nullptr;
   if (launch_to_channel_last(x_dev, x, s)) return 1;
-  if (c1) { if (launch_deconv_c1(x, in.stats, in.inv, in.act, w_c1, y, s)) return 1; }
-  else if (xb) { if (launch_conv_bf16x3(desc, cw, x, y, stats, s, inp)) return 1; }
-  else if (d4b) { if (launch_deconv4_bf16x3(cw, x, y, s, inp)) return 1; }
-  else if (b3) { if (launch_conv3d_bf16x3(cw, x, y, stats, s, inp)) return 1; }
-  else if (wino) { if (launch_conv3d_wino(cw, x, y, stats, s, inp, wino_variant_from_env())) return 1; }
-  else if (launch_conv(desc, cw, x, y, gate_p, stats, s, inp, recipe ? &se : nullptr)) return 1;
+  if (layer.launch(x, y, gate_p, stats, in, recipe ? &se : nullptr, s)) return 1;
   if (!opd && norm_act >= 0 && launch_norm_apply(y, stats, 1e-5, norm_act, nullptr, nullptr, y.p, nullptr, s)) return 1;
   if (launch_from_channel_last(y, y_dev, s)) return 1;
   if (hipStreamSynchronize(s) != hipSuccess) { set_error(std::string("stream sync failed in ") + who); return 1; }
@@ -1549,12 +1538,9 @@ int jh_op_depthwise(int k, int c, const float* w_host, const float* x_dev, int n
   Act x, y;
   if (sc.act(n, 1, h, w, c, &x)) return 1;
   if (sc.act(n, 1, h, w, c, &y)) return 1;
-  std::vector<float> wt((size_t)k * k * x.Cp, 0.f);
-  for (int ch = 0; ch < c; ++ch)
-    for (int t = 0; t < k * k; ++t) wt[(size_t)t * x.Cp + ch] = w_host[(size_t)ch * k * k + t];
+  const std::vector<float> wt = taps_major(w_host, c, k * k, x.Cp);
   float* wd; double* stats = nullptr;
-  if (sc.get(reinterpret_cast<void**>(&wd), wt.size() * sizeof(float))) return 1;
-  JH_CHECK_HIP(hipMemcpyAsync(wd, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  if (op_upload(sc, wt.data(), wt.size(), &wd)) return 1;
   if (norm_act >= 0) {
     if (sc.get(reinterpret_cast<void**>(&stats), (size_t)n * x.Cp * kStatW * sizeof(double))) return 1;
     JH_CHECK_HIP(hipMemsetAsync(stats, 0, (size_t)n * x.Cp * kStatW * sizeof(double), s));
@@ -1609,12 +1595,9 @@ int jh_op_depthwise_pool(int k, int c, const float* w_host, const float* x_dev, 
   Act x, y;
   if (sc.act(n, 1, h, w, c, &x)) return 1;
   if (sc.act(n, 1, h, w, c, &y)) return 1;
-  std::vector<float> wt((size_t)k * k * x.Cp, 0.f);
-  for (int ch = 0; ch < c; ++ch)
-    for (int t = 0; t < k * k; ++t) wt[(size_t)t * x.Cp + ch] = w_host[(size_t)ch * k * k + t];
+  const std::vector<float> wt = taps_major(w_host, c, k * k, x.Cp);
   float* wd; double *stats = nullptr, *pool = nullptr;
-  if (sc.get(reinterpret_cast<void**>(&wd), wt.size() * sizeof(float))) return 1;
-  JH_CHECK_HIP(hipMemcpyAsync(wd, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  if (op_upload(sc, wt.data(), wt.size(), &wd)) return 1;
   const size_t nst = (size_t)n * x.Cp * kStatW, npl = (size_t)n * x.Cp * kLimbs;
   if (sc.get(reinterpret_cast<void**>(&stats), nst * sizeof(double))) return 1;
   if (sc.get(reinterpret_cast<void**>(&pool), npl * sizeof(double))) return 1;
@@ -1717,14 +1700,11 @@ int jh_op_bifpn_node(int n_in, const int* modes, const float* weights, int act, 
   if (sc.act(n, 1, h, w, cout, &y)) return 1;
   JH_CHECK_HIP(hipMemsetAsync(y.p, 0, y.bytes(), s));
   const int Cp = in[0].Cp;
-  std::vector<float> dwt((size_t)9 * Cp, 0.f);
-  for (int ch = 0; ch < c; ++ch)
-    for (int t = 0; t < 9; ++t) dwt[(size_t)t * Cp + ch] = dw_host[(size_t)ch * 9 + t];
+  const std::vector<float> dwt = taps_major(dw_host, c, 9, Cp);
   float* dwd;
-  if (sc.get(reinterpret_cast<void**>(&dwd), dwt.size() * sizeof(float))) return 1;
-  JH_CHECK_HIP(hipMemcpyAsync(dwd, dwt.data(), dwt.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  if (op_upload(sc, dwt.data(), dwt.size(), &dwd)) return 1;
   ConvWeights cw;
-  if (pack_conv_weights(conv_desc(2, 1, 1, 0, c, cout), pw_host, bias_host, false, &cw)) return 1;
+  if (pack_conv_weights(conv_desc(2, 1, 1, 0, c, cout), pw_host, bias_host, false, WeightLayout::Plain, &cw)) return 1;
   double* ost;
   int rc = 0;
   do {

@@ -23,7 +23,6 @@
 // producer applied on load, exactly as the fp32 kernels do.  Weights are split and packed on the
 // host into per-lane B-operand order (one coalesced 1 KB read per slice, column block and half).
 // Epilogue = the fp32 kernels' (bias, fused statistics, 16-byte channel-last stores).
-#include <cstring>
 #include "conv_mfma.h"
 
 namespace jh {
@@ -185,19 +184,6 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_kernel(B3Args a) {
   conv_epilogue<TY, NCB, TY, TX, 4, false>(acc, e, red, nb0, oz0, oy0, ox0, tid);
 }
 
-static inline unsigned short bf16_rne(float f) {
-  unsigned u;
-  std::memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-static inline float bf16_to_f32(unsigned short h) {
-  unsigned u = (unsigned)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
 // torch layout (cout, cin, 3, 3, 3) -> [chunk][slice][cout block][hi, lo][lane][8] bf16:
 // lane = (K group g) * 16 + (cout % 16); element e of K group g = tap 2 slice + (g >> 1),
 // input channel 16 chunk + 8 (g & 1) + e
@@ -221,18 +207,7 @@ int pack_bf16x3_weights(int cin, int cout, const float* w, const float* b, ConvW
             packed[base + 512] = lo;
           }
   out->cin_p = cin_p; out->cout_p16 = cout_p16; out->phase_stride = packed.size() / 2;   // (in floats)
-  void* dev = nullptr;
-  JH_CHECK_HIP(hipMalloc(&dev, packed.size() * sizeof(unsigned short)));
-  JH_CHECK_HIP(hipMemcpy(dev, packed.data(), packed.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-  out->w = static_cast<float*>(dev);
-  out->bias = nullptr;
-  if (b) {
-    std::vector<float> bp(cout_p16, 0.f);
-    for (int i = 0; i < cout; ++i) bp[i] = b[i];
-    JH_CHECK_HIP(hipMalloc(&out->bias, bp.size() * sizeof(float)));
-    JH_CHECK_HIP(hipMemcpy(out->bias, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  return 0;
+  return upload_conv_weights(packed.data(), packed.size() * sizeof(unsigned short), b, cout, out);
 }
 
 template <int NCB>

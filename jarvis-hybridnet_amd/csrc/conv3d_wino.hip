@@ -18,10 +18,6 @@
 // partial sums cross waves through LDS (A^T along y mixes fy, i.e. waves), wave w finishes
 // z-slice w and hands its four (oy, ox) output phases to the shared epilogue (bias, 16-byte
 // stores, fused InstanceNorm statistics).
-#include <array>
-#include <cstdlib>
-#include <map>
-#include <mutex>
 #include <vector>
 #include "conv_mfma.h"
 #include "conv3d_wino.h"
@@ -364,24 +360,7 @@ int pack_wino_weights(int cin, int cout, const float* w, const float* b, ConvWei
           }
       }
   out->cin_p = cin_p; out->cout_p16 = cout_p16; out->phase_stride = packed.size();
-  JH_CHECK_HIP(hipMalloc(&out->w, packed.size() * sizeof(float)));
-  JH_CHECK_HIP(hipMemcpy(out->w, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-  out->bias = nullptr;
-  if (b) {
-    std::vector<float> bp(cout_p16, 0.f);
-    for (int i = 0; i < cout; ++i) bp[i] = b[i];
-    JH_CHECK_HIP(hipMalloc(&out->bias, bp.size() * sizeof(float)));
-    JH_CHECK_HIP(hipMemcpy(out->bias, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  return 0;
-}
-
-// variant: 4 = persistent wave-specialised form (conv3d_wino_pw.hip; the default -- it falls
-// back to variant 0 for launches with fewer than two tiles per CU or fewer than three channel
-// passes), 0 = one role per workgroup (JH_WINO_PW=0)
-int wino_variant_from_env() {
-  if (const char* e = getenv("JH_WINO_PW")) { if (atoi(e) == 0) return 0; }
-  return 4;
+  return upload_conv_weights(packed.data(), packed.size() * sizeof(float), b, cout, out);
 }
 
 // Host side of the persistent kernel's tables (conv3d_wino.h): the loader's per-shape patch tables (the tiles themselves
@@ -431,22 +410,7 @@ int launch_conv3d_wino(const ConvWeights& w, const Act& x, const Act& y, double*
   // tile a launch the same way, so their per-block fp32 partial sums of the statistics agree bit for bit
   a.tiling = wino_tiling(x.D, x.H, x.W, tz);
   const bool sh = a.tiling.shaped != 0;
-  if (sh && variant == 4 && !tables) {
-    // callers outside a network plan (the op-level test entry only; plans pass their own tables, so this allocation
-    // never runs under stream capture): one 5 KB table per (device, volume, channel padding), built on first use
-    static std::mutex mu;
-    static std::map<std::array<int, 5>, int*> cache;
-    std::lock_guard<std::mutex> lock(mu);
-    int device = 0;
-    JH_CHECK_HIP(hipGetDevice(&device));
-    int*& dev = cache[{device, x.D, x.H, x.W, x.Cp}];
-    if (!dev) {
-      const std::vector<int> host = wino_tables(x.D, x.H, x.W, x.Cp);
-      JH_CHECK_HIP(hipMalloc(&dev, host.size() * sizeof(int)));
-      JH_CHECK_HIP(hipMemcpy(dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
-    tables = dev;
-  }
+  JH_REQUIRE(!(sh && variant == 4) || tables, "persistent Winograd form on a volume with remainder strips: no tables");
   a.shape_tab = tables;
   if (variant == 4) {
     const int rc = launch_conv3d_wino_pw(a, nr_full, s);

@@ -9,19 +9,6 @@ template <> int launch_xconv_ncb<2, 3, 2, 1, 16, 1>(const XArgs&, hipStream_t);
 template <> int launch_xconv_ncb<2, 3, 1, 1, 16, 1>(const XArgs&, hipStream_t);
 template <> int launch_xconv_ncb<2, 3, 1, 1, 16, 2>(const XArgs&, hipStream_t);
 
-static inline unsigned short x_bf16_rne(float f) {
-  unsigned u;
-  std::memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-static inline float x_bf16_f32(unsigned short h) {
-  unsigned u = (unsigned)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
 // which (nd, k, stride) have a split-bf16 kernel, and with which channel chunk
 static int xconv_ch8(const ConvDesc& d) {
   const int cin_p = cpad(d.cin);
@@ -52,24 +39,13 @@ int pack_conv_bf16x3_weights(const ConvDesc& d, const float* w, const float* b, 
             const int tap = s * tps + g / ch8, ci = chunk * chk + (g % ch8) * 8 + e;
             if (tap >= ntap || ci >= d.cin || co >= d.cout) continue;
             const float v = w[((size_t)co * d.cin + ci) * ntap + tap];
-            const unsigned short hi = x_bf16_rne(v), lo = x_bf16_rne(v - x_bf16_f32(hi));
+            const unsigned short hi = bf16_rne(v), lo = bf16_rne(v - bf16_to_f32(hi));
             const size_t base = ((((size_t)chunk * nsl + s) * ncbt + cb) * 2) * 512 + (size_t)lane * 8 + e;
             packed[base] = hi;
             packed[base + 512] = lo;
           }
   out->cin_p = cin_p; out->cout_p16 = cout_p16; out->phase_stride = packed.size() / 2;
-  void* dev = nullptr;
-  JH_CHECK_HIP(hipMalloc(&dev, packed.size() * sizeof(unsigned short)));
-  JH_CHECK_HIP(hipMemcpy(dev, packed.data(), packed.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-  out->w = static_cast<float*>(dev);
-  out->bias = nullptr;
-  if (b) {
-    std::vector<float> bp(cout_p16, 0.f);
-    for (int i = 0; i < d.cout; ++i) bp[i] = b[i];
-    JH_CHECK_HIP(hipMalloc(&out->bias, bp.size() * sizeof(float)));
-    JH_CHECK_HIP(hipMemcpy(out->bias, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  return 0;
+  return upload_conv_weights(packed.data(), packed.size() * sizeof(unsigned short), b, d.cout, out);
 }
 
 int launch_conv_bf16x3(const ConvDesc& d, const ConvWeights& w, const Act& x, const Act& y, double* stats,

@@ -1,7 +1,6 @@
 // Host side of the MFMA convolution: descriptors, weight packing, dispatch.
 #include <vector>
 #include <cstring>
-#include <cstdlib>
 #include <algorithm>
 #include "conv_mfma.h"
 
@@ -60,7 +59,7 @@ void conv_out_shape(const ConvDesc& d, int D, int H, int W, int* Do, int* Ho, in
 static inline int deconv4_tap(int parity, int t) { return parity ? (t == 0 ? 2 : 0) : (t == 0 ? 3 : 1); }
 
 int pack_conv_weights(const ConvDesc& d, const float* w, const float* b, bool transposed,
-                      ConvWeights* out) {
+                      WeightLayout layout, ConvWeights* out) {
   const int cin_p = cpad(d.cin);
   const int cout_p16 = round_up(d.cout, 16);
   const int kd = (d.nd == 3) ? d.k : 1;
@@ -68,19 +67,11 @@ int pack_conv_weights(const ConvDesc& d, const float* w, const float* b, bool tr
   const int nk8 = cin_p / 8, nb = cout_p16 / 16;
   const size_t phase_stride = (size_t)ntap * nk8 * nb * 128;
   std::vector<float> packed(phase_stride * d.nphase, 0.f);
-  // kernels that read both operands 16 bytes at a time want two 8-channel steps per lane word
-  // ConvTranspose2d k4 s2 p1 without statistics and gate: the window form of csrc/deconv4.hip, one 2 x 2 convolution
-  // over the 4 cout_p columns (output sub-position, channel) of a window (JH_DECONV4_WINDOW=0: the four-parity forms)
+  // (which layout a layer takes: conv_weight_layout, csrc/conv_layer.hip)
+  const bool window = layout == WeightLayout::Window, paired = layout == WeightLayout::ChannelPaired;
+  const bool tap_paired = layout == WeightLayout::TapPaired;
   const int cout_p = cpad(d.cout);
-  // (=2: also the layers of 8 column blocks in either form, cout 25..32 -- the measurement knob of DESIGN 3.8a)
-  int wmode = 1;
-  if (const char* e = getenv("JH_DECONV4_WINDOW")) wmode = atoi(e);
-  const bool window = d.nd == 2 && d.ostride > 1 && d.plain_out && wmode != 0 &&
-                      deconv4_window_eligible(cin_p, cout_p, wmode >= 2);
   const int npair = (nk8 + 1) / 2, nbw = (4 * cout_p + 15) / 16;
-  const bool paired = !window && d.nd == 2 && d.ostride > 1 && deconv4_eligible(cin_p, cout_p16);
-  // stride-2 3D convs: two taps per 16-byte weight word (conv_mfma.h, TAPPAIR)
-  const bool tap_paired = d.nd == 3 && d.k == 3 && d.stride == 2 && d.ostride == 1;
   if (tap_paired) packed.assign((size_t)((ntap + 1) / 2) * nk8 * nb * 256, 0.f);
   if (window) packed.assign((size_t)ntap * npair * nbw * 256, 0.f);
   // geometry of the source tensor
@@ -126,17 +117,21 @@ int pack_conv_weights(const ConvDesc& d, const float* w, const float* b, bool tr
             }
         }
   }
-  out->cin_p = cin_p; out->cout_p16 = cout_p16; out->paired = tap_paired ? 2 : (window ? 3 : (paired ? 1 : 0));
+  out->cin_p = cin_p; out->cout_p16 = cout_p16; out->layout = layout;
   out->phase_stride = tap_paired ? packed.size() : (window ? packed.size() / d.nphase : phase_stride);
-  JH_CHECK_HIP(hipMalloc(&out->w, packed.size() * sizeof(float)));
-  JH_CHECK_HIP(hipMemcpy(out->w, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+  return upload_conv_weights(packed.data(), packed.size() * sizeof(float), b, d.cout, out);
+}
+
+// The tail of every weight packer: device copies of the packed weights and of the bias, zero-padded to out->cout_p16.
+int upload_conv_weights(const void* packed, size_t bytes, const float* b, int cout, ConvWeights* out) {
   out->bias = nullptr;
-  if (b) {
-    std::vector<float> bp(cout_p16, 0.f);
-    std::memcpy(bp.data(), b, d.cout * sizeof(float));
-    JH_CHECK_HIP(hipMalloc(&out->bias, bp.size() * sizeof(float)));
-    JH_CHECK_HIP(hipMemcpy(out->bias, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
+  JH_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&out->w), bytes));
+  JH_CHECK_HIP(hipMemcpy(out->w, packed, bytes, hipMemcpyHostToDevice));
+  if (!b) return 0;
+  std::vector<float> bp(out->cout_p16, 0.f);
+  std::memcpy(bp.data(), b, cout * sizeof(float));
+  JH_CHECK_HIP(hipMalloc(&out->bias, bp.size() * sizeof(float)));
+  JH_CHECK_HIP(hipMemcpy(out->bias, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -191,7 +186,7 @@ int launch_conv(const ConvDesc& d, const ConvWeights& w, const Act& x, const Act
   }
   a.N = x.N; a.Din = x.D; a.Hin = x.H; a.Win = x.W; a.cin_p = w.cin_p; a.in_px = x.Cp;
   a.Dy = y.D; a.Hy = y.H; a.Wy = y.W; a.cout_p = y.Cp; a.cout_p16 = w.cout_p16;
-  a.ostride = d.ostride; a.nphase = d.nphase; a.phase_stride = w.phase_stride; a.paired = w.paired;
+  a.ostride = d.ostride; a.nphase = d.nphase; a.phase_stride = w.phase_stride; a.layout = w.layout;
   for (int p = 0; p < d.nphase; ++p) a.phase[p] = d.phase[p];
   if (d.ostride > 1) { a.Dout = x.D; a.Hout = x.H; a.Wout = x.W; }
   else conv_out_shape(d, x.D, x.H, x.W, &a.Dout, &a.Hout, &a.Wout);
@@ -208,17 +203,12 @@ int launch_conv(const ConvDesc& d, const ConvWeights& w, const Act& x, const Act
   // LDS budget of the staged channel chunk (pick_kc8): 40 KB -- three to four workgroups per CU for the k5 / k4T
   // layers -- measured against 72 KB (two): k5s2 16->96 308 -> 287 us, head ConvTranspose 954 -> 928 us
   const size_t budget = kConvLdsBudget;
-  if (a.paired == 3) {                                // packed for the window form: nothing else reads that layout
-    JH_REQUIRE(d.nd == 2 && d.ostride == 2 && d.k == 2 && !stats && !gate && !(se && se->pool),
-               "window-form weights on a layer with statistics or a gate");
-    return launch_deconv4_window(a, s);
+  // the two layouts that one kernel alone reads (csrc/deconv4.hip; each checks the launch against its form)
+  switch (w.layout) {
+    case WeightLayout::Window: return launch_deconv4_window(a, s);
+    case WeightLayout::ChannelPaired: return launch_deconv4_fused(a, s);     // all four parities from one staged patch
+    case WeightLayout::TapPaired: case WeightLayout::Plain: break;
   }
-  if (d.nd == 2 && d.ostride == 2 && d.k == 2) {      // all four parities from one staged patch
-    const int rc = launch_deconv4_fused(a, s);
-    if (rc >= 0) return rc;
-  }
-  JH_REQUIRE((a.paired == 2) == (d.nd == 3 && d.k == 3 && d.stride == 2 && d.ostride == 1) && a.paired != 1,
-             "paired weight layout without a kernel that reads it");
   if (conv_pw_direct_eligible(d, a)) return launch_conv_pw_direct(a, s);
   if (d.nd == 2) {
     const int small = (a.Wout <= 8) ? 1 : 0;

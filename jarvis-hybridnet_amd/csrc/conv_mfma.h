@@ -779,10 +779,10 @@ int launch_conv_geom(const ConvArgs& a, int nr, size_t lds_budget, hipStream_t s
 bool conv_pw_direct_eligible(const ConvDesc& d, const ConvArgs& a);
 int launch_conv_pw_direct(const ConvArgs& a, hipStream_t s);
 
-// ConvTranspose2d k4 s2 p1 with the four parities in one workgroup (csrc/deconv4.hip); -1: not its layer
+// ConvTranspose2d k4 s2 p1 with the four parities in one workgroup (csrc/deconv4.hip; WeightLayout::ChannelPaired)
 int launch_deconv4_fused(const ConvArgs& a, hipStream_t s);
 bool deconv4_eligible(int cin_p, int cout_p16);
-// ... and its window form for layers without statistics and gate (weights packed as ConvWeights::paired == 3)
+// ... and its window form for layers without statistics and gate (weights packed as WeightLayout::Window)
 int launch_deconv4_window(const ConvArgs& a, hipStream_t s);
 bool deconv4_window_eligible(int cin_p, int cout_p, bool wide);
 

@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void conv_pw_direct_kernel(const ConvArgs a, i
 // partial sums differently): this kernel therefore takes the squeeze-excite gate in BOTH forms the plan uses -- a tensor,
 // or the recipe the general kernel evaluates in its prologue for small batches.
 bool conv_pw_direct_eligible(const ConvDesc& d, const ConvArgs& a) {
-  if (d.nd != 2 || d.k != 1 || d.stride != 1 || d.ostride != 1 || d.nphase != 1 || a.paired) return false;
+  if (d.nd != 2 || d.k != 1 || d.stride != 1 || d.ostride != 1 || d.nphase != 1 || a.layout != WeightLayout::Plain) return false;
   if (a.se.pool && (a.se.C > 64 || a.se.S > 64)) return false;
   if (a.cin_p > 48 || a.in_px != a.cin_p) return false;
   const int nb = a.cout_p16 / 16;

@@ -21,7 +21,7 @@
 // global load ~36 cycles of issue whatever its width (tools/mfma_valu_coissue.hip), against 32 per
 // MFMA, so both operands are read 16 bytes at a time: the patch keeps the channels of two
 // consecutive 8-channel steps interleaved per lane quarter ([kq][step parity][2]), the weights are
-// packed as [tap][step pair][column block][lane][4] (pack_conv_weights, ConvWeights::paired) --
+// packed as [tap][step pair][column block][lane][4] (WeightLayout::ChannelPaired) --
 // one ds_read_b128 / global_load_dwordx4 feeds four MFMAs instead of two.
 //
 // WINDOW FORM (deconv4_window_kernel, layers without fused statistics and without a gate: the
@@ -564,7 +564,7 @@ static int launch_deconv4_window_inst(const ConvArgs& a, hipStream_t s) {
 
 int launch_deconv4_window(const ConvArgs& a, hipStream_t s) {
   const int nb = (4 * a.cout_p + 15) / 16, kc8 = deconv4_window_kc8(a.cin_p);
-  JH_REQUIRE(a.paired == 3 && a.nphase == 4 && !a.stats && !a.gate && !a.se.pool &&
+  JH_REQUIRE(a.layout == WeightLayout::Window && a.nphase == 4 && !a.stats && !a.gate && !a.se.pool &&
              deconv4_window_eligible(a.cin_p, a.cout_p, true), "not a layer of the window form");
   JH_REQUIRE((long)a.Hin * a.Win * a.in_px < (1L << 29) && (long)a.Hy * a.Wy * a.cout_p < (1L << 31),
              "image too large for the window form's 32-bit offsets");
@@ -581,11 +581,11 @@ bool deconv4_eligible(int cin_p, int cout_p16) {
   return cout_p16 <= 32 && cin_p % 16 == 0;
 }
 
-// Returns -1 when the layer is not this kernel's (the caller then takes the general path).
 int launch_deconv4_fused(const ConvArgs& a, hipStream_t s) {
   const int nrp = a.cout_p16 / 16;
-  if (a.gate || nrp > 2 || a.nphase != 4) return -1;
-  if (!a.paired) return -1;                        // (pack_conv_weights decided with deconv4_eligible)
+  // (conv_weight_layout, csrc/conv_layer.hip, decided with deconv4_eligible)
+  JH_REQUIRE(a.layout == WeightLayout::ChannelPaired && !a.gate && nrp <= 2 && a.nphase == 4,
+             "not a layer of the fused four-parity kernel");
   const int kc8 = a.cin_p % 32 == 0 ? 4 : 2;
   if (nrp == 2 && kc8 == 4) return launch_deconv4_inst<2, 4>(a, s);
   if (nrp == 2 && kc8 == 2) return launch_deconv4_inst<2, 2>(a, s);

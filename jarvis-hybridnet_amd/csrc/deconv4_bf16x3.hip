@@ -10,7 +10,6 @@
 // one v_mfma_f32_16x16x32_bf16 step, three MFMAs per step (hi hi + lo hi + hi lo, fp32 accumulation).
 // Row, tap-row, chunk and plane offsets of the A reads are compile-time immediates; the parity only
 // moves the lane base.  Operands are requested one step ahead (see conv3d_bf16x3.hip).
-#include <cstring>
 #include "conv_mfma.h"
 
 namespace jh {
@@ -156,18 +155,6 @@ __global__ __launch_bounds__(256) void deconv4_bf16x3_kernel(D4Args a) {
   conv_epilogue<TY, NCB, TY, TX, 1, false>(acc, e, nullptr, 0, 0, oy0, ox0, lane);
 }
 
-static inline unsigned short d4_bf16_rne(float f) {
-  unsigned u;
-  std::memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-static inline float d4_bf16_f32(unsigned short h) {
-  unsigned u = (unsigned)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
 // kernel tap that feeds tap t of parity par (conv_host.hip: deconv4_tap)
 static inline int d4_tap(int par, int t) { return par ? (t == 0 ? 2 : 0) : (t == 0 ? 3 : 1); }
 
@@ -187,18 +174,13 @@ int pack_deconv4_bf16x3_weights(int cin, int cout, const float* w, ConvWeights* 
               if (ci >= cin || co >= cout) continue;
               const int ky = d4_tap(ph >> 1, ta), kx = d4_tap(ph & 1, tb);
               const float v = w[(((size_t)ci * cout + co) * 4 + ky) * 4 + kx];
-              const unsigned short hi = d4_bf16_rne(v), lo = d4_bf16_rne(v - d4_bf16_f32(hi));
+              const unsigned short hi = bf16_rne(v), lo = bf16_rne(v - bf16_to_f32(hi));
               const size_t base = ((((size_t)(ph * nchunk + chunk) * 2 + ta) * ncb + cb) * 2) * 512 + (size_t)lane * 8 + e;
               packed[base] = hi;
               packed[base + 512] = lo;
             }
   out->cin_p = cin_p; out->cout_p16 = cout_p16; out->phase_stride = packed.size() / 2;
-  void* dev = nullptr;
-  JH_CHECK_HIP(hipMalloc(&dev, packed.size() * sizeof(unsigned short)));
-  JH_CHECK_HIP(hipMemcpy(dev, packed.data(), packed.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-  out->w = static_cast<float*>(dev);
-  out->bias = nullptr;
-  return 0;
+  return upload_conv_weights(packed.data(), packed.size() * sizeof(unsigned short), nullptr, 0, out);
 }
 
 bool deconv4_bf16x3_eligible(int cout) { const int ncb = round_up(cout, 16) / 16; return ncb == 1 || ncb == 2; }

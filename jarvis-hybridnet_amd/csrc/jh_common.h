@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -96,16 +97,22 @@ struct ConvDesc {
   int cin, cout;
   int latency_class;   // 1: the plan belongs to the single-frame-set class (time batch < 8): tile forms that trade
                        // workgroups for fill (the whole-image tile) stay off.  A function of the class, never of the batch.
-  int plain_out;       // 1: every launch of the layer runs without fused statistics and without a gate (set by whoever
-                       // packs the weights): a ConvTranspose2d k4 s2 p1 may then take the window form (csrc/deconv4.hip)
+};
+
+// How pack_conv_weights() lays the MFMA form's weights out; which one a layer takes is decided in csrc/conv_layer.hip.
+enum class WeightLayout : int {
+  Plain = 0,          // [phase][tap][cin_p/8][cout_p16/16][64][2]
+  ChannelPaired = 1,  // [phase][tap][cin_p/16][cout_p16/16][64][4]: two 8-channel steps per 16-byte lane word (the
+                      // fused four-parity kernel of csrc/deconv4.hip reads its operands as b128)
+  TapPaired = 2,      // two taps per word (stride-2 3D convs)
+  Window = 3,         // the window form of ConvTranspose2d k4 s2 p1 (csrc/deconv4.hip):
+                      // [window tap][ceil(cin_p/16)][ceil(4 cout_p/16)][64][4] with columns sub * cout_p + channel
 };
 
 // Packed weights of one conv (all phases), see pack_conv_weights().
 struct ConvWeights {
-  float* w = nullptr;      // [phase][tap][cin_p/8][cout_p16/16][64][2]; paired: [phase][tap][cin_p/16][cout_p16/16][64][4]
-  int paired = 0;          // 1: two 8-channel steps per 16-byte lane word (kernels that read operands as b128);
-                           // 2: two taps per word (stride-2 3D convs); 3: the window form of ConvTranspose2d k4 s2 p1,
-                           // [window tap][ceil(cin_p/16)][ceil(4 cout_p/16)][64][4] with columns sub * cout_p + channel
+  float* w = nullptr;
+  WeightLayout layout = WeightLayout::Plain;
   float* bias = nullptr;   // [cout_p16] or nullptr
   size_t phase_stride = 0; // floats
   int cin_p = 0, cout_p16 = 0;
@@ -158,16 +165,18 @@ struct ConvArgs {
   int in_px;             // floats per input pixel in memory: cin_p, or 4 for the 3-channel network
                          // input (one float4 per pixel; channels 4.. of the K padding read 0)
   int ostride, nphase;
-  int paired = 0;        // layout of the weights (ConvWeights::paired)
+  WeightLayout layout = WeightLayout::Plain;   // of the weights (ConvWeights::layout)
   FastDiv fgx, fgy, ftx, fty;   // divisors: grid x / y, tiles per row / column (set by the launcher)
   size_t phase_stride;
   ConvPhase phase[8];
 };
 
 // host-side repack: torch layout (cout, cin, k..) [transposed: (cin, cout, k..)]
-// -> ConvWeights device buffers.  Returns 0 on success.
+// -> ConvWeights device buffers in the given layout.  Returns 0 on success.
 int pack_conv_weights(const ConvDesc& d, const float* w_host, const float* b_host,
-                      bool transposed, ConvWeights* out);
+                      bool transposed, WeightLayout layout, ConvWeights* out);
+// the tail of every pack_*_weights: packed bytes -> out->w, b (cout floats or nullptr) -> out->bias [out->cout_p16]
+int upload_conv_weights(const void* packed, size_t bytes, const float* b, int cout, ConvWeights* out);
 void free_conv_weights(ConvWeights* w);
 
 // InstanceNorm (+ activation) of the conv INPUT, applied while the patch is staged: the
@@ -353,10 +362,25 @@ __device__ __forceinline__ float silu_fast(float v) { return v * __builtin_amdgc
 struct NodeArgs;
 int launch_bifpn_node(const NodeArgs& a, hipStream_t s);
 int pack_wino_weights(int cin, int cout, const float* w, const float* b, ConvWeights* out);
-int wino_variant_from_env();
-// tables: the persistent kernel's tables for this launch shape (wino_tables, uploaded by the plan) or nullptr
+// variant: 4 = persistent wave-specialised form (conv3d_wino_pw.hip; it falls back to variant 0 for launches with
+// fewer than two tiles per CU or fewer than three channel passes), 0 = one role per workgroup
+// tables: the persistent kernel's tables for this launch shape (wino_tables, uploaded by the layer); nullptr for a
+// volume without remainder strips
 int launch_conv3d_wino(const ConvWeights& w, const Act& x, const Act& y, double* stats, hipStream_t s,
-                       const InNorm* in, int variant = 4, const int* tables = nullptr);
+                       const InNorm* in, int variant, const int* tables);
+// The weight split of the bf16x3 kernels (host side): hi = bf16_rne(v), lo = bf16_rne(v - bf16_to_f32(hi)).
+inline unsigned short bf16_rne(float f) {
+  unsigned u;
+  std::memcpy(&u, &f, 4);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (unsigned short)(u >> 16);
+}
+inline float bf16_to_f32(unsigned short h) {
+  const unsigned u = (unsigned)h << 16;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
 // split-bf16 form of the same convolution (csrc/conv3d_bf16x3.hip; precision mode bf16x3)
 int pack_bf16x3_weights(int cin, int cout, const float* w, const float* b, ConvWeights* out);
 int launch_conv3d_bf16x3(const ConvWeights& w, const Act& x, const Act& y, double* stats, hipStream_t s,

@@ -5,11 +5,13 @@
 // flat list of kernel launches on one stream with no host synchronisation and
 // no allocation, so a caller may capture it into a hipGraph.
 #pragma once
+#include <deque>
 #include <functional>
 #include <map>
 #include <string>
 #include <vector>
 #include "jh_common.h"
+#include "conv_layer.h"
 #include "preprocess.h"
 
 namespace jh {
@@ -97,7 +99,8 @@ class Plan {
     ops_.push_back(Op{std::move(fn), name, flops, bytes});
   }
   std::vector<void*> owned_;
-  std::vector<ConvWeights> convs_;
+  std::deque<ConvLayer> layers_;            // the convolution layers (add_conv); a deque: the ops hold pointers
+  std::vector<ConvWeights> convs_;          // pointwise weights of the fused BiFPN nodes
   double* arena_ = nullptr;
   size_t arena_doubles_ = 0;
   size_t bytes_ = 0;

@@ -7,7 +7,6 @@
 #include <cstdlib>
 #include "nets.h"
 #include "bifpn_node.h"
-#include "conv3d_wino.h"
 
 namespace jh {
 
@@ -109,42 +108,19 @@ int Plan::add_conv(const ParamMap& pm, const ConvDesc& d, const std::string& wke
   if (d.ostride > 1) taps = (d.nd == 2) ? 16 : 8;
   else taps = (size_t)d.k * d.k * (d.nd == 3 ? d.k : 1);
   const float *w = nullptr, *b = nullptr;
-  ConvDesc dd = d;
-  dd.latency_class = norm_block_kb == 0 ? 1 : 0;       // (the plan's time-batch class, set before build())
-  dd.plain_out = !want_stats && !gate && !se;
   if (get(pm, wkey, (size_t)d.cin * d.cout * taps, &w)) return 1;
   if (!bkey.empty() && get(pm, bkey, d.cout, &b)) return 1;
-  // 3x3x3 stride-1 convs (the V2V residual blocks) run as Winograd F(2x2,3x3) x direct z
-  bool wino = d.nd == 3 && d.k == 3 && d.stride == 1 && d.ostride == 1 && !transposed && !gate;
-  if (const char* e = getenv("JH_WINO")) wino = wino && atoi(e) != 0;      // (plan build time)
-  const int wino_variant = wino ? wino_variant_from_env() : 0;
-  // precision mode bf16x3 (opt-in, jh_set_precision): the same layers on the bf16 matrix cores with
-  // split operands (csrc/conv3d_bf16x3.hip)
-  const bool b3 = wino && precision >= 1;
-  // ... and the keypoint head's ConvTranspose2d (no bias, no fused statistics, no gate)
-  const bool d4b = d.nd == 2 && d.ostride > 1 && transposed && !b && !want_stats && !gate &&
-                   precision >= 1 && deconv4_bf16x3_eligible(d.cout);
-  // ... and the dense k x k convolutions with a generic split-bf16 kernel (no gate; the 3-channel
-  // network input keeps its own kernels)
-  // Level 1 (bf16x3) takes the 3D one (V2V's stride-2 front convolution); the 2D trunk convolutions only
-  // at level 2 (bf16x3_wide): split, they move the keypoints by up to 7.6e-4 mm on the fixture cases, which
-  // leaves no margin under the 1e-3 mm bar.
-  const bool xb = !wino && !d4b && !transposed && !gate && !se && conv_bf16x3_eligible(d) && x.Cp == cpad(d.cin) &&
-                  (precision == 2 || (precision == 1 && d.nd == 3));
-  ConvWeights cw;
-  if (xb) {
-    if (pack_conv_bf16x3_weights(d, w, b, &cw)) return 1;
-  } else if (d4b) {
-    if (pack_deconv4_bf16x3_weights(d.cin, d.cout, w, &cw)) return 1;
-  } else if (b3) {
-    if (pack_bf16x3_weights(d.cin, d.cout, w, b, &cw)) return 1;
-  } else if (wino) {
-    if (pack_wino_weights(d.cin, d.cout, w, b, &cw)) return 1;
-  } else {
-    if (pack_conv_weights(dd, w, b, transposed, &cw)) return 1;
-  }
-  convs_.push_back(cw);
-  bytes_ += cw.phase_stride * d.nphase * sizeof(float);
+  // which kernel form runs the layer, and in which weight layout: choose_conv (csrc/conv_layer.hip)
+  ConvUse use;
+  use.desc = d; use.desc.latency_class = norm_block_kb == 0 ? 1 : 0;   // (the plan's time-batch class, set before build())
+  use.transposed = transposed; use.has_bias = b != nullptr; use.want_stats = want_stats;
+  use.gate = se ? ConvGate::Recipe : (gate ? ConvGate::Tensor : ConvGate::None);
+  use.precision = precision;
+  use.in_px = x.Cp;
+  layers_.emplace_back();
+  const ConvLayer* layer = &layers_.back();
+  if (make_conv_layer(use, w, b, y.D, y.H, y.W, &layers_.back())) return 1;
+  bytes_ += layer->device_bytes();
   size_t off = 0;
   if (want_stats) {
     off = scratch((size_t)y.N * y.Cp * kStatW);
@@ -155,34 +131,18 @@ int Plan::add_conv(const ParamMap& pm, const ConvDesc& d, const std::string& wke
   const double opix = (double)y.N * y.pixels();
   const double taps_per_out = (d.ostride > 1) ? (double)taps / d.nphase : (double)taps;
   const double flops = 2.0 * opix * d.cin * d.cout * taps_per_out;
-  const double bytes = 4.0 * ((double)x.N * x.pixels() * d.cin + opix * d.cout + (double)d.cin * d.cout * taps);
-  // Winograd on a volume with remainder strips (e.g. 36^3 / 18^3 of the shipped 72^3 grid): the persistent kernel's
-  // tile table, built and uploaded here, at plan-build time (csrc/conv3d_wino.h)
-  const int* wino_tiles = nullptr;
-  if (wino && !b3) {
-    const std::vector<int> tt = wino_tables(y.D, y.H, y.W, x.Cp);
-    if (!tt.empty()) {
-      void* dev = nullptr;
-      if (alloc(&dev, tt.size() * sizeof(int))) return 1;
-      JH_CHECK_HIP(hipMemcpy(dev, tt.data(), tt.size() * sizeof(int), hipMemcpyHostToDevice));
-      wino_tiles = static_cast<const int*>(dev);
-    }
-  }
-  char nm[96];
-  snprintf(nm, sizeof nm, "conv%dd_k%ds%d%s_%dx%d@%d", d.nd, d.ostride > 1 ? (d.nd == 2 ? 4 : 2) : d.k,
-           d.ostride > 1 ? 2 : d.stride, d.ostride > 1 ? (d4b ? "Tbf16x3" : "T") : (b3 || xb ? "bf16x3" : (wino ? "wino" : "")), d.cin, d.cout, y.W);
-  push(nm, flops, bytes,
-       [this, d = dd, cw, x, y, gate, want_stats, off, in_stats_off, in_inv, in_act, wino, wino_variant, b3, d4b, xb,
-        wino_tiles, sev = se ? *se : SeGate(), se_pool_off](hipStream_t s) {
+  // (the one-channel vector-ALU kernel keeps its weights in registers and stores whole padded pixels)
+  const double bytes = layer->choice.form == ConvForm::DeconvC1
+      ? 4.0 * x.N * (x.pixels() * d.cin + (double)y.pixels() * y.Cp)
+      : 4.0 * ((double)x.N * x.pixels() * d.cin + opix * d.cout + (double)d.cin * d.cout * taps);
+  push(layer->profile_name(y.W), flops, bytes,
+       [this, layer, x, y, gate, want_stats, off, in_stats_off, in_inv, in_act, sev = se ? *se : SeGate(),
+        se_pool_off](hipStream_t s) {
     InNorm in;
     if (in_stats_off >= 0) { in.stats = sc((size_t)in_stats_off); in.inv = in_inv; in.act = in_act; }
     SeGate seg = sev;
     if (se_pool_off >= 0) seg.pool = sc((size_t)se_pool_off);
-    if (xb) return launch_conv_bf16x3(d, cw, x, y, want_stats ? sc(off) : nullptr, s, &in);
-    if (d4b) return launch_deconv4_bf16x3(cw, x, y, s, &in);
-    if (b3) return launch_conv3d_bf16x3(cw, x, y, want_stats ? sc(off) : nullptr, s, &in);
-    if (wino) return launch_conv3d_wino(cw, x, y, want_stats ? sc(off) : nullptr, s, &in, wino_variant, wino_tiles);
-    return launch_conv(d, cw, x, y, gate, want_stats ? sc(off) : nullptr, s, &in, se_pool_off >= 0 ? &seg : nullptr);
+    return layer->launch(x, y, gate, want_stats ? sc(off) : nullptr, in, se_pool_off >= 0 ? &seg : nullptr, s);
   });
   return 0;
 }
@@ -290,11 +250,8 @@ int EffTrackPlan::mbconv(const ParamMap& pm, const std::string& p, int stage, in
     JH_REQUIRE(stride == 1, "depthwise stages are stride 1");
     const float* w = nullptr;
     if (get(pm, p + "_depthwise_conv.weight", (size_t)mid * k * k, &w)) return 1;
-    std::vector<float> wt((size_t)k * k * raw.Cp, 0.f);
-    for (int c = 0; c < mid; ++c)
-      for (int t = 0; t < k * k; ++t) wt[(size_t)t * raw.Cp + c] = w[(size_t)c * k * k + t];
     float* wd = nullptr;
-    if (upload(wt, &wd)) return 1;
+    if (upload(taps_major(w, mid, k * k, raw.Cp), &wd)) return 1;
     st1 = scratch((size_t)raw.N * raw.Cp * kStatW);
     pooled = depthwise_can_pool(Ho, Wo);
     push(std::string("depthwise_k") + std::to_string(k) + (pooled ? "pool" : ""), 2.0 * raw.N * raw.pixels() * mid * k * k,
@@ -385,16 +342,13 @@ int EffTrackPlan::node(const ParamMap& pm, const std::string& cp, int n_in, cons
   const int cin = like.C;
   const float* dwh = nullptr;
   if (get(pm, cp + "depthwise_conv.weight", (size_t)cin * 9, &dwh)) return 1;
-  std::vector<float> wt((size_t)9 * like.Cp, 0.f);
-  for (int c = 0; c < cin; ++c)
-    for (int t = 0; t < 9; ++t) wt[(size_t)t * like.Cp + c] = dwh[(size_t)c * 9 + t];
   float* dwd = nullptr;
-  if (upload(wt, &dwd)) return 1;
+  if (upload(taps_major(dwh, cin, 9, like.Cp), &dwd)) return 1;
   const float *pwh = nullptr, *bh = nullptr;
   if (get(pm, cp + "pointwise_conv.weight", (size_t)cin * cout, &pwh)) return 1;
   if (get(pm, cp + "pointwise_conv.bias", cout, &bh)) return 1;
   ConvWeights cw;
-  if (pack_conv_weights(conv_desc(2, 1, 1, 0, cin, cout), pwh, bh, false, &cw)) return 1;
+  if (pack_conv_weights(conv_desc(2, 1, 1, 0, cin, cout), pwh, bh, false, WeightLayout::Plain, &cw)) return 1;
   convs_.push_back(cw);
   if (new_act(like.N, 1, like.H, like.W, cout, &out->a)) return 1;
   const size_t st = scratch((size_t)like.N * out->a.Cp * kStatW);
@@ -605,24 +559,7 @@ int EffTrackPlan::build(const ParamMap& pm, const std::string& pre, int size, in
     if (add_conv(pm, conv_desc(2, 3, 1, 1, ss.head, J), pre + "final_conv1.weight", "", false, mid.a,
                  res1, nullptr, false, nullptr, mid.st, mid.inv, ACT_NONE)) return 1;
   }
-  if (J == 1) {
-    // one output channel: vector-ALU kernel instead of a 16-wide MFMA column block
-    const float* wh = nullptr;
-    if (get(pm, pre + "deconv1.weight", (size_t)ss.head * 16, &wh)) return 1;
-    std::vector<float> wt((size_t)16 * mid.a.Cp, 0.f);
-    for (int c = 0; c < ss.head; ++c)
-      for (int t = 0; t < 16; ++t) wt[(size_t)t * mid.a.Cp + c] = wh[(size_t)c * 16 + t];
-    float* wd = nullptr;
-    if (upload(wt, &wd)) return 1;
-    const Act m = mid.a, h = heat;
-    const long mst = mid.st;
-    const float minv = mid.inv;
-    push("deconv_k4s2T_c1", 2.0 * N * h.pixels() * ss.head * 4,
-         4.0 * N * (m.pixels() * ss.head + (double)h.pixels() * h.Cp), [this, m, h, mst, minv, wd](hipStream_t s) {
-      return launch_deconv_c1(m, mst >= 0 ? sc((size_t)mst) : nullptr, minv, ACT_NONE, wd, h, s);
-    });
-    return finish();
-  }
+  // (J == 1, the CenterDetect head: the one-channel vector-ALU form)
   if (add_conv(pm, deconv2d_k4s2p1_desc(ss.head, J), pre + "deconv1.weight", "", true, mid.a, heat,
                nullptr, false, nullptr, mid.st, mid.inv, ACT_NONE)) return 1;
   return finish();

@@ -94,6 +94,7 @@ def test_conv2d_gate():
     (88, 23, 12, 12, False, -1),     # no instantiation of the fused kernel: four-phase general path
     (64, 23, 64, 64, False, 2, 12),  # more workgroups than CUs (a store-data hazard of an earlier epilogue
     (64, 23, 64, 64, False, -1, 12), # only showed with two workgroups resident per CU)
+    (64, 1, 9, 21, False, -1),       # the one-channel head: the vector-ALU kernel (csrc/deconv_c1.hip), ragged tiles
 ])
 def test_deconv2d_k4s2p1(case):
     cin, cout, H, W, bias, norm_act = case[:6]
