@@ -538,6 +538,82 @@ int jh_predictor_forward_images(jh_predictor* pr, const void* const* images_host
                                 const jh_yuv_surface* yuv, const jh_sensor_surface* sensor, const uint8_t* mask_dev,
                                 float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
 
+/* Several subjects in one frame set (ABI v4, additive; new design: the reference keeps ONE maximum per camera and puts
+ * every camera's maximum into one triangulation, jarvis3D.py:147-160).  Stage 1 as it stands finds the strongest subject;
+ * if the cameras disagree about which one that is, or one camera's maximum sits on a reflection, the one weighted DLT
+ * averages rays to different things.  Here the top few local maxima of every camera's centre heat map are kept, grouped
+ * across cameras by reprojection consistency, and each group is triangulated with the arithmetic of the existing
+ * triangulation.  A centre goes back in through jh_predictor_set_centers; robust single-subject detection is
+ * max_subjects = 1.
+ *
+ * jh_subjects_params.  Library defaults -- documented values, not recommendations: what suits a rig depends on its
+ * pixel scale and on what its CenterDetect emits -- are min_peak = 50 (the reference's `> 50` gate), nms_radius = 4,
+ * min_views = 2, max_error_px = 24.  Ranges, checked by every entry point below (non-zero with jh_last_error() set,
+ * nothing enqueued): max_subjects 1 .. 8, max_peaks 1 .. 8, nms_radius 1 .. 16, min_views >= 2, min_peak a number below
+ * +inf (-inf allowed), max_error_px >= 0 (+inf allowed).
+ *
+ * jh_op_center_peaks: heat (n,hh,wh,cp) channel-last dev, channel 0 -- what the centre arg-max reads -- -> peaks
+ * (n,max_peaks,3) = (x, y, value), count (n) int32.  With v(p) the value at flat index p = y*wh + x: p is a PEAK iff
+ * v(p) > min_peak and no q != p of the window |dx| <= nms_radius, |dy| <= nms_radius, clipped at the map's edge, has
+ * v(q) > v(p) or (v(q) == v(p) and q < p): of a plateau only the lowest index survives; NaN is never a peak and never
+ * suppresses one.  The peaks of an image are ordered by (value descending, index ascending) and the first max_peaks
+ * kept, as x = p % hh, y = p / wh (the arg-max's expression); empty slots are (-1, -1, -inf).  Slot 0 with min_peak =
+ * -inf is therefore the centre arg-max (jh_predictor_debug's det) bit for bit for any map that holds a value above -inf.
+ * One workgroup per image; a map up to 160 x 160 is read from memory once and held in LDS, a larger one takes a
+ * global-memory form of the same passes (scratch from hipMalloc: unit-test helper, synchronises).
+ *
+ * jh_op_associate_subjects: peaks (t,cams,max_peaks,3) dev as above, one calibration (calib_per_frame == 0: (cams,..))
+ * or one per frame set (!= 0: (t,cams,..)), mask (t,cams) bytes or NULL; sx2, sy2: full-frame pixels per heat-map pixel
+ * (a peak lies at (x*sx2, y*sy2)).  A slot takes part iff its camera is unmasked and x >= 0 and y >= 0; a masked
+ * camera's slots are never read and may be NaN.  For round k = 0 .. max_subjects-1:
+ *   candidates  every (a, i, b, j), cameras a < b, unused slots i of a and j of b: X = the weighted DLT of the existing
+ *               triangulation (weights value / 255) over exactly those two observations;
+ *   support     per camera with an unused slot, the unused peak nearest to reprojectPoint(X), d = sqrt(dx*dx + dy*dy),
+ *               one fp32 rounding per operation, ties to the lowest slot; the camera supports iff the homogeneous depth
+ *               of the projection is > 0 and d <= max_error_px (a NaN d never supports); views = supporting cameras,
+ *               cost = the fp32 sum of their d in camera order;
+ *   choice      largest views, then smallest cost, then lowest (a, i, b, j); views < min_views: this and all later
+ *               subjects are empty;
+ *   subject k   members[k][c] = the supporting slot of camera c or -1; centers[k] = the triangulation over the member
+ *               observations, BIT FOR BIT jh_reconstruct_point on the members' pixels and value / 255; error[k] = the
+ *               mean over the members of d against the projection of centers[k]; the members' slots become used.
+ * -> centers (t,max_subjects,3) world mm, NaN for an empty subject (an invalid row for jh_predictor_set_centers), views
+ * (t,max_subjects) int32 (0), members (t,max_subjects,cams) int32 (-1), error (t,max_subjects) px (NaN).  The result
+ * does not depend on timing.  cams <= 64.  The work of a frame set grows with cams^2 * max_peaks^2 per round: it is
+ * meant for cams * max_peaks up to a few hundred.  Synchronises (unit-test helper).
+ *
+ * jh_predictor_detect_subjects: stage 1 of the call's frames up to CenterDetect's heat map (resize or fused stem, the
+ * CenterDetect plan), then the two kernels in place of the arg-max and the triangulation, under the calibration in
+ * force (shared or per frame set).  Frames: exactly one of frames_dev (contiguous, as the forward of `format` takes
+ * them) and images_host + n_images (per-image pointers, as jh_predictor_forward_images); format any JH_FRAME_*, with yuv
+ * / sensor exactly where the format needs one.  mask_dev (T,C) or NULL: read in place, keep it alive until the stream
+ * has passed the call.  peaks_dev (T,C,max_peaks,3) optional (NULL to skip).  sx2, sy2 are the predictor's
+ * 2 * img_w / center_size and 2 * img_h / center_size.
+ * Plain launches, asynchronous, also on a graph-replaying predictor: the captured graphs, det, the centres set by
+ * jh_predictor_set_centers and whether they are in force, the mask buffer and the spread state are not touched, so the
+ * forwards before and after keep their bits.  The workspace (peaks and counts, and the global-form scratch of a map
+ * that does not fit the LDS) is allocated by the first such call of a predictor -- never by jh_predictor_create, so
+ * jh_predictor_device_bytes, the memory and the launches of a predictor that never asks are unchanged -- and that first
+ * call must not be made inside a stream capture.  Needs CenterDetect weights and all cameras local; otherwise, and for
+ * parameters out of range, non-zero with jh_last_error() set and nothing enqueued.
+ * Subject k of one call and subject k of the next are unrelated: identity across frames is the caller's. */
+typedef struct jh_subjects_params {
+  int32_t max_subjects, max_peaks, nms_radius, min_views;
+  float min_peak, max_error_px;
+} jh_subjects_params;
+int jh_subjects_params_check(const jh_subjects_params* params);    /* no GPU needed */
+int jh_op_center_peaks(const float* heat_dev, int n, int hh, int wh, int cp, const jh_subjects_params* params,
+                       float* peaks_dev, int32_t* count_dev, void* stream);
+int jh_op_associate_subjects(const float* peaks_dev, int t, int cams, const float* cam_dev, const float* intr_dev,
+                             const float* dist_dev, int calib_per_frame, const uint8_t* mask_dev, float sx2, float sy2,
+                             const jh_subjects_params* params, float* centers_dev, int32_t* views_dev,
+                             int32_t* members_dev, float* error_dev, void* stream);
+int jh_predictor_detect_subjects(jh_predictor* pr, const void* frames_dev, const void* const* images_host, int n_images,
+                                 int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor,
+                                 const uint8_t* mask_dev, const jh_subjects_params* params, float* centers_dev,
+                                 int32_t* views_dev, int32_t* members_dev, float* error_dev,
+                                 float* peaks_dev /* optional */, void* stream);
+
 /* HybridNetBackbone.forward: crops (T,C,3,B,B) normalised NCHW dev, center_hm
  * (T,C,2) int32, center3d (T,3) int32 -> heatmap_final (T,J,Gh,Gh,Gh) optional,
  * heatmaps_padded (T,C,J,hs,hs) optional, points (T,J,3), conf (T,J). */

@@ -62,6 +62,14 @@ class OpOperand(ctypes.Structure):
 
 assert ctypes.sizeof(OpOperand) == 72
 
+class SubjectsParamsStruct(ctypes.Structure):
+    """jh_subjects_params of include/jarvis_hip.h (built by subjects_params())."""
+    _fields_ = [("max_subjects", ctypes.c_int32), ("max_peaks", ctypes.c_int32), ("nms_radius", ctypes.c_int32),
+                ("min_views", ctypes.c_int32), ("min_peak", c_float), ("max_error_px", c_float)]
+
+
+assert ctypes.sizeof(SubjectsParamsStruct) == 24
+
 ABI_VERSION = 4                    # JH_ABI_VERSION of include/jarvis_hip.h
 # sizeof(jh_predictor_config): statically asserted on the C side (tests/abi_smoke.c) and here
 assert ctypes.sizeof(PredictorConfig) == 84
@@ -172,6 +180,16 @@ _SIGS = {
                                              c_void_p]),
     "jh_predictor_debug_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_views2d": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 8),
+    "jh_subjects_params_check": (c_int, [ctypes.POINTER(SubjectsParamsStruct)]),
+    "jh_op_center_peaks": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(SubjectsParamsStruct), c_void_p,
+                                   c_void_p, c_void_p]),
+    "jh_op_associate_subjects": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_float, c_float, ctypes.POINTER(SubjectsParamsStruct), c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]),
+    "jh_predictor_detect_subjects": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_int, c_int,
+                                             ctypes.POINTER(YuvSurfaceStruct), ctypes.POINTER(SensorSurfaceStruct),
+                                             c_void_p, ctypes.POINTER(SubjectsParamsStruct), c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_joint_argmax_all_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "jh_op_joint_argmax_all": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p]),
@@ -509,6 +527,31 @@ def centers(value, T):
     elif shape != (T, 3):
         raise ValueError("centers must have shape %s (world millimetres, one row per frame set); got %s" % (want, shape))
     return value.to(torch.float32).contiguous()
+
+
+def subjects_params(max_subjects, max_peaks=None, nms_radius=4, min_views=2, min_peak=50.0, max_error_px=24.0):
+    """The parameters of a detect_subjects call checked -> SubjectsParamsStruct (jh_subjects_params).  The defaults are
+    the library's documented defaults, not recommendations: min_peak 50 (the reference's `> 50` gate), nms_radius 4
+    heat-map pixels, min_views 2, max_error_px 24 full-frame pixels; max_peaks None = min(8, 2 * max_subjects).
+    Ranges (the library's own check, jh_subjects_params_check: host arithmetic, no device): max_subjects 1 .. 8,
+    max_peaks 1 .. 8, nms_radius 1 .. 16, min_views >= 2, min_peak a number below +inf (-inf allowed), max_error_px
+    >= 0 (+inf allowed).  ValueError for anything else, a non-integer count included."""
+    ints = dict(max_subjects=max_subjects, max_peaks=max_peaks, nms_radius=nms_radius, min_views=min_views)
+    if max_peaks is None and isinstance(max_subjects, int):
+        ints["max_peaks"] = max(1, min(8, 2 * max_subjects))
+    for name, v in ints.items():
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError("%s must be an int, got %r" % (name, v))
+        if abs(v) >= 2 ** 31:
+            raise ValueError("%s is out of range: %r" % (name, v))
+    try:
+        floats = (float(min_peak), float(max_error_px))
+    except (TypeError, ValueError):
+        raise ValueError("min_peak and max_error_px must be numbers, got %r and %r" % (min_peak, max_error_px))
+    p = SubjectsParamsStruct(ints["max_subjects"], ints["max_peaks"], ints["nms_radius"], ints["min_views"], *floats)
+    if lib().jh_subjects_params_check(ctypes.byref(p)) != 0:
+        raise ValueError(lib().jh_last_error().decode())
+    return p
 
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x3_wide": 2}

@@ -7,6 +7,7 @@ import torch
 from . import _native as N
 from . import arch
 from .spread import Spread3D  # noqa: F401 -- the name the forwards return
+from .subjects import Subjects
 
 
 # Per-camera 2D views of a 3D result (jh_predictor_views2d, include/jarvis_hip.h): points2D (T,C,J,2) int32 full-frame
@@ -277,6 +278,39 @@ class NativePredictor:
         if mask is not None:
             mask.record_stream(torch.cuda.current_stream())     # (read in place by the enqueued kernel)
         return Views2D(*out)
+
+    def detect_subjects(self, frames, params, camera_mask=None, return_peaks=False):
+        """Up to params.max_subjects subjects per frame set of checked frames (a _native.Frames with `data`, from
+        _describe, or with `images`, from _native.frame_images) -> Subjects of device tensors, on the current stream
+        (jh_predictor_detect_subjects): stage 1 up to CenterDetect's heat map, the top local maxima of every camera,
+        their grouping across cameras, one triangulation per group -- under the calibration in force.  params: what
+        _native.subjects_params made.  camera_mask (T,C) as forward().  return_peaks: the (T,C,max_peaks,3) peaks
+        (x, y, value; empty slots (-1, -1, -inf)) follow.  Plain launches: nothing of the forwards' state -- graphs,
+        centres, mask, spread -- is touched.  Needs CenterDetect weights and all cameras local (RuntimeError)."""
+        if not isinstance(params, N.SubjectsParamsStruct):
+            raise ValueError("params must come from _native.subjects_params, got %s" % type(params).__name__)
+        if frames.images is not None and len(frames.images) != self.T * self.C:
+            raise ValueError("expected %d images (time_batch * num_cameras), got %d" % (self.T * self.C,
+                                                                                         len(frames.images)))
+        mask = N.camera_mask(camera_mask, (self.T, self.C))
+        dev, K = frames.device, params.max_subjects
+        if mask is not None:
+            mask = mask.to(dev, non_blocking=True)
+        out = Subjects(torch.empty((self.T, K, 3), device=dev), torch.empty((self.T, K), device=dev, dtype=torch.int32),
+                       torch.empty((self.T, K, self.C), device=dev, dtype=torch.int32),
+                       torch.empty((self.T, K), device=dev))
+        peaks = torch.empty((self.T, self.C, params.max_peaks, 3), device=dev) if return_peaks else None
+        struct = frames.layout.struct() if frames.layout is not None else None
+        table = None
+        if frames.images is not None:
+            table = (N.c_void_p * len(frames.images))(*(t.data_ptr() for t in frames.images))
+        N.check(N.lib().jh_predictor_detect_subjects(
+            self.handle, N.ptr(frames.data), table, 0 if table is None else len(frames.images), frames.fmt,
+            struct if frames.fmt == N.FRAME_SURFACE else None, struct if frames.fmt == N.FRAME_SENSOR else None,
+            N.ptr(mask), ctypes.byref(params), *(N.ptr(t) for t in out), N.ptr(peaks), N.stream()))
+        if mask is not None:
+            mask.record_stream(torch.cuda.current_stream())     # (read in place by the enqueued kernel)
+        return (out, peaks) if return_peaks else out
 
     def debug(self, device):
         c3f = torch.empty((self.T, 3), device=device)

@@ -7,6 +7,7 @@
 #include "bifpn_node.h"
 #include "camera_mask.h"
 #include "views2d.h"
+#include "subjects.h"
 
 namespace jh {
 static thread_local std::string g_err;
@@ -550,6 +551,11 @@ struct jh_predictor {
   // by the first such call, so a predictor that never asks for 2D views owns what it always did
   float* v2d_max = nullptr;
   int* v2d_idx = nullptr;
+  // Several subjects (jh_predictor_detect_subjects): peaks [T * C][kMaxPeaks][3], counts [T * C] and the global-form
+  // scratch of the peak kernel (none where the heat map fits the LDS), ONE allocation made by the first such call
+  float* subj_peaks = nullptr;
+  int* subj_count = nullptr;
+  void* subj_ws = nullptr;
   // Per-joint 3D spread (jh_predictor_set_spread).  spread_on: run_3d launches the spread form of the soft-argmax tail,
   // which writes rows t0 .. t0+T3-1 of sp_cov (T,J,6), sp_peak (T,J,3) and sp_mass (T,J); spread.sums / .key: its
   // accumulators for one 3D chunk.  All of it ONE allocation of spread_bytes, made by the first enabling call: a
@@ -804,9 +810,8 @@ int jh_predictor_debug_v2v(jh_predictor* pr, float* out_dev, void* stream) {
   return launch_from_channel_last(pr->v2v->output, out_dev, static_cast<hipStream_t>(stream));
 }
 
-static int stage_center_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* det_dev,
-                             void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
+// Stage 1 up to CenterDetect's heat map (pr->center->heat): resize or fused stem, then the plan
+static int center_heat_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, hipStream_t s) {
   JH_REQUIRE(pr->center, "predictor was created without CenterDetect weights");
   const int N = pr->T * pr->Cloc, S = pr->cfg.center_size;
   if (pr->center->stem_fusable) {
@@ -823,7 +828,14 @@ static int stage_center_impl(jh_predictor* pr, const void* frames_dev, const Fra
             launch_preprocess_resize(frames_dev, fs, pr->center->input.p, N, pr->cfg.img_h,
                                      pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, pr->cell_for(fs)));
   }
-  if (pr->center->run(s)) return 1;
+  return pr->center->run(s);
+}
+
+static int stage_center_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* det_dev,
+                             void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (center_heat_impl(pr, frames_dev, fs, s)) return 1;
+  const int N = pr->T * pr->Cloc;
   const Act& h = pr->center->heat;
   JH_PROF("center_argmax", 0.0, 4.0 * N * h.H * h.W,
           launch_center_argmax(h.p, det_dev, N, h.H, h.W, h.Cp, s));
@@ -1163,6 +1175,119 @@ int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, co
                                pr->intr_at(t0), pr->dist_at(t0), pr->calib_fs, points2d_dev, conf2d_dev, reproj_dev,
                                err_dev, used_dev, pr->T3, pr->C,
                                pr->J, pr->Jp, pr->Hh, pr->Hh, pr->B / 2, s));
+  return 0;
+}
+
+// ---- several subjects (csrc/subjects.h)
+static int subjects_params(const jh_subjects_params* p, SubjectsParams* out) {
+  JH_REQUIRE(p, "null jh_subjects_params");
+  *out = SubjectsParams{p->max_subjects, p->max_peaks, p->nms_radius, p->min_views, p->min_peak, p->max_error_px};
+  return subjects_check(*out);
+}
+
+int jh_subjects_params_check(const jh_subjects_params* params) {
+  SubjectsParams sp;
+  return subjects_params(params, &sp);
+}
+
+int jh_op_center_peaks(const float* heat_dev, int n, int hh, int wh, int cp, const jh_subjects_params* params,
+                       float* peaks_dev, int32_t* count_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SubjectsParams sp;
+  if (subjects_params(params, &sp)) return 1;
+  JH_REQUIRE(heat_dev && peaks_dev && count_dev, "jh_op_center_peaks: null pointer");
+  JH_REQUIRE(n >= 1 && hh >= 1 && wh >= 1 && hh <= 32768 && wh <= 32768, "jh_op_center_peaks: heat map shape");
+  Scratch sc;
+  void* ws = nullptr;
+  const size_t bytes = center_peaks_workspace(n, hh, wh);
+  if (bytes && sc.get(&ws, bytes)) return 1;
+  if (launch_center_peaks(heat_dev, peaks_dev, count_dev, n, hh, wh, cp, sp.max_peaks, sp.nms_radius, sp.min_peak, ws,
+                          s)) return 1;
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int jh_op_associate_subjects(const float* peaks_dev, int t, int cams, const float* cam_dev, const float* intr_dev,
+                             const float* dist_dev, int calib_per_frame, const uint8_t* mask_dev, float sx2, float sy2,
+                             const jh_subjects_params* params, float* centers_dev, int32_t* views_dev,
+                             int32_t* members_dev, float* error_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SubjectsParams sp;
+  if (subjects_params(params, &sp)) return 1;
+  JH_REQUIRE(peaks_dev && cam_dev && intr_dev && dist_dev && centers_dev && views_dev && members_dev && error_dev,
+             "jh_op_associate_subjects: null pointer");
+  JH_REQUIRE(t >= 1 && cams >= 1 && cams <= 64, "jh_op_associate_subjects: at most 64 cameras");
+  if (launch_associate_subjects(peaks_dev, cam_dev, intr_dev, dist_dev, calib_per_frame ? cams : 0, mask_dev,
+                                centers_dev, views_dev, members_dev, error_dev, t, cams, sp.max_peaks, sp.max_subjects,
+                                sp.min_views, sp.max_error_px, sx2, sy2, 255.f, s)) return 1;
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int jh_predictor_detect_subjects(jh_predictor* pr, const void* frames_dev, const void* const* images_host, int n_images,
+                                 int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor,
+                                 const uint8_t* mask_dev, const jh_subjects_params* params, float* centers_dev,
+                                 int32_t* views_dev, int32_t* members_dev, float* error_dev, float* peaks_dev,
+                                 void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(pr, "jh_predictor_detect_subjects: null predictor");
+  SubjectsParams sp;
+  if (subjects_params(params, &sp)) return 1;
+  JH_REQUIRE(centers_dev && views_dev && members_dev && error_dev, "jh_predictor_detect_subjects: null output pointer");
+  JH_REQUIRE(pr->center, "jh_predictor_detect_subjects: predictor was created without CenterDetect weights");
+  JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "jh_predictor_detect_subjects needs all cameras local");
+  JH_REQUIRE((frames_dev != nullptr) != (images_host != nullptr),
+             "jh_predictor_detect_subjects: give frames_dev or images_host, not both");
+  const auto& c = pr->cfg;
+  FrameSource fs;
+  if (images_host) {
+    if (images_source(format, yuv, sensor, c.img_h, c.img_w, &fs)) return 1;
+  } else {
+    JH_REQUIRE(format >= JH_FRAME_RGB_F32 && format <= JH_FRAME_SENSOR, "jh_predictor_detect_subjects: unknown frame "
+               "format");
+    JH_REQUIRE((yuv != nullptr) == (format == JH_FRAME_SURFACE) && (sensor != nullptr) == (format == JH_FRAME_SENSOR),
+               "jh_predictor_detect_subjects: a description exactly where the format needs one");
+    if (format == JH_FRAME_SURFACE ? frame_source(yuv, c.img_h, c.img_w, &fs)
+        : format == JH_FRAME_SENSOR ? frame_source(sensor, c.img_h, c.img_w, &fs)
+                                    : frame_source(format, c.img_h, c.img_w, &fs)) return 1;
+  }
+  const int N = pr->T * pr->C;
+  const Act& h = pr->center->heat;
+  if (!pr->subj_peaks) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s, &cs);
+    JH_REQUIRE(cs == hipStreamCaptureStatusNone, "the first jh_predictor_detect_subjects call of a predictor allocates "
+               "its workspace: make it outside a stream capture");
+    // (one allocation: subj_peaks is set last, so a failure leaves the predictor as it was)
+    const size_t pk = ((size_t)N * kMaxPeaks * 3 * sizeof(float) + 255) / 256 * 256;
+    const size_t cn = ((size_t)N * sizeof(int) + 255) / 256 * 256;
+    const size_t ws = center_peaks_workspace(N, h.H, h.W);
+    char* base = nullptr;
+    if (pr->mem.get(reinterpret_cast<void**>(&base), pk + cn + ws)) return 1;
+    pr->subj_count = reinterpret_cast<int*>(base + pk);
+    pr->subj_ws = ws ? base + pk + cn : nullptr;
+    pr->subj_peaks = reinterpret_cast<float*>(base);
+  }
+  const void* frames = frames_dev;
+  if (images_host) {
+    if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, N, format, s)) return 1;
+    frames = pr->frames_table;                // (the launches read the table: `frames` itself is not dereferenced)
+  }
+  // (plain launches with this call's frame pointer: cur_cell is non-null only while a forward is being captured)
+  if (center_heat_impl(pr, frames, fs, s)) return 1;
+  JH_PROF("center_peaks", 0.0, 4.0 * N * h.H * h.W,
+          launch_center_peaks(h.p, pr->subj_peaks, pr->subj_count, N, h.H, h.W, h.Cp, sp.max_peaks, sp.nms_radius,
+                              sp.min_peak, pr->subj_ws, s));
+  // preds * (downsampling_scale * 2), as stage 2 scales the arg-max (jarvis3D.py:138-141,158-160)
+  const float sx2 = (float)((double)c.img_w / (double)c.center_size) * 2.f;
+  const float sy2 = (float)((double)c.img_h / (double)c.center_size) * 2.f;
+  JH_PROF("associate_subjects", 0.0, 0.0,
+          launch_associate_subjects(pr->subj_peaks, pr->cam_at(0), pr->intr_at(0), pr->dist_at(0), pr->calib_fs, mask_dev,
+                                    centers_dev, views_dev, members_dev, error_dev, pr->T, pr->C, sp.max_peaks,
+                                    sp.max_subjects, sp.min_views, sp.max_error_px, sx2, sy2, 255.f, s));
+  if (peaks_dev)
+    JH_CHECK_HIP(hipMemcpyAsync(peaks_dev, pr->subj_peaks, (size_t)N * sp.max_peaks * 3 * sizeof(float),
+                                hipMemcpyDeviceToDevice, s));
   return 0;
 }
 

@@ -65,6 +65,22 @@ def check_native_seam(predictor):
                 "call the replacement yourself." % (name, type(obj).__name__, cls.__name__))
 
 
+def image_frames(num_cameras, images, frame_format, frame_layout):
+    """The `images` argument of the per-image forms (C tensors, or T sequences of C tensors) checked -> Frames."""
+    if isinstance(images, (list, tuple)) and len(images) > 0 and torch.is_tensor(images[0]):
+        images = [images]
+    if not isinstance(images, (list, tuple)) or len(images) == 0:
+        raise ValueError("images must be a sequence of %d tensors or a sequence of such sequences"
+                         % num_cameras)
+    for t, frame_set in enumerate(images):
+        if not isinstance(frame_set, (list, tuple)) or len(frame_set) != num_cameras:
+            raise ValueError("frame set %d: expected a sequence of %d images (one per camera), got %s" % (
+                t, num_cameras,
+                len(frame_set) if isinstance(frame_set, (list, tuple)) else type(frame_set).__name__))
+    flat = [img for frame_set in images for img in frame_set]
+    return N.frame_images(flat, (len(images), num_cameras), frame_format, frame_layout)
+
+
 class JarvisPredictor3D(nn.Module):
     def __init__(self, cfg, weights_center_detect="latest", weights_hybridnet="latest",
                  trt_mode="off", precision=None):
@@ -300,22 +316,67 @@ class JarvisPredictor3D(nn.Module):
         batch are different subjects seen in the same frames (a detected batch finds the strongest one in every row).
         return_spread: as forward_batch -- the Spread3D of the batch (covariance in mm^2, peak voxel in mm and mass of
         every joint's heat map) comes last."""
-        if isinstance(images, (list, tuple)) and len(images) > 0 and torch.is_tensor(images[0]):
-            images = [images]
-        if not isinstance(images, (list, tuple)) or len(images) == 0:
-            raise ValueError("images must be a sequence of %d tensors or a sequence of such sequences"
-                             % self.num_cameras)
-        for t, frame_set in enumerate(images):
-            if not isinstance(frame_set, (list, tuple)) or len(frame_set) != self.num_cameras:
-                raise ValueError("frame set %d: expected a sequence of %d images (one per camera), got %s" % (
-                    t, self.num_cameras,
-                    len(frame_set) if isinstance(frame_set, (list, tuple)) else type(frame_set).__name__))
-        T = len(images)
-        flat = [img for frame_set in images for img in frame_set]
-        frames = N.frame_images(flat, (T, self.num_cameras), frame_format, frame_layout)
+        frames = image_frames(self.num_cameras, images, frame_format, frame_layout)
+        T = frames.lead[0]
         camera_mask = N.camera_mask(camera_mask, (T, self.num_cameras))
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d,
                          centers=N.centers(centers, T), return_spread=return_spread)
+
+    def detect_subjects(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, max_subjects,
+                        frame_format=None, frame_layout=None, camera_mask=None, images=False, return_peaks=False,
+                        **params):
+        """Where the subjects are, for a time batch: imgs as forward_batch takes them -- or, with images=True, as
+        forward_images takes them -- -> `Subjects` (centers (T,K,3) world mm, views (T,K), members (T,K,C), error
+        (T,K); K = max_subjects), device tensors, no host synchronisation.
+        CenterDetect runs once on the frames; instead of ONE maximum per camera the top `max_peaks` local maxima of
+        every camera's heat map are kept (maxima of their (2 nms_radius + 1)^2 window above `min_peak`), grouped
+        across cameras by reprojection consistency (a group's peaks lie within `max_error_px` full-frame pixels of the
+        projection of the point two of them triangulate; at least `min_views` cameras), most views first, and every
+        group is triangulated with the arithmetic of the detected forward.  **params: max_peaks, nms_radius, min_views,
+        min_peak, max_error_px (_native.subjects_params: the library's defaults 50 / 4 / 2 / 24 are defaults, not
+        recommendations).  An empty subject has NaN centres, views 0, members -1.
+        camera_mask (T,C), frame_format, frame_layout, per-frame-set calibration (T,C,...): as forward_batch.
+        return_peaks: (subjects, peaks (T,C,max_peaks,3) = (x, y, value) in heat-map pixels).
+        A centre goes back in as `centers=` of forward_batch / forward_images (forward_subjects does that).  Robust
+        single-subject detection is max_subjects=1: the cameras whose maximum lies on something else are left out of
+        the triangulation instead of dragging it.
+        Not covered: the drivers (predict3D_frames), JarvisPredictor2D, analyze_frames, the camera-sharded path, and
+        identity across frames -- subject k of frame set t and of t+1 are unrelated."""
+        check_native_seam(self)
+        p = N.subjects_params(max_subjects, **params)
+        if images:
+            frames = image_frames(self.num_cameras, imgs, frame_format, frame_layout)
+        else:
+            frames = N.describe_frames(imgs, (None, self.num_cameras), frame_format, frame_layout)
+        T = frames.lead[0]
+        mask = N.camera_mask(camera_mask, (T, self.num_cameras))
+        calib = (cameraMatrices, intrinsicMatrices, distortionCoefficients)
+        per_frame = N.calibration(calib, T, self.num_cameras)[0] == "frames"
+        pr = self.native(frames.height, frames.width, time_batch=T)
+        (pr.set_calibration_frames if per_frame else pr.set_calibration)(*calib)
+        return pr.detect_subjects(frames, p, mask, return_peaks)
+
+    def forward_subjects(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, max_subjects,
+                         frame_format=None, frame_layout=None, camera_mask=None, images=False, return_2d=False,
+                         return_spread=False, **params):
+        """Several subjects in one time batch: detect_subjects, then one centred forward_batch (images=True:
+        forward_images) per subject k on the same frames with centers=subjects.centers[:, k].
+        -> points (T,K,J,3), confidences (T,K,J), valid (T,K) int32, subjects[, views][, spreads]: row (t, k) is row t
+        of that centred call, bit for bit; an empty subject (NaN centre) is an invalid row, valid 0.  return_2d /
+        return_spread: a tuple of K Views2D / Spread3D, one per subject, follows.  camera_mask and the other arguments:
+        as detect_subjects.  No host synchronisation."""
+        calib = (cameraMatrices, intrinsicMatrices, distortionCoefficients)
+        subjects = self.detect_subjects(imgs, *calib, max_subjects, frame_format=frame_format,
+                                        frame_layout=frame_layout, camera_mask=camera_mask, images=images, **params)
+        rows = []
+        for k in range(max_subjects):
+            kw = dict(frame_format=frame_format, frame_layout=frame_layout, camera_mask=camera_mask,
+                      return_2d=return_2d, centers=subjects.centers[:, k], return_spread=return_spread)
+            rows.append((self.forward_images if images else self.forward_batch)(imgs, *calib, **kw))
+        out = tuple(torch.stack([r[i] for r in rows], 1) for i in range(3)) + (subjects,)
+        for i in range(3, len(rows[0])):             # (views, then spreads: one per subject)
+            out += (tuple(r[i] for r in rows),)
+        return out
 
     @staticmethod
     def _batch(pr, res, mask, return_2d):
