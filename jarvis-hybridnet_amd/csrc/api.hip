@@ -5,7 +5,6 @@
 #include <cstdlib>
 #include "nets.h"
 #include "bifpn_node.h"
-#include "camera_mask.h"
 #include "views2d.h"
 #include "subjects.h"
 
@@ -235,9 +234,9 @@ int jh_reproject_forward(const float* heatmaps_padded_dev, int cams, int joints,
   carve_reproject(c, cams, joints, hs, grid_size, &w);
   JH_REQUIRE(c.fits(), "workspace smaller than jh_reproject_workspace_bytes()");
   if (launch_to_channel_last(heatmaps_padded_dev, w.heat, s)) return 1;
-  if (launch_reproject(cam_dev, intr_dev, dist_dev, /*calib_fs=*/0, center3d_dev, center_hm_dev, w.heat.p, w.coarse,
+  if (launch_reproject(Calib{cam_dev, intr_dev, dist_dev, /*fs=*/0}, center3d_dev, center_hm_dev, w.heat.p, w.coarse,
                        w.vol.p, idx_dev, 1, cams, grid_size, grid_spacing, hs, w.heat.Cp,
-                       /*heat_pad=*/1, /*div255=*/0, s)) return 1;
+                       /*heat_pad=*/1, /*div255=*/0, /*mask=*/nullptr, s)) return 1;
   return launch_from_channel_last(w.vol, vol_dev, s);
 }
 
@@ -314,8 +313,8 @@ int jh_reconstruct_point(const float* points2d_dev, const float* maxvals_dev, in
   JH_REQUIRE(c.fits(), "workspace smaller than jh_reconstruct_workspace_bytes()");
   hipLaunchKernelGGL(pack_det_kernel, dim3(1), dim3(64), 0, s, points2d_dev, maxvals_dev, w.det, cams);
   JH_CHECK_HIP(hipGetLastError());
-  return launch_triangulate(w.det, cam_dev, intr_dev, dist_dev, /*calib_fs=*/0, point3d_dev, w.c3i, w.chm, w.valid, 1,
-                            cams, 1.f, 1.f, 1.f, 0, 1 << 20, 1 << 20, s);
+  return launch_triangulate(w.det, Calib{cam_dev, intr_dev, dist_dev, /*fs=*/0}, point3d_dev, w.c3i, w.chm, w.valid, 1,
+                            cams, 1.f, 1.f, 1.f, 0, 1 << 20, 1 << 20, /*mask=*/nullptr, nullptr, nullptr, s);
 }
 
 }  // extern "C"
@@ -426,32 +425,42 @@ static int frame_source(int format, int h, int w, FrameSource* out) {
 static_assert(JH_FRAME_SURFACE == kSrcYuvSurface && JH_FRAME_SENSOR == kSrcSensor,
               "frame format codes of the C ABI are preprocess.h's SRC");
 
-// FrameSource of a per-image call (jh_predictor_forward_images / jh_predictor2d_forward_images): `format` with exactly
-// the description it needs, checked as the contiguous entry points check it.  image_stride of a description is here
-// only the extent every plane ends within; every image is image 0 of its own pointer, so a semi-planar surface takes
-// the 2-byte chroma load whatever the parity of that extent (the kernel looks at the image's own base).
-static int images_source(int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor, int h, int w,
-                         FrameSource* out) {
-  JH_REQUIRE(format >= JH_FRAME_RGB_F32 && format <= JH_FRAME_SENSOR, "forward_images: unknown frame format");
+// FrameSource of an entry point that takes any format (`who`: its name in the messages): `format` with exactly the
+// description it needs, each checked by its one validation above.  per_image (jh_predictor_forward_images and its
+// like): image_stride of a description is then only the extent every plane ends within; every image is image 0 of its
+// own pointer, so a semi-planar surface takes the 2-byte chroma load whatever the parity of that extent (the kernel
+// looks at the image's own base).
+static int call_source(const char* who, int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor, int h,
+                       int w, bool per_image, FrameSource* out) {
+  const std::string name(who);
+  JH_REQUIRE(format >= JH_FRAME_RGB_F32 && format <= JH_FRAME_SENSOR, name + ": unknown frame format");
   JH_REQUIRE((yuv != nullptr) == (format == JH_FRAME_SURFACE),
-             "forward_images: JH_FRAME_SURFACE, and no other format, comes with a jh_yuv_surface");
+             name + ": JH_FRAME_SURFACE, and no other format, comes with a jh_yuv_surface");
   JH_REQUIRE((sensor != nullptr) == (format == JH_FRAME_SENSOR),
-             "forward_images: JH_FRAME_SENSOR, and no other format, comes with a jh_sensor_surface");
-  if (format == JH_FRAME_SURFACE) {
-    if (frame_source(yuv, h, w, out)) return 1;
+             name + ": JH_FRAME_SENSOR, and no other format, comes with a jh_sensor_surface");
+  if (format == JH_FRAME_SURFACE ? frame_source(yuv, h, w, out)
+      : format == JH_FRAME_SENSOR ? frame_source(sensor, h, w, out)
+                                  : frame_source(format, h, w, out)) return 1;
+  if (per_image && format == JH_FRAME_SURFACE) {
     auto& d = std::get<SrcDesc<kSrcYuvSurface>>(out->desc);
     d.pair = d.c_step == 2;
-  } else if (format == JH_FRAME_SENSOR) {
-    if (frame_source(sensor, h, w, out)) return 1;
-  } else if (frame_source(format, h, w, out)) {
-    return 1;
   }
-  out->per_image = true;
+  out->per_image = per_image;
   return 0;
 }
 
+// A buffer that the first call of its kind allocates (never jh_predictor_create): `bytes` of the predictor's memory,
+// not inside a stream capture -- `what` is the site's own message for that.
+template <typename T>
+static int first_call_alloc(Scratch& mem, hipStream_t s, size_t bytes, const char* what, T** out) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(s, &cs);
+  JH_REQUIRE(cs == hipStreamCaptureStatusNone, what);
+  return mem.get(reinterpret_cast<void**>(out), bytes);
+}
+
 // The host table of a per-image call checked and sent into the predictor's device table (allocated by the first such
-// call of a predictor, never inside a stream capture) on the caller's stream.
+// call of a predictor) on the caller's stream.
 static int upload_images(Scratch& mem, const void*** table, const void* const* images_host, int n_images, int want,
                          int format, hipStream_t s) {
   JH_REQUIRE(images_host, "forward_images: null image table");
@@ -461,13 +470,8 @@ static int upload_images(Scratch& mem, const void*** table, const void* const* i
     JH_REQUIRE(format != JH_FRAME_RGB_F32 || reinterpret_cast<uintptr_t>(images_host[i]) % 4 == 0,
                "forward_images: an fp32 image that is not 4-byte aligned");
   }
-  if (!*table) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cs);
-    JH_REQUIRE(cs == hipStreamCaptureStatusNone, "the first forward_images call of a predictor allocates its pointer "
-               "table: make it outside a stream capture");
-    if (mem.get(reinterpret_cast<void**>(table), (size_t)want * sizeof(void*))) return 1;
-  }
+  if (!*table && first_call_alloc(mem, s, (size_t)want * sizeof(void*), "the first forward_images call of a predictor "
+                                  "allocates its pointer table: make it outside a stream capture", table)) return 1;
   for (int off = 0; off < n_images; off += kPtrChunk) {
     PtrChunk c{};
     const int count = n_images - off < kPtrChunk ? n_images - off : kPtrChunk;
@@ -477,6 +481,71 @@ static int upload_images(Scratch& mem, const void*** table, const void* const* i
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }
+
+// What the creation of both predictors shares: the precision resolved into cfg (the predictor's own setting;
+// JH_PRECISION_DEFAULT follows the process-wide default), and EffTrackPlans set up, before build(), with it and with
+// the forms of the predictor's time-batch class (EffTrackPlan::node_rows, Plan::norm_block_kb).
+struct PlanSetup {
+  int precision = 0, node_rows = -1, norm_kb = 0;
+  int init(jh_predictor_config* cfg, int rows, int kb) {
+    JH_REQUIRE(cfg->precision >= JH_PRECISION_DEFAULT && cfg->precision <= JH_PRECISION_BF16X3_WIDE,
+               "jh_predictor_config.precision: unknown mode");
+    if (cfg->precision == JH_PRECISION_DEFAULT) cfg->precision = precision_mode();
+    precision = cfg->precision; node_rows = rows; norm_kb = kb;
+    return 0;
+  }
+  std::unique_ptr<EffTrackPlan> efftrack() const {
+    std::unique_ptr<EffTrackPlan> p(new EffTrackPlan());
+    p->precision = precision; p->node_rows = node_rows; p->norm_block_kb = norm_kb;
+    return p;
+  }
+};
+
+// preds * (downsampling_scale * 2), jarvis3D.py:138-141,158-160: CenterDetect's arg-max (or peaks) in full-frame pixels
+struct Scale2 { float x, y; };
+static Scale2 center_scale2(const jh_predictor_config& c) {
+  return {(float)((double)c.img_w / (double)c.center_size) * 2.f,
+          (float)((double)c.img_h / (double)c.center_size) * 2.f};
+}
+
+// What one call is, handed down to the stage functions: its frames and their source, the camera mask in force and the
+// stream.  (A stage-3 call has no frames: it gives the mask and the stream.)
+struct Call {
+  const void* frames = nullptr;              // contiguous frames; per-image: the device table (never dereferenced here)
+  FrameSource fs;
+  const unsigned char* mask = nullptr;       // [T][C] device bytes, nullptr = no mask (the plain kernels)
+  // what the launches read the frame pointer(s) through: the per-image table, the one-pointer cell of a forward that
+  // is being captured, or nullptr = `frames` itself
+  const void* const* cell = nullptr;
+  hipStream_t s = nullptr;
+};
+static Call make_call(const void* frames, const FrameSource& fs, void* stream, const unsigned char* mask = nullptr) {
+  Call c;
+  c.frames = frames; c.fs = fs; c.mask = mask; c.s = static_cast<hipStream_t>(stream);
+  if (fs.per_image) c.cell = static_cast<const void* const*>(frames);
+  return c;
+}
+static Call stage3_call(void* stream, const unsigned char* mask = nullptr) {
+  Call c;
+  c.mask = mask; c.s = static_cast<hipStream_t>(stream);
+  return c;
+}
+
+// The form of a whole-path forward, which names its graph slot: one slot per frame format (kSrc*, preprocess.h) and
+// per combination of the four flags.  masked: the masked kernels.  per_image: slots of its OWN -- a stream of per-image
+// calls and a stream of contiguous calls of one format never re-record each other.  centred: the forward from
+// caller-supplied centres (centers_on), which records no stage 1 -- a tracking loop that falls back to one detected
+// call between centred ones never re-records.  spread: the spread form of the tail (spread_on), which is another
+// recording -- a loop that alternates spread-on and spread-off calls never re-records either.
+constexpr int kGraphFmts = kSrcSensor + 1;
+struct ForwardForm {
+  int fmt = 0;
+  bool masked = false, per_image = false, centred = false, spread = false;
+  constexpr int index() const { return (((spread * 2 + centred) * 2 + per_image) * 2 + masked) * kGraphFmts + fmt; }
+};
+constexpr int kGraphSlots = kGraphFmts << 4;  // (four flags)
+static_assert(ForwardForm{kGraphFmts - 1, true, true, true, true}.index() == kGraphSlots - 1,
+              "the largest ForwardForm::index() is the last graph slot");
 
 struct jh_predictor {
   jh_predictor_config cfg{};
@@ -489,23 +558,22 @@ struct jh_predictor {
   // Per-frame calibration (jh_predictor_set_calibration_frames): T rows of the three arrays above, allocated by the
   // first such call.  calib_fs is the frame stride every launch that reads calibration is given: 0 -- all frames read
   // cam / intr / dist --, or C -- frame t reads row t of cam_f / intr_f / dist_f.  A call that starts at frame t0
-  // (stage 3, views2d) passes the pointers of row t0, as it passes the centres' and the mask's.
+  // (stage 3, views2d) passes the rows from t0 on, as it passes the centres' and the mask's.
   float *cam_f = nullptr, *intr_f = nullptr, *dist_f = nullptr;
   int calib_fs = 0;
-  const float* cam_at(int t0) const { return calib_fs ? cam_f + (size_t)t0 * calib_fs * 12 : cam; }
-  const float* intr_at(int t0) const { return calib_fs ? intr_f + (size_t)t0 * calib_fs * 9 : intr; }
-  const float* dist_at(int t0) const { return calib_fs ? dist_f + (size_t)t0 * calib_fs * 5 : dist; }
+  Calib calib_at(int t0) const {
+    return calib_fs ? Calib{cam_f, intr_f, dist_f, calib_fs}.at(t0) : Calib{cam, intr, dist, 0};
+  }
   float *det_all = nullptr, *c3f = nullptr;
   // Crop centres, truncated 3D centre and validity of a time batch: written by stage 2 (triangulation), read by
   // stage 3.  TWO sets: the staged entry points alternate between them, so that stage 3 of time batch i may run
   // on a second stream while stage 2 of batch i+1 (which writes the other set) is under way -- a stage-3 call
   // reads the set of the stage-2 call that preceded it in host call order (distributed.py).  The whole-path
   // forward always uses set 0 (its captured graph bakes the pointers).
-  int *c3i_[2] = {nullptr, nullptr}, *chm_[2] = {nullptr, nullptr}, *valid_[2] = {nullptr, nullptr};
+  struct CentreSet { int *c3i = nullptr, *chm = nullptr, *valid = nullptr; };
+  CentreSet cset[2];
   int slot = 0;
-  int* c3i_cur() const { return c3i_[slot]; }
-  int* chm_cur() const { return chm_[slot]; }
-  int* valid_cur() const { return valid_[slot]; }
+  const CentreSet& cur() const { return cset[slot]; }
   float2* coarse = nullptr;
   double* sa_partial = nullptr;
   int* sa_max = nullptr;
@@ -513,33 +581,21 @@ struct jh_predictor {
   // call, predict3D.py:82-85 -- 150+ launches of small kernels, launch-bound when issued one by one)
   int use_graph = 0;
   const void** frames_cell = nullptr;        // device: the frame pointer of the current call
-  const void* const* cur_cell = nullptr;     // non-null only while the forward is being captured
   // per-image frames (jh_predictor_forward_images): [T * C] device pointers, written on the caller's stream before
   // every such forward; the launches, captured or not, read this table.  Allocated by the first such call.
   const void** frames_table = nullptr;
-  // what a launch of source fs reads its frame pointer(s) through
-  const void* const* cell_for(const FrameSource& fs) const { return fs.per_image ? frames_table : cur_cell; }
   float *g_points = nullptr, *g_conf = nullptr;
   hipStream_t gstream = nullptr;             // capture stream (the caller's may be the null stream)
-  // One slot per frame format (kSrc*, preprocess.h); [kGraphFmts + fmt]: the masked form of that format;
-  // [2 * kGraphFmts + ...]: the same again for the per-image form, which has slots of its OWN -- a stream of
-  // per-image calls and a stream of contiguous calls of one format never re-record each other; [4 * kGraphFmts + ...]:
-  // all of these again for the forward from caller-supplied centres (centers_on), which records no stage 1 -- a
-  // tracking loop that falls back to one detected call between centred ones never re-records; [8 * kGraphFmts + ...]:
-  // all sixteen again for the spread form of the tail (spread_on), which is another recording -- a loop that
-  // alternates spread-on and spread-off calls never re-records either.  A launch
-  // carries its source's description by value, so a recording has ONE source: the slot keeps the FrameSource its
-  // graph was captured with, and a call with another one records again (forward_graph).  The same holds for the
-  // calibration's form: a recording holds the pointers and the frame stride (calib_fs) it was captured with.
-  static constexpr int kGraphFmts = kSrcSensor + 1;
+  // One slot per ForwardForm.  A launch carries its source's description by value, so a recording has ONE source: the
+  // slot keeps the FrameSource its graph was captured with, and a call with another one records again (forward_graph).
+  // The same holds for the calibration's form: a recording holds the pointers and the frame stride (calib_fs) it was
+  // captured with.
   struct GraphSlot { hipGraphExec_t exec = nullptr; FrameSource src; int calib_fs = 0; };
-  GraphSlot gslot[16 * kGraphFmts];
-  // Camera mask (camera_mask.h).  mask_buf [T][C]: the predictor's copy of the current call's mask -- the masked
-  // kernels (and a captured graph of them) read this buffer, so the mask may change from call to call.  mask_cur:
-  // the mask of the call under way, nullptr = no mask (the plain kernels).  n_active / n_detect [T]: written by
-  // the masked triangulation.
+  GraphSlot gslot[kGraphSlots];
+  // Camera mask (nets.h).  mask_buf [T][C]: the predictor's copy of the mask of a whole-path forward -- the masked
+  // kernels (and a captured graph of them) read this buffer, so the mask may change from call to call.
+  // n_active / n_detect [T]: written by the masked triangulation.
   unsigned char* mask_buf = nullptr;
-  const unsigned char* mask_cur = nullptr;
   int *n_active = nullptr, *n_detect = nullptr;
   // Caller-supplied centres (jh_predictor_set_centers).  centers_buf [T][3]: the predictor's copy of the centres in
   // force, allocated by the first such call -- the centred stage 2 (and a captured graph of it) reads this buffer, so
@@ -570,37 +626,26 @@ struct jh_predictor {
   }
 
   // 3D stage for frames t0 .. t0+T3-1 of the batch (heat_all holds those frames)
-  int run_3d(const float* heat_all, int t0, float* heatmap_final, float* points, float* conf,
-             hipStream_t s, const HeatLayout* layout = nullptr) {
+  int run_3d(const Call& call, const float* heat_all, int t0, float* heatmap_final, float* points, float* conf,
+             const HeatLayout* layout = nullptr) {
+    hipStream_t s = call.s;
     const double g3 = (double)G * G * G;
     // algorithmic traffic of the gather: every heatmap byte once in, the volume once out
-    if (mask_cur) {
-      // (algorithmic traffic as for all cameras: an upper bound, the unmasked cameras' heatmaps are what is read)
-      JH_PROF("reproject_gather_masked", 0.0, 4.0 * T3 * ((double)C * Hh * Hh * J + g3 * J),
-              launch_reproject_masked(cam_at(t0), intr_at(t0), dist_at(t0), calib_fs, c3i_cur() + t0 * 3,
-                                      chm_cur() + t0 * C * 2, heat_all, coarse, v2v->input.p, nullptr, T3, C, G,
-                                      cfg.grid_spacing, hs, Jp,
-                                      /*heat_pad=*/0, /*div255=*/1, mask_cur + (size_t)t0 * C, s, layout));
-    } else {
-    JH_PROF("reproject_gather", 0.0, 4.0 * T3 * ((double)C * Hh * Hh * J + g3 * J),
-            launch_reproject(cam_at(t0), intr_at(t0), dist_at(t0), calib_fs, c3i_cur() + t0 * 3,
-                             chm_cur() + t0 * C * 2, heat_all, coarse, v2v->input.p, nullptr, T3, C, G,
-                             cfg.grid_spacing, hs, Jp,
-                             /*heat_pad=*/0, /*div255=*/1, s, layout));
-    }
+    // (under a mask as for all cameras: an upper bound, the unmasked cameras' heatmaps are what is read)
+    JH_PROF(call.mask ? "reproject_gather_masked" : "reproject_gather", 0.0,
+            4.0 * T3 * ((double)C * Hh * Hh * J + g3 * J),
+            launch_reproject(calib_at(t0), cur().c3i + t0 * 3, cur().chm + t0 * C * 2, heat_all, coarse, v2v->input.p,
+                             nullptr, T3, C, G, cfg.grid_spacing, hs, Jp, /*heat_pad=*/0, /*div255=*/1,
+                             call.mask ? call.mask + (size_t)t0 * C : nullptr, s, layout));
     if (v2v->run(s)) return 1;
+    SoftargmaxSpread sp = spread;
     if (spread_on) {
-      SoftargmaxSpread sp = spread;
-      sp.valid = valid_cur() + t0;
+      sp.valid = cur().valid + t0;
       sp.cov = sp_cov + (size_t)t0 * J * 6; sp.peak = sp_peak + (size_t)t0 * J * 3; sp.mass = sp_mass + (size_t)t0 * J;
-      JH_PROF("softargmax_spread", 0.0, 4.0 * T3 * (g3 / 8) * J,
-              launch_softargmax(v2v->output.p, c3i_cur() + t0 * 3, sa_partial, sa_max, points, conf,
-                                heatmap_final, T3, J, Jp, Gh, cfg.grid_spacing, cfg.roi_cube_size, s, &sp));
-      return 0;
     }
-    JH_PROF("softargmax", 0.0, 4.0 * T3 * (g3 / 8) * J,
-            launch_softargmax(v2v->output.p, c3i_cur() + t0 * 3, sa_partial, sa_max, points, conf,
-                              heatmap_final, T3, J, Jp, Gh, cfg.grid_spacing, cfg.roi_cube_size, s));
+    JH_PROF(spread_on ? "softargmax_spread" : "softargmax", 0.0, 4.0 * T3 * (g3 / 8) * J,
+            launch_softargmax(v2v->output.p, cur().c3i + t0 * 3, sa_partial, sa_max, points, conf, heatmap_final, T3, J,
+                              Jp, Gh, cfg.grid_spacing, cfg.roi_cube_size, s, spread_on ? &sp : nullptr));
     return 0;
   }
 };
@@ -628,26 +673,17 @@ int jh_predictor_create(const jh_params* center_params, const jh_params* hybrid_
   // (... and with it the blocking of the InstanceNorm / pooled-sum passes, Plan::norm_block_kb; JH_NODE_ROWS=0 switches
   //  every class-dependent form off: one arithmetic for all time batches)
   const int norm_kb = node_rows && JH_ENV_KNOB("JH_NODE_ROWS") != 0 ? 64 : 0;
-  // precision: the predictor's own setting; JH_PRECISION_DEFAULT follows the process-wide default
-  JH_REQUIRE(cfg->precision >= JH_PRECISION_DEFAULT && cfg->precision <= JH_PRECISION_BF16X3_WIDE,
-             "jh_predictor_config.precision: unknown mode");
-  const int precision = cfg->precision == JH_PRECISION_DEFAULT ? precision_mode() : cfg->precision;
-  pr->cfg.precision = precision;
+  PlanSetup setup;
+  if (setup.init(&pr->cfg, node_rows, norm_kb)) return 1;
   if (center_params) {
-    pr->center.reset(new EffTrackPlan());
-    pr->center->precision = precision;
-    pr->center->node_rows = node_rows;
-    pr->center->norm_block_kb = norm_kb;
+    pr->center = setup.efftrack();
     if (pr->center->build(center_params->map, "", cfg->center_model, 1, N, cfg->center_size,
                           cfg->center_size)) return 1;
   }
-  pr->kp.reset(new EffTrackPlan());
-  pr->kp->precision = precision;
-  pr->kp->node_rows = node_rows;
-  pr->kp->norm_block_kb = norm_kb;
+  pr->kp = setup.efftrack();
   if (pr->kp->build(hybrid_params->map, "effTrack.", cfg->kp_model, pr->J, N, pr->B, pr->B)) return 1;
   pr->v2v.reset(new V2VPlan());
-  pr->v2v->precision = precision;
+  pr->v2v->precision = setup.precision;
   pr->v2v->norm_block_kb = norm_kb;
   if (pr->v2v->build(hybrid_params->map, "v2vNet.", pr->J, pr->T3, pr->G)) return 1;
   auto& m = pr->mem;
@@ -657,10 +693,10 @@ int jh_predictor_create(const jh_params* center_params, const jh_params* hybrid_
   if (m.get(reinterpret_cast<void**>(&pr->dist), (size_t)C * 5 * sizeof(float))) return 1;
   if (m.get(reinterpret_cast<void**>(&pr->det_all), (size_t)T * C * 3 * sizeof(float))) return 1;
   if (m.get(reinterpret_cast<void**>(&pr->c3f), (size_t)T * 3 * sizeof(float))) return 1;
-  for (int k = 0; k < 2; ++k) {
-    if (m.get(reinterpret_cast<void**>(&pr->c3i_[k]), (size_t)T * 3 * sizeof(int))) return 1;
-    if (m.get(reinterpret_cast<void**>(&pr->chm_[k]), (size_t)T * C * 2 * sizeof(int))) return 1;
-    if (m.get(reinterpret_cast<void**>(&pr->valid_[k]), (size_t)T * sizeof(int))) return 1;
+  for (auto& cs : pr->cset) {
+    if (m.get(reinterpret_cast<void**>(&cs.c3i), (size_t)T * 3 * sizeof(int))) return 1;
+    if (m.get(reinterpret_cast<void**>(&cs.chm), (size_t)T * C * 2 * sizeof(int))) return 1;
+    if (m.get(reinterpret_cast<void**>(&cs.valid), (size_t)T * sizeof(int))) return 1;
   }
   if (m.get(reinterpret_cast<void**>(&pr->coarse),
             (size_t)pr->T3 * C * pr->Gh * pr->Gh * pr->Gh * sizeof(float2))) return 1;
@@ -669,7 +705,7 @@ int jh_predictor_create(const jh_params* center_params, const jh_params* hybrid_
     if (m.get(reinterpret_cast<void**>(&pr->sa_partial), pb + mb)) return 1;
     pr->sa_max = reinterpret_cast<int*>(reinterpret_cast<char*>(pr->sa_partial) + pb);
   }
-  for (int k = 0; k < 2; ++k) JH_CHECK_HIP(hipMemset(pr->valid_[k], 0, (size_t)T * sizeof(int)));
+  for (auto& cs : pr->cset) JH_CHECK_HIP(hipMemset(cs.valid, 0, (size_t)T * sizeof(int)));
   if (m.get(reinterpret_cast<void**>(&pr->mask_buf), (size_t)T * C)) return 1;
   if (m.get(reinterpret_cast<void**>(&pr->n_active), (size_t)T * sizeof(int))) return 1;
   if (m.get(reinterpret_cast<void**>(&pr->n_detect), (size_t)T * sizeof(int))) return 1;
@@ -733,13 +769,11 @@ int jh_predictor_set_calibration_frames(jh_predictor* pr, const float* cam_dev, 
   JH_REQUIRE(cam_dev && intr_dev && dist_dev, "jh_predictor_set_calibration_frames: null calibration pointer");
   const size_t rows = (size_t)pr->T * pr->C;
   if (!pr->cam_f) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cs);
-    JH_REQUIRE(cs == hipStreamCaptureStatusNone, "the first jh_predictor_set_calibration_frames call of a predictor "
-               "allocates its per-frame calibration: make it outside a stream capture");
     // (one allocation: cam_f is set last, so a failure leaves the predictor as it was)
     float* base = nullptr;
-    if (pr->mem.get(reinterpret_cast<void**>(&base), rows * 26 * sizeof(float))) return 1;
+    if (first_call_alloc(pr->mem, s, rows * 26 * sizeof(float), "the first jh_predictor_set_calibration_frames call of "
+                         "a predictor allocates its per-frame calibration: make it outside a stream capture", &base))
+      return 1;
     pr->intr_f = base + rows * 12;
     pr->dist_f = base + rows * 21;
     pr->cam_f = base;
@@ -758,13 +792,10 @@ int jh_predictor_set_centers(jh_predictor* pr, const float* centers_dev, void* s
     pr->centers_on = false;
     return 0;
   }
-  if (!pr->centers_buf) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cs);
-    JH_REQUIRE(cs == hipStreamCaptureStatusNone, "the first jh_predictor_set_centers call of a predictor allocates its "
-               "centre buffer: make it outside a stream capture");
-    if (pr->mem.get(reinterpret_cast<void**>(&pr->centers_buf), (size_t)pr->T * 3 * sizeof(float))) return 1;
-  }
+  if (!pr->centers_buf &&
+      first_call_alloc(pr->mem, s, (size_t)pr->T * 3 * sizeof(float), "the first jh_predictor_set_centers call of a "
+                       "predictor allocates its centre buffer: make it outside a stream capture", &pr->centers_buf))
+    return 1;
   JH_CHECK_HIP(hipMemcpyAsync(pr->centers_buf, centers_dev, (size_t)pr->T * 3 * sizeof(float), hipMemcpyDeviceToDevice,
                               s));
   pr->centers_on = true;
@@ -811,13 +842,15 @@ int jh_predictor_debug_v2v(jh_predictor* pr, float* out_dev, void* stream) {
 }
 
 // Stage 1 up to CenterDetect's heat map (pr->center->heat): resize or fused stem, then the plan
-static int center_heat_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, hipStream_t s) {
+static int center_heat_impl(jh_predictor* pr, const Call& call) {
+  hipStream_t s = call.s;
+  const FrameSource& fs = call.fs;
   JH_REQUIRE(pr->center, "predictor was created without CenterDetect weights");
   const int N = pr->T * pr->Cloc, S = pr->cfg.center_size;
   if (pr->center->stem_fusable) {
     // resize + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->center->stem_src;
-    src.mode = 1; src.frames = frames_dev; src.frames_cell = pr->cell_for(fs); src.source = fs;
+    src.mode = 1; src.frames = call.frames; src.frames_cell = call.cell; src.source = fs;
     src.H = pr->cfg.img_h; src.W = pr->cfg.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = pr->cfg.mean[i]; src.stdv[i] = pr->cfg.std[i]; }
     // algorithmic bytes of the fused launch: the four bilinear taps of every network-input pixel (px_bytes
@@ -825,16 +858,15 @@ static int center_heat_impl(jh_predictor* pr, const void* frames_dev, const Fram
     pr->center->set_stem_traffic((double)N * S * S * (4.0 * fs.px_bytes() + pr->center->stem_channels()));
   } else {
     JH_PROF("preprocess_resize", 0.0, (double)N * S * S * (4.0 * fs.px_bytes() + 3 * 4),
-            launch_preprocess_resize(frames_dev, fs, pr->center->input.p, N, pr->cfg.img_h,
-                                     pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, pr->cell_for(fs)));
+            launch_preprocess_resize(call.frames, fs, pr->center->input.p, N, pr->cfg.img_h,
+                                     pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, call.cell));
   }
   return pr->center->run(s);
 }
 
-static int stage_center_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* det_dev,
-                             void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (center_heat_impl(pr, frames_dev, fs, s)) return 1;
+static int stage_center_impl(jh_predictor* pr, const Call& call, float* det_dev) {
+  hipStream_t s = call.s;
+  if (center_heat_impl(pr, call)) return 1;
   const int N = pr->T * pr->Cloc;
   const Act& h = pr->center->heat;
   JH_PROF("center_argmax", 0.0, 4.0 * N * h.H * h.W,
@@ -844,17 +876,17 @@ static int stage_center_impl(jh_predictor* pr, const void* frames_dev, const Fra
 
 int jh_predictor_stage_center(jh_predictor* pr, const float* frames_dev, float* det_dev,
                               void* stream) {
-  return stage_center_impl(pr, frames_dev, fixed_source(kSrcRgbF32), det_dev, stream);
+  return stage_center_impl(pr, make_call(frames_dev, fixed_source(kSrcRgbF32), stream), det_dev);
 }
 int jh_predictor_stage_center_u8(jh_predictor* pr, const uint8_t* frames_dev, float* det_dev,
                                  void* stream) {
-  return stage_center_impl(pr, frames_dev, fixed_source(kSrcBgrU8), det_dev, stream);
+  return stage_center_impl(pr, make_call(frames_dev, fixed_source(kSrcBgrU8), stream), det_dev);
 }
 
-static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs,
-                                const float* det_all_dev, float* heat_dev, void* stream,
+static int stage_keypoints_impl(jh_predictor* pr, const Call& call, const float* det_all_dev, float* heat_dev,
                                 int det_blocks = 1, bool next_centre_set = false) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = call.s;
+  const FrameSource& fs = call.fs;
   const auto& c = pr->cfg;
   if (next_centre_set) pr->slot ^= 1;        // (the staged API: the previous batch's stage 3 may still read the other set)
   if (pr->centers_on) {                      // (no detections are read, none are kept: `det` may be NULL)
@@ -869,26 +901,17 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, const 
     JH_CHECK_HIP(hipGetLastError());
     det_all_dev = pr->det_all;
   }
-  // preds * (downsampling_scale * 2), jarvis3D.py:138-141,158-160
-  const float sx2 = (float)((double)c.img_w / (double)c.center_size) * 2.f;
-  const float sy2 = (float)((double)c.img_h / (double)c.center_size) * 2.f;
+  const jh_predictor::CentreSet& cs = pr->cur();
   if (pr->centers_on) {
-    // the centres of jh_predictor_set_centers in place of a triangulation; masked or not by the mask pointer
+    // the centres of jh_predictor_set_centers in place of a triangulation
     JH_PROF("centers", 0.0, 0.0,
-            launch_centers(pr->centers_buf, pr->cam_at(0), pr->intr_at(0), pr->dist_at(0), pr->calib_fs, pr->c3f,
-                           pr->c3i_cur(), pr->chm_cur(), pr->valid_cur(), pr->T, pr->C, pr->B / 2, c.img_w, c.img_h,
-                           pr->mask_cur, pr->n_active, pr->n_detect, s));
-  } else if (pr->mask_cur) {
-    JH_PROF("triangulate_masked", 0.0, 0.0,
-            launch_triangulate_masked(det_all_dev, pr->cam_at(0), pr->intr_at(0), pr->dist_at(0), pr->calib_fs, pr->c3f,
-                                      pr->c3i_cur(), pr->chm_cur(), pr->valid_cur(), pr->T, pr->C, sx2, sy2, 255.f,
-                                      pr->B / 2,
-                                      c.img_w, c.img_h, pr->mask_cur, pr->n_active, pr->n_detect, s));
+            launch_centers(pr->centers_buf, pr->calib_at(0), pr->c3f, cs.c3i, cs.chm, cs.valid, pr->T, pr->C, pr->B / 2,
+                           c.img_w, c.img_h, call.mask, pr->n_active, pr->n_detect, s));
   } else {
-  JH_PROF("triangulate", 0.0, 0.0,
-          launch_triangulate(det_all_dev, pr->cam_at(0), pr->intr_at(0), pr->dist_at(0), pr->calib_fs, pr->c3f,
-                             pr->c3i_cur(), pr->chm_cur(), pr->valid_cur(), pr->T, pr->C, sx2, sy2, 255.f, pr->B / 2,
-                             c.img_w, c.img_h, s));
+    const Scale2 k = center_scale2(c);
+    JH_PROF(call.mask ? "triangulate_masked" : "triangulate", 0.0, 0.0,
+            launch_triangulate(det_all_dev, pr->calib_at(0), pr->c3f, cs.c3i, cs.chm, cs.valid, pr->T, pr->C, k.x, k.y,
+                               255.f, pr->B / 2, c.img_w, c.img_h, call.mask, pr->n_active, pr->n_detect, s));
   }
   if (det_all_dev != pr->det_all)
     JH_CHECK_HIP(hipMemcpyAsync(pr->det_all, det_all_dev, (size_t)pr->T * pr->C * 3 * sizeof(float),
@@ -896,15 +919,15 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, const 
   if (pr->kp->stem_fusable) {
     // crop + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->kp->stem_src;
-    src.mode = 2; src.frames = frames_dev; src.frames_cell = pr->cell_for(fs); src.source = fs;
-    src.center_hm = pr->chm_cur(); src.Cloc = pr->Cloc; src.C = pr->C; src.cam0 = c.cam_lo;
+    src.mode = 2; src.frames = call.frames; src.frames_cell = call.cell; src.source = fs;
+    src.center_hm = cs.chm; src.Cloc = pr->Cloc; src.C = pr->C; src.cam0 = c.cam_lo;
     src.H = c.img_h; src.W = c.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = c.mean[i]; src.stdv[i] = c.std[i]; }
     pr->kp->set_stem_traffic((double)pr->T * pr->Cloc * pr->B * pr->B * (fs.px_bytes() + pr->kp->stem_channels()));
   } else {
     JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->Cloc * pr->B * pr->B * (fs.px_bytes() + 12.0),
-            launch_preprocess_crop(frames_dev, fs, pr->chm_cur(), pr->kp->input.p, pr->T, pr->Cloc, pr->C,
-                                   c.cam_lo, c.img_h, c.img_w, pr->B, c.mean, c.std, s, pr->cell_for(fs)));
+            launch_preprocess_crop(call.frames, fs, cs.chm, pr->kp->input.p, pr->T, pr->Cloc, pr->C,
+                                   c.cam_lo, c.img_h, c.img_w, pr->B, c.mean, c.std, s, call.cell));
   }
   if (pr->kp->run(s)) return 1;
   if (heat_dev && heat_dev != pr->kp->heat.p)
@@ -915,37 +938,41 @@ static int stage_keypoints_impl(jh_predictor* pr, const void* frames_dev, const 
 
 int jh_predictor_stage_keypoints(jh_predictor* pr, const float* frames_dev,
                                  const float* det_all_dev, float* heat_dev, void* stream) {
-  return stage_keypoints_impl(pr, frames_dev, fixed_source(kSrcRgbF32), det_all_dev, heat_dev, stream, 1, true);
+  return stage_keypoints_impl(pr, make_call(frames_dev, fixed_source(kSrcRgbF32), stream), det_all_dev, heat_dev, 1,
+                              true);
 }
 int jh_predictor_stage_keypoints_u8(jh_predictor* pr, const uint8_t* frames_dev,
                                     const float* det_all_dev, float* heat_dev, void* stream) {
-  return stage_keypoints_impl(pr, frames_dev, fixed_source(kSrcBgrU8), det_all_dev, heat_dev, stream, 1, true);
+  return stage_keypoints_impl(pr, make_call(frames_dev, fixed_source(kSrcBgrU8), stream), det_all_dev, heat_dev, 1,
+                              true);
 }
 
 int jh_predictor_stage_keypoints_gathered(jh_predictor* pr, const void* frames_dev, int frames_u8,
                                           const float* det_gathered_dev, int n_blocks, float* heat_dev,
                                           void* stream) {
   JH_REQUIRE(n_blocks >= 1, "block count");
-  return stage_keypoints_impl(pr, frames_dev, fixed_source(frames_u8 ? kSrcBgrU8 : kSrcRgbF32), det_gathered_dev, heat_dev,
-                              stream, n_blocks, true);
+  return stage_keypoints_impl(pr, make_call(frames_dev, fixed_source(frames_u8 ? kSrcBgrU8 : kSrcRgbF32), stream),
+                              det_gathered_dev, heat_dev, n_blocks, true);
+}
+
+static int stage_3d_impl(jh_predictor* pr, const Call& call, const float* heat_all_dev, int t0, float* points_dev,
+                         float* conf_dev, int32_t* valid_dev, const HeatLayout* layout = nullptr) {
+  JH_REQUIRE(t0 >= 0 && t0 + pr->T3 <= pr->T, "frame range of the 3D stage");
+  if (pr->run_3d(call, heat_all_dev, t0, nullptr, points_dev, conf_dev, layout)) return 1;
+  if (valid_dev)
+    JH_CHECK_HIP(hipMemcpyAsync(valid_dev, pr->cur().valid + t0, (size_t)pr->T3 * sizeof(int),
+                                hipMemcpyDeviceToDevice, call.s));
+  return 0;
 }
 
 int jh_predictor_stage_3d(jh_predictor* pr, const float* heat_all_dev, int t0, float* points_dev,
                           float* conf_dev, int32_t* valid_dev, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  JH_REQUIRE(t0 >= 0 && t0 + pr->T3 <= pr->T, "frame range of the 3D stage");
-  if (pr->run_3d(heat_all_dev, t0, nullptr, points_dev, conf_dev, s)) return 1;
-  if (valid_dev)
-    JH_CHECK_HIP(hipMemcpyAsync(valid_dev, pr->valid_cur() + t0, (size_t)pr->T3 * sizeof(int),
-                                hipMemcpyDeviceToDevice, s));
-  return 0;
+  return stage_3d_impl(pr, stage3_call(stream), heat_all_dev, t0, points_dev, conf_dev, valid_dev);
 }
 
 int jh_predictor_stage_3d_blocks(jh_predictor* pr, const float* heat_blocks_dev, int n_blocks,
                                  int frames_per_block, int t_off, int t0, float* points_dev,
                                  float* conf_dev, int32_t* valid_dev, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  JH_REQUIRE(t0 >= 0 && t0 + pr->T3 <= pr->T, "frame range of the 3D stage");
   JH_REQUIRE(n_blocks >= 1 && pr->C % n_blocks == 0, "cameras must divide evenly over the blocks");
   JH_REQUIRE(t_off >= 0 && t_off + pr->T3 <= frames_per_block, "frame range inside a block");
   HeatLayout lay;
@@ -953,20 +980,15 @@ int jh_predictor_stage_3d_blocks(jh_predictor* pr, const float* heat_blocks_dev,
   lay.cams_per_block = pr->C / n_blocks;
   lay.frame_stride = (size_t)lay.cams_per_block * plane;
   lay.block_stride = (size_t)frames_per_block * lay.frame_stride;
-  if (pr->run_3d(heat_blocks_dev + (size_t)t_off * lay.frame_stride, t0, nullptr, points_dev, conf_dev, s,
-                 &lay)) return 1;
-  if (valid_dev)
-    JH_CHECK_HIP(hipMemcpyAsync(valid_dev, pr->valid_cur() + t0, (size_t)pr->T3 * sizeof(int),
-                                hipMemcpyDeviceToDevice, s));
-  return 0;
+  return stage_3d_impl(pr, stage3_call(stream), heat_blocks_dev + (size_t)t_off * lay.frame_stride, t0, points_dev,
+                       conf_dev, valid_dev, &lay);
 }
 
-static int forward_eager(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
-                         float* conf_dev, int32_t* valid_dev, void* stream) {
+static int forward_eager(jh_predictor* pr, const Call& call, float* points_dev, float* conf_dev, int32_t* valid_dev) {
   // (centres supplied by the caller: stage 1 does not run at all)
-  if (!pr->centers_on && stage_center_impl(pr, frames_dev, fs, pr->det_all, stream)) return 1;
-  if (stage_keypoints_impl(pr, frames_dev, fs, pr->det_all, nullptr, stream)) return 1;
-  return jh_predictor_stage_3d(pr, pr->kp->heat.p, 0, points_dev, conf_dev, valid_dev, stream);
+  if (!pr->centers_on && stage_center_impl(pr, call, pr->det_all)) return 1;
+  if (stage_keypoints_impl(pr, call, pr->det_all, nullptr)) return 1;
+  return stage_3d_impl(pr, call, pr->kp->heat.p, 0, points_dev, conf_dev, valid_dev);
 }
 
 // The forward as ONE graph launch.  Captured on first use (on the predictor's own stream: the
@@ -975,12 +997,11 @@ static int forward_eager(jh_predictor* pr, const void* frames_dev, const FrameSo
 // graph serves every later call: set the cell, launch the graph, copy the results out -- three
 // submissions instead of ~150.  Calibration lives in the predictor's buffers (set_calibration
 // copies into them), weights are immutable for the life of a predictor: nothing to invalidate.
-static int forward_graph(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
-                         float* conf_dev, int32_t* valid_dev, hipStream_t s) {
-  jh_predictor::GraphSlot& slot = pr->gslot[fs.fmt + (pr->mask_cur ? jh_predictor::kGraphFmts : 0) +
-                                            (fs.per_image ? 2 * jh_predictor::kGraphFmts : 0) +
-                                            (pr->centers_on ? 4 * jh_predictor::kGraphFmts : 0) +
-                                            (pr->spread_on ? 8 * jh_predictor::kGraphFmts : 0)];
+static int forward_graph(jh_predictor* pr, const Call& call, float* points_dev, float* conf_dev, int32_t* valid_dev) {
+  hipStream_t s = call.s;
+  const FrameSource& fs = call.fs;
+  const ForwardForm form{fs.fmt, call.mask != nullptr, fs.per_image, pr->centers_on, pr->spread_on};
+  jh_predictor::GraphSlot& slot = pr->gslot[form.index()];
   // the recorded launches hold the description they were captured with: another one records again (rare: a stream
   // keeps its layout, and a fixed format has nothing to differ in; the replay in flight is waited for before its
   // executable graph goes).  Likewise the calibration's form, shared or per frame: its pointers and frame stride are
@@ -994,9 +1015,13 @@ static int forward_graph(jh_predictor* pr, const void* frames_dev, const FrameSo
     hipGraph_t g = nullptr;
     if (!pr->gstream) JH_CHECK_HIP(hipStreamCreateWithFlags(&pr->gstream, hipStreamNonBlocking));
     JH_CHECK_HIP(hipStreamBeginCapture(pr->gstream, hipStreamCaptureModeRelaxed));
-    pr->cur_cell = pr->frames_cell;
-    const int rc = forward_eager(pr, nullptr, fs, pr->g_points, pr->g_conf, nullptr, pr->gstream);
-    pr->cur_cell = nullptr;
+    // the recording: this call on the capture stream, its frame pointer read through the cell (per-image: through the
+    // table, as every such call)
+    Call rec = call;
+    rec.s = pr->gstream;
+    rec.frames = nullptr;
+    if (!fs.per_image) rec.cell = pr->frames_cell;
+    const int rc = forward_eager(pr, rec, pr->g_points, pr->g_conf, nullptr);
     const hipError_t e = hipStreamEndCapture(pr->gstream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return 1; }
     JH_CHECK_HIP(e);
@@ -1008,29 +1033,14 @@ static int forward_graph(jh_predictor* pr, const void* frames_dev, const FrameSo
     slot.calib_fs = pr->calib_fs;
   }
   // (per-image: the recording reads frames_table, which this call's pointers have already been sent into)
-  if (!fs.per_image) hipLaunchKernelGGL(set_cell_kernel, dim3(1), dim3(1), 0, s, pr->frames_cell, frames_dev);
+  if (!fs.per_image) hipLaunchKernelGGL(set_cell_kernel, dim3(1), dim3(1), 0, s, pr->frames_cell, call.frames);
   JH_CHECK_HIP(hipGetLastError());
   JH_CHECK_HIP(hipGraphLaunch(slot.exec, s));
   const int n_pts = pr->T * pr->J * 3;
   hipLaunchKernelGGL(copy_out_kernel, dim3((n_pts + 255) / 256), dim3(256), 0, s, pr->g_points, pr->g_conf,
-                     pr->valid_[0], points_dev, conf_dev, valid_dev, n_pts, pr->T * pr->J, pr->T);
+                     pr->cset[0].valid, points_dev, conf_dev, valid_dev, n_pts, pr->T * pr->J, pr->T);
   JH_CHECK_HIP(hipGetLastError());
   return 0;
-}
-
-static int forward_unmasked(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
-                            float* conf_dev, int32_t* valid_dev, void* stream) {
-  JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
-  JH_REQUIRE(pr->T3 == pr->T, "forward needs time_batch_3d == time_batch");
-  JH_REQUIRE(frames_dev && points_dev && conf_dev, "null frame / output pointer");
-  pr->slot = 0;                               // (the whole-path forward and its captured graph: centre set 0)
-  // per-launch profiling needs the launches one by one; a caller that is itself capturing this
-  // stream gets the plain launches too (its graph then holds them)
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (pr->use_graph && !profiler().on) (void)hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs);
-  if (!pr->use_graph || profiler().on || cs != hipStreamCaptureStatusNone)
-    return forward_eager(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
-  return forward_graph(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, static_cast<hipStream_t>(stream));
 }
 
 // mask_dev != nullptr: the masked kernels, reading the predictor's copy of the mask (made here, on the caller's
@@ -1038,13 +1048,21 @@ static int forward_unmasked(jh_predictor* pr, const void* frames_dev, const Fram
 static int forward_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
                         float* conf_dev, int32_t* valid_dev, void* stream,
                         const unsigned char* mask_dev = nullptr) {
-  if (!mask_dev) return forward_unmasked(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
-  JH_CHECK_HIP(hipMemcpyAsync(pr->mask_buf, mask_dev, (size_t)pr->T * pr->C, hipMemcpyDeviceToDevice,
-                              static_cast<hipStream_t>(stream)));
-  pr->mask_cur = pr->mask_buf;
-  const int rc = forward_unmasked(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
-  pr->mask_cur = nullptr;
-  return rc;
+  if (mask_dev)
+    JH_CHECK_HIP(hipMemcpyAsync(pr->mask_buf, mask_dev, (size_t)pr->T * pr->C, hipMemcpyDeviceToDevice,
+                                static_cast<hipStream_t>(stream)));
+  const Call call = make_call(frames_dev, fs, stream, mask_dev ? pr->mask_buf : nullptr);
+  JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
+  JH_REQUIRE(pr->T3 == pr->T, "forward needs time_batch_3d == time_batch");
+  JH_REQUIRE(frames_dev && points_dev && conf_dev, "null frame / output pointer");
+  pr->slot = 0;                               // (the whole-path forward and its captured graph: centre set 0)
+  // per-launch profiling needs the launches one by one; a caller that is itself capturing this
+  // stream gets the plain launches too (its graph then holds them)
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (pr->use_graph && !profiler().on) (void)hipStreamIsCapturing(call.s, &cs);
+  if (!pr->use_graph || profiler().on || cs != hipStreamCaptureStatusNone)
+    return forward_eager(pr, call, points_dev, conf_dev, valid_dev);
+  return forward_graph(pr, call, points_dev, conf_dev, valid_dev);
 }
 int jh_predictor_forward(jh_predictor* pr, const float* frames_dev, float* points_dev,
                          float* conf_dev, int32_t* valid_dev, void* stream) {
@@ -1104,7 +1122,7 @@ int jh_predictor_forward_images(jh_predictor* pr, const void* const* images_host
   JH_REQUIRE(pr, "bad argument");
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
   FrameSource fs;
-  if (images_source(format, yuv, sensor, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
+  if (call_source("forward_images", format, yuv, sensor, pr->cfg.img_h, pr->cfg.img_w, true, &fs)) return 1;
   if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T * pr->C, format,
                     static_cast<hipStream_t>(stream))) return 1;
   // (the launches read the table: `frames` itself is not dereferenced)
@@ -1117,20 +1135,15 @@ int jh_predictor_stage_keypoints_masked(jh_predictor* pr, const void* frames_dev
   JH_REQUIRE(pr && mask_dev, "bad argument");
   JH_REQUIRE(format == JH_FRAME_RGB_F32 || format == JH_FRAME_BGR_U8, "masked stage 2: fp32 RGB or uint8 BGR frames");
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "masked stage 2 needs all cameras local");
-  pr->mask_cur = mask_dev;
-  const int rc = stage_keypoints_impl(pr, frames_dev, fixed_source(format), det_all_dev, heat_dev, stream, 1, true);
-  pr->mask_cur = nullptr;
-  return rc;
+  return stage_keypoints_impl(pr, make_call(frames_dev, fixed_source(format), stream, mask_dev), det_all_dev, heat_dev,
+                              1, true);
 }
 
 int jh_predictor_stage_3d_masked(jh_predictor* pr, const float* heat_all_dev, int t0, const uint8_t* mask_dev,
                                  float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
   JH_REQUIRE(pr && mask_dev, "bad argument");
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "masked stage 3 needs all cameras local");
-  pr->mask_cur = mask_dev;
-  const int rc = jh_predictor_stage_3d(pr, heat_all_dev, t0, points_dev, conf_dev, valid_dev, stream);
-  pr->mask_cur = nullptr;
-  return rc;
+  return stage_3d_impl(pr, stage3_call(stream, mask_dev), heat_all_dev, t0, points_dev, conf_dev, valid_dev);
 }
 
 int jh_predictor_debug_mask(jh_predictor* pr, int32_t* n_active_dev, int32_t* num_cams_detect_dev, void* stream) {
@@ -1156,13 +1169,13 @@ int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, co
     heat_all_dev = pr->kp->heat.p + (size_t)t0 * pr->C * pr->Hh * pr->Hh * pr->Jp;
   }
   if (!pr->v2d_max) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cs);
-    JH_REQUIRE(cs == hipStreamCaptureStatusNone, "the first jh_predictor_views2d call of a predictor allocates its "
-               "workspace: make it outside a stream capture");
+    // (two allocations: v2d_max is set last, so a failure leaves the predictor without either)
     const size_t n = joint_argmax_all_partials(N, pr->Hh, pr->Hh, pr->Jp);
-    if (pr->mem.get(reinterpret_cast<void**>(&pr->v2d_max), n * sizeof(float))) return 1;
+    float* pmax = nullptr;
+    if (first_call_alloc(pr->mem, s, n * sizeof(float), "the first jh_predictor_views2d call of a predictor allocates "
+                         "its workspace: make it outside a stream capture", &pmax)) return 1;
     if (pr->mem.get(reinterpret_cast<void**>(&pr->v2d_idx), n * sizeof(int))) return 1;
+    pr->v2d_max = pmax;
   }
   const double bytes = 4.0 * N * pr->Hh * pr->Hh * pr->Jp;
   JH_PROF("joint_argmax_all", 0.0, bytes,
@@ -1170,11 +1183,10 @@ int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, co
   // (the merge reads the partials of every slice and writes 24 B per (frame, camera, joint))
   const int slices = joint_argmax_all_shape(N, pr->Hh, pr->Hh, pr->Jp).slices;
   JH_PROF("views2d_final", 0.0, 8.0 * N * slices * pr->Jp + 24.0 * N * pr->J,
-          launch_views2d_final(pr->v2d_max, pr->v2d_idx, pr->chm_cur() + (size_t)t0 * pr->C * 2, pr->valid_cur() + t0,
-                               mask_dev ? mask_dev + (size_t)t0 * pr->C : nullptr, points_dev, pr->cam_at(t0),
-                               pr->intr_at(t0), pr->dist_at(t0), pr->calib_fs, points2d_dev, conf2d_dev, reproj_dev,
-                               err_dev, used_dev, pr->T3, pr->C,
-                               pr->J, pr->Jp, pr->Hh, pr->Hh, pr->B / 2, s));
+          launch_views2d_final(pr->v2d_max, pr->v2d_idx, pr->cur().chm + (size_t)t0 * pr->C * 2, pr->cur().valid + t0,
+                               mask_dev ? mask_dev + (size_t)t0 * pr->C : nullptr, points_dev, pr->calib_at(t0),
+                               points2d_dev, conf2d_dev, reproj_dev, err_dev, used_dev, pr->T3, pr->C, pr->J, pr->Jp,
+                               pr->Hh, pr->Hh, pr->B / 2, s));
   return 0;
 }
 
@@ -1217,7 +1229,7 @@ int jh_op_associate_subjects(const float* peaks_dev, int t, int cams, const floa
   JH_REQUIRE(peaks_dev && cam_dev && intr_dev && dist_dev && centers_dev && views_dev && members_dev && error_dev,
              "jh_op_associate_subjects: null pointer");
   JH_REQUIRE(t >= 1 && cams >= 1 && cams <= 64, "jh_op_associate_subjects: at most 64 cameras");
-  if (launch_associate_subjects(peaks_dev, cam_dev, intr_dev, dist_dev, calib_per_frame ? cams : 0, mask_dev,
+  if (launch_associate_subjects(peaks_dev, Calib{cam_dev, intr_dev, dist_dev, calib_per_frame ? cams : 0}, mask_dev,
                                 centers_dev, views_dev, members_dev, error_dev, t, cams, sp.max_peaks, sp.max_subjects,
                                 sp.min_views, sp.max_error_px, sx2, sy2, 255.f, s)) return 1;
   JH_CHECK_HIP(hipStreamSynchronize(s));
@@ -1240,30 +1252,18 @@ int jh_predictor_detect_subjects(jh_predictor* pr, const void* frames_dev, const
              "jh_predictor_detect_subjects: give frames_dev or images_host, not both");
   const auto& c = pr->cfg;
   FrameSource fs;
-  if (images_host) {
-    if (images_source(format, yuv, sensor, c.img_h, c.img_w, &fs)) return 1;
-  } else {
-    JH_REQUIRE(format >= JH_FRAME_RGB_F32 && format <= JH_FRAME_SENSOR, "jh_predictor_detect_subjects: unknown frame "
-               "format");
-    JH_REQUIRE((yuv != nullptr) == (format == JH_FRAME_SURFACE) && (sensor != nullptr) == (format == JH_FRAME_SENSOR),
-               "jh_predictor_detect_subjects: a description exactly where the format needs one");
-    if (format == JH_FRAME_SURFACE ? frame_source(yuv, c.img_h, c.img_w, &fs)
-        : format == JH_FRAME_SENSOR ? frame_source(sensor, c.img_h, c.img_w, &fs)
-                                    : frame_source(format, c.img_h, c.img_w, &fs)) return 1;
-  }
+  if (call_source("jh_predictor_detect_subjects", format, yuv, sensor, c.img_h, c.img_w, images_host != nullptr, &fs))
+    return 1;
   const int N = pr->T * pr->C;
   const Act& h = pr->center->heat;
   if (!pr->subj_peaks) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cs);
-    JH_REQUIRE(cs == hipStreamCaptureStatusNone, "the first jh_predictor_detect_subjects call of a predictor allocates "
-               "its workspace: make it outside a stream capture");
     // (one allocation: subj_peaks is set last, so a failure leaves the predictor as it was)
     const size_t pk = ((size_t)N * kMaxPeaks * 3 * sizeof(float) + 255) / 256 * 256;
     const size_t cn = ((size_t)N * sizeof(int) + 255) / 256 * 256;
     const size_t ws = center_peaks_workspace(N, h.H, h.W);
     char* base = nullptr;
-    if (pr->mem.get(reinterpret_cast<void**>(&base), pk + cn + ws)) return 1;
+    if (first_call_alloc(pr->mem, s, pk + cn + ws, "the first jh_predictor_detect_subjects call of a predictor "
+                         "allocates its workspace: make it outside a stream capture", &base)) return 1;
     pr->subj_count = reinterpret_cast<int*>(base + pk);
     pr->subj_ws = ws ? base + pk + cn : nullptr;
     pr->subj_peaks = reinterpret_cast<float*>(base);
@@ -1273,18 +1273,16 @@ int jh_predictor_detect_subjects(jh_predictor* pr, const void* frames_dev, const
     if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, N, format, s)) return 1;
     frames = pr->frames_table;                // (the launches read the table: `frames` itself is not dereferenced)
   }
-  // (plain launches with this call's frame pointer: cur_cell is non-null only while a forward is being captured)
-  if (center_heat_impl(pr, frames, fs, s)) return 1;
+  // (plain launches with this call's frame pointer)
+  if (center_heat_impl(pr, make_call(frames, fs, stream))) return 1;
   JH_PROF("center_peaks", 0.0, 4.0 * N * h.H * h.W,
           launch_center_peaks(h.p, pr->subj_peaks, pr->subj_count, N, h.H, h.W, h.Cp, sp.max_peaks, sp.nms_radius,
                               sp.min_peak, pr->subj_ws, s));
-  // preds * (downsampling_scale * 2), as stage 2 scales the arg-max (jarvis3D.py:138-141,158-160)
-  const float sx2 = (float)((double)c.img_w / (double)c.center_size) * 2.f;
-  const float sy2 = (float)((double)c.img_h / (double)c.center_size) * 2.f;
+  const Scale2 k = center_scale2(c);          // (as stage 2 scales the arg-max)
   JH_PROF("associate_subjects", 0.0, 0.0,
-          launch_associate_subjects(pr->subj_peaks, pr->cam_at(0), pr->intr_at(0), pr->dist_at(0), pr->calib_fs, mask_dev,
-                                    centers_dev, views_dev, members_dev, error_dev, pr->T, pr->C, sp.max_peaks,
-                                    sp.max_subjects, sp.min_views, sp.max_error_px, sx2, sy2, 255.f, s));
+          launch_associate_subjects(pr->subj_peaks, pr->calib_at(0), mask_dev, centers_dev, views_dev, members_dev,
+                                    error_dev, pr->T, pr->C, sp.max_peaks, sp.max_subjects, sp.min_views,
+                                    sp.max_error_px, k.x, k.y, 255.f, s));
   if (peaks_dev)
     JH_CHECK_HIP(hipMemcpyAsync(peaks_dev, pr->subj_peaks, (size_t)N * sp.max_peaks * 3 * sizeof(float),
                                 hipMemcpyDeviceToDevice, s));
@@ -1296,8 +1294,8 @@ int jh_predictor_debug(jh_predictor* pr, float* center3d_f_dev, int32_t* center3
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t T = pr->T, C = pr->C;
   if (center3d_f_dev) JH_CHECK_HIP(hipMemcpyAsync(center3d_f_dev, pr->c3f, T * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (center3d_i_dev) JH_CHECK_HIP(hipMemcpyAsync(center3d_i_dev, pr->c3i_cur(), T * 3 * sizeof(int), hipMemcpyDeviceToDevice, s));
-  if (center_hm_dev) JH_CHECK_HIP(hipMemcpyAsync(center_hm_dev, pr->chm_cur(), T * C * 2 * sizeof(int), hipMemcpyDeviceToDevice, s));
+  if (center3d_i_dev) JH_CHECK_HIP(hipMemcpyAsync(center3d_i_dev, pr->cur().c3i, T * 3 * sizeof(int), hipMemcpyDeviceToDevice, s));
+  if (center_hm_dev) JH_CHECK_HIP(hipMemcpyAsync(center_hm_dev, pr->cur().chm, T * C * 2 * sizeof(int), hipMemcpyDeviceToDevice, s));
   if (det_dev) JH_CHECK_HIP(hipMemcpyAsync(det_dev, pr->det_all, T * C * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
   return 0;
 }
@@ -1308,8 +1306,8 @@ int jh_predictor_hybridnet_forward(jh_predictor* pr, const float* crops_dev,
                                    float* points_dev, float* conf_dev, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   JH_REQUIRE(pr->Cloc == pr->C && pr->T3 == pr->T, "hybridnet_forward needs all cameras local");
-  JH_CHECK_HIP(hipMemcpyAsync(pr->chm_cur(), center_hm_dev, (size_t)pr->T * pr->C * 2 * sizeof(int), hipMemcpyDeviceToDevice, s));
-  JH_CHECK_HIP(hipMemcpyAsync(pr->c3i_cur(), center3d_dev, (size_t)pr->T * 3 * sizeof(int), hipMemcpyDeviceToDevice, s));
+  JH_CHECK_HIP(hipMemcpyAsync(pr->cur().chm, center_hm_dev, (size_t)pr->T * pr->C * 2 * sizeof(int), hipMemcpyDeviceToDevice, s));
+  JH_CHECK_HIP(hipMemcpyAsync(pr->cur().c3i, center3d_dev, (size_t)pr->T * 3 * sizeof(int), hipMemcpyDeviceToDevice, s));
   if (launch_to_channel_last(crops_dev, pr->kp->input, s)) return 1;
   pr->kp->stem_src.mode = 0;                      // (the crops are given: the stem reads the plan's input)
   if (pr->kp->run(s)) return 1;
@@ -1322,7 +1320,7 @@ int jh_predictor_hybridnet_forward(jh_predictor* pr, const float* crops_dev,
                        h.N, pr->J, h.Cp, pr->Hh);
     JH_CHECK_HIP(hipGetLastError());
   }
-  return pr->run_3d(pr->kp->heat.p, 0, heatmap_final_dev, points_dev, conf_dev, s);
+  return pr->run_3d(stage3_call(stream), pr->kp->heat.p, 0, heatmap_final_dev, points_dev, conf_dev);
 }
 
 // ----------------------------------------------------------------- 2D predictor
@@ -1348,16 +1346,12 @@ int jh_predictor2d_create(const jh_params* center_params, const jh_params* kp_pa
   pr->T = cfg->time_batch; pr->J = cfg->num_joints; pr->B = cfg->bbox;
   JH_REQUIRE(pr->T >= 1, "batch");
   JH_REQUIRE(cfg->img_w >= pr->B + 1 && cfg->img_h >= pr->B + 1, "image smaller than the bounding box");
-  JH_REQUIRE(cfg->precision >= JH_PRECISION_DEFAULT && cfg->precision <= JH_PRECISION_BF16X3_WIDE,
-             "jh_predictor_config.precision: unknown mode");
-  const int precision = cfg->precision == JH_PRECISION_DEFAULT ? precision_mode() : cfg->precision;
-  pr->cfg.precision = precision;
-  pr->center.reset(new EffTrackPlan());
-  pr->center->precision = precision;
+  PlanSetup setup;                            // (the plans' own node form and norm blocking: no time-batch class here)
+  if (setup.init(&pr->cfg, -1, 0)) return 1;
+  pr->center = setup.efftrack();
   if (pr->center->build(center_params->map, "", cfg->center_model, 1, pr->T, cfg->center_size,
                         cfg->center_size)) return 1;
-  pr->kp.reset(new EffTrackPlan());
-  pr->kp->precision = precision;
+  pr->kp = setup.efftrack();
   if (pr->kp->build(kp_params->map, "", cfg->kp_model, pr->J, pr->T, pr->B, pr->B)) return 1;
   if (pr->mem.get(reinterpret_cast<void**>(&pr->det), (size_t)pr->T * 3 * sizeof(float))) return 1;
   if (pr->mem.get(reinterpret_cast<void**>(&pr->chm), (size_t)pr->T * 2 * sizeof(int))) return 1;
@@ -1369,16 +1363,17 @@ int jh_predictor2d_create(const jh_params* center_params, const jh_params* kp_pa
 
 void jh_predictor2d_destroy(jh_predictor2d* pr) { delete pr; }
 
-static int forward2d_impl(jh_predictor2d* pr, const void* frames, const FrameSource& fs, int32_t* points_dev,
-                          float* conf_dev, int32_t* valid_dev, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
+static int forward2d_impl(jh_predictor2d* pr, const Call& call, int32_t* points_dev, float* conf_dev,
+                          int32_t* valid_dev) {
+  hipStream_t s = call.s;
+  const FrameSource& fs = call.fs;
   const auto& c = pr->cfg;
   const int S = c.center_size;
   // algorithmic bytes as in the 3D stages: four taps (resize) or one pixel (crop) of frame data + the float4 written.
   // (These counts used to be a flat 24 B per pixel for every format: fp32 resize is 60, uint8 crop 15.)
   JH_PROF("preprocess_resize", 0.0, (double)pr->T * S * S * (4.0 * fs.px_bytes() + 12.0),
-          launch_preprocess_resize(frames, fs, pr->center->input.p, pr->T, c.img_h, c.img_w, S,
-                                   c.mean, c.std, s, fs.per_image ? pr->frames_table : nullptr));
+          launch_preprocess_resize(call.frames, fs, pr->center->input.p, pr->T, c.img_h, c.img_w, S,
+                                   c.mean, c.std, s, call.cell));
   if (pr->center->run(s)) return 1;
   const Act& h = pr->center->heat;
   JH_PROF("center_argmax", 0.0, 4.0 * pr->T * h.H * h.W,
@@ -1388,8 +1383,8 @@ static int forward2d_impl(jh_predictor2d* pr, const void* frames, const FrameSou
   if (launch_center2d(pr->det, pr->chm, pr->valid, pr->T, sx, sy, pr->B / 2, c.img_w, c.img_h, s))
     return 1;
   JH_PROF("preprocess_crop", 0.0, (double)pr->T * pr->B * pr->B * (fs.px_bytes() + 12.0),
-          launch_preprocess_crop(frames, fs, pr->chm, pr->kp->input.p, pr->T, 1, 1, 0, c.img_h,
-                                 c.img_w, pr->B, c.mean, c.std, s, fs.per_image ? pr->frames_table : nullptr));
+          launch_preprocess_crop(call.frames, fs, pr->chm, pr->kp->input.p, pr->T, 1, 1, 0, c.img_h,
+                                 c.img_w, pr->B, c.mean, c.std, s, call.cell));
   if (pr->kp->run(s)) return 1;
   const Act& k = pr->kp->heat;
   JH_PROF("joint_argmax", 0.0, 4.0 * pr->T * k.H * k.W * pr->J,
@@ -1403,11 +1398,11 @@ static int forward2d_impl(jh_predictor2d* pr, const void* frames, const FrameSou
 
 int jh_predictor2d_forward(jh_predictor2d* pr, const float* frames_dev, int32_t* points_dev,
                            float* conf_dev, int32_t* valid_dev, void* stream) {
-  return forward2d_impl(pr, frames_dev, fixed_source(kSrcRgbF32), points_dev, conf_dev, valid_dev, stream);
+  return forward2d_impl(pr, make_call(frames_dev, fixed_source(kSrcRgbF32), stream), points_dev, conf_dev, valid_dev);
 }
 int jh_predictor2d_forward_u8(jh_predictor2d* pr, const uint8_t* frames_dev, int32_t* points_dev,
                               float* conf_dev, int32_t* valid_dev, void* stream) {
-  return forward2d_impl(pr, frames_dev, fixed_source(kSrcBgrU8), points_dev, conf_dev, valid_dev, stream);
+  return forward2d_impl(pr, make_call(frames_dev, fixed_source(kSrcBgrU8), stream), points_dev, conf_dev, valid_dev);
 }
 
 int jh_predictor2d_forward_yuv(jh_predictor2d* pr, const uint8_t* frames_dev, int format, int32_t* points_dev,
@@ -1417,7 +1412,7 @@ int jh_predictor2d_forward_yuv(jh_predictor2d* pr, const uint8_t* frames_dev, in
   JH_REQUIRE(pr, "bad argument");
   FrameSource fs;
   if (frame_source(format, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
-  return forward2d_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
+  return forward2d_impl(pr, make_call(frames_dev, fs, stream), points_dev, conf_dev, valid_dev);
 }
 
 int jh_predictor2d_forward_surface(jh_predictor2d* pr, const uint8_t* frames_dev, const jh_yuv_surface* surface,
@@ -1425,7 +1420,7 @@ int jh_predictor2d_forward_surface(jh_predictor2d* pr, const uint8_t* frames_dev
   JH_REQUIRE(pr && frames_dev, "bad argument");
   FrameSource fs;
   if (frame_source(surface, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
-  return forward2d_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
+  return forward2d_impl(pr, make_call(frames_dev, fs, stream), points_dev, conf_dev, valid_dev);
 }
 
 int jh_predictor2d_forward_sensor(jh_predictor2d* pr, const uint8_t* frames_dev, const jh_sensor_surface* surface,
@@ -1433,7 +1428,7 @@ int jh_predictor2d_forward_sensor(jh_predictor2d* pr, const uint8_t* frames_dev,
   JH_REQUIRE(pr && frames_dev, "bad argument");
   FrameSource fs;
   if (frame_source(surface, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
-  return forward2d_impl(pr, frames_dev, fs, points_dev, conf_dev, valid_dev, stream);
+  return forward2d_impl(pr, make_call(frames_dev, fs, stream), points_dev, conf_dev, valid_dev);
 }
 
 int jh_predictor2d_forward_images(jh_predictor2d* pr, const void* const* images_host, int n_images, int format,
@@ -1441,10 +1436,10 @@ int jh_predictor2d_forward_images(jh_predictor2d* pr, const void* const* images_
                                   int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
   JH_REQUIRE(pr && points_dev && conf_dev, "bad argument");
   FrameSource fs;
-  if (images_source(format, yuv, sensor, pr->cfg.img_h, pr->cfg.img_w, &fs)) return 1;
+  if (call_source("forward_images", format, yuv, sensor, pr->cfg.img_h, pr->cfg.img_w, true, &fs)) return 1;
   if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T, format,
                     static_cast<hipStream_t>(stream))) return 1;
-  return forward2d_impl(pr, pr->frames_table, fs, points_dev, conf_dev, valid_dev, stream);
+  return forward2d_impl(pr, make_call(pr->frames_table, fs, stream), points_dev, conf_dev, valid_dev);
 }
 
 // ------------------------------------------------------------------- profiling

@@ -19,7 +19,6 @@
 //                      predictor (2D keypoints, reprojections, reprojection errors), jarvis2D.py:139-149
 #include "jh_common.h"
 #include "preprocess.h"
-#include "camera_mask.h"
 #include "views2d.h"
 #include "subjects.h"
 #include "nets.h"
@@ -415,7 +414,7 @@ __device__ __forceinline__ void crop_centre(const float* __restrict__ cam, const
 // One 64-thread block per frame t.  det: [T][C][3] (x, y, raw maxval).
 // Outputs: center3d_f [T][3] float, center3d_i [T][3] int (truncated),
 // center_hm [T][C][2] int (truncated + clamped crop centres), valid [T].
-// MASK (camera_mask.h): camera c of frame t takes part iff mask[t][c] != 0.  A masked camera's term of A^T A is an
+// MASK (nets.h): camera c of frame t takes part iff mask[t][c] != 0.  A masked camera's term of A^T A is an
 // exact 0.0 -- SELECTED, not multiplied: its detection may be NaN -- and s + 0.0 == s, so the centre has the bits
 // of a run over the unmasked cameras alone; it is not counted either.  Its crop centre is still written (the
 // clamped projection of the centre: in range whatever its frame held).
@@ -499,26 +498,19 @@ __global__ __launch_bounds__(64) void triangulate_masked_kernel(
                          mask, n_active, n_detect);
 }
 
-int launch_triangulate_masked(const float* det, const float* cam, const float* intr, const float* dist, int calib_fs,
-                              float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C,
-                              float sx2, float sy2, float wdiv, int hw, int W, int H,
-                              const unsigned char* mask, int* n_active, int* n_detect, hipStream_t s) {
+int launch_triangulate(const float* det, const Calib& cal, float* center3d_f, int* center3d_i, int* center_hm,
+                       int* valid, int T, int C, float sx2, float sy2, float wdiv, int hw, int W, int H,
+                       const unsigned char* mask, int* n_active, int* n_detect, hipStream_t s) {
   JH_REQUIRE(C <= 64, "at most 64 cameras");
-  JH_REQUIRE(mask && n_active && n_detect, "camera mask");
-  JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
-  hipLaunchKernelGGL(triangulate_masked_kernel, dim3(T), dim3(64), 0, s, det, cam, intr, dist, calib_fs, center3d_f,
-                     center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H, mask, n_active, n_detect);
-  JH_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-int launch_triangulate(const float* det, const float* cam, const float* intr, const float* dist, int calib_fs,
-                       float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C,
-                       float sx2, float sy2, float wdiv, int hw, int W, int H, hipStream_t s) {
-  JH_REQUIRE(C <= 64, "at most 64 cameras");
-  JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
-  hipLaunchKernelGGL(triangulate_kernel, dim3(T), dim3(64), 0, s, det, cam, intr, dist, calib_fs, center3d_f,
-                     center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H);
+  if (calib_check(cal, C)) return 1;
+  if (mask) {
+    JH_REQUIRE(n_active && n_detect, "camera mask");
+    hipLaunchKernelGGL(triangulate_masked_kernel, dim3(T), dim3(64), 0, s, det, cal.cam, cal.intr, cal.dist, cal.fs,
+                       center3d_f, center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H, mask, n_active, n_detect);
+  } else {
+    hipLaunchKernelGGL(triangulate_kernel, dim3(T), dim3(64), 0, s, det, cal.cam, cal.intr, cal.dist, cal.fs,
+                       center3d_f, center3d_i, center_hm, valid, C, sx2, sy2, wdiv, hw, W, H);
+  }
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -563,19 +555,19 @@ __global__ __launch_bounds__(64) void centers_kernel(
 }
 
 // mask == nullptr: all cameras (n_active / n_detect are not touched, as by launch_triangulate)
-int launch_centers(const float* centers, const float* cam, const float* intr, const float* dist, int calib_fs,
-                   float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C, int hw, int W, int H,
-                   const unsigned char* mask, int* n_active, int* n_detect, hipStream_t s) {
+int launch_centers(const float* centers, const Calib& cal, float* center3d_f, int* center3d_i, int* center_hm,
+                   int* valid, int T, int C, int hw, int W, int H, const unsigned char* mask, int* n_active,
+                   int* n_detect, hipStream_t s) {
   JH_REQUIRE(C <= 64, "at most 64 cameras");
   JH_REQUIRE(centers, "caller-supplied centres");
-  JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
+  if (calib_check(cal, C)) return 1;
   if (mask) {
     JH_REQUIRE(n_active && n_detect, "camera mask");
-    hipLaunchKernelGGL(centers_kernel<true>, dim3(T), dim3(64), 0, s, centers, cam, intr, dist, calib_fs, center3d_f,
-                       center3d_i, center_hm, valid, C, hw, W, H, mask, n_active, n_detect);
+    hipLaunchKernelGGL(centers_kernel<true>, dim3(T), dim3(64), 0, s, centers, cal.cam, cal.intr, cal.dist, cal.fs,
+                       center3d_f, center3d_i, center_hm, valid, C, hw, W, H, mask, n_active, n_detect);
   } else {
-    hipLaunchKernelGGL(centers_kernel<false>, dim3(T), dim3(64), 0, s, centers, cam, intr, dist, calib_fs, center3d_f,
-                       center3d_i, center_hm, valid, C, hw, W, H, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(centers_kernel<false>, dim3(T), dim3(64), 0, s, centers, cal.cam, cal.intr, cal.dist, cal.fs,
+                       center3d_f, center3d_i, center_hm, valid, C, hw, W, H, nullptr, nullptr, nullptr);
   }
   JH_CHECK_HIP(hipGetLastError());
   return 0;
@@ -797,15 +789,15 @@ int launch_joint_argmax_all_combine(const float* pmax, const int* pidx, int* idx
 }
 
 int launch_views2d_final(const float* pmax, const int* pidx, const int* center_hm, const int* valid,
-                         const unsigned char* mask, const float* pts3d, const float* cam, const float* intr,
-                         const float* dist, int calib_fs, int* points2d, float* conf2d, float* reproj, float* err,
-                         unsigned char* used, int T, int C, int J, int Jp, int Hh, int Wh, int hw, hipStream_t s) {
+                         const unsigned char* mask, const float* pts3d, const Calib& cal, int* points2d,
+                         float* conf2d, float* reproj, float* err, unsigned char* used, int T, int C, int J, int Jp,
+                         int Hh, int Wh, int hw, hipStream_t s) {
   if (check_scan_shape(T * C, Hh, Wh, J, Jp)) return 1;
-  JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
+  if (calib_check(cal, C)) return 1;
   const ScanShape sh = joint_argmax_all_shape(T * C, Hh, Wh, Jp);
   hipLaunchKernelGGL(views2d_final_kernel, dim3(T * C), dim3(round_up(J, kWave)), 0, s, pmax, pidx, center_hm,
-                     valid, mask, pts3d, cam, intr, dist, calib_fs, points2d, conf2d, reproj, err, used, C, J, Jp,
-                     sh.slices, Hh, Wh, hw);
+                     valid, mask, pts3d, cal.cam, cal.intr, cal.dist, cal.fs, points2d, conf2d, reproj, err, used, C, J,
+                     Jp, sh.slices, Hh, Wh, hw);
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -1415,16 +1407,15 @@ __global__ __launch_bounds__(kAssocThreads) void associate_subjects_kernel(
   }
 }
 
-int launch_associate_subjects(const float* peaks, const float* cam, const float* intr, const float* dist, int calib_fs,
-                              const unsigned char* mask, float* centers, int* views, int* members, float* error, int T,
-                              int C, int P, int K, int min_views, float max_error_px, float sx2, float sy2, float wdiv,
-                              hipStream_t s) {
+int launch_associate_subjects(const float* peaks, const Calib& cal, const unsigned char* mask, float* centers,
+                              int* views, int* members, float* error, int T, int C, int P, int K, int min_views,
+                              float max_error_px, float sx2, float sy2, float wdiv, hipStream_t s) {
   JH_REQUIRE(T >= 1 && C >= 1 && C <= 64, "subject association: at most 64 cameras");
   JH_REQUIRE(P >= 1 && P <= kMaxPeaks && K >= 1 && K <= kMaxSubjects && min_views >= 2 && max_error_px >= 0.f,
              "subject association: max_peaks 1 .. 8, max_subjects 1 .. 8, min_views >= 2, max_error_px >= 0");
-  JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
-  hipLaunchKernelGGL(associate_subjects_kernel, dim3(T), dim3(kAssocThreads), 0, s, peaks, cam, intr, dist, calib_fs,
-                     mask, centers, views, members, error, C, P, K, min_views, max_error_px, sx2, sy2, wdiv);
+  if (calib_check(cal, C)) return 1;
+  hipLaunchKernelGGL(associate_subjects_kernel, dim3(T), dim3(kAssocThreads), 0, s, peaks, cal.cam, cal.intr, cal.dist,
+                     cal.fs, mask, centers, views, members, error, C, P, K, min_views, max_error_px, sx2, sy2, wdiv);
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -63,6 +63,26 @@ struct HeatLayout {
   size_t block_stride = 0, frame_stride = 0;
 };
 
+// The calibration a launch reads, shared by all frames or one per frame (jh_predictor_set_calibration_frames): frame t
+// of a launch reads cam + (t * fs + c) * 12, intr + (t * fs + c) * 9, dist + (t * fs + c) * 5.  Nothing else differs
+// between the two forms.  (repro_coarse_kernel takes it by value: the fields keep their order.)
+struct Calib {
+  const float* cam;    // [C][4][3]
+  const float* intr;   // [C][3][3]  (principal point in row 2)
+  const float* dist;   // [C][5]
+  int fs;              // frame stride in cameras: frame t reads row t * fs + c (0: shared by all frames, C: per frame)
+  // the calibration of a call that starts at frame t0 (as such a call passes the centres' and the mask's rows)
+  Calib at(int t0) const {
+    const size_t r = (size_t)t0 * fs;
+    return Calib{cam + r * 12, intr + r * 9, dist + r * 5, fs};
+  }
+};
+// every launcher that takes a Calib, for its C cameras
+inline int calib_check(const Calib& cal, int C) {
+  JH_REQUIRE(cal.fs == 0 || cal.fs == C, "calibration frame stride: 0 (shared) or the camera count");
+  return 0;
+}
+
 enum ActKind { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2 };
 
 // Optional per-launch timing with HIP events on the launch stream (bench.py's

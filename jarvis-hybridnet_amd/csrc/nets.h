@@ -17,13 +17,17 @@
 namespace jh {
 
 // kernels implemented in other translation units
-// calib_fs: the frame stride of the calibration in cameras.  Frame t of a launch reads cam + (t * calib_fs + c) * 12,
-// intr + (t * calib_fs + c) * 9, dist + (t * calib_fs + c) * 5: 0 = one calibration (C rows) shared by all frames,
-// C = one per frame (T * C rows, jh_predictor_set_calibration_frames).  Nothing else differs between the two forms.
-int launch_reproject(const float* cam, const float* intr, const float* dist, int calib_fs, const int* center3d,
-                     const int* center_hm, const float* heat, float2* coarse, float* vol,
-                     int* idx_out, int T, int C, int G, float spacing, int hs, int Jp,
-                     int heat_pad, int div255, hipStream_t s, const HeatLayout* layout = nullptr);
+// Calib (jh_common.h): the calibration, shared by all frames or one per frame.
+// Per-frame camera masks -- `mask`, here and below: [T][C] bytes on the device, nonzero = the camera
+// takes part in frame t; nullptr = all cameras.  The masked forms of the three kernels that sum over cameras are
+// kernels of their own (triangulate_masked_kernel, repro_gather_masked_kernel, repro_cube_masked_kernel) that share
+// their bodies with the plain kernels through a template parameter: the plain kernels keep their names, signatures and
+// code.
+// launch_reproject under a mask: frame t sums its unmasked cameras in camera order and divides by their number (IEEE
+// division; a frame without any camera gets an all-zero volume); at most 64 cameras then.
+int launch_reproject(const Calib& cal, const int* center3d, const int* center_hm, const float* heat, float2* coarse,
+                     float* vol, int* idx_out, int T, int C, int G, float spacing, int hs, int Jp, int heat_pad,
+                     int div255, const unsigned char* mask, hipStream_t s, const HeatLayout* layout = nullptr);
 // (frames_cell: the one-pointer cell of a graph replay, or nullptr; with src.per_image the table of N image pointers,
 //  which must then be given -- preprocess.h: image_base)
 int launch_preprocess_resize(const void* frames, const FrameSource& src, float* out, int N, int H, int W, int S,
@@ -40,14 +44,17 @@ int launch_center2d(const float* det, int* center_hm, int* valid, int T, float s
                     int W, int H, hipStream_t s);
 int launch_joint_argmax(const float* heat, const int* center_hm, int* points, float* conf, int T,
                         int J, int Jp, int Hh, int Wh, int hw, hipStream_t s);
-int launch_triangulate(const float* det, const float* cam, const float* intr, const float* dist, int calib_fs,
-                       float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C,
-                       float sx2, float sy2, float wdiv, int hw, int W, int H, hipStream_t s);
-// Caller-supplied 3D centres (T,3) in place of the triangulation: the buffers launch_triangulate[_masked] writes, det
-// excepted (geometry.hip: centers_kernel).  mask: (T,C) bytes or nullptr = all cameras.
-int launch_centers(const float* centers, const float* cam, const float* intr, const float* dist, int calib_fs,
-                   float* center3d_f, int* center3d_i, int* center_hm, int* valid, int T, int C, int hw, int W, int H,
-                   const unsigned char* mask, int* n_active, int* n_detect, hipStream_t s);
+// Under a mask (n_active and n_detect are then required) a masked camera adds an exact 0.0 to A^T A (selected, never
+// multiplied: its detection may be NaN) and is not counted.  n_active[t]: unmasked cameras of frame t, n_detect[t]:
+// those of them with maxval > 50 (valid[t] = n_detect[t] >= 2).  Crop centres are written for every camera.
+int launch_triangulate(const float* det, const Calib& cal, float* center3d_f, int* center3d_i, int* center_hm,
+                       int* valid, int T, int C, float sx2, float sy2, float wdiv, int hw, int W, int H,
+                       const unsigned char* mask, int* n_active, int* n_detect, hipStream_t s);
+// Caller-supplied 3D centres (T,3) in place of the triangulation: the buffers launch_triangulate writes, det excepted
+// (geometry.hip: centers_kernel).
+int launch_centers(const float* centers, const Calib& cal, float* center3d_f, int* center3d_i, int* center_hm,
+                   int* valid, int T, int C, int hw, int W, int H, const unsigned char* mask, int* n_active,
+                   int* n_detect, hipStream_t s);
 int launch_project_points(const float* pts, const float* cam, const float* intr, const float* dist,
                           float* uv, int P, int C, hipStream_t s);
 // The spread form of the soft-argmax tail (geometry.hip): workspace and outputs of T frame sets.

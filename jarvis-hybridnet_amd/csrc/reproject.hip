@@ -30,19 +30,11 @@
 #include <algorithm>
 #include <atomic>
 #include "jh_common.h"
-#include "camera_mask.h"
 
 namespace jh {
 
-struct ReproCalib {
-  const float* cam;    // [C][4][3]
-  const float* intr;   // [C][3][3]  (principal point in row 2)
-  const float* dist;   // [C][5]
-  int fs;              // frame stride in cameras: frame t reads row t * fs + c (0: shared by all frames, C: per frame)
-};
-
 __global__ __launch_bounds__(256) void repro_coarse_kernel(
-    ReproCalib cal, const int* __restrict__ center3d, const int* __restrict__ center_hm,
+    Calib cal, const int* __restrict__ center3d, const int* __restrict__ center_hm,
     float2* __restrict__ coarse, int C, int Gh, float spacing, int hs) {
   const int t = blockIdx.z, c = blockIdx.y;
   const int vox = blockIdx.x * blockDim.x + threadIdx.x;
@@ -117,7 +109,7 @@ __device__ __forceinline__ rp2 lerp_ref2(rp2 p0, rp2 p1, float w0, float w1) {
 // memory parallelism, hides the latency here.
 constexpr int kCamBatch = 1;
 
-// MASK (camera_mask.h): cameras with mask[t][c] == 0 are skipped -- their heatmaps are never loaded -- and the mean
+// MASK (nets.h): cameras with mask[t][c] == 0 are skipped -- their heatmaps are never loaded -- and the mean
 // divides by the number of cameras left.
 template <int Q, bool MASK>
 __device__ __forceinline__ void repro_gather_body(
@@ -364,7 +356,7 @@ __device__ __forceinline__ void lds_read_quads(cube_f4 (&h)[Q], unsigned addr) {
   }
 }
 
-// MASK (camera_mask.h): the camera loop walks the frame's unmasked cameras only -- position n of the walk is camera
+// MASK (nets.h): the camera loop walks the frame's unmasked cameras only -- position n of the walk is camera
 // cam(n), kept four deep in scalar registers from the wave's ballot over the mask row; the double buffers alternate by
 // POSITION, memory is addressed by CAMERA.  Nothing of a masked camera is requested: no table, no patch DMA, no tap.
 template <int Q, int CI, int NT, bool MASK>
@@ -834,11 +826,11 @@ static int launch_cube(const CubeArgs& a, int T, hipStream_t s, const unsigned c
               : launch_cube_kernel(repro_cube_kernel<Q, CI, NT>, big, grid, NT, lds, s, a);
 }
 
-static int reproject_impl(const float* cam, const float* intr, const float* dist, int calib_fs, const int* center3d,
-                          const int* center_hm, const float* heat, float2* coarse, float* vol,
-                          int* idx_out, int T, int C, int G, float spacing, int hs, int Jp,
-                          int heat_pad, int div255, hipStream_t s, const HeatLayout* layout,
-                          const unsigned char* mask) {
+// mask == nullptr: all cameras (the plain kernels); otherwise the masked kernels, which take at most 64 cameras
+int launch_reproject(const Calib& cal, const int* center3d, const int* center_hm, const float* heat, float2* coarse,
+                     float* vol, int* idx_out, int T, int C, int G, float spacing, int hs, int Jp, int heat_pad,
+                     int div255, const unsigned char* mask, hipStream_t s, const HeatLayout* layout) {
+  JH_REQUIRE(!mask || C <= 64, "at most 64 cameras");
   const int Gh = G / 2;
   const int Hst = hs - 2 + 2 * heat_pad;
   HeatLayout lay;                        // default: dense (T, C, Hh, Hh, Jp)
@@ -849,8 +841,7 @@ static int reproject_impl(const float* cam, const float* intr, const float* dist
   JH_REQUIRE(lay.cams_per_block >= 1 && C % lay.cams_per_block == 0, "cameras per heatmap block");
   JH_REQUIRE(G % 2 == 0 && Jp % 8 == 0 && Jp <= 64, "reprojection shape");
   JH_REQUIRE((size_t)hs * hs * Jp * 4 < ((size_t)1 << 31), "one camera's heatmap exceeds 2 GB");
-  JH_REQUIRE(calib_fs == 0 || calib_fs == C, "calibration frame stride: 0 (shared) or the camera count");
-  ReproCalib cal{cam, intr, dist, calib_fs};
+  if (calib_check(cal, C)) return 1;
   const int nvc = Gh * Gh * Gh;
   hipLaunchKernelGGL(repro_coarse_kernel, dim3((nvc + 255) / 256, C, T), dim3(256), 0, s, cal,
                      center3d, center_hm, coarse, C, Gh, spacing, hs);
@@ -898,24 +889,6 @@ static int reproject_impl(const float* cam, const float* intr, const float* dist
 #undef JH_RG
   JH_CHECK_HIP(hipGetLastError());
   return 0;
-}
-
-int launch_reproject(const float* cam, const float* intr, const float* dist, int calib_fs, const int* center3d,
-                     const int* center_hm, const float* heat, float2* coarse, float* vol,
-                     int* idx_out, int T, int C, int G, float spacing, int hs, int Jp,
-                     int heat_pad, int div255, hipStream_t s, const HeatLayout* layout) {
-  return reproject_impl(cam, intr, dist, calib_fs, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs,
-                        Jp, heat_pad, div255, s, layout, nullptr);
-}
-
-int launch_reproject_masked(const float* cam, const float* intr, const float* dist, int calib_fs, const int* center3d,
-                            const int* center_hm, const float* heat, float2* coarse, float* vol, int* idx_out,
-                            int T, int C, int G, float spacing, int hs, int Jp, int heat_pad, int div255,
-                            const unsigned char* mask, hipStream_t s, const HeatLayout* layout) {
-  JH_REQUIRE(mask, "camera mask");
-  JH_REQUIRE(C <= 64, "at most 64 cameras");
-  return reproject_impl(cam, intr, dist, calib_fs, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs,
-                        Jp, heat_pad, div255, s, layout, mask);
 }
 
 }  // namespace jh

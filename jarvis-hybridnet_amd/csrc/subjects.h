@@ -24,10 +24,9 @@ size_t center_peaks_workspace(int N, int Hh, int Wh);
 int launch_center_peaks(const float* heat, float* peaks, int* count, int N, int Hh, int Wh, int Cp, int max_peaks,
                         int nms_radius, float min_peak, void* workspace, hipStream_t s);
 // peaks [T][C][P][3] -> centers [T][K][3], views [T][K], members [T][K][C], error [T][K]; mask [T][C] or nullptr;
-// calib_fs as launch_triangulate.  The work of a frame set grows with C^2 * P^2 per round (K rounds).
-int launch_associate_subjects(const float* peaks, const float* cam, const float* intr, const float* dist, int calib_fs,
-                              const unsigned char* mask, float* centers, int* views, int* members, float* error, int T,
-                              int C, int P, int K, int min_views, float max_error_px, float sx2, float sy2, float wdiv,
-                              hipStream_t s);
+// The work of a frame set grows with C^2 * P^2 per round (K rounds).
+int launch_associate_subjects(const float* peaks, const Calib& cal, const unsigned char* mask, float* centers,
+                              int* views, int* members, float* error, int T, int C, int P, int K, int min_views,
+                              float max_error_px, float sx2, float sy2, float wdiv, hipStream_t s);
 
 }  // namespace jh

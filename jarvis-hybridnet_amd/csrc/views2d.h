@@ -16,11 +16,9 @@ int launch_joint_argmax_all(const float* heat, float* pmax, int* pidx, int N, in
 int launch_joint_argmax_all_combine(const float* pmax, const int* pidx, int* idx, float* maxv, int N, int Hh,
                                     int Wh, int J, int Jp, hipStream_t s);
 // partials + crop centres, validity, mask and 3D points of T frames -> the five outputs of jh_predictor_views2d
-// (calib_fs: the calibration's frame stride in cameras -- frame t projects with row t * calib_fs + c; 0 shared, C per
-//  frame)
 int launch_views2d_final(const float* pmax, const int* pidx, const int* center_hm, const int* valid,
-                         const unsigned char* mask, const float* pts3d, const float* cam, const float* intr,
-                         const float* dist, int calib_fs, int* points2d, float* conf2d, float* reproj, float* err,
-                         unsigned char* used, int T, int C, int J, int Jp, int Hh, int Wh, int hw, hipStream_t s);
+                         const unsigned char* mask, const float* pts3d, const Calib& cal, int* points2d,
+                         float* conf2d, float* reproj, float* err, unsigned char* used, int T, int C, int J, int Jp,
+                         int Hh, int Wh, int hw, hipStream_t s);
 
 }  // namespace jh

@@ -320,7 +320,7 @@ def test_driver_masks(tmp_path):
 # ---- the voxel-row form of the masked gather (repro_gather_masked_kernel): what the predictor launches when the grid
 # is no multiple of 8, for more than 32 channels, or under JH_REPRO_CUBE=0
 def _wide_case():
-    """The cfg2 rig with 36 joints: 40 channels, more than the cube form takes, so launch_reproject_masked sends it
+    """The cfg2 rig with 36 joints: 40 channels, more than the cube form takes, so launch_reproject (given a mask) sends it
     to repro_gather_masked_kernel<10>."""
     from jarvis_hybridnet_amd import synthetic as S
     c = dict(cases.PREDICTOR_CASES["cfg2"], J=36)

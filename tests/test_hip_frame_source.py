@@ -66,3 +66,67 @@ def test_sources_alternate_under_replay():
         assert not torch.equal(first["rggb"][0], first["bggr"][0])
     g.close()
     eager.close()
+
+
+def test_forward_forms_combine_under_replay():
+    """All 16 combinations of (masked, per-image, centred, spread) on ONE graph-replaying predictor, each visited twice
+    and never twice in a row, the input alternating between two frame sets from call to call: every call equals the
+    eager predictor's call of the same form on the same input.  The alternation tests above vary one flag at a time; two
+    forms that shared a graph slot would show only here, as a recording replayed for the other form."""
+    import itertools
+
+    from jarvis_hybridnet_amd import _native as N
+    from jarvis_hybridnet_amd._predictor import NativePredictor
+    c = cases.PREDICTOR_CASES["cfg2"]
+    inp = cases.predictor_inputs("cfg2")
+    H, W, C = c["H"], c["W"], c["C"]
+    kw = dict(num_cameras=C, num_joints=c["J"], center_size=c["center_size"], bbox=c["bbox"],
+              roi_cube_size=c["roi"], grid_spacing=c["spacing"], img_h=H, img_w=W, mean=S.MEAN, std=S.STD, time_batch=1)
+    dev = [cuda(inp[k]) for k in ("cam", "intr", "dist")]
+    x = torch.from_numpy(to_bgr_u8(inp["imgs"]))
+    y = torch.where(x < 128, x + 6, x - 6)                       # every pixel value moves by 6, none wraps
+    contig = {"X": cuda(x).unsqueeze(0), "Y": cuda(y).unsqueeze(0)}
+    views = {k: [cuda(img).clone() for img in v] for k, v in (("X", x), ("Y", y))}   # one allocation per image
+    mask = [[cam != 1 for cam in range(C)]]
+
+    g = NativePredictor(inp["sd_center"], inp["sd_hybrid"], **kw)
+    eager = NativePredictor(inp["sd_center"], inp["sd_hybrid"], **kw)
+    eager.graph_replay = False
+    assert g.graph_replay and not eager.graph_replay
+    for p in (g, eager):
+        p.set_calibration(*dev)
+    eager.forward(contig["X"])
+    # centres that are NOT the detected ones: three, two and two voxels (2 mm each) off
+    centres = eager.debug(contig["X"].device)["center3d"] + torch.tensor([6., -4., 4.], device="cuda")
+
+    def run(p, name, form):
+        masked, per_image, centred, spread = form
+        how = dict(camera_mask=mask if masked else None, centers=centres if centred else None, return_spread=spread)
+        out = p.forward_images(N.frame_images(views[name], C), **how) if per_image else p.forward(contig[name], **how)
+        assert len(out) == (4 if spread else 3)
+        return [t.clone() for t in out[:3]] + [t.clone() for t in (out[3] if spread else ())]
+
+    forms = list(itertools.product((False, True), repeat=4))
+    want = {(name, f): run(eager, name, f) for name in "XY" for f in forms}
+    torch.cuda.synchronize()
+
+    def differ(a, b):
+        return any(not torch.equal(s, t) for s, t in zip(a, b))
+    plain = (False, False, False, False)
+    assert differ(want["X", plain], want["Y", plain])
+    assert differ(want["X", plain], want["X", (True, False, False, False)])      # masked
+    assert differ(want["X", plain], want["X", (False, False, True, False)])      # centred
+
+    # second pass: another order (7 i + 3 is odd where i is even: every form meets the other input there)
+    order = forms + [forms[(7 * i + 3) % 16] for i in range(16)]
+    assert all(a != b for a, b in zip(order, order[1:])) and all(order.count(f) == 2 for f in forms)
+    for step, f in enumerate(order):
+        name = "XY"[step % 2]
+        got = run(g, name, f)
+        torch.cuda.synchronize()
+        assert len(got) == len(want[name, f]) == (6 if f[3] else 3)
+        for a, b in zip(got, want[name, f]):
+            assert torch.equal(a, b), (step, name, f)
+        assert int(got[2][0]) == 1, (step, name, f)
+    g.close()
+    eager.close()
