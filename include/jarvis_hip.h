@@ -88,6 +88,11 @@ typedef struct jh_v2v jh_v2v;
 int jh_v2v_create(const jh_params* p, const char* prefix, int joints, int t, int g, jh_v2v** out);
 int jh_v2v_forward(jh_v2v* net, const float* x_dev, float* y_dev, void* stream);
 void jh_v2v_destroy(jh_v2v* net);
+/* Whether a V2V plan created NOW for (joints, t, g) ends in the output fold (no GPU needed): *folded = 1 -- the closing
+ * passes of skip_res1 and decoder_res1 are applied by the output layer's launch on load, two launches fewer, same bits
+ * -- or 0: the three launches.  A function of (joints, g) -- at most 32 joints, g a multiple of 8 -- and of JH_V2V_FOLD
+ * (default on; 0: never) as it stands at the call, never of t.  Predictors build their V2V plan by the same rule. */
+int jh_v2v_fold(int joints, int t, int g, int* folded);
 
 /* ---- ReprojectionLayer.forward  (jarvis/hybridnet/repro_layer.py:110-119)
  * heatmaps_padded (1,C,J,hs,hs) NCHW dev, center3d (3) int32 dev, center_hm

@@ -106,6 +106,7 @@ _SIGS = {
     "jh_v2v_create": (c_int, [c_void_p, c_char_p, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "jh_v2v_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_v2v_destroy": (None, [c_void_p]),
+    "jh_v2v_fold": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int)]),
     "jh_reproject_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "jh_reproject_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p,

@@ -213,6 +213,11 @@ int jh_v2v_forward(jh_v2v* net, const float* x_dev, float* y_dev, void* stream) 
   return launch_from_channel_last(net->plan.output, y_dev, s);
 }
 void jh_v2v_destroy(jh_v2v* net) { delete net; }
+int jh_v2v_fold(int joints, int t, int g, int* folded) {
+  JH_REQUIRE(joints >= 1 && t >= 1 && g >= 4 && g % 4 == 0 && folded, "jh_v2v_fold: bad argument");
+  *folded = v2v_fold_applies(joints, g) ? 1 : 0;      // (never a function of t)
+  return 0;
+}
 
 // ------------------------------------------------------------------ reprojection
 int64_t jh_reproject_workspace_bytes(int cams, int joints, int hs, int grid_size) {

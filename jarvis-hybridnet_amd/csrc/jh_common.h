@@ -388,6 +388,15 @@ int pack_wino_weights(int cin, int cout, const float* w, const float* b, ConvWei
 // volume without remainder strips
 int launch_conv3d_wino(const ConvWeights& w, const Act& x, const Act& y, double* stats, hipStream_t s,
                        const InNorm* in, int variant, const int* tables);
+// V2V's output layer with the closing passes of skip_res1 and decoder_res1 applied on load (csrc/conv3d_out_fold.hip):
+//   y = W (relu(IN(r_dec) + relu(IN(u0))) + relu(IN(r_skip) + f1)) + b,   bit-equal to the three launches it replaces.
+// v2v_fold_shape: the shapes the kernel takes, a function of (J, G) only; v2v_fold_applies: ... and JH_V2V_FOLD (default
+// on) as it stands at the call -- the one place where a plan decides.  w: the 1 x 1 x 1 layer packed in the Plain layout.
+bool v2v_fold_shape(int J, int G);
+bool v2v_fold_applies(int J, int G);
+int launch_conv3d_out_fold(const ConvWeights& w, const Act& r_dec, const double* st_dec, const float* u0,
+                           const double* st_u0, const float* r_skip, const double* st_skip, const float* f1,
+                           const Act& y, hipStream_t s);
 // The weight split of the bf16x3 kernels (host side): hi = bf16_rne(v), lo = bf16_rne(v - bf16_to_f32(hi)).
 inline unsigned short bf16_rne(float f) {
   unsigned u;

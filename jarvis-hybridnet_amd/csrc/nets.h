@@ -175,8 +175,10 @@ class V2VPlan : public Plan {
 
  private:
   // x_stats >= 0: x is a raw conv output whose InstanceNorm + ReLU the block applies on load
+  // raw_stats != nullptr: the block stops behind its second convolution -- *out is that convolution's raw output,
+  // *raw_stats its statistics -- and the reader applies the closing relu(IN(out) + x) on load (the output fold)
   int res_block(const ParamMap& pm, const std::string& p, int c, const Act& x, const float* extra,
-                Act* out, long x_stats = -1);
+                Act* out, long x_stats = -1, size_t* raw_stats = nullptr);
 };
 
 }  // namespace jh

@@ -569,7 +569,7 @@ int EffTrackPlan::build(const ParamMap& pm, const std::string& pre, int size, in
 // Res3DBlock.forward, v2vnet.py:27-43: relu(IN(conv(relu(IN(conv(x))))) + x)
 // `extra`, when set, is added after the final relu (the encoder/decoder skip sum).
 int V2VPlan::res_block(const ParamMap& pm, const std::string& p, int c, const Act& x,
-                       const float* extra, Act* out, long x_stats) {
+                       const float* extra, Act* out, long x_stats, size_t* raw_stats) {
   Act a;
   if (new_act(x.N, x.D, x.H, x.W, c, &a)) return 1;
   size_t s1 = 0, s2 = 0;
@@ -581,6 +581,7 @@ int V2VPlan::res_block(const ParamMap& pm, const std::string& p, int c, const Ac
   if (add_conv(pm, conv_desc(3, 3, 1, 1, c, c), p + "res_branch.3.weight", p + "res_branch.3.bias",
                false, a, *out, nullptr, true, &s2, (long)s1, 1.f / (float)(x.D * x.H * x.W),
                ACT_RELU)) return 1;
+  if (raw_stats) { *raw_stats = s2; return 0; }     // closed by the reader (V2VPlan::build: the output fold)
   add_norm(*out, s2, ACT_RELU, x.p, extra, out->p, -1, x_stats);
   return 0;
 }
@@ -605,7 +606,12 @@ int V2VPlan::build(const ParamMap& pm, const std::string& pre, int J, int T, int
   // where the V2V stage is a chain of 47-us launches: 2.089 ms with the branch against 2.059 without (medium 3.68 /
   // 3.59) -- each of these kernels already spreads over the chip, the two chains only take turns.  The side-stream
   // machinery was removed after that measurement: a plan is one chain on the caller's stream.
-  if (res_block(pm, e + "skip_res1.", 2 * J, f1, nullptr, &skip)) return 1;
+  // The output fold (csrc/conv3d_out_fold.hip; JH_V2V_FOLD=0: off): skip_res1 and decoder_res1 stop behind their second
+  // convolutions and the output layer applies both closing passes on load -- `skip` and `d1` then hold raw tensors and
+  // two norm_apply launches are gone.  Decided from (J, G) and the knob, never from T.
+  const bool fold = v2v_fold_applies(J, G);
+  size_t st_skip = 0, st_dec = 0;
+  if (res_block(pm, e + "skip_res1.", 2 * J, f1, nullptr, &skip, -1, fold ? &st_skip : nullptr)) return 1;
   if (new_act(T, Gq, Gq, Gq, 4 * J, &e0)) return 1;
   if (add_conv(pm, conv_desc(3, 2, 2, 0, 2 * J, 4 * J), e + "encoder_pool1.block.0.weight",
                e + "encoder_pool1.block.0.bias", false, f1, e0, nullptr, true, &st)) return 1;
@@ -613,10 +619,35 @@ int V2VPlan::build(const ParamMap& pm, const std::string& pre, int J, int T, int
   if (new_act(T, Gh, Gh, Gh, 2 * J, &u0)) return 1;
   if (add_conv(pm, deconv3d_k2s2_desc(4 * J, 2 * J), e + "decoder_upsample1.block.0.weight",
                e + "decoder_upsample1.block.0.bias", true, e1, u0, nullptr, true, &st)) return 1;
-  if (res_block(pm, e + "decoder_res1.", 2 * J, u0, skip.p, &d1, (long)st)) return 1;   // ... + res1
+  const size_t st_u0 = st;
+  if (res_block(pm, e + "decoder_res1.", 2 * J, u0, skip.p, &d1, (long)st, fold ? &st_dec : nullptr)) return 1;   // ... + res1
   if (new_act(T, Gh, Gh, Gh, J, &output)) return 1;
-  if (add_conv(pm, conv_desc(3, 1, 1, 0, 2 * J, J), pre + "output_layer.weight",
-               pre + "output_layer.bias", false, d1, output, nullptr, false, nullptr)) return 1;
+  if (!fold) {
+    if (add_conv(pm, conv_desc(3, 1, 1, 0, 2 * J, J), pre + "output_layer.weight",
+                 pre + "output_layer.bias", false, d1, output, nullptr, false, nullptr)) return 1;
+    return finish();
+  }
+  // the layer's weights as add_conv packs them (the MFMA form's Plain layout, at every precision); the launch is the fold's
+  const float *w = nullptr, *b = nullptr;
+  if (get(pm, pre + "output_layer.weight", (size_t)2 * J * J, &w)) return 1;
+  if (get(pm, pre + "output_layer.bias", J, &b)) return 1;
+  ConvUse use;
+  use.desc = conv_desc(3, 1, 1, 0, 2 * J, J);
+  use.has_bias = true; use.precision = precision; use.in_px = d1.Cp;
+  layers_.emplace_back();
+  const ConvLayer* layer = &layers_.back();
+  if (make_conv_layer(use, w, b, Gh, Gh, Gh, &layers_.back())) return 1;
+  JH_REQUIRE(layer->choice.form == ConvForm::Mfma && layer->choice.layout == WeightLayout::Plain,
+             "output fold: the 1 x 1 x 1 layer's weight layout");
+  bytes_ += layer->device_bytes();
+  // algorithmic work of the layer; bytes: four reads of the padded 2 J-channel tensors, one write of the output, the weights
+  const double vox = (double)T * d1.pixels();
+  char nm[96];
+  snprintf(nm, sizeof nm, "conv3d_k1s1fold_%dx%d@%d", 2 * J, J, Gh);
+  push(nm, 2.0 * vox * 2 * J * J, 4.0 * (vox * (4.0 * d1.Cp + output.Cp) + 2.0 * J * J),
+       [this, layer, d1, u0, skip, f1, st_dec, st_u0, st_skip](hipStream_t s) {
+    return launch_conv3d_out_fold(layer->w, d1, sc(st_dec), u0.p, sc(st_u0), skip.p, sc(st_skip), f1.p, output, s);
+  });
   return finish();
 }
 
