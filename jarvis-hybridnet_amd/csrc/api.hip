@@ -1580,7 +1580,7 @@ static int op_conv_body(int nd, int kind, int k, int stride, int pad, int cin, i
   }
   if (launch_to_channel_last(x_dev, x, s)) return 1;
   if (layer.launch(x, y, gate_p, stats, in, recipe ? &se : nullptr, s)) return 1;
-  if (!opd && norm_act >= 0 && launch_norm_apply(y, stats, 1e-5, norm_act, nullptr, nullptr, y.p, nullptr, s)) return 1;
+  if (!opd && norm_act >= 0 && launch_norm_apply(y, stats, norm_act, nullptr, nullptr, y.p, nullptr, s)) return 1;
   if (launch_from_channel_last(y, y_dev, s)) return 1;
   if (hipStreamSynchronize(s) != hipSuccess) { set_error(std::string("stream sync failed in ") + who); return 1; }
   return 0;
@@ -1642,7 +1642,7 @@ int jh_op_norm_apply(const float* x_dev, int n, int c, int d, int h, int w, cons
     if (sc.get(reinterpret_cast<void**>(&pool), npl * sizeof(double))) return 1;
     JH_CHECK_HIP(hipMemsetAsync(pool, 0, npl * sizeof(double), s));
   }
-  if (launch_norm_apply(x, st, 1e-5, act, r1.p, r2.p, write_y ? x.p : nullptr, pool, s, st1, min_block_kb)) return 1;
+  if (launch_norm_apply(x, st, act, r1.p, r2.p, write_y ? x.p : nullptr, pool, s, st1, min_block_kb)) return 1;
   if (write_y && launch_from_channel_last(x, y_dev, s)) return 1;
   std::vector<double> hp(want_pool ? npl : 0);
   if (want_pool) JH_CHECK_HIP(hipMemcpyAsync(hp.data(), pool, npl * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1672,7 +1672,7 @@ int jh_op_depthwise(int k, int c, const float* w_host, const float* x_dev, int n
   }
   if (launch_to_channel_last(x_dev, x, s)) return 1;
   if (launch_depthwise(x, wd, k, y.p, stats, s)) return 1;
-  if (norm_act >= 0 && launch_norm_apply(y, stats, 1e-5, norm_act, nullptr, nullptr, y.p, nullptr, s)) return 1;
+  if (norm_act >= 0 && launch_norm_apply(y, stats, norm_act, nullptr, nullptr, y.p, nullptr, s)) return 1;
   if (launch_from_channel_last(y, y_dev, s)) return 1;
   JH_CHECK_HIP(hipStreamSynchronize(s));
   return 0;

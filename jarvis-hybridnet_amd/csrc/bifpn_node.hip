@@ -175,12 +175,10 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
         first = false;
         if (tid < a.n_in * Cp) {
           float mean = 0.f, rstd = 1.f;
-          if (has_st) {                          // biased variance, eps 1e-5
-            const double mu = sv0 * (double)a.inv_cnt[sk];
-            double var = sv1 * (double)a.inv_cnt[sk] - mu * mu;
-            if (var < 0.0) var = 0.0;
-            mean = (float)mu;
-            rstd = (float)(1.0 / sqrt(var + 1e-5));
+          if (has_st) {                          // (the sums were read with the weights: times-inv scaling)
+            const NormCoef nc = norm_coef(sv0 * (double)a.inv_cnt[sk], sv1 * (double)a.inv_cnt[sk]);
+            mean = nc.mean;
+            rstd = nc.rstd;
           }
           const float ak1 = a.w[sk] * rstd;
           mr_[sk * Cp + scn] = ak1;                      // a_k
@@ -282,21 +280,14 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
     }
     __syncthreads();
   } else {
-    // 1. depthwise weights and statistics -> mean / rstd (biased variance, eps 1e-5)
+    // 1. depthwise weights and statistics -> mean / rstd
     for (int i = tid; i < 9 * Cp; i += NT) dwl[i] = a.dw[i];
     for (int i = tid; i < a.n_in * Cp; i += NT) {
       const int k = i / Cp, c = i % Cp;
-      float mean = 0.f, rstd = 1.f;
-      if (a.st[k]) {
-        const double* st = a.st[k] + ((size_t)n * Cp + c) * kStatW;
-        const double mu = exact_read(st) * (double)a.inv_cnt[k];
-        double var = exact_read(st + kLimbs) * (double)a.inv_cnt[k] - mu * mu;
-        if (var < 0.0) var = 0.0;
-        mean = (float)mu;
-        rstd = (float)(1.0 / sqrt(var + 1e-5));
-      }
-      mr_[k * Cp + c] = mean;
-      mr_[3 * Cp + k * Cp + c] = rstd;
+      NormCoef nc{0.f, 1.f};
+      if (a.st[k]) nc = norm_coef_times_inv(a.st[k] + ((size_t)n * Cp + c) * kStatW, a.inv_cnt[k]);
+      mr_[k * Cp + c] = nc.mean;
+      mr_[3 * Cp + k * Cp + c] = nc.rstd;
     }
     __syncthreads();
 
@@ -334,8 +325,7 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
               float4 x = v[u][k];
               const float4 mu = *reinterpret_cast<const float4*>(mr_ + k * Cp + c);
               const float4 rs = *reinterpret_cast<const float4*>(mr_ + 3 * Cp + k * Cp + c);
-              x.x = (x.x - mu.x) * rs.x; x.y = (x.y - mu.y) * rs.y;
-              x.z = (x.z - mu.z) * rs.z; x.w = (x.w - mu.w) * rs.w;
+              x = norm_sub4(x, mu, rs);
               const float wk = a.w[k];
               if (k == 0) {
                 r = make_float4(__fmul_rn(wk, x.x), __fmul_rn(wk, x.y), __fmul_rn(wk, x.z), __fmul_rn(wk, x.w));
@@ -344,8 +334,8 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
                 r.z = __fadd_rn(r.z, __fmul_rn(wk, x.z)); r.w = __fadd_rn(r.w, __fmul_rn(wk, x.w));
               }
             }
-            r.x = node_act(r.x, a.act); r.y = node_act(r.y, a.act);
-            r.z = node_act(r.z, a.act); r.w = node_act(r.w, a.act);
+            r.x = act(r.x, a.act); r.y = act(r.y, a.act);
+            r.z = act(r.z, a.act); r.w = act(r.w, a.act);
           }
           *reinterpret_cast<float4*>(Ft + pix * SF + c4 * 4) = r;
         }

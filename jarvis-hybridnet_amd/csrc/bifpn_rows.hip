@@ -86,12 +86,9 @@ void bifpn_rows_kernel(const NodeArgs a, int seg_rows, int strips) {
     if (a.st[k]) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const double* st = a.st[k] + ((size_t)n * kRC + c + j) * kStatW;
-        const double mu = exact_read(st) * (double)a.inv_cnt[k];
-        double var = exact_read(st + kLimbs) * (double)a.inv_cnt[k] - mu * mu;
-        if (var < 0.0) var = 0.0;
-        m4[j] = (float)mu;
-        r4[j] = (float)(1.0 / sqrt(var + 1e-5));
+        const NormCoef nc = norm_coef_times_inv(a.st[k] + ((size_t)n * kRC + c + j) * kStatW, a.inv_cnt[k]);
+        m4[j] = nc.mean;
+        r4[j] = nc.rstd;
       }
     }
 #pragma unroll

@@ -119,12 +119,9 @@ __global__ __launch_bounds__(kPsPairs * 128) void bifpn_rows_ps_kernel(const Nod
         if (a.st[k]) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const double* sp = a.st[k] + ((size_t)n * RC + c + j) * kStatW;
-            const double mu = exact_read(sp) * (double)a.inv_cnt[k];
-            double var = exact_read(sp + kLimbs) * (double)a.inv_cnt[k] - mu * mu;
-            if (var < 0.0) var = 0.0;
-            m4[j] = (float)mu;
-            r4[j] = (float)(1.0 / sqrt(var + 1e-5));
+            const NormCoef nc = norm_coef_times_inv(a.st[k] + ((size_t)n * RC + c + j) * kStatW, a.inv_cnt[k]);
+            m4[j] = nc.mean;
+            r4[j] = nc.rstd;
           }
         }
 #pragma unroll

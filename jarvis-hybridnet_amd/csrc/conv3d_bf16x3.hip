@@ -67,17 +67,7 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_kernel(B3Args a) {
   const int tx = tile % a.tiles_x, ty = (tile / a.tiles_x) % a.tiles_y, tz = tile / (a.tiles_x * a.tiles_y);
   const int oz0 = tz * TZ, oy0 = ty * TY, ox0 = tx * TX;
 
-  if (a.in_stats) {
-    for (int c = tid; c < a.cin_p; c += 256) {
-      const double* st = a.in_stats + ((size_t)n * a.cin_p + c) * kStatW;
-      const double mu = exact_read(st) * (double)a.in_inv;
-      double var = exact_read(st + kLimbs) * (double)a.in_inv - mu * mu;
-      if (var < 0.0) var = 0.0;
-      const float rsf = (float)(1.0 / sqrt(var + 1e-5));
-      nrm[c] = -(float)mu * rsf;
-      nrm[a.cin_p + c] = rsf;
-    }
-  }
+  if (a.in_stats) norm_table_fill(NormTable::FmaRstd, nrm, a.cin_p, a.in_stats, n, a.cin_p, a.in_inv, tid, 256);
   const float* __restrict__ xin = a.x + (size_t)n * a.D * a.H * a.W * a.cin_p;
 
   // A-operand addresses of this lane: row block rb = y row, row = x = lane & 15, K group g = lane >> 4:
@@ -112,16 +102,12 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_kernel(B3Args a) {
         if (a.in_stats) {
           const float4 m = *reinterpret_cast<const float4*>(nrm + c0);
           const float4 r = *reinterpret_cast<const float4*>(nrm + a.cin_p + c0);
-          v.x = __fmaf_rn(v.x, r.x, m.x); v.y = __fmaf_rn(v.y, r.y, m.y);
-          v.z = __fmaf_rn(v.z, r.z, m.z); v.w = __fmaf_rn(v.w, r.w, m.w);
-          if (a.in_act == ACT_RELU) {
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-          }
+          v = norm_fma4(v, m, r);
+          if (a.in_act == ACT_RELU) v = act4(v, ACT_RELU);      // (V2V: ReLU or nothing)
         }
       }
-      const bf16x4 hi = {(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-      const bf16x4 lo = {(__bf16)(v.x - (float)hi[0]), (__bf16)(v.y - (float)hi[1]),
-                         (__bf16)(v.z - (float)hi[2]), (__bf16)(v.w - (float)hi[3])};
+      bf16x4 hi, lo;
+      split_bf16x4(v, hi, lo);
       *reinterpret_cast<bf16x4*>(smem + pix * 32 + q * 8) = hi;
       *reinterpret_cast<bf16x4*>(smem + PLANE + pix * 32 + q * 8) = lo;
     }

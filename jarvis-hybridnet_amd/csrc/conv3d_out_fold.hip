@@ -11,7 +11,7 @@
 //
 // Bit-equal to the three launches by construction:
 //   * mean / rstd of the three statistics slots exactly as norm_apply_kernel derives them (elementwise.hip: fp64,
-//     `/ (double)P`, double eps, rounded to float), one (slot, channel) per thread, shared through LDS;
+//     norm_coef_over_count of operand_load.h), one (slot, channel) per thread, shared through LDS;
 //   * the elementwise part term for term what norm_apply_kernel evaluates (subtract, multiply, add, max; the build
 //     contracts nothing);
 //   * the contraction in the order of conv_mfma_kernel: voxels as A, weights as B (the packed operand of
@@ -42,7 +42,6 @@ struct OutFoldArgs {
   const double *st_dec, *st_u0, *st_skip;
   const float *w, *bias;
   float* y;
-  double eps;
   int P, Cp, cout_p, cout_p16;
 };
 
@@ -63,12 +62,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_out_fold_kernel(const OutFoldAr
   if (tid < 3 * Cp) {
     const int slot = tid / Cp, c = tid - slot * Cp;
     const double* base = slot == 0 ? a.st_dec : (slot == 1 ? a.st_u0 : a.st_skip);
-    const double* st = base + ((size_t)n * Cp + c) * kStatW;
-    const double mu = exact_read(st) / (double)P;
-    double var = exact_read(st + kLimbs) / (double)P - mu * mu;
-    if (var < 0.0) var = 0.0;
-    nrm_s[slot][0][c] = (float)mu;
-    nrm_s[slot][1][c] = (float)(1.0 / sqrt(var + a.eps));
+    const NormCoef k = norm_coef_over_count(base + ((size_t)n * Cp + c) * kStatW, P);
+    nrm_s[slot][0][c] = k.mean;
+    nrm_s[slot][1][c] = k.rstd;
   }
   __syncthreads();                                 // the only barrier: waves are independent from here on
   const int nrb = P >> 4;
@@ -235,7 +231,7 @@ int launch_conv3d_out_fold(const ConvWeights& w, const Act& r_dec, const double*
   OutFoldArgs a;
   a.r_dec = r_dec.p; a.u0 = u0; a.r_skip = r_skip; a.f1 = f1;
   a.st_dec = st_dec; a.st_u0 = st_u0; a.st_skip = st_skip;
-  a.w = w.w; a.bias = w.bias; a.y = y.p; a.eps = 1e-5;
+  a.w = w.w; a.bias = w.bias; a.y = y.p;
   a.P = (int)P; a.Cp = r_dec.Cp; a.cout_p = y.Cp; a.cout_p16 = w.cout_p16;
   const int nrb = (int)(P / 16);
   // row blocks per wave: up to 16, to amortise the prologue (fp64 mean / rstd, weights), but never fewer waves than

@@ -65,19 +65,8 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino_kernel(const WinoArgs a) {
   const int n = bid.z;
   const int nk8 = a.cin_p >> 3, nb = a.cout_p16 >> 4;
 
-  if (a.in_stats) {
-    for (int c = tid; c < a.cin_p; c += 256) {
-      const double* st = a.in_stats + ((size_t)n * a.cin_p + c) * kStatW;
-      const double mu = exact_read(st) * (double)a.in_inv;
-      double var = exact_read(st + kLimbs) * (double)a.in_inv - mu * mu;
-      if (var < 0.0) var = 0.0;
-      // (mean is stored as -mean * rstd: the commit is one FMA, exactly as in conv3d_wino_pw.hip --
-      // the two kernels must agree bit for bit, a launch picks one or the other by its tile count)
-      const float rsf = (float)(1.0 / sqrt(var + 1e-5));
-      nrm[c] = -(float)mu * rsf;
-      nrm[a.cin_p + c] = rsf;
-    }
-  }
+  // (FmaRstd: the products conv3d_wino_pw.hip forms at its commit -- a launch picks one or the other by its tile count)
+  if (a.in_stats) norm_table_fill(NormTable::FmaRstd, nrm, a.cin_p, a.in_stats, n, a.cin_p, a.in_inv, tid, 256);
   const float* __restrict__ xin = a.x + (size_t)n * a.D * a.H * a.W * a.cin_p;
 
   f32x4 acc[4][kWTZ][NR];
@@ -135,14 +124,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino_kernel(const WinoArgs a) {
           const int c = c0 + (idx & 1) * 4;
           const float4 nm = *reinterpret_cast<const float4*>(nrm + c);
           const float4 rs = *reinterpret_cast<const float4*>(nrm + a.cin_p + c);
-          v.x = fmaf(v.x, rs.x, nm.x); v.y = fmaf(v.y, rs.y, nm.y);
-          v.z = fmaf(v.z, rs.z, nm.z); v.w = fmaf(v.w, rs.w, nm.w);
-          if (a.in_act == ACT_RELU) {
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-          } else if (a.in_act == ACT_SILU) {
-            v.x = silu_fast(v.x); v.y = silu_fast(v.y);
-            v.z = silu_fast(v.z); v.w = silu_fast(v.w);
-          }
+          v = act4(norm_fma4(v, nm, rs), a.in_act);
         }
         *reinterpret_cast<float4*>(R + idx * 4) = v;          // [pix][q] = idx order
       }

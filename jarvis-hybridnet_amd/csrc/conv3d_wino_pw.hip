@@ -210,16 +210,7 @@ __global__ __launch_bounds__(512) void conv3d_wino_pw_kernel(const WinoArgs a, i
     // mean / rstd of image n (all channels) -> NT.  Written and read by the loader wave only
     // (program order inside one wave), so no barrier is involved.
     auto norm_table = [&](int n) __attribute__((always_inline)) {
-      if (a.in_stats) {
-        for (int c = lane; c < a.cin_p; c += 64) {
-          const double* st = a.in_stats + ((size_t)n * a.cin_p + c) * kStatW;
-          const double m = exact_read(st) * (double)a.in_inv;
-          double var = exact_read(st + kLimbs) * (double)a.in_inv - m * m;
-          if (var < 0.0) var = 0.0;
-          NT[c] = (float)m;
-          NT[a.cin_p + c] = (float)(1.0 / sqrt(var + 1e-5));
-        }
-      }
+      if (a.in_stats) norm_table_fill(NormTable::MeanRstd, NT, a.cin_p, a.in_stats, n, a.cin_p, a.in_inv, lane, 64);
     };
     // Two fp32 lanes per VALU instruction (v_pk_add_f32 / v_pk_mul_f32): while the matrix waves
     // stream MFMAs this wave gets roughly one issue slot per MFMA, so its instruction COUNT is
@@ -264,12 +255,9 @@ __global__ __launch_bounds__(512) void conv3d_wino_pw_kernel(const WinoArgs a, i
         *reinterpret_cast<float4*>(Rd + (lane + it * 64) * 4) = make_float4(lo.x, lo.y, hi.x, hi.y);   // [pix][q]
       }
     };
-    const int cmode = !a.in_stats ? 0 : (a.in_act == ACT_RELU ? 2 : (a.in_act == ACT_SILU ? 3 : 1));
+    const int cmode = operand_mode(a.in_stats, a.in_act);
     auto commit = [&](unsigned inv, int c0, float* Rd) __attribute__((always_inline)) {
-      if (cmode == 0) commit_mode(std::integral_constant<int, 0>{}, inv, c0, Rd);
-      else if (cmode == 2) commit_mode(std::integral_constant<int, 2>{}, inv, c0, Rd);
-      else if (cmode == 1) commit_mode(std::integral_constant<int, 1>{}, inv, c0, Rd);
-      else commit_mode(std::integral_constant<int, 3>{}, inv, c0, Rd);
+      dispatch_mode(cmode, [&](auto mode_c) __attribute__((always_inline)) { commit_mode(mode_c, inv, c0, Rd); });
     };
     // input transform B^T d B of every (z-slice, tile, channel quad): 6 x 16 x 2 = 192 items
     auto transform = [&](const float* Rs, float* Vd, int lc) __attribute__((always_inline)) {

@@ -81,17 +81,7 @@ __global__ __launch_bounds__(256) void conv_bf16x3_kernel(XArgs a) {
   const int oz0 = tz * TZ, oy0 = ty * TY, ox0 = tx * 16;
   const int iz0 = oz0 * S - (ND == 3 ? a.pad : 0), iy0 = oy0 * S - a.pad, ix0 = ox0 * S - a.pad;
 
-  if (a.in_stats) {
-    for (int c = tid; c < a.cin_p; c += 256) {
-      const double* st = a.in_stats + ((size_t)n * a.cin_p + c) * kStatW;
-      const double mu = exact_read(st) * (double)a.in_inv;
-      double var = exact_read(st + kLimbs) * (double)a.in_inv - mu * mu;
-      if (var < 0.0) var = 0.0;
-      const float rsf = (float)(1.0 / sqrt(var + 1e-5));
-      nrm[c] = -(float)mu * rsf;
-      nrm[a.cin_p + c] = rsf;
-    }
-  }
+  if (a.in_stats) norm_table_fill(NormTable::FmaRstd, nrm, a.cin_p, a.in_stats, n, a.cin_p, a.in_inv, tid, 256);
   const float* __restrict__ xin = a.x + (size_t)n * a.Din * a.Hin * a.Win * a.cin_p;
 
   // this lane's A rows: x = lane & 15; K group g reads tap (g / CH8) of the slice, channel octet g % CH8
@@ -134,18 +124,11 @@ __global__ __launch_bounds__(256) void conv_bf16x3_kernel(XArgs a) {
         if (a.in_stats) {
           const float4 m = *reinterpret_cast<const float4*>(nrm + c0);
           const float4 r = *reinterpret_cast<const float4*>(nrm + a.cin_p + c0);
-          v.x = __fmaf_rn(v.x, r.x, m.x); v.y = __fmaf_rn(v.y, r.y, m.y);
-          v.z = __fmaf_rn(v.z, r.z, m.z); v.w = __fmaf_rn(v.w, r.w, m.w);
-          if (a.in_act == ACT_RELU) {
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-          } else if (a.in_act == ACT_SILU) {
-            v.x = silu_fast(v.x); v.y = silu_fast(v.y); v.z = silu_fast(v.z); v.w = silu_fast(v.w);
-          }
+          v = act4(norm_fma4(v, m, r), a.in_act);
         }
       }
-      const xbf16x4 hi = {(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-      const xbf16x4 lo = {(__bf16)(v.x - (float)hi[0]), (__bf16)(v.y - (float)hi[1]),
-                          (__bf16)(v.z - (float)hi[2]), (__bf16)(v.w - (float)hi[3])};
+      xbf16x4 hi, lo;
+      split_bf16x4(v, hi, lo);
       unsigned char* dst = smem + ((pz * G::PY + py) * G::PXS + G::slot(px)) * G::PB + q * 8;
       *reinterpret_cast<xbf16x4*>(dst) = hi;
       *reinterpret_cast<xbf16x4*>(dst + G::PLANE) = lo;

@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "jh_common.h"
+#include "operand_load.h"
 
 namespace jh {
 
@@ -250,17 +251,8 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
 #pragma unroll
     for (int nr = 0; nr < NR; ++nr) acc[mr][nr] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  if (a.in_stats) {
-    // InstanceNorm of the input from the producer's fused statistics (biased variance)
-    for (int c = tid; c < a.cin_p; c += 256) {
-      const double* st = a.in_stats + ((size_t)n * a.cin_p + c) * kStatW;
-      const double mu = exact_read(st) * (double)a.in_inv;
-      double var = exact_read(st + kLimbs) * (double)a.in_inv - mu * mu;
-      if (var < 0.0) var = 0.0;
-      nrm[c] = (float)mu;
-      nrm[a.cin_p + c] = (float)(1.0 / sqrt(var + 1e-5));
-    }
-  }
+  // InstanceNorm of the input from the producer's fused statistics
+  if (a.in_stats) norm_table_fill(NormTable::MeanRstd, nrm, a.cin_p, a.in_stats, n, a.cin_p, a.in_inv, tid, 256);
 
   // the squeeze-excite gate of image n, behind mean / rstd (read while the patch is staged)
   float* gate_l = nrm + (a.in_stats ? 2 * a.cin_p : 0);
@@ -268,29 +260,16 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
   if (a.gate)
     for (int c = tid; c < a.cin_p; c += 256) gate_l[c] = a.gate[(size_t)n * a.cin_p + c];
   if (a.se.pool) {
-    // the gate of image n from the pooled sums: the arithmetic of se_gate_kernel (elementwise.hip), term
-    // for term, so the fused and the stand-alone form give the same bits
+    // the gate of image n from the pooled sums (operand_load.h: the bits of se_gate_kernel)
     const int C = a.se.C, S = a.se.S;
     float* mean = gate_l + a.cin_p;
     float* hid = mean + ((C + 3) & ~3);
-    for (int c = tid; c < C; c += 256)
-      mean[c] = (float)(exact_read(a.se.pool + ((size_t)n * a.cin_p + c) * kLimbs) * (double)a.se.inv_hw);
+    for (int c = tid; c < C; c += 256) mean[c] = se_mean(a.se.pool + ((size_t)n * a.cin_p + c) * kLimbs, a.se.inv_hw);
     __syncthreads();
-    for (int j = tid; j < S; j += 256) {
-      float acc = a.se.br[j];
-      for (int c = 0; c < C; ++c) acc = fmaf(a.se.wr[j * C + c], mean[c], acc);
-      hid[j] = acc / (1.f + expf(-acc));
-    }
+    for (int j = tid; j < S; j += 256) hid[j] = se_hidden(a.se.br[j], a.se.wr + j * C, mean, C);
     __syncthreads();
-    for (int c = tid; c < a.cin_p; c += 256) {
-      float g = 0.f;
-      if (c < C) {
-        float acc = a.se.be[c];
-        for (int j = 0; j < S; ++j) acc = fmaf(a.se.we[c * S + j], hid[j], acc);
-        g = 1.f / (1.f + expf(-acc));
-      }
-      gate_l[c] = g;
-    }
+    for (int c = tid; c < a.cin_p; c += 256)
+      gate_l[c] = c < C ? se_gate_value(a.se.be[c], a.se.we + c * S, hid, S) : 0.f;
   }
 
   const float* __restrict__ xin = a.x + (size_t)n * a.Din * a.Hin * a.Win * a.in_px;
@@ -377,14 +356,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
     if (a.in_stats) {
       const float4 mu = *reinterpret_cast<const float4*>(nrm + c);
       const float4 rs = *reinterpret_cast<const float4*>(nrm + a.cin_p + c);
-      v.x = (v.x - mu.x) * rs.x; v.y = (v.y - mu.y) * rs.y;
-      v.z = (v.z - mu.z) * rs.z; v.w = (v.w - mu.w) * rs.w;
-      if (a.in_act == ACT_RELU) {
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-      } else if (a.in_act == ACT_SILU) {
-        v.x = silu_fast(v.x); v.y = silu_fast(v.y);
-        v.z = silu_fast(v.z); v.w = silu_fast(v.w);
-      }
+      v = act4(norm_sub4(v, mu, rs), a.in_act);
     }
     if (gated) {
       const float4 g = *reinterpret_cast<const float4*>(gate_l + c);
@@ -417,7 +389,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
     if constexpr (PF) {
       // mode: 0 copy, 1 norm, 2 norm + relu, 3 norm + silu (dispatched once per pass, not per
       // item); the gate multiplies in every mode
-      const int mode = !a.in_stats ? 0 : (a.in_act == ACT_RELU ? 2 : (a.in_act == ACT_SILU ? 3 : 1));
+      const int mode = operand_mode(a.in_stats, a.in_act);
       auto commit_pf = [&](auto mode_c) __attribute__((always_inline)) {
         constexpr int MODE = decltype(mode_c)::value;
         float4 mu0 = make_float4(0.f, 0.f, 0.f, 0.f), rs0 = make_float4(1.f, 1.f, 1.f, 1.f), gt0 = rs0;
@@ -447,14 +419,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
             if (MODE != 0) {
               // pixels outside the image and channels past the tensor (loaded as 0) stay 0
               const float m = (pvo[it] < 0 || c0 + c4 * 4 >= a.in_px) ? 0.f : 1.f;
-              v.x = (v.x - mu.x) * rs.x; v.y = (v.y - mu.y) * rs.y;
-              v.z = (v.z - mu.z) * rs.z; v.w = (v.w - mu.w) * rs.w;
-              if (MODE == 2) {
-                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-              } else if (MODE == 3) {
-                v.x = silu_fast(v.x); v.y = silu_fast(v.y);
-                v.z = silu_fast(v.z); v.w = silu_fast(v.w);
-              }
+              v = act4(norm_sub4(v, mu, rs), mode_act(MODE));
               v.x *= m; v.y *= m; v.z *= m; v.w *= m;
             }
             if (gated) { v.x *= gt.x; v.y *= gt.y; v.z *= gt.z; v.w *= gt.w; }
@@ -464,10 +429,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
           }
         }
       };
-      if (mode == 0) commit_pf(std::integral_constant<int, 0>{});
-      else if (mode == 3) commit_pf(std::integral_constant<int, 3>{});
-      else if (mode == 2) commit_pf(std::integral_constant<int, 2>{});
-      else commit_pf(std::integral_constant<int, 1>{});
+      dispatch_mode(mode, commit_pf);
     } else {
       for (int idx = tid; idx < G::NPIX * Q4; idx += 256) {
         const float* src;

@@ -60,17 +60,11 @@ __global__ __launch_bounds__(256) void conv_pw_direct_kernel(const ConvArgs a, i
 #pragma unroll
   for (int u = 0; u < KW; ++u) { mu4[u] = (pf4){0.f, 0.f, 0.f, 0.f}; rs4[u] = (pf4){1.f, 1.f, 1.f, 1.f}; g4[u] = rs4[u]; }
   if (normed) {
-    float m = 0.f, r = 1.f;
-    if (lane < a.cin_p) {
-      const double* st = a.in_stats + ((size_t)n * a.cin_p + lane) * kStatW;
-      const double mu = exact_read(st) * (double)a.in_inv;
-      double var = exact_read(st + kLimbs) * (double)a.in_inv - mu * mu;
-      if (var < 0.0) var = 0.0;
-      m = (float)mu;
-      r = (float)(1.0 / sqrt(var + 1e-5));
-    }
-    nrm_s[wave][0][lane] = m;
-    nrm_s[wave][1][lane] = r;
+    // (MeanRstd form, one channel per lane and no loop: the reader is called directly)
+    NormCoef k{0.f, 1.f};
+    if (lane < a.cin_p) k = norm_coef_times_inv(a.in_stats + ((size_t)n * a.cin_p + lane) * kStatW, a.in_inv);
+    nrm_s[wave][0][lane] = k.mean;
+    nrm_s[wave][1][lane] = k.rstd;
     __builtin_amdgcn_wave_barrier();               // this wave wrote, this wave reads (LDS operations complete in order)
 #pragma unroll
     for (int u = 0; u < KW; ++u)
@@ -86,26 +80,15 @@ __global__ __launch_bounds__(256) void conv_pw_direct_kernel(const ConvArgs a, i
       if (16 * u + 4 * kq < a.cin_p) g4[u] = *reinterpret_cast<const pf4*>(a.gate + (size_t)n * a.cin_p + 16 * u + 4 * kq);
   } else if (a.se.pool) {
     // the squeeze-excite gate of image n from the pooled sums, per wave (C <= 48 channels, S <= 16 hidden units: lane c /
-    // lane j each own one): the arithmetic of se_gate_kernel (elementwise.hip) and of the general kernel's prologue, term
-    // for term -- whichever form the plan picks (by batch size), the gate has the same bits
+    // lane j each own one), the recipe of operand_load.h: whichever form the plan picks (by batch size), the gate has
+    // the same bits
     __shared__ float se_s[4][2][64];
     const int C = a.se.C, S = a.se.S;
-    se_s[wave][0][lane] = lane < C ? (float)(exact_read(a.se.pool + ((size_t)n * a.cin_p + lane) * kLimbs) * (double)a.se.inv_hw) : 0.f;
+    se_s[wave][0][lane] = lane < C ? se_mean(a.se.pool + ((size_t)n * a.cin_p + lane) * kLimbs, a.se.inv_hw) : 0.f;
     __builtin_amdgcn_wave_barrier();
-    float hid = 0.f;
-    if (lane < S) {
-      float acc = a.se.br[lane];
-      for (int c = 0; c < C; ++c) acc = fmaf(a.se.wr[lane * C + c], se_s[wave][0][c], acc);
-      hid = acc / (1.f + expf(-acc));
-    }
-    se_s[wave][1][lane] = hid;
+    se_s[wave][1][lane] = lane < S ? se_hidden(a.se.br[lane], a.se.wr + lane * C, se_s[wave][0], C) : 0.f;
     __builtin_amdgcn_wave_barrier();
-    float g = 0.f;
-    if (lane < C) {
-      float acc = a.se.be[lane];
-      for (int j = 0; j < S; ++j) acc = fmaf(a.se.we[lane * S + j], se_s[wave][1][j], acc);
-      g = 1.f / (1.f + expf(-acc));
-    }
+    const float g = lane < C ? se_gate_value(a.se.be[lane], a.se.we + lane * S, se_s[wave][1], S) : 0.f;
     __builtin_amdgcn_wave_barrier();                // (every lane has read the means before they are overwritten)
     se_s[wave][0][lane] = g;
     __builtin_amdgcn_wave_barrier();
@@ -152,6 +135,7 @@ __global__ __launch_bounds__(256) void conv_pw_direct_kernel(const ConvArgs a, i
       pf4 v = x[u];
       if (normed) {
         v = (v - mu4[u]) * rs4[u];
+        // (one branch per word, not per value: the per-value form of act() measured 3 - 6 % slower on these layers)
         if (act == ACT_SILU) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = silu_fast(v[j]);

@@ -66,16 +66,7 @@ constexpr int kDSPAD = 4;
 // buffer loads, the next channel pass's loads in flight under this pass's MFMAs; InstanceNorm / activation on load).
 // mean / rstd of image n's input channels into nrm[0 .. 2 cin_p)
 __device__ __forceinline__ void deconv4_load_norm(const ConvArgs& a, float* nrm, int n, int tid) {
-  if (a.in_stats) {
-    for (int c = tid; c < a.cin_p; c += 256) {
-      const double* st = a.in_stats + ((size_t)n * a.cin_p + c) * kStatW;
-      const double mu = exact_read(st) * (double)a.in_inv;
-      double var = exact_read(st + kLimbs) * (double)a.in_inv - mu * mu;
-      if (var < 0.0) var = 0.0;
-      nrm[c] = (float)mu;
-      nrm[a.cin_p + c] = (float)(1.0 / sqrt(var + 1e-5));
-    }
-  }
+  if (a.in_stats) norm_table_fill(NormTable::MeanRstd, nrm, a.cin_p, a.in_stats, n, a.cin_p, a.in_inv, tid, 256);
 }
 
 // NPIX patch pixels of KC8 * 8 channels per pass; `map(pix, &iy, &ix)` says which input pixel a patch pixel is
@@ -127,14 +118,7 @@ struct Deconv4Stage {
         float4 v = pf[it];
         if (MODE != 0) {
           const float m = (pvo[it] < 0 || c0 + c4 * 4 >= a.in_px) ? 0.f : 1.f;
-          v.x = (v.x - mu.x) * rs.x; v.y = (v.y - mu.y) * rs.y;
-          v.z = (v.z - mu.z) * rs.z; v.w = (v.w - mu.w) * rs.w;
-          if (MODE == 2) {
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-          } else if (MODE == 3) {
-            v.x = silu_fast(v.x); v.y = silu_fast(v.y);
-            v.z = silu_fast(v.z); v.w = silu_fast(v.w);
-          }
+          v = act4(norm_sub4(v, mu, rs), mode_act(MODE));
           v.x *= m; v.y *= m; v.z *= m; v.w *= m;
         }
         // quad c4 = channels of step c4 / 2, lane quarters 2 (c4 & 1) and + 1; slot of
@@ -147,11 +131,9 @@ struct Deconv4Stage {
   }
   // the pass's items from registers to the patch in LDS
   __device__ __forceinline__ void commit(const ConvArgs& a, const float* nrm, float2* lds2, int c0) {
-    const int mode = !a.in_stats ? 0 : (a.in_act == ACT_RELU ? 2 : (a.in_act == ACT_SILU ? 3 : 1));
-    if (mode == 0) commit_mode<0>(a, nrm, lds2, c0);
-    else if (mode == 3) commit_mode<3>(a, nrm, lds2, c0);
-    else if (mode == 2) commit_mode<2>(a, nrm, lds2, c0);
-    else commit_mode<1>(a, nrm, lds2, c0);
+    dispatch_mode(operand_mode(a.in_stats, a.in_act), [&](auto mode_c) __attribute__((always_inline)) {
+      commit_mode<decltype(mode_c)::value>(a, nrm, lds2, c0);
+    });
   }
 };
 

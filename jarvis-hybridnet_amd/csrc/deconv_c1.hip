@@ -16,6 +16,7 @@
 //
 // out(oy, ox) = sum_ci sum_ky,kx in(iy, ix, ci) * w(ci, 0, ky, kx),  oy = 2 iy - 1 + ky.
 #include "jh_common.h"
+#include "operand_load.h"
 
 namespace jh {
 
@@ -39,12 +40,9 @@ __global__ __launch_bounds__(256) void deconv_c1_kernel(
   for (int c = tid; c < Cp; c += 256) {
     float mean = 0.f, rstd = 1.f;
     if (st) {
-      const double* s2 = st + ((size_t)n * Cp + c) * kStatW;
-      const double mu = exact_read(s2) * (double)inv_cnt;
-      double var = exact_read(s2 + kLimbs) * (double)inv_cnt - mu * mu;
-      if (var < 0.0) var = 0.0;
-      mean = (float)mu;
-      rstd = (float)(1.0 / sqrt(var + 1e-5));
+      const NormCoef k = norm_coef_times_inv(st + ((size_t)n * Cp + c) * kStatW, inv_cnt);
+      mean = k.mean;
+      rstd = k.rstd;
     }
     nrm[c] = mean;
     nrm[Cp + c] = rstd;
@@ -81,16 +79,7 @@ __global__ __launch_bounds__(256) void deconv_c1_kernel(
         const int pix = (it0 + u) * 16 + slot;
         if (it0 + u < ITERS && pix < NPX && cact) {
           float4 x4 = v[u];
-          if (ok[u]) {
-            x4.x = (x4.x - mu.x) * rs.x; x4.y = (x4.y - mu.y) * rs.y;
-            x4.z = (x4.z - mu.z) * rs.z; x4.w = (x4.w - mu.w) * rs.w;
-            if (in_act == ACT_RELU) {
-              x4.x = fmaxf(x4.x, 0.f); x4.y = fmaxf(x4.y, 0.f); x4.z = fmaxf(x4.z, 0.f); x4.w = fmaxf(x4.w, 0.f);
-            } else if (in_act == ACT_SILU) {
-              x4.x = silu_fast(x4.x); x4.y = silu_fast(x4.y);
-              x4.z = silu_fast(x4.z); x4.w = silu_fast(x4.w);
-            }
-          }
+          if (ok[u]) x4 = act4(norm_sub4(x4, mu, rs), in_act);
           *reinterpret_cast<float4*>(tile + pix * S + lc4 * 4) = x4;
         }
       }

@@ -15,14 +15,9 @@
 // All of them stream float4 channel vectors; one thread owns a fixed channel
 // quad and walks pixels, so per-channel reductions stay in registers.
 #include "jh_common.h"
+#include "operand_load.h"
 
 namespace jh {
-
-__device__ __forceinline__ float act_apply(float v, int act) {
-  if (act == ACT_RELU) return fmaxf(v, 0.f);
-  if (act == ACT_SILU) return v / (1.f + expf(-v));
-  return v;
-}
 
 // Block-level reduction of per-thread float4 partials that belong to channel
 // quad (tid % q), followed by order-independent fp64 accumulation (exact_add: kLimbs
@@ -56,7 +51,7 @@ __device__ __forceinline__ void block_channel_reduce(float4 s1, float4 s2, int n
 // tensor has 132 quads: one pixel row per 256 threads used 132 of them).
 template <int ACT, bool R1, bool R2, bool Y, bool R1N = false>
 __global__ __launch_bounds__(1024) void norm_apply_kernel(
-    const float* __restrict__ x, const double* __restrict__ stats, double eps,
+    const float* __restrict__ x, const double* __restrict__ stats,
     const float* __restrict__ r1, const float* __restrict__ r2, float* __restrict__ y,
     double* __restrict__ pool, int P, int Cp, int ppb, const double* __restrict__ stats1 = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -74,12 +69,9 @@ __global__ __launch_bounds__(1024) void norm_apply_kernel(
   if (stats) {
     float* mr = sm + (pool ? rows * q * 4 : 0);          // [Cp] mean, [Cp] rstd
     for (int c = tid; c < Cp; c += BT) {
-      const double* st = stats + ((size_t)n * Cp + c) * kStatW;
-      const double mu = exact_read(st) / (double)P;
-      double var = exact_read(st + kLimbs) / (double)P - mu * mu;
-      if (var < 0.0) var = 0.0;
-      mr[c] = (float)mu;
-      mr[Cp + c] = (float)(1.0 / sqrt(var + eps));
+      const NormCoef k = norm_coef_over_count(stats + ((size_t)n * Cp + c) * kStatW, P);
+      mr[c] = k.mean;
+      mr[Cp + c] = k.rstd;
     }
     __syncthreads();
     if (active) {
@@ -92,12 +84,9 @@ __global__ __launch_bounds__(1024) void norm_apply_kernel(
   if (R1N) {
     float* mr = sm + (pool ? rows * q * 4 : 0);
     for (int c = tid; c < Cp; c += BT) {
-      const double* st = stats1 + ((size_t)n * Cp + c) * kStatW;
-      const double mu = exact_read(st) / (double)P;
-      double var = exact_read(st + kLimbs) / (double)P - mu * mu;
-      if (var < 0.0) var = 0.0;
-      mr[c] = (float)mu;
-      mr[Cp + c] = (float)(1.0 / sqrt(var + eps));
+      const NormCoef k = norm_coef_over_count(stats1 + ((size_t)n * Cp + c) * kStatW, P);
+      mr[c] = k.mean;
+      mr[Cp + c] = k.rstd;
     }
     __syncthreads();
     if (active) {
@@ -110,20 +99,12 @@ __global__ __launch_bounds__(1024) void norm_apply_kernel(
   const int p0 = blockIdx.x * ppb;
   const int p1 = min(P, p0 + ppb);
   float4 ps = make_float4(0, 0, 0, 0);
-  auto act1 = [](float v) __attribute__((always_inline)) {
-    if (ACT == ACT_RELU) return fmaxf(v, 0.f);
-    if (ACT == ACT_SILU) return silu_fast(v);
-    return v;
-  };
   auto finish = [&](float4 v, float4 a1, float4 a2, size_t off) __attribute__((always_inline)) {
-    v.x = (v.x - mean.x) * rstd.x; v.y = (v.y - mean.y) * rstd.y;
-    v.z = (v.z - mean.z) * rstd.z; v.w = (v.w - mean.w) * rstd.w;
-    if (R1N) {       // relu((r1 - mean1) * rstd1): the expression the stand-alone pass evaluates (ACT_RELU form above)
-      a1.x = fmaxf((a1.x - mean1.x) * rstd1.x, 0.f); a1.y = fmaxf((a1.y - mean1.y) * rstd1.y, 0.f);
-      a1.z = fmaxf((a1.z - mean1.z) * rstd1.z, 0.f); a1.w = fmaxf((a1.w - mean1.w) * rstd1.w, 0.f);
-    }
+    v = norm_sub4(v, mean, rstd);
+    // relu((r1 - mean1) * rstd1): the expression the stand-alone pass evaluates (ACT_RELU form)
+    if (R1N) a1 = act4(norm_sub4(a1, mean1, rstd1), ACT_RELU);
     if (R1) { v.x += a1.x; v.y += a1.y; v.z += a1.z; v.w += a1.w; }
-    v.x = act1(v.x); v.y = act1(v.y); v.z = act1(v.z); v.w = act1(v.w);
+    v = act4(v, ACT);
     if (R2) { v.x += a2.x; v.y += a2.y; v.z += a2.z; v.w += a2.w; }
     if (Y) *reinterpret_cast<float4*>(y + off) = v;         // !Y: pooled sums only
     ps.x += v.x; ps.y += v.y; ps.z += v.z; ps.w += v.w;
@@ -155,7 +136,7 @@ __global__ __launch_bounds__(1024) void norm_apply_kernel(
     block_channel_reduce(ps, ps, 1, q, rows, tid, active, pool + (size_t)n * Cp * kLimbs, 1, sm);
 }
 
-int launch_norm_apply(const Act& x, const double* stats, double eps, int act, const float* r1,
+int launch_norm_apply(const Act& x, const double* stats, int act, const float* r1,
                       const float* r2, float* y, double* pool, hipStream_t s, const double* r1_stats,
                       int min_block_kb) {
   const int P = (int)x.pixels();
@@ -183,17 +164,17 @@ int launch_norm_apply(const Act& x, const double* stats, double eps, int act, co
   if (r1_stats) {     // residual operand normalised (+ReLU) on load: V2V residual blocks only
     JH_REQUIRE(stats && r1 && y && act == ACT_RELU && !pool, "norm_apply: normalised residual operand");
     if (r2)
-      hipLaunchKernelGGL((norm_apply_kernel<ACT_RELU, true, true, true, true>), grid, dim3(bt), sm, s, x.p, stats, eps,
+      hipLaunchKernelGGL((norm_apply_kernel<ACT_RELU, true, true, true, true>), grid, dim3(bt), sm, s, x.p, stats,
                          r1, r2, y, pool, P, x.Cp, ppb, r1_stats);
     else
-      hipLaunchKernelGGL((norm_apply_kernel<ACT_RELU, true, false, true, true>), grid, dim3(bt), sm, s, x.p, stats, eps,
+      hipLaunchKernelGGL((norm_apply_kernel<ACT_RELU, true, false, true, true>), grid, dim3(bt), sm, s, x.p, stats,
                          r1, r2, y, pool, P, x.Cp, ppb, r1_stats);
     JH_CHECK_HIP(hipGetLastError());
     return 0;
   }
 #define JH_NA(A, B1, B2, BY)                                                                              \
   if (act == A && (r1 != nullptr) == B1 && (r2 != nullptr) == B2 && (y != nullptr) == BY) {             \
-    hipLaunchKernelGGL((norm_apply_kernel<A, B1, B2, BY>), grid, dim3(bt), sm, s, x.p, stats, eps, r1, r2, y, \
+    hipLaunchKernelGGL((norm_apply_kernel<A, B1, B2, BY>), grid, dim3(bt), sm, s, x.p, stats, r1, r2, y,      \
                        pool, P, x.Cp, ppb, nullptr);                                                               \
     JH_CHECK_HIP(hipGetLastError());                                                                      \
     return 0;                                                                                             \
@@ -215,24 +196,12 @@ __global__ __launch_bounds__(256) void se_gate_kernel(
   float* mean = sm;
   float* hid = sm + C;
   const int n = blockIdx.x;
-  for (int c = threadIdx.x; c < C; c += blockDim.x)
-    mean[c] = (float)(exact_read(pool + ((size_t)n * Cp + c) * kLimbs) * (double)inv_hw);
+  for (int c = threadIdx.x; c < C; c += blockDim.x) mean[c] = se_mean(pool + ((size_t)n * Cp + c) * kLimbs, inv_hw);
   __syncthreads();
-  for (int j = threadIdx.x; j < S; j += blockDim.x) {
-    float acc = br[j];
-    for (int c = 0; c < C; ++c) acc = fmaf(wr[j * C + c], mean[c], acc);
-    hid[j] = acc / (1.f + expf(-acc));
-  }
+  for (int j = threadIdx.x; j < S; j += blockDim.x) hid[j] = se_hidden(br[j], wr + j * C, mean, C);
   __syncthreads();
-  for (int c = threadIdx.x; c < Cp; c += blockDim.x) {
-    float g = 0.f;
-    if (c < C) {
-      float acc = be[c];
-      for (int j = 0; j < S; ++j) acc = fmaf(we[c * S + j], hid[j], acc);
-      g = 1.f / (1.f + expf(-acc));
-    }
-    gate[(size_t)n * Cp + c] = g;
-  }
+  for (int c = threadIdx.x; c < Cp; c += blockDim.x)
+    gate[(size_t)n * Cp + c] = c < C ? se_gate_value(be[c], we + c * S, hid, S) : 0.f;
 }
 
 int launch_se_gate(const double* pool, int N, int C, int Cp, int S, float inv_hw, const float* wr,
@@ -409,11 +378,9 @@ __global__ __launch_bounds__(256) void depthwise_lds_kernel(
       if (tid < q * 4) {
         const int cq = tid >> 2, comp = tid & 3;
         const double P = (double)(H * W);
-        const double mu = tot[(cq * 2 + 0) * 4 + comp] / P;
-        double var = tot[(cq * 2 + 1) * 4 + comp] / P - mu * mu;
-        if (var < 0.0) var = 0.0;
-        mr[tid] = (float)mu;
-        mr[CC + tid] = (float)(1.0 / sqrt(var + 1e-5));
+        const NormCoef k = norm_coef(tot[(cq * 2 + 0) * 4 + comp] / P, tot[(cq * 2 + 1) * 4 + comp] / P);   // (over count)
+        mr[tid] = k.mean;
+        mr[CC + tid] = k.rstd;
       }
       __syncthreads();
       df4 ps = (df4){0.f, 0.f, 0.f, 0.f};
@@ -544,8 +511,8 @@ __global__ __launch_bounds__(256) void fuse_kernel(FuseArgs f, float* __restrict
       acc.z = __fadd_rn(acc.z, __fmul_rn(f.w[k], v.z));
       acc.w = __fadd_rn(acc.w, __fmul_rn(f.w[k], v.w));
     }
-    acc.x = act_apply(acc.x, f.act); acc.y = act_apply(acc.y, f.act);
-    acc.z = act_apply(acc.z, f.act); acc.w = act_apply(acc.w, f.act);
+    acc.x = act_exact(acc.x, f.act); acc.y = act_exact(acc.y, f.act);
+    acc.z = act_exact(acc.z, f.act); acc.w = act_exact(acc.w, f.act);
     *reinterpret_cast<float4*>(out + i * 4) = acc;
   }
 }
