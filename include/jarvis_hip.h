@@ -690,6 +690,15 @@ long jh_deconv4_window_launches(void);
 int jh_conv_form(int nd, int kind, int k, int stride, int pad, int cin, int cout, int has_bias,
                  int want_stats, int gate /*0 none, 1 tensor, 2 recipe*/, int precision,
                  int in_px /*0: cpad(cin)*/, char* name, int name_cap);
+/* Which kernel form a fused BiFPN node takes, with its row segmentation and launch shape (no GPU needed;
+ * csrc/node_layer.h): c -> cout channels (unpadded) on n images of h x w, n_in inputs in modes[] (0 same level, 1 x2
+ * up-sampled, 2 x4 up-sampled, 3 2x2-max-pooled), activation 0 none / 1 relu / 2 silu, batch_class 0 by launch size
+ * (jh_op_bifpn_node) / 1 time batch below 8 / 2 time batch of 8 and more, want_pool: the caller could use the
+ * 2x2-max-pooled output.  Reads JH_NODE_ROWS once per process.  name receives "tile", "rows_wave", "rows_pairs" or
+ * "rows_wg"; out receives seg_rows, strips, segs, grid.x, grid.y, block.x, dynamic LDS bytes, pool (the node writes the
+ * pooled output).  Fails for a node no form takes. */
+int jh_node_form(int c, int cout, int n, int h, int w, int n_in, const int* modes, int act, int batch_class,
+                 int want_pool, char* name, int name_cap, int32_t out[8]);
 /* TEST-ONLY: the operand transform a consumer applies while it stages its input (csrc/jh_common.h: InNorm, SeGate),
  * described from the host so that only the consumer is under test. */
 typedef struct jh_op_operand {

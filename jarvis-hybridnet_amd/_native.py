@@ -206,6 +206,8 @@ _SIGS = {
                    [c_void_p, c_int, c_void_p, c_void_p]),
     "jh_deconv4_window_launches": (ctypes.c_long, []),
     "jh_conv_form": (c_int, [c_int] * 12 + [c_char_p, c_int]),
+    "jh_node_form": (c_int, [c_int] * 6 + [ctypes.POINTER(c_int)] + [c_int] * 3 +
+                     [c_char_p, c_int, ctypes.POINTER(ctypes.c_int32)]),
     "jh_op_conv_operand": (c_int, [c_int] * 7 + [c_void_p, c_void_p, c_void_p] + [c_int] * 4 +
                            [c_void_p, ctypes.POINTER(OpOperand), c_void_p, c_void_p]),
     "jh_op_se_gate": (c_int, [c_void_p, c_int, c_int, c_int, c_float] + [c_void_p] * 6),

@@ -489,19 +489,20 @@ static int upload_images(Scratch& mem, const void*** table, const void* const* i
 
 // What the creation of both predictors shares: the precision resolved into cfg (the predictor's own setting;
 // JH_PRECISION_DEFAULT follows the process-wide default), and EffTrackPlans set up, before build(), with it and with
-// the forms of the predictor's time-batch class (EffTrackPlan::node_rows, Plan::norm_block_kb).
+// the forms of the predictor's time-batch class (EffTrackPlan::node_class, Plan::norm_block_kb).
 struct PlanSetup {
-  int precision = 0, node_rows = -1, norm_kb = 0;
-  int init(jh_predictor_config* cfg, int rows, int kb) {
+  int precision = 0, norm_kb = 0;
+  NodeBatchClass node_class = NodeBatchClass::ByLaunchSize;
+  int init(jh_predictor_config* cfg, NodeBatchClass cls, int kb) {
     JH_REQUIRE(cfg->precision >= JH_PRECISION_DEFAULT && cfg->precision <= JH_PRECISION_BF16X3_WIDE,
                "jh_predictor_config.precision: unknown mode");
     if (cfg->precision == JH_PRECISION_DEFAULT) cfg->precision = precision_mode();
-    precision = cfg->precision; node_rows = rows; norm_kb = kb;
+    precision = cfg->precision; node_class = cls; norm_kb = kb;
     return 0;
   }
   std::unique_ptr<EffTrackPlan> efftrack() const {
     std::unique_ptr<EffTrackPlan> p(new EffTrackPlan());
-    p->precision = precision; p->node_rows = node_rows; p->norm_block_kb = norm_kb;
+    p->precision = precision; p->node_class = node_class; p->norm_block_kb = norm_kb;
     return p;
   }
 };
@@ -673,13 +674,13 @@ int jh_predictor_create(const jh_params* center_params, const jh_params* hybrid_
   JH_REQUIRE(cfg->cam_lo >= 0 && cfg->cam_n >= 1 && cfg->cam_lo + cfg->cam_n <= pr->C, "camera range");
   JH_REQUIRE(pr->G % 4 == 0, "ROI_CUBE_SIZE / GRID_SPACING must be a multiple of 4");
   const int N = pr->T * pr->Cloc;
-  // (form of the BiFPN nodes: by the time batch alone, see EffTrackPlan::node_rows)
-  const int node_rows = pr->T >= 8 ? 1 : 0;
+  // (form of the BiFPN nodes: by the time batch alone, see EffTrackPlan::node_class)
+  const NodeBatchClass node_class = pr->T >= 8 ? NodeBatchClass::AtLeast8 : NodeBatchClass::Below8;
   // (... and with it the blocking of the InstanceNorm / pooled-sum passes, Plan::norm_block_kb; JH_NODE_ROWS=0 switches
   //  every class-dependent form off: one arithmetic for all time batches)
-  const int norm_kb = node_rows && JH_ENV_KNOB("JH_NODE_ROWS") != 0 ? 64 : 0;
+  const int norm_kb = node_class == NodeBatchClass::AtLeast8 && JH_ENV_KNOB("JH_NODE_ROWS") != 0 ? 64 : 0;
   PlanSetup setup;
-  if (setup.init(&pr->cfg, node_rows, norm_kb)) return 1;
+  if (setup.init(&pr->cfg, node_class, norm_kb)) return 1;
   if (center_params) {
     pr->center = setup.efftrack();
     if (pr->center->build(center_params->map, "", cfg->center_model, 1, N, cfg->center_size,
@@ -1352,7 +1353,7 @@ int jh_predictor2d_create(const jh_params* center_params, const jh_params* kp_pa
   JH_REQUIRE(pr->T >= 1, "batch");
   JH_REQUIRE(cfg->img_w >= pr->B + 1 && cfg->img_h >= pr->B + 1, "image smaller than the bounding box");
   PlanSetup setup;                            // (the plans' own node form and norm blocking: no time-batch class here)
-  if (setup.init(&pr->cfg, -1, 0)) return 1;
+  if (setup.init(&pr->cfg, NodeBatchClass::ByLaunchSize, 0)) return 1;
   pr->center = setup.efftrack();
   if (pr->center->build(center_params->map, "", cfg->center_model, 1, pr->T, cfg->center_size,
                         cfg->center_size)) return 1;
@@ -1491,6 +1492,26 @@ int jh_conv_form(int nd, int kind, int k, int stride, int pad, int cin, int cout
   use.precision = precision;
   use.in_px = in_px;
   snprintf(name, (size_t)name_cap, "%s", conv_choice_name(choose_conv(use)).c_str());
+  return 0;
+}
+
+int jh_node_form(int c, int cout, int n, int h, int w, int n_in, const int* modes, int act, int batch_class,
+                 int want_pool, char* name, int name_cap, int32_t* out) {
+  JH_REQUIRE(c >= 1 && cout >= 1 && n >= 1 && h >= 1 && w >= 1 && n_in >= 2 && n_in <= 3 && modes && act >= 0 &&
+             act <= 2 && batch_class >= 0 && batch_class <= 2 && name && name_cap > 0 && out,
+             "jh_node_form: bad argument");
+  NodeUse use;
+  use.Cp = cpad(c); use.cout_p = cpad(cout); use.cout_p16 = round_up(cout, 16);
+  use.N = n; use.H = h; use.W = w; use.n_in = n_in; use.act = act;
+  for (int i = 0; i < n_in; ++i) use.mode[i] = modes[i];
+  use.cls = static_cast<NodeBatchClass>(batch_class);
+  use.want_pool = want_pool != 0;
+  NodeChoice ch;
+  if (choose_node(use, &ch)) return 1;
+  snprintf(name, (size_t)name_cap, "%s", node_choice_name(ch).c_str());
+  const int32_t v[8] = {ch.seg_rows, ch.strips, ch.segs, (int32_t)ch.grid.x, (int32_t)ch.grid.y, (int32_t)ch.block.x,
+                        (int32_t)ch.lds, ch.pool ? 1 : 0};
+  std::copy(v, v + 8, out);
   return 0;
 }
 
@@ -1837,7 +1858,9 @@ int jh_op_bifpn_node(int n_in, const int* modes, const float* weights, int act, 
     if (hipMemsetAsync(ost, 0, (size_t)n * y.Cp * kStatW * sizeof(double), s) != hipSuccess) { rc = 1; break; }
     a.dw = dwd; a.pw = cw.w; a.bias = cw.bias; a.y = y.p; a.stats = ost;
     a.N = n; a.H = h; a.W = w; a.Cp = Cp; a.cout_p = y.Cp; a.cout_p16 = cw.cout_p16;
-    if ((rc = launch_bifpn_node(a, s))) break;
+    NodeChoice choice;
+    if ((rc = choose_node(node_use(a, NodeBatchClass::ByLaunchSize, false), &choice))) break;
+    if ((rc = launch_bifpn_node(a, choice, s))) break;
     if ((rc = launch_from_channel_last(y, y_dev, s))) break;
     if (hipStreamSynchronize(s) != hipSuccess) { set_error("stream sync failed in jh_op_bifpn_node"); rc = 1; }
   } while (0);

@@ -1,4 +1,5 @@
-// Arguments of the fused BiFPN node kernel (csrc/bifpn_node.hip).
+// Arguments of the fused BiFPN node kernels (csrc/bifpn_node.hip, csrc/bifpn_rows*.hip); which kernel runs a node and
+// how it is launched: csrc/node_layer.h.
 #pragma once
 #include "jh_common.h"
 
@@ -19,15 +20,9 @@ struct NodeArgs {
   int N, H, W, Cp, cout_p, cout_p16, cf;   // cf = channels per halo chunk (multiple of 4)
   int blds = 0;            // pointwise weights staged in LDS behind the operand tile
   int alias = 0;           // operand tile written over the halo tile (single channel chunk)
-  float* y_pool = nullptr; // row-streaming form, two inputs: also the 2x2-max-pooled raw output [N][H/2][W/2][cout_p]
-  int rows = -1;           // row-streaming form (bifpn_rows.hip): 1 wherever the shape allows, 0 never, -1 by launch size,
-                           // 2 = the workgroup form with 8-row segments (wide pyramids, time batches below 8)
+  float* y_pool = nullptr; // row-streaming forms (NodeChoice::pool): also the 2x2-max-pooled raw output [N][H/2][W/2][cout_p]
+  int reserved = 0;        // unused: keeps sizeof(NodeArgs), and with it the offsets of the row kernels' scalar arguments
 };
-
-
-// csrc/bifpn_rows.hip: will this node take the row-streaming form?  (host; also used when a plan is built)
-bool bifpn_rows_eligible(const NodeArgs& a);
-bool bifpn_rows_ragged88(const NodeArgs& a);    // 88 channels, class >= 8, width no multiple of 16: workgroup form
 
 #if defined(__HIPCC__)
 constexpr int kNodeTY = 8, kNodeTX = 16, kNodePY = 10, kNodePX = 18, kNodeNRG = 4;

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include "conv_mfma.h"
 #include "bifpn_node.h"
+#include "node_layer.h"
 
 namespace jh {
 
@@ -497,76 +498,36 @@ __global__ __launch_bounds__(512, 6) void bifpn_node_kernel(const NodeArgs a) {
   }
 }
 
-template <int NIN, int M0, int M1, int M2, bool ONE, int CP = 0>
-static int launch_node_one(const NodeArgs& a, size_t lds, hipStream_t s) {
-  auto kern = bifpn_node_kernel<NIN, M0, M1, M2, ONE, CP>;
-  static bool big = false;
-  if (lds > 64 * 1024 && !big) {
-    JH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    big = true;
-  }
-  const int tiles = ((a.H + kNodeTY - 1) / kNodeTY) * ((a.W + kNodeTX - 1) / kNodeTX);
-  hipLaunchKernelGGL(kern, dim3(tiles, a.N), dim3(512), lds, s, a);
-  JH_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
 template <int NIN, int M0, int M1, int M2>
-static int launch_node_variant(const NodeArgs& a, size_t lds, hipStream_t s) {
+static int launch_node_variant(const NodeArgs& a, const NodeChoice& c, hipStream_t s) {
   // the small model's pyramid (56 channels, one MFMA group of 4 column blocks, weights in LDS)
   if (a.alias && a.blds && a.Cp == 56 && a.cf == 56 && a.cout_p16 == 16 * kNodeNRG)
-    return launch_node_one<NIN, M0, M1, M2, true, 56>(a, lds, s);
-  if (a.alias) return launch_node_one<NIN, M0, M1, M2, true>(a, lds, s);
-  return launch_node_one<NIN, M0, M1, M2, false>(a, lds, s);
+    return launch_node_kernel<bifpn_node_kernel<NIN, M0, M1, M2, true, 56>>(c, s, a);
+  if (a.alias) return launch_node_kernel<bifpn_node_kernel<NIN, M0, M1, M2, true, 0>>(c, s, a);
+  return launch_node_kernel<bifpn_node_kernel<NIN, M0, M1, M2, false, 0>>(c, s, a);
 }
 
-bool bifpn_rows_eligible(const NodeArgs& a);
-int launch_bifpn_rows(const NodeArgs& a, hipStream_t s);
-
-int launch_bifpn_node(const NodeArgs& args, hipStream_t s) {
-  if (bifpn_rows_eligible(args)) return launch_bifpn_rows(args, s);      // csrc/bifpn_rows.hip
-  NodeArgs a = args;
-  const size_t head = ((size_t)3 * a.Cp * 2 + (size_t)9 * a.Cp) * sizeof(float);
-  const size_t at_bytes = (size_t)128 * (a.Cp + 4) * sizeof(float);
-  const size_t red = (size_t)8 * kNodeNRG * 16 * 2 * sizeof(double);   // conv_epilogue: fp64 partials
-  const size_t halo_px = (size_t)kNodePY * kNodePX * sizeof(float);
-  // preferred: the whole channel range in one halo chunk, operand tile aliased onto it
-  // (3 workgroups per CU for the 56-channel pyramid of the small model)
-  const size_t b_bytes = (size_t)(a.Cp / 8) * (a.cout_p16 / 16) * 128 * sizeof(float);
-  a.blds = (b_bytes <= 16 * 1024) ? 1 : 0;        // 512 threads x 32 bytes
-  size_t lds = head + std::max(halo_px * a.Cp, at_bytes + (a.blds ? b_bytes : red));
-  a.cf = a.Cp;
-  a.alias = 1;
-  if (a.Cp > 64 || a.Cp < 32 || lds > 54 * 1024) {
-    // fallback: separate operand tile, halo chunked to the LDS budget
-    a.alias = 0;
-    a.blds = 0;
-    size_t budget = 78 * 1024;
-    const size_t fixed = head + at_bytes;
-    if (fixed + halo_px * 12 > budget) budget = 156 * 1024;
-    int cf = std::min(a.Cp, 64);          // the depthwise rounds handle <= 16 channel quads
-    while (cf > 8 && fixed + halo_px * cf > budget) cf -= 4;
-    a.cf = cf;
-    lds = fixed + halo_px * cf;
-    JH_REQUIRE(halo_px * cf >= red, "halo chunk too small");
+int launch_bifpn_node(const NodeArgs& args, const NodeChoice& c, hipStream_t s) {
+  switch (c.form) {
+    case NodeForm::RowsWave: return launch_bifpn_rows(args, c, s);
+    case NodeForm::RowsPairs: return launch_bifpn_rows_ps(args, c, s);
+    case NodeForm::RowsWg: return launch_bifpn_rows_wg(args, c, s);
+    case NodeForm::Tile: break;
   }
-  JH_REQUIRE(lds <= 160 * 1024, "BiFPN node does not fit LDS");
-  const int m0 = a.mode[0], m1 = a.mode[1], m2 = a.mode[2];
-  JH_REQUIRE(m0 == FUSE_SAME, "first input of a node is at the node's own level");
-  if (a.n_in == 2 && m1 == FUSE_UP2) return launch_node_variant<2, FUSE_SAME, FUSE_UP2, 0>(a, lds, s);
-  if (a.n_in == 2 && m1 == FUSE_POOL2) return launch_node_variant<2, FUSE_SAME, FUSE_POOL2, 0>(a, lds, s);
-  if (a.n_in == 3 && m1 == FUSE_SAME && m2 == FUSE_POOL2)
-    return launch_node_variant<3, FUSE_SAME, FUSE_SAME, FUSE_POOL2>(a, lds, s);
-  if (a.n_in == 3 && m1 == FUSE_UP2 && m2 == FUSE_UP4)
-    return launch_node_variant<3, FUSE_SAME, FUSE_UP2, FUSE_UP4>(a, lds, s);
-  // (bottom-up node whose finer-level input arrives pooled -- written by that level's row node -- but which is
-  //  itself too small for the row form)
-  if (a.n_in == 3 && m1 == FUSE_SAME && m2 == FUSE_SAME)
-    return launch_node_variant<3, FUSE_SAME, FUSE_SAME, FUSE_SAME>(a, lds, s);
-  // (... and its two-input sibling at the coarsest level: P7 from P7_in and the pooled P6 written by P6's row node)
-  if (a.n_in == 2 && m1 == FUSE_SAME) return launch_node_variant<2, FUSE_SAME, FUSE_SAME, 0>(a, lds, s);
-  JH_REQUIRE(false, "unsupported BiFPN node variant");
+  NodeArgs a = args;
+  a.blds = c.blds; a.alias = c.alias; a.cf = c.cf;
+  switch (c.variant) {
+    case NodeVariant::Up2: return launch_node_variant<2, FUSE_SAME, FUSE_UP2, 0>(a, c, s);
+    case NodeVariant::Pool2: return launch_node_variant<2, FUSE_SAME, FUSE_POOL2, 0>(a, c, s);
+    case NodeVariant::SamePool2: return launch_node_variant<3, FUSE_SAME, FUSE_SAME, FUSE_POOL2>(a, c, s);
+    case NodeVariant::Up2Up4: return launch_node_variant<3, FUSE_SAME, FUSE_UP2, FUSE_UP4>(a, c, s);
+    // (bottom-up node whose finer-level input arrives pooled -- written by that level's row node -- but which is
+    //  itself too small for the row form)
+    case NodeVariant::Same3: return launch_node_variant<3, FUSE_SAME, FUSE_SAME, FUSE_SAME>(a, c, s);
+    // (... and its two-input sibling at the coarsest level: P7 from P7_in and the pooled P6 written by P6's row node)
+    case NodeVariant::Same2: return launch_node_variant<2, FUSE_SAME, FUSE_SAME, 0>(a, c, s);
+  }
+  JH_REQUIRE(false, "BiFPN node: variant");
 }
 
 }  // namespace jh

@@ -27,6 +27,7 @@
 
 #include "conv_mfma.h"
 #include "bifpn_node.h"
+#include "node_layer.h"
 
 namespace jh {
 
@@ -352,106 +353,30 @@ void bifpn_rows_kernel(const NodeArgs a, int seg_rows, int strips) {
   }
 }
 
-// Which nodes take the row-streaming form: the 56-channel (small model) or 88-channel (medium) pyramid with as many
-// output column blocks as the input has, no max-pooled input, level at least 32 pixels wide and a multiple of 16
-// (JH_NODE_ROWS=0: never).
-bool bifpn_rows_wg_shape_ok(const NodeArgs& a);                 // csrc/bifpn_rows_wg.hip
-int launch_bifpn_rows_wg(const NodeArgs& a, hipStream_t s);
-bool bifpn_rows_ps_ok(const NodeArgs& a, int seg_rows, int strips, int segs);      // csrc/bifpn_rows_ps.hip
-int launch_bifpn_rows_ps(const NodeArgs& a, int seg_rows, int strips, int segs, hipStream_t s);
-
-// 88 channels, time-batch class >= 8, a level whose width is no multiple of 16 (or below 16): the one-wave / pair forms
-// need whole 16-pixel strips, the tile kernel's path for more than 64 channels is slow whatever the level -- the
-// workgroup form masks the last strip's pixels past the row end.  The reference's DEFAULT geometry (320-pixel images:
-// levels 80 / 40 / 20 / 10 / 5) has four of its five levels here.  A function of the node only.
-bool bifpn_rows_ragged88(const NodeArgs& a) {
-  return a.Cp == 88 && a.rows == 1 && (a.W % 16 != 0 || a.W < 16);
-}
-
-bool bifpn_rows_eligible(const NodeArgs& a) {
-  if (JH_ENV_KNOB("JH_NODE_ROWS") == 0 || a.rows == 0) return false;
-  // (160 channels, the large model: the workgroup form, csrc/bifpn_rows_wg.hip.
-  //  a.rows == 2 -- the wide pyramids at time batches below 8 -- is the same form with 8-row segments, also at 88
-  //  channels, where one wave per strip is the faster form at bench scale but far too slow per row for a few images)
-  const bool wg = (a.Cp == 160 || (a.Cp == 88 && (a.rows == 2 || bifpn_rows_ragged88(a)))) && bifpn_rows_wg_shape_ok(a);
-  if (a.rows == 2 && !wg) return false;
-  if (a.Cp != 56 && a.Cp != 88 && !wg) return false;
-  // (88 / 160 channels: also the 16-pixel-wide level -- one strip per image -- because the tile kernel's path for more
-  //  than 64 channels is slow there, 0.10 ms per launch against 0.05; at 56 channels the tile kernel wins below 32 pixels)
-  if (a.cout_p16 != (a.Cp + 15) / 16 * 16 || a.mode[0] != FUSE_SAME) return false;
-  if (wg) {
-    // the workgroup form masks the pixels past the row end of its last strip: every level down to 2 x 2 (the tile
-    // kernel's path for more than 64 channels costs 35-130 us per launch whatever the level)
-    if (a.W < 2 || a.H < 2) return false;
-  } else if (a.W % 16 != 0 || a.W < (a.Cp >= 88 ? 16 : 32) || a.H < 16) {
-    return false;
-  }
-  if (a.rows < 0) {
-    // (one wave per workgroup walking >= 10 rows: below ~2048 strips the chip is not filled and the tile form wins)
-    if (((a.W + 15) / 16) * ((a.H + 7) / 8) * a.N < 2048) return false;
-  }
-  const bool up2_ok = a.W % 2 == 0 && a.H % 2 == 0, up4_ok = a.W % 4 == 0 && a.H % 4 == 0;
-  if (a.n_in == 2) return (a.mode[1] == FUSE_UP2 && up2_ok) || (wg && a.mode[1] == FUSE_SAME);
-  return a.n_in == 3 && ((a.mode[1] == FUSE_UP2 && a.mode[2] == FUSE_UP4 && up4_ok) ||
-                         (a.mode[1] == FUSE_SAME && a.mode[2] == FUSE_SAME));
+// Launch geometry of the kernel for the chooser (csrc/node_layer.hip).
+NodeKernelGeo bifpn_rows_geo(int Cp) {
+  return Cp == 88 ? NodeKernelGeo{64, RowGeo<88>::lds_bytes(), 1} : NodeKernelGeo{64, RowGeo<56>::lds_bytes(), 1};
 }
 
 template <int RC>
-static int launch_rows_rc(const NodeArgs& a, hipStream_t s) {
-  const int strips = a.W / 16;
-  // Rows per workgroup: a function of the node (image size, number of inputs) ONLY -- the float partial sums of the
-  // statistics are taken per strip segment, so the segmentation must not depend on how many images a launch
-  // carries (bit-equal results for any number of cameras per rank).  Measured at 384 images (P3 two-input node:
-  // 8 rows 240 us, 16: 205, 32: 191; P4: 8: 74, 16: 66, 32: 71; three-input head: 16: 221, 32: 223; three
-  // same-level inputs at P4: 8: 116, 16: 99): half the image height, 16 / 8 rows for the head.
-  int seg_rows = a.n_in == 2 || a.mode[1] == FUSE_SAME ? std::max(8, a.H / 2) : (a.H >= 64 ? 16 : 8);
-  // (88 channels, producer / consumer pairs: four items per 512-thread workgroup, so fewer and longer segments fill the
-  //  chip better -- measured at 384 images: 32-row segments at the 32-pixel levels 0.155 -> 0.140 / 0.188 -> 0.167 ms,
-  //  the three-input head at 64 pixels 0.445 -> 0.397 with 32 rows instead of 16; the 16-pixel levels keep 8 rows: 0.051
-  //  against 0.078 with one segment per image)
-  if (RC == 88 && a.H >= 32) {
-    seg_rows = 32;
-    // (the pairs of a workgroup must walk the same number of rows: a level that is no multiple of 32 -- 80 x 80 in the
-    //  reference's DEFAULT 320-pixel geometry -- takes its largest even divisor up to 40 that leaves two segments; with
-    //  32 it fell back to the one-wave form at 1.4x the time per pixel)
-    if (a.H % 32 != 0)
-      for (int d = std::min(40, a.H / 2) & ~1; d >= 8; d -= 2)
-        if (a.H % d == 0) { seg_rows = d; break; }
-  }
-  seg_rows = (seg_rows + 1) & ~1;                // (even: the kernel's row loop is unrolled by two on row parity)
-  if (seg_rows > a.H) seg_rows = a.H;
-  const int segs = (a.H + seg_rows - 1) / seg_rows;
-  // 88 channels at bench scale: producer / consumer wave pairs (csrc/bifpn_rows_ps.hip) -- the same arithmetic per
-  // output value and the same segmentation, so the results are bit-equal to the kernel below
-  if (RC == 88 && bifpn_rows_ps_ok(a, seg_rows, strips, segs)) return launch_bifpn_rows_ps(a, seg_rows, strips, segs, s);
-  const size_t lds = RowGeo<RC>::lds_bytes();
-  const dim3 grid(strips * segs, a.N);
+static int launch_rows_rc(const NodeArgs& a, const NodeChoice& c, hipStream_t s) {
 #define JH_ROWS(NIN, M1, M2, ACT, POOL) \
-  hipLaunchKernelGGL((bifpn_rows_kernel<RC, NIN, M1, M2, ACT, POOL>), grid, dim3(64), lds, s, a, seg_rows, strips)
-  JH_REQUIRE(!a.y_pool || (a.n_in == 2 && a.act == ACT_SILU && a.cout_p == RC && a.H % 2 == 0),
-             "row-streaming node: pooled output");
-  if (a.n_in == 2) {
-    if (a.act == ACT_SILU && a.y_pool) JH_ROWS(2, FUSE_UP2, 0, ACT_SILU, true);
-    else if (a.act == ACT_SILU) JH_ROWS(2, FUSE_UP2, 0, ACT_SILU, false);
-    else if (a.act == ACT_NONE) JH_ROWS(2, FUSE_UP2, 0, ACT_NONE, false);
-    else JH_REQUIRE(false, "row-streaming node: activation");
-  } else if (a.mode[1] == FUSE_SAME) {
-    if (a.act == ACT_SILU) JH_ROWS(3, FUSE_SAME, FUSE_SAME, ACT_SILU, false);
-    else JH_REQUIRE(false, "row-streaming node: activation");
-  } else {
-    if (a.act == ACT_SILU) JH_ROWS(3, FUSE_UP2, FUSE_UP4, ACT_SILU, false);
-    else if (a.act == ACT_NONE) JH_ROWS(3, FUSE_UP2, FUSE_UP4, ACT_NONE, false);
-    else JH_REQUIRE(false, "row-streaming node: activation");
+  launch_node_kernel<bifpn_rows_kernel<RC, NIN, M1, M2, ACT, POOL>>(c, s, a, c.seg_rows, c.strips)
+  const bool silu = a.act == ACT_SILU;
+  switch (c.variant) {
+    case NodeVariant::Up2:
+      if (c.pool) return JH_ROWS(2, FUSE_UP2, 0, ACT_SILU, true);
+      return silu ? JH_ROWS(2, FUSE_UP2, 0, ACT_SILU, false) : JH_ROWS(2, FUSE_UP2, 0, ACT_NONE, false);
+    case NodeVariant::Same3: return JH_ROWS(3, FUSE_SAME, FUSE_SAME, ACT_SILU, false);
+    case NodeVariant::Up2Up4:
+      return silu ? JH_ROWS(3, FUSE_UP2, FUSE_UP4, ACT_SILU, false) : JH_ROWS(3, FUSE_UP2, FUSE_UP4, ACT_NONE, false);
+    default: JH_REQUIRE(false, "row-streaming node: variant");
   }
 #undef JH_ROWS
-  JH_CHECK_HIP(hipGetLastError());
-  return 0;
 }
 
-int launch_bifpn_rows(const NodeArgs& a, hipStream_t s) {
-  if (a.Cp == 160 || a.rows == 2 || bifpn_rows_ragged88(a)) return launch_bifpn_rows_wg(a, s);
-  if (a.Cp == 88) return launch_rows_rc<88>(a, s);
-  return launch_rows_rc<56>(a, s);
+int launch_bifpn_rows(const NodeArgs& a, const NodeChoice& c, hipStream_t s) {
+  return a.Cp == 88 ? launch_rows_rc<88>(a, c, s) : launch_rows_rc<56>(a, c, s);
 }
 
 }  // namespace jh

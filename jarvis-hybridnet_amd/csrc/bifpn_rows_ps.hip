@@ -29,6 +29,7 @@
 
 #include "conv_mfma.h"
 #include "bifpn_node.h"
+#include "node_layer.h"
 
 namespace jh {
 
@@ -380,51 +381,29 @@ __global__ __launch_bounds__(kPsPairs * 128) void bifpn_rows_ps_kernel(const Nod
   }
 }
 
-// Is this launch one for the producer / consumer form?  (Decided by the caller's segmentation: every pair of a
-// workgroup must walk the same number of rows, and the items must fill whole workgroups.)
-bool bifpn_rows_ps_ok(const NodeArgs& a, int seg_rows, int strips, int segs) {
-  if (a.Cp != 88 || a.cout_p != 88) return false;
-  if (a.H % seg_rows != 0 || seg_rows % 2 != 0) return false;
-  return ((long)strips * segs * a.N) % kPsPairs == 0;
-}
+// Launch geometry of the kernel for the chooser (csrc/node_layer.hip).
+NodeKernelGeo bifpn_rows_ps_geo(int) { return NodeKernelGeo{kPsPairs * 128, PsGeo<88>::lds_bytes(), kPsPairs}; }
 
-int launch_bifpn_rows_ps(const NodeArgs& a, int seg_rows, int strips, int segs, hipStream_t s) {
+int launch_bifpn_rows_ps(const NodeArgs& a, const NodeChoice& c, hipStream_t s) {
   constexpr int RC = 88;
-  const size_t lds = PsGeo<RC>::lds_bytes();
-  const dim3 grid((unsigned)((long)strips * segs * a.N / kPsPairs)), block(kPsPairs * 128);
   // REPACK for the two-input nodes only (384 images: P3 0.432 -> 0.397 ms, def320's 80-pixel level 0.350 -> 0.322).
   // Three inputs stay on the one pass: fully repacked the producer holds 21 loads of a row in flight -- 256 registers +
   // 72..128 B of scratch; with only the fusion repacked the eight P4 nodes of medium took 2.418 against 2.378 ms (both
   // forms were removed after that measurement).
-#define JH_PS(NIN, M1, M2, ACT, POOL)                                                                            \
-  do {                                                                                                           \
-    auto kern = bifpn_rows_ps_kernel<RC, NIN, M1, M2, ACT, POOL, (NIN == 2 ? 1 : 0)>;                            \
-    static bool big = false;                                                                                     \
-    if (!big) {                                                                                                  \
-      JH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                      \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                 \
-      big = true;                                                                                                \
-    }                                                                                                            \
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a, seg_rows, strips, segs);                                    \
-  } while (0)
-  JH_REQUIRE(!a.y_pool || (a.n_in == 2 && a.act == ACT_SILU && a.cout_p == RC && a.H % 2 == 0),
-             "producer / consumer node: pooled output");
-  if (a.n_in == 2) {
-    if (a.act == ACT_SILU && a.y_pool) JH_PS(2, FUSE_UP2, 0, ACT_SILU, true);
-    else if (a.act == ACT_SILU) JH_PS(2, FUSE_UP2, 0, ACT_SILU, false);
-    else if (a.act == ACT_NONE) JH_PS(2, FUSE_UP2, 0, ACT_NONE, false);
-    else JH_REQUIRE(false, "producer / consumer node: activation");
-  } else if (a.mode[1] == FUSE_SAME) {
-    if (a.act == ACT_SILU) JH_PS(3, FUSE_SAME, FUSE_SAME, ACT_SILU, false);
-    else JH_REQUIRE(false, "producer / consumer node: activation");
-  } else {
-    if (a.act == ACT_SILU) JH_PS(3, FUSE_UP2, FUSE_UP4, ACT_SILU, false);
-    else if (a.act == ACT_NONE) JH_PS(3, FUSE_UP2, FUSE_UP4, ACT_NONE, false);
-    else JH_REQUIRE(false, "producer / consumer node: activation");
+#define JH_PS(NIN, M1, M2, ACT, POOL)                                                                 \
+  launch_node_kernel<bifpn_rows_ps_kernel<RC, NIN, M1, M2, ACT, POOL, (NIN == 2 ? 1 : 0)>>(c, s, a, c.seg_rows, \
+                                                                                           c.strips, c.segs)
+  const bool silu = a.act == ACT_SILU;
+  switch (c.variant) {
+    case NodeVariant::Up2:
+      if (c.pool) return JH_PS(2, FUSE_UP2, 0, ACT_SILU, true);
+      return silu ? JH_PS(2, FUSE_UP2, 0, ACT_SILU, false) : JH_PS(2, FUSE_UP2, 0, ACT_NONE, false);
+    case NodeVariant::Same3: return JH_PS(3, FUSE_SAME, FUSE_SAME, ACT_SILU, false);
+    case NodeVariant::Up2Up4:
+      return silu ? JH_PS(3, FUSE_UP2, FUSE_UP4, ACT_SILU, false) : JH_PS(3, FUSE_UP2, FUSE_UP4, ACT_NONE, false);
+    default: JH_REQUIRE(false, "producer / consumer node: variant");
   }
 #undef JH_PS
-  JH_CHECK_HIP(hipGetLastError());
-  return 0;
 }
 
 }  // namespace jh

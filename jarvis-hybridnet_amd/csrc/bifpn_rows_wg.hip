@@ -22,16 +22,17 @@
 // Also (round 4, single-frame latency of the medium / large models):
 //   * 88 channels = 5.5 channel groups: six waves, the last one's quads 2, 3 and output channels 88..95 masked.  At
 //     bench scale one wave per strip (bifpn_rows.hip) is the faster form there (0.49 against 0.67 ms per P3 node);
-//     this form serves the 88-channel pyramid at time batches below 8 only (NodeArgs::rows == 2),
+//     this form serves the 88-channel pyramid at time batches below 8 and its ragged levels only (choose_node, csrc/node_layer.hip),
 //   * the last strip of a row masks the pixels past the row end (no store, no statistics): every level down to
 //     2 x 2 and widths that are not multiples of 16 qualify,
-//   * rows == 2 picks short segments (a node is a latency chain of its rows when there are only a few images),
+//   * time batches below 8 take short segments (a node is a latency chain of its rows when there are only a few images),
 //   * a variant with two same-level inputs (P7's bottom-up node fed by P6's pooled output).
 #include <algorithm>
 #include <type_traits>
 
 #include "conv_mfma.h"
 #include "bifpn_node.h"
+#include "node_layer.h"
 
 namespace jh {
 
@@ -425,73 +426,36 @@ void bifpn_rows_wg_kernel(const NodeArgs a, int seg_rows, int strips) {
   else body(std::integral_constant<int, 0>{});
 }
 
-// Shapes of the workgroup form (the channel count is checked by the caller, bifpn_rows_eligible): as many output
-// channels as input channels, no padding in either.
-bool bifpn_rows_wg_shape_ok(const NodeArgs& a) {
-  return (a.Cp == 160 || a.Cp == 88) && a.cout_p == a.Cp && a.cout_p16 == (a.Cp + 15) / 16 * 16;
+// Launch geometry of the kernel for the chooser (csrc/node_layer.hip).
+NodeKernelGeo bifpn_rows_wg_geo(int Cp) {
+  using G88 = RowWgGeo<88>;
+  using G160 = RowWgGeo<160>;
+  return Cp == 88 ? NodeKernelGeo{(G88::NW + G88::NH) * 64, G88::lds_bytes(), 1}
+                  : NodeKernelGeo{(G160::NW + G160::NH) * 64, G160::lds_bytes(), 1};
 }
 
 template <int RC>
-static int launch_rows_wg_rc(const NodeArgs& a, hipStream_t s) {
-  const int strips = (a.W + 15) / 16;
-  // Rows per workgroup: a function of the node and of the predictor's time-batch CLASS only (the float partial sums
-  // of the statistics are taken per strip segment: bit-equal results for any number of images per launch), as in
-  // bifpn_rows.hip.  a.rows == 2 (time batches below 8, the single-frame caller among them: few images, a node is a
-  // latency chain of its rows): short segments -- measured per node with one 12-camera frame set, 88 / 160 channels,
-  // us: 64-row levels 16 rows 33 / 62 (8: 41 / 72, 4: 50 / 79, 32: 53 / 103); 32-row levels 4 rows 18 / 29 (8: 22 / 38,
-  // 2: 26 / 42); 16 rows and below 2 rows 13 / 21 (4: 15 / 26, 8: 21 / 37).
-  int seg_rows = a.rows == 2 ? (a.H >= 64 ? 16 : (a.H >= 32 ? 4 : 2))
-                 : (a.n_in == 2 || a.mode[1] == FUSE_SAME ? std::max(8, a.H / 2) : (a.H >= 64 ? 16 : 8));
-  // (time-batch class >= 8, levels of 32 pixels and more: ONE segment per strip -- the workgroup's prologue (its waves'
-  //  weight slices, the statistics' fp64 arithmetic, two warm-up rows) is paid once per 64 rows instead of per 16 or 32:
-  //  measured at 160 channels, 384 images: P3 node 1.218 -> 1.133 ms, head 1.270 -> 1.024, P4 0.331 -> 0.292 / 0.431 ->
-  //  0.389; the 16-pixel levels keep 8 rows, 0.106 against 0.112 with 16)
-  //  (88 channels on a ragged level -- bifpn_rows_ragged88 -- keep half-image segments: 192 images x 3 strips of a 40-pixel
-  //  level are 576 workgroups on 512 slots with one segment per strip)
-  if (a.rows != 2 && a.H >= 32 && !bifpn_rows_ragged88(a)) seg_rows = a.H;
-  seg_rows = (seg_rows + 1) & ~1;
-  if (seg_rows > a.H) seg_rows = a.H;
-  const int segs = (a.H + seg_rows - 1) / seg_rows;
-  const size_t lds = RowWgGeo<RC>::lds_bytes();
-  const dim3 grid(strips * segs, a.N), block((RowWgGeo<RC>::NW + RowWgGeo<RC>::NH) * 64);
-#define JH_ROWS(NIN, M1, M2, ACT, POOL)                                                                            \
-  do {                                                                                                             \
-    auto kern = bifpn_rows_wg_kernel<RC, NIN, M1, M2, ACT, POOL, true>;                                            \
-    static bool big = false;                                                                                       \
-    if (!big && lds > 64 * 1024) {                                                                                 \
-      JH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                        \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                   \
-      big = true;                                                                                                  \
-    }                                                                                                              \
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a, seg_rows, strips);                                            \
-  } while (0)
-  JH_REQUIRE(!a.y_pool || (a.act == ACT_SILU && a.H % 2 == 0 && (a.n_in == 2 || a.mode[1] == FUSE_SAME)),
-             "workgroup row-streaming node: pooled output");
-  if (a.n_in == 2 && a.mode[1] == FUSE_SAME) {       // (bottom-up node of the coarsest level: P7 from P7_in and pooled P6)
-    JH_REQUIRE(a.act == ACT_SILU && !a.y_pool, "workgroup row-streaming node: two same-level inputs");
-    JH_ROWS(2, FUSE_SAME, 0, ACT_SILU, false);
-  } else if (a.n_in == 2) {
-    if (a.act == ACT_SILU && a.y_pool) JH_ROWS(2, FUSE_UP2, 0, ACT_SILU, true);
-    else if (a.act == ACT_SILU) JH_ROWS(2, FUSE_UP2, 0, ACT_SILU, false);
-    else if (a.act == ACT_NONE) JH_ROWS(2, FUSE_UP2, 0, ACT_NONE, false);
-    else JH_REQUIRE(false, "row-streaming node: activation");
-  } else if (a.mode[1] == FUSE_SAME) {
-    if (a.act == ACT_SILU && a.y_pool) JH_ROWS(3, FUSE_SAME, FUSE_SAME, ACT_SILU, true);
-    else if (a.act == ACT_SILU) JH_ROWS(3, FUSE_SAME, FUSE_SAME, ACT_SILU, false);
-    else JH_REQUIRE(false, "row-streaming node: activation");
-  } else {
-    if (a.act == ACT_SILU) JH_ROWS(3, FUSE_UP2, FUSE_UP4, ACT_SILU, false);
-    else if (a.act == ACT_NONE) JH_ROWS(3, FUSE_UP2, FUSE_UP4, ACT_NONE, false);
-    else JH_REQUIRE(false, "row-streaming node: activation");
+static int launch_rows_wg_rc(const NodeArgs& a, const NodeChoice& c, hipStream_t s) {
+#define JH_ROWS(NIN, M1, M2, ACT, POOL) \
+  launch_node_kernel<bifpn_rows_wg_kernel<RC, NIN, M1, M2, ACT, POOL, true>>(c, s, a, c.seg_rows, c.strips)
+  const bool silu = a.act == ACT_SILU;
+  switch (c.variant) {
+    case NodeVariant::Same2:       // (bottom-up node of the coarsest level: P7 from P7_in and pooled P6)
+      return JH_ROWS(2, FUSE_SAME, 0, ACT_SILU, false);
+    case NodeVariant::Up2:
+      if (c.pool) return JH_ROWS(2, FUSE_UP2, 0, ACT_SILU, true);
+      return silu ? JH_ROWS(2, FUSE_UP2, 0, ACT_SILU, false) : JH_ROWS(2, FUSE_UP2, 0, ACT_NONE, false);
+    case NodeVariant::Same3:
+      return c.pool ? JH_ROWS(3, FUSE_SAME, FUSE_SAME, ACT_SILU, true) : JH_ROWS(3, FUSE_SAME, FUSE_SAME, ACT_SILU, false);
+    case NodeVariant::Up2Up4:
+      return silu ? JH_ROWS(3, FUSE_UP2, FUSE_UP4, ACT_SILU, false) : JH_ROWS(3, FUSE_UP2, FUSE_UP4, ACT_NONE, false);
+    default: JH_REQUIRE(false, "workgroup row-streaming node: variant");
   }
 #undef JH_ROWS
-  JH_CHECK_HIP(hipGetLastError());
-  return 0;
 }
 
-int launch_bifpn_rows_wg(const NodeArgs& a, hipStream_t s) {
-  if (a.Cp == 88) return launch_rows_wg_rc<88>(a, s);
-  return launch_rows_wg_rc<160>(a, s);
+int launch_bifpn_rows_wg(const NodeArgs& a, const NodeChoice& c, hipStream_t s) {
+  return a.Cp == 88 ? launch_rows_wg_rc<88>(a, c, s) : launch_rows_wg_rc<160>(a, c, s);
 }
 
 }  // namespace jh

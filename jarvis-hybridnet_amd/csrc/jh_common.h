@@ -379,8 +379,6 @@ __device__ __forceinline__ double sum_xor32(double s) {
 __device__ __forceinline__ float silu_fast(float v) { return v * __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
 #endif
 
-struct NodeArgs;
-int launch_bifpn_node(const NodeArgs& a, hipStream_t s);
 int pack_wino_weights(int cin, int cout, const float* w, const float* b, ConvWeights* out);
 // variant: 4 = persistent wave-specialised form (conv3d_wino_pw.hip; it falls back to variant 0 for launches with
 // fewer than two tiles per CU or fewer than three channel passes), 0 = one role per workgroup

@@ -12,6 +12,7 @@
 #include <vector>
 #include "jh_common.h"
 #include "conv_layer.h"
+#include "node_layer.h"
 #include "preprocess.h"
 
 namespace jh {
@@ -145,11 +146,11 @@ class EffTrackPlan : public Plan {
   // algorithmic bytes of the (fused) stem launch for the profiler: taps read from the frames + stem output
   void set_stem_traffic(double bytes);
   int stem_channels() const { return stem_ch_; }
-  // Which form the high-resolution BiFPN nodes take (NodeArgs::rows), set before build().  A predictor sets it
-  // from its time batch ALONE (not from the number of cameras it owns), so that a camera-sharded rank and the
-  // single-GPU run of the same time batch launch the same kernels and stay bit-equal; -1: by the
-  // number of workgroups of the launch (stand-alone operator).
-  int node_rows = -1;
+  // The time-batch class that choose_node() (csrc/node_layer.h) reads for every BiFPN node of this plan, set before
+  // build().  A predictor sets it from its time batch ALONE (not from the number of cameras it owns), so that a
+  // camera-sharded rank and the single-GPU run of the same time batch launch the same kernels and stay bit-equal
+  // (SURVEY 8e); ByLaunchSize: by the number of workgroups of the launch, as the stand-alone operator does.
+  NodeBatchClass node_class = NodeBatchClass::ByLaunchSize;
   Act input;     // [N][H][W][8]   normalised image, channel-last
   Act heat;      // [N][H/2][W/2][Jp]  res2 (ConvTranspose output)
   Act res1;      // [N][H/4][W/4][Jp]  final_conv1 output (only with want_res1)
@@ -164,7 +165,7 @@ class EffTrackPlan : public Plan {
   int pool(const Ref& x, Ref* out);
   int node(const ParamMap& pm, const std::string& conv_prefix, int n_in, const Ref* ins,
            const int* modes, const float* w, int act, const Act& like, int cout, Ref* out,
-           Ref* pooled = nullptr);   // pooled: also MaxPool2d(2,2) of the raw output, if the node's form can (else a.p = 0)
+           Ref* pooled = nullptr);   // pooled: also MaxPool2d(2,2) of the raw output, if NodeChoice::pool (else a.p = 0)
 };
 
 class V2VPlan : public Plan {

@@ -366,18 +366,14 @@ int EffTrackPlan::node(const ParamMap& pm, const std::string& cp, int n_in, cons
   a.dw = dwd; a.pw = cw.w; a.bias = cw.bias; a.y = out->a.p;
   a.N = like.N; a.H = like.H; a.W = like.W; a.Cp = like.Cp;
   a.cout_p = out->a.Cp; a.cout_p16 = cw.cout_p16;
-  // (time batches below 8 -- node_rows 0: the 56-channel pyramid keeps the tile form, 13 us per node for one frame
-  //  set; the wide pyramids take the workgroup row form with short segments, csrc/bifpn_rows_wg.hip: their tile path
-  //  costs 35-130 us per node whatever the level)
-  a.rows = node_rows == 0 && like.Cp >= 88 ? 2 : node_rows;
+  // form, segmentation and launch shape: decided here, once (csrc/node_layer.hip)
+  NodeChoice choice;
+  if (choose_node(node_use(a, node_class, pooled != nullptr), &choice)) return 1;
   if (pooled) {
-    // the row-streaming two-input form can write the 2x2-max-pooled raw output on the side (bifpn_rows.hip): the
-    // bottom-up node of the next level then reads a same-resolution tensor with THIS node's statistics
+    // a row form can write the 2x2-max-pooled raw output on the side: the bottom-up node of the next level then reads
+    // a same-resolution tensor with THIS node's statistics
     pooled->a = Act{};
-    // (160 channels, csrc/bifpn_rows_wg.hip: also the node with three same-level inputs, so the bottom-up pass stays in
-    //  the row-streaming form one level further down)
-    const bool same3 = n_in == 3 && modes[1] == FUSE_SAME && modes[2] == FUSE_SAME && (like.Cp == 160 || a.rows == 2 || bifpn_rows_ragged88(a));
-    if ((n_in == 2 || same3) && act == ACT_SILU && out->a.Cp == like.Cp && like.H % 2 == 0 && bifpn_rows_eligible(a)) {
+    if (choice.pool) {
       if (new_act(like.N, 1, like.H / 2, like.W / 2, cout, &pooled->a)) return 1;
       pooled->st = (long)st; pooled->inv = out->inv; pooled->act = out->act;
       a.y_pool = pooled->a.p;
@@ -388,13 +384,13 @@ int EffTrackPlan::node(const ParamMap& pm, const std::string& cp, int n_in, cons
   char nm[64];
   snprintf(nm, sizeof nm, "bifpn_node_%dx%d@%d", cin, cout, like.W);
   const long s0 = sts[0], s1 = sts[1], s2 = sts[2];
-  push(nm, 2.0 * px * cin * (9.0 + cout), bytes, [this, a, s0, s1, s2, st](hipStream_t s) {
+  push(nm, 2.0 * px * cin * (9.0 + cout), bytes, [this, a, choice, s0, s1, s2, st](hipStream_t s) {
     NodeArgs b = a;
     b.st[0] = s0 >= 0 ? sc((size_t)s0) : nullptr;
     b.st[1] = s1 >= 0 ? sc((size_t)s1) : nullptr;
     b.st[2] = s2 >= 0 ? sc((size_t)s2) : nullptr;
     b.stats = sc(st);
-    return launch_bifpn_node(b, s);
+    return launch_bifpn_node(b, choice, s);
   });
   return 0;
 }

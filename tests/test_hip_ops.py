@@ -232,21 +232,24 @@ NODE_CASES = [  # (C, Cout, H, W, modes, act, n): the node shapes of the small /
     (56, 56, 8, 8, (0, 3), 2, 3),           # P7 of the bottom-up pass
     (56, 64, 64, 64, (0, 1, 2), 0, 3),      # head: P3 + x2 P4 + x4 P5 -> first_conv (no activation)
     (88, 88, 32, 32, (0, 0, 3), 2, 3),      # medium model: wider pyramid (chunked halo path)
-    # >= 2048 strips per launch: the stand-alone operator takes the row-streaming form (csrc/bifpn_rows.hip)
+    # The stand-alone operator asks choose_node (csrc/node_layer.hip) in class NodeBatchClass::ByLaunchSize: a row form
+    # only from 2048 strips of eight rows per launch on, hence the image counts below.  What each case runs is pinned
+    # in tests/test_node_form_cpu.py (OP_ROWS).  One wave per strip, NodeForm::RowsWave (csrc/bifpn_rows.hip):
     (56, 56, 64, 64, (0, 1), 2, 64),        # P3 top-down, 16-row segments
     (56, 64, 64, 64, (0, 1, 2), 0, 64),     # head (three inputs, no activation, 64 output channels)
     (56, 56, 32, 32, (0, 1), 2, 256),       # P4 top-down, 8-row segments
     (56, 56, 48, 32, (0, 1), 2, 192),       # height that is not a power of two
     (56, 56, 32, 32, (0, 0, 0), 2, 256),    # P4 bottom-up when P3's node has written its pooled output: three same-level inputs
-    # the medium model's 88-channel pyramid in the row-streaming form (22 channel quads x 2 pixel slots per wave,
-    # 6 output column blocks, one wave per SIMD)
+    # the medium model's 88-channel pyramid: whole workgroups of four (strip, segment) items take the producer /
+    # consumer pairs, NodeForm::RowsPairs (csrc/bifpn_rows_ps.hip); otherwise RowsWave (22 channel quads x 2 pixel
+    # slots per wave, 6 output column blocks, one wave per SIMD)
     (88, 88, 64, 64, (0, 1), 2, 64),        # P3 top-down
     (88, 88, 64, 64, (0, 1, 2), 0, 64),     # head: first_conv 88 -> 88, no activation
     (88, 88, 32, 32, (0, 1), 2, 256),       # P4 top-down
     (88, 88, 32, 32, (0, 0, 0), 2, 256),    # P4 bottom-up with three same-level inputs
     (88, 88, 48, 32, (0, 1), 2, 192),       # ragged height
     (88, 88, 16, 16, (0, 1), 2, 2048),      # P5 top-down of the medium model: one 16-pixel strip per image
-    # the large model's 160-channel pyramid: workgroup row-streaming form (csrc/bifpn_rows_wg.hip: ten waves per
+    # the large model's 160-channel pyramid: NodeForm::RowsWg (csrc/bifpn_rows_wg.hip: ten waves per
     # strip, one output column block and one 16-channel slice of the ring each)
     (160, 160, 32, 32, (0, 0, 3), 2, 3),    # tile form (small launch)
     (160, 160, 64, 64, (0, 1), 2, 64),      # P3 top-down
@@ -263,9 +266,9 @@ NODE_CASES = [  # (C, Cout, H, W, modes, act, n): the node shapes of the small /
     (160, 160, 24, 24, (0, 1), 2, 512),     # 192-pixel crops: P4 is 24 wide (one full and one half strip)
     (160, 160, 24, 40, (0, 1, 2), 0, 384),  # three strips, the last one half empty; x1 / x2 / x4 inputs
     (56, 56, 4, 4, (0, 0), 2, 3),           # the tile kernel's two-same-input variant (fallback of the above)
-    # 88 channels on level sizes of the reference's DEFAULT 320-pixel geometry (round 6; the stand-alone operator has no
-    # time-batch class, so the ragged levels take the tile kernel here -- the workgroup row form on them is exercised by
-    # the default_medium_320 fixture in its T = 8 class)
+    # 88 channels on level sizes of the reference's DEFAULT 320-pixel geometry (round 6; RowsWg on a ragged 88-channel
+    # level is a choice of the classes AtLeast8 / Below8 only, so in ByLaunchSize those levels take NodeForm::Tile here
+    # -- RowsWg on them is exercised by the default_medium_320 fixture in its T = 8 class)
     (88, 88, 40, 40, (0, 1), 2, 20),        # P4 top-down, 2.5 tiles wide
     (88, 88, 20, 20, (0, 0, 3), 2, 20),     # P5 bottom-up
     (88, 88, 80, 80, (0, 1), 2, 43),        # P3 top-down: 40-row segments (80 % 32 != 0); 430 items: one-wave form
