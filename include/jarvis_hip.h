@@ -619,6 +619,88 @@ int jh_predictor_detect_subjects(jh_predictor* pr, const void* frames_dev, const
                                  int32_t* views_dev, int32_t* members_dev, float* error_dev,
                                  float* peaks_dev /* optional */, void* stream);
 
+/* Per-joint robust triangulation (ABI v4, additive; new design: the reference's only 3D keypoints are V2V's).  A
+ * classical 3D point per joint, triangulated from the cameras' own 2D keypoints with the cameras that disagree left out:
+ * the one 3D estimate that does not pass through the voxel cube.  It still meets the rays of a limb that has left
+ * roi_cube_size (V2V's soft-argmax saturates at the cube face), it names the camera whose keypoint sits on a reflection
+ * or an occluder (the reprojection layer's camera mean is dragged by it), and it is a check on V2V that is independent
+ * of V2V (err of jh_predictor_views2d is measured against V2V's own point).
+ *
+ * jh_joints3d_params.  Library defaults -- documented values, not recommendations -- are min_views = 2, refine_radius =
+ * 1, min_conf = 0.1, max_error_px = 8.  Ranges, checked by every entry point below (non-zero with jh_last_error() set,
+ * nothing enqueued; jh_joints3d_params_check needs no GPU): min_views >= 2, refine_radius 0 .. 3, min_conf 0 .. 1,
+ * max_error_px >= 0 (+inf allowed); a NaN is out of range.
+ *
+ * Observation of joint j in camera c of frame set t: used[t][c], points2d = (x2d, y2d) and conf2d exactly as
+ * jh_predictor_views2d defines them, the sub-pixel offset (ox, oy) of the peak, and the weight w = conf2d.  Its pixel is
+ *   u = (float)x2d + 2 * ox,  v = (float)y2d + 2 * oy      (the product is exact, the sum rounded once in fp32).
+ * It is USABLE iff used[t][c] is set, w > 0 and w >= min_conf, and u and v are finite.
+ * Sub-pixel offset, refine_radius = r > 0: m the arg-max index of joint j's map, (mx, my) its column and row by the
+ * expression of jh_predictor_views2d for the predictor's square maps, (m % (B/2), m / (B/2)) (jh_op_joint_peaks_refine
+ * on an hh x wh map: mx = m % wh, my = m / wh).  Over the window |x - mx| <= r, |y - my| <= r clipped at the map's edge,
+ * walked y ascending, then x ascending, with h the heat value at (x, y) and wgt = fmaxf(h, 0) (a NaN pixel counts as 0):
+ *   S0 = sum wgt,  Sx = sum wgt * (x - mx),  Sy = sum wgt * (y - my),
+ * every product and every sum rounded once in fp32, in walk order, starting from 0;  ox = S0 > 0 ? Sx / S0 : 0,  oy = S0 >
+ * 0 ? Sy / S0 : 0  (one fp32 division each): the centroid of the window, in heat-map pixels, |ox|, |oy| <= r.  An index m
+ * outside the map (a map without any number has no arg-max) reads nothing and has offset 0.  r = 0: the heat map is not
+ * read again, ox = oy = 0, and (u, v) are the integers converted.
+ *
+ * Consensus per (t, j): the association of jh_op_associate_subjects with one slot per camera and one round.
+ *   candidates  every pair of usable cameras a < b: X = the weighted DLT of the existing triangulation over exactly those
+ *               two observations -- pixel (u, v) as given (no scaling), weight w (no division);
+ *   support     a usable camera c supports X iff the homogeneous depth of the projection of X in c is > 0 and d =
+ *               sqrt(dx*dx + dy*dy) <= max_error_px, dx and dy the differences between reprojectPoint(X) and (u, v), one
+ *               fp32 rounding per operation (a NaN d never supports); views = the number of supporting cameras, cost =
+ *               the fp32 sum of their d in camera order;
+ *   choice      most views, then smallest cost, then lowest (a, b);
+ *   empty       no pair, or views < min_views: the joint is empty;
+ *   result      members[t][j][c] uint8 = 1 for a supporting camera, else 0; views[t][j] int32; points[t][j] = the
+ *               triangulation over the members' observations, A^T A summed in camera order, BIT FOR BIT
+ *               jh_reconstruct_point on the members' pixels (u, v) and weights w; error[t][j] = the fp32 mean (sum in
+ *               camera order, one division by views) over the members of d against the projection of points[t][j].
+ * An empty joint, and every joint of a frame set that is not valid: points and error NaN, views 0, members 0.
+ * The result does not depend on timing.  Two consequences:
+ *   - with max_error_px = +inf, min_conf = 0 and min_views = 2 the members of a joint with a pair are all usable cameras
+ *     in front of which the chosen pair's point lies; the point is then jh_reconstruct_point over them;
+ *   - nothing of the heat map of a camera that is not used reaches an output (it may hold anything).
+ *
+ * jh_op_joint_peaks_refine: heat (n,hh,wh,jp) channel-last dev, idx (n,j) int32 flat indices y*wh + x (what
+ * jh_op_joint_argmax_all writes) -> offsets (n,j,2) = (ox, oy) as above for radius 0 .. 3 (0: all zero).  At most
+ * (2 radius + 1)^2 values are read per (n, j).  Synchronises (unit-test helper).
+ * jh_op_triangulate_joints: obs (t,cams,j,3) = (u, v, w) dev, a camera that is not used as (NaN, NaN, 0); one
+ * calibration (calib_per_frame == 0: (cams,..)) or one per frame set (!= 0: (t,cams,..)); params->refine_radius is
+ * checked and not used -> points (t,j,3), views (t,j) int32, members (t,j,cams) uint8, error (t,j).  cams <= 64; the
+ * work of a joint grows with cams^3.  Synchronises (unit-test helper).
+ * jh_predictor_triangulate_joints: for the frames t0 .. t0+T3-1, after the forward / stage-3 call, on the same stream,
+ * with the conventions of jh_predictor_views2d: heat_all_dev NULL = the heat maps of the last whole-path forward (all
+ * cameras local), otherwise (T3,C,B/2,B/2,Jp); mask_dev the (T,C) mask that forward was given, read in place, or NULL;
+ * the crop centres / validity set that stage 3 read; the calibration in force, shared or per frame set.  Outputs points
+ * (T3,J,3) world mm, views (T3,J), members (T3,J,C), error (T3,J) px, and obs_dev (T3,C,J,3) optional (NULL to skip): the
+ * observations (u, v, w), (NaN, NaN, 0) for a camera that is not used.  With refine_radius = 0 the observations are
+ * points2d converted and conf2d of jh_predictor_views2d, bit for bit.
+ * Plain launches, asynchronous, also on a graph-replaying predictor: the call runs behind the replay and the captured
+ * graphs are untouched: the scan, the observations -- written straight into obs_dev when it is given, into a buffer of
+ * the predictor's own otherwise -- and the consensus, three launches and no copy.  The scan's (max, index) workspace is
+ * shared with jh_predictor_views2d: a later views2d call runs its own scan again.  Workspace and buffer
+ * are allocated by the first call that needs them -- never by jh_predictor_create, so jh_predictor_device_bytes,
+ * the memory, the launches and the bits of a predictor that never asks are unchanged -- and that first call must not be
+ * made inside a stream capture. */
+typedef struct jh_joints3d_params {
+  int32_t min_views, refine_radius;
+  float min_conf, max_error_px;
+} jh_joints3d_params;
+int jh_joints3d_params_check(const jh_joints3d_params* params);    /* no GPU needed */
+int jh_op_joint_peaks_refine(const float* heat_dev, int n, int hh, int wh, int jp, const int32_t* idx_dev, int j,
+                             int radius, float* offsets_dev, void* stream);
+int jh_op_triangulate_joints(const float* obs_dev, int t, int cams, int j, const float* cam_dev, const float* intr_dev,
+                             const float* dist_dev, int calib_per_frame, const jh_joints3d_params* params,
+                             float* points_dev, int32_t* views_dev, uint8_t* members_dev, float* error_dev,
+                             void* stream);
+int jh_predictor_triangulate_joints(jh_predictor* pr, const float* heat_all_dev, int t0, const uint8_t* mask_dev,
+                                    const jh_joints3d_params* params, float* points_dev, int32_t* views_dev,
+                                    uint8_t* members_dev, float* error_dev, float* obs_dev /* optional */,
+                                    void* stream);
+
 /* HybridNetBackbone.forward: crops (T,C,3,B,B) normalised NCHW dev, center_hm
  * (T,C,2) int32, center3d (T,3) int32 -> heatmap_final (T,J,Gh,Gh,Gh) optional,
  * heatmaps_padded (T,C,J,hs,hs) optional, points (T,J,3), conf (T,J). */

@@ -13,3 +13,4 @@ from .yuv_surface import YuvSurface  # noqa: E402,F401 -- pure Python: importing
 from .sensor_surface import SensorSurface  # noqa: E402,F401 -- likewise
 from .spread import Spread3D  # noqa: E402,F401 -- likewise
 from .subjects import Subjects  # noqa: E402,F401 -- likewise
+from .triangulated import Triangulated3D  # noqa: E402,F401 -- likewise

@@ -70,6 +70,15 @@ class SubjectsParamsStruct(ctypes.Structure):
 
 assert ctypes.sizeof(SubjectsParamsStruct) == 24
 
+
+class Joints3dParamsStruct(ctypes.Structure):
+    """jh_joints3d_params of include/jarvis_hip.h (built by joints3d_params())."""
+    _fields_ = [("min_views", ctypes.c_int32), ("refine_radius", ctypes.c_int32), ("min_conf", c_float),
+                ("max_error_px", c_float)]
+
+
+assert ctypes.sizeof(Joints3dParamsStruct) == 16
+
 ABI_VERSION = 4                    # JH_ABI_VERSION of include/jarvis_hip.h
 # sizeof(jh_predictor_config): statically asserted on the C side (tests/abi_smoke.c) and here
 assert ctypes.sizeof(PredictorConfig) == 84
@@ -191,6 +200,14 @@ _SIGS = {
                                              ctypes.POINTER(YuvSurfaceStruct), ctypes.POINTER(SensorSurfaceStruct),
                                              c_void_p, ctypes.POINTER(SubjectsParamsStruct), c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_joints3d_params_check": (c_int, [ctypes.POINTER(Joints3dParamsStruct)]),
+    "jh_op_joint_peaks_refine": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                                         c_void_p]),
+    "jh_op_triangulate_joints": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                         ctypes.POINTER(Joints3dParamsStruct), c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
+    "jh_predictor_triangulate_joints": (c_int, [c_void_p, c_void_p, c_int, c_void_p,
+                                                ctypes.POINTER(Joints3dParamsStruct)] + [c_void_p] * 6),
     "jh_joint_argmax_all_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "jh_op_joint_argmax_all": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p]),
@@ -555,6 +572,45 @@ def subjects_params(max_subjects, max_peaks=None, nms_radius=4, min_views=2, min
     if lib().jh_subjects_params_check(ctypes.byref(p)) != 0:
         raise ValueError(lib().jh_last_error().decode())
     return p
+
+
+def joints3d_params(min_views=2, refine_radius=1, min_conf=0.1, max_error_px=8.0):
+    """The parameters of a triangulate_joints call checked -> Joints3dParamsStruct (jh_joints3d_params).  The defaults
+    are the library's documented defaults, not recommendations: min_views 2, refine_radius 1 heat-map pixel (0: the
+    integer peak), min_conf 0.1, max_error_px 8 full-frame pixels.  Ranges (the library's own check,
+    jh_joints3d_params_check: host arithmetic, no device): min_views >= 2, refine_radius 0 .. 3, min_conf 0 .. 1,
+    max_error_px >= 0 (+inf allowed).  ValueError for anything else, a non-integer count included."""
+    ints = dict(min_views=min_views, refine_radius=refine_radius)
+    for name, v in ints.items():
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError("%s must be an int, got %r" % (name, v))
+        if abs(v) >= 2 ** 31:
+            raise ValueError("%s is out of range: %r" % (name, v))
+    try:
+        floats = (float(min_conf), float(max_error_px))
+    except (TypeError, ValueError):
+        raise ValueError("min_conf and max_error_px must be numbers, got %r and %r" % (min_conf, max_error_px))
+    p = Joints3dParamsStruct(min_views, refine_radius, *floats)
+    if lib().jh_joints3d_params_check(ctypes.byref(p)) != 0:
+        raise ValueError(lib().jh_last_error().decode())
+    return p
+
+
+def triangulation_params(value):
+    """What return_triangulated= / params= of the forwards accept -> Joints3dParamsStruct, or None for a false value:
+    True = the defaults, a Joints3dParamsStruct (joints3d_params()) as it is, a dict = the keywords of
+    joints3d_params()."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return joints3d_params()
+    if isinstance(value, dict):
+        return joints3d_params(**value)
+    if isinstance(value, Joints3dParamsStruct):
+        if lib().jh_joints3d_params_check(ctypes.byref(value)) != 0:
+            raise ValueError(lib().jh_last_error().decode())
+        return value
+    raise ValueError("return_triangulated must be True or come from _native.joints3d_params, got %r" % (value,))
 
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x3_wide": 2}

@@ -8,6 +8,7 @@ from . import _native as N
 from . import arch
 from .spread import Spread3D  # noqa: F401 -- the name the forwards return
 from .subjects import Subjects
+from .triangulated import Triangulated3D
 
 
 # Per-camera 2D views of a 3D result (jh_predictor_views2d, include/jarvis_hip.h): points2D (T,C,J,2) int32 full-frame
@@ -279,6 +280,36 @@ class NativePredictor:
             mask.record_stream(torch.cuda.current_stream())     # (read in place by the enqueued kernel)
         return Views2D(*out)
 
+    def triangulate_joints(self, heat=None, t0=0, camera_mask=None, params=None):
+        """A second 3D estimate of every joint of the frames t0 .. t0+T3-1, triangulated from the cameras' own 2D
+        keypoints with the cameras that disagree left out (jh_predictor_triangulate_joints): call right after the
+        forward / stage_3d, on the same stream -> Triangulated3D of device tensors.  heat, camera_mask: as views2d().
+        params: what _native.joints3d_params made, a dict of its keywords, or None / True = the library's defaults
+        (min_views 2, refine_radius 1, min_conf 0.1, max_error_px 8).  Plain launches behind a graph replay; the first
+        call allocates its workspace (not inside a stream capture).  Nothing of the forwards' state is touched."""
+        p = N.triangulation_params(True if params is None else params)
+        if p is None:
+            raise ValueError("params must be True, a dict or come from _native.joints3d_params")
+        T3 = self.T3
+        if heat is not None and not (heat.is_cuda and heat.is_contiguous() and heat.dtype == torch.float32 and
+                                     tuple(heat.shape) == (T3, self.C, self.Hh, self.Hh, self.Jp)):
+            raise ValueError("heat must be a contiguous (%d, %d, %d, %d, %d) float32 device tensor"
+                             % (T3, self.C, self.Hh, self.Hh, self.Jp))
+        dev = heat.device if heat is not None else torch.device("cuda", torch.cuda.current_device())
+        mask = N.camera_mask(camera_mask, (self.T, self.C))
+        if mask is not None:
+            mask = mask.to(dev, non_blocking=True)
+        out = Triangulated3D(torch.empty((T3, self.J, 3), device=dev),
+                             torch.empty((T3, self.J), device=dev, dtype=torch.int32),
+                             torch.empty((T3, self.J, self.C), device=dev, dtype=torch.uint8),
+                             torch.empty((T3, self.J), device=dev),
+                             torch.empty((T3, self.C, self.J, 3), device=dev))
+        N.check(N.lib().jh_predictor_triangulate_joints(self.handle, N.ptr(heat), int(t0), N.ptr(mask), ctypes.byref(p),
+                                                        *(N.ptr(t) for t in out), N.stream()))
+        if mask is not None:
+            mask.record_stream(torch.cuda.current_stream())     # (read in place by the enqueued kernel)
+        return out
+
     def detect_subjects(self, frames, params, camera_mask=None, return_peaks=False):
         """Up to params.max_subjects subjects per frame set of checked frames (a _native.Frames with `data`, from
         _describe, or with `images`, from _native.frame_images) -> Subjects of device tensors, on the current stream
@@ -416,10 +447,12 @@ class MultiStreamPredictor:
         self._calib_of[i] = (self._calib, self._calib_refs)       # the tensors live as long as their key is compared
 
     def forward(self, frames, out=None, then=None, frame_format=None, camera_mask=None, return_2d=False,
-                frame_layout=None, centers=None, return_spread=False):
+                frame_layout=None, centers=None, return_spread=False, return_triangulated=False):
         """return_2d: the five tensors of NativePredictor.views2d for this batch are appended to the outputs
         (points, conf, valid, points2D, confidences2D, reprojections, errors, used).
         return_spread: the three tensors of the batch's Spread3D (cov (T,J,3,3), peak, mass) are appended behind them.
+        return_triangulated (True or what _native.joints3d_params made): the five tensors of the batch's Triangulated3D
+        (NativePredictor.triangulate_joints) are appended last.
         `then(outputs)`, when given, runs inside the batch's stream context right behind the forward and
         before its event is recorded (the drivers enqueue the device->host copy of the results there); its
         return value replaces the outputs.  frame_format, camera_mask, frame_layout: as NativePredictor.forward.
@@ -429,6 +462,7 @@ class MultiStreamPredictor:
         described = p0._describe(frames, frame_format, frame_layout)               # before any stream work
         camera_mask = N.camera_mask(camera_mask, (p0.T, p0.C))
         centers = N.centers(centers, p0.T)
+        tri_params = N.triangulation_params(return_triangulated)
         i = self._next
         self._next = (i + 1) % len(self.preds)
         s = self.streams[i]
@@ -449,6 +483,8 @@ class MultiStreamPredictor:
                 res = tuple(res) + tuple(self.preds[i].views2d(res[0], camera_mask=camera_mask))
             if return_spread:
                 res = tuple(res) + spread
+            if tri_params is not None:
+                res = tuple(res) + tuple(self.preds[i].triangulate_joints(camera_mask=camera_mask, params=tri_params))
             if then is not None:
                 res = then(res)
             ev = torch.cuda.Event(enable_timing=self.timing)

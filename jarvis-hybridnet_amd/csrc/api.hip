@@ -7,6 +7,7 @@
 #include "bifpn_node.h"
 #include "views2d.h"
 #include "subjects.h"
+#include "joints3d.h"
 
 namespace jh {
 static thread_local std::string g_err;
@@ -613,6 +614,9 @@ struct jh_predictor {
   // by the first such call, so a predictor that never asks for 2D views owns what it always did
   float* v2d_max = nullptr;
   int* v2d_idx = nullptr;
+  // Per-joint triangulation (jh_predictor_triangulate_joints): the observations [T3 * C][J][3] of a call that brings no
+  // buffer for them, allocated by the first such call; the scan's partials above are shared with the 2D views
+  float* j3_obs = nullptr;
   // Several subjects (jh_predictor_detect_subjects): peaks [T * C][kMaxPeaks][3], counts [T * C] and the global-form
   // scratch of the peak kernel (none where the heat map fits the LDS), ONE allocation made by the first such call
   float* subj_peaks = nullptr;
@@ -1161,6 +1165,24 @@ int jh_predictor_debug_mask(jh_predictor* pr, int32_t* n_active_dev, int32_t* nu
   return 0;
 }
 
+}  // extern "C"
+
+// The (max, index) partials of the all-joint argmax for the T3 * C heat maps of a 3D chunk, shared by
+// jh_predictor_views2d and jh_predictor_triangulate_joints: allocated by whichever is called first (`what`: its message
+// for a call inside a stream capture).
+static int scan_workspace(jh_predictor* pr, hipStream_t s, const char* what) {
+  if (pr->v2d_max) return 0;
+  // (two allocations: v2d_max is set last, so a failure leaves the predictor without either)
+  const size_t n = joint_argmax_all_partials(pr->T3 * pr->C, pr->Hh, pr->Hh, pr->Jp);
+  float* pmax = nullptr;
+  if (first_call_alloc(pr->mem, s, n * sizeof(float), what, &pmax)) return 1;
+  if (pr->mem.get(reinterpret_cast<void**>(&pr->v2d_idx), n * sizeof(int))) return 1;
+  pr->v2d_max = pmax;
+  return 0;
+}
+
+extern "C" {
+
 int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, const float* points_dev,
                          const uint8_t* mask_dev, int32_t* points2d_dev, float* conf2d_dev, float* reproj_dev,
                          float* err_dev, uint8_t* used_dev, void* stream) {
@@ -1174,15 +1196,8 @@ int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, co
                "all cameras are local");
     heat_all_dev = pr->kp->heat.p + (size_t)t0 * pr->C * pr->Hh * pr->Hh * pr->Jp;
   }
-  if (!pr->v2d_max) {
-    // (two allocations: v2d_max is set last, so a failure leaves the predictor without either)
-    const size_t n = joint_argmax_all_partials(N, pr->Hh, pr->Hh, pr->Jp);
-    float* pmax = nullptr;
-    if (first_call_alloc(pr->mem, s, n * sizeof(float), "the first jh_predictor_views2d call of a predictor allocates "
-                         "its workspace: make it outside a stream capture", &pmax)) return 1;
-    if (pr->mem.get(reinterpret_cast<void**>(&pr->v2d_idx), n * sizeof(int))) return 1;
-    pr->v2d_max = pmax;
-  }
+  if (scan_workspace(pr, s, "the first jh_predictor_views2d call of a predictor allocates its workspace: make it "
+                     "outside a stream capture")) return 1;
   const double bytes = 4.0 * N * pr->Hh * pr->Hh * pr->Jp;
   JH_PROF("joint_argmax_all", 0.0, bytes,
           launch_joint_argmax_all(heat_all_dev, pr->v2d_max, pr->v2d_idx, N, pr->Hh, pr->Hh, pr->J, pr->Jp, s));
@@ -1193,6 +1208,87 @@ int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, co
                                mask_dev ? mask_dev + (size_t)t0 * pr->C : nullptr, points_dev, pr->calib_at(t0),
                                points2d_dev, conf2d_dev, reproj_dev, err_dev, used_dev, pr->T3, pr->C, pr->J, pr->Jp,
                                pr->Hh, pr->Hh, pr->B / 2, s));
+  return 0;
+}
+
+// ---- per-joint robust triangulation (csrc/joints3d.h)
+static int joints3d_params(const jh_joints3d_params* p, Joints3dParams* out) {
+  JH_REQUIRE(p, "null jh_joints3d_params");
+  *out = Joints3dParams{p->min_views, p->refine_radius, p->min_conf, p->max_error_px};
+  return joints3d_check(*out);
+}
+
+int jh_joints3d_params_check(const jh_joints3d_params* params) {
+  Joints3dParams jp;
+  return joints3d_params(params, &jp);
+}
+
+int jh_op_joint_peaks_refine(const float* heat_dev, int n, int hh, int wh, int jp, const int32_t* idx_dev, int j,
+                             int radius, float* offsets_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(heat_dev && idx_dev && offsets_dev, "jh_op_joint_peaks_refine: null pointer");
+  JH_REQUIRE(n >= 1 && hh >= 1 && wh >= 1 && (long long)hh * wh < (1ll << 30), "jh_op_joint_peaks_refine: heat map shape");
+  JH_REQUIRE(j >= 1 && j <= jp && jp <= 1024, "jh_op_joint_peaks_refine: 1 <= j <= jp <= 1024");
+  JH_REQUIRE(radius >= 0 && radius <= kMaxRefineRadius, "jh_op_joint_peaks_refine: radius must be 0 .. 3");
+  if (launch_joint_peaks_refine(heat_dev, idx_dev, offsets_dev, n, hh, wh, j, jp, radius, s)) return 1;
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int jh_op_triangulate_joints(const float* obs_dev, int t, int cams, int j, const float* cam_dev, const float* intr_dev,
+                             const float* dist_dev, int calib_per_frame, const jh_joints3d_params* params,
+                             float* points_dev, int32_t* views_dev, uint8_t* members_dev, float* error_dev,
+                             void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  Joints3dParams jp;
+  if (joints3d_params(params, &jp)) return 1;
+  JH_REQUIRE(obs_dev && cam_dev && intr_dev && dist_dev && points_dev && views_dev && members_dev && error_dev,
+             "jh_op_triangulate_joints: null pointer");
+  JH_REQUIRE(t >= 1 && j >= 1, "jh_op_triangulate_joints: at least one frame set and one joint");
+  JH_REQUIRE(cams >= 1 && cams <= 64, "jh_op_triangulate_joints: 1 .. 64 cameras");
+  if (launch_joints3d(obs_dev, Calib{cam_dev, intr_dev, dist_dev, calib_per_frame ? cams : 0}, points_dev, views_dev,
+                      members_dev, error_dev, t, cams, j, jp.min_views, jp.min_conf, jp.max_error_px, s)) return 1;
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int jh_predictor_triangulate_joints(jh_predictor* pr, const float* heat_all_dev, int t0, const uint8_t* mask_dev,
+                                    const jh_joints3d_params* params, float* points_dev, int32_t* views_dev,
+                                    uint8_t* members_dev, float* error_dev, float* obs_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(pr, "jh_predictor_triangulate_joints: null predictor");
+  Joints3dParams jp;
+  if (joints3d_params(params, &jp)) return 1;
+  JH_REQUIRE(points_dev && views_dev && members_dev && error_dev, "jh_predictor_triangulate_joints: null output pointer");
+  JH_REQUIRE(t0 >= 0 && t0 + pr->T3 <= pr->T, "frame range of the joint triangulation");
+  const int N = pr->T3 * pr->C;
+  if (!heat_all_dev) {
+    JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "the predictor's own heat maps hold all cameras only when "
+               "all cameras are local");
+    heat_all_dev = pr->kp->heat.p + (size_t)t0 * pr->C * pr->Hh * pr->Hh * pr->Jp;
+  }
+  const char* what = "the first jh_predictor_triangulate_joints call of a predictor allocates its workspace: make it "
+                     "outside a stream capture";
+  if (scan_workspace(pr, s, what)) return 1;
+  // (the observations go straight into the caller's buffer when there is one; the predictor's own, allocated by the
+  // first call that brings none, otherwise)
+  if (!obs_dev) {
+    if (!pr->j3_obs && first_call_alloc(pr->mem, s, (size_t)N * pr->J * 3 * sizeof(float), what, &pr->j3_obs)) return 1;
+    obs_dev = pr->j3_obs;
+  }
+  JH_PROF("joint_argmax_all", 0.0, 4.0 * N * pr->Hh * pr->Hh * pr->Jp,
+          launch_joint_argmax_all(heat_all_dev, pr->v2d_max, pr->v2d_idx, N, pr->Hh, pr->Hh, pr->J, pr->Jp, s));
+  const int slices = joint_argmax_all_shape(N, pr->Hh, pr->Hh, pr->Jp).slices;
+  const int win = 2 * jp.refine_radius + 1;
+  // (the partials of every slice; with a radius, win^2 sectors of the heat map per observation; 12 B written)
+  JH_PROF("joint_observations", 0.0, 8.0 * N * slices * pr->Jp + (jp.refine_radius ? 32.0 * win * win : 0.0) * N * pr->J +
+          12.0 * N * pr->J,
+          launch_joint_observations(pr->v2d_max, pr->v2d_idx, heat_all_dev, pr->cur().chm + (size_t)t0 * pr->C * 2,
+                                    pr->cur().valid + t0, mask_dev ? mask_dev + (size_t)t0 * pr->C : nullptr, obs_dev,
+                                    pr->T3, pr->C, pr->J, pr->Jp, pr->Hh, pr->B / 2, jp.refine_radius, s));
+  JH_PROF("joints3d", 0.0, 12.0 * N * pr->J + 24.0 * pr->T3 * pr->J,
+          launch_joints3d(obs_dev, pr->calib_at(t0), points_dev, views_dev, members_dev, error_dev, pr->T3, pr->C,
+                          pr->J, jp.min_views, jp.min_conf, jp.max_error_px, s));
   return 0;
 }
 

@@ -21,4 +21,24 @@ int launch_views2d_final(const float* pmax, const int* pidx, const int* center_h
                          float* conf2d, float* reproj, float* err, unsigned char* used, int T, int C, int J, int Jp,
                          int Hh, int Wh, int hw, hipStream_t s);
 
+// Device side of the scan, for the kernels that read its partials (geometry.hip: the 2D views; joints3d.hip: the
+// observations of the joint triangulation): the order and the merge of the slices.
+// (value descending, index ascending): total on non-NaN values; NaN never wins
+__device__ __forceinline__ void argmax_take(float v, int i, float& best, int& bi) {
+  if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+}
+
+// (max, index) of channel j of image n over its slices (the partials of launch_joint_argmax_all)
+__device__ __forceinline__ void argmax_combine(const float* __restrict__ pmax, const int* __restrict__ pidx,
+                                               int n, int slices, int Jp, int j, float* best, int* bi) {
+  float b = -INFINITY;
+  int i = 0x7fffffff;
+  for (int k = 0; k < slices; ++k) {
+    const size_t o = ((size_t)n * slices + k) * Jp + j;
+    argmax_take(pmax[o], pidx[o], b, i);
+  }
+  *best = b;
+  *bi = i;
+}
+
 }  // namespace jh

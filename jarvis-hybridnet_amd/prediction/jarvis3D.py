@@ -150,7 +150,7 @@ class JarvisPredictor3D(nn.Module):
         return None if m is None else m.unsqueeze(0)
 
     def forward(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None,
-                return_2d=False, centers=None, return_spread=False):
+                return_2d=False, centers=None, return_spread=False, return_triangulated=False):
         """imgs (C,3,H,W) RGB in [0,1] -> (points3D (1,J,3), confidences (1,J)) or (None, None).
         return_2d: a third element, the per-camera `Views2D` of this frame set (leading dimension 1: 2D keypoints of
         every camera from the heat maps this forward computed anyway, the reprojections of the 3D keypoints and
@@ -173,7 +173,15 @@ class JarvisPredictor3D(nn.Module):
         the frame set (leading dimension 1), or None with the others.  Per joint, of the normalised heat map
         softplus(V2V output) whose mean is the keypoint: cov (1,J,3,3) its covariance in mm^2 from fp64 sums, peak
         (1,J,3) the voxel of its maximum in mm (the mode: |peak - point| beyond the spread means a multi-modal map),
-        mass (1,J) its sum.  points3D and confidences keep their bits."""
+        mass (1,J) its sum.  points3D and confidences keep their bits.
+        return_triangulated (True = the library's defaults, or what _native.joints3d_params made, or a dict of its
+        keywords): the last element, the `Triangulated3D` of the frame set (leading dimension 1), or None with the
+        others: per joint a second 3D point triangulated from the cameras' own 2D keypoints (the arg-max of the heat
+        maps this forward computed anyway, refined to sub-pixel position by the centroid of a (2 refine_radius + 1)^2
+        window), with the cameras that disagree left out by a consensus over two-view triangulations -- the one 3D
+        estimate that does not pass through the voxel cube: it still meets the rays of a limb outside ROI_CUBE_SIZE, it
+        names the camera whose keypoint sits on a reflection (members), and it checks V2V independently of V2V.
+        points3D and confidences keep their bits; it composes with everything above."""
         mask = self._frame_mask(camera_mask)
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(imgs, (self.num_cameras,))
@@ -181,13 +189,15 @@ class JarvisPredictor3D(nn.Module):
         self.reproTool.intrinsicMatrices = intrinsicMatrices
         self.reproTool.distortionCoefficients = distortionCoefficients
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers, return_spread)
+                         centers, return_spread, return_triangulated)
 
-    def _run(self, frames, calib, mask, return_2d, single=False, centers=None, return_spread=False):
+    def _run(self, frames, calib, mask, return_2d, single=False, centers=None, return_spread=False,
+             return_triangulated=False):
         """The forward of checked frames (a _native.Frames; single: one frame set, lead (C,)) with a checked mask and
         checked centres (_native.centers for the frames' time batch, or None), on the native predictor of their size:
         nothing of the predictor is touched before this."""
         check_native_seam(self)
+        tri = N.triangulation_params(return_triangulated)   # (True: the defaults; None: not asked for)
         per_frame = False
         if single:
             frames = frames._replace(lead=(1,) + frames.lead, data=frames.data.unsqueeze(0))
@@ -198,67 +208,76 @@ class JarvisPredictor3D(nn.Module):
         (pr.set_calibration_frames if per_frame else pr.set_calibration)(*calib)
         # (return_spread decides for this call alone: the native predictor sets its flag, on or off, before it runs)
         res = pr._forward(frames, None, mask, centers, *((True,) if return_spread else ()))
-        return self._single(pr, res, mask, return_2d) if single else self._batch(pr, res, mask, return_2d)
+        return self._single(pr, res, mask, return_2d, tri) if single else self._batch(pr, res, mask, return_2d, tri)
 
     @staticmethod
-    def _single(pr, res, mask, return_2d):
-        """The single-frame forms' return value: (points3D, confidences[, Views2D]), every element None when fewer
-        than two cameras saw the subject (jarvis3D.py:157,187-190).  The 2D views are enqueued behind the forward,
-        before the one host synchronisation (reading the validity flag).
+    def _single(pr, res, mask, return_2d, tri=None):
+        """The single-frame forms' return value: (points3D, confidences[, Views2D][, Spread3D][, Triangulated3D]), every
+        element None when fewer than two cameras saw the subject (jarvis3D.py:157,187-190).  The 2D views and the
+        triangulation (tri: its checked parameters) are enqueued behind the forward, before the one host
+        synchronisation (reading the validity flag).
         Views2D are HybridNet's own 2D detections, on the crop around the projection of the TRIANGULATED centre;
         JarvisPredictor2D crops around each camera's own centre detection.  The two agree wherever the crops cover
         the subject; they are not bit-equal."""
         points, conf, valid = res[:3]
         extra = ((pr.views2d(points, camera_mask=mask),) if return_2d else ()) + tuple(res[3:])
+        if tri is not None:
+            extra += (pr.triangulate_joints(camera_mask=mask, params=tri),)
         if int(valid[0].item()) == 0:
             return (None, None) + (None,) * len(extra)
         return (points, conf) + extra
 
     def forward_uint8(self, imgs_bgr, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None,
-                      return_2d=False, centers=None, return_spread=False):
+                      return_2d=False, centers=None, return_spread=False, return_triangulated=False):
         """imgs_bgr (C,H,W,3) uint8 BGR exactly as the video decoder delivers them
         (predict3D.py:72-78).  Same result as forward() on
         `imgs_bgr.float().permute(0,3,1,2)[:, [2,1,0]] / 255.` (predict3D.py:79-80); the
-        conversion runs inside the resize / crop kernels.  camera_mask, return_2d, centers, return_spread: as
-        forward() -- the Spread3D (covariance in mm^2, peak voxel in mm and mass of every joint's heat map) comes last."""
+        conversion runs inside the resize / crop kernels.  camera_mask, return_2d, centers, return_spread,
+        return_triangulated: as forward() -- the Spread3D (covariance in mm^2, peak voxel in mm and mass of every joint's
+        heat map), then the Triangulated3D come last."""
         mask = self._frame_mask(camera_mask)
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(imgs_bgr, (self.num_cameras,), "bgr")
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers, return_spread)
+                         centers, return_spread, return_triangulated)
 
     def forward_yuv(self, frames, frame_format, cameraMatrices, intrinsicMatrices, distortionCoefficients,
-                    camera_mask=None, return_2d=False, centers=None, return_spread=False):
+                    camera_mask=None, return_2d=False, centers=None, return_spread=False,
+                    return_triangulated=False):
         """frames (C,3H/2,W) uint8 YUV 4:2:0 as video decoders produce them natively, frame_format 'i420'
         (FFmpeg yuv420p: Y, U, V planes) or 'nv12' (Y plane, interleaved UV plane); H and W even.  Same result,
         bit for bit, as forward_uint8 on the BGR bytes of cv2.cvtColor(COLOR_YUV2BGR_I420 / _NV12) of each
         image (BT.601 limited range); the conversion runs inside the resize / crop kernels.
-        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d, centers, return_spread: as
-        forward() -- the Spread3D (covariance in mm^2, peak voxel in mm and mass of every joint's heat map) comes last."""
+        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d, centers, return_spread,
+        return_triangulated: as forward() -- the Spread3D (covariance in mm^2, peak voxel in mm and mass of every joint's
+        heat map), then the Triangulated3D come last."""
         mask = self._frame_mask(camera_mask)
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(frames, (self.num_cameras,), N.yuv_format(frame_format))
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers, return_spread)
+                         centers, return_spread, return_triangulated)
 
     def forward_surface(self, frames, surface, cameraMatrices, intrinsicMatrices, distortionCoefficients,
-                        camera_mask=None, return_2d=False, centers=None, return_spread=False):
+                        camera_mask=None, return_2d=False, centers=None, return_spread=False,
+                        return_triangulated=False):
         """frames (C,image_stride) uint8: one YUV 4:2:0 image per camera, read in place through the YuvSurface
         `surface` (pitched decoder surfaces, I420 / YV12 / NV12 / NV21, BT.601 / BT.709, limited / full range), or one
         raw sensor image per camera through the SensorSurface `surface` (Mono8, or an 8-bit Bayer mosaic demosaiced
         bilinearly on the GPU; pitched buffers with a header in front likewise).
         Same result, bit for bit, as forward_uint8 on the BGR bytes the surface's conversion gives
         (include/jarvis_hip.h); bytes outside the planes are never read.
-        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d, centers, return_spread: as
-        forward() -- the Spread3D (covariance in mm^2, peak voxel in mm and mass of every joint's heat map) comes last."""
+        -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d, centers, return_spread,
+        return_triangulated: as forward() -- the Spread3D (covariance in mm^2, peak voxel in mm and mass of every joint's
+        heat map), then the Triangulated3D come last."""
         mask = self._frame_mask(camera_mask)
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(frames, (self.num_cameras,), None, N.surface(surface))
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers, return_spread)
+                         centers, return_spread, return_triangulated)
 
     def forward_batch(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
-                      camera_mask=None, return_2d=False, frame_layout=None, centers=None, return_spread=False):
+                      camera_mask=None, return_2d=False, frame_layout=None, centers=None, return_spread=False,
+                      return_triangulated=False):
         """Throughput form: imgs (T,C,3,H,W) fp32 RGB or (T,C,H,W,3) uint8 BGR,
         independent time steps -> points (T,J,3), confidences (T,J), valid (T) int32;
         no host synchronisation.  frame_format 'i420' / 'nv12': imgs (T,C,3H/2,W) uint8 YUV 4:2:0 (see
@@ -286,7 +305,10 @@ class JarvisPredictor3D(nn.Module):
         return_spread: the `Spread3D` of the batch comes last, (points, confidences, valid[, views], spread): per joint
         the covariance cov (T,J,3,3) in mm^2 of the normalised heat map softplus(V2V output) (fp64 sums, rounded once),
         the voxel of its maximum peak (T,J,3) in mm and its sum mass (T,J); NaN rows where valid[t] = 0.  The other
-        outputs keep their bits; it composes with everything above."""
+        outputs keep their bits; it composes with everything above.
+        return_triangulated: the `Triangulated3D` of the batch comes last (see forward()): points (T,J,3), views (T,J),
+        members (T,J,C), error (T,J), observations (T,C,J,3); NaN / 0 rows where valid[t] = 0 and for a joint on which
+        fewer than min_views cameras agree.  Under per-frame-set calibration row t uses row t's calibration."""
         if centers is not None:
             if not torch.is_tensor(imgs) or imgs.dim() < 1:
                 raise ValueError("imgs must be a tensor of time steps")
@@ -297,11 +319,11 @@ class JarvisPredictor3D(nn.Module):
             camera_mask = N.camera_mask(camera_mask, (imgs.shape[0], self.num_cameras))
         frames = N.describe_frames(imgs, (None, self.num_cameras), frame_format, frame_layout)
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d,
-                         centers=centers, return_spread=return_spread)
+                         centers=centers, return_spread=return_spread, return_triangulated=return_triangulated)
 
     def forward_images(self, images, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
                        frame_layout=None, camera_mask=None, return_2d=False, centers=None,
-                       return_spread=False):
+                       return_spread=False, return_triangulated=False):
         """forward_batch on images that lie where their producers left them: `images` a sequence of C tensors (one
         frame set) or a sequence of T such sequences, each tensor ONE image -- fp32 (3,H,W); uint8 (H,W,3);
         frame_format 'i420' / 'nv12': uint8 (3H/2,W); frame_layout (a YuvSurface or a SensorSurface): 1-D uint8 of at
@@ -314,13 +336,14 @@ class JarvisPredictor3D(nn.Module):
         set (T,C,...), as forward_batch.
         centers (T,3): as forward_batch.  With the same images in several rows and one centre per row, the rows of a
         batch are different subjects seen in the same frames (a detected batch finds the strongest one in every row).
-        return_spread: as forward_batch -- the Spread3D of the batch (covariance in mm^2, peak voxel in mm and mass of
-        every joint's heat map) comes last."""
+        return_spread, return_triangulated: as forward_batch -- the Spread3D of the batch (covariance in mm^2, peak voxel
+        in mm and mass of every joint's heat map), then its Triangulated3D come last."""
         frames = image_frames(self.num_cameras, images, frame_format, frame_layout)
         T = frames.lead[0]
         camera_mask = N.camera_mask(camera_mask, (T, self.num_cameras))
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d,
-                         centers=N.centers(centers, T), return_spread=return_spread)
+                         centers=N.centers(centers, T), return_spread=return_spread,
+                         return_triangulated=return_triangulated)
 
     def detect_subjects(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, max_subjects,
                         frame_format=None, frame_layout=None, camera_mask=None, images=False, return_peaks=False,
@@ -358,27 +381,32 @@ class JarvisPredictor3D(nn.Module):
 
     def forward_subjects(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, max_subjects,
                          frame_format=None, frame_layout=None, camera_mask=None, images=False, return_2d=False,
-                         return_spread=False, **params):
+                         return_spread=False, return_triangulated=False, **params):
         """Several subjects in one time batch: detect_subjects, then one centred forward_batch (images=True:
         forward_images) per subject k on the same frames with centers=subjects.centers[:, k].
         -> points (T,K,J,3), confidences (T,K,J), valid (T,K) int32, subjects[, views][, spreads]: row (t, k) is row t
         of that centred call, bit for bit; an empty subject (NaN centre) is an invalid row, valid 0.  return_2d /
-        return_spread: a tuple of K Views2D / Spread3D, one per subject, follows.  camera_mask and the other arguments:
-        as detect_subjects.  No host synchronisation."""
+        return_spread / return_triangulated: a tuple of K Views2D / Spread3D / Triangulated3D, one per subject, follows,
+        in that order.  camera_mask and the other arguments: as detect_subjects.  No host synchronisation."""
         calib = (cameraMatrices, intrinsicMatrices, distortionCoefficients)
         subjects = self.detect_subjects(imgs, *calib, max_subjects, frame_format=frame_format,
                                         frame_layout=frame_layout, camera_mask=camera_mask, images=images, **params)
         rows = []
         for k in range(max_subjects):
             kw = dict(frame_format=frame_format, frame_layout=frame_layout, camera_mask=camera_mask,
-                      return_2d=return_2d, centers=subjects.centers[:, k], return_spread=return_spread)
+                      return_2d=return_2d, centers=subjects.centers[:, k], return_spread=return_spread,
+                      return_triangulated=return_triangulated)
             rows.append((self.forward_images if images else self.forward_batch)(imgs, *calib, **kw))
         out = tuple(torch.stack([r[i] for r in rows], 1) for i in range(3)) + (subjects,)
-        for i in range(3, len(rows[0])):             # (views, then spreads: one per subject)
+        for i in range(3, len(rows[0])):             # (views, then spreads, then triangulations: one per subject)
             out += (tuple(r[i] for r in rows),)
         return out
 
     @staticmethod
-    def _batch(pr, res, mask, return_2d):
-        # (points, conf, valid[, views][, spread]): the Spread3D, when asked for, is res[3]
-        return tuple(res[:3]) + (pr.views2d(res[0], camera_mask=mask),) + tuple(res[3:]) if return_2d else res
+    def _batch(pr, res, mask, return_2d, tri=None):
+        # (points, conf, valid[, views][, spread][, triangulated]): the Spread3D, when asked for, is res[3]
+        if return_2d:
+            res = tuple(res[:3]) + (pr.views2d(res[0], camera_mask=mask),) + tuple(res[3:])
+        if tri is not None:
+            res = tuple(res) + (pr.triangulate_joints(camera_mask=mask, params=tri),)
+        return res

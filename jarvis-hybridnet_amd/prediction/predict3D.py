@@ -89,6 +89,32 @@ def create_header_spread(writer, cfg):
     writer.writerow(list(SPREAD_COLUMNS) * len(names))
 
 
+TRIANGULATED_COLUMNS = ("x", "y", "z", "views", "error")
+
+
+def triangulated_row(points, views, error, num_joints):
+    """One row of triangulated3D.csv from a frame set's slice of a `Triangulated3D`: points (J,3) mm, views (J), error
+    (J) px -> [x, y, z, views, error] per joint, the floats as numpy float32 elements (the element type of the
+    confidences in data3D.csv), views as an int; an empty joint (views 0) is ['NaN', 'NaN', 'NaN', 0, 'NaN'], an
+    invalid frame set (points None) 'NaN' x 5J."""
+    if points is None:
+        return ["NaN"] * (num_joints * len(TRIANGULATED_COLUMNS))
+    points = points.detach().cpu().float().reshape(num_joints, 3).numpy()
+    views = views.detach().cpu().reshape(num_joints).numpy()
+    error = error.detach().cpu().float().reshape(num_joints).numpy()
+    row = []
+    for p, v, e in zip(points, views, error):
+        row = row + (list(p) + [int(v), e] if int(v) > 0 else ["NaN"] * 3 + [0, "NaN"])
+    return row
+
+
+def create_header_triangulated(writer, cfg):
+    """Two header rows: every joint name five times, then TRIANGULATED_COLUMNS per joint."""
+    names = list(cfg.KEYPOINT_NAMES)
+    writer.writerow(list(itertools.chain.from_iterable(itertools.repeat(x, len(TRIANGULATED_COLUMNS)) for x in names)))
+    writer.writerow(list(TRIANGULATED_COLUMNS) * len(names))
+
+
 def views2d_row(points2D, confidences2D, used, num_joints):
     """One row of a camera's data2D_<name>.csv from its slice of a frame set's `Views2D`: points2D (J,2),
     confidences2D (J): predict2D.frame_row of the same numbers ([x, y, confidence] per joint), or 'NaN' x 3J when
@@ -117,7 +143,7 @@ def create_header_reprojection_error(writer, cfg, camera_names):
 def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                      distortionCoefficients, cfg, output_dir, params=None, time_batch=1, streams=1,
                      frame_spec=None, frame_format="bgr", camera_mask=None, output_2d=False, camera_names=None,
-                     frame_layout=None, centers=None, output_spread=False):
+                     frame_layout=None, centers=None, output_spread=False, output_triangulated=False):
     """Run `predictor` over an iterable of multi-view frame sets -- (C,H,W,3) uint8 BGR
     arrays / tensors exactly as cv2 delivers them, or (C,3,H,W) fp32 RGB -- and write
     data3D.csv (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -191,10 +217,21 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     without the option): one row per frame set, per joint the six covariance entries of its 3D heat map in mm^2 and the
     voxel of its maximum in mm -- cxx,cxy,cxz,cyy,cyz,czz,px,py,pz (JarvisPredictor3D.forward_batch(...,
     return_spread=True); rows of spread_row, the header of create_header_spread when data3D.csv gets its header) --,
-    'NaN' x 9J for an invalid frame set.  It composes with time_batch, streams, camera_mask, centers and output_2d."""
+    'NaN' x 9J for an invalid frame set.  It composes with time_batch, streams, camera_mask, centers and output_2d.
+
+    output_triangulated (True = the library's defaults, or what _native.joints3d_params made, or a dict of its
+    keywords): also write `triangulated3D.csv` beside data3D.csv (which, like info.yaml, is byte-identical with and
+    without the option): one row per frame set, per joint the 3D point triangulated from the cameras' own 2D keypoints
+    with the cameras that disagree left out, the number of cameras that agree and their mean reprojection error in
+    pixels -- x,y,z,views,error (JarvisPredictor3D.forward_batch(..., return_triangulated=); rows of triangulated_row,
+    the header of create_header_triangulated when data3D.csv gets its header) --, 'NaN' for an empty joint's numbers
+    and for an invalid frame set.  It composes with time_batch, streams, camera_mask, centers, output_2d and
+    output_spread."""
     import contextlib
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
     yuv = driver_format(frame_format, frame_spec, 3, frame_layout)
+    tri_params = N.triangulation_params(output_triangulated)
+    tail = 3 if tri_params is not None else 0                   # (points, views and error of the Triangulated3D, last)
     run_mask, mask_iter = None, None
     if camera_mask is not None:
         C = cfg.HYBRIDNET.NUM_CAMERAS
@@ -245,14 +282,23 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             if len(names) == J:
                 create_header_spread(writer_spread, cfg)
 
+        writer_tri = None
+        if tri_params is not None:
+            writer_tri = open_csv("triangulated3D.csv")
+            if len(names) == J:
+                create_header_triangulated(writer_tri, cfg)
+
         def emit(outs, real):
             pts, conf, valid = outs[:3]
             for t in range(real):
                 ok = int(valid[t]) != 0
                 writer.writerow(frame_row(pts[t] if ok else None, conf[t] if ok else None, J))
                 if output_spread:
-                    cov, peak = outs[-3], outs[-2]
+                    cov, peak = outs[-3 - tail], outs[-2 - tail]
                     writer_spread.writerow(spread_row(cov[t] if ok else None, peak[t] if ok else None, J))
+                if tri_params is not None:
+                    tp, tv, te = outs[-3:]
+                    writer_tri.writerow(triangulated_row(tp[t] if ok else None, tv[t], te[t], J))
                 if output_2d:
                     p2d, c2d, _, err, used = outs[3:8]
                     for c, w in enumerate(writers_2d):
@@ -260,6 +306,10 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                     writer_err.writerow(reprojection_error_row(err[t]))
 
         ring = {}                                               # pinned host copies of the outputs, per slot
+
+        def written(outs):
+            """The tensors of a batch that a file gets: the five of a Triangulated3D cut to points, views, error."""
+            return outs if tri_params is None else tuple(outs[:-5]) + (outs[-5], outs[-4], outs[-2])
 
         def submit(x, slot, mask=None, centers=None):
             kw = {} if mask is None else {"camera_mask": mask}
@@ -269,6 +319,8 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                 kw["return_2d"] = True
             if output_spread:
                 kw["return_spread"] = True
+            if tri_params is not None:
+                kw["return_triangulated"] = tri_params
             if frame_layout is not None:
                 kw["frame_layout"] = frame_layout
             if hasattr(predictor, "native_streams"):
@@ -276,16 +328,21 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                 msp = predictor.native_streams(d.height, d.width, time_batch, streams)
                 msp.set_calibration(*calib)
                 # results leave for pinned host memory on the forward's own stream (behind it, before its event)
-                res = msp.forward(x, then=lambda outs: host_outputs(ring, slot, outs),
+                # (of a Triangulated3D only what the CSV holds: members and observations stay on the device)
+                res = msp.forward(x, then=lambda outs: host_outputs(ring, slot, written(outs)),
                                   frame_format=frame_format if yuv else None, **kw)
                 return res, msp.last_event
             # any object with the batch interface
             res = predictor.forward_batch(x, *calib, frame_format=frame_format, **kw) if yuv else \
                 predictor.forward_batch(x, *calib, **kw)
+            tri = ()
+            if tri_params is not None:
+                res, tri = tuple(res[:-1]), (res[-1].points, res[-1].views, res[-1].error)
             if output_spread:
-                res = tuple(res[:-1]) + tuple(res[-1])         # (..., Spread3D) -> its three tensors, last
+                res = tuple(res[:-1]) + tuple(res[-1])         # (..., Spread3D) -> its three tensors
             if output_2d:
                 res = tuple(res[:3]) + tuple(res[3]) + tuple(res[4:])     # (points, conf, valid, Views2D, ...) -> tensors
+            res = tuple(res) + tri
             ev = None
             if x.is_cuda:
                 res = host_outputs(ring, slot, res)
