@@ -601,7 +601,7 @@ int jh_predictor_forward_images(jh_predictor* pr, const void* const* images_host
  * jh_predictor_device_bytes, the memory and the launches of a predictor that never asks are unchanged -- and that first
  * call must not be made inside a stream capture.  Needs CenterDetect weights and all cameras local; otherwise, and for
  * parameters out of range, non-zero with jh_last_error() set and nothing enqueued.
- * Subject k of one call and subject k of the next are unrelated: identity across frames is the caller's. */
+ * Subject k of one call and subject k of the next are unrelated; jh_op_track_subjects below gives them an identity. */
 typedef struct jh_subjects_params {
   int32_t max_subjects, max_peaks, nms_radius, min_views;
   float min_peak, max_error_px;
@@ -618,6 +618,79 @@ int jh_predictor_detect_subjects(jh_predictor* pr, const void* frames_dev, const
                                  const uint8_t* mask_dev, const jh_subjects_params* params, float* centers_dev,
                                  int32_t* views_dev, int32_t* members_dev, float* error_dev,
                                  float* peaks_dev /* optional */, void* stream);
+
+/* Subject identity across frame sets (ABI v4, additive; new design: the reference follows one animal).  The rows of
+ * jh_predictor_detect_subjects are ordered inside one frame set, so two animals swap rows whenever their view counts or
+ * costs swap.  Here up to eight TRACKS live in caller-owned device memory (jh_track_state); the detections of every
+ * frame set are matched to them greedily, nearest first, and come out again in SLOT order: slot k of frame set t and of
+ * t+1 is the same track, and ids[t][k] names it for the whole run.  Everything happens on the device: no host
+ * synchronisation per frame set.
+ *
+ * jh_track_params.  max_subjects = K, 1 .. 8: the slots in use, and the detections per frame set.  max_missed >= 0: the
+ * frame sets a track may go unmatched and still keep its identity.  predict 0: a track is matched against its last
+ * position; 1: against last position + velocity * frame sets elapsed.  coast 1: the output centre of an unmatched live
+ * track is its predicted position; 0: NaN.  max_jump_mm > 0 (+inf allowed, NaN refused): the gate per elapsed frame set.
+ * predict and coast are 0 or 1.  There are no defaults on this side; max_jump_mm is the rig's.  Checked by
+ * jh_track_params_check (no GPU needed) and by jh_op_track_subjects: non-zero with jh_last_error() set, nothing enqueued.
+ *
+ * jh_track_state: device memory owned by the caller, 272 bytes; jh_op_track_subjects touches no slot >= K.
+ * missed[k] = -1: slot k is free (id -1, pos = vel = 0); >= 0: the frame sets since the track's last match.
+ * jh_op_track_reset makes all eight slots free, next_id 0, every float and reserved word 0.
+ *
+ * jh_op_track_subjects: centers (t,K,3), views (t,K) int32, members (t,K,cams) int32, error (t,K) dev: the four tensors
+ * jh_predictor_detect_subjects writes.  views / members / error may be NULL together; views_out / members_out /
+ * error_out are then NULL too.  Outputs must not alias inputs.  The frame sets of a call are consecutive in time and
+ * processed in ascending t; the state carries over from call to call, so one call of t frame sets and t calls of one give
+ * the same bits.  For each frame set:
+ *   1 live, prediction   slot k is live iff missed[k] >= 0.  With predict, p_k = pos_k + vel_k * (float)(missed_k + 1),
+ *                        one fp32 multiply and one add per component; without, p_k = pos_k.
+ *   2 present            detection i is present iff its three centre components are finite.
+ *   3 distance, gate     d(k,i) = sqrt(dx*dx + dy*dy + dz*dz), dx = p_k.x - c_i.x and so on, one fp32 rounding per
+ *                        operation, the sum left to right.  The pair of a live slot and a present detection is eligible
+ *                        iff d <= max_jump_mm * (float)(missed_k + 1) (one fp32 multiply); a NaN d is never eligible.
+ *   4 greedy match       among the eligible pairs whose slot and detection are both unassigned, the smallest d, ties to
+ *                        the lowest k, then the lowest i; assign it; repeat until none is left.
+ *   5 matched slot       vel = predict ? (c_i - pos) / (float)(missed + 1) : 0 (one fp32 subtract and one divide per
+ *                        component), then pos = c_i, missed = 0.
+ *   6 unmatched live     missed += 1; if missed > max_missed the slot becomes free: missed = -1, id = -1, pos = vel = 0.
+ *   7 births             the unmatched present detections in ascending i each take the lowest free slot (one freed in
+ *                        step 6 of this frame set counts): id = next_id++, pos = c_i, vel = 0, missed = 0.  With no free
+ *                        slot the detection is dropped and dropped[t] counts it.
+ *   8 row (t,k)          slots: the detection the slot holds in this frame set, or -1.  ids, missed: the slot's values
+ *                        after the frame set (-1 when free).  centers_out: c_i bit for bit; for a live unmatched slot
+ *                        with coast, pos + vel * (float)missed (pos when predict == 0); otherwise NaN.  views_out: the
+ *                        detection's views, or 0.  members_out: its members row, or all -1.  error_out: its error, or
+ *                        NaN.
+ * -> centers_out (t,K,3), views_out (t,K), members_out (t,K,cams), error_out (t,K), ids / slots / missed (t,K) int32,
+ * dropped (t) int32.  A row of centers_out goes into jh_predictor_set_centers as a row of centers does.
+ * Asynchronous: one launch of one 64-lane wave on `stream`, no synchronisation, nothing allocated, legal inside a stream
+ * capture; calls on one state must be ordered by the caller (one stream, or events).  The result does not depend on
+ * timing.  The time of a call is the latency of t * K dependent wave steps.
+ * Out of scope: the optimal (min-sum) assignment -- the match is greedy --, eviction of a coasting track in favour of
+ * a new detection, more than eight slots, and several trackers per launch. */
+typedef struct jh_track_params {
+  int32_t max_subjects;   /* K, 1 .. 8 */
+  int32_t max_missed;     /* >= 0: frame sets a track may go unmatched and still keep its identity */
+  int32_t predict;        /* 0: match against the last position; 1: against last position + velocity * frames elapsed */
+  int32_t coast;          /* 1: an unmatched live track's output centre is its predicted position, 0: NaN */
+  float   max_jump_mm;    /* > 0, +inf allowed, NaN refused: the gate per elapsed frame set */
+} jh_track_params;
+
+typedef struct jh_track_state {      /* device memory owned by the caller; slots >= K are never touched */
+  float pos[8][3], vel[8][3];
+  int32_t missed[8];                 /* -1: free slot; >= 0: frame sets since the last match */
+  int32_t id[8];                     /* identity of the slot's track, -1 when free */
+  int32_t next_id, reserved[3];
+} jh_track_state;
+
+int jh_track_params_check(const jh_track_params* params);          /* no GPU needed */
+int jh_op_track_reset(jh_track_state* state_dev, void* stream);    /* all slots free, next_id 0, floats 0 */
+int jh_op_track_subjects(const float* centers_dev, const int32_t* views_dev, const int32_t* members_dev,
+                         const float* error_dev, int t, int cams, const jh_track_params* params,
+                         jh_track_state* state_dev,
+                         float* centers_out, int32_t* views_out, int32_t* members_out, float* error_out,
+                         int32_t* ids_out, int32_t* slots_out, int32_t* missed_out, int32_t* dropped_out,
+                         void* stream);
 
 /* Per-joint robust triangulation (ABI v4, additive; new design: the reference's only 3D keypoints are V2V's).  A
  * classical 3D point per joint, triangulated from the cameras' own 2D keypoints with the cameras that disagree left out:

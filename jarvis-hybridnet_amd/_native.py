@@ -79,6 +79,21 @@ class Joints3dParamsStruct(ctypes.Structure):
 
 assert ctypes.sizeof(Joints3dParamsStruct) == 16
 
+
+class TrackParamsStruct(ctypes.Structure):
+    """jh_track_params of include/jarvis_hip.h (built by track_params())."""
+    _fields_ = [("max_subjects", ctypes.c_int32), ("max_missed", ctypes.c_int32), ("predict", ctypes.c_int32),
+                ("coast", ctypes.c_int32), ("max_jump_mm", c_float)]
+
+
+class TrackStateStruct(ctypes.Structure):
+    """jh_track_state of include/jarvis_hip.h: the layout of the tracker's device memory (tracks.SubjectTracker)."""
+    _fields_ = [("pos", c_float * 3 * 8), ("vel", c_float * 3 * 8), ("missed", ctypes.c_int32 * 8),
+                ("id", ctypes.c_int32 * 8), ("next_id", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+assert ctypes.sizeof(TrackParamsStruct) == 20 and ctypes.sizeof(TrackStateStruct) == 272
+
 ABI_VERSION = 4                    # JH_ABI_VERSION of include/jarvis_hip.h
 # sizeof(jh_predictor_config): statically asserted on the C side (tests/abi_smoke.c) and here
 assert ctypes.sizeof(PredictorConfig) == 84
@@ -200,6 +215,10 @@ _SIGS = {
                                              ctypes.POINTER(YuvSurfaceStruct), ctypes.POINTER(SensorSurfaceStruct),
                                              c_void_p, ctypes.POINTER(SubjectsParamsStruct), c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_track_params_check": (c_int, [ctypes.POINTER(TrackParamsStruct)]),
+    "jh_op_track_reset": (c_int, [c_void_p, c_void_p]),
+    "jh_op_track_subjects": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                     ctypes.POINTER(TrackParamsStruct)] + [c_void_p] * 10),
     "jh_joints3d_params_check": (c_int, [ctypes.POINTER(Joints3dParamsStruct)]),
     "jh_op_joint_peaks_refine": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                                          c_void_p]),
@@ -570,6 +589,31 @@ def subjects_params(max_subjects, max_peaks=None, nms_radius=4, min_views=2, min
         raise ValueError("min_peak and max_error_px must be numbers, got %r and %r" % (min_peak, max_error_px))
     p = SubjectsParamsStruct(ints["max_subjects"], ints["max_peaks"], ints["nms_radius"], ints["min_views"], *floats)
     if lib().jh_subjects_params_check(ctypes.byref(p)) != 0:
+        raise ValueError(lib().jh_last_error().decode())
+    return p
+
+
+def track_params(max_subjects, max_jump_mm, max_missed=0, predict=True, coast=False):
+    """The parameters of a subject tracker checked -> TrackParamsStruct (jh_track_params).  max_jump_mm has no default:
+    it is the rig's (how far an animal moves between two frame sets).  The others are documented values, not
+    recommendations: max_missed 0 (a track that goes unmatched once ends), predict True (match against last position +
+    velocity * frame sets elapsed), coast False (an unmatched live track's centre is NaN).  Ranges (the library's own
+    check, jh_track_params_check: host arithmetic, no device): max_subjects 1 .. 8, max_missed >= 0, max_jump_mm > 0
+    (+inf allowed).  ValueError for anything else, a non-integer count and a predict / coast that is no bool included."""
+    for name, v in dict(max_subjects=max_subjects, max_missed=max_missed).items():
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError("%s must be an int, got %r" % (name, v))
+        if abs(v) >= 2 ** 31:
+            raise ValueError("%s is out of range: %r" % (name, v))
+    for name, v in dict(predict=predict, coast=coast).items():
+        if not (isinstance(v, int) and v in (0, 1)):            # (a bool is an int)
+            raise ValueError("%s must be a bool, got %r" % (name, v))
+    try:
+        jump = float(max_jump_mm)
+    except (TypeError, ValueError):
+        raise ValueError("max_jump_mm must be a number, got %r" % (max_jump_mm,))
+    p = TrackParamsStruct(max_subjects, max_missed, int(predict), int(coast), jump)
+    if lib().jh_track_params_check(ctypes.byref(p)) != 0:
         raise ValueError(lib().jh_last_error().decode())
     return p
 

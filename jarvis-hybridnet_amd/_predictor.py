@@ -8,6 +8,7 @@ from . import _native as N
 from . import arch
 from .spread import Spread3D  # noqa: F401 -- the name the forwards return
 from .subjects import Subjects
+from .tracks import check_tracker
 from .triangulated import Triangulated3D
 
 
@@ -485,6 +486,43 @@ class MultiStreamPredictor:
                 res = tuple(res) + spread
             if tri_params is not None:
                 res = tuple(res) + tuple(self.preds[i].triangulate_joints(camera_mask=camera_mask, params=tri_params))
+            if then is not None:
+                res = then(res)
+            ev = torch.cuda.Event(enable_timing=self.timing)
+            ev.record(s)
+        self.events[i] = ev
+        self.last_event = ev
+        return res
+
+    def forward_subjects(self, frames, params, tracker=None, then=None, frame_format=None, camera_mask=None,
+                         frame_layout=None):
+        """Several subjects of one batch, on the batch's stream: detect_subjects (params: what _native.subjects_params
+        made, K = params.max_subjects), the update of `tracker` (a tracks.SubjectTracker of K slots, or None) and K
+        centred forwards, one per subject (or slot) -> points (T,K,J,3), conf (T,K,J), valid (T,K), then the four
+        tensors of the Subjects (centers, views, members, error; in slot order under a tracker), then the four of the
+        Tracks (ids, slots, missed, dropped) when there is a tracker.  The tracker orders its updates itself (an event
+        from batch to batch), so the batches of a recording update it in call order although they run on different
+        streams.  then, frame_format, camera_mask, frame_layout: as forward()."""
+        p0 = self.preds[0]
+        described = p0._describe(frames, frame_format, frame_layout)               # before any stream work
+        camera_mask = N.camera_mask(camera_mask, (p0.T, p0.C))
+        K = params.max_subjects
+        check_tracker(tracker, K)
+        i = self._next
+        self._next = (i + 1) % len(self.preds)
+        s = self.streams[i]
+        s.wait_stream(torch.cuda.current_stream())       # `frames` may still be in the making
+        frames.record_stream(s)                          # (see forward)
+        with torch.cuda.stream(s):
+            self._frames_calibration(i)
+            pr = self.preds[i]
+            subjects = pr.detect_subjects(described, params, camera_mask)
+            tracks = ()
+            if tracker is not None:
+                subjects, tracks = tracker.update(subjects)
+            rows = [pr._forward(described, None, camera_mask, N.centers(subjects.centers[:, k], p0.T))
+                    for k in range(K)]
+            res = tuple(torch.stack([r[j] for r in rows], 1) for j in range(3)) + tuple(subjects) + tuple(tracks)
             if then is not None:
                 res = then(res)
             ev = torch.cuda.Event(enable_timing=self.timing)

@@ -8,6 +8,7 @@
 #include "views2d.h"
 #include "subjects.h"
 #include "joints3d.h"
+#include "tracks.h"
 
 namespace jh {
 static thread_local std::string g_err;
@@ -1289,6 +1290,48 @@ int jh_predictor_triangulate_joints(jh_predictor* pr, const float* heat_all_dev,
   JH_PROF("joints3d", 0.0, 12.0 * N * pr->J + 24.0 * pr->T3 * pr->J,
           launch_joints3d(obs_dev, pr->calib_at(t0), points_dev, views_dev, members_dev, error_dev, pr->T3, pr->C,
                           pr->J, jp.min_views, jp.min_conf, jp.max_error_px, s));
+  return 0;
+}
+
+// ---- subject identity across frame sets (csrc/tracks.h)
+static_assert(sizeof(jh_track_state) == sizeof(TrackState) && sizeof(jh_track_state) == 272, "jh_track_state layout");
+static_assert(sizeof(jh_track_params) == 20, "jh_track_params layout");
+
+static int track_params(const jh_track_params* p, TrackParams* out) {
+  JH_REQUIRE(p, "null jh_track_params");
+  *out = TrackParams{p->max_subjects, p->max_missed, p->predict, p->coast, p->max_jump_mm};
+  return tracks_check(*out);
+}
+
+int jh_track_params_check(const jh_track_params* params) {
+  TrackParams tp;
+  return track_params(params, &tp);
+}
+
+int jh_op_track_reset(jh_track_state* state_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(state_dev, "jh_op_track_reset: null state");
+  JH_PROF("track_reset", 0.0, (double)sizeof(jh_track_state),
+          launch_track_reset(reinterpret_cast<TrackState*>(state_dev), s));
+  return 0;
+}
+
+int jh_op_track_subjects(const float* centers_dev, const int32_t* views_dev, const int32_t* members_dev,
+                         const float* error_dev, int t, int cams, const jh_track_params* params,
+                         jh_track_state* state_dev, float* centers_out, int32_t* views_out, int32_t* members_out,
+                         float* error_out, int32_t* ids_out, int32_t* slots_out, int32_t* missed_out,
+                         int32_t* dropped_out, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  TrackParams tp;
+  if (track_params(params, &tp)) return 1;
+  JH_REQUIRE(centers_dev && state_dev && centers_out && ids_out && slots_out && missed_out && dropped_out,
+             "jh_op_track_subjects: null pointer");
+  JH_REQUIRE(t >= 1 && cams >= 1, "jh_op_track_subjects: at least one frame set and one camera");
+  // (every row read and written once; members are the bulk)
+  JH_PROF("track_subjects", 0.0, 8.0 * t * tp.max_subjects * (7.0 + (members_dev ? cams : 0)),
+          launch_track_subjects(centers_dev, views_dev, members_dev, error_dev, t, cams, tp,
+                                reinterpret_cast<TrackState*>(state_dev), centers_out, views_out, members_out,
+                                error_out, ids_out, slots_out, missed_out, dropped_out, s));
   return 0;
 }
 

@@ -17,6 +17,7 @@ from .._params import flat_state, weights_fingerprint
 from .._predictor import NativePredictor
 from ..efficienttrack.efficienttrack import EfficientTrack
 from ..hybridnet.hybridnet import HybridNet
+from ..tracks import check_tracker
 from ..utils.reprojection import ReprojectionTool
 
 
@@ -347,7 +348,7 @@ class JarvisPredictor3D(nn.Module):
 
     def detect_subjects(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, max_subjects,
                         frame_format=None, frame_layout=None, camera_mask=None, images=False, return_peaks=False,
-                        **params):
+                        tracker=None, **params):
         """Where the subjects are, for a time batch: imgs as forward_batch takes them -- or, with images=True, as
         forward_images takes them -- -> `Subjects` (centers (T,K,3) world mm, views (T,K), members (T,K,C), error
         (T,K); K = max_subjects), device tensors, no host synchronisation.
@@ -363,10 +364,16 @@ class JarvisPredictor3D(nn.Module):
         A centre goes back in as `centers=` of forward_batch / forward_images (forward_subjects does that).  Robust
         single-subject detection is max_subjects=1: the cameras whose maximum lies on something else are left out of
         the triangulation instead of dragging it.
-        Not covered: the drivers (predict3D_frames), JarvisPredictor2D, analyze_frames, the camera-sharded path, and
-        identity across frames -- subject k of frame set t and of t+1 are unrelated."""
+        tracker: a tracks.SubjectTracker of max_subjects slots.  Without one, subject k of frame set t and of t+1 are
+        unrelated.  With one, the Subjects come back in SLOT order -- slot k is the same animal from frame set to frame
+        set and from call to call, as far as nearest-first matching under the tracker's gate can tell -- and a `Tracks`
+        (ids, slots, missed, dropped) follows, behind `peaks` when those are asked for: (subjects[, peaks], tracks).
+        The tracker's kernel runs behind the detection on the same stream: still no host synchronisation.
+        Not covered: JarvisPredictor2D, analyze_frames and the camera-sharded path (the driver: predict3D_frames(...,
+        max_subjects=))."""
         check_native_seam(self)
         p = N.subjects_params(max_subjects, **params)
+        check_tracker(tracker, max_subjects)
         if images:
             frames = image_frames(self.num_cameras, imgs, frame_format, frame_layout)
         else:
@@ -377,20 +384,31 @@ class JarvisPredictor3D(nn.Module):
         per_frame = N.calibration(calib, T, self.num_cameras)[0] == "frames"
         pr = self.native(frames.height, frames.width, time_batch=T)
         (pr.set_calibration_frames if per_frame else pr.set_calibration)(*calib)
-        return pr.detect_subjects(frames, p, mask, return_peaks)
+        res = pr.detect_subjects(frames, p, mask, return_peaks)
+        if tracker is None:
+            return res
+        subjects, tracks = tracker.update(res[0] if return_peaks else res)
+        return (subjects, res[1], tracks) if return_peaks else (subjects, tracks)
 
     def forward_subjects(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, max_subjects,
                          frame_format=None, frame_layout=None, camera_mask=None, images=False, return_2d=False,
-                         return_spread=False, return_triangulated=False, **params):
+                         return_spread=False, return_triangulated=False, tracker=None, **params):
         """Several subjects in one time batch: detect_subjects, then one centred forward_batch (images=True:
         forward_images) per subject k on the same frames with centers=subjects.centers[:, k].
         -> points (T,K,J,3), confidences (T,K,J), valid (T,K) int32, subjects[, views][, spreads]: row (t, k) is row t
         of that centred call, bit for bit; an empty subject (NaN centre) is an invalid row, valid 0.  return_2d /
         return_spread / return_triangulated: a tuple of K Views2D / Spread3D / Triangulated3D, one per subject, follows,
-        in that order.  camera_mask and the other arguments: as detect_subjects.  No host synchronisation."""
+        in that order.  camera_mask and the other arguments: as detect_subjects.  No host synchronisation.
+        tracker (a tracks.SubjectTracker, see detect_subjects): the subjects are put into slot order first and the
+        centred forwards run on the tracked centres, so k is a slot -- one animal -- in every output; the `Tracks` comes
+        last.  Row (t, k) is then row (t, tracks.slots[t, k]) of the call without a tracker, bit for bit, and an invalid
+        row where the slot holds no detection (with coast=True: the forward at the track's predicted centre)."""
         calib = (cameraMatrices, intrinsicMatrices, distortionCoefficients)
-        subjects = self.detect_subjects(imgs, *calib, max_subjects, frame_format=frame_format,
+        subjects = self.detect_subjects(imgs, *calib, max_subjects, frame_format=frame_format, tracker=tracker,
                                         frame_layout=frame_layout, camera_mask=camera_mask, images=images, **params)
+        tracks = ()
+        if tracker is not None:
+            subjects, tracks = subjects[0], subjects[1:]
         rows = []
         for k in range(max_subjects):
             kw = dict(frame_format=frame_format, frame_layout=frame_layout, camera_mask=camera_mask,
@@ -400,7 +418,7 @@ class JarvisPredictor3D(nn.Module):
         out = tuple(torch.stack([r[i] for r in rows], 1) for i in range(3)) + (subjects,)
         for i in range(3, len(rows[0])):             # (views, then spreads, then triangulations: one per subject)
             out += (tuple(r[i] for r in rows),)
-        return out
+        return out + tracks
 
     @staticmethod
     def _batch(pr, res, mask, return_2d, tri=None):

@@ -115,6 +115,47 @@ def create_header_triangulated(writer, cfg):
     writer.writerow(list(TRIANGULATED_COLUMNS) * len(names))
 
 
+SUBJECT_COLUMNS = ("id", "cx", "cy", "cz", "views", "error", "missed")
+
+
+def subjects_row(centers, views, error, ids=None, missed=None, dropped=0):
+    """One row of subjects3D.csv from a frame set's slice of a `Subjects` -- centers (K,3) mm, views (K), error (K) px
+    -- and of a `Tracks` -- ids (K), missed (K), dropped -- or None for both (no tracker: id -1, missed -1) ->
+    [id, cx, cy, cz, views, error, missed] per slot, then dropped: ints as ints, the floats as numpy float32 elements
+    (the element type of the confidences in data3D.csv), 'NaN' for a NaN."""
+    import math
+    centers = centers.detach().cpu().float().reshape(-1, 3).numpy()
+    error = error.detach().cpu().float().reshape(-1).numpy()
+    row = []
+    for k in range(centers.shape[0]):
+        row.append(-1 if ids is None else int(ids[k]))
+        row += ["NaN" if math.isnan(v) else v for v in centers[k]]
+        row += [int(views[k]), "NaN" if math.isnan(error[k]) else error[k], -1 if missed is None else int(missed[k])]
+    return row + [int(dropped)]
+
+
+def create_header_subjects(writer, max_subjects):
+    """Two header rows: subject<k> once per column of the slot, then SUBJECT_COLUMNS per slot; `dropped` closes both."""
+    n = len(SUBJECT_COLUMNS)
+    writer.writerow(list(itertools.chain.from_iterable(itertools.repeat("subject%d" % k, n)
+                                                       for k in range(max_subjects))) + ["dropped"])
+    writer.writerow(list(SUBJECT_COLUMNS) * max_subjects + ["dropped"])
+
+
+def _tracker(track, max_subjects):
+    """The driver's `track` argument -> a tracks.SubjectTracker of max_subjects slots, or None: None stays None, a
+    SubjectTracker is taken as it is (its slots must be max_subjects), a dict is its keywords.  ValueError otherwise."""
+    from ..tracks import SubjectTracker, check_tracker
+    if track is None or isinstance(track, SubjectTracker):
+        return check_tracker(track, max_subjects)
+    if not isinstance(track, dict):
+        raise ValueError("track must be a dict of SubjectTracker's keywords, a SubjectTracker or None, got %r" % (track,))
+    if "max_subjects" in track or "max_jump_mm" not in track:
+        raise ValueError("track takes max_jump_mm (required), max_missed, predict, coast and device; the slots are "
+                         "max_subjects")
+    return SubjectTracker(max_subjects, **track)
+
+
 def views2d_row(points2D, confidences2D, used, num_joints):
     """One row of a camera's data2D_<name>.csv from its slice of a frame set's `Views2D`: points2D (J,2),
     confidences2D (J): predict2D.frame_row of the same numbers ([x, y, confidence] per joint), or 'NaN' x 3J when
@@ -143,7 +184,8 @@ def create_header_reprojection_error(writer, cfg, camera_names):
 def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                      distortionCoefficients, cfg, output_dir, params=None, time_batch=1, streams=1,
                      frame_spec=None, frame_format="bgr", camera_mask=None, output_2d=False, camera_names=None,
-                     frame_layout=None, centers=None, output_spread=False, output_triangulated=False):
+                     frame_layout=None, centers=None, output_spread=False, output_triangulated=False,
+                     max_subjects=None, subject_params=None, track=None):
     """Run `predictor` over an iterable of multi-view frame sets -- (C,H,W,3) uint8 BGR
     arrays / tensors exactly as cv2 delivers them, or (C,3,H,W) fp32 RGB -- and write
     data3D.csv (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -226,12 +268,48 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     pixels -- x,y,z,views,error (JarvisPredictor3D.forward_batch(..., return_triangulated=); rows of triangulated_row,
     the header of create_header_triangulated when data3D.csv gets its header) --, 'NaN' for an empty joint's numbers
     and for an invalid frame set.  It composes with time_batch, streams, camera_mask, centers, output_2d and
-    output_spread."""
+    output_spread.
+
+    max_subjects = K (1 .. 8): a recording with several animals.  Every batch goes through forward_subjects
+    (JarvisPredictor3D.forward_subjects / MultiStreamPredictor.forward_subjects): up to K subjects are detected per frame
+    set and each gets its own centred forward.  subject_params: a dict of detect_subjects' keywords (max_peaks,
+    nms_radius, min_views, min_peak, max_error_px).  track: a dict of tracks.SubjectTracker's keywords -- max_jump_mm,
+    the rig's, is required; max_missed, predict, coast -- or a SubjectTracker of K slots; ONE tracker lives for the run
+    and is updated batch after batch in frame order, on the device, whatever `streams` is.  track=None: the rows are in
+    detection order -- most views first within each frame set -- and have NO identity: file k is then not one animal.
+    Files, in place of data3D.csv (which is not written in this mode; info.yaml is):
+      data3D_subject{k}.csv  k = 0 .. K-1, the slot (the row, without a tracker): exactly the format and header of
+                             data3D.csv; the 'NaN' row where the slot holds no detection in that frame set -- with
+                             coast=True it holds the forward at the track's predicted centre -- or the row is invalid.
+      subjects3D.csv         one row per frame set: per slot id,cx,cy,cz,views,error,missed -- the track's identity (-1:
+                             the slot is free, or there is no tracker), the centre in world mm ('NaN' when empty), the
+                             cameras that support it (0 when empty), their mean reprojection error in pixels ('NaN'),
+                             the frame sets since the track's last match (-1: free, or no tracker) -- and last
+                             `dropped`, the detections of the frame set that found no slot; under a row of slot names
+                             and a row of column names when data3D_subject{k}.csv get their header.
+    It works with time_batch, streams, camera_mask, frame_format and frame_layout, and the files do not depend on
+    time_batch (below 8, as above) or streams.  The padding rows of a short last group pass through the tracker behind
+    the real ones: a SubjectTracker handed in is not where the recording ended once the call returns (reset() it before
+    it is used again).  Together with centers, output_2d, output_spread or output_triangulated: ValueError; so are
+    subject_params or track without max_subjects.  Calls without max_subjects are untouched."""
     import contextlib
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
     yuv = driver_format(frame_format, frame_spec, 3, frame_layout)
     tri_params = N.triangulation_params(output_triangulated)
     tail = 3 if tri_params is not None else 0                   # (points, views and error of the Triangulated3D, last)
+    subj_params, tracker = None, None
+    if max_subjects is not None:
+        clash = [name for name, on in (("centers", centers is not None), ("output_2d", output_2d),
+                                       ("output_spread", output_spread), ("output_triangulated", tri_params is not None))
+                 if on]
+        if clash:
+            raise ValueError("max_subjects does not combine with %s" % ", ".join(clash))
+        if subject_params is not None and not isinstance(subject_params, dict):
+            raise ValueError("subject_params must be a dict of detect_subjects' keywords, got %r" % (subject_params,))
+        subj_params = N.subjects_params(max_subjects, **(subject_params or {}))
+        tracker = _tracker(track, max_subjects)
+    elif subject_params is not None or track is not None:
+        raise ValueError("subject_params and track need max_subjects")
     run_mask, mask_iter = None, None
     if camera_mask is not None:
         C = cfg.HYBRIDNET.NUM_CAMERAS
@@ -263,10 +341,19 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             f = files.enter_context(open(os.path.join(output_dir, name), "w", newline=""))
             return csv.writer(f, delimiter=",", quotechar='"', quoting=csv.QUOTE_MINIMAL)
 
-        writer = open_csv("data3D.csv")
         names = getattr(cfg, "KEYPOINT_NAMES", [])
-        if len(names) == J:
-            create_header(writer, cfg)
+        writer, writers_subj, writer_tracks = None, [], None
+        if max_subjects is None:
+            writer = open_csv("data3D.csv")
+            if len(names) == J:
+                create_header(writer, cfg)
+        else:
+            writers_subj = [open_csv("data3D_subject%d.csv" % k) for k in range(max_subjects)]
+            writer_tracks = open_csv("subjects3D.csv")
+            if len(names) == J:
+                for w in writers_subj:
+                    create_header(w, cfg)
+                create_header_subjects(writer_tracks, max_subjects)
         writers_2d, writer_err = [], None
         if output_2d:
             from .predict2D import create_header as create_header_2d
@@ -349,6 +436,49 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                 ev = torch.cuda.Event()
                 ev.record()
             return res, ev
+
+        def emit_subjects(outs, real):
+            """outs: points (T,K,J,3), conf (T,K,J), valid (T,K), centers, views, error[, ids, missed, dropped]."""
+            pts, conf, valid, ctr, views, err = outs[:6]
+            ids, missed, dropped = outs[6:9] if tracker is not None else (None, None, None)
+            for t in range(real):
+                for k, w in enumerate(writers_subj):
+                    ok = int(valid[t, k]) != 0
+                    w.writerow(frame_row(pts[t, k] if ok else None, conf[t, k] if ok else None, J))
+                writer_tracks.writerow(subjects_row(ctr[t], views[t], err[t], None if ids is None else ids[t],
+                                                    None if ids is None else missed[t],
+                                                    0 if ids is None else dropped[t]))
+
+        def submit_subjects(x, slot, mask=None):
+            kw = {} if mask is None else {"camera_mask": mask}
+            if frame_layout is not None:
+                kw["frame_layout"] = frame_layout
+            if yuv:
+                kw["frame_format"] = frame_format
+
+            def written(outs):
+                # (members and slots stay on the device: no file holds them)
+                return tuple(outs[:5]) + (outs[6],) + ((outs[7], outs[9], outs[10]) if tracker is not None else ())
+
+            if hasattr(predictor, "native_streams"):
+                d = N.describe_shape(x.shape, x.dtype, (time_batch, None), frame_format if yuv else None, frame_layout)
+                msp = predictor.native_streams(d.height, d.width, time_batch, streams)
+                msp.set_calibration(*calib)
+                res = msp.forward_subjects(x, subj_params, tracker,
+                                           then=lambda outs: host_outputs(ring, slot, written(outs)), **kw)
+                return res, msp.last_event
+            # any object with forward_subjects
+            res = predictor.forward_subjects(x, *calib, max_subjects, tracker=tracker, **kw, **(subject_params or {}))
+            res = written(tuple(res[:3]) + tuple(res[3]) + (tuple(res[4]) if tracker is not None else ()))
+            ev = None
+            if x.is_cuda:
+                res = host_outputs(ring, slot, res)
+                ev = torch.cuda.Event()
+                ev.record()
+            return res, ev
+
+        if max_subjects is not None:
+            submit, emit = submit_subjects, emit_subjects
 
         pipe, key = None, None
         _end = object()

@@ -9,7 +9,8 @@ class Subjects(NamedTuple):
     views (T,K) int32 the number of cameras that support the subject (0 when empty); members (T,K,C) int32 the slot of
     the supporting peak of every camera or -1; error (T,K) the mean distance in full-frame pixels between the members'
     peaks and the projection of the centre (NaN when empty).  Subjects are ordered by (views descending, cost
-    ascending) within ONE frame set: subject k of frame set t and of t+1 are unrelated."""
+    ascending) within ONE frame set: subject k of frame set t and of t+1 are unrelated, unless a tracks.SubjectTracker put
+    them into slot order (detect_subjects(..., tracker=))."""
     centers: object
     views: object
     members: object
