@@ -774,6 +774,60 @@ int jh_predictor_triangulate_joints(jh_predictor* pr, const float* heat_all_dev,
                                     uint8_t* members_dev, float* error_dev, float* obs_dev /* optional */,
                                     void* stream);
 
+/* ---- per-joint camera masks: leave a camera out of the voxel gather for the joints it gets wrong (additive, ABI 4)
+ * The reprojection layer averages every joint's heat map over the cameras; a camera mask leaves a camera out for a
+ * whole frame set.  A joint mask jm (T,J,C) uint8 gives every joint a camera set of its own -- members (T,J,C) of
+ * jh_predictor_triangulate_joints is one.  With a(t,c) the camera mask of the call (1 when there is none):
+ *   e(t,j,c) = a(t,c) && jm[t][j][c] != 0,  n(t,j) = sum_c e(t,j,c);
+ *   fallback: n(t,j) == 0 -> e(t,j,.) = a(t,.), n(t,j) = sum_c a(t,c) -- an empty joint behaves as in the plain or
+ *   camera-masked forward; the padding channels J <= j < Jp have e = a;
+ *   vol[t][vox][j] = (sum over c ascending with e(t,j,c) of heat[t][c][tap(t,c,vox)][j]) / n(t,j): an fp32 sum from +0
+ *   in camera order, an IEEE division by (float)n as the camera-masked kernels divide (no camera at all: divisor 1, sums
+ *   0), then the /255 of the forward in its existing form; tap is the gather index of the existing kernels, virtual zero
+ *   border included.
+ * A heat value with e = 0 is selected out, not multiplied -- it may be NaN --, and a camera with e(t,.,c) = 0 for every
+ * channel is not loaded at all.  So: all ones is bit-equal to no joint mask; jm[t][j][c] = m[t][c] for all j is bit-equal
+ * to the camera-masked gather with m; a camera mask composes as jm & m; an all-zero jm is the plain result; rows of a
+ * batch are independent.  The joint-masked gather has the voxel-row form only (any even grid, up to 64 channels, up to 64
+ * cameras): where the plain gather runs its cube form the two are different kernels with the same indices and sum order.
+ * jh_predictor_set_joint_mask: the mode of every later whole-path forward of this predictor.  JH_JOINT_MASK_GIVEN copies
+ * joint_mask_dev (T,J,C) into a buffer of the predictor's own, on `stream`; JH_JOINT_MASK_CONSENSUS makes the forward run
+ * the three launches of jh_predictor_triangulate_joints between stage 2 and stage 3 -- on its own heat maps, with the
+ * call's camera mask, the centres stage 2 wrote and the calibration in force; params NULL = min_views 2, refine_radius 1,
+ * min_conf 0.1, max_error_px 8 -- and takes the members as the joint mask (an invalid frame set has no members and falls
+ * back), so V2V runs once, on the cleaned volume; JH_JOINT_MASK_OFF (mask and params ignored) returns to the plain
+ * forward.  While the mode is not off every whole-path forward entry runs plain launches: there is no graph slot for the
+ * form, the captured graphs stay untouched and replay again once the mode is off.  Spread, centres, camera masks and
+ * per-frame-set calibration compose unchanged.  The buffers are allocated by the first call with a mode that is not off
+ * -- never by jh_predictor_create, and jh_predictor_device_bytes does not count them --, which must not be made inside a
+ * stream capture.  A bad mode, a NULL mask with GIVEN, out-of-range params, more than 64 cameras or cameras that are not
+ * all local: non-zero, jh_last_error() set, nothing enqueued, the mode unchanged.
+ * jh_predictor_get_joint_mask: the effective sets e as cameras_out (T,J,C) uint8 and n as count_out (T,J) int32 (either
+ * may be NULL) of the last joint-masked forward / stage 3 (rows t0 .. t0+T3-1 each), copied on `stream`.
+ * jh_predictor_stage_3d_joint_masked: jh_predictor_stage_3d_masked (mask_dev (T,C) or NULL) with joint_mask_dev (T,J,C),
+ * rows t0 .. t0+T3-1 read in place.  A caller gets the consensus in the staged path by calling
+ * jh_predictor_triangulate_joints between its stages.  The gather's workspace is the predictor's: joint-masked stage-3
+ * calls of one predictor are ordered on one stream.
+ * jh_reproject_forward_joint_masked: the operator alone, with jh_reproject_forward's conventions (T = 1, padded NCHW
+ * in, NCDHW out, not divided by 255): mask_dev (cams) uint8 or NULL, joint_mask_dev (joints,cams) uint8; workspace of
+ * jh_reproject_joint_masked_workspace_bytes. */
+#define JH_JOINT_MASK_OFF 0
+#define JH_JOINT_MASK_GIVEN 1
+#define JH_JOINT_MASK_CONSENSUS 2
+int jh_predictor_set_joint_mask(jh_predictor* pr, int mode, const uint8_t* joint_mask_dev /* (T,J,C) or NULL */,
+                                const jh_joints3d_params* params /* NULL = defaults */, void* stream);
+int jh_predictor_get_joint_mask(jh_predictor* pr, uint8_t* cameras_out_dev, int32_t* count_out_dev, void* stream);
+int jh_predictor_stage_3d_joint_masked(jh_predictor* pr, const float* heat_all_dev, int t0,
+                                       const uint8_t* mask_dev /* or NULL */, const uint8_t* joint_mask_dev,
+                                       float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
+int64_t jh_reproject_joint_masked_workspace_bytes(int cams, int joints, int hs, int grid_size);
+int jh_reproject_forward_joint_masked(const float* heatmaps_padded_dev, int cams, int joints, int hs,
+                                      const int32_t* center3d_dev, const int32_t* center_hm_dev,
+                                      const float* cam_dev, const float* intr_dev, const float* dist_dev,
+                                      int grid_size, float grid_spacing, const uint8_t* mask_dev /* or NULL */,
+                                      const uint8_t* joint_mask_dev, float* vol_dev, void* workspace_dev,
+                                      int64_t workspace_bytes, void* stream);
+
 /* HybridNetBackbone.forward: crops (T,C,3,B,B) normalised NCHW dev, center_hm
  * (T,C,2) int32, center3d (T,3) int32 -> heatmap_final (T,J,Gh,Gh,Gh) optional,
  * heatmaps_padded (T,C,J,hs,hs) optional, points (T,J,3), conf (T,J). */

@@ -14,4 +14,5 @@ from .sensor_surface import SensorSurface  # noqa: E402,F401 -- likewise
 from .spread import Spread3D  # noqa: E402,F401 -- likewise
 from .subjects import Subjects  # noqa: E402,F401 -- likewise
 from .triangulated import Triangulated3D  # noqa: E402,F401 -- likewise
+from .joint_mask import JointMask  # noqa: E402,F401 -- likewise
 from .tracks import SubjectTracker, Tracks  # noqa: E402,F401 -- likewise (a SubjectTracker loads it when it is made)

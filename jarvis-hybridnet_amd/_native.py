@@ -227,6 +227,13 @@ _SIGS = {
                                          c_void_p]),
     "jh_predictor_triangulate_joints": (c_int, [c_void_p, c_void_p, c_int, c_void_p,
                                                 ctypes.POINTER(Joints3dParamsStruct)] + [c_void_p] * 6),
+    "jh_predictor_set_joint_mask": (c_int, [c_void_p, c_int, c_void_p, ctypes.POINTER(Joints3dParamsStruct), c_void_p]),
+    "jh_predictor_get_joint_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_predictor_stage_3d_joint_masked": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 6),
+    "jh_reproject_joint_masked_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "jh_reproject_forward_joint_masked": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_int64, c_void_p]),
     "jh_joint_argmax_all_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "jh_op_joint_argmax_all": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p]),
@@ -655,6 +662,37 @@ def triangulation_params(value):
             raise ValueError(lib().jh_last_error().decode())
         return value
     raise ValueError("return_triangulated must be True or come from _native.joints3d_params, got %r" % (value,))
+
+
+JOINT_MASK_OFF, JOINT_MASK_GIVEN, JOINT_MASK_CONSENSUS = 0, 1, 2       # JH_JOINT_MASK_* of include/jarvis_hip.h
+
+
+def joint_mask(value, T, J, C):
+    """A joint_mask argument checked (jh_predictor_set_joint_mask) -> None, (JOINT_MASK_GIVEN, mask) or
+    (JOINT_MASK_CONSENSUS, params).  None stays None.  A bool or integer tensor (or array / sequence) of shape (T,J,C)
+    -- (J,C) too when T == 1 --, host or device, nonzero = camera c counts for joint j of frame set t: made a contiguous
+    uint8 tensor of (T,J,C) with values 0 / 1 on the device it is on (Triangulated3D.members of one call is a joint_mask
+    of the next).  'consensus' or True: the members of the forward's own per-joint consensus, with the library's
+    default parameters; a dict of joints3d_params() keywords, or what joints3d_params() made: with those.  Anything
+    else -- False, another string, a floating dtype, another shape -- raises ValueError."""
+    if value is None:
+        return None
+    if value is True or (isinstance(value, str) and value == "consensus"):
+        return JOINT_MASK_CONSENSUS, joints3d_params()
+    if isinstance(value, (dict, Joints3dParamsStruct)):
+        return JOINT_MASK_CONSENSUS, triangulation_params(value)
+    if value is False or isinstance(value, str):
+        raise ValueError("joint_mask must be None, a (%d, %d, %d) bool / integer tensor, 'consensus' / True, or the "
+                         "parameters of joints3d_params; got %r" % (T, J, C, value))
+    if not torch.is_tensor(value):
+        try:
+            value = torch.as_tensor(value)
+        except Exception as e:                              # noqa: BLE001 -- ragged / non-numeric sequences
+            raise ValueError("joint_mask must be a bool or integer tensor or sequence of shape (%d, %d, %d): %s"
+                             % (T, J, C, e))
+    if T == 1 and tuple(value.shape) == (J, C):
+        value = value.unsqueeze(0)
+    return JOINT_MASK_GIVEN, camera_mask(value, (T, J, C), "joint_mask")
 
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16x3_wide": 2}

@@ -6,6 +6,7 @@ import torch
 
 from . import _native as N
 from . import arch
+from .joint_mask import JointMask
 from .spread import Spread3D  # noqa: F401 -- the name the forwards return
 from .subjects import Subjects
 from .tracks import check_tracker
@@ -49,6 +50,7 @@ class NativePredictor:
         self.device_bytes = N.lib().jh_predictor_device_bytes(self.handle)
         self._centred = False                        # centres are in force (set_centers)
         self._spread = False                         # the 3D stage runs the spread form of its tail (set_spread)
+        self._joint_masked = False                   # a joint mask is in force (set_joint_mask)
 
     def close(self):
         if getattr(self, "handle", None) and N is not None and N._lib is not None:
@@ -133,6 +135,35 @@ class NativePredictor:
             cov = out.cov
         return Spread3D(cov, peak, mass)
 
+    # ---- per-joint camera masks --------------------------------------------
+    def set_joint_mask(self, joint_mask):
+        """joint_mask: what _native.joint_mask made, or None.  From now on every forward of this predictor gathers every
+        joint's voxel volume from that joint's own cameras (jh_predictor_set_joint_mask; a given mask is copied on the
+        current stream; the first such call allocates the buffers: not inside a stream capture) and runs plain
+        launches; None: back to the plain forward and its graph replay."""
+        if joint_mask is None:
+            if self._joint_masked:
+                N.check(N.lib().jh_predictor_set_joint_mask(self.handle, N.JOINT_MASK_OFF, None, None, N.stream()))
+                self._joint_masked = False
+            return
+        mode, what = joint_mask
+        if mode == N.JOINT_MASK_GIVEN:
+            dev = what.to("cuda", non_blocking=True)
+            N.check(N.lib().jh_predictor_set_joint_mask(self.handle, mode, N.ptr(dev), None, N.stream()))
+            dev.record_stream(torch.cuda.current_stream())      # (copied by the call: free once it is enqueued)
+        else:
+            N.check(N.lib().jh_predictor_set_joint_mask(self.handle, mode, None, ctypes.byref(what), N.stream()))
+        self._joint_masked = True
+
+    def joint_mask(self):
+        """The effective camera sets of the last joint-masked forward / stage_3d -> JointMask of device tensors, copied
+        on the current stream (jh_predictor_get_joint_mask)."""
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = JointMask(torch.empty((self.T, self.J, self.C), device=dev, dtype=torch.uint8),
+                        torch.empty((self.T, self.J), device=dev, dtype=torch.int32))
+        N.check(N.lib().jh_predictor_get_joint_mask(self.handle, N.ptr(out.cameras), N.ptr(out.count), N.stream()))
+        return out
+
     def debug_v2v(self, device):
         """The V2V output of the last 3D chunk, (T3,J,Gh,Gh,Gh): what the soft-argmax tail read (jh_predictor_debug_v2v)."""
         Gh = int(self.cfg.roi_cube_size / self.cfg.grid_spacing) // 2
@@ -142,7 +173,7 @@ class NativePredictor:
 
     # ---- single-GPU forward ----------------------------------------------
     def forward(self, frames, out=None, frame_format=None, camera_mask=None, frame_layout=None, centers=None,
-                return_spread=False):
+                return_spread=False, joint_mask=None):
         """frames (T,C,3,H,W) fp32 RGB, or (T,C,H,W,3) uint8 BGR as decoded, or with frame_format 'i420' / 'nv12'
         (T,C,3H/2,W) uint8 YUV 4:2:0 -> points (T,J,3), conf (T,J), valid (T) int32.  frame_format None: the
         dtype decides between fp32 RGB and uint8 BGR; 'bgr' requires uint8 BGR.
@@ -154,18 +185,22 @@ class NativePredictor:
         centers (T,3): this call runs from these centres (set_centers); None: it detects -- centres set earlier are
         cleared first.
         return_spread: the Spread3D of this call follows valid: (points, conf, valid, spread).  The flag is set before
-        the call (set_spread) and decides for this call alone; points, conf and valid keep their bits."""
+        the call (set_spread) and decides for this call alone; points, conf and valid keep their bits.
+        joint_mask (_native.joint_mask: a (T,J,C) mask, 'consensus', or joints3d_params keywords): every joint's
+        voxel volume is averaged over that joint's own cameras and the call's JointMask comes last; None: the plain
+        forward -- a joint mask set earlier is cleared first."""
         return self._forward(self._describe(frames, frame_format, frame_layout), out,
-                             N.camera_mask(camera_mask, (self.T, self.C)), N.centers(centers, self.T), return_spread)
+                             N.camera_mask(camera_mask, (self.T, self.C)), N.centers(centers, self.T), return_spread,
+                             N.joint_mask(joint_mask, self.T, self.J, self.C))
 
-    def forward_images(self, frames, out=None, camera_mask=None, centers=None, return_spread=False):
+    def forward_images(self, frames, out=None, camera_mask=None, centers=None, return_spread=False, joint_mask=None):
         """forward() on T * C separately placed images: `frames` what _native.frame_images made of the flat list
         (index t * C + c) (jh_predictor_forward_images).  The images are read where they lie; nothing is gathered."""
         if len(frames.images) != self.T * self.C:
             raise ValueError("expected %d images (time_batch * num_cameras), got %d" % (self.T * self.C,
                                                                                          len(frames.images)))
         return self._forward(frames, out, N.camera_mask(camera_mask, (self.T, self.C)), N.centers(centers, self.T),
-                             return_spread)
+                             return_spread, N.joint_mask(joint_mask, self.T, self.J, self.C))
 
     def _describe(self, frames, frame_format=None, frame_layout=None):
         """Raw pointers cross the C ABI: refuse anything whose bytes would be misread (_native.describe_frames for
@@ -173,12 +208,15 @@ class NativePredictor:
         return N.describe_frames(frames, (self.T, self.Cloc), frame_format, frame_layout,
                                  (self.cfg.img_h, self.cfg.img_w), error=RuntimeError, in_place=True)
 
-    def _forward(self, frames, out, mask, centers=None, spread=False):
+    def _forward(self, frames, out, mask, centers=None, spread=False, joint_mask=None):
         """The forward of checked frames (a _native.Frames) with a checked mask (_native.camera_mask) or None, and
         checked centres (_native.centers) or None = detect.  spread: the call runs the spread form and its Spread3D
-        follows the three outputs."""
+        follows the three outputs.  joint_mask: what _native.joint_mask made, or None = the plain forward; the call's
+        JointMask comes last."""
         dev = frames.device
         self.set_spread(spread)
+        if joint_mask is not None or self._joint_masked:
+            self.set_joint_mask(joint_mask)
         if centers is not None or self._centred:
             self.set_centers(centers)
         if out is None:
@@ -190,7 +228,8 @@ class NativePredictor:
         N.call_forward("jh_predictor", self.handle, frames, mask, out)
         if mask is not None and mask.is_cuda:
             mask.record_stream(torch.cuda.current_stream())     # (free once the call is enqueued)
-        return tuple(out) + (self.spread(),) if spread else out
+        res = tuple(out) + (self.spread(),) if spread else out
+        return tuple(res) + (self.joint_mask(),) if joint_mask is not None else res
 
     # ---- camera-sharded stages -------------------------------------------
     def stage_center(self, frames, det):
@@ -226,7 +265,20 @@ class NativePredictor:
                              % (self.T, self.C))
         return camera_mask
 
-    def stage_3d(self, heat_all, t0, points, conf, valid, camera_mask=None):
+    def stage_3d(self, heat_all, t0, points, conf, valid, camera_mask=None, joint_mask=None):
+        """joint_mask: a contiguous (T,J,C) uint8 DEVICE tensor, rows t0 .. t0+T3-1 read in place (kept alive by the
+        caller until the stream has passed the call; all cameras local): the joint-masked gather
+        (jh_predictor_stage_3d_joint_masked); read the effective sets with joint_mask()."""
+        if joint_mask is not None:
+            if not (torch.is_tensor(joint_mask) and joint_mask.is_cuda and joint_mask.dtype == torch.uint8
+                    and joint_mask.is_contiguous() and tuple(joint_mask.shape) == (self.T, self.J, self.C)):
+                raise ValueError("the staged calls take joint_mask as a contiguous (%d, %d, %d) uint8 device tensor"
+                                 % (self.T, self.J, self.C))
+            mask = self._device_mask(camera_mask) if camera_mask is not None else None
+            N.check(N.lib().jh_predictor_stage_3d_joint_masked(
+                self.handle, N.ptr(heat_all), t0, N.ptr(mask), N.ptr(joint_mask), N.ptr(points), N.ptr(conf),
+                N.ptr(valid), N.stream()))
+            return
         if camera_mask is not None:
             mask = self._device_mask(camera_mask)
             N.check(N.lib().jh_predictor_stage_3d_masked(self.handle, N.ptr(heat_all), t0, N.ptr(mask), N.ptr(points),
@@ -448,12 +500,14 @@ class MultiStreamPredictor:
         self._calib_of[i] = (self._calib, self._calib_refs)       # the tensors live as long as their key is compared
 
     def forward(self, frames, out=None, then=None, frame_format=None, camera_mask=None, return_2d=False,
-                frame_layout=None, centers=None, return_spread=False, return_triangulated=False):
+                frame_layout=None, centers=None, return_spread=False, return_triangulated=False, joint_mask=None):
         """return_2d: the five tensors of NativePredictor.views2d for this batch are appended to the outputs
         (points, conf, valid, points2D, confidences2D, reprojections, errors, used).
         return_spread: the three tensors of the batch's Spread3D (cov (T,J,3,3), peak, mass) are appended behind them.
         return_triangulated (True or what _native.joints3d_params made): the five tensors of the batch's Triangulated3D
-        (NativePredictor.triangulate_joints) are appended last.
+        (NativePredictor.triangulate_joints) are appended behind them.
+        joint_mask (as NativePredictor.forward): the two tensors of the batch's JointMask (cameras, count) are appended
+        last.
         `then(outputs)`, when given, runs inside the batch's stream context right behind the forward and
         before its event is recorded (the drivers enqueue the device->host copy of the results there); its
         return value replaces the outputs.  frame_format, camera_mask, frame_layout: as NativePredictor.forward.
@@ -464,6 +518,8 @@ class MultiStreamPredictor:
         camera_mask = N.camera_mask(camera_mask, (p0.T, p0.C))
         centers = N.centers(centers, p0.T)
         tri_params = N.triangulation_params(return_triangulated)
+        if joint_mask is not None:
+            joint_mask = N.joint_mask(joint_mask, p0.T, p0.J, p0.C)
         i = self._next
         self._next = (i + 1) % len(self.preds)
         s = self.streams[i]
@@ -477,7 +533,10 @@ class MultiStreamPredictor:
             t.record_stream(s)
         with torch.cuda.stream(s):
             self._frames_calibration(i)
-            res = self.preds[i]._forward(described, out, camera_mask, centers, return_spread)
+            res = self.preds[i]._forward(described, out, camera_mask, centers, return_spread,
+                                         **({} if joint_mask is None else {"joint_mask": joint_mask}))
+            if joint_mask is not None:
+                res, jm = res[:-1], tuple(res[-1])
             if return_spread:
                 res, spread = res[:3], tuple(res[3])
             if return_2d:
@@ -486,6 +545,8 @@ class MultiStreamPredictor:
                 res = tuple(res) + spread
             if tri_params is not None:
                 res = tuple(res) + tuple(self.preds[i].triangulate_joints(camera_mask=camera_mask, params=tri_params))
+            if joint_mask is not None:
+                res = tuple(res) + jm
             if then is not None:
                 res = then(res)
             ev = torch.cuda.Event(enable_timing=self.timing)

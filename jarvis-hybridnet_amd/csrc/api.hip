@@ -247,6 +247,45 @@ int jh_reproject_forward(const float* heatmaps_padded_dev, int cams, int joints,
   return launch_from_channel_last(w.vol, vol_dev, s);
 }
 
+// (the plain operator's pieces first, then the gather's channel sets and counts)
+static size_t carve_reproject_joint(Carver& c, int cams, int joints, int hs, int g, ReproWs* w, JointSets* js) {
+  carve_reproject(c, cams, joints, hs, g, w);
+  js->sets = c.take<unsigned long long>((size_t)cams);
+  js->ncam = c.take<int>((size_t)cpad(joints));
+  return c.off;
+}
+
+int64_t jh_reproject_joint_masked_workspace_bytes(int cams, int joints, int hs, int grid_size) {
+  Carver c(nullptr, 0);
+  ReproWs w;
+  JointSets js;
+  return (int64_t)carve_reproject_joint(c, cams, joints, hs, grid_size, &w, &js);
+}
+
+int jh_reproject_forward_joint_masked(const float* heatmaps_padded_dev, int cams, int joints, int hs,
+                                      const int32_t* center3d_dev, const int32_t* center_hm_dev,
+                                      const float* cam_dev, const float* intr_dev, const float* dist_dev,
+                                      int grid_size, float grid_spacing, const uint8_t* mask_dev,
+                                      const uint8_t* joint_mask_dev, float* vol_dev, void* workspace_dev,
+                                      int64_t workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(workspace_dev && workspace_bytes >= 0, "workspace (see jh_reproject_joint_masked_workspace_bytes)");
+  JH_REQUIRE(grid_size > 0 && grid_size % 2 == 0, "grid size must be even");
+  JH_REQUIRE(joint_mask_dev, "jh_reproject_forward_joint_masked: null joint mask");
+  JH_REQUIRE(cams >= 1 && cams <= 64 && joints >= 1 && joints <= 64, "jh_reproject_forward_joint_masked: 1 .. 64 "
+             "cameras and joints");
+  Carver c(workspace_dev, (size_t)workspace_bytes);
+  ReproWs w;
+  JointSets js;
+  carve_reproject_joint(c, cams, joints, hs, grid_size, &w, &js);
+  JH_REQUIRE(c.fits(), "workspace smaller than jh_reproject_joint_masked_workspace_bytes()");
+  if (launch_to_channel_last(heatmaps_padded_dev, w.heat, s)) return 1;
+  if (launch_reproject_joint_masked(Calib{cam_dev, intr_dev, dist_dev, /*fs=*/0}, center3d_dev, center_hm_dev, w.heat.p,
+                                    w.coarse, w.vol.p, nullptr, 1, cams, grid_size, grid_spacing, hs, joints, w.heat.Cp,
+                                    /*heat_pad=*/1, /*div255=*/0, mask_dev, joint_mask_dev, js, s)) return 1;
+  return launch_from_channel_last(w.vol, vol_dev, s);
+}
+
 int64_t jh_softargmax_workspace_bytes(int t, int joints, int gh) {
   Carver c(nullptr, 0);
   SoftWs w;
@@ -522,6 +561,8 @@ struct Call {
   const void* frames = nullptr;              // contiguous frames; per-image: the device table (never dereferenced here)
   FrameSource fs;
   const unsigned char* mask = nullptr;       // [T][C] device bytes, nullptr = no mask (the plain kernels)
+  // [T][J][C] device bytes, nullptr = no joint mask: stage 3 runs the joint-masked gather (nets.h: JointSets)
+  const unsigned char* joint_mask = nullptr;
   // what the launches read the frame pointer(s) through: the per-image table, the one-pointer cell of a forward that
   // is being captured, or nullptr = `frames` itself
   const void* const* cell = nullptr;
@@ -631,6 +672,18 @@ struct jh_predictor {
   SoftargmaxSpread spread;
   float *sp_cov = nullptr, *sp_peak = nullptr, *sp_mass = nullptr;
   size_t spread_bytes = 0;
+  // Per-joint camera masks (jh_predictor_set_joint_mask).  jm_mode: JH_JOINT_MASK_*; while it is not off the whole-path
+  // forward runs eagerly and gives stage 3 jm_buf [T][J][C] -- the caller's mask (GIVEN), or the members of the
+  // consensus over its own heat maps, written between stage 2 and stage 3 with jm_params (CONSENSUS; jm_points /
+  // jm_views / jm_error take the consensus' other outputs).  jm_sets: the workspace of the gather for one 3D chunk and,
+  // in eff [T][J][C] / cnt [T][J], the effective sets of the last joint-masked stage 3, rows t0 .. t0+T3-1.
+  // All of it allocated by the first call that asks (joint_mask_workspace), never by jh_predictor_create.
+  int jm_mode = 0;
+  unsigned char* jm_buf = nullptr;
+  JointSets jm_sets;
+  Joints3dParams jm_params{};
+  float *jm_points = nullptr, *jm_error = nullptr;
+  int* jm_views = nullptr;
   ~jh_predictor() {
     for (auto& g : gslot) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (gstream) (void)hipStreamDestroy(gstream);
@@ -643,11 +696,22 @@ struct jh_predictor {
     const double g3 = (double)G * G * G;
     // algorithmic traffic of the gather: every heatmap byte once in, the volume once out
     // (under a mask as for all cameras: an upper bound, the unmasked cameras' heatmaps are what is read)
-    JH_PROF(call.mask ? "reproject_gather_masked" : "reproject_gather", 0.0,
-            4.0 * T3 * ((double)C * Hh * Hh * J + g3 * J),
-            launch_reproject(calib_at(t0), cur().c3i + t0 * 3, cur().chm + t0 * C * 2, heat_all, coarse, v2v->input.p,
-                             nullptr, T3, C, G, cfg.grid_spacing, hs, Jp, /*heat_pad=*/0, /*div255=*/1,
-                             call.mask ? call.mask + (size_t)t0 * C : nullptr, s, layout));
+    if (call.joint_mask) {
+      // (the sets of the chunk, then the gather; the effective sets land in rows t0 .. of eff / cnt)
+      JointSets js = jm_sets;
+      js.eff += (size_t)t0 * J * C; js.cnt += (size_t)t0 * J;
+      JH_PROF("reproject_gather_joint_masked", 0.0, 4.0 * T3 * ((double)C * Hh * Hh * J + g3 * J),
+              launch_reproject_joint_masked(calib_at(t0), cur().c3i + t0 * 3, cur().chm + t0 * C * 2, heat_all, coarse,
+                                            v2v->input.p, nullptr, T3, C, G, cfg.grid_spacing, hs, J, Jp, /*heat_pad=*/0,
+                                            /*div255=*/1, call.mask ? call.mask + (size_t)t0 * C : nullptr,
+                                            call.joint_mask + (size_t)t0 * J * C, js, s, layout));
+    } else {
+      JH_PROF(call.mask ? "reproject_gather_masked" : "reproject_gather", 0.0,
+              4.0 * T3 * ((double)C * Hh * Hh * J + g3 * J),
+              launch_reproject(calib_at(t0), cur().c3i + t0 * 3, cur().chm + t0 * C * 2, heat_all, coarse, v2v->input.p,
+                               nullptr, T3, C, G, cfg.grid_spacing, hs, Jp, /*heat_pad=*/0, /*div255=*/1,
+                               call.mask ? call.mask + (size_t)t0 * C : nullptr, s, layout));
+    }
     if (v2v->run(s)) return 1;
     SoftargmaxSpread sp = spread;
     if (spread_on) {
@@ -995,10 +1059,21 @@ int jh_predictor_stage_3d_blocks(jh_predictor* pr, const float* heat_blocks_dev,
                        conf_dev, valid_dev, &lay);
 }
 
+// the three launches of jh_predictor_triangulate_joints (defined with it, below)
+static int triangulate_joints_launches(jh_predictor* pr, const float* heat_all_dev, int t0, const unsigned char* mask_dev,
+                                       const Joints3dParams& jp, float* points_dev, int* views_dev,
+                                       unsigned char* members_dev, float* error_dev, float* obs_dev, hipStream_t s);
+
 static int forward_eager(jh_predictor* pr, const Call& call, float* points_dev, float* conf_dev, int32_t* valid_dev) {
   // (centres supplied by the caller: stage 1 does not run at all)
   if (!pr->centers_on && stage_center_impl(pr, call, pr->det_all)) return 1;
   if (stage_keypoints_impl(pr, call, pr->det_all, nullptr)) return 1;
+  // JH_JOINT_MASK_CONSENSUS: the members of the per-joint consensus over the heat maps stage 2 has just written -- the
+  // call's camera mask, the centre set stage 2 wrote and the calibration in force -- become the joint mask of stage 3
+  // (an invalid frame set has no members: its joints fall back)
+  if (call.joint_mask && pr->jm_mode == JH_JOINT_MASK_CONSENSUS &&
+      triangulate_joints_launches(pr, pr->kp->heat.p, 0, call.mask, pr->jm_params, pr->jm_points, pr->jm_views,
+                                  pr->jm_buf, pr->jm_error, pr->j3_obs, call.s)) return 1;
   return stage_3d_impl(pr, call, pr->kp->heat.p, 0, points_dev, conf_dev, valid_dev);
 }
 
@@ -1062,11 +1137,17 @@ static int forward_impl(jh_predictor* pr, const void* frames_dev, const FrameSou
   if (mask_dev)
     JH_CHECK_HIP(hipMemcpyAsync(pr->mask_buf, mask_dev, (size_t)pr->T * pr->C, hipMemcpyDeviceToDevice,
                                 static_cast<hipStream_t>(stream)));
-  const Call call = make_call(frames_dev, fs, stream, mask_dev ? pr->mask_buf : nullptr);
+  Call call = make_call(frames_dev, fs, stream, mask_dev ? pr->mask_buf : nullptr);
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
   JH_REQUIRE(pr->T3 == pr->T, "forward needs time_batch_3d == time_batch");
   JH_REQUIRE(frames_dev && points_dev && conf_dev, "null frame / output pointer");
   pr->slot = 0;                               // (the whole-path forward and its captured graph: centre set 0)
+  // a joint mask in force (jh_predictor_set_joint_mask): plain launches, no graph slot of its own -- the captured
+  // graphs stay as they are and replay again once the mode is off
+  if (pr->jm_mode != JH_JOINT_MASK_OFF) {
+    call.joint_mask = pr->jm_buf;
+    return forward_eager(pr, call, points_dev, conf_dev, valid_dev);
+  }
   // per-launch profiling needs the launches one by one; a caller that is itself capturing this
   // stream gets the plain launches too (its graph then holds them)
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1182,6 +1263,15 @@ static int scan_workspace(jh_predictor* pr, hipStream_t s, const char* what) {
   return 0;
 }
 
+// The scan's partials and, with own_obs, the predictor's own observation buffer [T3 * C][J][3] of the per-joint
+// triangulation: each allocated by the first call that needs it.
+static int triangulate_joints_workspace(jh_predictor* pr, hipStream_t s, bool own_obs, const char* what) {
+  if (scan_workspace(pr, s, what)) return 1;
+  if (own_obs && !pr->j3_obs &&
+      first_call_alloc(pr->mem, s, (size_t)pr->T3 * pr->C * pr->J * 3 * sizeof(float), what, &pr->j3_obs)) return 1;
+  return 0;
+}
+
 extern "C" {
 
 int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, const float* points_dev,
@@ -1262,21 +1352,25 @@ int jh_predictor_triangulate_joints(jh_predictor* pr, const float* heat_all_dev,
   if (joints3d_params(params, &jp)) return 1;
   JH_REQUIRE(points_dev && views_dev && members_dev && error_dev, "jh_predictor_triangulate_joints: null output pointer");
   JH_REQUIRE(t0 >= 0 && t0 + pr->T3 <= pr->T, "frame range of the joint triangulation");
-  const int N = pr->T3 * pr->C;
   if (!heat_all_dev) {
     JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "the predictor's own heat maps hold all cameras only when "
                "all cameras are local");
     heat_all_dev = pr->kp->heat.p + (size_t)t0 * pr->C * pr->Hh * pr->Hh * pr->Jp;
   }
-  const char* what = "the first jh_predictor_triangulate_joints call of a predictor allocates its workspace: make it "
-                     "outside a stream capture";
-  if (scan_workspace(pr, s, what)) return 1;
   // (the observations go straight into the caller's buffer when there is one; the predictor's own, allocated by the
   // first call that brings none, otherwise)
-  if (!obs_dev) {
-    if (!pr->j3_obs && first_call_alloc(pr->mem, s, (size_t)N * pr->J * 3 * sizeof(float), what, &pr->j3_obs)) return 1;
-    obs_dev = pr->j3_obs;
-  }
+  if (triangulate_joints_workspace(pr, s, !obs_dev, "the first jh_predictor_triangulate_joints call of a predictor "
+                                   "allocates its workspace: make it outside a stream capture")) return 1;
+  return triangulate_joints_launches(pr, heat_all_dev, t0, mask_dev, jp, points_dev, views_dev, members_dev, error_dev,
+                                     obs_dev ? obs_dev : pr->j3_obs, s);
+}
+
+}  // extern "C"
+
+static int triangulate_joints_launches(jh_predictor* pr, const float* heat_all_dev, int t0, const unsigned char* mask_dev,
+                                       const Joints3dParams& jp, float* points_dev, int* views_dev,
+                                       unsigned char* members_dev, float* error_dev, float* obs_dev, hipStream_t s) {
+  const int N = pr->T3 * pr->C;
   JH_PROF("joint_argmax_all", 0.0, 4.0 * N * pr->Hh * pr->Hh * pr->Jp,
           launch_joint_argmax_all(heat_all_dev, pr->v2d_max, pr->v2d_idx, N, pr->Hh, pr->Hh, pr->J, pr->Jp, s));
   const int slices = joint_argmax_all_shape(N, pr->Hh, pr->Hh, pr->Jp).slices;
@@ -1291,6 +1385,87 @@ int jh_predictor_triangulate_joints(jh_predictor* pr, const float* heat_all_dev,
           launch_joints3d(obs_dev, pr->calib_at(t0), points_dev, views_dev, members_dev, error_dev, pr->T3, pr->C,
                           pr->J, jp.min_views, jp.min_conf, jp.max_error_px, s));
   return 0;
+}
+
+// ---- per-joint camera masks (nets.h: JointSets)
+// Everything a joint-masked stage 3 of this predictor needs beyond the caller's mask, ONE allocation made by the first
+// call that asks: the gather's sets and counts for a 3D chunk, the effective sets and counts of a time batch, the
+// predictor's own mask [T][J][C] and the consensus' other outputs.
+static int joint_mask_workspace(jh_predictor* pr, hipStream_t s, const char* what) {
+  if (pr->jm_buf) return 0;
+  const size_t T = pr->T, T3 = pr->T3, J = pr->J, C = pr->C, Jp = pr->Jp;
+  auto pad = [](size_t n) { return (n + 255) / 256 * 256; };
+  const size_t b_sets = pad(T3 * C * 8), b_ncam = pad(T3 * Jp * 4), b_cnt = pad(T * J * 4), b_eff = pad(T * J * C);
+  const size_t b_pts = pad(T * J * 12), b_tj = pad(T * J * 4);
+  char* base = nullptr;
+  if (first_call_alloc(pr->mem, s, b_sets + b_ncam + b_cnt + 2 * b_eff + b_pts + 2 * b_tj, what, &base)) return 1;
+  pr->jm_sets.sets = reinterpret_cast<unsigned long long*>(base); base += b_sets;
+  pr->jm_sets.ncam = reinterpret_cast<int*>(base); base += b_ncam;
+  pr->jm_sets.cnt = reinterpret_cast<int*>(base); base += b_cnt;
+  pr->jm_sets.eff = reinterpret_cast<unsigned char*>(base); base += b_eff;
+  pr->jm_points = reinterpret_cast<float*>(base); base += b_pts;
+  pr->jm_error = reinterpret_cast<float*>(base); base += b_tj;
+  pr->jm_views = reinterpret_cast<int*>(base); base += b_tj;
+  pr->jm_buf = reinterpret_cast<unsigned char*>(base);       // (set last: the workspace is there)
+  return 0;
+}
+
+extern "C" {
+
+int jh_predictor_set_joint_mask(jh_predictor* pr, int mode, const uint8_t* joint_mask_dev,
+                                const jh_joints3d_params* params, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(pr, "jh_predictor_set_joint_mask: null predictor");
+  JH_REQUIRE(mode >= JH_JOINT_MASK_OFF && mode <= JH_JOINT_MASK_CONSENSUS, "jh_predictor_set_joint_mask: mode must be "
+             "JH_JOINT_MASK_OFF, JH_JOINT_MASK_GIVEN or JH_JOINT_MASK_CONSENSUS");
+  if (mode == JH_JOINT_MASK_OFF) {            // (the buffers stay for the next joint-masked call)
+    pr->jm_mode = mode;
+    return 0;
+  }
+  JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "jh_predictor_set_joint_mask needs all cameras local");
+  JH_REQUIRE(pr->C <= 64, "jh_predictor_set_joint_mask: at most 64 cameras");
+  JH_REQUIRE(mode != JH_JOINT_MASK_GIVEN || joint_mask_dev, "jh_predictor_set_joint_mask: JH_JOINT_MASK_GIVEN needs "
+             "a mask");
+  const jh_joints3d_params defaults{2, 1, 0.1f, 8.f};
+  Joints3dParams jp;
+  if (mode == JH_JOINT_MASK_CONSENSUS && joints3d_params(params ? params : &defaults, &jp)) return 1;
+  const char* what = "the first jh_predictor_set_joint_mask call of a predictor allocates its buffers: make it outside "
+                     "a stream capture";
+  if (joint_mask_workspace(pr, s, what)) return 1;
+  if (mode == JH_JOINT_MASK_CONSENSUS) {
+    if (triangulate_joints_workspace(pr, s, true, what)) return 1;
+    pr->jm_params = jp;
+  } else {
+    JH_CHECK_HIP(hipMemcpyAsync(pr->jm_buf, joint_mask_dev, (size_t)pr->T * pr->J * pr->C, hipMemcpyDeviceToDevice, s));
+  }
+  pr->jm_mode = mode;
+  return 0;
+}
+
+int jh_predictor_get_joint_mask(jh_predictor* pr, uint8_t* cameras_out_dev, int32_t* count_out_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(pr, "jh_predictor_get_joint_mask: null predictor");
+  JH_REQUIRE(pr->jm_buf, "jh_predictor_get_joint_mask: no joint-masked call was made (jh_predictor_set_joint_mask, "
+             "jh_predictor_stage_3d_joint_masked)");
+  const size_t n = (size_t)pr->T * pr->J;
+  if (cameras_out_dev)
+    JH_CHECK_HIP(hipMemcpyAsync(cameras_out_dev, pr->jm_sets.eff, n * pr->C, hipMemcpyDeviceToDevice, s));
+  if (count_out_dev)
+    JH_CHECK_HIP(hipMemcpyAsync(count_out_dev, pr->jm_sets.cnt, n * sizeof(int), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+int jh_predictor_stage_3d_joint_masked(jh_predictor* pr, const float* heat_all_dev, int t0, const uint8_t* mask_dev,
+                                       const uint8_t* joint_mask_dev, float* points_dev, float* conf_dev,
+                                       int32_t* valid_dev, void* stream) {
+  JH_REQUIRE(pr && joint_mask_dev, "jh_predictor_stage_3d_joint_masked: null predictor / joint mask");
+  JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "joint-masked stage 3 needs all cameras local");
+  JH_REQUIRE(pr->C <= 64, "joint-masked stage 3: at most 64 cameras");
+  if (joint_mask_workspace(pr, static_cast<hipStream_t>(stream), "the first joint-masked call of a predictor allocates "
+                           "its buffers: make it outside a stream capture")) return 1;
+  Call call = stage3_call(stream, mask_dev);
+  call.joint_mask = joint_mask_dev;
+  return stage_3d_impl(pr, call, heat_all_dev, t0, points_dev, conf_dev, valid_dev);
 }
 
 // ---- subject identity across frame sets (csrc/tracks.h)

@@ -63,6 +63,15 @@ struct HeatLayout {
   size_t block_stride = 0, frame_stride = 0;
 };
 
+// The workspace of the joint-masked voxel gather (nets.h: launch_reproject_joint_masked), device pointers: sets [T][C]
+// one bit per channel, ncam [T][Jp]; eff [T][J][C] bytes and cnt [T][J], optional, the same for a caller to read.
+struct JointSets {
+  unsigned long long* sets = nullptr;
+  int* ncam = nullptr;
+  unsigned char* eff = nullptr;
+  int* cnt = nullptr;
+};
+
 // The calibration a launch reads, shared by all frames or one per frame (jh_predictor_set_calibration_frames): frame t
 // of a launch reads cam + (t * fs + c) * 12, intr + (t * fs + c) * 9, dist + (t * fs + c) * 5.  Nothing else differs
 // between the two forms.  (repro_coarse_kernel takes it by value: the fields keep their order.)

@@ -111,12 +111,20 @@ constexpr int kCamBatch = 1;
 
 // MASK (nets.h): cameras with mask[t][c] == 0 are skipped -- their heatmaps are never loaded -- and the mean
 // divides by the number of cameras left.
-template <int Q, bool MASK>
+// JOINT (launch_reproject_joint_masked): every channel has a camera set of its own.  sets[t][c] holds one bit per
+// channel -- bit j: camera c counts for channel j of frame t --, ncam[t][j] the number of cameras of channel j, both
+// written by repro_joint_sets_kernel with the fallback of an empty channel applied.  A camera whose set is 0 is skipped
+// like a masked one; of a loaded camera a lane SELECTS the values of its quad's four channels (never multiplies: a value
+// that is selected out may be NaN), and every channel divides by its own count.
+enum GatherMask { kMaskNone = 0, kMaskCamera = 1, kMaskJoint = 2 };
+template <int Q, int MK>
 __device__ __forceinline__ void repro_gather_body(
     const float2* __restrict__ coarse, const float* __restrict__ heat, float* __restrict__ vol,
     int* __restrict__ idx_out, int C, int G, int hs, int Jp, int heat_pad, int div255, int ci_n,
     int cj_n, FastDiv fgh, FastDiv frows, FastDiv fcjn, FastDiv fbpp, HeatLayout lay,
-    const unsigned char* __restrict__ mask) {
+    const unsigned char* __restrict__ mask, const unsigned long long* __restrict__ sets = nullptr,
+    const int* __restrict__ ncam = nullptr) {
+  constexpr bool MASK = MK == kMaskCamera, JOINT = MK == kMaskJoint;
   extern __shared__ __attribute__((aligned(16))) float2 ctab[];   // [C][ci_n][cj_n][Gh]
   const BlockId bid = xcd_block();             // consecutive planes share heatmap regions
   const int t = bid.y;
@@ -186,6 +194,11 @@ __device__ __forceinline__ void repro_gather_body(
     if constexpr (MASK) {
       if (mask[(size_t)t * C + cb] == 0) continue;            // (uniform)
     }
+    unsigned long long cset = 0;                              // (uniform: a scalar load)
+    if constexpr (JOINT) {
+      cset = sets[(size_t)t * C + cb];
+      if (cset == 0) continue;
+    }
     int src[kCamBatch];
 #pragma unroll
     for (int cc = 0; cc < kCamBatch; ++cc) {
@@ -230,7 +243,14 @@ __device__ __forceinline__ void repro_gather_body(
     for (int q = 0; q < Q; ++q)
 #pragma unroll
       for (int cc = 0; cc < kCamBatch; ++cc) {     // camera order = the reference's sum order
-        acc[q].x += h[q][cc].x; acc[q].y += h[q][cc].y; acc[q].z += h[q][cc].z; acc[q].w += h[q][cc].w;
+        if constexpr (JOINT) {
+          // the four bits of this lane's channel quad; a channel that is not in the set adds +0
+          const unsigned bits = (unsigned)(cset >> (((q * 64 + lane) % Q) * 4));
+          acc[q].x += (bits & 1u) ? h[q][cc].x : 0.f; acc[q].y += (bits & 2u) ? h[q][cc].y : 0.f;
+          acc[q].z += (bits & 4u) ? h[q][cc].z : 0.f; acc[q].w += (bits & 8u) ? h[q][cc].w : 0.f;
+        } else {
+          acc[q].x += h[q][cc].x; acc[q].y += h[q][cc].y; acc[q].z += h[q][cc].z; acc[q].w += h[q][cc].w;
+        }
       }
   }
   // mean over cameras, then the /255 of hybridnet/model.py:72: two IEEE divisions per value in the
@@ -264,8 +284,15 @@ __device__ __forceinline__ void repro_gather_body(
     const int vsrc = item / Q, quad = item % Q;
     if (wave_vox0 + vsrc < vox_end) {
       float4 r;
-      r.x = mean(acc[q].x); r.y = mean(acc[q].y);
-      r.z = mean(acc[q].z); r.w = mean(acc[q].w);
+      if constexpr (JOINT) {
+        // (a channel without any camera: its sum is 0, it divides by 1)
+        const int4 n = *reinterpret_cast<const int4*>(ncam + (size_t)t * Jp + quad * 4);
+        r.x = __fdiv_rn(acc[q].x, (float)max(n.x, 1)); r.y = __fdiv_rn(acc[q].y, (float)max(n.y, 1));
+        r.z = __fdiv_rn(acc[q].z, (float)max(n.z, 1)); r.w = __fdiv_rn(acc[q].w, (float)max(n.w, 1));
+      } else {
+        r.x = mean(acc[q].x); r.y = mean(acc[q].y);
+        r.z = mean(acc[q].z); r.w = mean(acc[q].w);
+      }
       if (div255) {
         r.x = divc(r.x, 255.f, r255); r.y = divc(r.y, 255.f, r255);
         r.z = divc(r.z, 255.f, r255); r.w = divc(r.w, 255.f, r255);
@@ -280,8 +307,8 @@ __global__ __launch_bounds__(256) void repro_gather_kernel(
     const float2* __restrict__ coarse, const float* __restrict__ heat, float* __restrict__ vol,
     int* __restrict__ idx_out, int C, int G, int hs, int Jp, int heat_pad, int div255, int ci_n,
     int cj_n, FastDiv fgh, FastDiv frows, FastDiv fcjn, FastDiv fbpp, HeatLayout lay) {
-  repro_gather_body<Q, false>(coarse, heat, vol, idx_out, C, G, hs, Jp, heat_pad, div255, ci_n, cj_n, fgh, frows, fcjn,
-                              fbpp, lay, nullptr);
+  repro_gather_body<Q, kMaskNone>(coarse, heat, vol, idx_out, C, G, hs, Jp, heat_pad, div255, ci_n, cj_n, fgh, frows,
+                                  fcjn, fbpp, lay, nullptr);
 }
 
 template <int Q>
@@ -290,8 +317,46 @@ __global__ __launch_bounds__(256) void repro_gather_masked_kernel(
     int* __restrict__ idx_out, int C, int G, int hs, int Jp, int heat_pad, int div255, int ci_n,
     int cj_n, FastDiv fgh, FastDiv frows, FastDiv fcjn, FastDiv fbpp, HeatLayout lay,
     const unsigned char* __restrict__ mask) {
-  repro_gather_body<Q, true>(coarse, heat, vol, idx_out, C, G, hs, Jp, heat_pad, div255, ci_n, cj_n, fgh, frows, fcjn,
-                             fbpp, lay, mask);
+  repro_gather_body<Q, kMaskCamera>(coarse, heat, vol, idx_out, C, G, hs, Jp, heat_pad, div255, ci_n, cj_n, fgh, frows,
+                                    fcjn, fbpp, lay, mask);
+}
+
+template <int Q>
+__global__ __launch_bounds__(256) void repro_gather_joint_kernel(
+    const float2* __restrict__ coarse, const float* __restrict__ heat, float* __restrict__ vol,
+    int* __restrict__ idx_out, int C, int G, int hs, int Jp, int heat_pad, int div255, int ci_n,
+    int cj_n, FastDiv fgh, FastDiv frows, FastDiv fcjn, FastDiv fbpp, HeatLayout lay,
+    const unsigned long long* __restrict__ sets, const int* __restrict__ ncam) {
+  repro_gather_body<Q, kMaskJoint>(coarse, heat, vol, idx_out, C, G, hs, Jp, heat_pad, div255, ci_n, cj_n, fgh, frows,
+                                   fcjn, fbpp, lay, nullptr, sets, ncam);
+}
+
+// The camera sets of the joint-masked gather, one wave per frame set, lane = channel (Jp <= 64, C <= 64).
+//   a(t,c) = mask[t][c] != 0 (no mask: 1);  e(t,j,c) = a(t,c) && jm[t][j][c] != 0 for j < J, a(t,c) for J <= j < Jp;
+//   a channel whose set is empty falls back to a(t,.).
+// -> sets[t][c] bit j = e(t,j,c), ncam[t][j] = the number of cameras of channel j; eff[t][j][c] (bytes) and cnt[t][j],
+//    j < J, the same for a caller to read (optional).
+__global__ __launch_bounds__(64) void repro_joint_sets_kernel(
+    const unsigned char* __restrict__ mask, const unsigned char* __restrict__ jm, unsigned long long* __restrict__ sets,
+    int* __restrict__ ncam, unsigned char* __restrict__ eff, int* __restrict__ cnt, int C, int J, int Jp) {
+  const int t = blockIdx.x, j = threadIdx.x;
+  const unsigned char* row = jm + ((size_t)t * J + min(j, J - 1)) * C;
+  int n = 0, na = 0;
+  for (int c = 0; c < C; ++c) {
+    const bool a = !mask || mask[(size_t)t * C + c] != 0;
+    na += a;
+    n += a && (j >= J || row[c] != 0);
+  }
+  const bool fallback = n == 0;
+  for (int c = 0; c < C; ++c) {
+    const bool a = !mask || mask[(size_t)t * C + c] != 0;
+    const bool e = j < Jp && a && (fallback || j >= J || row[c] != 0);
+    const unsigned long long set = __builtin_amdgcn_ballot_w64(e);
+    if (j == 0) sets[(size_t)t * C + c] = set;
+    if (eff && j < J) eff[((size_t)t * J + j) * C + c] = e;
+  }
+  if (j < Jp) ncam[(size_t)t * Jp + j] = fallback ? na : n;
+  if (cnt && j < J) cnt[(size_t)t * J + j] = fallback ? na : n;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -826,11 +891,13 @@ static int launch_cube(const CubeArgs& a, int T, hipStream_t s, const unsigned c
               : launch_cube_kernel(repro_cube_kernel<Q, CI, NT>, big, grid, NT, lds, s, a);
 }
 
-// mask == nullptr: all cameras (the plain kernels); otherwise the masked kernels, which take at most 64 cameras
-int launch_reproject(const Calib& cal, const int* center3d, const int* center_hm, const float* heat, float2* coarse,
-                     float* vol, int* idx_out, int T, int C, int G, float spacing, int hs, int Jp, int heat_pad,
-                     int div255, const unsigned char* mask, hipStream_t s, const HeatLayout* layout) {
-  JH_REQUIRE(!mask || C <= 64, "at most 64 cameras");
+// mask == nullptr: all cameras (the plain kernels); otherwise the masked kernels, which take at most 64 cameras.
+// sets != nullptr: the joint-masked kernel (the voxel-row form alone) on sets / ncam of repro_joint_sets_kernel.
+static int reproject_impl(const Calib& cal, const int* center3d, const int* center_hm, const float* heat, float2* coarse,
+                          float* vol, int* idx_out, int T, int C, int G, float spacing, int hs, int Jp, int heat_pad,
+                          int div255, const unsigned char* mask, hipStream_t s, const HeatLayout* layout,
+                          const unsigned long long* sets, const int* ncam) {
+  JH_REQUIRE(!(mask || sets) || C <= 64, "at most 64 cameras");
   const int Gh = G / 2;
   const int Hst = hs - 2 + 2 * heat_pad;
   HeatLayout lay;                        // default: dense (T, C, Hh, Hh, Jp)
@@ -848,7 +915,7 @@ int launch_reproject(const Calib& cal, const int* center3d, const int* center_hm
   JH_CHECK_HIP(hipGetLastError());
   // cube form: G a multiple of 8 (the cubes' thickness; j and k may leave a ragged last cube: 72 = 4.5 x 16), at most
   // 32 channels (JH_REPRO_CUBE=0: the voxel-row form below; JH_REPRO_CUBE=16: only grids that are multiples of 16)
-  if (G % 8 == 0 && G >= 16 && Jp <= 32 && JH_ENV_KNOB("JH_REPRO_CUBE") != 0 &&
+  if (!sets && G % 8 == 0 && G >= 16 && Jp <= 32 && JH_ENV_KNOB("JH_REPRO_CUBE") != 0 &&
       (G % 16 == 0 || JH_ENV_KNOB("JH_REPRO_CUBE") != 16)) {
     CubeArgs ca{coarse, heat, vol, idx_out, C, G, hs, heat_pad, div255, 0, 0, lay};
     const int Q = Jp / 4;
@@ -880,8 +947,12 @@ int launch_reproject(const Calib& cal, const int* center3d, const int* center_hm
                        cj_n, make_fastdiv(Gh), make_fastdiv(ci_n * cj_n), make_fastdiv(cj_n), make_fastdiv(bpp), lay,
                        mask_arg...);
   };
-#define JH_RG(QV) \
-  case QV: mask ? launch_rows(repro_gather_masked_kernel<QV>, mask) : launch_rows(repro_gather_kernel<QV>); break;
+#define JH_RG(QV)                                                                            \
+  case QV:                                                                                   \
+    if (sets) launch_rows(repro_gather_joint_kernel<QV>, sets, ncam);                        \
+    else if (mask) launch_rows(repro_gather_masked_kernel<QV>, mask);                        \
+    else launch_rows(repro_gather_kernel<QV>);                                               \
+    break;
   switch (Jp / 4) {
     JH_RG(2) JH_RG(4) JH_RG(6) JH_RG(8) JH_RG(10) JH_RG(12) JH_RG(14) JH_RG(16)
     default: JH_REQUIRE(false, "unsupported joint count");
@@ -889,6 +960,27 @@ int launch_reproject(const Calib& cal, const int* center3d, const int* center_hm
 #undef JH_RG
   JH_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+int launch_reproject(const Calib& cal, const int* center3d, const int* center_hm, const float* heat, float2* coarse,
+                     float* vol, int* idx_out, int T, int C, int G, float spacing, int hs, int Jp, int heat_pad,
+                     int div255, const unsigned char* mask, hipStream_t s, const HeatLayout* layout) {
+  return reproject_impl(cal, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs, Jp, heat_pad, div255,
+                        mask, s, layout, nullptr, nullptr);
+}
+
+int launch_reproject_joint_masked(const Calib& cal, const int* center3d, const int* center_hm, const float* heat,
+                                  float2* coarse, float* vol, int* idx_out, int T, int C, int G, float spacing, int hs,
+                                  int J, int Jp, int heat_pad, int div255, const unsigned char* mask,
+                                  const unsigned char* joint_mask, const JointSets& js, hipStream_t s,
+                                  const HeatLayout* layout) {
+  JH_REQUIRE(joint_mask && js.sets && js.ncam, "joint mask and its workspace");
+  JH_REQUIRE(C >= 1 && C <= 64 && J >= 1 && J <= Jp && Jp <= 64, "joint-masked gather: at most 64 cameras and channels");
+  hipLaunchKernelGGL(repro_joint_sets_kernel, dim3(T), dim3(64), 0, s, mask, joint_mask, js.sets, js.ncam, js.eff, js.cnt,
+                     C, J, Jp);
+  JH_CHECK_HIP(hipGetLastError());
+  return reproject_impl(cal, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs, Jp, heat_pad, div255,
+                        nullptr, s, layout, js.sets, js.ncam);
 }
 
 }  // namespace jh

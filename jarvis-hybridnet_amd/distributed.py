@@ -125,10 +125,10 @@ class ShardedPredictor:
             self.trace.append((label, ev))
 
     def step(self, frames_local, frame_format=None, camera_mask=None, return_2d=False, frame_layout=None,
-             return_spread=False):
-        """frames_local (T, Cloc, 3, H, W) -> points (T,J,3), conf (T,J), valid (T).  camera_mask, frame_layout:
-        None only; return_2d, return_spread: False only."""
-        self.submit(frames_local, frame_format, camera_mask, return_2d, frame_layout, return_spread)
+             return_spread=False, joint_mask=None):
+        """frames_local (T, Cloc, 3, H, W) -> points (T,J,3), conf (T,J), valid (T).  camera_mask, frame_layout,
+        joint_mask: None only; return_2d, return_spread: False only."""
+        self.submit(frames_local, frame_format, camera_mask, return_2d, frame_layout, return_spread, joint_mask)
         return self.flush()
 
     # ---- pipelined form: the bulk exchange of time batch i runs under the CenterDetect
@@ -137,12 +137,15 @@ class ShardedPredictor:
     #     stage_center(i+1) || exchange(i)  ->  stage_3d(i) [second stream] || stage_keypoints(i+1)
     #     -> exchange(i+1) started asynchronously once stage_3d(i) has let go of the receive buffer
     def submit(self, frames_local, frame_format=None, camera_mask=None, return_2d=False, frame_layout=None,
-               return_spread=False):
+               return_spread=False, joint_mask=None):
         """Start time batch i+1; returns the results of batch i (None on the first call).  frame_format: None or
         'bgr' only -- the camera-sharded stages take fp32 RGB or uint8 BGR frames, not YUV 4:2:0.  camera_mask: None
         only -- per-frame camera masks are a single-GPU feature.  return_2d: False only -- so are the per-camera 2D views.
         frame_layout: None only -- so are described YUV surfaces and raw sensor surfaces.  return_spread: False only --
-        so is the per-joint 3D spread."""
+        so is the per-joint 3D spread.  joint_mask: None only -- so are per-joint camera masks."""
+        if joint_mask is not None:
+            raise ValueError("the camera-sharded path does not take a joint_mask: use "
+                             "JarvisPredictor3D.forward_batch(..., joint_mask=...) on one GPU")
         if return_spread:
             raise ValueError("the camera-sharded path does not return the per-joint 3D spread: use "
                              "JarvisPredictor3D.forward_batch(..., return_spread=True) on one GPU")

@@ -151,7 +151,7 @@ class JarvisPredictor3D(nn.Module):
         return None if m is None else m.unsqueeze(0)
 
     def forward(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None,
-                return_2d=False, centers=None, return_spread=False, return_triangulated=False):
+                return_2d=False, centers=None, return_spread=False, return_triangulated=False, joint_mask=None):
         """imgs (C,3,H,W) RGB in [0,1] -> (points3D (1,J,3), confidences (1,J)) or (None, None).
         return_2d: a third element, the per-camera `Views2D` of this frame set (leading dimension 1: 2D keypoints of
         every camera from the heat maps this forward computed anyway, the reprojections of the 3D keypoints and
@@ -182,7 +182,18 @@ class JarvisPredictor3D(nn.Module):
         window), with the cameras that disagree left out by a consensus over two-view triangulations -- the one 3D
         estimate that does not pass through the voxel cube: it still meets the rays of a limb outside ROI_CUBE_SIZE, it
         names the camera whose keypoint sits on a reflection (members), and it checks V2V independently of V2V.
-        points3D and confidences keep their bits; it composes with everything above."""
+        points3D and confidences keep their bits; it composes with everything above.
+        joint_mask: every joint's voxel volume is averaged over that joint's own cameras, so a camera whose keypoint
+        sits on a reflection or an occluder no longer drags that joint (it keeps counting for its good joints).  A
+        (J,C) bool / integer tensor, host or device (nonzero = camera c counts for joint j; the `members` of a
+        previous call's Triangulated3D is one); or 'consensus' / True: the members of this call's own per-joint
+        consensus, computed between KeypointDetect and the voxel gather with the library's default parameters, so V2V
+        runs once, on the cleaned volume; or a dict of _native.joints3d_params keywords, or what it made: the
+        consensus with those.  camera_mask composes as joint_mask & camera_mask; a joint left without a camera falls
+        back to the cameras of the call.  All ones gives the bits of the call without it.  The call runs plain
+        launches (no graph replay).  The last element, behind the Triangulated3D, is the `JointMask` of the frame set
+        (cameras (1,J,C), count (1,J): the sets that were used), or None with the others.  This says nothing about
+        trained networks: whether the cleaned volume gives better keypoints is the user's to measure."""
         mask = self._frame_mask(camera_mask)
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(imgs, (self.num_cameras,))
@@ -190,13 +201,14 @@ class JarvisPredictor3D(nn.Module):
         self.reproTool.intrinsicMatrices = intrinsicMatrices
         self.reproTool.distortionCoefficients = distortionCoefficients
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers, return_spread, return_triangulated)
+                         centers, return_spread, return_triangulated, joint_mask)
 
     def _run(self, frames, calib, mask, return_2d, single=False, centers=None, return_spread=False,
-             return_triangulated=False):
+             return_triangulated=False, joint_mask=None):
         """The forward of checked frames (a _native.Frames; single: one frame set, lead (C,)) with a checked mask and
         checked centres (_native.centers for the frames' time batch, or None), on the native predictor of their size:
-        nothing of the predictor is touched before this."""
+        nothing of the predictor is touched before this.  joint_mask: the argument as given (_native.joint_mask checks
+        it here, for the frames' time batch)."""
         check_native_seam(self)
         tri = N.triangulation_params(return_triangulated)   # (True: the defaults; None: not asked for)
         per_frame = False
@@ -205,18 +217,27 @@ class JarvisPredictor3D(nn.Module):
         else:
             # the batched forms take one calibration for the batch, (C,...), or one per frame set, (T,C,...)
             per_frame = N.calibration(tuple(calib), frames.lead[0], self.num_cameras)[0] == "frames"
+        jm = None
+        if joint_mask is not None:
+            jm = N.joint_mask(joint_mask, frames.lead[0], self.cfg.KEYPOINTDETECT.NUM_JOINTS, self.num_cameras)
         pr = self.native(frames.height, frames.width, time_batch=frames.lead[0])
         (pr.set_calibration_frames if per_frame else pr.set_calibration)(*calib)
-        # (return_spread decides for this call alone: the native predictor sets its flag, on or off, before it runs)
-        res = pr._forward(frames, None, mask, centers, *((True,) if return_spread else ()))
-        return self._single(pr, res, mask, return_2d, tri) if single else self._batch(pr, res, mask, return_2d, tri)
+        # (return_spread and joint_mask decide for this call alone: the native predictor sets its flags, on or off,
+        # before it runs)
+        res = pr._forward(frames, None, mask, centers, *((True,) if return_spread else ()),
+                          **({} if jm is None else {"joint_mask": jm}))
+        used = ()
+        if jm is not None:                                   # (the JointMask comes last, behind the Triangulated3D)
+            res, used = tuple(res[:-1]), (res[-1],)
+        return self._single(pr, res, mask, return_2d, tri, used) if single else \
+            self._batch(pr, res, mask, return_2d, tri, used)
 
     @staticmethod
-    def _single(pr, res, mask, return_2d, tri=None):
+    def _single(pr, res, mask, return_2d, tri=None, used=()):
         """The single-frame forms' return value: (points3D, confidences[, Views2D][, Spread3D][, Triangulated3D]), every
         element None when fewer than two cameras saw the subject (jarvis3D.py:157,187-190).  The 2D views and the
         triangulation (tri: its checked parameters) are enqueued behind the forward, before the one host
-        synchronisation (reading the validity flag).
+        synchronisation (reading the validity flag).  used: the call's JointMask, which comes last.
         Views2D are HybridNet's own 2D detections, on the crop around the projection of the TRIANGULATED centre;
         JarvisPredictor2D crops around each camera's own centre detection.  The two agree wherever the crops cover
         the subject; they are not bit-equal."""
@@ -224,12 +245,14 @@ class JarvisPredictor3D(nn.Module):
         extra = ((pr.views2d(points, camera_mask=mask),) if return_2d else ()) + tuple(res[3:])
         if tri is not None:
             extra += (pr.triangulate_joints(camera_mask=mask, params=tri),)
+        extra += tuple(used)
         if int(valid[0].item()) == 0:
             return (None, None) + (None,) * len(extra)
         return (points, conf) + extra
 
     def forward_uint8(self, imgs_bgr, cameraMatrices, intrinsicMatrices, distortionCoefficients, camera_mask=None,
-                      return_2d=False, centers=None, return_spread=False, return_triangulated=False):
+                      return_2d=False, centers=None, return_spread=False, return_triangulated=False,
+                      joint_mask=None):
         """imgs_bgr (C,H,W,3) uint8 BGR exactly as the video decoder delivers them
         (predict3D.py:72-78).  Same result as forward() on
         `imgs_bgr.float().permute(0,3,1,2)[:, [2,1,0]] / 255.` (predict3D.py:79-80); the
@@ -240,11 +263,11 @@ class JarvisPredictor3D(nn.Module):
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(imgs_bgr, (self.num_cameras,), "bgr")
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers, return_spread, return_triangulated)
+                         centers, return_spread, return_triangulated, joint_mask)
 
     def forward_yuv(self, frames, frame_format, cameraMatrices, intrinsicMatrices, distortionCoefficients,
                     camera_mask=None, return_2d=False, centers=None, return_spread=False,
-                    return_triangulated=False):
+                    return_triangulated=False, joint_mask=None):
         """frames (C,3H/2,W) uint8 YUV 4:2:0 as video decoders produce them natively, frame_format 'i420'
         (FFmpeg yuv420p: Y, U, V planes) or 'nv12' (Y plane, interleaved UV plane); H and W even.  Same result,
         bit for bit, as forward_uint8 on the BGR bytes of cv2.cvtColor(COLOR_YUV2BGR_I420 / _NV12) of each
@@ -256,11 +279,11 @@ class JarvisPredictor3D(nn.Module):
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(frames, (self.num_cameras,), N.yuv_format(frame_format))
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers, return_spread, return_triangulated)
+                         centers, return_spread, return_triangulated, joint_mask)
 
     def forward_surface(self, frames, surface, cameraMatrices, intrinsicMatrices, distortionCoefficients,
                         camera_mask=None, return_2d=False, centers=None, return_spread=False,
-                        return_triangulated=False):
+                        return_triangulated=False, joint_mask=None):
         """frames (C,image_stride) uint8: one YUV 4:2:0 image per camera, read in place through the YuvSurface
         `surface` (pitched decoder surfaces, I420 / YV12 / NV12 / NV21, BT.601 / BT.709, limited / full range), or one
         raw sensor image per camera through the SensorSurface `surface` (Mono8, or an 8-bit Bayer mosaic demosaiced
@@ -274,11 +297,11 @@ class JarvisPredictor3D(nn.Module):
         centers = N.centers(centers, 1)                      # (3,) -> (1,3) checked, or None
         frames = N.describe_frames(frames, (self.num_cameras,), None, N.surface(surface))
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), mask, return_2d, True,
-                         centers, return_spread, return_triangulated)
+                         centers, return_spread, return_triangulated, joint_mask)
 
     def forward_batch(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
                       camera_mask=None, return_2d=False, frame_layout=None, centers=None, return_spread=False,
-                      return_triangulated=False):
+                      return_triangulated=False, joint_mask=None):
         """Throughput form: imgs (T,C,3,H,W) fp32 RGB or (T,C,H,W,3) uint8 BGR,
         independent time steps -> points (T,J,3), confidences (T,J), valid (T) int32;
         no host synchronisation.  frame_format 'i420' / 'nv12': imgs (T,C,3H/2,W) uint8 YUV 4:2:0 (see
@@ -309,7 +332,10 @@ class JarvisPredictor3D(nn.Module):
         outputs keep their bits; it composes with everything above.
         return_triangulated: the `Triangulated3D` of the batch comes last (see forward()): points (T,J,3), views (T,J),
         members (T,J,C), error (T,J), observations (T,C,J,3); NaN / 0 rows where valid[t] = 0 and for a joint on which
-        fewer than min_views cameras agree.  Under per-frame-set calibration row t uses row t's calibration."""
+        fewer than min_views cameras agree.  Under per-frame-set calibration row t uses row t's calibration.
+        joint_mask: as forward(), (T,J,C) for a tensor; row t of the batch depends on row t of the mask alone, and an
+        invalid frame set is as in the plain call.  The `JointMask` of the batch (cameras (T,J,C), count (T,J)) comes
+        last.  `Triangulated3D.members` of one call is a valid joint_mask of the next."""
         if centers is not None:
             if not torch.is_tensor(imgs) or imgs.dim() < 1:
                 raise ValueError("imgs must be a tensor of time steps")
@@ -320,11 +346,12 @@ class JarvisPredictor3D(nn.Module):
             camera_mask = N.camera_mask(camera_mask, (imgs.shape[0], self.num_cameras))
         frames = N.describe_frames(imgs, (None, self.num_cameras), frame_format, frame_layout)
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d,
-                         centers=centers, return_spread=return_spread, return_triangulated=return_triangulated)
+                         centers=centers, return_spread=return_spread, return_triangulated=return_triangulated,
+                         joint_mask=joint_mask)
 
     def forward_images(self, images, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
                        frame_layout=None, camera_mask=None, return_2d=False, centers=None,
-                       return_spread=False, return_triangulated=False):
+                       return_spread=False, return_triangulated=False, joint_mask=None):
         """forward_batch on images that lie where their producers left them: `images` a sequence of C tensors (one
         frame set) or a sequence of T such sequences, each tensor ONE image -- fp32 (3,H,W); uint8 (H,W,3);
         frame_format 'i420' / 'nv12': uint8 (3H/2,W); frame_layout (a YuvSurface or a SensorSurface): 1-D uint8 of at
@@ -338,13 +365,14 @@ class JarvisPredictor3D(nn.Module):
         centers (T,3): as forward_batch.  With the same images in several rows and one centre per row, the rows of a
         batch are different subjects seen in the same frames (a detected batch finds the strongest one in every row).
         return_spread, return_triangulated: as forward_batch -- the Spread3D of the batch (covariance in mm^2, peak voxel
-        in mm and mass of every joint's heat map), then its Triangulated3D come last."""
+        in mm and mass of every joint's heat map), then its Triangulated3D come last.  joint_mask: as forward_batch;
+        its JointMask comes last of all."""
         frames = image_frames(self.num_cameras, images, frame_format, frame_layout)
         T = frames.lead[0]
         camera_mask = N.camera_mask(camera_mask, (T, self.num_cameras))
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d,
                          centers=N.centers(centers, T), return_spread=return_spread,
-                         return_triangulated=return_triangulated)
+                         return_triangulated=return_triangulated, joint_mask=joint_mask)
 
     def detect_subjects(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, max_subjects,
                         frame_format=None, frame_layout=None, camera_mask=None, images=False, return_peaks=False,
@@ -392,7 +420,7 @@ class JarvisPredictor3D(nn.Module):
 
     def forward_subjects(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, max_subjects,
                          frame_format=None, frame_layout=None, camera_mask=None, images=False, return_2d=False,
-                         return_spread=False, return_triangulated=False, tracker=None, **params):
+                         return_spread=False, return_triangulated=False, tracker=None, joint_mask=None, **params):
         """Several subjects in one time batch: detect_subjects, then one centred forward_batch (images=True:
         forward_images) per subject k on the same frames with centers=subjects.centers[:, k].
         -> points (T,K,J,3), confidences (T,K,J), valid (T,K) int32, subjects[, views][, spreads]: row (t, k) is row t
@@ -402,7 +430,9 @@ class JarvisPredictor3D(nn.Module):
         tracker (a tracks.SubjectTracker, see detect_subjects): the subjects are put into slot order first and the
         centred forwards run on the tracked centres, so k is a slot -- one animal -- in every output; the `Tracks` comes
         last.  Row (t, k) is then row (t, tracks.slots[t, k]) of the call without a tracker, bit for bit, and an invalid
-        row where the slot holds no detection (with coast=True: the forward at the track's predicted centre)."""
+        row where the slot holds no detection (with coast=True: the forward at the track's predicted centre).
+        joint_mask: passed to each centred forward (as forward_batch); a tuple of K JointMasks follows the other
+        per-subject tuples."""
         calib = (cameraMatrices, intrinsicMatrices, distortionCoefficients)
         subjects = self.detect_subjects(imgs, *calib, max_subjects, frame_format=frame_format, tracker=tracker,
                                         frame_layout=frame_layout, camera_mask=camera_mask, images=images, **params)
@@ -413,18 +443,18 @@ class JarvisPredictor3D(nn.Module):
         for k in range(max_subjects):
             kw = dict(frame_format=frame_format, frame_layout=frame_layout, camera_mask=camera_mask,
                       return_2d=return_2d, centers=subjects.centers[:, k], return_spread=return_spread,
-                      return_triangulated=return_triangulated)
+                      return_triangulated=return_triangulated, joint_mask=joint_mask)
             rows.append((self.forward_images if images else self.forward_batch)(imgs, *calib, **kw))
         out = tuple(torch.stack([r[i] for r in rows], 1) for i in range(3)) + (subjects,)
-        for i in range(3, len(rows[0])):             # (views, then spreads, then triangulations: one per subject)
+        for i in range(3, len(rows[0])):             # (views, spreads, triangulations, joint masks: one per subject)
             out += (tuple(r[i] for r in rows),)
         return out + tracks
 
     @staticmethod
-    def _batch(pr, res, mask, return_2d, tri=None):
-        # (points, conf, valid[, views][, spread][, triangulated]): the Spread3D, when asked for, is res[3]
+    def _batch(pr, res, mask, return_2d, tri=None, used=()):
+        # (points, conf, valid[, views][, spread][, triangulated][, joint mask]): the Spread3D, when asked for, is res[3]
         if return_2d:
             res = tuple(res[:3]) + (pr.views2d(res[0], camera_mask=mask),) + tuple(res[3:])
         if tri is not None:
             res = tuple(res) + (pr.triangulate_joints(camera_mask=mask, params=tri),)
-        return res
+        return tuple(res) + tuple(used) if used else res

@@ -185,7 +185,7 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                      distortionCoefficients, cfg, output_dir, params=None, time_batch=1, streams=1,
                      frame_spec=None, frame_format="bgr", camera_mask=None, output_2d=False, camera_names=None,
                      frame_layout=None, centers=None, output_spread=False, output_triangulated=False,
-                     max_subjects=None, subject_params=None, track=None):
+                     max_subjects=None, subject_params=None, track=None, joint_mask=None):
     """Run `predictor` over an iterable of multi-view frame sets -- (C,H,W,3) uint8 BGR
     arrays / tensors exactly as cv2 delivers them, or (C,3,H,W) fp32 RGB -- and write
     data3D.csv (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -291,16 +291,34 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     time_batch (below 8, as above) or streams.  The padding rows of a short last group pass through the tracker behind
     the real ones: a SubjectTracker handed in is not where the recording ended once the call returns (reset() it before
     it is used again).  Together with centers, output_2d, output_spread or output_triangulated: ValueError; so are
-    subject_params or track without max_subjects.  Calls without max_subjects are untouched."""
+    subject_params or track without max_subjects.  Calls without max_subjects are untouched.
+
+    joint_mask ('consensus' or True = the library's defaults, or what _native.joints3d_params made, or a dict of its
+    keywords): every forward is the joint-masked one (JarvisPredictor3D.forward_batch(..., joint_mask=)) -- per joint,
+    the cameras whose own 2D keypoint disagrees with the consensus of the others are left out of that joint's voxel
+    volume --, so data3D.csv holds the joint-masked keypoints, and `joint_cameras.csv` is written beside it: one row per
+    frame set, per joint count,cameras -- the number of cameras the joint was averaged over and their set as the decimal
+    sum of 2^c (rows of joint_mask.joint_cameras_row, the header of joint_mask.create_header_joint_cameras when
+    data3D.csv gets its header) --, 'NaN' x 2J for an invalid frame set.  It composes with time_batch, streams,
+    camera_mask, centers and the other outputs; a tensor-valued mask is not taken here, and together with max_subjects
+    it is a ValueError."""
     import contextlib
+    from ..joint_mask import create_header_joint_cameras, joint_cameras_row
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
     yuv = driver_format(frame_format, frame_spec, 3, frame_layout)
     tri_params = N.triangulation_params(output_triangulated)
-    tail = 3 if tri_params is not None else 0                   # (points, views and error of the Triangulated3D, last)
+    tail = 3 if tri_params is not None else 0                   # (points, views and error of the Triangulated3D ...)
+    jm_params = None
+    if joint_mask is not None:
+        if torch.is_tensor(joint_mask) or isinstance(joint_mask, (list, tuple)) or hasattr(joint_mask, "__array__"):
+            raise ValueError("predict3D_frames takes joint_mask='consensus' or the consensus' parameters, not a mask")
+        jm_params = N.joint_mask(joint_mask, 1, 1, 1)[1]
+    jm_tail = 2 if jm_params is not None else 0                 # (... then cameras and count of the JointMask, last)
     subj_params, tracker = None, None
     if max_subjects is not None:
         clash = [name for name, on in (("centers", centers is not None), ("output_2d", output_2d),
-                                       ("output_spread", output_spread), ("output_triangulated", tri_params is not None))
+                                       ("output_spread", output_spread), ("output_triangulated", tri_params is not None),
+                                       ("joint_mask", jm_params is not None))
                  if on]
         if clash:
             raise ValueError("max_subjects does not combine with %s" % ", ".join(clash))
@@ -375,8 +393,17 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             if len(names) == J:
                 create_header_triangulated(writer_tri, cfg)
 
+        writer_jm = None
+        if jm_params is not None:
+            writer_jm = open_csv("joint_cameras.csv")
+            if len(names) == J:
+                for row in create_header_joint_cameras(names):
+                    writer_jm.writerow(row)
+
         def emit(outs, real):
             pts, conf, valid = outs[:3]
+            if jm_params is not None:
+                outs, (jm_cams, jm_count) = outs[:-2], outs[-2:]
             for t in range(real):
                 ok = int(valid[t]) != 0
                 writer.writerow(frame_row(pts[t] if ok else None, conf[t] if ok else None, J))
@@ -386,6 +413,8 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                 if tri_params is not None:
                     tp, tv, te = outs[-3:]
                     writer_tri.writerow(triangulated_row(tp[t] if ok else None, tv[t], te[t], J))
+                if jm_params is not None:
+                    writer_jm.writerow(joint_cameras_row(jm_cams[t].tolist(), jm_count[t].tolist(), ok))
                 if output_2d:
                     p2d, c2d, _, err, used = outs[3:8]
                     for c, w in enumerate(writers_2d):
@@ -396,7 +425,10 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
 
         def written(outs):
             """The tensors of a batch that a file gets: the five of a Triangulated3D cut to points, views, error."""
-            return outs if tri_params is None else tuple(outs[:-5]) + (outs[-5], outs[-4], outs[-2])
+            if tri_params is None:
+                return outs
+            end = len(outs) - jm_tail
+            return tuple(outs[:end - 5]) + (outs[end - 5], outs[end - 4], outs[end - 2]) + tuple(outs[end:])
 
         def submit(x, slot, mask=None, centers=None):
             kw = {} if mask is None else {"camera_mask": mask}
@@ -408,6 +440,8 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                 kw["return_spread"] = True
             if tri_params is not None:
                 kw["return_triangulated"] = tri_params
+            if jm_params is not None:
+                kw["joint_mask"] = jm_params
             if frame_layout is not None:
                 kw["frame_layout"] = frame_layout
             if hasattr(predictor, "native_streams"):
@@ -423,8 +457,10 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             res = predictor.forward_batch(x, *calib, frame_format=frame_format, **kw) if yuv else \
                 predictor.forward_batch(x, *calib, **kw)
             tri = ()
+            if jm_params is not None:
+                res, tri = tuple(res[:-1]), tuple(res[-1])     # (the JointMask's two tensors go last)
             if tri_params is not None:
-                res, tri = tuple(res[:-1]), (res[-1].points, res[-1].views, res[-1].error)
+                res, tri = tuple(res[:-1]), (res[-1].points, res[-1].views, res[-1].error) + tri
             if output_spread:
                 res = tuple(res[:-1]) + tuple(res[-1])         # (..., Spread3D) -> its three tensors
             if output_2d:
