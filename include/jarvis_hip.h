@@ -336,11 +336,27 @@ int jh_predictor_forward_yuv(jh_predictor* pr, const uint8_t* frames_dev, int fo
  * jh_yuv_surface_check (no GPU needed) is the validation every entry point applies: h, w even and positive;
  * c_step 1 or 2; y_pitch >= w, c_pitch >= (w/2) * c_step; offsets >= 0; for c_step 2, |u_offset - v_offset| == 1
  * with min(u_offset, v_offset) and c_pitch even; every plane ends at or before image_stride; matrix and range
- * known; reserved 0.  Returns 0, or nonzero with jh_last_error() set.
+ * known; sample a known code (below).  Returns 0, or nonzero with jh_last_error() set.
+ * Samples wider than a byte (additive: the last word, `reserved` in earlier headers, is the sample code).
+ * JH_SAMPLE_U8 = 0 is every description above.  JH_SAMPLE_U16(shift), shift 0 .. 8: every Y, U and V sample is a
+ * little-endian 16-bit word and is reduced to a byte inside the fetch, byte = min(sample >> shift, 255); the
+ * conversion above then runs on the bytes, so the result equals, bit for bit, that of the 8-bit description of the
+ * reduced planes.  shift = bits - 8 is LSB-aligned data (yuv420p10le: 2, yuv420p12le: 4), shift = 8 MSB-aligned data
+ * (P010 / P012 / P016).  Truncation, not rounding: what a decoder's own 8-bit output of the same stream is not
+ * guaranteed to be, but what a shift on the host gives; no gain or gamma, and the network never sees more than 8 bits.
+ * Offsets and pitches stay in BYTES, c_step counts SAMPLES.  The rules for JH_SAMPLE_U16: every offset, pitch and
+ * image_stride even (every 16-bit load is aligned); y_pitch >= 2 w; c_pitch >= (w/2) * c_step * 2; for c_step 2,
+ * |u_offset - v_offset| == 2 with min(u_offset, v_offset) and c_pitch multiples of 4 (the pair is one 4-byte load
+ * where the image base is a multiple of 4, two 2-byte loads otherwise); every plane's last BYTE lies before
+ * image_stride.  The packed codes of jh_sensor_surface, and every other value, are refused.
  * jh_predictor_forward_surface: jh_predictor_forward_yuv through a description; mask_dev as in
  * jh_predictor_forward_masked, or NULL.  A graph-replaying predictor keeps one captured graph for this form (and
  * one for its masked form); a recording has one layout, so a call whose description differs from the recorded one
  * records again. */
+#define JH_SAMPLE_U8 0
+#define JH_SAMPLE_U16(shift) (0x100 | (shift))
+#define JH_SAMPLE_P10 0x200
+#define JH_SAMPLE_P12 0x300
 #define JH_YUV_BT601 0
 #define JH_YUV_BT709 1
 #define JH_YUV_LIMITED 0
@@ -353,7 +369,7 @@ typedef struct jh_yuv_surface {
   int32_t c_step;              /* 1: planar (I420, YV12); 2: semi-planar (NV12, NV21) */
   int32_t matrix;              /* JH_YUV_BT601 = 0, JH_YUV_BT709 = 1 */
   int32_t range;               /* JH_YUV_LIMITED = 0, JH_YUV_FULL = 1 */
-  int32_t reserved;            /* 0 */
+  int32_t sample;              /* JH_SAMPLE_U8 = 0 (the `reserved` word of earlier headers) or JH_SAMPLE_U16(shift) */
 } jh_yuv_surface;
 int jh_yuv_surface_check(const jh_yuv_surface* surface, int h, int w);
 int jh_predictor_forward_surface(jh_predictor* pr, const uint8_t* frames_dev, const jh_yuv_surface* surface,
@@ -381,7 +397,26 @@ int jh_predictor_forward_surface(jh_predictor* pr, const uint8_t* frames_dev, co
  * take the uint8 path unchanged: the result equals, bit for bit, jh_predictor_forward_u8 on the converted frames.
  * jh_sensor_surface_check (no GPU needed) is the validation every entry point applies: h, w positive; pattern
  * known; for a Bayer pattern h, w even and >= 4; pitch >= w; offset >= 0; offset + (h-1) * pitch + w <=
- * image_stride; reserved 0.  Returns 0, or nonzero with jh_last_error() set.
+ * image_stride; sample a known code (below).  Returns 0, or nonzero with jh_last_error() set.
+ * Samples wider than a byte (additive: the fifth word, `reserved` in earlier headers, is the sample code; pitch,
+ * offset and image_stride stay in bytes).  A sample is reduced to a byte inside the fetch, byte = min(sample >> shift,
+ * 255) -- the truncation a camera applies when its PixelFormat is switched from Mono12 to Mono8 --, and the bytes go
+ * the way described above: the result equals, bit for bit, that of the 8-bit description of the reduced bytes.
+ * Rounding, gain, black level, gamma or white-balance tables, and more than 8 bits for the network are not offered.
+ *   JH_SAMPLE_U8 = 0: one byte per sample, every description above.
+ *   JH_SAMPLE_U16(shift), shift 0 .. 8: raw(y, x) is the little-endian 16-bit word at offset + y * pitch + 2 x.
+ *     shift = bits - 8 is LSB-aligned data (Mono10 / 12 / 14 / 16, BayerXX10 / 12 / 16), shift = 8 MSB-aligned data;
+ *     a sample with bits above the declared depth saturates to 255.  offset, pitch and image_stride are even.
+ *   JH_SAMPLE_P10 / JH_SAMPLE_P12: GenICam PFNC 10p / 12p (Mono10p, Mono12p, BayerRG12p ...).  Every row is a
+ *     little-endian bit stream that starts at offset + y * pitch, at any byte; sample x occupies bits
+ *     [n x, n x + n) of it and the byte is its top 8 bits, bits [n x + n - 8, n x + n).  The unused high bits of a
+ *     row's last byte may hold anything.  The legacy GigE Vision Mono12Packed / Mono10Packed nibble order is ANOTHER
+ *     layout and has no code: unpack it first.
+ * With row_bytes(w) = w, 2 w, ceil(10 w / 8), ceil(12 w / 8): pitch >= row_bytes(w) and offset + (h-1) * pitch +
+ * row_bytes(w) <= image_stride.  Every other value of `sample` is refused.
+ * Per-image pointers (jh_predictor_forward_images and its like): an image of a JH_SAMPLE_U16 description, sensor or
+ * YUV, must be 2-byte aligned -- checked on the host as the 4-byte rule of fp32 images is: nothing is enqueued and
+ * jh_last_error() names the image; packed and 8-bit images may start anywhere.
  * jh_predictor_forward_sensor: mask_dev as in jh_predictor_forward_masked, or NULL; jh_predictor_views2d follows it
  * as it follows any forward.  A graph-replaying predictor keeps one captured graph for this form (and one for its
  * masked form); a call whose description differs from the recorded one records again. */
@@ -394,7 +429,7 @@ typedef struct jh_sensor_surface {
   int64_t image_stride;        /* bytes from image n to image n+1 (n = t * cameras + c) */
   int64_t offset, pitch;       /* raw(y, x) at offset + y * pitch + x */
   int32_t pattern;             /* JH_SENSOR_* */
-  int32_t reserved;            /* 0 */
+  int32_t sample;              /* JH_SAMPLE_* (the `reserved` word of earlier headers): 0 = one byte per sample */
 } jh_sensor_surface;
 int jh_sensor_surface_check(const jh_sensor_surface* surface, int h, int w);
 int jh_predictor_forward_sensor(jh_predictor* pr, const uint8_t* frames_dev, const jh_sensor_surface* surface,

@@ -34,7 +34,8 @@ class PredictorConfig(ctypes.Structure):
 
 
 class YuvSurfaceStruct(ctypes.Structure):
-    """jh_yuv_surface of include/jarvis_hip.h (built by yuv_surface.YuvSurface.struct())."""
+    """jh_yuv_surface of include/jarvis_hip.h (built by yuv_surface.YuvSurface.struct()).  The last field keeps the
+    name it had when it was spare: it is the header's `sample`, the JH_SAMPLE_* code (0 = one byte per sample)."""
     _fields_ = [("image_stride", ctypes.c_int64), ("y_offset", ctypes.c_int64), ("y_pitch", ctypes.c_int64),
                 ("u_offset", ctypes.c_int64), ("v_offset", ctypes.c_int64), ("c_pitch", ctypes.c_int64),
                 ("c_step", ctypes.c_int32), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32),
@@ -45,7 +46,8 @@ assert ctypes.sizeof(YuvSurfaceStruct) == 64
 
 
 class SensorSurfaceStruct(ctypes.Structure):
-    """jh_sensor_surface of include/jarvis_hip.h (built by sensor_surface.SensorSurface.struct())."""
+    """jh_sensor_surface of include/jarvis_hip.h (built by sensor_surface.SensorSurface.struct()).  `reserved` is the
+    header's `sample`, as in YuvSurfaceStruct."""
     _fields_ = [("image_stride", ctypes.c_int64), ("offset", ctypes.c_int64), ("pitch", ctypes.c_int64),
                 ("pattern", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 

@@ -375,30 +375,50 @@ int jh_reconstruct_point(const float* points2d_dev, const float* maxvals_dev, in
     if (_pf.on) _pf.end(s);                                    \
   } while (0)
 
+// A sample code (JH_SAMPLE_*) taken apart: kind 0 = one byte, else kSample* of preprocess.h; shift of the 16-bit words.
+// Any value that is no code -- 1 in particular, or a shift above 8 -- gives kind -1.
+struct SampleCode { int kind, shift; };
+static SampleCode sample_code(int32_t code) {
+  if (code == JH_SAMPLE_U8) return {0, 0};
+  if (code >= JH_SAMPLE_U16(0) && code <= JH_SAMPLE_U16(8)) return {kSampleU16, code & 0xff};
+  if (code == JH_SAMPLE_P10) return {kSampleP10, 2};
+  if (code == JH_SAMPLE_P12) return {kSampleP12, 4};
+  return {-1, 0};
+}
+
 // The one validation of a described YUV 4:2:0 surface of h x w images (include/jarvis_hip.h): every surface entry
 // point and jh_yuv_surface_check.  Host arithmetic only.  (__int128: a plane's end may not wrap for any int64 field.)
+// sb: bytes per sample; offsets and pitches are in bytes, c_step in samples.
 static int yuv_surface_check(const jh_yuv_surface* sp, int h, int w) {
   JH_REQUIRE(sp, "null jh_yuv_surface");
   const jh_yuv_surface& q = *sp;
   JH_REQUIRE(h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0, "YUV 4:2:0 frames need an even, positive height and width");
+  const SampleCode sc = sample_code(q.sample);
+  JH_REQUIRE(sc.kind == 0 || sc.kind == kSampleU16, "jh_yuv_surface.sample (the reserved word of earlier headers) must "
+             "be JH_SAMPLE_U8 or JH_SAMPLE_U16(shift) with shift 0 .. 8");
+  const int sb = sc.kind == kSampleU16 ? 2 : 1;
   JH_REQUIRE(q.c_step == 1 || q.c_step == 2, "jh_yuv_surface.c_step must be 1 (planar) or 2 (semi-planar)");
-  JH_REQUIRE(q.y_pitch >= w, "jh_yuv_surface.y_pitch is smaller than the width");
-  JH_REQUIRE(q.c_pitch >= (int64_t)(w / 2) * q.c_step, "jh_yuv_surface.c_pitch is smaller than a chroma row");
+  JH_REQUIRE(q.y_pitch >= (int64_t)w * sb, "jh_yuv_surface.y_pitch is smaller than the width");
+  JH_REQUIRE(q.c_pitch >= (int64_t)(w / 2) * q.c_step * sb, "jh_yuv_surface.c_pitch is smaller than a chroma row");
   JH_REQUIRE(q.y_offset >= 0 && q.u_offset >= 0 && q.v_offset >= 0 && q.image_stride >= 0,
              "jh_yuv_surface offsets must not be negative");
   if (q.c_step == 2) {
-    JH_REQUIRE(q.u_offset - q.v_offset == 1 || q.v_offset - q.u_offset == 1,
-               "jh_yuv_surface: semi-planar U and V are neighbouring bytes");
-    JH_REQUIRE((q.u_offset < q.v_offset ? q.u_offset : q.v_offset) % 2 == 0 && q.c_pitch % 2 == 0,
-               "jh_yuv_surface: a semi-planar chroma pair starts at an even offset and c_pitch is even");
+    JH_REQUIRE(q.u_offset - q.v_offset == sb || q.v_offset - q.u_offset == sb,
+               "jh_yuv_surface: semi-planar U and V are neighbouring samples");
+    JH_REQUIRE((q.u_offset < q.v_offset ? q.u_offset : q.v_offset) % (2 * sb) == 0 && q.c_pitch % (2 * sb) == 0,
+               "jh_yuv_surface: a semi-planar chroma pair starts at an even offset and c_pitch is even (16-bit "
+               "samples: multiples of 4)");
   }
-  const __int128 y_end = (__int128)q.y_offset + (__int128)(h - 1) * q.y_pitch + w;
-  const __int128 c_span = (__int128)(h / 2 - 1) * q.c_pitch + (__int128)(w / 2 - 1) * q.c_step + 1;
+  if (sb == 2)
+    JH_REQUIRE(q.image_stride % 2 == 0 && q.y_offset % 2 == 0 && q.y_pitch % 2 == 0 && q.u_offset % 2 == 0 &&
+                   q.v_offset % 2 == 0 && q.c_pitch % 2 == 0,
+               "jh_yuv_surface: 16-bit samples need even offsets, pitches and image_stride");
+  const __int128 y_end = (__int128)q.y_offset + (__int128)(h - 1) * q.y_pitch + (__int128)w * sb;
+  const __int128 c_span = (__int128)(h / 2 - 1) * q.c_pitch + ((__int128)(w / 2 - 1) * q.c_step + 1) * sb;
   JH_REQUIRE(y_end <= q.image_stride && q.u_offset + c_span <= q.image_stride && q.v_offset + c_span <= q.image_stride,
              "jh_yuv_surface: a plane ends beyond image_stride");
   JH_REQUIRE(q.matrix == JH_YUV_BT601 || q.matrix == JH_YUV_BT709, "jh_yuv_surface.matrix: unknown");
   JH_REQUIRE(q.range == JH_YUV_LIMITED || q.range == JH_YUV_FULL, "jh_yuv_surface.range: unknown");
-  JH_REQUIRE(q.reserved == 0, "jh_yuv_surface.reserved must be 0");
   return 0;
 }
 
@@ -414,11 +434,22 @@ static int frame_source(const jh_yuv_surface* sp, int h, int w, FrameSource* out
                                  {{16, 1220945, 1879825, 2215014, -223607, -558796},
                                   {0, 1048576, 1651297, 1945738, -196424, -490864}}};
   const int* c = k[q.matrix][q.range];
+  const auto fill = [&](YuvSurface& a) {
+    a.image_stride = q.image_stride; a.y_offset = q.y_offset; a.y_pitch = q.y_pitch;
+    a.u_offset = q.u_offset; a.v_offset = q.v_offset; a.c_pitch = q.c_pitch; a.c_step = q.c_step;
+    a.y0 = c[0]; a.cy = c[1]; a.cvr = c[2]; a.cub = c[3]; a.cug = c[4]; a.cvg = c[5];
+  };
+  // the sample code chooses the form: 16-bit samples are kSrcYuvWide, kernels of their own
+  if (const SampleCode sc = sample_code(q.sample); sc.kind == kSampleU16) {
+    SrcDesc<kSrcYuvWide> a;
+    fill(a);
+    a.shift = sc.shift;
+    out->fmt = kSrcYuvWide; out->desc = a;
+    return 0;
+  }
   SrcDesc<kSrcYuvSurface> a;
-  a.image_stride = q.image_stride; a.y_offset = q.y_offset; a.y_pitch = q.y_pitch;
-  a.u_offset = q.u_offset; a.v_offset = q.v_offset; a.c_pitch = q.c_pitch; a.c_step = q.c_step;
+  fill(a);
   a.pair = q.c_step == 2 && q.image_stride % 2 == 0;
-  a.y0 = c[0]; a.cy = c[1]; a.cvr = c[2]; a.cub = c[3]; a.cug = c[4]; a.cvg = c[5];
   out->fmt = kSrcYuvSurface; out->desc = a;
   return 0;
 }
@@ -433,11 +464,19 @@ static int sensor_surface_check(const jh_sensor_surface* sp, int h, int w) {
   if (q.pattern != JH_SENSOR_MONO)
     JH_REQUIRE(h % 2 == 0 && w % 2 == 0 && h >= 4 && w >= 4,
                "Bayer frames need an even height and width of at least 4");
-  JH_REQUIRE(q.pitch >= w, "jh_sensor_surface.pitch is smaller than the width");
+  const SampleCode sc = sample_code(q.sample);
+  JH_REQUIRE(sc.kind >= 0, "jh_sensor_surface.sample (the reserved word of earlier headers) must be JH_SAMPLE_U8, "
+             "JH_SAMPLE_U16(shift) with shift 0 .. 8, JH_SAMPLE_P10 or JH_SAMPLE_P12");
+  // bytes the w samples of a row occupy: w, 2 w, ceil(10 w / 8), ceil(12 w / 8)
+  const int64_t row = sc.kind == 0 ? w : sc.kind == kSampleU16 ? 2 * (int64_t)w
+                      : ((sc.kind == kSampleP10 ? 10 : 12) * (int64_t)w + 7) / 8;
+  JH_REQUIRE(q.pitch >= row, "jh_sensor_surface.pitch is smaller than the width (the bytes of a row of samples)");
   JH_REQUIRE(q.offset >= 0, "jh_sensor_surface.offset must not be negative");
-  JH_REQUIRE((__int128)q.offset + (__int128)(h - 1) * q.pitch + w <= q.image_stride,
+  JH_REQUIRE((__int128)q.offset + (__int128)(h - 1) * q.pitch + row <= q.image_stride,
              "jh_sensor_surface: the image ends beyond image_stride");
-  JH_REQUIRE(q.reserved == 0, "jh_sensor_surface.reserved must be 0");
+  if (sc.kind == kSampleU16)
+    JH_REQUIRE(q.offset % 2 == 0 && q.pitch % 2 == 0 && q.image_stride % 2 == 0,
+               "jh_sensor_surface: 16-bit samples need an even offset, pitch and image_stride");
   return 0;
 }
 
@@ -445,8 +484,19 @@ static int sensor_surface_check(const jh_sensor_surface* sp, int h, int w) {
 static int frame_source(const jh_sensor_surface* sp, int h, int w, FrameSource* out) {
   if (sensor_surface_check(sp, h, w)) return 1;
   const jh_sensor_surface& q = *sp;
+  const auto fill = [&](SensorSurface& a) {
+    a.image_stride = q.image_stride; a.offset = q.offset; a.pitch = q.pitch; a.pattern = q.pattern; a.h = h; a.w = w;
+  };
+  // the sample code chooses the form: anything wider than a byte is kSrcSensorWide, kernels of their own
+  if (const SampleCode sc = sample_code(q.sample); sc.kind != 0) {
+    SrcDesc<kSrcSensorWide> a;
+    fill(a);
+    a.kind = sc.kind; a.shift = sc.shift;
+    out->fmt = kSrcSensorWide; out->desc = a;
+    return 0;
+  }
   SrcDesc<kSrcSensor> a;
-  a.image_stride = q.image_stride; a.offset = q.offset; a.pitch = q.pitch; a.pattern = q.pattern; a.h = h; a.w = w;
+  fill(a);
   out->fmt = kSrcSensor; out->desc = a;
   return 0;
 }
@@ -487,10 +537,8 @@ static int call_source(const char* who, int format, const jh_yuv_surface* yuv, c
   if (format == JH_FRAME_SURFACE ? frame_source(yuv, h, w, out)
       : format == JH_FRAME_SENSOR ? frame_source(sensor, h, w, out)
                                   : frame_source(format, h, w, out)) return 1;
-  if (per_image && format == JH_FRAME_SURFACE) {
-    auto& d = std::get<SrcDesc<kSrcYuvSurface>>(out->desc);
-    d.pair = d.c_step == 2;
-  }
+  if (per_image)
+    if (auto* d = std::get_if<SrcDesc<kSrcYuvSurface>>(&out->desc)) d->pair = d->c_step == 2;
   out->per_image = per_image;
   return 0;
 }
@@ -508,13 +556,18 @@ static int first_call_alloc(Scratch& mem, hipStream_t s, size_t bytes, const cha
 // The host table of a per-image call checked and sent into the predictor's device table (allocated by the first such
 // call of a predictor) on the caller's stream.
 static int upload_images(Scratch& mem, const void*** table, const void* const* images_host, int n_images, int want,
-                         int format, hipStream_t s) {
+                         const FrameSource& fs, hipStream_t s) {
   JH_REQUIRE(images_host, "forward_images: null image table");
   JH_REQUIRE(n_images == want, "forward_images: n_images must be time_batch * num_cameras (2D predictor: time_batch)");
+  // 16-bit samples (a wide sensor surface of 16-bit words, every wide YUV surface) are loaded as aligned 2-byte words
+  const auto* sw = std::get_if<SrcDesc<kSrcSensorWide>>(&fs.desc);
+  const bool words = fs.fmt == kSrcYuvWide || (sw && sw->kind == kSampleU16);
   for (int i = 0; i < n_images; ++i) {
     JH_REQUIRE(images_host[i], "forward_images: a null image pointer");
-    JH_REQUIRE(format != JH_FRAME_RGB_F32 || reinterpret_cast<uintptr_t>(images_host[i]) % 4 == 0,
+    JH_REQUIRE(fs.fmt != kSrcRgbF32 || reinterpret_cast<uintptr_t>(images_host[i]) % 4 == 0,
                "forward_images: an fp32 image that is not 4-byte aligned");
+    JH_REQUIRE(!words || reinterpret_cast<uintptr_t>(images_host[i]) % 2 == 0,
+               "forward_images: image " + std::to_string(i) + " of 16-bit samples is not 2-byte aligned");
   }
   if (!*table && first_call_alloc(mem, s, (size_t)want * sizeof(void*), "the first forward_images call of a predictor "
                                   "allocates its pointer table: make it outside a stream capture", table)) return 1;
@@ -586,7 +639,7 @@ static Call stage3_call(void* stream, const unsigned char* mask = nullptr) {
 // caller-supplied centres (centers_on), which records no stage 1 -- a tracking loop that falls back to one detected
 // call between centred ones never re-records.  spread: the spread form of the tail (spread_on), which is another
 // recording -- a loop that alternates spread-on and spread-off calls never re-records either.
-constexpr int kGraphFmts = kSrcSensor + 1;
+constexpr int kGraphFmts = kSrcCount;
 struct ForwardForm {
   int fmt = 0;
   bool masked = false, per_image = false, centred = false, spread = false;
@@ -1215,7 +1268,7 @@ int jh_predictor_forward_images(jh_predictor* pr, const void* const* images_host
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
   FrameSource fs;
   if (call_source("forward_images", format, yuv, sensor, pr->cfg.img_h, pr->cfg.img_w, true, &fs)) return 1;
-  if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T * pr->C, format,
+  if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T * pr->C, fs,
                     static_cast<hipStream_t>(stream))) return 1;
   // (the launches read the table: `frames` itself is not dereferenced)
   return forward_impl(pr, pr->frames_table, fs, points_dev, conf_dev, valid_dev, stream, mask_dev);
@@ -1590,7 +1643,7 @@ int jh_predictor_detect_subjects(jh_predictor* pr, const void* frames_dev, const
   }
   const void* frames = frames_dev;
   if (images_host) {
-    if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, N, format, s)) return 1;
+    if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, N, fs, s)) return 1;
     frames = pr->frames_table;                // (the launches read the table: `frames` itself is not dereferenced)
   }
   // (plain launches with this call's frame pointer)
@@ -1757,7 +1810,7 @@ int jh_predictor2d_forward_images(jh_predictor2d* pr, const void* const* images_
   JH_REQUIRE(pr && points_dev && conf_dev, "bad argument");
   FrameSource fs;
   if (call_source("forward_images", format, yuv, sensor, pr->cfg.img_h, pr->cfg.img_w, true, &fs)) return 1;
-  if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T, format,
+  if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T, fs,
                     static_cast<hipStream_t>(stream))) return 1;
   return forward2d_impl(pr, make_call(pr->frames_table, fs, stream), points_dev, conf_dev, valid_dev);
 }

@@ -103,8 +103,8 @@ int launch_preprocess_crop(const void* frames, const FrameSource& src, const int
   return 0;
 }
 
-// A YUV 4:2:0 or raw sensor form (SRC 2 .. 5) -> [N][H][W][3] uint8 BGR through the pixel function the resize / crop
-// use (rgb8_px): the unit-test form of yuv420_px, yuv_surface_px and sensor_px.  One thread per output pixel; only
+// A YUV 4:2:0 or raw sensor form (SRC 2 .. 7) -> [N][H][W][3] uint8 BGR through the pixel function the resize / crop
+// use (rgb8_px): the unit-test form of yuv420_px, yuv_surface_px, yuv_wide_px and sensor_px.  One thread per output pixel; only
 // plane bytes resp. the H x W samples are read.
 template <int SRC>
 __global__ __launch_bounds__(256) void frames_to_bgr_kernel(const void* __restrict__ frames,
@@ -132,7 +132,7 @@ int launch_frames_to_bgr(const void* frames, const FrameSource& src, unsigned ch
         if constexpr (!kIsRgb8<SRC>) {
           JH_REQUIRE(kIsRgb8<SRC>, "YUV 4:2:0 format");
         } else {
-          if constexpr (SRC == kSrcSensor)
+          if constexpr (kIsSensor<SRC>)
             JH_REQUIRE(N >= 1 && H >= 1 && W >= 1 && d.h == H && d.w == W, "raw sensor frames: image size");
           else
             JH_REQUIRE(N >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0,

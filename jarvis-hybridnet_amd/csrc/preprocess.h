@@ -3,7 +3,7 @@
 // convolution that applies it while staging its input patch (stem.hip): ONE definition, so the fused
 // and the unfused path produce the same bits.
 //
-// The frames come in one of six SOURCE FORMS (SRC, the kSrc* codes; 0 .. 3 are JH_FRAME_* of include/jarvis_hip.h):
+// The frames come in one of eight SOURCE FORMS (SRC, the kSrc* codes; 0 .. 3 are JH_FRAME_* of include/jarvis_hip.h):
 //   0 kSrcRgbF32      [N][3][H][W] fp32 RGB in [0,1] (the API input of JarvisPredictor3D.forward);
 //   1 kSrcBgrU8       [N][H][W][3] uint8 BGR as the video decoder delivers it, converted like predict3D.py:79-80
 //                     (`.float()...[:, [2,1,0]] / 255.`) on the fly, so the 4x larger fp32 frame never exists;
@@ -17,7 +17,14 @@
 //                     surfaces, YV12 / NV21 and BT.709 / full-range streams are read in place (yuv_surface_px);
 //   5 kSrcSensor      a raw sensor image (jh_sensor_surface): one byte per pixel, Mono8 or an 8-bit Bayer mosaic,
 //                     demosaiced per fetched pixel (sensor_px); the (R, G, B) bytes enter the uint8 arithmetic
-//                     unchanged, as the YUV forms' bytes do.
+//                     unchanged, as the YUV forms' bytes do;
+//   6 kSrcSensorWide  a raw sensor image whose samples are wider than a byte: 16-bit words or the GenICam 10p / 12p
+//                     bit stream (jh_sensor_surface.sample).  A sample is reduced to its top byte where it is loaded
+//                     (byte8) and the bytes go through the demosaic of form 5 (sensor_px);
+//   7 kSrcYuvWide     a described YUV 4:2:0 surface of 16-bit samples (P010, yuv420p10le): reduced the same way, then
+//                     converted with the constants of form 4 (yuv_wide_px).
+// Callers see 6 and 7 as JH_FRAME_SENSOR / JH_FRAME_SURFACE: the frame_source constructors choose them from the
+// description's sample code, so the kernels of forms 4 and 5 carry nothing of the wide ones.
 //
 // A source form is four local things, and a new one adds exactly these:
 //   1. its description: a specialisation of SrcDesc<SRC> (what a kernel of that form takes BY VALUE -- wave-uniform,
@@ -39,6 +46,9 @@
 // Alignment under a table: fp32 images are 4-byte aligned (checked on the host); the byte forms may start at ANY
 // address -- the one wider load there is, the 2-byte chroma pair of NV12 and of semi-planar surfaces, is taken only
 // from an even image base, and an image at an odd address reads the pair as two bytes (yuv420_px, yuv_surface_px).
+// An image of 16-bit samples is 2-byte aligned (checked on the host, as fp32's rule is); its semi-planar chroma pair is
+// one 4-byte load where the pair's address is a multiple of 4 and two 2-byte loads otherwise (yuv_wide_px).  Packed
+// 10p / 12p images are read byte by byte and may start anywhere.
 #pragma once
 #include <type_traits>
 #include <variant>
@@ -46,10 +56,13 @@
 
 namespace jh {
 
-enum { kSrcRgbF32 = 0, kSrcBgrU8 = 1, kSrcI420 = 2, kSrcNV12 = 3, kSrcYuvSurface = 4, kSrcSensor = 5 };
-template <int SRC> constexpr bool kIsYuv = SRC == kSrcI420 || SRC == kSrcNV12 || SRC == kSrcYuvSurface;
+enum { kSrcRgbF32 = 0, kSrcBgrU8 = 1, kSrcI420 = 2, kSrcNV12 = 3, kSrcYuvSurface = 4, kSrcSensor = 5,
+       kSrcSensorWide = 6, kSrcYuvWide = 7, kSrcCount = 8 };
+template <int SRC> constexpr bool kIsYuv = SRC == kSrcI420 || SRC == kSrcNV12 || SRC == kSrcYuvSurface ||
+                                           SRC == kSrcYuvWide;
+template <int SRC> constexpr bool kIsSensor = SRC == kSrcSensor || SRC == kSrcSensorWide;
 // the forms whose pixel is converted once to (R, G, B) bytes for all three channels
-template <int SRC> constexpr bool kIsRgb8 = kIsYuv<SRC> || SRC == kSrcSensor;
+template <int SRC> constexpr bool kIsRgb8 = kIsYuv<SRC> || kIsSensor<SRC>;
 
 // The base pointer and the index under which the pixel functions find image n of a launch (see the head of this file).
 // cell: the one-pointer cell of a graph replay (or nullptr: `frames` is the base), or with per_image the table.
@@ -174,6 +187,46 @@ struct SensorSurface {
   }
 };
 
+// How a sample wider than a byte is stored (the high byte of JH_SAMPLE_*, include/jarvis_hip.h).
+enum { kSampleU16 = 1, kSampleP10 = 2, kSampleP12 = 3 };
+
+// The byte of one 16-bit little-endian sample at p (2-byte aligned): min(sample >> shift, 255), shift 0 .. 8.  With
+// shift 8 (MSB-aligned data: P010) the byte IS the sample's high byte, one byte load.  shift is wave-uniform.
+__device__ __forceinline__ int u16_byte(const unsigned char* p, int shift) {
+  if (shift == 8) return p[1];
+  return min((int)*reinterpret_cast<const unsigned short*>(p) >> shift, 255);
+}
+
+// A raw sensor surface of wide samples (SRC 6): the layout of form 5 -- offset, pitch and image_stride in bytes --
+// with how a sample is stored and how far it is shifted down.
+struct SensorSurfaceWide : SensorSurface {
+  int kind = kSampleU16;       // kSample*
+  int shift = 0;               // kSampleU16: 0 .. 8; the packed kinds take the top 8 bits of the n they hold
+  bool operator==(const SensorSurfaceWide& o) const {
+    return SensorSurface::operator==(o) && kind == o.kind && shift == o.shift;
+  }
+};
+
+// byte8: sample (y, x) of the wide image whose first sample lies at img, as the byte the demosaic works on.
+// 16-bit words: u16_byte (offset, pitch, image_stride and the image base are even: the load is aligned).
+// 10p / 12p: a row is a little-endian bit stream B[] starting at img + y * pitch; sample x holds bits
+// [n x, n x + n) and its byte is bits [b, b + 8), b = n x + n - 8.  With k = b >> 3, r = b & 7 that is
+// ((B[k] | B[k+1] << 8) >> r) & 0xff, and B[k+1] is loaded only when r != 0: then bit b + 7 = n x + n - 1, the
+// sample's own top bit, lies in byte k + 1 = (n x + n - 1) >> 3 <= (n w - 1) >> 3 < ceil(n w / 8) = row_bytes(w), so
+// no byte that holds no sample bit is addressed -- for the last sample of a row too, whatever w % 4 (10p: r = 2, 4,
+// 6, 0 for x % 4 = 0 .. 3) or the parity of w (12p: r = 4 for even x, 0 for odd x).  When r == 0 byte k is the
+// sample's last byte and B[k+1], which may be the next row's or nobody's, is left alone.  The & 0xff drops whatever
+// lies above the sample in B[k+1]: the next sample, or the unused high bits of the row's last byte.
+__device__ __forceinline__ int byte8(const unsigned char* img, int y, int x, const SensorSurfaceWide& s) {
+  const unsigned char* row = img + (long long)y * s.pitch;
+  if (s.kind == kSampleU16) return u16_byte(row + 2 * (long long)x, s.shift);
+  const int n = s.kind == kSampleP10 ? 10 : 12;
+  const int b = n * x + (n - 8), k = b >> 3, r = b & 7;
+  int v = row[k];
+  if (r) v |= row[k + 1] << 8;
+  return (v >> r) & 0xff;
+}
+
 // pixel (y, x) of raw image n (SRC 5).  mono: the byte, three times.  Bayer: the bilinear demosaic defined in
 // include/jarvis_hip.h -- a border pixel takes the RGB of the interior pixel it clamps to, so the 3 x 3 neighbourhood
 // never leaves the h x w samples; then, by the parity of the site against the pattern, a green site reads 5 bytes
@@ -202,21 +255,82 @@ __device__ __forceinline__ Rgb8 sensor_px(const void* frames, size_t n, int y, i
   return py == 0 ? Rgb8{lr, own, ab} : Rgb8{ab, own, lr};
 }
 
-// The description a kernel of source form SRC takes by value: the surface of the two described forms, nothing (an
+// The same pixel of a wide image (SRC 6): the clamp, the sites and the sums of the function above, every sample taken
+// through byte8.  (Its own body, not a template over both: form 5 addresses its neighbours from the centre byte's
+// pointer, and a shared body did not keep the instructions of its kernels.)
+__device__ __forceinline__ Rgb8 sensor_px(const void* frames, size_t n, int y, int x, const SensorSurfaceWide& s) {
+  const unsigned char* img = static_cast<const unsigned char*>(frames) + (long long)n * s.image_stride + s.offset;
+  if (s.pattern == 0) {
+    const int v = byte8(img, y, x, s);
+    return Rgb8{v, v, v};
+  }
+  y = min(max(y, 1), s.h - 2);
+  x = min(max(x, 1), s.w - 2);
+  const auto at = [&](int dy, int dx) { return byte8(img, y + dy, x + dx, s); };
+  const int ry = s.pattern == 2 || s.pattern == 4, rx = s.pattern == 2 || s.pattern == 3;
+  const int py = (y & 1) ^ ry, px = (x & 1) ^ rx;
+  const int own = at(0, 0);
+  if (py == px) {
+    const int g = (at(-1, 0) + at(1, 0) + at(0, 1) + at(0, -1) + 2) >> 2;
+    const int opp = (at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1) + 2) >> 2;
+    return py == 0 ? Rgb8{own, g, opp} : Rgb8{opp, g, own};
+  }
+  const int lr = (at(0, -1) + at(0, 1) + 1) >> 1, ab = (at(-1, 0) + at(1, 0) + 1) >> 1;
+  return py == 0 ? Rgb8{lr, own, ab} : Rgb8{ab, own, lr};
+}
+
+// A described surface of 16-bit samples (SRC 7): the fields of form 4 -- offsets and pitches in bytes, c_step in
+// samples, `pair` unused -- and the shift that reduces a sample.
+struct YuvSurfaceWide : YuvSurface {
+  int shift = 0;               // 0 .. 8
+  bool operator==(const YuvSurfaceWide& o) const { return YuvSurface::operator==(o) && shift == o.shift; }
+};
+
+// pixel (y, x) of image n of a 16-bit surface: one Y load and, for the block's chroma, the two samples of a
+// semi-planar pair in ONE 4-byte load where the pair's address is a multiple of 4 -- its offset in the image is one
+// (jh_yuv_surface_check), so that is every image whose base is a multiple of 4 --, in two 2-byte loads otherwise;
+// planar: the U and the V sample.  Every sample becomes a byte (u16_byte) before the conversion of form 4.
+__device__ __forceinline__ Rgb8 yuv_wide_px(const void* frames, size_t n, int y, int x, const YuvSurfaceWide& s) {
+  const unsigned char* img = static_cast<const unsigned char*>(frames) + (long long)n * s.image_stride;
+  const int Y = u16_byte(img + s.y_offset + (long long)y * s.y_pitch + 2 * (long long)x, s.shift);
+  const long long crow = (long long)(y >> 1) * s.c_pitch;
+  int U, V;
+  if (s.c_step == 2) {
+    const bool u_first = s.u_offset < s.v_offset;
+    const unsigned char* pair = img + (u_first ? s.u_offset : s.v_offset) + crow + 2 * (long long)(x & ~1);
+    int a, b;                                           // the pair's first and second sample, reduced
+    if (!(reinterpret_cast<uintptr_t>(pair) & 3)) {
+      const unsigned int uv = *reinterpret_cast<const unsigned int*>(pair);
+      a = min((int)(uv & 0xffffu) >> s.shift, 255); b = min((int)(uv >> 16) >> s.shift, 255);
+    } else {
+      a = u16_byte(pair, s.shift); b = u16_byte(pair + 2, s.shift);
+    }
+    U = u_first ? a : b; V = u_first ? b : a;
+  } else {
+    const long long c = crow + 2 * (long long)(x >> 1);
+    U = u16_byte(img + s.u_offset + c, s.shift); V = u16_byte(img + s.v_offset + c, s.shift);
+  }
+  return yuv_to_rgb8(Y, U, V, s);
+}
+
+// The description a kernel of source form SRC takes by value: the surface of the four described forms, nothing (an
 // empty class) for the four whose layout follows from (H, W).
 template <int SRC> struct SrcDesc {
   bool operator==(const SrcDesc&) const { return true; }
 };
 template <> struct SrcDesc<kSrcYuvSurface> : YuvSurface {};
 template <> struct SrcDesc<kSrcSensor> : SensorSurface {};
+template <> struct SrcDesc<kSrcSensorWide> : SensorSurfaceWide {};
+template <> struct SrcDesc<kSrcYuvWide> : YuvSurfaceWide {};
 
 // pixel (y, x) of image n as (R, G, B) bytes: the forms that convert once for all three channels
 template <int SRC>
 __device__ __forceinline__ Rgb8 rgb8_px(const void* frames, size_t n, int y, int x, int H, int W,
                                         const SrcDesc<SRC>& d) {
   static_assert(kIsRgb8<SRC>, "rgb8_px: YUV and raw sensor formats only");
-  if constexpr (SRC == kSrcSensor) return sensor_px(frames, n, y, x, d);
+  if constexpr (kIsSensor<SRC>) return sensor_px(frames, n, y, x, d);
   else if constexpr (SRC == kSrcYuvSurface) return yuv_surface_px(frames, n, y, x, d);
+  else if constexpr (SRC == kSrcYuvWide) return yuv_wide_px(frames, n, y, x, d);
   else return yuv420_px<SRC>(frames, n, y, x, H, W);
 }
 
@@ -304,13 +418,17 @@ __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int
 // frame_source constructors of api.hip; everything between the C entry point and a kernel launch takes this.
 struct FrameSource {
   int fmt = kSrcRgbF32;                                                                  // kSrc*
-  std::variant<std::monostate, SrcDesc<kSrcYuvSurface>, SrcDesc<kSrcSensor>> desc;       // monostate: fmt needs none
+  std::variant<std::monostate, SrcDesc<kSrcYuvSurface>, SrcDesc<kSrcSensor>, SrcDesc<kSrcSensorWide>,
+               SrcDesc<kSrcYuvWide>> desc;                                               // monostate: fmt needs none
   bool per_image = false;      // the launches read a table of one device pointer per image instead of one base
   bool operator==(const FrameSource& o) const { return fmt == o.fmt && desc == o.desc && per_image == o.per_image; }
   bool operator!=(const FrameSource& o) const { return !(*this == o); }
-  // bytes of frame data per source pixel: fp32 RGB 12, uint8 BGR 3, YUV 4:2:0 1.5, raw sensor 1
+  // bytes of frame data per source pixel: fp32 RGB 12, uint8 BGR 3, YUV 4:2:0 1.5 (16-bit: 3), raw sensor 1 (16-bit
+  // words 2, 10p 1.25, 12p 1.5)
   double px_bytes() const {
-    return fmt == kSrcRgbF32 ? 12.0 : fmt == kSrcBgrU8 ? 3.0 : fmt == kSrcSensor ? 1.0 : 1.5;
+    if (const auto* w = std::get_if<SrcDesc<kSrcSensorWide>>(&desc))
+      return w->kind == kSampleU16 ? 2.0 : w->kind == kSampleP10 ? 1.25 : 1.5;
+    return fmt == kSrcRgbF32 ? 12.0 : fmt == kSrcBgrU8 ? 3.0 : fmt == kSrcSensor ? 1.0 : fmt == kSrcYuvWide ? 3.0 : 1.5;
   }
 };
 
@@ -336,6 +454,8 @@ int dispatch_src(const FrameSource& src, F&& f) {
     case kSrcNV12: return row(SrcTag<kSrcNV12>{});
     case kSrcYuvSurface: return row(SrcTag<kSrcYuvSurface>{});
     case kSrcSensor: return row(SrcTag<kSrcSensor>{});
+    case kSrcSensorWide: return row(SrcTag<kSrcSensorWide>{});
+    case kSrcYuvWide: return row(SrcTag<kSrcYuvWide>{});
   }
   set_error("requirement failed: src.fmt is no kSrc* code (frame format)");
   return 1;

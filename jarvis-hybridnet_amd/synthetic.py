@@ -206,10 +206,60 @@ def bgr_to_yuv420(bgr, fmt):
     return pack_yuv420(q(y), q(pool(u)), q(pool(v)), fmt)
 
 
+def reduce_samples(a, shift):
+    """Samples wider than a byte -> the bytes the fetch makes of them: min(sample >> shift, 255), uint8 (the
+    truncation a camera applies when its PixelFormat goes from Mono12 to Mono8; a sample with bits above the declared
+    depth saturates)."""
+    a = np.asarray(a)
+    if a.dtype.kind not in "ui":
+        raise ValueError("reduce_samples takes integer samples, got %s" % a.dtype)
+    return np.minimum(a.astype(np.uint32) >> shift, 255).astype(np.uint8)
+
+
+def widen(bytes_, shift, rng, saturate=False):
+    """uint8 bytes -> uint16 samples with random low `shift` bits that reduce_samples(., shift) takes back to the
+    bytes.  saturate (the second variant, shift < 8): where a byte is 255, about half of the samples also get random
+    bits ABOVE the declared depth of 8 + shift bits -- they still reduce to 255, by saturation."""
+    b = np.asarray(bytes_, np.uint8)
+    if not 0 <= shift <= 8:
+        raise ValueError("shift must be 0..8, got %r" % (shift,))
+    out = (b.astype(np.uint16) << shift) | rng.integers(0, 1 << shift, b.shape, dtype=np.uint16)
+    if saturate and shift < 8:
+        over = rng.integers(0, 1 << (8 - shift), b.shape, dtype=np.uint16) << (8 + shift)
+        out = np.where((b == 255) & (rng.integers(0, 2, b.shape) == 1), out | over, out).astype(np.uint16)
+    return out
+
+
+def pack_bits(samples, bits):
+    """Rows of samples (..., W) -> the GenICam PFNC 10p / 12p bytes (..., ceil(bits * W / 8)) uint8: every row a
+    little-endian bit stream, sample x at bits [bits * x, bits * x + bits); the unused high bits of a row's last
+    byte are 0.  Samples are taken modulo 2^bits."""
+    a = np.asarray(samples).astype(np.uint16)
+    W = a.shape[-1]
+    stream = ((a[..., None] >> np.arange(bits, dtype=np.uint16)) & 1).astype(np.uint8).reshape(a.shape[:-1] + (W * bits,))
+    return np.packbits(stream, axis=-1, bitorder="little")
+
+
+def unpack_bits(packed, bits, width):
+    """The inverse of pack_bits: (..., ceil(bits * width / 8)) uint8 -> (..., width) uint16 (test of the packer)."""
+    stream = np.unpackbits(np.asarray(packed, np.uint8), axis=-1, bitorder="little")[..., :bits * width]
+    stream = stream.reshape(stream.shape[:-1] + (width, bits)).astype(np.uint16)
+    return (stream << np.arange(bits, dtype=np.uint16)).sum(-1, dtype=np.uint16)
+
+
+def _le16(a):
+    """uint16 (..., W) -> their little-endian bytes (..., 2W) uint8."""
+    a = np.asarray(a).astype("<u2")
+    return np.ascontiguousarray(a).view(np.uint8).reshape(a.shape[:-1] + (2 * a.shape[-1],))
+
+
 def pack_yuv_surface(y, u, v, surface, fill=0):
     """Planes Y (..., H, W), U and V (..., H/2, W/2) uint8 -> (..., image_stride) uint8 laid out as the YuvSurface
     `surface` describes; every byte that belongs to no plane (pitch padding, the rows between the planes, the gap up
-    to image_stride) is `fill`."""
+    to image_stride) is `fill`.  A 16-bit description (surface.bits > 8) takes uint16 planes and writes every sample
+    as two little-endian bytes."""
+    if surface.sample:
+        return _pack_yuv_surface16(y, u, v, surface, fill)
     y, u, v = np.asarray(y, np.uint8), np.asarray(u, np.uint8), np.asarray(v, np.uint8)
     s, lead = surface, y.shape[:-2]
     H, W = s.height, s.width
@@ -221,6 +271,28 @@ def pack_yuv_surface(y, u, v, surface, fill=0):
         rows, cols = plane.shape[-2:]
         idx = offset + np.arange(rows)[:, None] * pitch + np.arange(cols)[None, :] * step
         out[..., idx.reshape(-1)] = plane.reshape(lead + (-1,))
+
+    put(y, s.y_offset, s.y_pitch, 1)
+    put(u, s.u_offset, s.c_pitch, s.c_step)
+    put(v, s.v_offset, s.c_pitch, s.c_step)
+    return out
+
+
+def _pack_yuv_surface16(y, u, v, surface, fill):
+    y, u, v = (np.asarray(p) for p in (y, u, v))
+    if any(p.dtype != np.uint16 for p in (y, u, v)):
+        raise ValueError("a 16-bit surface takes uint16 planes, got %s / %s / %s" % (y.dtype, u.dtype, v.dtype))
+    s, lead = surface, y.shape[:-2]
+    H, W = s.height, s.width
+    if y.shape[-2:] != (H, W) or u.shape != lead + (H // 2, W // 2) or v.shape != u.shape:
+        raise ValueError("planes %s / %s / %s do not fit a %d x %d surface" % (y.shape, u.shape, v.shape, H, W))
+    out = np.full(lead + (s.image_stride,), fill, np.uint8)
+
+    def put(plane, offset, pitch, step):
+        rows, cols = plane.shape[-2:]
+        idx = offset + np.arange(rows)[:, None, None] * pitch + np.arange(cols)[None, :, None] * (2 * step) \
+            + np.arange(2)[None, None, :]
+        out[..., idx.reshape(-1)] = _le16(plane).reshape(lead + (-1,))
 
     put(y, s.y_offset, s.y_pitch, 1)
     put(u, s.u_offset, s.c_pitch, s.c_step)
@@ -303,12 +375,28 @@ def sensor_to_bgr(raw, pattern):
 
 def pack_sensor_surface(raw, surface, fill=0):
     """raw (..., H, W) uint8 -> (..., image_stride) uint8 laid out as the SensorSurface `surface` describes; every
-    byte that is no sample (the bytes before `offset`, pitch padding, the gap up to image_stride) is `fill`."""
-    raw = np.asarray(raw, np.uint8)
-    s, lead = surface, raw.shape[:-2]
+    byte that is no sample (the bytes before `offset`, pitch padding, the gap up to image_stride) is `fill`.
+    A wide description (surface.container != 'u8') takes uint16 samples: the 16-bit containers store them as two
+    little-endian bytes, 'packed' as the 10p / 12p bit stream of each row (pack_bits) -- there the unused high bits of
+    a row's last byte take the bits of `fill` too."""
+    s = surface
+    wide = s.container != "u8"
+    raw = np.asarray(raw) if wide else np.asarray(raw, np.uint8)
+    if wide and raw.dtype != np.uint16:
+        raise ValueError("a %r surface takes uint16 samples, got %s" % (s.container, raw.dtype))
+    lead = raw.shape[:-2]
     if raw.shape[-2:] != (s.height, s.width):
         raise ValueError("raw %s does not fit a %d x %d surface" % (raw.shape, s.height, s.width))
     out = np.full(lead + (s.image_stride,), fill, np.uint8)
-    idx = s.offset + np.arange(s.height)[:, None] * s.pitch + np.arange(s.width)[None, :]
-    out[..., idx.reshape(-1)] = raw.reshape(lead + (-1,))
+    rows = raw
+    if s.container == "packed":
+        rows = pack_bits(raw, s.bits)
+        spare = 8 * rows.shape[-1] - s.bits * s.width           # unused high bits of the last byte of a row
+        if spare:
+            rows[..., -1] |= (fill & 0xff) >> (8 - spare) << (8 - spare)
+    elif wide:
+        rows = _le16(raw)
+    nb = rows.shape[-1]
+    idx = s.offset + np.arange(s.height)[:, None] * s.pitch + np.arange(nb)[None, :]
+    out[..., idx.reshape(-1)] = rows.reshape(lead + (-1,))
     return out
