@@ -1014,6 +1014,26 @@ int jh_op_bifpn_node(int n_in, const int* modes, const float* weights, int act, 
                      int h, int w, const float* x0_dev, const float* x1_dev, const float* x2_dev,
                      const float* dw_host, const float* pw_host, const float* bias_host, float* y_dev,
                      void* stream);
+/* TEST-ONLY: what jh_op_bifpn_node leaves out of a node as the network plans run it (csrc/node_layer.h). */
+typedef struct jh_op_node_ex {
+  int32_t batch_class;             /* as in jh_node_form: 0 by launch size / 1 time batch below 8 / 2 of 8 and more */
+  int32_t want_pool;               /* the caller could use the 2x2-max-pooled raw output, if the form can write it */
+  const double* in_sums_host[3];   /* per input (n, c, 2) sum and sum of squares that REPLACE the statistics the entry
+                                    * computes from the tensor's own pixels, or NULL */
+  int64_t in_count[3];             /* ... and the pixels they were taken over: inv_cnt = 1 / count as a float (a pooled
+                                    * tensor carries its producer's statistics and pixel count) */
+  float* y_pool_dev;               /* (n, cout, h/2, w/2) NCHW dev: written exactly when the choice says `pool` */
+  int32_t* pool_written_host;      /* receives 1 when y_pool_dev was written, else 0; or NULL */
+  double* out_sums_host;           /* (n, cout, 2): the statistics the node emitted for its consumers, the limbs of each
+                                    * value added in the reader's fixed order; or NULL */
+} jh_op_node_ex;
+/* jh_op_bifpn_node in the time-batch class `ex` names, with the pooled output, handed-on input statistics and the
+ * emitted statistics.  jh_op_bifpn_node is this call with class 0, no pooled output, no overrides and no extra outputs.
+ * Both fill the buffers behind y and y_pool with NaN before the launch: a pixel nobody wrote arrives as NaN. */
+int jh_op_bifpn_node_ex(int n_in, const int* modes, const float* weights, int act, int n, int c, int cout,
+                        int h, int w, const float* x0_dev, const float* x1_dev, const float* x2_dev,
+                        const float* dw_host, const float* pw_host, const float* bias_host, float* y_dev,
+                        const jh_op_node_ex* ex, void* stream);
 
 #ifdef __cplusplus
 }

@@ -64,6 +64,17 @@ class OpOperand(ctypes.Structure):
 
 assert ctypes.sizeof(OpOperand) == 72
 
+
+class OpNodeEx(ctypes.Structure):
+    """jh_op_node_ex of include/jarvis_hip.h (test entry jh_op_bifpn_node_ex): host and device pointers as raw
+    addresses."""
+    _fields_ = [("batch_class", ctypes.c_int32), ("want_pool", ctypes.c_int32), ("in_sums_host", c_void_p * 3),
+                ("in_count", ctypes.c_int64 * 3), ("y_pool_dev", c_void_p),
+                ("pool_written_host", ctypes.POINTER(ctypes.c_int32)), ("out_sums_host", c_void_p)]
+
+
+assert ctypes.sizeof(OpNodeEx) == 80
+
 class SubjectsParamsStruct(ctypes.Structure):
     """jh_subjects_params of include/jarvis_hip.h (built by subjects_params())."""
     _fields_ = [("max_subjects", ctypes.c_int32), ("max_peaks", ctypes.c_int32), ("nms_radius", ctypes.c_int32),
@@ -266,6 +277,9 @@ _SIGS = {
     "jh_op_bifpn_node": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_float), c_int, c_int, c_int,
                                  c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
+    "jh_op_bifpn_node_ex": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_float), c_int, c_int, c_int,
+                                    c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, ctypes.POINTER(OpNodeEx), c_void_p]),
 }
 
 

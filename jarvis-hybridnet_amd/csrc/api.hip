@@ -2170,13 +2170,21 @@ int jh_op_joint_argmax_all(const float* heat_dev, int n, int hh, int wh, int j, 
 
 // One fused BiFPN node (csrc/bifpn_node.hip) as a unit-test entry point: every input is a RAW
 // tensor that the node normalises on load with its own InstanceNorm statistics (computed here
-// on the host), exactly as inside the network plan.
-int jh_op_bifpn_node(int n_in, const int* modes, const float* weights, int act, int n, int c, int cout,
-                     int h, int w, const float* x0_dev, const float* x1_dev, const float* x2_dev,
-                     const float* dw_host, const float* pw_host, const float* bias_host, float* y_dev,
-                     void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
+// on the host), exactly as inside the network plan.  The body of jh_op_bifpn_node (ex == nullptr: class ByLaunchSize,
+// no pooled output, every input with the statistics of its own pixels) and of jh_op_bifpn_node_ex (the time-batch
+// class, the pooled output, statistics a producer handed on, the node's emitted statistics).
+static int op_node_body(int n_in, const int* modes, const float* weights, int act, int n, int c, int cout, int h,
+                        int w, const float* x0_dev, const float* x1_dev, const float* x2_dev, const float* dw_host,
+                        const float* pw_host, const float* bias_host, float* y_dev, const jh_op_node_ex* ex,
+                        hipStream_t s, const char* who) {
   JH_REQUIRE(n_in >= 2 && n_in <= 3 && modes && weights && y_dev, "bad argument");
+  if (ex && ex->pool_written_host) *ex->pool_written_host = 0;
+  JH_REQUIRE(n >= 1 && c >= 1 && cout >= 1 && h >= 1 && w >= 1 && x0_dev && x1_dev && (n_in < 3 || x2_dev) && dw_host &&
+             pw_host, "bad argument");
+  for (int i = 0; i < n_in; ++i) {   // (an up-sampled input of h / 2 rows has no source for output row h - 1 of an odd h)
+    const int step = modes[i] == FUSE_UP2 ? 2 : (modes[i] == FUSE_UP4 ? 4 : 1);
+    JH_REQUIRE(h % step == 0 && w % step == 0, "an up-sampled input needs a node of whole multiples of its step");
+  }
   const float* xs[3] = {x0_dev, x1_dev, x2_dev};
   Scratch sc;
   Act in[3], y;
@@ -2189,8 +2197,17 @@ int jh_op_bifpn_node(int n_in, const int* modes, const float* weights, int act, 
     else if (modes[i] == FUSE_POOL2) { hi = h * 2; wi = w * 2; }
     if (sc.act(n, 1, hi, wi, c, &in[i])) return 1;
     if (launch_to_channel_last(xs[i], in[i], s)) return 1;
-    // statistics of the raw input (sum, sum of squares per (n, channel)), whole value in limb 1
     const size_t px = (size_t)hi * wi;
+    if (ex && ex->in_sums_host[i]) {
+      // statistics a producer handed on, over ITS pixel count (a pooled tensor carries its producer's: EffTrackPlan::node)
+      JH_REQUIRE(ex->in_count[i] >= 1, "pixel count of the given statistics");
+      double* st_dev = nullptr;
+      if (op_upload_stats(sc, ex->in_sums_host[i], n, c, in[i].Cp, &st_dev)) return 1;
+      a.in[i] = in[i].p; a.st[i] = st_dev; a.inv_cnt[i] = 1.f / (float)ex->in_count[i]; a.mode[i] = modes[i];
+      a.w[i] = weights[i];
+      continue;
+    }
+    // statistics of the raw input (sum, sum of squares per (n, channel)), whole value in limb 1
     std::vector<float> host((size_t)n * c * px);
     JH_CHECK_HIP(hipMemcpyAsync(host.data(), xs[i], host.size() * sizeof(float), hipMemcpyDeviceToHost, s));
     JH_CHECK_HIP(hipStreamSynchronize(s));
@@ -2211,7 +2228,8 @@ int jh_op_bifpn_node(int n_in, const int* modes, const float* weights, int act, 
     a.w[i] = weights[i];
   }
   if (sc.act(n, 1, h, w, cout, &y)) return 1;
-  JH_CHECK_HIP(hipMemsetAsync(y.p, 0, y.bytes(), s));
+  // (NaN: an output pixel that no workgroup stores reaches the caller as NaN, not as a zero that could pass)
+  JH_CHECK_HIP(hipMemsetAsync(y.p, 0xFF, y.bytes(), s));
   const int Cp = in[0].Cp;
   const std::vector<float> dwt = taps_major(dw_host, c, 9, Cp);
   float* dwd;
@@ -2219,20 +2237,62 @@ int jh_op_bifpn_node(int n_in, const int* modes, const float* weights, int act, 
   ConvWeights cw;
   if (pack_conv_weights(conv_desc(2, 1, 1, 0, c, cout), pw_host, bias_host, false, WeightLayout::Plain, &cw)) return 1;
   double* ost;
+  const size_t nst = (size_t)n * y.Cp * kStatW;
+  std::vector<double> hst(ex && ex->out_sums_host ? nst : 0);
   int rc = 0;
   do {
-    if ((rc = sc.get(reinterpret_cast<void**>(&ost), (size_t)n * y.Cp * kStatW * sizeof(double)))) break;
-    if (hipMemsetAsync(ost, 0, (size_t)n * y.Cp * kStatW * sizeof(double), s) != hipSuccess) { rc = 1; break; }
+    if ((rc = sc.get(reinterpret_cast<void**>(&ost), nst * sizeof(double)))) break;
+    if (hipMemsetAsync(ost, 0, nst * sizeof(double), s) != hipSuccess) { rc = 1; break; }
     a.dw = dwd; a.pw = cw.w; a.bias = cw.bias; a.y = y.p; a.stats = ost;
     a.N = n; a.H = h; a.W = w; a.Cp = Cp; a.cout_p = y.Cp; a.cout_p16 = cw.cout_p16;
     NodeChoice choice;
-    if ((rc = choose_node(node_use(a, NodeBatchClass::ByLaunchSize, false), &choice))) break;
+    const NodeBatchClass cls = ex ? static_cast<NodeBatchClass>(ex->batch_class) : NodeBatchClass::ByLaunchSize;
+    if ((rc = choose_node(node_use(a, cls, ex && ex->want_pool), &choice))) break;
+    Act yp;
+    if (choice.pool) {   // the pooled output is written exactly when the choice says so, as in EffTrackPlan::node
+      if (!ex->y_pool_dev) {
+        set_error(std::string(who) + ": the node writes its pooled output, y_pool_dev is NULL");
+        rc = 1;
+        break;
+      }
+      if ((rc = sc.act(n, 1, h / 2, w / 2, cout, &yp))) break;
+      if (hipMemsetAsync(yp.p, 0xFF, yp.bytes(), s) != hipSuccess) { rc = 1; break; }
+      a.y_pool = yp.p;
+    }
     if ((rc = launch_bifpn_node(a, choice, s))) break;
     if ((rc = launch_from_channel_last(y, y_dev, s))) break;
-    if (hipStreamSynchronize(s) != hipSuccess) { set_error("stream sync failed in jh_op_bifpn_node"); rc = 1; }
+    if (choice.pool && (rc = launch_from_channel_last(yp, ex->y_pool_dev, s))) break;
+    if (!hst.empty() &&
+        hipMemcpyAsync(hst.data(), ost, nst * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess) { rc = 1; break; }
+    if (hipStreamSynchronize(s) != hipSuccess) { set_error(std::string("stream sync failed in ") + who); rc = 1; break; }
+    if (ex && ex->pool_written_host) *ex->pool_written_host = choice.pool ? 1 : 0;
+    // the emitted statistics as a consumer reads them: the limbs added in exact_read's order
+    for (int b = 0; b < n && !hst.empty(); ++b)
+      for (int ch = 0; ch < cout; ++ch) {
+        const double* q = hst.data() + ((size_t)b * y.Cp + ch) * kStatW;
+        ex->out_sums_host[((size_t)b * cout + ch) * 2] = (q[0] + q[1]) + q[2];
+        ex->out_sums_host[((size_t)b * cout + ch) * 2 + 1] = (q[kLimbs] + q[kLimbs + 1]) + q[kLimbs + 2];
+      }
   } while (0);
   free_conv_weights(&cw);
   return rc;
+}
+
+int jh_op_bifpn_node(int n_in, const int* modes, const float* weights, int act, int n, int c, int cout,
+                     int h, int w, const float* x0_dev, const float* x1_dev, const float* x2_dev,
+                     const float* dw_host, const float* pw_host, const float* bias_host, float* y_dev,
+                     void* stream) {
+  return op_node_body(n_in, modes, weights, act, n, c, cout, h, w, x0_dev, x1_dev, x2_dev, dw_host, pw_host, bias_host,
+                      y_dev, nullptr, static_cast<hipStream_t>(stream), "jh_op_bifpn_node");
+}
+
+int jh_op_bifpn_node_ex(int n_in, const int* modes, const float* weights, int act, int n, int c, int cout,
+                        int h, int w, const float* x0_dev, const float* x1_dev, const float* x2_dev,
+                        const float* dw_host, const float* pw_host, const float* bias_host, float* y_dev,
+                        const jh_op_node_ex* ex, void* stream) {
+  JH_REQUIRE(ex && ex->batch_class >= 0 && ex->batch_class <= 2, "jh_op_bifpn_node_ex: batch_class");
+  return op_node_body(n_in, modes, weights, act, n, c, cout, h, w, x0_dev, x1_dev, x2_dev, dw_host, pw_host, bias_host,
+                      y_dev, ex, static_cast<hipStream_t>(stream), "jh_op_bifpn_node_ex");
 }
 
 }  // extern "C"

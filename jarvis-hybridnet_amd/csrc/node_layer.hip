@@ -173,7 +173,9 @@ int choose_node(const NodeUse& u, NodeChoice* out) {
   // ---- pooled output: the two-input form can write the 2x2-max-pooled raw output on the side, so that the bottom-up
   // node of the next level reads a same-resolution tensor with THIS node's statistics; the workgroup form also from
   // three same-level inputs, so the bottom-up pass stays in a row form one level further down.
-  c.pool = u.want_pool && u.act == ACT_SILU && u.cout_p == u.Cp && u.H % 2 == 0 &&
+  // (an even width too: with an odd one the lane of the last pixel of a row would own pooled column W / 2, which is
+  //  the first pixel of the NEXT pooled row -- across a segment border another workgroup's)
+  c.pool = u.want_pool && u.act == ACT_SILU && u.cout_p == u.Cp && u.H % 2 == 0 && u.W % 2 == 0 &&
            (u.n_in == 2 || (wg && v == NodeVariant::Same3));
   JH_REQUIRE(!(c.pool && v == NodeVariant::Same2), "row-streaming node: pooled output of two same-level inputs");
 

@@ -207,6 +207,10 @@ BOUNDARY_ROWS = [
     ((56, 56, 63, 64, (0, 1), 2, 384), ATLEAST8, 1, ("tile", 0, 0, 0, 32, 384, 512, 48416, 0)),
     # ReLU: the tile form only
     ((56, 56, 64, 64, (0, 1), 1, 12), BELOW8, 0, ("tile", 0, 0, 0, 32, 12, 512, 48416, 0)),
+    # ... nor an odd width: the last pixel's lane would own pooled column W / 2, the first pixel of the next pooled row
+    # (the same node one pixel wider writes it)
+    ((160, 160, 6, 5, (0, 0, 0), 2, 12), ATLEAST8, 1, ("rows_wg", 6, 1, 1, 1, 12, 768, 71168, 0)),
+    ((160, 160, 6, 6, (0, 0, 0), 2, 12), ATLEAST8, 1, ("rows_wg", 6, 1, 1, 1, 12, 768, 71168, 1)),
 ]
 
 # Nodes that no form takes.
@@ -237,6 +241,35 @@ def test_node_cases_of_the_op_test():
         assert form(case) == want, case
 
 
+def test_output_cases_run_what_the_plans_run():
+    """tests/node_cases.py: every row of a time-batch class has a case with 3 (or 2) images, and jh_node_form gives that
+    case the row's form, rows per segment, strips, segments, block, LDS and pooled output -- only the grid, which counts
+    the images, may differ.  So tests/test_hip_node_outputs.py executes what the plans execute."""
+    from tests import node_cases as NC
+    cases = NC.cases()
+    assert len({k.id for k in cases}) == len(cases)
+    assert all(NC.runnable(r[0]) for r in MODEL_ROWS)
+    assert [r[0][:4] for r in BOUNDARY_ROWS if not NC.runnable(r[0])] == [(56, 56, 63, 64)]   # (no such tensors)
+    for node, cls, want_pool, want in MODEL_ROWS + [r for r in BOUNDARY_ROWS if r[1] != BY_SIZE and NC.runnable(r[0])]:
+        k = NC.by_key(cases, node[:6], cls, want_pool)
+        assert k.want[:4] + k.want[6:] == want[:4] + want[6:] and k.node[6] in (2, 3)   # (rows that differ in images only)
+        got = form(k.node, cls, want_pool)
+        assert got is not None, k.id
+        assert got[:4] + got[6:] == want[:4] + want[6:], (k.id, got, want)
+        # the largest tensor of the GPU file is 3 x 160 x 64 x 64 floats; 88 channels at 80 x 80 run with 2 images
+        assert k.node[6] * max(k.node[0], k.node[1]) * k.node[2] * k.node[3] <= 3 * 160 * 64 * 64
+    # every form, and every form that writes the pooled output, is among them
+    assert {k.want[0] for k in cases} == set(NC.FORMS)
+    assert {k.want[0] for k in cases if k.want[8]} == {"rows_wave", "rows_pairs", "rows_wg"}
+    # the chains of the GPU file are made of table cases, and every node but the last writes its pooled output
+    for c, cls, levels in NC.CHAINS:
+        ks = NC.chain_nodes(cases, c, cls, levels)
+        for k in ks:
+            got = form(k.node, k.cls, k.want_pool)
+            assert got[:4] + got[6:] == k.want[:4] + k.want[6:], (k.id, got)
+        assert all(k.want[8] for k in ks[:-1]), (c, cls, levels)
+
+
 @pytest.mark.parametrize("case,cls,want_pool", ERROR_ROWS)
 def test_nodes_no_form_takes(case, cls, want_pool):
     assert form(case, cls, want_pool) is None
@@ -257,6 +290,27 @@ def test_bad_arguments_are_refused():
     assert f(56, 56, 3, 64, 64, 2, None, 2, 0, 0, name, len(name), out) != 0
     assert f(56, 56, 3, 64, 64, 2, m3, 2, 0, 0, None, 0, out) != 0
     assert f(56, 56, 3, 64, 64, 2, m3, 2, 0, 0, name, len(name), None) != 0
+
+
+def test_node_operator_refuses_what_it_cannot_run():
+    """jh_op_bifpn_node / jh_op_bifpn_node_ex check their arguments before they touch the GPU: a class outside 0 .. 2, a
+    missing struct, and an up-sampled input of a node that is no whole multiple of its step (the 31-row x2 input of a
+    63-row node has no source for output row 62)."""
+    lib = N.lib()
+    m3, w3 = (ctypes.c_int * 3)(0, 1, 0), (ctypes.c_float * 3)(0.5, 0.5, 0.0)
+    p = ctypes.cast(ctypes.create_string_buffer(64), ctypes.c_void_p).value      # never read: the checks come first
+    ex = N.OpNodeEx()
+    ex.batch_class = 3
+    args = (2, m3, w3, 2, 1, 56, 56, 64, 64, p, p, None, p, p, p, p)
+    assert lib.jh_op_bifpn_node_ex(*args, ctypes.byref(ex), None) != 0
+    assert b"batch_class" in lib.jh_last_error()
+    assert lib.jh_op_bifpn_node_ex(*args, None, None) != 0
+    ex.batch_class = ATLEAST8
+    odd = (2, m3, w3, 2, 1, 56, 56, 63, 64, p, p, None, p, p, p, p)
+    assert lib.jh_op_bifpn_node_ex(*odd, ctypes.byref(ex), None) != 0
+    assert b"up-sampled" in lib.jh_last_error()
+    assert lib.jh_op_bifpn_node(*odd, None) != 0
+    assert b"up-sampled" in lib.jh_last_error()
 
 
 def test_node_rows_knob_off_is_the_tile_form_everywhere():
