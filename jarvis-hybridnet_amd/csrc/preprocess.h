@@ -33,7 +33,7 @@
 //   2. its pixel function, selected in rgb8_px<SRC> (a form delivering (R, G, B) bytes) or frame_px<SRC>;
 //   3. its row in dispatch_src, the one place a run-time format code becomes a template argument: the resize, the
 //      crop, the fused stem and the to-BGR launchers all instantiate through it;
-//   4. its host constructor in api.hip (frame_source), which validates what the caller gave and builds the FrameSource
+//   4. its host constructor in api_frames.hip (frame_source), which validates what the caller gave and builds the FrameSource
 //      every layer below takes.
 // Nothing else names a form: the kernels, StemSource and the predictor's graph slots carry a SrcDesc<SRC> resp. a
 // FrameSource whatever it holds.
@@ -415,7 +415,7 @@ __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int
 
 // ---------------------------------------------------------------------------------------------------- host side
 // Where a call's frames come from: the format code and the description that format has.  Built (and validated) by the
-// frame_source constructors of api.hip; everything between the C entry point and a kernel launch takes this.
+// frame_source constructors of api_frames.hip; everything between the C entry point and a kernel launch takes this.
 struct FrameSource {
   int fmt = kSrcRgbF32;                                                                  // kSrc*
   std::variant<std::monostate, SrcDesc<kSrcYuvSurface>, SrcDesc<kSrcSensor>, SrcDesc<kSrcSensorWide>,

@@ -14,7 +14,7 @@ struct TrackParams {
   float max_jump_mm;
 };
 
-// jh_track_state of include/jarvis_hip.h, field for field (api.hip asserts the size)
+// jh_track_state of include/jarvis_hip.h, field for field (api_features.hip asserts the size)
 struct TrackState {
   float pos[kMaxTracks][3], vel[kMaxTracks][3];
   int missed[kMaxTracks], id[kMaxTracks];

@@ -46,6 +46,19 @@ def test_header_is_valid_c_and_links(tmp_path):
     assert out.split() == ["abi", str(N.ABI_VERSION), "config", str(ctypes.sizeof(N.PredictorConfig))]
 
 
+def test_workspace_carving(tmp_path):
+    """csrc/workspace.h alone in a host translation unit (g++ -std=c++17 -Wall -Werror: the header is free of HIP):
+    tests/workspace_smoke.cpp checks the Carver's two passes and the first-call carve helper against a stand-in allocator
+    and a stand-in capture check."""
+    import subprocess
+    exe = str(tmp_path / "workspace_smoke")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-pedantic",
+                    "-I", os.path.join(ROOT, "jarvis-hybridnet_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "workspace_smoke.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    assert out.split() == ["workspace", "ok"]
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(N, "_lib", None)
     monkeypatch.setattr(N, "LIB_PATH", "/nonexistent/libjarvis_hip.so")
