@@ -4,6 +4,9 @@
 // operators api_ops.hip; predictor.h is what they share.
 #include <cstring>
 #include "predictor.h"
+#include "centers.h"
+#include "reproject.h"
+#include "softargmax.h"
 
 namespace jh {
 static thread_local std::string g_err;

@@ -1,6 +1,7 @@
 // C ABI, the frame descriptions: the one validation of each described surface, the FrameSource every entry point hands
 // to the kernels (preprocess.h), the pointer table of a per-image call, and the conversion operators.
 #include "predictor.h"
+#include "preprocess.h"
 
 using namespace jh;
 

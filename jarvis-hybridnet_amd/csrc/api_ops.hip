@@ -98,7 +98,7 @@ static int op_conv_body(int nd, int kind, int k, int stride, int pad, int cin, i
   return 0;
 }
 
-// The all-joint argmax on its own (csrc/geometry.hip): the (max, index) partials live in the caller's workspace.
+// The all-joint argmax on its own (csrc/views2d.hip): the (max, index) partials live in the caller's workspace.
 static size_t carve_joint_argmax_all(Carver& c, int n, int hh, int wh, int jp, float** pmax, int** pidx) {
   const size_t k = joint_argmax_all_partials(n, hh, wh, jp);
   *pmax = c.take<float>(k);

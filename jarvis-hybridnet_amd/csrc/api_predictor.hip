@@ -1,6 +1,10 @@
 // C ABI, the 3D predictor: creation, the three stages, the whole-path forward (plain launches or one graph launch) and
 // the debug entries.  What a predictor owns is predictor.h; the optional features are api_features.hip.
 #include "predictor.h"
+#include "centers.h"
+#include "preprocess.h"
+#include "reproject.h"
+#include "softargmax.h"
 
 using namespace jh;
 
@@ -542,9 +546,7 @@ int jh_predictor_hybridnet_forward(jh_predictor* pr, const float* crops_dev,
   if (heatmaps_padded_dev) {
     const Act& h = pr->kp->heat;
     const size_t total = (size_t)h.N * pr->J * pr->hs * pr->hs;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(export_padded_kernel, dim3(blocks), dim3(256), 0, s, h.p, heatmaps_padded_dev,
+    hipLaunchKernelGGL(export_padded_kernel, dim3(stride_blocks(total)), dim3(256), 0, s, h.p, heatmaps_padded_dev,
                        h.N, pr->J, h.Cp, pr->Hh);
     JH_CHECK_HIP(hipGetLastError());
   }

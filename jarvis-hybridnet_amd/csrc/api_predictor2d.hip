@@ -1,5 +1,8 @@
 // C ABI, the 2D predictor: CenterDetect, one crop, KeypointDetect and the per-joint arg-max of one camera.
 #include "predictor.h"
+#include "centers.h"
+#include "preprocess.h"
+#include "views2d.h"
 
 using namespace jh;
 

@@ -1,7 +1,7 @@
-// Device functions of the weighted DLT triangulation and of the projection, shared by geometry.hip (triangulation,
-// caller-supplied centres, 2D views, subject association) and joints3d.hip (per-joint robust triangulation): ONE
-// definition, so that a point triangulated from a subset of the observations has the bits of the triangulation run on
-// that subset, whichever kernel does it.
+// Device functions of the weighted DLT triangulation and of the projection, shared by centers.hip (triangulation,
+// caller-supplied centres), views2d.hip (2D views), subjects.hip (subject association) and joints3d.hip (per-joint
+// robust triangulation): ONE definition, so that a point triangulated from a subset of the observations has the bits
+// of the triangulation run on that subset, whichever kernel does it.
 #pragma once
 #include "jh_common.h"
 
@@ -114,6 +114,52 @@ __device__ __forceinline__ void dlt_solve(const double* ata, float* point) {
     for (int j = 0; j < 4; ++j) a[i][j] = 0.5 * (ata[i * 4 + j] + ata[j * 4 + i]);
   smallest_eigvec4(a, x);
   for (int k = 0; k < 3; ++k) point[k] = (float)(x[k] / x[3]);
+}
+
+// The pieces the two consensus kernels share (associate_subjects_kernel, joints3d_kernel): a hypothesis from two
+// observations, the point of its members, and the distance that decides support and is reported as the error.
+// A row below is the float[8] of one observation: r0[4], then r1[4] of dlt_rows.
+
+// |(u, v) - (x, y)| in pixels, one fp32 rounding per operation (also the reprojection error of the 2D views)
+__device__ __forceinline__ float pixel_distance(float u, float v, float x, float y) {
+  const float dx = __fsub_rn(u, x), dy = __fsub_rn(v, y);
+  return __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+}
+
+// the two-view DLT point of the rows ra, rb (summed in this order: the first camera, then the second)
+__device__ __forceinline__ void dlt_pair_point(const float* ra, const float* rb, float* X) {
+  double ata[16];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      double s = 0.0;
+      s += dlt_term(ra, ra + 4, i, j);
+      s += dlt_term(rb, rb + 4, i, j);
+      ata[i * 4 + j] = s;
+    }
+  dlt_solve(ata, X);
+}
+
+// The DLT point of the members among the cameras 0 .. C-1: A^T A summed in camera order, then dlt_solve.
+// row_of(c): the row of camera c's observation, or < 0 when the camera is not a member.  A non-member's term is
+// evaluated on the row `fallback` (any row that has been written) and SELECTED as an exact 0.0, like a masked camera's
+// in triangulate_body: s + 0.0 == s, so the point has the bits of the triangulation of the members alone.
+template <class RowOf>
+__device__ __forceinline__ void dlt_members_point(const float (*rows)[8], int C, int fallback, RowOf row_of,
+                                                  float* point) {
+  double ata[16];
+  for (int e = 0; e < 16; ++e) {
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) {
+      const int r = row_of(c);
+      const int sl = r >= 0 ? r : fallback;
+      const double term = dlt_term(rows[sl], rows[sl] + 4, e >> 2, e & 3);
+      s += r >= 0 ? term : 0.0;
+    }
+    ata[e] = s;
+  }
+  dlt_solve(ata, point);
 }
 
 }  // namespace jh

@@ -562,10 +562,7 @@ __global__ __launch_bounds__(256) void from_channel_last_kernel(const float* __r
 }
 
 int launch_to_channel_last(const float* src, const Act& dst, hipStream_t s) {
-  const size_t total = dst.elems();
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(to_channel_last_kernel, dim3(blocks), dim3(256), 0, s, src, dst.p, dst.N,
+  hipLaunchKernelGGL(to_channel_last_kernel, dim3(stride_blocks(dst.elems())), dim3(256), 0, s, src, dst.p, dst.N,
                      dst.C, dst.Cp, dst.pixels());
   JH_CHECK_HIP(hipGetLastError());
   return 0;
@@ -573,9 +570,7 @@ int launch_to_channel_last(const float* src, const Act& dst, hipStream_t s) {
 
 int launch_from_channel_last(const Act& src, float* dst, hipStream_t s) {
   const size_t total = (size_t)src.N * src.C * src.pixels();
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(from_channel_last_kernel, dim3(blocks), dim3(256), 0, s, src.p, dst, src.N,
+  hipLaunchKernelGGL(from_channel_last_kernel, dim3(stride_blocks(total)), dim3(256), 0, s, src.p, dst, src.N,
                      src.C, src.Cp, src.pixels());
   JH_CHECK_HIP(hipGetLastError());
   return 0;

@@ -25,6 +25,11 @@ constexpr int kWave = 64;
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline int cpad(int c) { return round_up(c, 8); }
+// blocks of 256 threads for a grid-stride loop over `total` elements: one thread per element, at most 8192 blocks
+inline int stride_blocks(size_t total) {
+  const size_t blocks = (total + 255) / 256;
+  return (int)(blocks < 8192 ? blocks : 8192);
+}
 
 // thread-local last error text, exported through jh_last_error()
 void set_error(const std::string& msg);
@@ -63,7 +68,7 @@ struct HeatLayout {
   size_t block_stride = 0, frame_stride = 0;
 };
 
-// The workspace of the joint-masked voxel gather (nets.h: launch_reproject_joint_masked), device pointers: sets [T][C]
+// The workspace of the joint-masked voxel gather (reproject.h: launch_reproject_joint_masked), device pointers: sets [T][C]
 // one bit per channel, ncam [T][Jp]; eff [T][J][C] bytes and cnt [T][J], optional, the same for a caller to read.
 struct JointSets {
   unsigned long long* sets = nullptr;

@@ -1,11 +1,12 @@
 // Per-joint robust triangulation from the cameras' 2D keypoints (csrc/joints3d.h; the definition: include/jarvis_hip.h,
-// jh_joints3d_params).  Two kernels behind the all-joint arg-max scan (geometry.hip, launch_joint_argmax_all):
+// jh_joints3d_params).  Two kernels behind the all-joint arg-max scan (views2d.hip, launch_joint_argmax_all):
 //   joint_observations_kernel / joint_peaks_refine_kernel   the observation (u, v, w) of every (frame set, camera,
 //       joint): views2d's pixel and confidence, the pixel moved by the centroid of the (2r+1)^2 window around the peak
 //   joints3d_kernel   the consensus over two-view triangulations and the triangulation of its members
 // The DLT and the projection are those of the triangulation (csrc/dlt.h), the merge of the scan's slices that of the 2D
 // views (csrc/views2d.h): one definition each, the same bits.
 #include "jh_common.h"
+#include "argmax.h"
 #include "dlt.h"
 #include "views2d.h"
 #include "joints3d.h"
@@ -71,7 +72,9 @@ __global__ void joint_observations_kernel(const float* __restrict__ pmax, const 
   float b;
   int m;
   argmax_combine(pmax, pidx, n, slices, Jp, j, &b, &m);
-  const int mx = m % Hh, my = m / Hh, P = Hh * Hh;
+  const int P = Hh * Hh;
+  int mx, my;
+  heat_xy(m, Hh, Hh, &mx, &my);
   const int x = mx * 2 + center_hm[(size_t)n * 2 + 0] - hw;
   const int y = my * 2 + center_hm[(size_t)n * 2 + 1] - hw;
   float ox = 0.f, oy = 0.f;
@@ -87,10 +90,10 @@ __global__ void joint_observations_kernel(const float* __restrict__ pmax, const 
 // camera, the two DLT rows (dlt_rows: the triangulation's, the pixel as given, weight w) and the pixel of every usable
 // observation (w > 0, w >= min_conf, finite pixel; an unused camera's row is (NaN, NaN, 0)).
 // The C (C - 1) / 2 pairs a < b of cameras are strided over the lanes: the two-view DLT point, its support (a usable
-// camera supports iff the point lies in front of it and projects within max_err of its pixel; NaN never does), and the
-// key  views << 50 | ~bits(cost) << 18 | ~(a * C + b)  whose maximum is the choice: most views, then the smallest cost
-// (a sum of non-negative floats: its bits order as it does), then the lowest (a, b).  The key is a total order on
-// distinct pairs and the wave maximum (xor shuffles) is exact, so the choice does not depend on timing.  Lane 0 then
+// camera supports iff the point lies in front of it and projects within max_err of its pixel; NaN never does), and
+// consensus_key (argmax.h) of the views, the cost and a * C + b, whose maximum is the choice: most views, then the
+// smallest cost, then the lowest (a, b).  The key is a total order on distinct pairs and the wave maximum
+// (wave_max_u64) is exact, so the choice does not depend on timing.  Lane 0 then
 // evaluates the winner again for its members and triangulates them -- A^T A summed in camera order, a non-member's term
 // selected as an exact 0.0 like a masked camera's in triangulate_body: the bits of the triangulation of the members
 // alone.  The eigen-solves run in fp64, one per pair and lane: at C = 12 two per lane, then two on lane 0.
@@ -115,8 +118,7 @@ __device__ __forceinline__ void j3_support(const J3Wave& w, const float* X, int 
     if (w.usable[c]) {
       float u, v, depth;
       project_one(w.M + c * 12, w.K + c * 9, w.D + c * 5, X[0], X[1], X[2], &u, &v, &depth);
-      const float dx = __fsub_rn(u, w.px[c]), dy = __fsub_rn(v, w.py[c]);
-      d = __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+      d = pixel_distance(u, v, w.px[c], w.py[c]);
       ok = depth > 0.f && d <= max_err;         // (NaN compares false)
     }
     if (ok) { ++n; sum = __fadd_rn(sum, d); }
@@ -124,21 +126,6 @@ __device__ __forceinline__ void j3_support(const J3Wave& w, const float* X, int 
   }
   *views = n;
   *cost = sum;
-}
-
-// the two-view DLT point of the cameras a < b
-__device__ __forceinline__ void j3_pair_point(const J3Wave& w, int a, int b, float* X) {
-  double ata[16];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      double s = 0.0;
-      s += dlt_term(w.rows[a], w.rows[a] + 4, i, j);
-      s += dlt_term(w.rows[b], w.rows[b] + 4, i, j);
-      ata[i * 4 + j] = s;
-    }
-  dlt_solve(ata, X);
 }
 
 __global__ __launch_bounds__(kJ3Waves * 64) void joints3d_kernel(
@@ -183,22 +170,15 @@ __global__ __launch_bounds__(kJ3Waves * 64) void joints3d_kernel(
       if (!w.usable[a] || !w.usable[b]) continue;
       float X[3], cost;
       int nv;
-      j3_pair_point(w, a, b, X);
+      dlt_pair_point(w.rows[a], w.rows[b], X);    // (a < b: the cameras in order)
       j3_support(w, X, C, max_err, &nv, &cost, nullptr);
-      const unsigned long long key = ((unsigned long long)nv << 50) |
-                                     ((unsigned long long)(~__float_as_uint(cost)) << 18) |
-                                     (unsigned long long)(0x3FFFF - (a * C + b));
-      best = best > key ? best : key;
+      best = max_u64(best, consensus_key(nv, cost, a * C + b));
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = (unsigned long long)__shfl_xor((long long)best, o);
-    best = best > other ? best : other;
-  }
+  best = wave_max_u64(best);
   if (!live || lane != 0) return;
   const size_t o = (size_t)t * J + j;
-  if ((int)(best >> 50) < min_views) {          // (also "no pair": best == 0)
+  if (consensus_views(best) < min_views) {      // (also "no pair": best == 0)
     const float nan = __int_as_float(0x7fc00000);
     for (int a = 0; a < 3; ++a) points[o * 3 + a] = nan;
     views_out[o] = 0;
@@ -206,30 +186,20 @@ __global__ __launch_bounds__(kJ3Waves * 64) void joints3d_kernel(
     for (int c = 0; c < C; ++c) members[o * C + c] = 0;
     return;
   }
-  const int idx = 0x3FFFF - (int)(best & 0x3FFFF), a = idx / C, b = idx - a * C;
+  const int idx = consensus_index(best), a = idx / C, b = idx - a * C;
   float X[3], cost, pt[3];
   int nv;
-  j3_pair_point(w, a, b, X);
+  dlt_pair_point(w.rows[a], w.rows[b], X);
   j3_support(w, X, C, max_err, &nv, &cost, w.member);
-  double ata[16];
-  for (int e = 0; e < 16; ++e) {
-    double s = 0.0;
-    for (int c = 0; c < C; ++c) {
-      const int sl = w.member[c] ? c : a;       // (a non-member's rows may never have been written)
-      const double term = dlt_term(w.rows[sl], w.rows[sl] + 4, e >> 2, e & 3);
-      s += w.member[c] ? term : 0.0;
-    }
-    ata[e] = s;
-  }
-  dlt_solve(ata, pt);
+  // (the fallback row is camera a's: a non-member's rows may never have been written)
+  dlt_members_point(w.rows, C, a, [&](int c) { return w.member[c] ? c : -1; }, pt);
   float esum = 0.f;
   for (int c = 0; c < C; ++c) {
     members[o * C + c] = w.member[c];
     if (!w.member[c]) continue;
     float u, v;
     project_one(w.M + c * 12, w.K + c * 9, w.D + c * 5, pt[0], pt[1], pt[2], &u, &v);
-    const float dx = __fsub_rn(u, w.px[c]), dy = __fsub_rn(v, w.py[c]);
-    esum = __fadd_rn(esum, __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy))));
+    esum = __fadd_rn(esum, pixel_distance(u, v, w.px[c], w.py[c]));
   }
   for (int k = 0; k < 3; ++k) points[o * 3 + k] = pt[k];
   views_out[o] = nv;

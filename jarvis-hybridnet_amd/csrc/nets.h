@@ -17,75 +17,6 @@
 
 namespace jh {
 
-// kernels implemented in other translation units
-// Calib (jh_common.h): the calibration, shared by all frames or one per frame.
-// Per-frame camera masks -- `mask`, here and below: [T][C] bytes on the device, nonzero = the camera
-// takes part in frame t; nullptr = all cameras.  The masked forms of the three kernels that sum over cameras are
-// kernels of their own (triangulate_masked_kernel, repro_gather_masked_kernel, repro_cube_masked_kernel) that share
-// their bodies with the plain kernels through a template parameter: the plain kernels keep their names, signatures and
-// code.
-// launch_reproject under a mask: frame t sums its unmasked cameras in camera order and divides by their number (IEEE
-// division; a frame without any camera gets an all-zero volume); at most 64 cameras then.
-int launch_reproject(const Calib& cal, const int* center3d, const int* center_hm, const float* heat, float2* coarse,
-                     float* vol, int* idx_out, int T, int C, int G, float spacing, int hs, int Jp, int heat_pad,
-                     int div255, const unsigned char* mask, hipStream_t s, const HeatLayout* layout = nullptr);
-// Per-joint camera masks -- joint_mask: [T][J][C] bytes on the device, nonzero = camera c counts for
-// joint j of frame t.  With a(t,c) the camera mask (1 without one), the effective set of joint j is
-// e(t,j,c) = a(t,c) && joint_mask[t][j][c]; an empty set falls back to a(t,.), and so do the padding channels.  One
-// launch turns (mask, joint_mask) into the workspace `js` -- sets [T][C] 64-bit channel sets, ncam [T][Jp] counts; eff
-// [T][J][C] bytes and cnt [T][J] optional copies for a caller to read -- and the voxel-row gather (a kernel of its own
-// on the shared body; there is no joint-masked cube form) sums every channel over its own cameras in camera order and
-// divides by its own count (IEEE division; no camera at all: 0).  At most 64 cameras and 64 channels.
-// (JointSets: jh_common.h)
-int launch_reproject_joint_masked(const Calib& cal, const int* center3d, const int* center_hm, const float* heat,
-                                  float2* coarse, float* vol, int* idx_out, int T, int C, int G, float spacing, int hs,
-                                  int J, int Jp, int heat_pad, int div255, const unsigned char* mask,
-                                  const unsigned char* joint_mask, const JointSets& js, hipStream_t s,
-                                  const HeatLayout* layout = nullptr);
-// (frames_cell: the one-pointer cell of a graph replay, or nullptr; with src.per_image the table of N image pointers,
-//  which must then be given -- preprocess.h: image_base)
-int launch_preprocess_resize(const void* frames, const FrameSource& src, float* out, int N, int H, int W, int S,
-                             const float* mean, const float* stdv, hipStream_t s,
-                             const void* const* frames_cell = nullptr);
-int launch_preprocess_crop(const void* frames, const FrameSource& src, const int* center_hm, float* out, int T,
-                           int Cloc, int C, int cam0, int H, int W, int B, const float* mean,
-                           const float* stdv, hipStream_t s, const void* const* frames_cell = nullptr);
-int launch_frames_to_bgr(const void* frames, const FrameSource& src, unsigned char* out, int N, int H, int W,
-                         hipStream_t s);
-int launch_center_argmax(const float* heat, float* det, int N, int Hh, int Wh, int Cp,
-                         hipStream_t s);
-int launch_center2d(const float* det, int* center_hm, int* valid, int T, float sx, float sy, int hw,
-                    int W, int H, hipStream_t s);
-int launch_joint_argmax(const float* heat, const int* center_hm, int* points, float* conf, int T,
-                        int J, int Jp, int Hh, int Wh, int hw, hipStream_t s);
-// Under a mask (n_active and n_detect are then required) a masked camera adds an exact 0.0 to A^T A (selected, never
-// multiplied: its detection may be NaN) and is not counted.  n_active[t]: unmasked cameras of frame t, n_detect[t]:
-// those of them with maxval > 50 (valid[t] = n_detect[t] >= 2).  Crop centres are written for every camera.
-int launch_triangulate(const float* det, const Calib& cal, float* center3d_f, int* center3d_i, int* center_hm,
-                       int* valid, int T, int C, float sx2, float sy2, float wdiv, int hw, int W, int H,
-                       const unsigned char* mask, int* n_active, int* n_detect, hipStream_t s);
-// Caller-supplied 3D centres (T,3) in place of the triangulation: the buffers launch_triangulate writes, det excepted
-// (geometry.hip: centers_kernel).
-int launch_centers(const float* centers, const Calib& cal, float* center3d_f, int* center3d_i, int* center_hm,
-                   int* valid, int T, int C, int hw, int W, int H, const unsigned char* mask, int* n_active,
-                   int* n_detect, hipStream_t s);
-int launch_project_points(const float* pts, const float* cam, const float* intr, const float* dist,
-                          float* uv, int P, int C, hipStream_t s);
-// The spread form of the soft-argmax tail (geometry.hip): workspace and outputs of T frame sets.
-// sums: softargmax_spread_sums(T, Jp) doubles with T * Jp 64-bit keys right behind them (`key`), one allocation;
-// valid: [T] validity flags (rows of a frame set that is not valid are NaN) or nullptr = all valid;
-// cov [T][J][6] (xx, xy, xz, yy, yz, zz; mm^2), peak [T][J][3] (mm), mass [T][J].
-struct SoftargmaxSpread {
-  double* sums = nullptr;
-  unsigned long long* key = nullptr;
-  const int* valid = nullptr;
-  float *cov = nullptr, *peak = nullptr, *mass = nullptr;
-};
-size_t softargmax_spread_sums(int T, int Jp);
-int launch_softargmax(const float* x, const int* center3d, double* partial, int* pmax,
-                      float* points, float* conf, float* heatmap_final, int T, int J, int Jp,
-                      int Gh, float spacing, float roi, hipStream_t s, const SoftargmaxSpread* spread = nullptr);
-
 typedef std::map<std::string, std::vector<float>> ParamMap;
 
 // Common machinery: owned device buffers, a zero-initialised scratch arena for

@@ -5,6 +5,7 @@
 #include <memory>
 #include "../../include/jarvis_hip.h"
 #include "nets.h"
+#include "softargmax.h"
 #include "joints3d.h"
 #include "workspace.h"
 

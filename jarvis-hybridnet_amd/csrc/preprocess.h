@@ -1,5 +1,5 @@
 // Per-pixel arithmetic of the frame pre-processing (jarvis/prediction/jarvis3D.py:143-145 resize +
-// normalise, :168-178 crop + normalise), shared by the stand-alone kernels (geometry.hip) and the stem
+// normalise, :168-178 crop + normalise), shared by the stand-alone kernels (preprocess.hip) and the stem
 // convolution that applies it while staging its input patch (stem.hip): ONE definition, so the fused
 // and the unfused path produce the same bits.
 //
@@ -473,5 +473,17 @@ struct StemSource {
   int H = 0, W = 0;                            // frame size
   float mean[3] = {0, 0, 0}, stdv[3] = {1, 1, 1};
 };
+
+// The stand-alone kernels (preprocess.hip).
+// (frames_cell: the one-pointer cell of a graph replay, or nullptr; with src.per_image the table of N image pointers,
+//  which must then be given -- image_base)
+int launch_preprocess_resize(const void* frames, const FrameSource& src, float* out, int N, int H, int W, int S,
+                             const float* mean, const float* stdv, hipStream_t s,
+                             const void* const* frames_cell = nullptr);
+int launch_preprocess_crop(const void* frames, const FrameSource& src, const int* center_hm, float* out, int T,
+                           int Cloc, int C, int cam0, int H, int W, int B, const float* mean,
+                           const float* stdv, hipStream_t s, const void* const* frames_cell = nullptr);
+int launch_frames_to_bgr(const void* frames, const FrameSource& src, unsigned char* out, int N, int H, int W,
+                         hipStream_t s);
 
 }  // namespace jh

@@ -1,7 +1,7 @@
 // Several subjects in one frame set (include/jarvis_hip.h: jh_subjects_params, jh_op_center_peaks,
 // jh_op_associate_subjects, jh_predictor_detect_subjects): the top-P local maxima of every camera's centre heat map in
 // place of its one arg-max, and their grouping across cameras by reprojection consistency in place of the one
-// triangulation.  Kernels and launchers: geometry.hip; the only reader of the parameters' ranges: subjects_check.
+// triangulation.  Kernels and launchers: subjects.hip; the only reader of the parameters' ranges: subjects_check.
 #pragma once
 #include "jh_common.h"
 

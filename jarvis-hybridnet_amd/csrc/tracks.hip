@@ -5,6 +5,7 @@
 // The arithmetic is spelled with the _rn intrinsics, one IEEE rounding per operation of the definition, so that a
 // float32 emulation of the header text gives the same bits.
 #include "jh_common.h"
+#include "argmax.h"
 #include "tracks.h"
 
 namespace jh {
@@ -17,7 +18,7 @@ __device__ __forceinline__ bool track_finite(float v) { return fabsf(v) < INFINI
 // eligible and touch no memory.
 //
 // Per frame set: the key of a pair is  bits(d) << 6 | lane  when the pair is eligible (d >= 0: its bit pattern orders
-// as it does) and all ones otherwise; the wave minimum (xor shuffles, as joints3d_kernel's key maximum) is the
+// as it does) and all ones otherwise; the wave minimum (wave_min_u64, argmax.h: xor shuffles) is the
 // smallest d, then the lowest k, then the lowest i -- a total order, no LDS atomics, so the result does not depend on
 // timing.  The winner's row and column take the all-ones key and the step repeats, at most K times.  Births are
 // resolved from two ballots (free slots, unmatched present detections) by every lane alike.
@@ -75,12 +76,7 @@ __global__ __launch_bounds__(64) void track_subjects_kernel(
     // 4: greedy match.  det: the detection slot k holds; slot: the slot detection i went to
     int det = -1, slot = -1;
     for (int r = 0; r < K; ++r) {
-      unsigned long long best = key;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = (unsigned long long)__shfl_xor((long long)best, o);
-        best = best < other ? best : other;
-      }
+      const unsigned long long best = wave_min_u64(key);
       if (best == kNone) break;                  // (wave-uniform)
       const int wk = (int)(best & 63) >> 3, wi = (int)(best & 7);
       if (k == wk) { det = wi; key = kNone; }

@@ -1,9 +1,15 @@
-// Per-camera 2D views of the 3D predictor (jh_predictor_views2d): the all-joint argmax in one pass over
-// [N][Hh*Wh][Jp] channel-last heat maps and the kernels that merge its slices (csrc/geometry.hip).
+// Arg-max of the keypoint heat maps (csrc/views2d.hip): the 2D predictor's one-joint-per-block form, and for the
+// per-camera 2D views of the 3D predictor (jh_predictor_views2d) the all-joint argmax in one pass over
+// [N][Hh*Wh][Jp] channel-last heat maps and the kernels that merge its slices.
 #pragma once
 #include "jh_common.h"
+#include "argmax.h"
 
 namespace jh {
+
+// heat [T][Hh][Wh][Jp] -> points [T][J][2] = (m % Hh, m / Wh) * 2 + center_hm - hw, conf [T][J] = min(max, 255) / 255
+int launch_joint_argmax(const float* heat, const int* center_hm, int* points, float* conf, int T,
+                        int J, int Jp, int Hh, int Wh, int hw, hipStream_t s);
 
 // How the scan cuts a shape: threads per block, pixels per slice, slices per image.
 struct ScanShape { int threads = 0, ppb = 0, slices = 0; };
@@ -21,13 +27,8 @@ int launch_views2d_final(const float* pmax, const int* pidx, const int* center_h
                          float* conf2d, float* reproj, float* err, unsigned char* used, int T, int C, int J, int Jp,
                          int Hh, int Wh, int hw, hipStream_t s);
 
-// Device side of the scan, for the kernels that read its partials (geometry.hip: the 2D views; joints3d.hip: the
-// observations of the joint triangulation): the order and the merge of the slices.
-// (value descending, index ascending): total on non-NaN values; NaN never wins
-__device__ __forceinline__ void argmax_take(float v, int i, float& best, int& bi) {
-  if (v > best || (v == best && i < bi)) { best = v; bi = i; }
-}
-
+// Device side of the scan, for the kernels that read its partials (views2d.hip: the 2D views; joints3d.hip: the
+// observations of the joint triangulation): the merge of the slices, in the order of argmax_take (argmax.h).
 // (max, index) of channel j of image n over its slices (the partials of launch_joint_argmax_all)
 __device__ __forceinline__ void argmax_combine(const float* __restrict__ pmax, const int* __restrict__ pidx,
                                                int n, int slices, int Jp, int j, float* best, int* bi) {
