@@ -902,6 +902,79 @@ int jh_predictor2d_forward_images(jh_predictor2d* pr, const void* const* images_
                                   const jh_yuv_surface* yuv, const jh_sensor_surface* sensor,
                                   int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
 
+/* ---- pixel surfaces: RGB in any byte order, 4-byte and planar RGB, grey, and YUV that is not 4:2:0 (additive, ABI 4)
+ * ONE description for what Python imaging libraries, cameras and capture cards hand out besides BGR and YUV 4:2:0,
+ * read in place.  An image is three 8-bit components per pixel -- R, G, B (JH_PIXEL_RGB) or Y, U, V (JH_PIXEL_YUV) --
+ * and every component has its own address rule inside the `image_stride` bytes of ONE h x w image:
+ *   component k of pixel (y, x) is the byte at offset[k] + (y >> ys[k]) * pitch[k] + (x >> xs[k]) * step[k].
+ * Frames are (T,cam_n) such images back to back (the 2D predictor: (T)), image n at byte n * image_stride.
+ * Chroma is replicated: pixel (y, x) takes sample (y >> ys, x >> xs), as the 4:2:0 forms do and as OpenCV's
+ * COLOR_YUV2BGR_YUY2 does.  JH_PIXEL_YUV converts with the formula and the four constant rows printed for
+ * jh_yuv_surface above (same table, same int32 arithmetic), selected by (matrix, range).  The (R, G, B) bytes then take
+ * the uint8 path unchanged: the result equals, bit for bit, jh_predictor_forward_u8 on the converted frames.
+ * Components may interleave and may coincide (grey), so there is no overlap rule.  No byte before an image's base and
+ * none at or beyond image_stride is ever addressed; bytes inside the image that are no component (an alpha byte, pitch
+ * padding, gaps) may hold anything and never reach a result.
+ * The common layouts as values of the fields, for h x w tight (cw = ceil(w/2), ch = ceil(h/2)):
+ *   layout      offset (R,G,B resp. Y,U,V)            step     pitch                 xs      ys
+ *   rgb24       0, 1, 2                               3        3w                    0       0
+ *   bgr24       2, 1, 0                               3        3w                    0       0
+ *   bgra/bgr0   2, 1, 0   (rgba 0,1,2; argb 1,2,3; abgr 3,2,1)  4   4w               0       0
+ *   planar RGB  0, hw, 2hw                            1        w                     0       0
+ *   gbrp        R 2hw, G 0, B hw                      1        w                     0       0
+ *   grey        0, 0, 0                               1        w                     0       0
+ *   yuyv422     Y 0, U 1, V 3  (yvyu: U 3, V 1)       2, 4, 4  4cw                   0,1,1   0
+ *   uyvy422     Y 1, U 0, V 2                         2, 4, 4  4cw                   0,1,1   0
+ *   nv16        Y 0, U hw, V hw+1                     1, 2, 2  w, 2cw, 2cw           0,1,1   0
+ *   yuv422p     Y 0, U hw, V hw + h cw                1        w, cw, cw             0,1,1   0
+ *   yuv444p     0, hw, 2hw                            1        w                     0       0
+ *   nv24        Y 0, U hw, V hw+1                     1, 2, 2  w, 2w, 2w             0       0
+ *   yuv440p     Y 0, U hw, V hw + ch w                1        w                     0       0,1,1
+ *   yuv411p     Y 0, U hw, V hw + h ceil(w/4)         1        w, ceil(w/4) twice    0,2,2   0
+ *   4:2:0       as jh_yuv_surface places them         1 or 2   as there              0,1,1   0,1,1
+ * jh_pixel_surface_check (no GPU needed) is the validation every entry point applies: h, w > 0 of ANY parity (a
+ * subsampled plane is ceil wide / high); colour known; JH_PIXEL_YUV: matrix and range known, JH_PIXEL_RGB: both 0;
+ * sample == JH_SAMPLE_U8 (every other value refused: room for later); step[k] 1 .. 8; xs[k], ys[k] 0 .. 2;
+ * JH_PIXEL_RGB: every shift 0; JH_PIXEL_YUV: xs[0] == ys[0] == 0, xs[1] == xs[2], ys[1] == ys[2]; offset[k] >= 0;
+ * pitch[k] >= ((w-1) >> xs[k]) * step[k] + 1;
+ * offset[k] + ((h-1) >> ys[k]) * pitch[k] + ((w-1) >> xs[k]) * step[k] + 1 <= image_stride.
+ * Returns 0, or nonzero with jh_last_error() set.
+ * The entry points take EXACTLY ONE OF frames_dev (contiguous, image n at n * image_stride) and images_host + n_images
+ * (one device pointer per image, as jh_predictor_forward_images; an image may start at any address and image_stride is
+ * then only the extent every component ends within).  mask_dev as in jh_predictor_forward_masked, or NULL.  Everything
+ * that follows a forward (jh_predictor_views2d, set_centers, set_spread, set_joint_mask, triangulate_joints, per-frame
+ * calibration) follows these as it follows any forward.  A graph-replaying predictor keeps captured graphs of its own
+ * for this form -- contiguous and per image, each unmasked and masked --; a call whose description differs from the
+ * recorded one records again, and alternating with any other format re-records neither.
+ * Out of scope: the staged jh_predictor_stage_* entries, the camera-sharded path, and samples wider than a byte. */
+#define JH_PIXEL_RGB 0   /* components 0,1,2 are R,G,B bytes */
+#define JH_PIXEL_YUV 1   /* components 0,1,2 are Y,U,V; converted as jh_yuv_surface converts */
+typedef struct jh_pixel_surface {
+  int64_t image_stride;          /* bytes from image n to image n+1 */
+  int64_t offset[3], pitch[3];   /* component k of pixel (y,x): the byte at                        */
+  int32_t step[3];               /*   offset[k] + (y >> ys[k]) * pitch[k] + (x >> xs[k]) * step[k] */
+  int32_t xs[3], ys[3];
+  int32_t colour;                /* JH_PIXEL_RGB / JH_PIXEL_YUV */
+  int32_t matrix, range;         /* JH_YUV_*; must be 0 for JH_PIXEL_RGB */
+  int32_t sample;                /* JH_SAMPLE_U8 only; every other value refused (room for later) */
+} jh_pixel_surface;
+int jh_pixel_surface_check(const jh_pixel_surface* surface, int h, int w);
+/* unit-test helper, as jh_op_yuv_surface_to_bgr: n images -> (n,h,w,3) uint8 BGR; synchronises */
+int jh_op_pixels_to_bgr(const uint8_t* frames_dev, const jh_pixel_surface* surface, int n, int h, int w,
+                        uint8_t* out_bgr_dev, void* stream);
+int jh_predictor_forward_pixels(jh_predictor* pr, const uint8_t* frames_dev, const void* const* images_host,
+                                int n_images, const jh_pixel_surface* surface, const uint8_t* mask_dev /* or NULL */,
+                                float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream);
+/* the outputs of jh_predictor2d_forward_surface */
+int jh_predictor2d_forward_pixels(jh_predictor2d* pr, const uint8_t* frames_dev, const void* const* images_host,
+                                  int n_images, const jh_pixel_surface* surface, int32_t* points_dev, float* conf_dev,
+                                  int32_t* valid_dev, void* stream);
+/* jh_predictor_detect_subjects with the description in place of (format, yuv, sensor) */
+int jh_predictor_detect_subjects_pixels(jh_predictor* pr, const uint8_t* frames_dev, const void* const* images_host,
+                                        int n_images, const jh_pixel_surface* surface, const uint8_t* mask_dev,
+                                        const jh_subjects_params* params, float* centers_dev, int32_t* views_dev,
+                                        int32_t* members_dev, float* error_dev, float* peaks_dev, void* stream);
+
 /* ---- per-launch timing (HIP events on the launch stream; used by bench.py for
  * the roofline figures).  begin() switches recording on for every kernel the
  * library launches from this process; end() synchronises and returns the number

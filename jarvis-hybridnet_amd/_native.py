@@ -54,6 +54,17 @@ class SensorSurfaceStruct(ctypes.Structure):
 
 assert ctypes.sizeof(SensorSurfaceStruct) == 32
 
+
+class PixelSurfaceStruct(ctypes.Structure):
+    """jh_pixel_surface of include/jarvis_hip.h (built by pixel_surface.PixelSurface.struct())."""
+    _fields_ = [("image_stride", ctypes.c_int64), ("offset", ctypes.c_int64 * 3), ("pitch", ctypes.c_int64 * 3),
+                ("step", ctypes.c_int32 * 3), ("xs", ctypes.c_int32 * 3), ("ys", ctypes.c_int32 * 3),
+                ("colour", ctypes.c_int32), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32),
+                ("sample", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(PixelSurfaceStruct) == 112
+
 class OpOperand(ctypes.Structure):
     """jh_op_operand of include/jarvis_hip.h (test entry jh_op_conv_operand): host pointers as raw addresses."""
     _fields_ = [("in_sums_host", c_void_p), ("in_act", ctypes.c_int32), ("latency_class", ctypes.c_int32),
@@ -204,6 +215,19 @@ _SIGS = {
                                               c_void_p, c_void_p, c_void_p]),
     "jh_op_sensor_to_bgr": (c_int, [c_void_p, ctypes.POINTER(SensorSurfaceStruct), c_int, c_int, c_int, c_void_p,
                                     c_void_p]),
+    "jh_pixel_surface_check": (c_int, [ctypes.POINTER(PixelSurfaceStruct), c_int, c_int]),
+    "jh_op_pixels_to_bgr": (c_int, [c_void_p, ctypes.POINTER(PixelSurfaceStruct), c_int, c_int, c_int, c_void_p,
+                                    c_void_p]),
+    "jh_predictor_forward_pixels": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_int,
+                                            ctypes.POINTER(PixelSurfaceStruct), c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
+    "jh_predictor2d_forward_pixels": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_int,
+                                              ctypes.POINTER(PixelSurfaceStruct), c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
+    "jh_predictor_detect_subjects_pixels": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_int,
+                                                    ctypes.POINTER(PixelSurfaceStruct), c_void_p,
+                                                    ctypes.POINTER(SubjectsParamsStruct), c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_forward_masked": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p]),
     "jh_predictor_forward_images": (c_int, [c_void_p, ctypes.POINTER(c_void_p), c_int, c_int,
@@ -314,6 +338,10 @@ FRAME_CODES = {"rgb": 0, "bgr": 1, "i420": 2, "nv12": 3, "surface": 4, "sensor":
 FRAME_FORMATS = {k: FRAME_CODES[k] for k in ("bgr", "i420", "nv12")}       # the names a frame_format argument takes
 YUV_FORMATS = ("i420", "nv12")
 FRAME_SURFACE, FRAME_SENSOR = FRAME_CODES["surface"], FRAME_CODES["sensor"]
+# What Frames.fmt carries for image_stride bytes per image read through a PixelSurface.  No JH_FRAME_* code of the header:
+# the form has entry points of its own (jh_predictor_forward_pixels and its like), and this value never reaches a C
+# `format` argument.
+FRAME_PIXELS = 8
 
 
 class Frames(NamedTuple):
@@ -345,20 +373,21 @@ def yuv_format(name):
 def surface(layout):
     """The `surface` argument of the forms that take described frames only (forward_surface): not None."""
     if layout is None:
-        raise ValueError("surface must be a YuvSurface or a SensorSurface, got None")
+        raise ValueError("surface must be a YuvSurface or a SensorSurface (or a PixelSurface), got None")
     return layout
 
 
 def check_layout(layout, frame_format=None, hw=None):
-    """A frame_layout argument checked: None stays None; otherwise a yuv_surface.YuvSurface or a
-    sensor_surface.SensorSurface, not combined with frame_format 'i420' / 'nv12' (the layout says what the bytes
+    """A frame_layout argument checked: None stays None; otherwise a yuv_surface.YuvSurface, a
+    sensor_surface.SensorSurface or a pixel_surface.PixelSurface, not combined with frame_format 'i420' / 'nv12' (the layout says what the bytes
     are) and of the frame size `hw` when that is given.  ValueError otherwise."""
     if layout is None:
         return None
+    from .pixel_surface import PixelSurface
     from .sensor_surface import SensorSurface
     from .yuv_surface import YuvSurface
-    if not isinstance(layout, (YuvSurface, SensorSurface)):
-        raise ValueError("frame_layout must be a YuvSurface or a SensorSurface or None, got %r"
+    if not isinstance(layout, (YuvSurface, SensorSurface, PixelSurface)):
+        raise ValueError("frame_layout must be a YuvSurface or a SensorSurface (or a PixelSurface) or None, got %r"
                          % (type(layout).__name__,))
     if frame_format in YUV_FORMATS:
         raise ValueError("frame_layout describes the bytes itself: do not combine it with frame_format=%r"
@@ -373,6 +402,8 @@ def describe_shape(shape, dtype, lead, frame_format=None, frame_layout=None, hw=
     """THE rules of what frames are, on a shape and a dtype alone (no tensor, no device) -> Frames without bytes.
     lead: the leading dimensions, None entries match any size.  After them one image is
       frame_layout (a YuvSurface / SensorSurface)  uint8 (image_stride,); with at_least, image_stride bytes or more
+      frame_layout (a PixelSurface)                 likewise, or uint8 of ANY shape with exactly image_stride bytes
+                                                    ((H,W,3), (H,W,4), (3,H,W) tensors go in as they are)
       frame_format 'i420' / 'nv12'                  uint8 (3H/2, W), H and W even
       dtype uint8                                   BGR (H, W, 3)
       otherwise                                     fp32 RGB (3, H, W); frame_format 'bgr' refuses it
@@ -389,8 +420,11 @@ def describe_shape(shape, dtype, lead, frame_format=None, frame_layout=None, hw=
     H, W = hw if hw is not None else ("H", "W")
     hint = ""
     if layout is not None:
+        from .pixel_surface import PixelSurface
         from .sensor_surface import SensorSurface
         kind, error = "sensor" if isinstance(layout, SensorSurface) else "surface", ValueError
+        if isinstance(layout, PixelSurface):
+            kind = "pixels"
         what = "frames of a %s (%simage_stride = %d bytes per image)" % (
             type(layout).__name__, "at least " if at_least else "", layout.image_stride)
         want, tail = torch.uint8, ("image_stride" if at_least else layout.image_stride,)
@@ -416,6 +450,11 @@ def describe_shape(shape, dtype, lead, frame_format=None, frame_layout=None, hw=
         not isinstance(w, int) or int(g) == w for g, w in zip(shape, full))
     if fits and at_least and layout is not None:
         fits = int(shape[-1]) >= layout.image_stride
+    if not fits and kind == "pixels" and shape is not None and dtype == want and len(shape) > len(lead):
+        # any trailing shape of exactly image_stride bytes
+        fits = math.prod(int(n) for n in shape[len(lead):]) == layout.image_stride and all(
+            w is None or int(g) == w for g, w in zip(shape, lead))
+        hint = " (or any trailing shape of exactly image_stride bytes)"
     if not fits:
         raise error("%s must be %s of shape %s; got %s%s" % (
             what, "uint8" if want == torch.uint8 else "float32", _shape_text(lead, tail),
@@ -427,7 +466,7 @@ def describe_shape(shape, dtype, lead, frame_format=None, frame_layout=None, hw=
         H = rows // 3 * 2
     elif hw is None and layout is None:
         H, W = (int(shape[-3]), int(shape[-2])) if kind == "bgr" else (int(shape[-2]), int(shape[-1]))
-    return Frames(FRAME_CODES[kind], H, W, layout, tuple(int(n) for n in shape[:len(lead)]))
+    return Frames(FRAME_PIXELS if kind == "pixels" else FRAME_CODES[kind], H, W, layout, tuple(int(n) for n in shape[:len(lead)]))
 
 
 def _shape_text(lead, tail):
@@ -483,7 +522,10 @@ def forward_symbol(which, fmt, masked=False, per_image=False):
     'jh_predictor2d' (which takes no masks); fmt: the JH_FRAME_* code; masked: a camera mask is given; per_image: the
     frames are separately placed images.  Per-image frames of any format have one entry point, so have described
     surfaces and sensor images (their 3D forms take the mask, NULL for none); a mask on the fixed formats goes
-    through the 3D predictor's masked entry point; otherwise every fixed format has its own."""
+    through the 3D predictor's masked entry point; otherwise every fixed format has its own.  Pixel surfaces have one
+    entry point for contiguous and per-image frames."""
+    if fmt == FRAME_PIXELS:
+        return which + "_forward_pixels"
     if per_image:
         return which + "_forward_images"
     if fmt in (FRAME_SURFACE, FRAME_SENSOR):
@@ -502,7 +544,12 @@ def call_forward(which, handle, frames, mask, outs):
         raise ValueError("%s takes no camera mask" % which)
     name = forward_symbol(which, frames.fmt, mask is not None, frames.images is not None)
     struct = frames.layout.struct() if frames.layout is not None else None
-    if frames.images is not None:
+    if frames.fmt == FRAME_PIXELS:
+        # (exactly one of the contiguous frames and the table of per-image pointers)
+        n = 0 if frames.images is None else len(frames.images)
+        table = (c_void_p * n)(*(t.data_ptr() for t in frames.images)) if n else None
+        args = (ptr(frames.data) if not n else None, table, n, struct) + ((ptr(mask),) if masks else ())
+    elif frames.images is not None:
         table = (c_void_p * len(frames.images))(*(t.data_ptr() for t in frames.images))
         args = (table, len(frames.images), frames.fmt, struct if frames.fmt == FRAME_SURFACE else None,
                 struct if frames.fmt == FRAME_SENSOR else None) + ((ptr(mask),) if masks else ())

@@ -388,10 +388,14 @@ class NativePredictor:
         table = None
         if frames.images is not None:
             table = (N.c_void_p * len(frames.images))(*(t.data_ptr() for t in frames.images))
-        N.check(N.lib().jh_predictor_detect_subjects(
-            self.handle, N.ptr(frames.data), table, 0 if table is None else len(frames.images), frames.fmt,
-            struct if frames.fmt == N.FRAME_SURFACE else None, struct if frames.fmt == N.FRAME_SENSOR else None,
-            N.ptr(mask), ctypes.byref(params), *(N.ptr(t) for t in out), N.ptr(peaks), N.stream()))
+        where = (self.handle, N.ptr(frames.data), table, 0 if table is None else len(frames.images))
+        rest = (N.ptr(mask), ctypes.byref(params), *(N.ptr(t) for t in out), N.ptr(peaks), N.stream())
+        if frames.fmt == N.FRAME_PIXELS:                     # (a PixelSurface: the entry point of its own)
+            N.check(N.lib().jh_predictor_detect_subjects_pixels(*where, struct, *rest))
+        else:
+            N.check(N.lib().jh_predictor_detect_subjects(
+                *where, frames.fmt, struct if frames.fmt == N.FRAME_SURFACE else None,
+                struct if frames.fmt == N.FRAME_SENSOR else None, *rest))
         if mask is not None:
             mask.record_stream(torch.cuda.current_stream())     # (read in place by the enqueued kernel)
         return (out, peaks) if return_peaks else out

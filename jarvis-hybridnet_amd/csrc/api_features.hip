@@ -394,11 +394,13 @@ int jh_op_associate_subjects(const float* peaks_dev, int t, int cams, const floa
   return 0;
 }
 
-int jh_predictor_detect_subjects(jh_predictor* pr, const void* frames_dev, const void* const* images_host, int n_images,
-                                 int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor,
-                                 const uint8_t* mask_dev, const jh_subjects_params* params, float* centers_dev,
-                                 int32_t* views_dev, int32_t* members_dev, float* error_dev, float* peaks_dev,
-                                 void* stream) {
+// jh_predictor_detect_subjects and jh_predictor_detect_subjects_pixels: the frames' description is (format, yuv,
+// sensor) or `pixels` (call_source)
+static int detect_subjects_impl(jh_predictor* pr, const void* frames_dev, const void* const* images_host, int n_images,
+                                int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor,
+                                const jh_pixel_surface* pixels, const uint8_t* mask_dev,
+                                const jh_subjects_params* params, float* centers_dev, int32_t* views_dev,
+                                int32_t* members_dev, float* error_dev, float* peaks_dev, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   JH_REQUIRE(pr, "jh_predictor_detect_subjects: null predictor");
   SubjectsParams sp;
@@ -410,8 +412,8 @@ int jh_predictor_detect_subjects(jh_predictor* pr, const void* frames_dev, const
              "jh_predictor_detect_subjects: give frames_dev or images_host, not both");
   const auto& c = pr->cfg;
   FrameSource fs;
-  if (call_source("jh_predictor_detect_subjects", format, yuv, sensor, c.img_h, c.img_w, images_host != nullptr, &fs))
-    return 1;
+  if (call_source("jh_predictor_detect_subjects", format, yuv, sensor, pixels, c.img_h, c.img_w,
+                  images_host != nullptr, &fs)) return 1;
   const int N = pr->T * pr->C;
   const Act& h = pr->center->heat;
   if (!pr->subj_peaks) {
@@ -445,6 +447,24 @@ int jh_predictor_detect_subjects(jh_predictor* pr, const void* frames_dev, const
     JH_CHECK_HIP(hipMemcpyAsync(peaks_dev, pr->subj_peaks, (size_t)N * sp.max_peaks * 3 * sizeof(float),
                                 hipMemcpyDeviceToDevice, s));
   return 0;
+}
+
+int jh_predictor_detect_subjects(jh_predictor* pr, const void* frames_dev, const void* const* images_host, int n_images,
+                                 int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor,
+                                 const uint8_t* mask_dev, const jh_subjects_params* params, float* centers_dev,
+                                 int32_t* views_dev, int32_t* members_dev, float* error_dev, float* peaks_dev,
+                                 void* stream) {
+  return detect_subjects_impl(pr, frames_dev, images_host, n_images, format, yuv, sensor, nullptr, mask_dev, params,
+                              centers_dev, views_dev, members_dev, error_dev, peaks_dev, stream);
+}
+
+int jh_predictor_detect_subjects_pixels(jh_predictor* pr, const uint8_t* frames_dev, const void* const* images_host,
+                                        int n_images, const jh_pixel_surface* surface, const uint8_t* mask_dev,
+                                        const jh_subjects_params* params, float* centers_dev, int32_t* views_dev,
+                                        int32_t* members_dev, float* error_dev, float* peaks_dev, void* stream) {
+  JH_REQUIRE(surface, "jh_predictor_detect_subjects_pixels: null jh_pixel_surface");
+  return detect_subjects_impl(pr, frames_dev, images_host, n_images, kSrcPixels, nullptr, nullptr, surface, mask_dev,
+                              params, centers_dev, views_dev, members_dev, error_dev, peaks_dev, stream);
 }
 
 }  // extern "C"

@@ -52,22 +52,28 @@ static int yuv_surface_check(const jh_yuv_surface* sp, int h, int w) {
   return 0;
 }
 
+// The fixed-point constants of a checked (matrix, range) into a description that carries them (YuvSurface,
+// PixelSurface): {Y0, CY, CVR, CUB, CUG, CVG}.  BT.601 limited = OpenCV's literals (yuv_to_rgb8); the others
+// round(x * 2^20) of the float64 matrix (include/jarvis_hip.h)
+template <class S>
+static void yuv_constants(int matrix, int range, S& a) {
+  static const int k[2][2][6] = {{{16, 1220542, 1673527, 2116026, -409993, -852492},
+                                  {0, 1048576, 1470104, 1858077, -360853, -748826}},
+                                 {{16, 1220945, 1879825, 2215014, -223607, -558796},
+                                  {0, 1048576, 1651297, 1945738, -196424, -490864}}};
+  const int* c = k[matrix][range];
+  a.y0 = c[0]; a.cy = c[1]; a.cvr = c[2]; a.cub = c[3]; a.cug = c[4]; a.cvg = c[5];
+}
+
 // FrameSource of a described YUV 4:2:0 surface of h x w images: the check above, then the description as the kernels
 // take it (preprocess.h) -- the layout and the constants of its (matrix, range)
 int jh::frame_source(const jh_yuv_surface* sp, int h, int w, FrameSource* out) {
   if (yuv_surface_check(sp, h, w)) return 1;
   const jh_yuv_surface& q = *sp;
-  // {Y0, CY, CVR, CUB, CUG, CVG}: BT.601 limited = OpenCV's literals (yuv_to_rgb8); the others round(x * 2^20) of
-  // the float64 matrix (include/jarvis_hip.h)
-  static const int k[2][2][6] = {{{16, 1220542, 1673527, 2116026, -409993, -852492},
-                                  {0, 1048576, 1470104, 1858077, -360853, -748826}},
-                                 {{16, 1220945, 1879825, 2215014, -223607, -558796},
-                                  {0, 1048576, 1651297, 1945738, -196424, -490864}}};
-  const int* c = k[q.matrix][q.range];
   const auto fill = [&](YuvSurface& a) {
     a.image_stride = q.image_stride; a.y_offset = q.y_offset; a.y_pitch = q.y_pitch;
     a.u_offset = q.u_offset; a.v_offset = q.v_offset; a.c_pitch = q.c_pitch; a.c_step = q.c_step;
-    a.y0 = c[0]; a.cy = c[1]; a.cvr = c[2]; a.cub = c[3]; a.cug = c[4]; a.cvg = c[5];
+    yuv_constants(q.matrix, q.range, a);
   };
   // the sample code chooses the form: 16-bit samples are kSrcYuvWide, kernels of their own
   if (const SampleCode sc = sample_code(q.sample); sc.kind == kSampleU16) {
@@ -131,6 +137,65 @@ int jh::frame_source(const jh_sensor_surface* sp, int h, int w, FrameSource* out
   return 0;
 }
 
+// The one validation of a described pixel surface of h x w images (include/jarvis_hip.h): every pixel entry point and
+// jh_pixel_surface_check.  Host arithmetic only.  (__int128: a component's last byte may not wrap for any int64 field.)
+static int pixel_surface_check(const jh_pixel_surface* sp, int h, int w) {
+  JH_REQUIRE(sp, "null jh_pixel_surface");
+  const jh_pixel_surface& q = *sp;
+  JH_REQUIRE(h > 0 && w > 0, "pixel surfaces need a positive height and width");
+  JH_REQUIRE(q.colour == JH_PIXEL_RGB || q.colour == JH_PIXEL_YUV, "jh_pixel_surface.colour: unknown");
+  if (q.colour == JH_PIXEL_YUV) {
+    JH_REQUIRE(q.matrix == JH_YUV_BT601 || q.matrix == JH_YUV_BT709, "jh_pixel_surface.matrix: unknown");
+    JH_REQUIRE(q.range == JH_YUV_LIMITED || q.range == JH_YUV_FULL, "jh_pixel_surface.range: unknown");
+  } else {
+    JH_REQUIRE(q.matrix == 0 && q.range == 0, "jh_pixel_surface: matrix and range must be 0 for JH_PIXEL_RGB");
+  }
+  JH_REQUIRE(q.sample == JH_SAMPLE_U8, "jh_pixel_surface.sample must be JH_SAMPLE_U8");
+  for (int k = 0; k < 3; ++k)
+    JH_REQUIRE(q.step[k] >= 1 && q.step[k] <= 8, "jh_pixel_surface.step must be 1 .. 8");
+  for (int k = 0; k < 3; ++k)
+    JH_REQUIRE(q.xs[k] >= 0 && q.xs[k] <= 2 && q.ys[k] >= 0 && q.ys[k] <= 2, "jh_pixel_surface.xs and ys must be 0 .. 2");
+  if (q.colour == JH_PIXEL_RGB) {
+    for (int k = 0; k < 3; ++k)
+      JH_REQUIRE(q.xs[k] == 0 && q.ys[k] == 0, "jh_pixel_surface: R, G and B are not subsampled (xs and ys must be 0)");
+  } else {
+    JH_REQUIRE(q.xs[0] == 0 && q.ys[0] == 0 && q.xs[1] == q.xs[2] && q.ys[1] == q.ys[2],
+               "jh_pixel_surface: Y is not subsampled, and U and V are subsampled alike");
+  }
+  for (int k = 0; k < 3; ++k) JH_REQUIRE(q.offset[k] >= 0, "jh_pixel_surface.offset must not be negative");
+  for (int k = 0; k < 3; ++k)
+    JH_REQUIRE(q.pitch[k] >= (int64_t)((w - 1) >> q.xs[k]) * q.step[k] + 1,
+               "jh_pixel_surface.pitch is smaller than a row of the component");
+  for (int k = 0; k < 3; ++k)
+    JH_REQUIRE((__int128)q.offset[k] + (__int128)((h - 1) >> q.ys[k]) * q.pitch[k] +
+                       (__int128)((w - 1) >> q.xs[k]) * q.step[k] + 1 <= q.image_stride,
+               "jh_pixel_surface: a component ends beyond image_stride");
+  return 0;
+}
+
+// FrameSource of a described pixel surface of h x w images: the check above, then the description as the kernels take
+// it -- the address rules, for Y U V the constants of its (matrix, range), and the distinct component bytes per pixel
+// (components that share one address rule, as the three of a grey image do, count once)
+int jh::frame_source(const jh_pixel_surface* sp, int h, int w, FrameSource* out) {
+  if (pixel_surface_check(sp, h, w)) return 1;
+  const jh_pixel_surface& q = *sp;
+  SrcDesc<kSrcPixels> a;
+  a.image_stride = q.image_stride;
+  a.bytes = 0.f;
+  for (int k = 0; k < 3; ++k) {
+    a.offset[k] = q.offset[k]; a.pitch[k] = q.pitch[k]; a.step[k] = q.step[k]; a.xs[k] = q.xs[k]; a.ys[k] = q.ys[k];
+    bool seen = false;
+    for (int j = 0; j < k; ++j)
+      seen = seen || (q.offset[j] == q.offset[k] && q.pitch[j] == q.pitch[k] && q.step[j] == q.step[k] &&
+                      q.xs[j] == q.xs[k] && q.ys[j] == q.ys[k]);
+    if (!seen) a.bytes += 1.f / (float)(1 << (q.xs[k] + q.ys[k]));
+  }
+  a.yuv = q.colour == JH_PIXEL_YUV;
+  if (a.yuv) yuv_constants(q.matrix, q.range, a);
+  out->fmt = kSrcPixels; out->desc = a;
+  return 0;
+}
+
 static_assert(JH_FRAME_RGB_F32 == kSrcRgbF32 && JH_FRAME_BGR_U8 == kSrcBgrU8 && JH_FRAME_I420 == kSrcI420 &&
                   JH_FRAME_NV12 == kSrcNV12, "frame format codes of the C ABI are preprocess.h's SRC");
 
@@ -156,9 +221,16 @@ static_assert(JH_FRAME_SURFACE == kSrcYuvSurface && JH_FRAME_SENSOR == kSrcSenso
 // like): image_stride of a description is then only the extent every plane ends within; every image is image 0 of its
 // own pointer, so a semi-planar surface takes the 2-byte chroma load whatever the parity of that extent (the kernel
 // looks at the image's own base).
-int jh::call_source(const char* who, int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor, int h,
-                    int w, bool per_image, FrameSource* out) {
+// pixels: the third description (the *_pixels entry points, whose frames have no JH_FRAME_* code): it comes alone.
+int jh::call_source(const char* who, int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor,
+                    const jh_pixel_surface* pixels, int h, int w, bool per_image, FrameSource* out) {
   const std::string name(who);
+  if (pixels) {
+    JH_REQUIRE(!yuv && !sensor, name + ": a jh_pixel_surface comes with no other description");
+    if (frame_source(pixels, h, w, out)) return 1;
+    out->per_image = per_image;
+    return 0;
+  }
   JH_REQUIRE(format >= JH_FRAME_RGB_F32 && format <= JH_FRAME_SENSOR, name + ": unknown frame format");
   JH_REQUIRE((yuv != nullptr) == (format == JH_FRAME_SURFACE),
              name + ": JH_FRAME_SURFACE, and no other format, comes with a jh_yuv_surface");
@@ -218,6 +290,20 @@ int jh_yuv_surface_check(const jh_yuv_surface* surface, int h, int w) { return y
 
 int jh_sensor_surface_check(const jh_sensor_surface* surface, int h, int w) {
   return sensor_surface_check(surface, h, w);
+}
+
+int jh_pixel_surface_check(const jh_pixel_surface* surface, int h, int w) {
+  return pixel_surface_check(surface, h, w);
+}
+
+int jh_op_pixels_to_bgr(const uint8_t* frames_dev, const jh_pixel_surface* surface, int n, int h, int w,
+                        uint8_t* out_bgr_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(frames_dev && out_bgr_dev && n >= 1, "null frame / output pointer");
+  FrameSource fs;
+  if (frame_source(surface, h, w, &fs) || launch_frames_to_bgr(frames_dev, fs, out_bgr_dev, n, h, w, s)) return 1;
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
 }
 
 int jh_op_yuv420_to_bgr(const uint8_t* frames_dev, int format, int n, int h, int w, uint8_t* out_bgr_dev,

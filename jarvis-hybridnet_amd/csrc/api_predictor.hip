@@ -503,11 +503,30 @@ int jh_predictor_forward_images(jh_predictor* pr, const void* const* images_host
   JH_REQUIRE(pr, "bad argument");
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
   FrameSource fs;
-  if (call_source("forward_images", format, yuv, sensor, pr->cfg.img_h, pr->cfg.img_w, true, &fs)) return 1;
+  if (call_source("forward_images", format, yuv, sensor, nullptr, pr->cfg.img_h, pr->cfg.img_w, true, &fs)) return 1;
   if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T * pr->C, fs,
                     static_cast<hipStream_t>(stream))) return 1;
   // (the launches read the table: `frames` itself is not dereferenced)
   return forward_impl(pr, pr->frames_table, fs, points_dev, conf_dev, valid_dev, stream, mask_dev);
+}
+
+int jh_predictor_forward_pixels(jh_predictor* pr, const uint8_t* frames_dev, const void* const* images_host,
+                                int n_images, const jh_pixel_surface* surface, const uint8_t* mask_dev,
+                                float* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
+  JH_REQUIRE(pr && surface, "jh_predictor_forward_pixels: null predictor / jh_pixel_surface");
+  JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
+  JH_REQUIRE((frames_dev != nullptr) != (images_host != nullptr),
+             "jh_predictor_forward_pixels: give frames_dev or images_host, not both");
+  FrameSource fs;
+  if (call_source("jh_predictor_forward_pixels", kSrcPixels, nullptr, nullptr, surface, pr->cfg.img_h, pr->cfg.img_w,
+                  images_host != nullptr, &fs)) return 1;
+  const void* frames = frames_dev;
+  if (images_host) {
+    if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T * pr->C, fs,
+                      static_cast<hipStream_t>(stream))) return 1;
+    frames = pr->frames_table;                // (the launches read the table: `frames` itself is not dereferenced)
+  }
+  return forward_impl(pr, frames, fs, points_dev, conf_dev, valid_dev, stream, mask_dev);
 }
 
 int jh_predictor_debug_v2v(jh_predictor* pr, float* out_dev, void* stream) {

@@ -106,10 +106,28 @@ int jh_predictor2d_forward_images(jh_predictor2d* pr, const void* const* images_
                                   int32_t* points_dev, float* conf_dev, int32_t* valid_dev, void* stream) {
   JH_REQUIRE(pr && points_dev && conf_dev, "bad argument");
   FrameSource fs;
-  if (call_source("forward_images", format, yuv, sensor, pr->cfg.img_h, pr->cfg.img_w, true, &fs)) return 1;
+  if (call_source("forward_images", format, yuv, sensor, nullptr, pr->cfg.img_h, pr->cfg.img_w, true, &fs)) return 1;
   if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T, fs,
                     static_cast<hipStream_t>(stream))) return 1;
   return forward2d_impl(pr, make_call(pr->frames_table, fs, stream), points_dev, conf_dev, valid_dev);
+}
+
+int jh_predictor2d_forward_pixels(jh_predictor2d* pr, const uint8_t* frames_dev, const void* const* images_host,
+                                  int n_images, const jh_pixel_surface* surface, int32_t* points_dev, float* conf_dev,
+                                  int32_t* valid_dev, void* stream) {
+  JH_REQUIRE(pr && surface && points_dev && conf_dev, "bad argument");
+  JH_REQUIRE((frames_dev != nullptr) != (images_host != nullptr),
+             "jh_predictor2d_forward_pixels: give frames_dev or images_host, not both");
+  FrameSource fs;
+  if (call_source("jh_predictor2d_forward_pixels", kSrcPixels, nullptr, nullptr, surface, pr->cfg.img_h, pr->cfg.img_w,
+                  images_host != nullptr, &fs)) return 1;
+  const void* frames = frames_dev;
+  if (images_host) {
+    if (upload_images(pr->mem, &pr->frames_table, images_host, n_images, pr->T, fs,
+                      static_cast<hipStream_t>(stream))) return 1;
+    frames = pr->frames_table;
+  }
+  return forward2d_impl(pr, make_call(frames, fs, stream), points_dev, conf_dev, valid_dev);
 }
 
 }  // extern "C"

@@ -269,9 +269,10 @@ namespace jh {
 FrameSource fixed_source(int format);
 int frame_source(const jh_yuv_surface* sp, int h, int w, FrameSource* out);
 int frame_source(const jh_sensor_surface* sp, int h, int w, FrameSource* out);
+int frame_source(const jh_pixel_surface* sp, int h, int w, FrameSource* out);
 int frame_source(int format, int h, int w, FrameSource* out);
-int call_source(const char* who, int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor, int h, int w,
-                bool per_image, FrameSource* out);
+int call_source(const char* who, int format, const jh_yuv_surface* yuv, const jh_sensor_surface* sensor,
+                const jh_pixel_surface* pixels, int h, int w, bool per_image, FrameSource* out);
 int upload_images(Scratch& mem, const void*** table, const void* const* images_host, int n_images, int want,
                   const FrameSource& fs, hipStream_t s);
 // api_predictor.hip: the stages

@@ -3,7 +3,7 @@
 // convolution that applies it while staging its input patch (stem.hip): ONE definition, so the fused
 // and the unfused path produce the same bits.
 //
-// The frames come in one of eight SOURCE FORMS (SRC, the kSrc* codes; 0 .. 3 are JH_FRAME_* of include/jarvis_hip.h):
+// The frames come in one of nine SOURCE FORMS (SRC, the kSrc* codes; 0 .. 3 are JH_FRAME_* of include/jarvis_hip.h):
 //   0 kSrcRgbF32      [N][3][H][W] fp32 RGB in [0,1] (the API input of JarvisPredictor3D.forward);
 //   1 kSrcBgrU8       [N][H][W][3] uint8 BGR as the video decoder delivers it, converted like predict3D.py:79-80
 //                     (`.float()...[:, [2,1,0]] / 255.`) on the fly, so the 4x larger fp32 frame never exists;
@@ -22,7 +22,13 @@
 //                     bit stream (jh_sensor_surface.sample).  A sample is reduced to its top byte where it is loaded
 //                     (byte8) and the bytes go through the demosaic of form 5 (sensor_px);
 //   7 kSrcYuvWide     a described YUV 4:2:0 surface of 16-bit samples (P010, yuv420p10le): reduced the same way, then
-//                     converted with the constants of form 4 (yuv_wide_px).
+//                     converted with the constants of form 4 (yuv_wide_px);
+//   8 kSrcPixels      a described pixel surface (jh_pixel_surface): three 8-bit components per pixel, R G B or Y U V,
+//                     each found by its own address rule -- offset, pitch, step and the two subsampling shifts -- so
+//                     RGB in any byte order, 4-byte and planar RGB, grey, packed YUYV / UYVY and planar or semi-planar
+//                     4:2:2 / 4:4:4 / 4:4:0 / 4:1:1 are values of one description (pixels_px).  YUV components are
+//                     converted with the constants of form 4.  No public JH_FRAME_* code: the form has entry points
+//                     of its own (jh_predictor_forward_pixels and its like).
 // Callers see 6 and 7 as JH_FRAME_SENSOR / JH_FRAME_SURFACE: the frame_source constructors choose them from the
 // description's sample code, so the kernels of forms 4 and 5 carry nothing of the wide ones.
 //
@@ -57,12 +63,12 @@
 namespace jh {
 
 enum { kSrcRgbF32 = 0, kSrcBgrU8 = 1, kSrcI420 = 2, kSrcNV12 = 3, kSrcYuvSurface = 4, kSrcSensor = 5,
-       kSrcSensorWide = 6, kSrcYuvWide = 7, kSrcCount = 8 };
+       kSrcSensorWide = 6, kSrcYuvWide = 7, kSrcPixels = 8, kSrcCount = 9 };
 template <int SRC> constexpr bool kIsYuv = SRC == kSrcI420 || SRC == kSrcNV12 || SRC == kSrcYuvSurface ||
                                            SRC == kSrcYuvWide;
 template <int SRC> constexpr bool kIsSensor = SRC == kSrcSensor || SRC == kSrcSensorWide;
 // the forms whose pixel is converted once to (R, G, B) bytes for all three channels
-template <int SRC> constexpr bool kIsRgb8 = kIsYuv<SRC> || kIsSensor<SRC>;
+template <int SRC> constexpr bool kIsRgb8 = kIsYuv<SRC> || kIsSensor<SRC> || SRC == kSrcPixels;
 
 // The base pointer and the index under which the pixel functions find image n of a launch (see the head of this file).
 // cell: the one-pointer cell of a graph replay (or nullptr: `frames` is the base), or with per_image the table.
@@ -143,8 +149,10 @@ struct YuvSurface {
 };
 
 // yuv_to_rgb8 with the constants of the surface's (matrix, range): the same scheme, int32 throughout (every
-// partial sum of the four constant rows stays below 2^30, tests/test_yuv_surface_cpu.py)
-__host__ __device__ __forceinline__ Rgb8 yuv_to_rgb8(int Y, int U, int V, const YuvSurface& s) {
+// partial sum of the four constant rows stays below 2^30, tests/test_yuv_surface_cpu.py).  S: a description that
+// carries the six constants (YuvSurface and what derives from it, PixelSurface).
+template <class S>
+__host__ __device__ __forceinline__ Rgb8 yuv_to_rgb8(int Y, int U, int V, const S& s) {
   constexpr int SHIFT = 20, HALF = 1 << (SHIFT - 1);
   const int u = U - 128, v = V - 128;
   const int yy = (Y > s.y0 ? Y - s.y0 : 0) * s.cy + HALF;
@@ -313,7 +321,42 @@ __device__ __forceinline__ Rgb8 yuv_wide_px(const void* frames, size_t n, int y,
   return yuv_to_rgb8(Y, U, V, s);
 }
 
-// The description a kernel of source form SRC takes by value: the surface of the four described forms, nothing (an
+// A described pixel surface as the kernels take it (SRC 8): the address rules of a jh_pixel_surface the host has checked
+// (jh_pixel_surface_check) and, for Y U V components, the fixed-point constants of its (matrix, range) -- the table of
+// form 4.  Passed BY VALUE in the kernel arguments, as YuvSurface is: every field is wave-uniform and stays in scalar
+// registers (the arrays are only ever indexed by constants).
+struct PixelSurface {
+  long long image_stride = 0;
+  long long offset[3] = {0, 0, 0}, pitch[3] = {0, 0, 0};
+  int step[3] = {1, 1, 1}, xs[3] = {0, 0, 0}, ys[3] = {0, 0, 0};
+  int yuv = 0;                 // components are Y U V (JH_PIXEL_YUV): convert; else they are R G B
+  int y0 = 16, cy = 0, cvr = 0, cub = 0, cug = 0, cvg = 0;
+  float bytes = 3.f;           // distinct component bytes per pixel (FrameSource::px_bytes), computed once on the host
+  bool operator==(const PixelSurface& o) const {
+    for (int k = 0; k < 3; ++k)
+      if (offset[k] != o.offset[k] || pitch[k] != o.pitch[k] || step[k] != o.step[k] || xs[k] != o.xs[k] ||
+          ys[k] != o.ys[k]) return false;
+    return image_stride == o.image_stride && yuv == o.yuv && y0 == o.y0 && cy == o.cy && cvr == o.cvr &&
+           cub == o.cub && cug == o.cug && cvg == o.cvg && bytes == o.bytes;
+  }
+};
+
+// pixel (y, x) of image n of a described pixel surface: three byte loads, component k at
+// offset[k] + (y >> ys[k]) * pitch[k] + (x >> xs[k]) * step[k] -- inside [0, image_stride) for every (y, x) of the
+// h x w image the description was checked for.  64-bit offsets, as yuv_surface_px.  The branch on `yuv` is wave-uniform.
+// (One 4-byte load for the layouts whose three bytes share an aligned word -- BGRA, YUYV -- was measured and gained
+//  nothing over the byte loads: DESIGN.md 3.15e.)
+__device__ __forceinline__ Rgb8 pixels_px(const void* frames, size_t n, int y, int x, const PixelSurface& s) {
+  const unsigned char* img = static_cast<const unsigned char*>(frames) + (long long)n * s.image_stride;
+  int c[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    c[k] = img[s.offset[k] + (long long)(y >> s.ys[k]) * s.pitch[k] + (long long)(x >> s.xs[k]) * s.step[k]];
+  if (s.yuv) return yuv_to_rgb8(c[0], c[1], c[2], s);
+  return Rgb8{c[0], c[1], c[2]};
+}
+
+// The description a kernel of source form SRC takes by value: the surface of the five described forms, nothing (an
 // empty class) for the four whose layout follows from (H, W).
 template <int SRC> struct SrcDesc {
   bool operator==(const SrcDesc&) const { return true; }
@@ -322,13 +365,15 @@ template <> struct SrcDesc<kSrcYuvSurface> : YuvSurface {};
 template <> struct SrcDesc<kSrcSensor> : SensorSurface {};
 template <> struct SrcDesc<kSrcSensorWide> : SensorSurfaceWide {};
 template <> struct SrcDesc<kSrcYuvWide> : YuvSurfaceWide {};
+template <> struct SrcDesc<kSrcPixels> : PixelSurface {};
 
 // pixel (y, x) of image n as (R, G, B) bytes: the forms that convert once for all three channels
 template <int SRC>
 __device__ __forceinline__ Rgb8 rgb8_px(const void* frames, size_t n, int y, int x, int H, int W,
                                         const SrcDesc<SRC>& d) {
-  static_assert(kIsRgb8<SRC>, "rgb8_px: YUV and raw sensor formats only");
+  static_assert(kIsRgb8<SRC>, "rgb8_px: YUV, raw sensor and pixel-surface formats only");
   if constexpr (kIsSensor<SRC>) return sensor_px(frames, n, y, x, d);
+  else if constexpr (SRC == kSrcPixels) return pixels_px(frames, n, y, x, d);
   else if constexpr (SRC == kSrcYuvSurface) return yuv_surface_px(frames, n, y, x, d);
   else if constexpr (SRC == kSrcYuvWide) return yuv_wide_px(frames, n, y, x, d);
   else return yuv420_px<SRC>(frames, n, y, x, H, W);
@@ -419,13 +464,14 @@ __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int
 struct FrameSource {
   int fmt = kSrcRgbF32;                                                                  // kSrc*
   std::variant<std::monostate, SrcDesc<kSrcYuvSurface>, SrcDesc<kSrcSensor>, SrcDesc<kSrcSensorWide>,
-               SrcDesc<kSrcYuvWide>> desc;                                               // monostate: fmt needs none
+               SrcDesc<kSrcYuvWide>, SrcDesc<kSrcPixels>> desc;                          // monostate: fmt needs none
   bool per_image = false;      // the launches read a table of one device pointer per image instead of one base
   bool operator==(const FrameSource& o) const { return fmt == o.fmt && desc == o.desc && per_image == o.per_image; }
   bool operator!=(const FrameSource& o) const { return !(*this == o); }
   // bytes of frame data per source pixel: fp32 RGB 12, uint8 BGR 3, YUV 4:2:0 1.5 (16-bit: 3), raw sensor 1 (16-bit
-  // words 2, 10p 1.25, 12p 1.5)
+  // words 2, 10p 1.25, 12p 1.5), a pixel surface the distinct component bytes of its description
   double px_bytes() const {
+    if (const auto* p = std::get_if<SrcDesc<kSrcPixels>>(&desc)) return p->bytes;
     if (const auto* w = std::get_if<SrcDesc<kSrcSensorWide>>(&desc))
       return w->kind == kSampleU16 ? 2.0 : w->kind == kSampleP10 ? 1.25 : 1.5;
     return fmt == kSrcRgbF32 ? 12.0 : fmt == kSrcBgrU8 ? 3.0 : fmt == kSrcSensor ? 1.0 : fmt == kSrcYuvWide ? 3.0 : 1.5;
@@ -456,6 +502,7 @@ int dispatch_src(const FrameSource& src, F&& f) {
     case kSrcSensor: return row(SrcTag<kSrcSensor>{});
     case kSrcSensorWide: return row(SrcTag<kSrcSensorWide>{});
     case kSrcYuvWide: return row(SrcTag<kSrcYuvWide>{});
+    case kSrcPixels: return row(SrcTag<kSrcPixels>{});
   }
   set_error("requirement failed: src.fmt is no kSrc* code (frame format)");
   return 1;

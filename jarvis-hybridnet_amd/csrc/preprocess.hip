@@ -5,7 +5,8 @@
 //                      False, no antialias) + (x-mean)/std
 //                      jarvis/prediction/jarvis3D.py:143-145
 //  preprocess_crop     bounding-box crop + normalisation   jarvis3D.py:168-178
-//  frames_to_bgr       a YUV 4:2:0 or raw sensor form as uint8 BGR: the unit-test form of the pixel functions
+//  frames_to_bgr       a YUV 4:2:0, raw sensor or pixel-surface form as uint8 BGR: the unit-test form of the pixel
+//                      functions
 #include "jh_common.h"
 #include "preprocess.h"
 
@@ -84,8 +85,8 @@ int launch_preprocess_crop(const void* frames, const FrameSource& src, const int
   return 0;
 }
 
-// A YUV 4:2:0 or raw sensor form (SRC 2 .. 7) -> [N][H][W][3] uint8 BGR through the pixel function the resize / crop
-// use (rgb8_px): the unit-test form of yuv420_px, yuv_surface_px, yuv_wide_px and sensor_px.  One thread per output pixel; only
+// A YUV 4:2:0, raw sensor or pixel-surface form (SRC 2 .. 8) -> [N][H][W][3] uint8 BGR through the pixel function the
+// resize / crop use (rgb8_px): the unit-test form of yuv420_px, yuv_surface_px, yuv_wide_px, sensor_px and pixels_px.  One thread per output pixel; only
 // plane bytes resp. the H x W samples are read.
 template <int SRC>
 __global__ __launch_bounds__(256) void frames_to_bgr_kernel(const void* __restrict__ frames,
@@ -114,6 +115,8 @@ int launch_frames_to_bgr(const void* frames, const FrameSource& src, unsigned ch
         } else {
           if constexpr (kIsSensor<SRC>)
             JH_REQUIRE(N >= 1 && H >= 1 && W >= 1 && d.h == H && d.w == W, "raw sensor frames: image size");
+          else if constexpr (SRC == kSrcPixels)
+            JH_REQUIRE(N >= 1 && H >= 1 && W >= 1, "pixel surfaces: image size");   // (checked for H x W by the caller)
           else
             JH_REQUIRE(N >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0,
                        "YUV 4:2:0 frames need an even height and width");

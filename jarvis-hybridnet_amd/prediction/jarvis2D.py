@@ -106,10 +106,12 @@ class JarvisPredictor2D(nn.Module):
 
     def forward_surface(self, img, surface):
         """img (image_stride,) or (1,image_stride) uint8: one YUV 4:2:0 image read through the YuvSurface `surface`,
-        or one raw Mono8 / Bayer image read through the SensorSurface `surface` (see
-        JarvisPredictor3D.forward_surface) -> (points2D (J,2) int64 pixels, confidences (J,)) or (None, None)."""
-        if torch.is_tensor(img) and img.dim() == 1:
-            img = img.unsqueeze(0)
+        or one raw Mono8 / Bayer image read through the SensorSurface `surface`, or one image of a PixelSurface (any
+        shape of exactly image_stride bytes, e.g. (H,W,3) RGB; see JarvisPredictor3D.forward_surface) -> (points2D (J,2) int64 pixels, confidences (J,)) or (None, None)."""
+        from ..pixel_surface import PixelSurface
+        if torch.is_tensor(img) and (img.dim() == 1 or (isinstance(surface, PixelSurface) and
+                                                        img.numel() == surface.image_stride)):
+            img = img.unsqueeze(0)                           # (a PixelSurface: ONE image of any shape, e.g. (H,W,3))
         frames = N.describe_frames(img, (1,), None, N.surface(surface))
         return self._run(frames, True)
 

@@ -287,7 +287,10 @@ class JarvisPredictor3D(nn.Module):
         """frames (C,image_stride) uint8: one YUV 4:2:0 image per camera, read in place through the YuvSurface
         `surface` (pitched decoder surfaces, I420 / YV12 / NV12 / NV21, BT.601 / BT.709, limited / full range), or one
         raw sensor image per camera through the SensorSurface `surface` (Mono8, or an 8-bit Bayer mosaic demosaiced
-        bilinearly on the GPU; pitched buffers with a header in front likewise).
+        bilinearly on the GPU; pitched buffers with a header in front likewise), or one image per camera through the
+        PixelSurface `surface` (RGB in any byte order, 4-byte and planar RGB, grey, YUYV / UYVY, planar and semi-planar
+        YUV 4:2:2 / 4:4:4 / 4:4:0 / 4:1:1): frames (C,image_stride), or any (C,...) with exactly image_stride bytes per
+        camera -- (C,H,W,3), (C,H,W,4) and (C,3,H,W) tensors go in as they are.
         Same result, bit for bit, as forward_uint8 on the BGR bytes the surface's conversion gives
         (include/jarvis_hip.h); bytes outside the planes are never read.
         -> (points3D (1,J,3), confidences (1,J)) or (None, None).  camera_mask, return_2d, centers, return_spread,
@@ -311,8 +314,9 @@ class JarvisPredictor3D(nn.Module):
         its own mask row only.  None: all cameras.
         return_2d: the per-camera `Views2D` of the batch (leading dimension T; see forward()) follows `valid`:
         (points, confidences, valid, views).  Rows of invalid frames: used 0, points2D -1, NaN reprojections.
-        frame_layout: a YuvSurface or a SensorSurface -- imgs (T,C,image_stride) uint8, see forward_surface; not
-        together with frame_format 'i420' / 'nv12'.
+        frame_layout: a YuvSurface, a SensorSurface or a PixelSurface -- imgs (T,C,image_stride) uint8 (a PixelSurface:
+        any (T,C,...) with exactly image_stride bytes per image), see forward_surface; not together with frame_format
+        'i420' / 'nv12'.
         Calibration: cameraMatrices (C,4,3), intrinsicMatrices (C,3,3), distortionCoefficients (C,1,5) -- one
         calibration shared by the T frame sets --, or the same three with a leading T -- (T,C,4,3) / (T,C,3,3) /
         (T,C,1,5), row t the calibration of frame set t, as the reference's validation analysis gives every sample the

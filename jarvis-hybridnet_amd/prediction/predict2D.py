@@ -74,7 +74,8 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
     'nv12' raises ValueError.
 
     frame_layout: a YuvSurface -- the frames are (image_stride,) uint8 described YUV 4:2:0 surfaces (fill callables
-    with `frame_spec=((image_stride,), torch.uint8)`) --, or a SensorSurface -- (image_stride,) uint8 raw Mono8 /
+    with `frame_spec=((image_stride,), torch.uint8)`) --, a PixelSurface -- (image_stride,) uint8 or any uint8 shape of
+    exactly image_stride bytes, such as (H,W,3) RGB --, or a SensorSurface -- (image_stride,) uint8 raw Mono8 /
     Bayer sensor images --, see predict3D_frames; not together with 'i420' / 'nv12'."""
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
     yuv = driver_format(frame_format, frame_spec, 2, frame_layout)

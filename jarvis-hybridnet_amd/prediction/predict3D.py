@@ -222,7 +222,9 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     frame_layout: a YuvSurface -- the frame sets are (C, image_stride) uint8, one described YUV 4:2:0 surface per
     camera (pitched decoder output, I420 / YV12 / NV12 / NV21, BT.601 / BT.709, limited / full range; fill callables
     with `frame_spec=((C, image_stride), torch.uint8)`; device-resident frame sets likewise), read in place
-    (JarvisPredictor3D.forward_surface).  Or a SensorSurface -- the frame sets are (C, image_stride) uint8 raw
+    (JarvisPredictor3D.forward_surface).  Or a PixelSurface -- (C, image_stride) uint8, or any (C, ...) uint8 with exactly
+    image_stride bytes per camera, such as (C,H,W,3) RGB or (C,H,W,4) BGRA arrays as they are.
+    Or a SensorSurface -- the frame sets are (C, image_stride) uint8 raw
     sensor images, Mono8 or an 8-bit Bayer mosaic as a machine-vision camera delivers them: a third of the bytes of
     BGR to stage and upload, demosaiced inside the resize / crop kernels.  Not together with frame_format
     'i420' / 'nv12': ValueError.  The predictor is given `frame_layout=` only when it is set here.

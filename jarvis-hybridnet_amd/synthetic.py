@@ -400,3 +400,53 @@ def pack_sensor_surface(raw, surface, fill=0):
     idx = s.offset + np.arange(s.height)[:, None] * s.pitch + np.arange(nb)[None, :]
     out[..., idx.reshape(-1)] = rows.reshape(lead + (-1,))
     return out
+
+
+def _component_index(s, k):
+    """Byte offsets (H, W) of component k of every pixel of a PixelSurface image."""
+    y = (np.arange(s.height) >> s.ys[k])[:, None]
+    x = (np.arange(s.width) >> s.xs[k])[None, :]
+    return s.offset[k] + y * s.pitch[k] + x * s.step[k]
+
+
+def pixels_to_bgr(buf, surface):
+    """The numpy reference of the pixel-surface fetch (include/jarvis_hip.h): buf (..., image_stride) uint8 laid out as
+    the PixelSurface `surface` describes -> (..., H, W, 3) uint8 BGR.  Component k of pixel (y, x) is the byte at
+    offset[k] + (y >> ys[k]) * pitch[k] + (x >> xs[k]) * step[k]; colour 'yuv' converts (Y, U, V) in int32 with the
+    constants of the surface's matrix and range (the arithmetic of a YuvSurface), chroma replicated."""
+    s = surface
+    buf = np.asarray(buf, np.uint8)
+    if buf.shape[-1] != s.image_stride:
+        raise ValueError("buf %s does not hold images of %d bytes" % (buf.shape, s.image_stride))
+    c = [buf[..., _component_index(s, k)].astype(np.int32) for k in range(3)]
+    if s.colour == "yuv":
+        y0, cy, cvr, cub, cug, cvg = s.coefficients
+        u, v = c[1] - 128, c[2] - 128
+        yy = np.maximum(c[0] - y0, 0) * cy + (1 << 19)
+        c = [(yy + cvr * v) >> 20, (yy + cvg * v + cug * u) >> 20, (yy + cub * u) >> 20]
+    return np.stack([np.clip(c[2], 0, 255), np.clip(c[1], 0, 255), np.clip(c[0], 0, 255)], axis=-1).astype(np.uint8)
+
+
+def pack_pixel_surface(planes_or_bgr, surface, fill=0):
+    """Test data laid out as the PixelSurface `surface` describes -> (..., image_stride) uint8; every byte that is no
+    component (an alpha byte, pitch padding, gaps, the bytes before the first offset) is `fill`.  colour 'rgb': uint8
+    BGR (..., H, W, 3).  colour 'yuv': the planes (Y (..., H, W), U, V (..., ceil(H / 2^ys), ceil(W / 2^xs)))."""
+    s = surface
+    H, W = s.height, s.width
+    if s.colour == "rgb":
+        bgr = np.asarray(planes_or_bgr, np.uint8)
+        if bgr.shape[-3:] != (H, W, 3):
+            raise ValueError("bgr %s does not fit a %d x %d surface" % (bgr.shape, H, W))
+        planes = [bgr[..., 2], bgr[..., 1], bgr[..., 0]]
+    else:
+        planes = [np.asarray(p, np.uint8) for p in planes_or_bgr]
+        want = [(((H - 1) >> s.ys[k]) + 1, ((W - 1) >> s.xs[k]) + 1) for k in range(3)]
+        if len(planes) != 3 or any(p.shape[-2:] != w for p, w in zip(planes, want)):
+            raise ValueError("planes %s do not fit a %d x %d surface (%s)" % ([p.shape for p in planes], H, W, want))
+    lead = planes[0].shape[:-2]
+    out = np.full(lead + (s.image_stride,), fill, np.uint8)
+    for k, plane in enumerate(planes):
+        rows, cols = plane.shape[-2:]
+        idx = s.offset[k] + np.arange(rows)[:, None] * s.pitch[k] + np.arange(cols)[None, :] * s.step[k]
+        out[..., idx.reshape(-1)] = plane.reshape(lead + (-1,))
+    return out
