@@ -4,8 +4,8 @@ operators, against heat maps whose answer is known, and against itself over the 
 cfg2 (tests/cases.py: 4 cameras 640 x 512, crops of 256: heat maps 128 x 128 with 23 joints in 24 channels).
 
 Bounds.  Offsets and observations: exact (bits).  Consensus: views and members exact; every non-empty point bit-equal to
-jh_reconstruct_point (pinned by tests/test_hip_ops.py) on the members' pixels and weights; error within 1e-3 px of the
-float64 reference (fp32 projections of coordinates below 1024 px round at 6e-5 px per operation, the bound
+jh_reconstruct_point (pinned by tests/test_hip_geometry_ops.py) on the members' pixels and weights; error within 1e-3 px
+of the float64 reference (fp32 projections of coordinates below 1024 px round at 6e-5 px per operation, the bound
 tests/test_hip_subjects.py derives); the float64 SVD and the fp64 eigen-solve agree within 1e-2 mm.  The reference
 asserts, before anything is compared and over every candidate pair, that no support distance lies within 1e-2 px of
 max_error_px and that no choice rests on a cost difference below 1e-2 px; the scenes' seeds are fixed and were chosen on

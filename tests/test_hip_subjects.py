@@ -4,9 +4,10 @@ frame forms, and forward_subjects against the centred forward_batch.  On cfg2 (t
 center_size 256: heat maps 128 x 128, sx2 = 5, sy2 = 4 full-frame pixels per heat-map pixel).
 
 Bounds.  Peaks: exact (bits of (x, y, value) and the counts).  Association: views and members exact; every non-empty
-centre bit-equal to jh_reconstruct_point (pinned by tests/test_hip_ops.py) on the members' pixels and value / 255 -- the
-weight the triangulation gives a detection, formed here by the same IEEE division --; error within 1e-3 px of the
-float64 reference (fp32 projections of coordinates below 1024 px round at 6e-5 px per operation).  The scenes' peaks are
+centre bit-equal to jh_reconstruct_point (pinned by tests/test_hip_geometry_ops.py) on the members' pixels and
+value / 255 -- the weight the triangulation gives a detection, formed here by the same IEEE division --; error within
+1e-3 px of the float64 reference (fp32 projections of coordinates below 1024 px round at 6e-5 px per operation).  The
+scenes' peaks are
 projections rounded to the grid, at most sqrt(2.5^2 + 2^2) = 3.2 px <= sx2 / sqrt(2) off; max_error_px is 3 sx2 / sqrt(2).
 The reference asserts, before anything is compared, that no choice of a round, no support decision and no nearest peak
 lies within 1e-2 px of a tie.  Everything here calls a symbol the feature adds."""
