@@ -1023,12 +1023,15 @@ typedef struct jh_op_operand {
                                * is.  InstanceNorm (eps 1e-5) + in_act are applied on load, 1 / pixels as a float */
   int32_t in_act;             /* 0 none / 1 relu / 2 silu, behind that InstanceNorm */
   int32_t latency_class;      /* ConvDesc::latency_class: 1 = the tile forms of the single-frame-set plans */
-  int32_t want_stats;         /* 1: the launch also accumulates the fused statistics of y (not returned); 0 and no gate:
+  int32_t want_stats;         /* 1: the launch also accumulates the fused statistics of y (out_sums_host); 0 and no gate:
                                * a ConvTranspose2d k4 s2 p1 may take the window form */
   int32_t se_c, se_s;         /* the squeeze-excite gate as the recipe (se_pool_host != NULL): channels (= cin), squeeze */
   float se_inv_hw;            /* 1 / pixels the pooled sums were taken over */
   const float *se_wr_host, *se_br_host, *se_we_host, *se_be_host; /* (se_s, se_c), (se_s), (se_c, se_s), (se_c) */
   const double* se_pool_host; /* (n, se_c) pooled sums of the activated tensor */
+  double* out_sums_host;      /* (n, cout, 2), with want_stats: the statistics the launch emitted for its consumers, the
+                               * limbs of each value added in the reader's fixed order; the buffer behind y then starts
+                               * as NaN.  NULL: not returned */
 } jh_op_operand;
 /* jh_op_conv with the operand transform: y is always the RAW convolution output (no InstanceNorm behind it).  The gate
  * is either gate_dev (n, cin) or the recipe in `operand`.  kind 1 with cout == 1, no bias, no statistics: the
@@ -1055,6 +1058,18 @@ int jh_op_depthwise(int k, int c, const float* w_host, const float* x_dev, int n
  * y_dev (N,C,h,w) RAW depthwise output, pool_dev (N,C) = sum over pixels of SiLU(InstanceNorm(y)). */
 int jh_op_depthwise_pool(int k, int c, const float* w_host, const float* x_dev, int n, int h, int w,
                          float* y_dev, float* pool_dev, void* stream);
+/* TEST-ONLY: the depthwise launch with everything it hands to its consumers: y_dev (n,c,h,w) RAW, out_sums_host
+ * (n, c, 2) the emitted sum and sum of squares (limbs added in the reader's order) and, want_pool (refused unless the
+ * image is one tile: h, w <= 20), pool_host (n, c) doubles = the pooled sums of SiLU(InstanceNorm(y)) of the same
+ * launch, read from their limbs as jh_op_norm_apply reads them.  The buffer behind y starts as NaN. */
+int jh_op_depthwise_ex(int k, int c, const float* w_host, const float* x_dev, int n, int h, int w, int want_pool,
+                       float* y_dev, double* out_sums_host, double* pool_host, void* stream);
+/* TEST-ONLY: the stem convolution Conv2d(3 -> cout, k3, s2, p1, no bias) of the EfficientNet trunk on its own
+ * (csrc/stem.hip, the form fed by a pre-processed tensor): w_host (cout,3,3,3), x_dev (n,3,h,w) -> y_dev
+ * (n,cout,h/2,w/2) RAW and out_sums_host (n, cout, 2) as above.  cout 16 or 32; h, w even.  The input is laid out as
+ * jh_efftrack_forward lays it out (one float4 per pixel); the buffer behind y starts as NaN. */
+int jh_op_stem(int cout, const float* w_host, const float* x_dev, int n, int h, int w, float* y_dev,
+               double* out_sums_host, void* stream);
 
 /* The YUV 4:2:0 -> BGR conversion of jh_predictor_forward_yuv on its own: frames (n,3h/2,w) in format
  * JH_FRAME_I420 / JH_FRAME_NV12 -> out_bgr (n,h,w,3) uint8 BGR (device pointers; h, w even). */

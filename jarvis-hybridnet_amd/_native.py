@@ -70,10 +70,11 @@ class OpOperand(ctypes.Structure):
     _fields_ = [("in_sums_host", c_void_p), ("in_act", ctypes.c_int32), ("latency_class", ctypes.c_int32),
                 ("want_stats", ctypes.c_int32), ("se_c", ctypes.c_int32), ("se_s", ctypes.c_int32),
                 ("se_inv_hw", c_float), ("se_wr_host", c_void_p), ("se_br_host", c_void_p),
-                ("se_we_host", c_void_p), ("se_be_host", c_void_p), ("se_pool_host", c_void_p)]
+                ("se_we_host", c_void_p), ("se_be_host", c_void_p), ("se_pool_host", c_void_p),
+                ("out_sums_host", c_void_p)]
 
 
-assert ctypes.sizeof(OpOperand) == 72
+assert ctypes.sizeof(OpOperand) == 80
 
 
 class OpNodeEx(ctypes.Structure):
@@ -297,6 +298,9 @@ _SIGS = {
                                 c_void_p, c_void_p]),
     "jh_op_depthwise_pool": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                      c_void_p]),
+    "jh_op_depthwise_ex": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "jh_op_stem": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "jh_op_yuv420_to_bgr": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "jh_op_bifpn_node": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_float), c_int, c_int, c_int,
                                  c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

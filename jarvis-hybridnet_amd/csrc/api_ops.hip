@@ -18,6 +18,17 @@ static int op_upload_stats(Scratch& sc, const double* sums_host, int n, int c, i
   return op_upload(sc, st.data(), st.size(), dev);
 }
 
+// Emitted statistics [N][Cp][kStatW] (copied to the host) -> (n, c, 2) as a consumer reads them: the limbs of each value
+// added in exact_read's order.
+static void op_read_stats(const std::vector<double>& hst, int n, int c, int Cp, double* out) {
+  for (int b = 0; b < n; ++b)
+    for (int ch = 0; ch < c; ++ch) {
+      const double* q = hst.data() + ((size_t)b * Cp + ch) * kStatW;
+      out[((size_t)b * c + ch) * 2] = (q[0] + q[1]) + q[2];
+      out[((size_t)b * c + ch) * 2 + 1] = (q[kLimbs] + q[kLimbs + 1]) + q[kLimbs + 2];
+    }
+}
+
 // The squeeze-excite recipe from host values: pooled sums (n, C) -> [N][Cp][kLimbs] (first limb), weights as they are.
 static int op_upload_se(Scratch& sc, const double* pool_host, int n, int C, int Cp, int S, float inv_hw,
                         const float* wr, const float* br, const float* we, const float* be, SeGate* out) {
@@ -56,8 +67,12 @@ static int op_conv_body(int nd, int kind, int k, int stride, int pad, int cin, i
   if (sc.act(n, Do, Ho, Wo, cout, &y)) return 1;
   // (a plain ConvTranspose2d -- no statistics, no InstanceNorm behind it -- starts from NaN instead: an output element
   //  that no workgroup stores then reaches the caller as NaN; pad channels are not copied out.  The fill exists for the
-  //  exactly-once-stores check of tests/test_hip_deconv4_window.py)
-  JH_CHECK_HIP(hipMemsetAsync(y.p, kind == 1 && plain_out ? 0xFF : 0, y.bytes(), s));
+  //  exactly-once-stores check of tests/test_hip_deconv4_window.py.
+  //  A caller that reads the emitted statistics back gets the NaN fill too: a pixel nobody stored is then a finding of
+  //  its own, apart from a statistics error.)
+  const bool read_stats = opd && opd->out_sums_host;
+  JH_REQUIRE(!read_stats || want_stats, "out_sums_host needs want_stats");
+  JH_CHECK_HIP(hipMemsetAsync(y.p, (kind == 1 && plain_out) || read_stats ? 0xFF : 0, y.bytes(), s));
   ConvUse use;
   use.desc = desc; use.desc.latency_class = opd ? opd->latency_class : 0;
   use.transposed = kind != 0; use.has_bias = b_host != nullptr; use.want_stats = want_stats;
@@ -94,7 +109,11 @@ static int op_conv_body(int nd, int kind, int k, int stride, int pad, int cin, i
   if (layer.launch(x, y, gate_p, stats, in, recipe ? &se : nullptr, s)) return 1;
   if (!opd && norm_act >= 0 && launch_norm_apply(y, stats, norm_act, nullptr, nullptr, y.p, nullptr, s)) return 1;
   if (launch_from_channel_last(y, y_dev, s)) return 1;
+  std::vector<double> hst(read_stats ? (size_t)n * y.Cp * kStatW : 0);
+  if (read_stats)
+    JH_CHECK_HIP(hipMemcpyAsync(hst.data(), stats, hst.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   if (hipStreamSynchronize(s) != hipSuccess) { set_error(std::string("stream sync failed in ") + who); return 1; }
+  if (read_stats) op_read_stats(hst, n, cout, y.Cp, opd->out_sums_host);
   return 0;
 }
 
@@ -205,12 +224,7 @@ static int op_node_body(int n_in, const int* modes, const float* weights, int ac
     if (hipStreamSynchronize(s) != hipSuccess) { set_error(std::string("stream sync failed in ") + who); rc = 1; break; }
     if (ex && ex->pool_written_host) *ex->pool_written_host = choice.pool ? 1 : 0;
     // the emitted statistics as a consumer reads them: the limbs added in exact_read's order
-    for (int b = 0; b < n && !hst.empty(); ++b)
-      for (int ch = 0; ch < cout; ++ch) {
-        const double* q = hst.data() + ((size_t)b * y.Cp + ch) * kStatW;
-        ex->out_sums_host[((size_t)b * cout + ch) * 2] = (q[0] + q[1]) + q[2];
-        ex->out_sums_host[((size_t)b * cout + ch) * 2 + 1] = (q[kLimbs] + q[kLimbs + 1]) + q[kLimbs + 2];
-      }
+    if (!hst.empty()) op_read_stats(hst, n, cout, y.Cp, ex->out_sums_host);
   } while (0);
   free_conv_weights(&cw);
   return rc;
@@ -379,6 +393,78 @@ int jh_op_depthwise_pool(int k, int c, const float* w_host, const float* x_dev, 
       out[(size_t)i * c + ch] = (float)((q[0] + q[1]) + q[2]);
     }
   JH_CHECK_HIP(hipMemcpy(pool_dev, out.data(), out.size() * sizeof(float), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// Depthwise as the MBConv blocks run it, with everything it hands on: the raw y, the emitted statistics and (want_pool,
+// one-tile images) the pooled sums of SiLU(InstanceNorm(y)) of the same launch.
+int jh_op_depthwise_ex(int k, int c, const float* w_host, const float* x_dev, int n, int h, int w, int want_pool,
+                       float* y_dev, double* out_sums_host, double* pool_host, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(w_host && x_dev && y_dev && out_sums_host && n >= 1 && c >= 1 && h >= 1 && w >= 1 && (k == 3 || k == 5),
+             "jh_op_depthwise_ex: bad argument");
+  JH_REQUIRE(!want_pool || (pool_host && depthwise_can_pool(h, w)),
+             "jh_op_depthwise_ex: pooled sums need a one-tile image and pool_host");
+  Scratch sc;
+  Act x, y;
+  if (sc.act(n, 1, h, w, c, &x)) return 1;
+  if (sc.act(n, 1, h, w, c, &y)) return 1;
+  const std::vector<float> wt = taps_major(w_host, c, k * k, x.Cp);
+  float* wd; double *stats = nullptr, *pool = nullptr;
+  if (op_upload(sc, wt.data(), wt.size(), &wd)) return 1;
+  const size_t nst = (size_t)n * x.Cp * kStatW, npl = (size_t)n * x.Cp * kLimbs;
+  if (sc.get(reinterpret_cast<void**>(&stats), nst * sizeof(double))) return 1;
+  JH_CHECK_HIP(hipMemsetAsync(stats, 0, nst * sizeof(double), s));
+  if (want_pool) {
+    if (sc.get(reinterpret_cast<void**>(&pool), npl * sizeof(double))) return 1;
+    JH_CHECK_HIP(hipMemsetAsync(pool, 0, npl * sizeof(double), s));
+  }
+  // (NaN: an output pixel that no workgroup stores reaches the caller as NaN)
+  JH_CHECK_HIP(hipMemsetAsync(y.p, 0xFF, y.bytes(), s));
+  if (launch_to_channel_last(x_dev, x, s)) return 1;
+  if (launch_depthwise(x, wd, k, y.p, stats, s, pool)) return 1;
+  if (launch_from_channel_last(y, y_dev, s)) return 1;
+  std::vector<double> hst(nst), hp(want_pool ? npl : 0);
+  JH_CHECK_HIP(hipMemcpyAsync(hst.data(), stats, nst * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (want_pool) JH_CHECK_HIP(hipMemcpyAsync(hp.data(), pool, npl * sizeof(double), hipMemcpyDeviceToHost, s));
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  op_read_stats(hst, n, c, x.Cp, out_sums_host);
+  if (want_pool)
+    for (int i = 0; i < n; ++i)
+      for (int ch = 0; ch < c; ++ch) {
+        const double* q = hp.data() + ((size_t)i * x.Cp + ch) * kLimbs;
+        pool_host[(size_t)i * c + ch] = (q[0] + q[1]) + q[2];
+      }
+  return 0;
+}
+
+// The stem convolution (csrc/stem.hip) on its own, fed the way jh_efftrack_forward feeds it: the image as one float4 per
+// pixel (EffTrackPlan::build: input.Cp = 4).
+int jh_op_stem(int cout, const float* w_host, const float* x_dev, int n, int h, int w, float* y_dev,
+               double* out_sums_host, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(w_host && x_dev && y_dev && out_sums_host && n >= 1 && h >= 2 && w >= 2, "jh_op_stem: bad argument");
+  JH_REQUIRE((cout == 16 || cout == 32) && h % 2 == 0 && w % 2 == 0, "jh_op_stem: cout 16 or 32, even h and w");
+  Scratch sc;
+  Act x, y;
+  if (sc.act(n, 1, h, w, 3, &x)) return 1;
+  x.Cp = 4;
+  if (sc.act(n, 1, h / 2, w / 2, cout, &y)) return 1;
+  std::vector<float> packed((size_t)27 * cout);
+  pack_stem_weights(w_host, packed.data(), cout);
+  float* wd; double* stats = nullptr;
+  if (op_upload(sc, packed.data(), packed.size(), &wd)) return 1;
+  const size_t nst = (size_t)n * y.Cp * kStatW;
+  if (sc.get(reinterpret_cast<void**>(&stats), nst * sizeof(double))) return 1;
+  JH_CHECK_HIP(hipMemsetAsync(stats, 0, nst * sizeof(double), s));
+  JH_CHECK_HIP(hipMemsetAsync(y.p, 0xFF, y.bytes(), s));
+  if (launch_to_channel_last(x_dev, x, s)) return 1;
+  if (launch_stem_conv(x, wd, y, stats, s)) return 1;
+  if (launch_from_channel_last(y, y_dev, s)) return 1;
+  std::vector<double> hst(nst);
+  JH_CHECK_HIP(hipMemcpyAsync(hst.data(), stats, nst * sizeof(double), hipMemcpyDeviceToHost, s));
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  op_read_stats(hst, n, cout, y.Cp, out_sums_host);
   return 0;
 }
 

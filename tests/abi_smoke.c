@@ -15,9 +15,10 @@ _Static_assert(offsetof(jh_predictor_config, time_batch) == 40, "time_batch offs
 _Static_assert(offsetof(jh_predictor_config, mean) == 56, "mean offset");
 _Static_assert(offsetof(jh_predictor_config, std) == 68, "std offset");
 _Static_assert(offsetof(jh_predictor_config, precision) == 80, "precision offset");
-_Static_assert(sizeof(jh_op_operand) == 72, "jh_op_operand layout (mirrored in _native.py: OpOperand)");
+_Static_assert(sizeof(jh_op_operand) == 80, "jh_op_operand layout (mirrored in _native.py: OpOperand)");
 _Static_assert(offsetof(jh_op_operand, se_inv_hw) == 28, "se_inv_hw offset");
 _Static_assert(offsetof(jh_op_operand, se_pool_host) == 64, "se_pool_host offset");
+_Static_assert(offsetof(jh_op_operand, out_sums_host) == 72, "out_sums_host offset of jh_op_operand");
 _Static_assert(sizeof(jh_op_node_ex) == 80, "jh_op_node_ex layout (mirrored in _native.py: OpNodeEx)");
 _Static_assert(offsetof(jh_op_node_ex, in_count) == 32, "in_count offset");
 _Static_assert(offsetof(jh_op_node_ex, out_sums_host) == 72, "out_sums_host offset");

@@ -110,10 +110,11 @@ def _seed(r):
     return 1000 * r.k + 10 * r.cin + r.cout + sum(r.shape)
 
 
-def operand_input(seed, shape, const=False):
+def operand_input(seed, shape, const=False, sign=None):
     """(n, c, *spatial) float32: each (image, channel) has EXACTLY (in float64, before the rounding to float32) the drawn
     sigma and mean; `const`: channel CONST_CHANNEL of image 0 is the constant CONST_VALUE (variance 0: the clamp of a
-    negative variance and rstd = 1 / sqrt(eps))."""
+    negative variance and rstd = 1 / sqrt(eps)); `sign` (+1 / -1): every mean with that sign instead of a drawn one
+    (the draws, hence every other number, stay what they are without it)."""
     g = torch.Generator().manual_seed(seed)
     n, c = shape[:2]
     dims = tuple(range(2, len(shape)))
@@ -122,7 +123,8 @@ def operand_input(seed, shape, const=False):
     z = z / z.pow(2).mean(dims, keepdim=True).sqrt()
     sigma = 0.5 + 1.5 * torch.rand(n, c, generator=g, dtype=torch.float64)
     ratio = 2.05 + 1.9 * torch.rand(n, c, generator=g, dtype=torch.float64)
-    sign = (torch.rand(n, c, generator=g) < 0.5).double() * 2 - 1
+    drawn = (torch.rand(n, c, generator=g) < 0.5).double() * 2 - 1
+    sign = drawn if sign is None else torch.full_like(drawn, float(sign))
     ex = (...,) + (None,) * len(dims)
     x = (z * sigma[ex] + (sign * ratio * sigma)[ex]).float()
     if const:
