@@ -234,6 +234,43 @@ int jh_predictor_set_calibration_frames(jh_predictor* pr, const float* cam_dev /
  * Validation: pr non-NULL; otherwise non-zero with jh_last_error() set, nothing enqueued. */
 int jh_predictor_set_centers(jh_predictor* pr, const float* centers_dev /* (T,3) or NULL */, void* stream);
 
+/* Per-camera tone tables: black level, gain, white balance and gamma as ONE byte-to-value lookup inside the resize /
+ * crop fetch, so that raw-sensor, decoder-surface and plain BGR frames reach the networks in the distribution the
+ * networks were trained on without a host pass.
+ * tables (num_cameras,3,256) fp32 (the 2D predictor: (3,256)): tables[c][ch][k] is the value the pre-processing sees
+ * for byte k of channel ch (0 = R, 1 = G, 2 = B) of camera c, in place of k * (1/255).  All num_cameras cameras' tables
+ * are given, also to a camera-sharded predictor (cam_lo, cam_n), which reads rows cam_lo .. cam_lo + cam_n - 1.
+ * Every byte source form is covered: uint8 BGR, I420 / NV12, jh_yuv_surface, jh_sensor_surface, their wide forms and
+ * jh_pixel_surface.  A pixel is first converted to its (R, G, B) bytes exactly as without tables (colour conversion,
+ * demosaic, sample reduction); each byte is then replaced by tables[c][ch][byte]; everything after that is untouched:
+ * the four-tap bilinear resize, the crop's zero outside the frame, (v - mean) / std.
+ * Results: a forward under tables equals, BIT FOR BIT, jh_predictor_forward on the fp32 RGB frames
+ * F[t][c][ch][y][x] = tables[c][ch][B[t][c][y][x][ch]], B being the bytes the form's jh_op_*_to_bgr helper gives --
+ * in points, confidences, valid, jh_predictor_debug, jh_predictor_views2d and everything else that follows a forward.
+ * tables[..][k] = fl(fl(k) * fl(1/255)) gives the bits of the call without tables;
+ * tables[c][ch][k] = fl(fl(L[c][ch][k]) * fl(1/255)) for a uint8 LUT L gives the bits of jh_predictor_forward_u8 on the
+ * L-mapped bytes.
+ * The index is always the clamped byte the conversion produced, 0 .. 255: whatever the frames hold (a masked camera's
+ * garbage, padding), no table read leaves its 256 entries, and nothing outside the planes is read, as without tables.
+ * Table values are taken as given and should be finite.
+ * fp32 RGB frames have no byte: a call with fp32 frames while tables are set fails with jh_last_error()
+ * "tone tables apply to byte frames" and enqueues nothing.
+ * Read by every entry point that fetches frames: the whole-path forwards (_u8, _yuv, _surface, _sensor, _pixels,
+ * _masked, _images), jh_predictor_stage_center_u8, jh_predictor_stage_keypoints_u8 / _masked / _gathered,
+ * jh_predictor_detect_subjects*, and the 2D forwards.
+ * Lifetime, as jh_predictor_set_centers: the tables are copied on `stream` into a buffer the predictor owns, allocated
+ * by the first such call (never by *_create, not inside a stream capture; jh_predictor_device_bytes grows by it only
+ * then).  NULL returns to the plain form.  A predictor that never asks makes the launches it always made.
+ * Graph replay: a recording is made with or without tables, so switching them on or off records again; the VALUES live
+ * in the predictor's buffer and may change from call to call under one recording.
+ * Out of scope: tables indexed by more than 8 bits (with JH_SAMPLE_U16(shift) a caller chooses WHICH 8 bits of a wide
+ * sample index the table); a 3x3 colour-correction matrix; gains applied before the demosaic (with linear gains the
+ * per-channel table commutes with the bilinear demosaic up to rounding); rounding instead of truncation of wide samples.
+ * Validation: pr non-NULL; otherwise non-zero with jh_last_error() set, nothing enqueued. */
+int jh_predictor_set_tone(jh_predictor* pr, const float* tables_dev /* (num_cameras,3,256) or NULL */, void* stream);
+/* (jh_predictor2d_set_tone and the unit-test helper jh_op_frames_to_rgb_f32 are declared with the 2D predictor and
+ *  the frame descriptions, below) */
+
 /* Stage 1 (jarvis3D.py:135-155): resize + normalise + CenterDetect + argmax for
  * the owned cameras.  frames (T,cam_n,3,H,W) dev -> det (T,cam_n,3) = (x, y,
  * raw maxval) dev. */
@@ -287,6 +324,9 @@ int jh_predictor_forward(jh_predictor* pr, const float* frames_dev, float* point
  * itself being captured. */
 int jh_predictor_set_graph_replay(jh_predictor* pr, int on);
 int jh_predictor_graph_replay(const jh_predictor* pr);
+/* how many times a whole-path forward of this predictor has been recorded so far (a first call of a form, a changed
+ * description or calibration form, tone tables switched on or off): a call that replays adds none */
+int64_t jh_predictor_graph_records(const jh_predictor* pr);
 /* uint8 ingest (jarvis/prediction/predict3D.py:72-80): the
  * same three entry points for frames (T,cam_n,H,W,3) uint8 BGR exactly as the video
  * decoder delivers them.  The `.float().permute(0,3,1,2)[:, [2,1,0]] / 255.` of the
@@ -343,7 +383,8 @@ int jh_predictor_forward_yuv(jh_predictor* pr, const uint8_t* frames_dev, int fo
  * conversion above then runs on the bytes, so the result equals, bit for bit, that of the 8-bit description of the
  * reduced planes.  shift = bits - 8 is LSB-aligned data (yuv420p10le: 2, yuv420p12le: 4), shift = 8 MSB-aligned data
  * (P010 / P012 / P016).  Truncation, not rounding: what a decoder's own 8-bit output of the same stream is not
- * guaranteed to be, but what a shift on the host gives; no gain or gamma, and the network never sees more than 8 bits.
+ * guaranteed to be, but what a shift on the host gives; gain and gamma are tables over that byte (jh_predictor_set_tone), and the network
+ * never sees more than 8 bits.
  * Offsets and pitches stay in BYTES, c_step counts SAMPLES.  The rules for JH_SAMPLE_U16: every offset, pitch and
  * image_stride even (every 16-bit load is aligned); y_pitch >= 2 w; c_pitch >= (w/2) * c_step * 2; for c_step 2,
  * |u_offset - v_offset| == 2 with min(u_offset, v_offset) and c_pitch multiples of 4 (the pair is one 4-byte load
@@ -392,8 +433,9 @@ int jh_predictor_forward_surface(jh_predictor* pr, const uint8_t* frames_dev, co
  *   at a green site: green is the byte, the colour whose samples lie left and right = (W + E + 1) >> 1, the colour
  *     whose samples lie above and below = (N + S + 1) >> 1.
  * A border pixel (y in {0, h-1} or x in {0, w-1}) takes the RGB of the interior pixel (clamp(y, 1, h-2),
- * clamp(x, 1, w-2)): clamp first, then demosaic, so no byte outside the h x w samples is addressed.  No white
- * balance, gamma or colour correction: the bytes are taken as the camera delivers them.  The (R, G, B) bytes then
+ * clamp(x, 1, w-2)): clamp first, then demosaic, so no byte outside the h x w samples is addressed.  The
+ * bytes are taken as the camera delivers them; black level, white balance and gamma are per-channel tables applied to
+ * the demosaiced bytes (jh_predictor_set_tone), a colour-correction matrix is not offered.  The (R, G, B) bytes then
  * take the uint8 path unchanged: the result equals, bit for bit, jh_predictor_forward_u8 on the converted frames.
  * jh_sensor_surface_check (no GPU needed) is the validation every entry point applies: h, w positive; pattern
  * known; for a Bayer pattern h, w even and >= 4; pitch >= w; offset >= 0; offset + (h-1) * pitch + w <=
@@ -402,7 +444,8 @@ int jh_predictor_forward_surface(jh_predictor* pr, const uint8_t* frames_dev, co
  * offset and image_stride stay in bytes).  A sample is reduced to a byte inside the fetch, byte = min(sample >> shift,
  * 255) -- the truncation a camera applies when its PixelFormat is switched from Mono12 to Mono8 --, and the bytes go
  * the way described above: the result equals, bit for bit, that of the 8-bit description of the reduced bytes.
- * Rounding, gain, black level, gamma or white-balance tables, and more than 8 bits for the network are not offered.
+ * Rounding instead of truncation and more than 8 bits for the network are not offered; gain, black level, gamma and
+ * white balance are tables over the reduced byte (jh_predictor_set_tone).
  *   JH_SAMPLE_U8 = 0: one byte per sample, every description above.
  *   JH_SAMPLE_U16(shift), shift 0 .. 8: raw(y, x) is the little-endian 16-bit word at offset + y * pitch + 2 x.
  *     shift = bits - 8 is LSB-aligned data (Mono10 / 12 / 14 / 16, BayerXX10 / 12 / 16), shift = 8 MSB-aligned data;
@@ -969,6 +1012,16 @@ int jh_predictor_forward_pixels(jh_predictor* pr, const uint8_t* frames_dev, con
 int jh_predictor2d_forward_pixels(jh_predictor2d* pr, const uint8_t* frames_dev, const void* const* images_host,
                                   int n_images, const jh_pixel_surface* surface, int32_t* points_dev, float* conf_dev,
                                   int32_t* valid_dev, void* stream);
+/* Tone tables of the 2D predictor: one camera's (3,256); see jh_predictor_set_tone */
+int jh_predictor2d_set_tone(jh_predictor2d* pr, const float* tables_dev /* (3,256) or NULL */, void* stream);
+/* unit-test helper of the tone tables: n images of any byte form -> (n,3,h,w) fp32 RGB, the values the resize / crop
+ * fetch sees for every pixel; synchronises.  The form is `format` (JH_FRAME_BGR_U8 .. JH_FRAME_SENSOR, with the
+ * jh_yuv_surface resp. jh_sensor_surface that JH_FRAME_SURFACE / JH_FRAME_SENSOR come with) or a jh_pixel_surface
+ * alone (format ignored), validated as the entry points validate.  tables_dev (cams,3,256) or NULL: image i reads
+ * camera i % cams; NULL gives byte * (1/255). */
+int jh_op_frames_to_rgb_f32(const void* frames_dev, int format, const jh_yuv_surface* yuv,
+                            const jh_sensor_surface* sensor, const jh_pixel_surface* pixels, int n, int h, int w,
+                            const float* tables_dev, int cams, float* out_dev, void* stream);
 /* jh_predictor_detect_subjects with the description in place of (format, yuv, sensor) */
 int jh_predictor_detect_subjects_pixels(jh_predictor* pr, const uint8_t* frames_dev, const void* const* images_host,
                                         int n_images, const jh_pixel_surface* surface, const uint8_t* mask_dev,

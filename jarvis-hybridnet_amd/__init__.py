@@ -12,7 +12,8 @@ __version__ = "0.1.0"
 from .yuv_surface import YuvSurface  # noqa: E402,F401 -- pure Python: importing the package still loads no library
 from .sensor_surface import SensorSurface  # noqa: E402,F401 -- likewise
 from .pixel_surface import PixelSurface  # noqa: E402,F401 -- likewise
-from .spread import Spread3D  # noqa: E402,F401 -- likewise
+from .tone import ToneTables  # noqa: E402,F401 -- likewise
+from .spread import Spread3D # noqa: E402,F401 -- likewise
 from .subjects import Subjects  # noqa: E402,F401 -- likewise
 from .triangulated import Triangulated3D  # noqa: E402,F401 -- likewise
 from .joint_mask import JointMask  # noqa: E402,F401 -- likewise

@@ -179,13 +179,19 @@ _SIGS = {
     "jh_predictor_destroy": (None, [c_void_p]),
     "jh_predictor_set_graph_replay": (c_int, [c_void_p, c_int]),
     "jh_predictor_graph_replay": (c_int, [c_void_p]),
+    "jh_predictor_graph_records": (c_int64, [c_void_p]),
     "jh_predictor_launches": (c_int64, [c_void_p]),
     "jh_predictor_device_bytes": (c_int64, [c_void_p]),
     "jh_predictor_precision": (c_int, [c_void_p]),
     "jh_predictor_set_calibration": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_set_calibration_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_set_centers": (c_int, [c_void_p, c_void_p, c_void_p]),
-    "jh_predictor_stage_center": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jh_predictor_set_tone": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "jh_predictor2d_set_tone": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "jh_op_frames_to_rgb_f32": (c_int, [c_void_p, c_int, ctypes.POINTER(YuvSurfaceStruct),
+                                        ctypes.POINTER(SensorSurfaceStruct), ctypes.POINTER(PixelSurfaceStruct), c_int,
+                                        c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "jh_predictor_stage_center":(c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_stage_keypoints": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_stage_3d": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),

@@ -9,6 +9,7 @@ from . import arch
 from .joint_mask import JointMask
 from .spread import Spread3D  # noqa: F401 -- the name the forwards return
 from .subjects import Subjects
+from .tone import check_tone
 from .tracks import check_tracker
 from .triangulated import Triangulated3D
 
@@ -51,6 +52,7 @@ class NativePredictor:
         self._centred = False                        # centres are in force (set_centers)
         self._spread = False                         # the 3D stage runs the spread form of its tail (set_spread)
         self._joint_masked = False                   # a joint mask is in force (set_joint_mask)
+        self._toned = False                          # tone tables are in force (set_tone)
 
     def close(self):
         if getattr(self, "handle", None) and N is not None and N._lib is not None:
@@ -67,6 +69,11 @@ class NativePredictor:
     @graph_replay.setter
     def graph_replay(self, on):
         N.check(N.lib().jh_predictor_set_graph_replay(self.handle, int(bool(on))))
+
+    @property
+    def graph_records(self):
+        """How many times a whole-path forward has been recorded so far: a call that replays adds none."""
+        return int(N.lib().jh_predictor_graph_records(self.handle))
 
     # ---- calibration -----------------------------------------------------
     def set_calibration(self, cam, intr, dist):
@@ -104,6 +111,25 @@ class NativePredictor:
         N.check(N.lib().jh_predictor_set_centers(self.handle, N.ptr(dev), N.stream()))
         dev.record_stream(torch.cuda.current_stream())          # (copied by the call: free once it is enqueued)
         self._centred = True
+
+    # ---- per-camera tone tables --------------------------------------------
+    def set_tone(self, tone):
+        """tone: a ToneTables of num_cameras cameras (all of them, also on a camera-sharded predictor), or an array it
+        accepts: from now on every call of this predictor that fetches byte frames replaces byte k of channel ch of
+        camera c by tone.tables[c][ch][k] in place of k / 255 (jh_predictor_set_tone; copied on the current stream; the
+        first such call allocates the buffer: not inside a stream capture).  fp32 frames are then refused
+        (RuntimeError "tone tables apply to byte frames").  None: back to the plain form."""
+        tone = check_tone(tone, self.C)
+        if tone is None:
+            if self._toned:
+                N.check(N.lib().jh_predictor_set_tone(self.handle, None, N.stream()))
+                self._toned = False
+            return
+        dev = torch.tensor(tone.tables).to("cuda")
+        N.check(N.lib().jh_predictor_set_tone(self.handle, N.ptr(dev), N.stream()))
+        dev.record_stream(torch.cuda.current_stream())          # (copied by the call: free once it is enqueued)
+        self._toned = True
+        self.device_bytes = N.lib().jh_predictor_device_bytes(self.handle)
 
     # ---- per-joint 3D spread ----------------------------------------------
     def set_spread(self, on):
@@ -489,6 +515,16 @@ class MultiStreamPredictor:
                     t.record_stream(s)
         self._calib = key
         self._calib_of = [None] * len(self.preds)
+
+    def set_tone(self, tone):
+        """Tone tables of every predictor (NativePredictor.set_tone), written on that predictor's OWN stream, so the
+        copy is ordered against the forwards in flight there.  None: back to the plain form."""
+        tone = check_tone(tone, self.preds[0].C)
+        cur = torch.cuda.current_stream()
+        for p, s in zip(self.preds, self.streams):
+            s.wait_stream(cur)
+            with torch.cuda.stream(s):
+                p.set_tone(tone)
 
     def _frames_calibration(self, i):
         """Inside predictor i's stream context: its copy of the per-frame calibration in force, if it has not got it."""

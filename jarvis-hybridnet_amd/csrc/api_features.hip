@@ -137,6 +137,12 @@ int jh_predictor_set_centers(jh_predictor* pr, const float* centers_dev, void* s
   return 0;
 }
 
+// ---- tone tables
+int jh_predictor_set_tone(jh_predictor* pr, const float* tables_dev, void* stream) {
+  JH_REQUIRE(pr, "jh_predictor_set_tone: null predictor");
+  return pr->tone.set(pr->mem, tables_dev, pr->C, static_cast<hipStream_t>(stream));
+}
+
 // ---- per-joint 3D spread
 int jh_predictor_set_spread(jh_predictor* pr, int on) {
   JH_REQUIRE(pr, "jh_predictor_set_spread: null predictor");
@@ -414,6 +420,10 @@ static int detect_subjects_impl(jh_predictor* pr, const void* frames_dev, const 
   FrameSource fs;
   if (call_source("jh_predictor_detect_subjects", format, yuv, sensor, pixels, c.img_h, c.img_w,
                   images_host != nullptr, &fs)) return 1;
+  {   // (fp32 frames under tone tables are refused before anything is allocated or enqueued)
+    Call probe = make_call(frames_dev, fs, stream);
+    if (pr->tone_call(&probe)) return 1;
+  }
   const int N = pr->T * pr->C;
   const Act& h = pr->center->heat;
   if (!pr->subj_peaks) {

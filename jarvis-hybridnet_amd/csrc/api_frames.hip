@@ -306,6 +306,22 @@ int jh_op_pixels_to_bgr(const uint8_t* frames_dev, const jh_pixel_surface* surfa
   return 0;
 }
 
+int jh_op_frames_to_rgb_f32(const void* frames_dev, int format, const jh_yuv_surface* yuv,
+                            const jh_sensor_surface* sensor, const jh_pixel_surface* pixels, int n, int h, int w,
+                            const float* tables_dev, int cams, float* out_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(frames_dev && out_dev && n >= 1 && h >= 1 && w >= 1, "jh_op_frames_to_rgb_f32: null frame / output "
+             "pointer or empty size");
+  JH_REQUIRE(!tables_dev || cams >= 1, "jh_op_frames_to_rgb_f32: tables come with their camera count");
+  FrameSource fs;
+  if (call_source("jh_op_frames_to_rgb_f32", format, yuv, sensor, pixels, h, w, false, &fs)) return 1;
+  JH_REQUIRE(fs.fmt != kSrcRgbF32, "jh_op_frames_to_rgb_f32: tone tables apply to byte frames");
+  if (tables_dev) { fs.tone = tables_dev; fs.tone_cam0 = 0; fs.tone_cams = cams; }
+  if (launch_frames_to_rgb_f32(frames_dev, fs, out_dev, n, h, w, s)) return 1;
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 int jh_op_yuv420_to_bgr(const uint8_t* frames_dev, int format, int n, int h, int w, uint8_t* out_bgr_dev,
                         void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);

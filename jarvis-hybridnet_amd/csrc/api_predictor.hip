@@ -87,7 +87,9 @@ int jh_predictor::run_3d(const Call& call, const float* heat_all, int t0, float*
 }
 
 // Stage 1 up to CenterDetect's heat map (pr->center->heat): resize or fused stem, then the plan
-int jh::center_heat_impl(jh_predictor* pr, const Call& call) {
+int jh::center_heat_impl(jh_predictor* pr, const Call& call_in) {
+  Call call = call_in;
+  if (pr->tone_call(&call)) return 1;
   hipStream_t s = call.s;
   const FrameSource& fs = call.fs;
   JH_REQUIRE(pr->center, "predictor was created without CenterDetect weights");
@@ -119,8 +121,10 @@ static int stage_center_impl(jh_predictor* pr, const Call& call, float* det_dev)
   return 0;
 }
 
-static int stage_keypoints_impl(jh_predictor* pr, const Call& call, const float* det_all_dev, float* heat_dev,
+static int stage_keypoints_impl(jh_predictor* pr, const Call& call_in, const float* det_all_dev, float* heat_dev,
                                 int det_blocks = 1, bool next_centre_set = false) {
+  Call call = call_in;
+  if (pr->tone_call(&call)) return 1;
   hipStream_t s = call.s;
   const FrameSource& fs = call.fs;
   const auto& c = pr->cfg;
@@ -235,6 +239,7 @@ static int forward_graph(jh_predictor* pr, const Call& call, float* points_dev, 
     JH_CHECK_HIP(ei);
     slot.src = fs;
     slot.calib_fs = pr->calib_fs;
+    ++pr->graph_records;
   }
   // (per-image: the recording reads frames_table, which this call's pointers have already been sent into)
   if (!fs.per_image) hipLaunchKernelGGL(set_cell_kernel, dim3(1), dim3(1), 0, s, pr->frames_cell, call.frames);
@@ -252,13 +257,15 @@ static int forward_graph(jh_predictor* pr, const Call& call, float* points_dev, 
 static int forward_impl(jh_predictor* pr, const void* frames_dev, const FrameSource& fs, float* points_dev,
                         float* conf_dev, int32_t* valid_dev, void* stream,
                         const unsigned char* mask_dev = nullptr) {
-  if (mask_dev)
-    JH_CHECK_HIP(hipMemcpyAsync(pr->mask_buf, mask_dev, (size_t)pr->T * pr->C, hipMemcpyDeviceToDevice,
-                                static_cast<hipStream_t>(stream)));
   Call call = make_call(frames_dev, fs, stream, mask_dev ? pr->mask_buf : nullptr);
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
   JH_REQUIRE(pr->T3 == pr->T, "forward needs time_batch_3d == time_batch");
   JH_REQUIRE(frames_dev && points_dev && conf_dev, "null frame / output pointer");
+  // (tone tables in force become part of the call's source here, so that the graph slot below sees them)
+  if (pr->tone_call(&call)) return 1;
+  if (mask_dev)
+    JH_CHECK_HIP(hipMemcpyAsync(pr->mask_buf, mask_dev, (size_t)pr->T * pr->C, hipMemcpyDeviceToDevice,
+                                static_cast<hipStream_t>(stream)));
   pr->slot = 0;                               // (the whole-path forward and its captured graph: centre set 0)
   // a joint mask in force (jh_predictor_set_joint_mask): plain launches, no graph slot of its own -- the captured
   // graphs stay as they are and replay again once the mode is off
@@ -365,6 +372,7 @@ int jh_predictor_set_graph_replay(jh_predictor* pr, int on) {
   return 0;
 }
 int jh_predictor_graph_replay(const jh_predictor* pr) { return pr ? pr->use_graph : 0; }
+int64_t jh_predictor_graph_records(const jh_predictor* pr) { return pr ? pr->graph_records : 0; }
 
 int64_t jh_predictor_launches(const jh_predictor* pr) {
   return (int64_t)((pr->center ? pr->center->launches() : 0) + pr->kp->launches() +
@@ -374,7 +382,7 @@ int jh_predictor_precision(const jh_predictor* pr) { return pr ? pr->cfg.precisi
 
 int64_t jh_predictor_device_bytes(const jh_predictor* pr) {
   return (int64_t)((pr->center ? pr->center->device_bytes() : 0) + pr->kp->device_bytes() +
-                   pr->v2v->device_bytes() + pr->spread_bytes);
+                   pr->v2v->device_bytes() + pr->spread_bytes + pr->tone.bytes);
 }
 
 int jh_predictor_set_calibration(jh_predictor* pr, const float* cam_dev, const float* intr_dev,

@@ -6,8 +6,10 @@
 
 using namespace jh;
 
-static int forward2d_impl(jh_predictor2d* pr, const Call& call, int32_t* points_dev, float* conf_dev,
+static int forward2d_impl(jh_predictor2d* pr, const Call& call_in, int32_t* points_dev, float* conf_dev,
                           int32_t* valid_dev) {
+  Call call = call_in;
+  if (pr->tone.apply(&call, 0, 1)) return 1;  // (one camera: every image reads table 0)
   hipStream_t s = call.s;
   const FrameSource& fs = call.fs;
   const auto& c = pr->cfg;
@@ -65,6 +67,11 @@ int jh_predictor2d_create(const jh_params* center_params, const jh_params* kp_pa
 }
 
 void jh_predictor2d_destroy(jh_predictor2d* pr) { delete pr; }
+
+int jh_predictor2d_set_tone(jh_predictor2d* pr, const float* tables_dev, void* stream) {
+  JH_REQUIRE(pr, "jh_predictor2d_set_tone: null predictor");
+  return pr->tone.set(pr->mem, tables_dev, 1, static_cast<hipStream_t>(stream));
+}
 
 int jh_predictor2d_forward(jh_predictor2d* pr, const float* frames_dev, int32_t* points_dev,
                            float* conf_dev, int32_t* valid_dev, void* stream) {

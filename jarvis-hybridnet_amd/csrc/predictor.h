@@ -134,6 +134,41 @@ inline Call stage3_call(void* stream, const unsigned char* mask = nullptr) {
   return c;
 }
 
+// Tone tables of a predictor (jh_predictor_set_tone / jh_predictor2d_set_tone): buf (cameras, 3, 256) is the predictor's
+// copy, allocated by the first setting call; on: in force.  apply() puts them into a call's source -- image n of every
+// launch is camera cam0 + n % cams -- and refuses fp32 frames, which have no byte; idempotent, so every function that
+// fetches frames applies it to the call it was given.
+struct ToneState {
+  float* buf = nullptr;
+  bool on = false;
+  size_t bytes = 0;            // what jh_predictor_device_bytes reports for it
+  int apply(Call* c, int cam0, int cams) const {
+    if (!on) return 0;
+    if (c->fs.fmt == kSrcRgbF32) {
+      set_error("tone tables apply to byte frames");
+      return 1;
+    }
+    c->fs.tone = buf; c->fs.tone_cam0 = cam0; c->fs.tone_cams = cams;
+    return 0;
+  }
+  // the body of both setters: NULL switches the tables off (the buffer stays for the next setting call)
+  int set(Scratch& mem, const float* tables_dev, int cams, hipStream_t s) {
+    if (!tables_dev) {
+      on = false;
+      return 0;
+    }
+    const size_t n = (size_t)cams * 768 * sizeof(float);
+    if (!buf) {
+      if (first_call_alloc(mem, s, n, "the first set_tone call of a predictor allocates its table buffer: make it "
+                           "outside a stream capture", &buf)) return 1;
+      bytes = n;
+    }
+    JH_CHECK_HIP(hipMemcpyAsync(buf, tables_dev, n, hipMemcpyDeviceToDevice, s));
+    on = true;
+    return 0;
+  }
+};
+
 // The form of a whole-path forward, which names its graph slot: one slot per frame format (kSrc*, preprocess.h) and
 // per combination of the four flags.  masked: the masked kernels.  per_image: slots of its OWN -- a stream of per-image
 // calls and a stream of contiguous calls of one format never re-record each other.  centred: the forward from
@@ -199,6 +234,7 @@ struct jh_predictor {
   // captured with.
   struct GraphSlot { hipGraphExec_t exec = nullptr; jh::FrameSource src; int calib_fs = 0; };
   GraphSlot gslot[jh::kGraphSlots];
+  int64_t graph_records = 0;                 // recordings made so far (jh_predictor_graph_records): a replay adds none
   // Camera mask (nets.h).  mask_buf [T][C]: the predictor's copy of the mask of a whole-path forward -- the masked
   // kernels (and a captured graph of them) read this buffer, so the mask may change from call to call.
   // n_active / n_detect [T]: written by the masked triangulation.
@@ -242,6 +278,9 @@ struct jh_predictor {
   jh::Joints3dParams jm_params{};
   float *jm_points = nullptr, *jm_error = nullptr;
   int* jm_views = nullptr;
+  // Tone tables (jh_predictor_set_tone), all num_cameras cameras': a launch's image n is camera cam_lo + n % Cloc
+  jh::ToneState tone;
+  int tone_call(jh::Call* c) const { return tone.apply(c, cfg.cam_lo, Cloc); }
   ~jh_predictor() {
     for (auto& g : gslot) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (gstream) (void)hipStreamDestroy(gstream);
@@ -260,6 +299,7 @@ struct jh_predictor2d {
   float* det = nullptr;
   int *chm = nullptr, *valid = nullptr;
   const void** frames_table = nullptr;       // per-image frames: [T] device pointers (jh_predictor2d_forward_images)
+  jh::ToneState tone;                        // one camera's tables (jh_predictor2d_set_tone)
 };
 
 namespace jh {

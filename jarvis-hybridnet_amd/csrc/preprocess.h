@@ -80,16 +80,44 @@ __device__ __forceinline__ const void* image_base(const void* frames, const void
   return frames;
 }
 
-template <int SRC>
+// TONE TABLES (jh_predictor_set_tone): the one place a byte becomes a network input is byte_value below.  A byte form's
+// kernels exist in two compile-time variants, chosen by the type of their last argument:
+//   NoTone      the plain form, byte * (1/255): an empty class, so these kernels are what they were without tables;
+//   ToneTables  the predictor's (cameras, 3, 256) fp32 tables, [camera][0 = R, 1 = G, 2 = B][byte]: image n of a launch
+//               is camera cam0 + n % cams (the 3D predictor's images are (t, local camera); the 2D predictor has one
+//               table) and byte k of channel ch becomes tables[camera][ch][k].
+// of(n) is what the pixel functions take for image n: NoTone again, or the image's own 3 x 256 table (ToneLut).  The
+// index is always a byte the conversion clamped to 0 .. 255, so no read leaves the 256 entries whatever the frames hold.
+// The lookup goes through the vector cache, not through LDS: 3 KB per camera stay resident, and the stem keeps its LDS.
+struct NoTone {
+  __host__ __device__ NoTone of(int) const { return NoTone{}; }
+};
+struct ToneLut { const float* lut; };
+struct ToneTables {
+  const float* tables;
+  int cam0, cams;
+  __device__ __forceinline__ ToneLut of(int n) const { return ToneLut{tables + (size_t)(cam0 + n % cams) * 768}; }
+};
+template <class Tone> constexpr bool kIsTone = !std::is_same_v<Tone, NoTone>;
+
+// the value the pre-processing sees for `byte` (0 .. 255) of channel ch (0 = R, 1 = G, 2 = B)
+template <class Tone>
+__device__ __forceinline__ float byte_value(int byte, int ch, const Tone& tone) {
+  // the reference driver divides on the GPU, where torch evaluates `x / 255.` as
+  // x * (1.f / 255.f) (division by a host scalar is a multiplication by its reciprocal)
+  if constexpr (kIsTone<Tone>) return tone.lut[ch * 256 + byte];
+  else return __fmul_rn((float)byte, __fdiv_rn(1.f, 255.f));
+}
+
+template <int SRC, class Tone = NoTone>
 __device__ __forceinline__ float frame_px(const void* frames, size_t n, int c, int y, int x, int H,
-                                          int W) {
+                                          int W, const Tone& tone = Tone{}) {
   static_assert(SRC == kSrcRgbF32 || SRC == kSrcBgrU8, "frame_px: interleaved / planar RGB formats only");
+  static_assert(SRC != kSrcRgbF32 || !kIsTone<Tone>, "tone tables apply to byte frames");
   if (SRC == 0)
     return static_cast<const float*>(frames)[((n * 3 + c) * H + y) * W + x];
   const unsigned char* p = static_cast<const unsigned char*>(frames) + ((n * H + y) * W + x) * 3;
-  // the reference driver divides on the GPU, where torch evaluates `x / 255.` as
-  // x * (1.f / 255.f) (division by a host scalar is a multiplication by its reciprocal)
-  return __fmul_rn((float)p[2 - c], __fdiv_rn(1.f, 255.f));
+  return byte_value(p[2 - c], c, tone);
 }
 
 // BT.601 limited range -> (R, G, B) bytes: the fixed-point arithmetic of OpenCV's
@@ -381,24 +409,24 @@ __device__ __forceinline__ Rgb8 rgb8_px(const void* frames, size_t n, int y, int
 
 // the three channels (r, g, b) of one pixel as the uint8 path scales them; YUV and raw sensor forms: one conversion
 // for all three channels
-template <int SRC>
+template <int SRC, class Tone = NoTone>
 __device__ __forceinline__ void frame_px3(const void* frames, size_t n, int y, int x, int H, int W,
-                                          const SrcDesc<SRC>& d, float v[3]) {
+                                          const SrcDesc<SRC>& d, float v[3], const Tone& tone = Tone{}) {
   if constexpr (kIsRgb8<SRC>) {
     const Rgb8 p = rgb8_px<SRC>(frames, n, y, x, H, W, d);
-    const float k = __fdiv_rn(1.f, 255.f);
-    v[0] = __fmul_rn((float)p.r, k); v[1] = __fmul_rn((float)p.g, k); v[2] = __fmul_rn((float)p.b, k);
+    v[0] = byte_value(p.r, 0, tone); v[1] = byte_value(p.g, 1, tone); v[2] = byte_value(p.b, 2, tone);
   } else {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = frame_px<SRC>(frames, n, c, y, x, H, W);
+    for (int c = 0; c < 3; ++c) v[c] = frame_px<SRC>(frames, n, c, y, x, H, W, tone);
   }
 }
 
 // pixel (oy, ox) of the S x S resized + normalised image n: torchvision tensor resize (bilinear,
 // align_corners = False, no antialias), then (x - mean) / std; (r, g, b, 0)
-template <int SRC>
+template <int SRC, class Tone = NoTone>
 __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, int ox, int H, int W, float sy,
-                                            float sx, float3 mean, float3 stdv, const SrcDesc<SRC>& d) {
+                                            float sx, float3 mean, float3 stdv, const SrcDesc<SRC>& d,
+                                            const Tone& tone = Tone{}) {
   float ry = fmaxf(__fsub_rn(__fmul_rn(sy, __fadd_rn((float)oy, 0.5f)), 0.5f), 0.f);
   float rx = fmaxf(__fsub_rn(__fmul_rn(sx, __fadd_rn((float)ox, 0.5f)), 0.5f), 0.f);
   int y0 = min((int)floorf(ry), H - 1), x0 = min((int)floorf(rx), W - 1);
@@ -411,8 +439,8 @@ __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, i
   // below is that of the uint8 path, so the result equals SRC 1 on the converted bytes bit for bit)
   float q00[3], q01[3], q10[3], q11[3];
   if constexpr (kIsRgb8<SRC>) {
-    frame_px3<SRC>(frames, n, y0, x0, H, W, d, q00); frame_px3<SRC>(frames, n, y0, x1, H, W, d, q01);
-    frame_px3<SRC>(frames, n, y1, x0, H, W, d, q10); frame_px3<SRC>(frames, n, y1, x1, H, W, d, q11);
+    frame_px3<SRC>(frames, n, y0, x0, H, W, d, q00, tone); frame_px3<SRC>(frames, n, y0, x1, H, W, d, q01, tone);
+    frame_px3<SRC>(frames, n, y1, x0, H, W, d, q10, tone); frame_px3<SRC>(frames, n, y1, x1, H, W, d, q11, tone);
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -420,8 +448,8 @@ __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, i
     if constexpr (kIsRgb8<SRC>) {
       p00 = q00[c]; p01 = q01[c]; p10 = q10[c]; p11 = q11[c];
     } else {
-      p00 = frame_px<SRC>(frames, n, c, y0, x0, H, W); p01 = frame_px<SRC>(frames, n, c, y0, x1, H, W);
-      p10 = frame_px<SRC>(frames, n, c, y1, x0, H, W); p11 = frame_px<SRC>(frames, n, c, y1, x1, H, W);
+      p00 = frame_px<SRC>(frames, n, c, y0, x0, H, W, tone); p01 = frame_px<SRC>(frames, n, c, y0, x1, H, W, tone);
+      p10 = frame_px<SRC>(frames, n, c, y1, x0, H, W, tone); p11 = frame_px<SRC>(frames, n, c, y1, x1, H, W, tone);
     }
     const float a = __fmaf_rn(p00, lx0, __fmul_rn(p01, lx1));
     const float b = __fmaf_rn(p10, lx0, __fmul_rn(p11, lx1));
@@ -434,9 +462,10 @@ __device__ __forceinline__ float4 resize_px(const void* frames, int n, int oy, i
 // pixel (oy, ox) of the B x B crop of image n around (cx, cy), normalised; pixels of the window that
 // lie outside the frame are 0 BEFORE the normalisation (jarvis3D.py:168-178 never leaves the frame: the
 // crop centre is clamped; kept for safety as the stand-alone kernel has it)
-template <int SRC>
+template <int SRC, class Tone = NoTone>
 __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int cy, int oy, int ox, int H,
-                                          int W, int B, float3 mean, float3 stdv, const SrcDesc<SRC>& d) {
+                                          int W, int B, float3 mean, float3 stdv, const SrcDesc<SRC>& d,
+                                          const Tone& tone = Tone{}) {
   const int hw = B / 2;
   const int ix = cx - hw + ox, iy = cy - hw + oy;
   const float mv[3] = {mean.x, mean.y, mean.z}, sv[3] = {stdv.x, stdv.y, stdv.z};
@@ -445,13 +474,13 @@ __device__ __forceinline__ float4 crop_px(const void* frames, int n, int cx, int
   if constexpr (kIsRgb8<SRC>) {
     // (outside the frame: 0 before the normalisation, as for the other formats -- not the conversion of Y = U = V = 0)
     float q[3] = {0.f, 0.f, 0.f};
-    if (ok) frame_px3<SRC>(frames, n, iy, ix, H, W, d, q);
+    if (ok) frame_px3<SRC>(frames, n, iy, ix, H, W, d, q, tone);
 #pragma unroll
     for (int c = 0; c < 3; ++c) r[c] = __fdiv_rn(__fsub_rn(q[c], mv[c]), sv[c]);
   } else {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float v = ok ? frame_px<SRC>(frames, n, c, iy, ix, H, W) : 0.f;
+      const float v = ok ? frame_px<SRC>(frames, n, c, iy, ix, H, W, tone) : 0.f;
       r[c] = __fdiv_rn(__fsub_rn(v, mv[c]), sv[c]);
     }
   }
@@ -466,7 +495,15 @@ struct FrameSource {
   std::variant<std::monostate, SrcDesc<kSrcYuvSurface>, SrcDesc<kSrcSensor>, SrcDesc<kSrcSensorWide>,
                SrcDesc<kSrcYuvWide>, SrcDesc<kSrcPixels>> desc;                          // monostate: fmt needs none
   bool per_image = false;      // the launches read a table of one device pointer per image instead of one base
-  bool operator==(const FrameSource& o) const { return fmt == o.fmt && desc == o.desc && per_image == o.per_image; }
+  // Tone tables in force (nullptr: the plain form): the predictor's device buffer, and which of its cameras image n of
+  // a launch is (ToneTables).  Part of the description, so a recorded graph is recorded again when tables are switched
+  // on or off; their VALUES live in the buffer and may change under one recording.
+  const float* tone = nullptr;
+  int tone_cam0 = 0, tone_cams = 1;
+  bool operator==(const FrameSource& o) const {
+    return fmt == o.fmt && desc == o.desc && per_image == o.per_image && tone == o.tone && tone_cam0 == o.tone_cam0 &&
+           tone_cams == o.tone_cams;
+  }
   bool operator!=(const FrameSource& o) const { return !(*this == o); }
   // bytes of frame data per source pixel: fp32 RGB 12, uint8 BGR 3, YUV 4:2:0 1.5 (16-bit: 3), raw sensor 1 (16-bit
   // words 2, 10p 1.25, 12p 1.5), a pixel surface the distinct component bytes of its description
@@ -478,19 +515,35 @@ struct FrameSource {
   }
 };
 
-// The one place a run-time format code becomes a template argument: f(SrcTag<SRC>{}, const SrcDesc<SRC>&) -> int
-// for the form src holds; an unknown code, or a described form without its description, is an error.
+// The one place a run-time format code becomes a template argument: f(SrcTag<SRC>{}, const SrcDesc<SRC>&, tone) -> int
+// for the form src holds, tone being NoTone{} or the ToneTables of src.tone; an unknown code, a described form without
+// its description, or tables with fp32 frames (which have no byte) is an error.  A caller that has no tone form may
+// pass f(tag, desc): it is then called for sources without tables only.
 template <int SRC> using SrcTag = std::integral_constant<int, SRC>;
 template <class F>
 int dispatch_src(const FrameSource& src, F&& f) {
   const auto row = [&](auto tag) -> int {
     constexpr int SRC = decltype(tag)::value;
+    const auto with_tone = [&](const SrcDesc<SRC>& d) -> int {
+      if constexpr (!std::is_invocable_v<F&, decltype(tag), const SrcDesc<SRC>&, NoTone>) {
+        JH_REQUIRE(!src.tone, "this launch has no tone form");
+        return f(tag, d);
+      } else if (!src.tone) {
+        return f(tag, d, NoTone{});
+      } else if constexpr (SRC == kSrcRgbF32) {
+        set_error("tone tables apply to byte frames");
+        return 1;
+      } else {
+        JH_REQUIRE(src.tone_cams >= 1 && src.tone_cam0 >= 0, "tone tables: camera range");
+        return f(tag, d, ToneTables{src.tone, src.tone_cam0, src.tone_cams});
+      }
+    };
     if constexpr (std::is_empty_v<SrcDesc<SRC>>) {
-      return f(tag, SrcDesc<SRC>{});
+      return with_tone(SrcDesc<SRC>{});
     } else {
       const SrcDesc<SRC>* d = std::get_if<SrcDesc<SRC>>(&src.desc);
       JH_REQUIRE(d, "a described surface comes with its own frame format");
-      return f(tag, *d);
+      return with_tone(*d);
     }
   };
   switch (src.fmt) {
@@ -532,5 +585,8 @@ int launch_preprocess_crop(const void* frames, const FrameSource& src, const int
                            const float* stdv, hipStream_t s, const void* const* frames_cell = nullptr);
 int launch_frames_to_bgr(const void* frames, const FrameSource& src, unsigned char* out, int N, int H, int W,
                          hipStream_t s);
+// the values the fetch sees, [N][3][H][W] fp32, under src's tone tables (or none): the unit-test form of byte_value
+int launch_frames_to_rgb_f32(const void* frames, const FrameSource& src, float* out, int N, int H, int W,
+                             hipStream_t s);
 
 }  // namespace jh

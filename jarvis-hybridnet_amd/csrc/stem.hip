@@ -43,11 +43,13 @@ struct StemSrcArgs {           // MODE != 0: the frames this launch pre-processe
   SrcDesc<SRC> desc;           // the form's description (uniform: scalar registers); MODE == 0: the empty one
 };
 
-template <int MODE, int SRC, int CO = 16>
+// Tone: NoTone, or the predictor's tone tables (preprocess.h) -- the workgroup's image n is one camera, so its 3 x 256
+// table is one uniform base; the lookups go through the vector cache and the kernel's LDS stays what it is.
+template <int MODE, int SRC, int CO = 16, class Tone = NoTone>
 __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict__ x,
                                                         const float* __restrict__ w /* [9][3][CO] */,
                                                         float* __restrict__ y, double* __restrict__ stats,
-                                                        int H, int W, StemSrcArgs<SRC> sa) {
+                                                        int H, int W, StemSrcArgs<SRC> sa, Tone tone) {
   static_assert(CO == 16 || CO == 32, "stem output channels");
   // (the statistics scratch lies over the patch, which is dead once every thread has its 16 sums: 19.5 instead of
   //  35.8 KB of LDS = twice the workgroups per CU; the kernel is bound by the latency of its patch loads)
@@ -66,6 +68,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
   const void* frames = sa.frames;
   int ni = n;                  // the image as the pixel functions index it: n of the base, or 0 of its own pointer
   int ccx = 0, ccy = 0;
+  const auto lut = tone.of(n);
   if (MODE != 0) {
     // (n is workgroup-uniform: the table entry, like the cell, is one scalar load)
     if (sa.per_image) frames = image_base(frames, sa.frames_cell, 1, ni);
@@ -88,8 +91,9 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
       // (the convolution's zero padding lies outside the pre-processed image: zeros, not normalised zeros)
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (ok)
-        v = MODE == 1 ? resize_px<SRC>(frames, ni, iy, ix, sa.FH, sa.FW, sa.sy, sa.sx, sa.mean, sa.stdv, sa.desc)
-                      : crop_px<SRC>(frames, ni, ccx, ccy, iy, ix, sa.FH, sa.FW, H, sa.mean, sa.stdv, sa.desc);
+        v = MODE == 1
+                ? resize_px<SRC>(frames, ni, iy, ix, sa.FH, sa.FW, sa.sy, sa.sx, sa.mean, sa.stdv, sa.desc, lut)
+                : crop_px<SRC>(frames, ni, ccx, ccy, iy, ix, sa.FH, sa.FW, H, sa.mean, sa.stdv, sa.desc, lut);
       patch[i] = v;
     }
   }
@@ -169,10 +173,10 @@ int launch_stem_conv(const Act& x, const float* w_dev, const Act& y, double* sta
   const int tiles = ((y.H + kStT - 1) / kStT) * ((y.W + kStT - 1) / kStT);
   if (y.Cp == 32)
     hipLaunchKernelGGL((stem_conv_kernel<0, 0, 32>), dim3(tiles, x.N), dim3(256), 0, s, x.p, w_dev, y.p, stats, x.H,
-                       x.W, StemSrcArgs<0>{});
+                       x.W, StemSrcArgs<0>{}, NoTone{});
   else
     hipLaunchKernelGGL((stem_conv_kernel<0, 0, 16>), dim3(tiles, x.N), dim3(256), 0, s, x.p, w_dev, y.p, stats, x.H,
-                       x.W, StemSrcArgs<0>{});
+                       x.W, StemSrcArgs<0>{}, NoTone{});
   JH_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -191,8 +195,9 @@ int launch_stem_conv_src(const StemSource& src, const Act& x, const float* w_dev
   //  and loses locality with more workgroups in flight: 654 -> 711 us at eight per CU; 16 KB of unused dynamic LDS
   //  keep it at four.  The other forms are latency-bound and want the eight.)
   const size_t pad_f32 = 16384;
-  const auto launch = [&](auto mode, auto tag, const auto& d) {
+  const auto launch = [&](auto mode, auto tag, const auto& d, auto tone) {
     constexpr int M = decltype(mode)::value, U = decltype(tag)::value;
+    using Tn = decltype(tone);
     StemSrcArgs<U> sa{};
     sa.frames = src.frames; sa.frames_cell = src.frames_cell; sa.center_hm = src.center_hm;
     sa.Cloc = src.Cloc; sa.C = src.C; sa.cam0 = src.cam0; sa.FH = src.H; sa.FW = src.W;
@@ -202,15 +207,16 @@ int launch_stem_conv_src(const StemSource& src, const Act& x, const float* w_dev
     sa.stdv = make_float3(src.stdv[0], src.stdv[1], src.stdv[2]);
     sa.desc = d;
     if (y.Cp == 32)
-      hipLaunchKernelGGL((stem_conv_kernel<M, U, 32>), grid, dim3(256), 0, s, x.p, w_dev, y.p, stats, x.H, x.W, sa);
+      hipLaunchKernelGGL((stem_conv_kernel<M, U, 32, Tn>), grid, dim3(256), 0, s, x.p, w_dev, y.p, stats, x.H, x.W, sa,
+                         tone);
     else
-      hipLaunchKernelGGL((stem_conv_kernel<M, U, 16>), grid, dim3(256), (M == 1 && U == 0) ? pad_f32 : 0, s, x.p,
-                         w_dev, y.p, stats, x.H, x.W, sa);
+      hipLaunchKernelGGL((stem_conv_kernel<M, U, 16, Tn>), grid, dim3(256), (M == 1 && U == 0) ? pad_f32 : 0, s, x.p,
+                         w_dev, y.p, stats, x.H, x.W, sa, tone);
     return 0;
   };
-  if (dispatch_src(src.source, [&](auto tag, const auto& d) {
-        return src.mode == 1 ? launch(std::integral_constant<int, 1>{}, tag, d)
-                             : launch(std::integral_constant<int, 2>{}, tag, d);
+  if (dispatch_src(src.source, [&](auto tag, const auto& d, auto tone) {
+        return src.mode == 1 ? launch(std::integral_constant<int, 1>{}, tag, d, tone)
+                             : launch(std::integral_constant<int, 2>{}, tag, d, tone);
       }))
     return 1;
   JH_CHECK_HIP(hipGetLastError());

@@ -31,6 +31,22 @@ class _Native2D:
         pc, pk = N.Params(center_state), N.Params(kp_state)
         N.check(N.lib().jh_predictor2d_create(pc.handle, pk.handle, ctypes.byref(c),
                                               ctypes.byref(self.handle)))
+        self._toned = False
+
+    def set_tone(self, tone):
+        """tone: a ToneTables of one camera, or None = the plain form (jh_predictor2d_set_tone; copied on the current
+        stream, the first such call allocates the buffer)."""
+        from ..tone import check_tone
+        tone = check_tone(tone, 1)
+        if tone is None:
+            if self._toned:
+                N.check(N.lib().jh_predictor2d_set_tone(self.handle, None, N.stream()))
+                self._toned = False
+            return
+        dev = torch.tensor(tone.tables).to("cuda")
+        N.check(N.lib().jh_predictor2d_set_tone(self.handle, N.ptr(dev), N.stream()))
+        dev.record_stream(torch.cuda.current_stream())          # (copied by the call: free once it is enqueued)
+        self._toned = True
 
     def _forward(self, frames):
         """The forward of checked frames (a _native.Frames of T images of this predictor's size)."""
@@ -68,6 +84,16 @@ class JarvisPredictor2D(nn.Module):
         self.bounding_box_size = cfg.KEYPOINTDETECT.BOUNDING_BOX_SIZE
         self.center_detect_img_size = int(cfg.CENTERDETECT.IMAGE_SIZE)
         self._native = {}
+        self._tone = None                                    # the ToneTables in force (set_tone)
+
+    def set_tone(self, tone):
+        """tone: a ToneTables of ONE camera ((1,3,256); a (3,256) array too), or None: every forward of byte frames then
+        replaces byte k of channel ch by tone.tables[0][ch][k] in place of k / 255 (JarvisPredictor3D.set_tone).  It
+        holds for every native predictor this object has or later makes."""
+        from ..tone import check_tone
+        self._tone = check_tone(tone, 1)
+        for pr in self._native.values():
+            pr.set_tone(self._tone)
 
     def native(self, img_h, img_w, batch=1):
         key = (img_h, img_w, batch)
@@ -75,6 +101,8 @@ class JarvisPredictor2D(nn.Module):
             self._native[key] = _Native2D(flat_state(self.centerDetect),
                                           flat_state(self.keypointDetect), self.cfg, img_h, img_w,
                                           batch, self.precision)
+            if self._tone is not None:
+                self._native[key].set_tone(self._tone)
         return self._native[key]
 
     def forward(self, img, frame_layout=None):

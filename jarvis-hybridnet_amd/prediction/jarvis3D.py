@@ -98,8 +98,28 @@ class JarvisPredictor3D(nn.Module):
         self.reproTool = ReprojectionTool()
         self.center_detect_img_size = int(cfg.CENTERDETECT.IMAGE_SIZE)
         self._native = {}
+        self._tone = None                                    # the ToneTables in force (set_tone)
+
+    def set_tone(self, tone):
+        """tone: a ToneTables of NUM_CAMERAS cameras (tone.ToneTables: identity, from_bytes, from_curve), or None.  From
+        now on every forward of byte frames -- uint8 BGR, YUV, surfaces, raw sensor and pixel surfaces -- replaces byte
+        k of channel ch of camera c by tone.tables[c][ch][k] in place of k / 255 inside the resize / crop fetch: black
+        level, gain, white balance and gamma without a host pass.  The result equals, bit for bit, forward() on the
+        fp32 frames tables[c][ch][bytes].  It holds for every native predictor this object has or later makes
+        (native(), native_streams()).  fp32 frames have no byte: forward() then raises RuntimeError ("tone tables apply
+        to byte frames").  None: back to the plain form."""
+        from ..tone import check_tone
+        self._tone = check_tone(tone, self.num_cameras)
+        for pr in self._native.values():
+            pr.set_tone(self._tone)
 
     def _make_native(self, img_h, img_w, time_batch, cam_lo, cam_n):
+        pr = self._make_native_plain(img_h, img_w, time_batch, cam_lo, cam_n)
+        if self._tone is not None:
+            pr.set_tone(self._tone)
+        return pr
+
+    def _make_native_plain(self, img_h, img_w, time_batch, cam_lo, cam_n):
         c = self.cfg
         return NativePredictor(
             flat_state(self.centerDetect), flat_state(self.hybridNet),

@@ -54,7 +54,7 @@ def frame_row(points2D, confidences, num_joints):
 
 
 def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch=1,
-                     csv_name="data2D.csv", frame_spec=None, frame_format="bgr", frame_layout=None):
+                     csv_name="data2D.csv", frame_spec=None, frame_format="bgr", frame_layout=None, tone=None):
     """Run `predictor` (JarvisPredictor2D) over an iterable of frames -- (H,W,3) uint8 BGR arrays
     / tensors exactly as cv2 delivers them, or (3,H,W) fp32 RGB -- and write `csv_name`
     (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -76,9 +76,14 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
     frame_layout: a YuvSurface -- the frames are (image_stride,) uint8 described YUV 4:2:0 surfaces (fill callables
     with `frame_spec=((image_stride,), torch.uint8)`) --, a PixelSurface -- (image_stride,) uint8 or any uint8 shape of
     exactly image_stride bytes, such as (H,W,3) RGB --, or a SensorSurface -- (image_stride,) uint8 raw Mono8 /
-    Bayer sensor images --, see predict3D_frames; not together with 'i420' / 'nv12'."""
+    Bayer sensor images --, see predict3D_frames; not together with 'i420' / 'nv12'.
+
+    tone: a ToneTables of one camera: the run is made under predictor.set_tone(tone) (byte frames only; see
+    predict3D_frames).  The predictor keeps the setting afterwards; None leaves it as it is."""
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
     yuv = driver_format(frame_format, frame_spec, 2, frame_layout)
+    if tone is not None:
+        predictor.set_tone(tone)
     from .predict3D import _as_host
     os.makedirs(output_dir, exist_ok=True)
     if params is not None:
@@ -141,12 +146,16 @@ def predict2D_frames(predictor, frames, cfg, output_dir, params=None, time_batch
     return n
 
 
-def predict2D_recordings(predictor, recordings, cfg, output_dir, params=None, time_batch=1, frame_layout=None):
+def predict2D_recordings(predictor, recordings, cfg, output_dir, params=None, time_batch=1, frame_layout=None,
+                         tone=None):
     """`recordings`: {recording path: iterable of frames}.  One CSV per recording, named as the
     reference names them: `data2D.csv` for a single file, `<video>_data2D.csv` per video of a
     directory (predict2D.py:49-68).  Returns {csv file name: number of frames}.  frame_layout: the YuvSurface or SensorSurface of
-    every recording's frames (predict2D_frames), or None."""
+    every recording's frames (predict2D_frames), or None.  tone: the ToneTables of every recording's camera
+    (predict2D_frames), or None."""
     kw = {} if frame_layout is None else {"frame_layout": frame_layout}
+    if tone is not None:
+        kw["tone"] = tone
     multiple = len(recordings) > 1 or bool(getattr(params, "multiple_videos", False))
     done = {}
     for i, (path, frames) in enumerate(recordings.items()):

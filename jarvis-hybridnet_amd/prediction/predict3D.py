@@ -185,7 +185,7 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                      distortionCoefficients, cfg, output_dir, params=None, time_batch=1, streams=1,
                      frame_spec=None, frame_format="bgr", camera_mask=None, output_2d=False, camera_names=None,
                      frame_layout=None, centers=None, output_spread=False, output_triangulated=False,
-                     max_subjects=None, subject_params=None, track=None, joint_mask=None):
+                     max_subjects=None, subject_params=None, track=None, joint_mask=None, tone=None):
     """Run `predictor` over an iterable of multi-view frame sets -- (C,H,W,3) uint8 BGR
     arrays / tensors exactly as cv2 delivers them, or (C,3,H,W) fp32 RGB -- and write
     data3D.csv (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -303,11 +303,18 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     sum of 2^c (rows of joint_mask.joint_cameras_row, the header of joint_mask.create_header_joint_cameras when
     data3D.csv gets its header) --, 'NaN' x 2J for an invalid frame set.  It composes with time_batch, streams,
     camera_mask, centers and the other outputs; a tensor-valued mask is not taken here, and together with max_subjects
-    it is a ValueError."""
+    it is a ValueError.
+
+    tone: a ToneTables of NUM_CAMERAS cameras (black level, gain, white balance and gamma per camera and channel as one
+    byte-to-value table, applied inside the resize / crop fetch): the run is made under predictor.set_tone(tone), and
+    its files are byte-identical to those of a run on the fp32 frames tables[c][ch][bytes].  Byte frames only (fp32
+    frame sets raise RuntimeError).  The predictor keeps the setting afterwards; None leaves it as it is."""
     import contextlib
     from ..joint_mask import create_header_joint_cameras, joint_cameras_row
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
     yuv = driver_format(frame_format, frame_spec, 3, frame_layout)
+    if tone is not None:
+        predictor.set_tone(tone)
     tri_params = N.triangulation_params(output_triangulated)
     tail = 3 if tri_params is not None else 0                   # (points, views and error of the Triangulated3D ...)
     jm_params = None
