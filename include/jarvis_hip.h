@@ -234,6 +234,73 @@ int jh_predictor_set_calibration_frames(jh_predictor* pr, const float* cam_dev /
  * Validation: pr non-NULL; otherwise non-zero with jh_last_error() set, nothing enqueued. */
 int jh_predictor_set_centers(jh_predictor* pr, const float* centers_dev /* (T,3) or NULL */, void* stream);
 
+/* Centre keyframes (ABI v4, additive; new design: the reference detects on every frame set).  The rows of a time batch
+ * are consecutive frame sets, and stage 1 only decides where the crops and the voxel cube go: CenterDetect runs on the
+ * KEY rows of the batch -- every k-th row and the last one --, the rows in between take a centre interpolated on the
+ * device between their two key rows, and every row then runs the centred stage 2 and stage 3 of
+ * jh_predictor_set_centers.  Opt-in: a predictor that never asks owns, launches and computes what it always did.
+ *
+ * Definition, for T = time_batch rows of which the first n_rows are real (1 <= n_rows <= T; a short last group of a
+ * recording is padded behind them) and every = k >= 1:
+ *  1. Key rows.  Key slot i holds row min(i * k, n_rows - 1).  The distinct ones are keys = {0, k, 2k, ... < n_rows}
+ *     and n_rows - 1, ascending: ceil((n_rows - 1) / k) + 1 of them.  A predictor has K(T, k) = ceil((T - 1) / k) + 1
+ *     key slots (1 for T = 1), the count at n_rows = T; with n_rows < T the slots behind the last key repeat it, so no
+ *     launch size depends on n_rows and nothing is read out of range.  jh_center_keyframe_rows is this rule on the host.
+ *  2. Stage 1 on the key slots.  The resize (or fused stem fetch), CenterDetect and the centre arg-max run on K * C
+ *     images, image (i, c) being camera c of key slot i's row, read where it lies through the per-image fetch (any frame
+ *     format, tone tables included).  CenterDetect is a second launch plan of the predictor, for K * C images in the
+ *     PREDICTOR's time-batch class, so a key row's detection has the bits the full plan gives that row.  The detections
+ *     of slot i go to row keys[i] of the (T,C,3) detection buffer; every other row of it is zero.
+ *  3. The triangulation of a detected call (plain, or masked under a camera mask) runs over all T rows: a key row gets
+ *     its float centre and valid = (cameras with maxval > 50) >= 2 with the arithmetic of a detected call.
+ *  4. Fill, row t -> centre[t] (fp32) and source[t] (int32):
+ *       t a key row:   valid -> its float centre unchanged, source 0 (detected); not valid -> NaN, source -1.  An invalid
+ *                      key row is never given a neighbour's centre.
+ *       t between the key rows ta < t < tb, a and b their float centres:
+ *         both valid   w = (float)(t - ta) / (float)(tb - ta);  centre = a + (b - a) * w, per coordinate, every operation
+ *                      rounded once to fp32 and none contracted (fdiv, fsub, fmul, fadd in that order); source 1.
+ *         one valid    that key's centre unchanged, source 2 (held).
+ *         none valid   NaN, source -1.
+ *       t >= n_rows:   the centre of row n_rows - 1, source 2, or NaN and -1 where that row is not valid.
+ *  5. The filled (T,3) centres go through the code of jh_predictor_set_centers: integer centre, crop centres and valid
+ *     as defined there (a NaN centre is its invalid row), then the crop stem, KeypointDetect, the gather, V2V and the
+ *     tail, and behind them jh_predictor_views2d, the spread, jh_predictor_triangulate_joints and the joint-mask
+ *     consensus, exactly as after jh_predictor_set_centers.
+ * Results: with every = 1 every row is a key row and the call equals the detected call bit for bit wherever that is
+ * valid (an invalid row is the invalid row of a centred call: computed as if its centre were (0,0,0)).  For any k the
+ * call equals, bit for bit, the centred call on the filled centres, whose key rows are the detected call's.  A valid
+ * key row whose triangulated centre is not finite or not below 2^24 is an invalid row here (jh_predictor_set_centers).
+ * The result depends on which rows share a batch: the key rows are rows of the batch.
+ *
+ * jh_center_keyframe_rows: host only, no device is touched.  The distinct key rows of (time_batch, every, n_rows),
+ * ascending, into rows[0 .. cap); rows may be NULL (cap is then ignored).  Returns their number, or -1 with
+ * jh_last_error() set: time_batch < 1, every < 1, n_rows outside 1 .. time_batch, cap below the number.
+ *
+ * jh_predictor_set_center_keyframes: every = 0 switches the feature off (center_params may be NULL; the plan and the
+ * buffers stay for the next enabling call).  every >= 1: from now on every whole-path forward of this predictor
+ * (jh_predictor_forward, _u8, _yuv, _surface, _sensor, _pixels, _masked, _images) is a keyframe call with that every
+ * and n_rows.  It runs plain launches and touches no graph slot, like a joint-masked call; the captured graphs replay
+ * with their bits once it is off.  The staged entry points, jh_predictor_detect_subjects and the 2D predictor are not
+ * affected.  The first enabling call builds the key plan and allocates the buffers (T * C pointers and detections, the
+ * (T,3) centres and (T) sources) -- never jh_predictor_create, so jh_predictor_device_bytes grows only then --, and a
+ * call whose every gives another K builds another plan in place of it.  Such a call needs center_params (CenterDetect's
+ * parameters again: those of jh_predictor_create may be gone), must be made outside a stream capture and synchronises
+ * the device; a call that changes n_rows alone, or every within one K, builds nothing, and center_params may be NULL.
+ * Validation, non-zero with jh_last_error() set and nothing enqueued: pr NULL; every < 0; a predictor created without
+ * CenterDetect weights; cam_n < num_cameras; n_rows outside 1 .. time_batch; center_params NULL where the plan has to be
+ * built.  Caller-supplied centres and keyframes both in force: the FORWARD fails, with a message that names both.
+ *
+ * jh_predictor_get_center_keyframes: the filled centres (T,3) fp32 and sources (T) int32 of the last keyframe call,
+ * copied on `stream`; either may be NULL.
+ * jh_predictor_debug after a keyframe call: center3d is the filled centre, the integers and crop centres are derived
+ * from it, det holds the key rows' detections and zeros elsewhere.  jh_predictor_debug_mask after a masked one: n_active
+ * as for a detected masked call, num_cams_detect = 0 as after a centred call (the key rows' counts are not kept). */
+int jh_center_keyframe_rows(int time_batch, int every, int n_rows, int32_t* rows, int cap);   /* no GPU needed */
+int jh_predictor_set_center_keyframes(jh_predictor* pr, const jh_params* center_params, int every, int n_rows,
+                                      void* stream);
+int jh_predictor_get_center_keyframes(jh_predictor* pr, float* centers_dev /* (T,3) */, int32_t* source_dev /* (T) */,
+                                      void* stream);
+
 /* Per-camera tone tables: black level, gain, white balance and gamma as ONE byte-to-value lookup inside the resize /
  * crop fetch, so that raw-sensor, decoder-surface and plain BGR frames reach the networks in the distribution the
  * networks were trained on without a host pass.

@@ -187,6 +187,9 @@ _SIGS = {
     "jh_predictor_set_calibration_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor_set_centers": (c_int, [c_void_p, c_void_p, c_void_p]),
     "jh_predictor_set_tone": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "jh_center_keyframe_rows": (c_int, [c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int]),
+    "jh_predictor_set_center_keyframes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "jh_predictor_get_center_keyframes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "jh_predictor2d_set_tone": (c_int, [c_void_p, c_void_p, c_void_p]),
     "jh_op_frames_to_rgb_f32": (c_int, [c_void_p, c_int, ctypes.POINTER(YuvSurfaceStruct),
                                         ctypes.POINTER(SensorSurfaceStruct), ctypes.POINTER(PixelSurfaceStruct), c_int,
@@ -646,6 +649,35 @@ def centers(value, T):
     elif shape != (T, 3):
         raise ValueError("centers must have shape %s (world millimetres, one row per frame set); got %s" % (want, shape))
     return value.to(torch.float32).contiguous()
+
+
+def center_keyframe_rows(time_batch, every, n_rows=None):
+    """The key rows of a time batch under centre keyframes, ascending (jh_center_keyframe_rows: the library's own rule,
+    host arithmetic, no device): {0, every, 2 every, ... < n_rows} and n_rows - 1, of the first n_rows (default: all)
+    rows of the batch.  ValueError for what the library refuses: time_batch < 1, every < 1, n_rows outside
+    1 .. time_batch, or an argument that is no int."""
+    n_rows = time_batch if n_rows is None else n_rows
+    for name, v in dict(time_batch=time_batch, every=every, n_rows=n_rows).items():
+        if isinstance(v, bool) or not isinstance(v, int) or abs(v) >= 2 ** 31:
+            raise ValueError("%s must be an int, got %r" % (name, v))
+    rows = (ctypes.c_int32 * max(1, min(time_batch, 1 << 20)))()
+    n = lib().jh_center_keyframe_rows(time_batch, every, n_rows, rows, len(rows))
+    if n < 0:
+        raise ValueError(lib().jh_last_error().decode())
+    return list(rows[:n])
+
+
+def center_every(value, T):
+    """A center_every argument checked -> None or (every, n_rows).  None stays None; an int k >= 1: CenterDetect on
+    every k-th row of the T-row batch and on the last one; (k, n_rows): likewise for a batch whose first n_rows rows
+    are real (the padded last group of a recording), 1 <= n_rows <= T.  Anything else raises ValueError."""
+    if value is None:
+        return None
+    every, n_rows = value if isinstance(value, (tuple, list)) and len(value) == 2 else (value, T)
+    if n_rows is None:
+        raise ValueError("center_every=(every, n_rows): n_rows must be an int, got None")
+    center_keyframe_rows(T, every, n_rows)
+    return every, n_rows
 
 
 def subjects_params(max_subjects, max_peaks=None, nms_radius=4, min_views=2, min_peak=50.0, max_error_px=24.0):

@@ -20,6 +20,11 @@ from .triangulated import Triangulated3D
 # confidences2D 0, errors NaN; an invalid frame has NaN reprojections too.
 Views2D = collections.namedtuple("Views2D", "points2D confidences2D reprojections errors used")
 
+# What a centre-keyframe call placed its rows by (jh_predictor_get_center_keyframes, include/jarvis_hip.h): centers (T,3)
+# fp32 world millimetres, NaN where the row has none; source (T) int32: 0 detected (a valid key row), 1 interpolated
+# between its two key rows, 2 held (one neighbouring key row's centre; a padding row), -1 none.
+CenterKeyframes = collections.namedtuple("CenterKeyframes", "centers source")
+
 
 class NativePredictor:
     """Owns the launch plans of CenterDetect, KeypointDetect and V2V plus all
@@ -43,6 +48,8 @@ class NativePredictor:
         self.Hh = bbox // 2
         self.handle = ctypes.c_void_p()
         pc = N.Params(center_state) if center_state is not None else None
+        # (kept: the first set_center_keyframes call of an `every` hands CenterDetect's parameters over again)
+        self._center_state = center_state
         ph = N.Params(hybrid_state)
         N.check(N.lib().jh_predictor_create(pc.handle if pc else None, ph.handle,
                                             ctypes.byref(cfg), ctypes.byref(self.handle)))
@@ -53,6 +60,8 @@ class NativePredictor:
         self._spread = False                         # the 3D stage runs the spread form of its tail (set_spread)
         self._joint_masked = False                   # a joint mask is in force (set_joint_mask)
         self._toned = False                          # tone tables are in force (set_tone)
+        self._keyframed = False                      # centre keyframes are in force (set_center_keyframes)
+        self._key_slots = 0                          # the key slots the predictor's key plan was built for (0: none)
 
     def close(self):
         if getattr(self, "handle", None) and N is not None and N._lib is not None:
@@ -111,6 +120,42 @@ class NativePredictor:
         N.check(N.lib().jh_predictor_set_centers(self.handle, N.ptr(dev), N.stream()))
         dev.record_stream(torch.cuda.current_stream())          # (copied by the call: free once it is enqueued)
         self._centred = True
+
+    # ---- centre keyframes ---------------------------------------------------
+    def set_center_keyframes(self, every, n_rows=None):
+        """every = k >= 1: from now on every forward of this predictor runs CenterDetect on the key rows of its time
+        batch alone -- rows 0, k, 2k, ... and the last real one (_native.center_keyframe_rows) -- and gives the rows in
+        between a centre interpolated on the device between their two key rows; every row then runs the centred stage 2
+        and 3 (jh_predictor_set_center_keyframes has the definition).  n_rows: how many leading rows of the batch are
+        real (default: all); the padding rows behind them hold the last real row's centre and never serve as keys.
+        None / 0: off; a predictor that holds none is not called at all.  The first call of an `every` builds a second
+        CenterDetect plan for the key rows (not inside a stream capture; device_bytes grows); with every = 1 the result
+        equals the detected one bit for bit.  The library refuses (RuntimeError) every < 0, n_rows outside 1 .. T, a
+        predictor without CenterDetect weights and one that does not own all cameras."""
+        if not every:
+            if self._keyframed:
+                N.check(N.lib().jh_predictor_set_center_keyframes(self.handle, None, 0, 0, N.stream()))
+                self._keyframed = False
+            return
+        every, n_rows = int(every), self.T if n_rows is None else int(n_rows)
+        slots = N.lib().jh_center_keyframe_rows(self.T, every, self.T, None, 0)      # (-1: the library refuses below)
+        params = None
+        if slots != self._key_slots and self._center_state is not None:
+            params = N.Params(self._center_state)
+        N.check(N.lib().jh_predictor_set_center_keyframes(self.handle, params.handle if params else None, every,
+                                                          n_rows, N.stream()))
+        self._keyframed, self._key_slots = True, slots
+        self.device_bytes = N.lib().jh_predictor_device_bytes(self.handle)
+
+    def center_keyframes(self):
+        """The centres the last keyframe call placed its rows by and where each came from -> CenterKeyframes of device
+        tensors, copied on the current stream (jh_predictor_get_center_keyframes)."""
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = CenterKeyframes(torch.empty((self.T, 3), device=dev),
+                              torch.empty((self.T,), device=dev, dtype=torch.int32))
+        N.check(N.lib().jh_predictor_get_center_keyframes(self.handle, N.ptr(out.centers), N.ptr(out.source),
+                                                          N.stream()))
+        return out
 
     # ---- per-camera tone tables --------------------------------------------
     def set_tone(self, tone):
@@ -199,7 +244,7 @@ class NativePredictor:
 
     # ---- single-GPU forward ----------------------------------------------
     def forward(self, frames, out=None, frame_format=None, camera_mask=None, frame_layout=None, centers=None,
-                return_spread=False, joint_mask=None):
+                return_spread=False, joint_mask=None, center_every=None):
         """frames (T,C,3,H,W) fp32 RGB, or (T,C,H,W,3) uint8 BGR as decoded, or with frame_format 'i420' / 'nv12'
         (T,C,3H/2,W) uint8 YUV 4:2:0 -> points (T,J,3), conf (T,J), valid (T) int32.  frame_format None: the
         dtype decides between fp32 RGB and uint8 BGR; 'bgr' requires uint8 BGR.
@@ -214,19 +259,24 @@ class NativePredictor:
         the call (set_spread) and decides for this call alone; points, conf and valid keep their bits.
         joint_mask (_native.joint_mask: a (T,J,C) mask, 'consensus', or joints3d_params keywords): every joint's
         voxel volume is averaged over that joint's own cameras and the call's JointMask comes last; None: the plain
-        forward -- a joint mask set earlier is cleared first."""
+        forward -- a joint mask set earlier is cleared first.
+        center_every (k, or (k, n_rows); _native.center_every): this call detects on its key rows only
+        (set_center_keyframes) and its CenterKeyframes comes last of all; None: every row detects -- keyframes set
+        earlier are cleared first.  Not together with centers (ValueError)."""
         return self._forward(self._describe(frames, frame_format, frame_layout), out,
                              N.camera_mask(camera_mask, (self.T, self.C)), N.centers(centers, self.T), return_spread,
-                             N.joint_mask(joint_mask, self.T, self.J, self.C))
+                             N.joint_mask(joint_mask, self.T, self.J, self.C), N.center_every(center_every, self.T))
 
-    def forward_images(self, frames, out=None, camera_mask=None, centers=None, return_spread=False, joint_mask=None):
+    def forward_images(self, frames, out=None, camera_mask=None, centers=None, return_spread=False, joint_mask=None,
+                       center_every=None):
         """forward() on T * C separately placed images: `frames` what _native.frame_images made of the flat list
         (index t * C + c) (jh_predictor_forward_images).  The images are read where they lie; nothing is gathered."""
         if len(frames.images) != self.T * self.C:
             raise ValueError("expected %d images (time_batch * num_cameras), got %d" % (self.T * self.C,
                                                                                          len(frames.images)))
         return self._forward(frames, out, N.camera_mask(camera_mask, (self.T, self.C)), N.centers(centers, self.T),
-                             return_spread, N.joint_mask(joint_mask, self.T, self.J, self.C))
+                             return_spread, N.joint_mask(joint_mask, self.T, self.J, self.C),
+                             N.center_every(center_every, self.T))
 
     def _describe(self, frames, frame_format=None, frame_layout=None):
         """Raw pointers cross the C ABI: refuse anything whose bytes would be misread (_native.describe_frames for
@@ -234,17 +284,23 @@ class NativePredictor:
         return N.describe_frames(frames, (self.T, self.Cloc), frame_format, frame_layout,
                                  (self.cfg.img_h, self.cfg.img_w), error=RuntimeError, in_place=True)
 
-    def _forward(self, frames, out, mask, centers=None, spread=False, joint_mask=None):
+    def _forward(self, frames, out, mask, centers=None, spread=False, joint_mask=None, center_keys=None):
         """The forward of checked frames (a _native.Frames) with a checked mask (_native.camera_mask) or None, and
         checked centres (_native.centers) or None = detect.  spread: the call runs the spread form and its Spread3D
         follows the three outputs.  joint_mask: what _native.joint_mask made, or None = the plain forward; the call's
-        JointMask comes last."""
+        JointMask comes last.  center_keys: what _native.center_every made, or None = every row detects; the call's
+        CenterKeyframes comes last of all."""
+        if centers is not None and center_keys is not None:
+            raise ValueError("centers= and center_every= do not combine: a call either brings its centres or detects "
+                             "them on its key rows")
         dev = frames.device
         self.set_spread(spread)
         if joint_mask is not None or self._joint_masked:
             self.set_joint_mask(joint_mask)
         if centers is not None or self._centred:
             self.set_centers(centers)
+        if center_keys is not None or self._keyframed:
+            self.set_center_keyframes(*(center_keys or (0,)))
         if out is None:
             out = (torch.empty((self.T, self.J, 3), device=dev),
                    torch.empty((self.T, self.J), device=dev),
@@ -255,7 +311,8 @@ class NativePredictor:
         if mask is not None and mask.is_cuda:
             mask.record_stream(torch.cuda.current_stream())     # (free once the call is enqueued)
         res = tuple(out) + (self.spread(),) if spread else out
-        return tuple(res) + (self.joint_mask(),) if joint_mask is not None else res
+        res = tuple(res) + (self.joint_mask(),) if joint_mask is not None else res
+        return tuple(res) + (self.center_keyframes(),) if center_keys is not None else res
 
     # ---- camera-sharded stages -------------------------------------------
     def stage_center(self, frames, det):
@@ -540,7 +597,8 @@ class MultiStreamPredictor:
         self._calib_of[i] = (self._calib, self._calib_refs)       # the tensors live as long as their key is compared
 
     def forward(self, frames, out=None, then=None, frame_format=None, camera_mask=None, return_2d=False,
-                frame_layout=None, centers=None, return_spread=False, return_triangulated=False, joint_mask=None):
+                frame_layout=None, centers=None, return_spread=False, return_triangulated=False, joint_mask=None,
+                center_every=None):
         """return_2d: the five tensors of NativePredictor.views2d for this batch are appended to the outputs
         (points, conf, valid, points2D, confidences2D, reprojections, errors, used).
         return_spread: the three tensors of the batch's Spread3D (cov (T,J,3,3), peak, mass) are appended behind them.
@@ -552,11 +610,18 @@ class MultiStreamPredictor:
         before its event is recorded (the drivers enqueue the device->host copy of the results there); its
         return value replaces the outputs.  frame_format, camera_mask, frame_layout: as NativePredictor.forward.
         centers (T,3): the centres of THIS batch (NativePredictor.set_centers), written on the stream of the predictor
-        the batch runs on; None: the batch detects."""
+        the batch runs on; None: the batch detects.
+        center_every (k, or (k, n_rows) for a batch whose first n_rows rows are real; _native.center_every): THIS batch
+        detects on its key rows only (NativePredictor.set_center_keyframes) and the two tensors of its CenterKeyframes
+        (centers, source) are appended last of all.  The key rows are rows of the batch, so with k > 1 the result
+        depends on how a recording is cut into batches (time_batch), not on the number of streams."""
         p0 = self.preds[0]
         described = p0._describe(frames, frame_format, frame_layout)               # before any stream work
         camera_mask = N.camera_mask(camera_mask, (p0.T, p0.C))
         centers = N.centers(centers, p0.T)
+        center_keys = N.center_every(center_every, p0.T)
+        if centers is not None and center_keys is not None:
+            raise ValueError("centers= and center_every= do not combine")
         tri_params = N.triangulation_params(return_triangulated)
         if joint_mask is not None:
             joint_mask = N.joint_mask(joint_mask, p0.T, p0.J, p0.C)
@@ -574,7 +639,10 @@ class MultiStreamPredictor:
         with torch.cuda.stream(s):
             self._frames_calibration(i)
             res = self.preds[i]._forward(described, out, camera_mask, centers, return_spread,
-                                         **({} if joint_mask is None else {"joint_mask": joint_mask}))
+                                         **({} if joint_mask is None else {"joint_mask": joint_mask}),
+                                         **({} if center_keys is None else {"center_keys": center_keys}))
+            if center_keys is not None:
+                res, keyframes = res[:-1], tuple(res[-1])
             if joint_mask is not None:
                 res, jm = res[:-1], tuple(res[-1])
             if return_spread:
@@ -587,6 +655,8 @@ class MultiStreamPredictor:
                 res = tuple(res) + tuple(self.preds[i].triangulate_joints(camera_mask=camera_mask, params=tri_params))
             if joint_mask is not None:
                 res = tuple(res) + jm
+            if center_keys is not None:
+                res = tuple(res) + keyframes
             if then is not None:
                 res = then(res)
             ev = torch.cuda.Event(enable_timing=self.timing)

@@ -3,6 +3,7 @@
 // feature's memory is a workspace its first call carves (predictor.h: first_call_carve): a predictor that never asks
 // owns what jh_predictor_create gave it.
 #include "predictor.h"
+#include "center_keys.h"
 #include "views2d.h"
 #include "subjects.h"
 #include "tracks.h"
@@ -135,6 +136,67 @@ int jh_predictor_set_centers(jh_predictor* pr, const float* centers_dev, void* s
                               s));
   pr->centers_on = true;
   return 0;
+}
+
+// ---- centre keyframes (csrc/center_keys.h)
+int jh_center_keyframe_rows(int time_batch, int every, int n_rows, int32_t* rows, int cap) {
+  int count = 0;
+  return center_key_rows(time_batch, every, n_rows, rows, cap, &count) ? -1 : count;
+}
+
+int jh_predictor_set_center_keyframes(jh_predictor* pr, const jh_params* center_params, int every, int n_rows,
+                                      void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(pr, "jh_predictor_set_center_keyframes: null predictor");
+  JH_REQUIRE(every >= 0, "jh_predictor_set_center_keyframes: every must be 0 (off) or at least 1");
+  jh_predictor::CenterKeys& ck = pr->ck;
+  if (every == 0) {                           // (back to detection on every row; the plan and the buffers stay)
+    ck.every = 0;
+    return 0;
+  }
+  JH_REQUIRE(pr->center, "jh_predictor_set_center_keyframes: predictor was created without CenterDetect weights");
+  JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "jh_predictor_set_center_keyframes needs all cameras local");
+  JH_REQUIRE(n_rows >= 1 && n_rows <= pr->T, "jh_predictor_set_center_keyframes: n_rows must be 1 .. time_batch");
+  const int K = center_key_slots(pr->T, every);
+  const char* what = "a jh_predictor_set_center_keyframes call that builds the key plan allocates: make it outside a "
+                     "stream capture";
+  if (!ck.plan || ck.K != K) {
+    JH_REQUIRE(center_params, "jh_predictor_set_center_keyframes: the key plan has to be built, which needs "
+               "center_params");
+    if (outside_capture(s, what)) return 1;
+    // (in the PREDICTOR's time-batch class, as a predictor built for a camera subset is: node forms and the blocking of
+    // the InstanceNorm passes follow T, not K)
+    std::unique_ptr<EffTrackPlan> plan = pr->setup.efftrack();
+    if (plan->build(center_params->map, "", pr->cfg.center_model, 1, K * pr->C, pr->cfg.center_size,
+                    pr->cfg.center_size)) return 1;
+    JH_CHECK_HIP(hipDeviceSynchronize());     // (the uploads are done; a plan this one replaces is no longer read)
+    ck.plan = std::move(plan);
+    ck.K = K;
+  }
+  if (!ck.table) {
+    const size_t T = pr->T, C = pr->C;
+    struct Ws { const void** table; float *det, *centers; int* source; } w;
+    CarveSizes size;
+    if (first_call_carve(pr->mem, s, what, &w, [&](Carver& c, Ws& p) {
+          p.table = c.take<const void*>(T * C);
+          p.det = c.take<float>(T * C * 3);
+          p.centers = c.take<float>(T * 3);
+          p.source = c.take<int>(T);
+        }, &size)) return 1;
+    ck.table = w.table; ck.det = w.det; ck.centers = w.centers; ck.source = w.source;
+    ck.bytes = size.payload;
+  }
+  ck.every = every; ck.n_rows = n_rows;
+  return 0;
+}
+
+int jh_predictor_get_center_keyframes(jh_predictor* pr, float* centers_dev, int32_t* source_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(pr, "jh_predictor_get_center_keyframes: null predictor");
+  JH_REQUIRE(pr->ck.centers, "jh_predictor_get_center_keyframes: centre keyframes were never enabled "
+             "(jh_predictor_set_center_keyframes)");
+  return copy_if(centers_dev, pr->ck.centers, (size_t)pr->T * 3 * sizeof(float), s) ||
+         copy_if(source_dev, pr->ck.source, (size_t)pr->T * sizeof(int), s);
 }
 
 // ---- tone tables

@@ -213,6 +213,18 @@ int jh::frame_source(int format, int h, int w, FrameSource* out) {
   return 0;
 }
 
+// Bytes from image n to image n + 1 of contiguous frames of h x w images: what the pixel functions of preprocess.h
+// multiply n by -- the fixed formats' image size, a description's image_stride.
+long long jh::image_bytes(const FrameSource& fs, int h, int w) {
+  const long long px = (long long)h * w;
+  return std::visit([&](const auto& d) -> long long {
+    if constexpr (std::is_same_v<std::decay_t<decltype(d)>, std::monostate>)
+      return fs.fmt == kSrcRgbF32 ? px * 12 : fs.fmt == kSrcBgrU8 ? px * 3 : px + px / 2;
+    else
+      return d.image_stride;
+  }, fs.desc);
+}
+
 static_assert(JH_FRAME_SURFACE == kSrcYuvSurface && JH_FRAME_SENSOR == kSrcSensor,
               "frame format codes of the C ABI are preprocess.h's SRC");
 

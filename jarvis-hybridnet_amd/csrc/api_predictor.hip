@@ -1,6 +1,7 @@
 // C ABI, the 3D predictor: creation, the three stages, the whole-path forward (plain launches or one graph launch) and
 // the debug entries.  What a predictor owns is predictor.h; the optional features are api_features.hip.
 #include "predictor.h"
+#include "center_keys.h"
 #include "centers.h"
 #include "preprocess.h"
 #include "reproject.h"
@@ -86,29 +87,35 @@ int jh_predictor::run_3d(const Call& call, const float* heat_all, int t0, float*
   return 0;
 }
 
-// Stage 1 up to CenterDetect's heat map (pr->center->heat): resize or fused stem, then the plan
-int jh::center_heat_impl(jh_predictor* pr, const Call& call_in) {
-  Call call = call_in;
-  if (pr->tone_call(&call)) return 1;
+// Stage 1 up to the heat map of a CenterDetect plan (plan->heat) for the N images of `call`: resize or fused stem, then
+// the plan
+static int center_heat_plan(jh_predictor* pr, EffTrackPlan* plan, int N, const Call& call) {
   hipStream_t s = call.s;
   const FrameSource& fs = call.fs;
-  JH_REQUIRE(pr->center, "predictor was created without CenterDetect weights");
-  const int N = pr->T * pr->Cloc, S = pr->cfg.center_size;
-  if (pr->center->stem_fusable) {
+  const int S = pr->cfg.center_size;
+  if (plan->stem_fusable) {
     // resize + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
-    StemSource& src = pr->center->stem_src;
+    StemSource& src = plan->stem_src;
     src.mode = 1; src.frames = call.frames; src.frames_cell = call.cell; src.source = fs;
     src.H = pr->cfg.img_h; src.W = pr->cfg.img_w;
     for (int i = 0; i < 3; ++i) { src.mean[i] = pr->cfg.mean[i]; src.stdv[i] = pr->cfg.std[i]; }
     // algorithmic bytes of the fused launch: the four bilinear taps of every network-input pixel (px_bytes
     // each) + the stem's output at half resolution (16 or 32 channels = 16 or 32 B per input pixel)
-    pr->center->set_stem_traffic((double)N * S * S * (4.0 * fs.px_bytes() + pr->center->stem_channels()));
+    plan->set_stem_traffic((double)N * S * S * (4.0 * fs.px_bytes() + plan->stem_channels()));
   } else {
     JH_PROF("preprocess_resize", 0.0, (double)N * S * S * (4.0 * fs.px_bytes() + 3 * 4),
-            launch_preprocess_resize(call.frames, fs, pr->center->input.p, N, pr->cfg.img_h,
+            launch_preprocess_resize(call.frames, fs, plan->input.p, N, pr->cfg.img_h,
                                      pr->cfg.img_w, S, pr->cfg.mean, pr->cfg.std, s, call.cell));
   }
-  return pr->center->run(s);
+  return plan->run(s);
+}
+
+// ... of the predictor's own plan (pr->center->heat), all T * Cloc images
+int jh::center_heat_impl(jh_predictor* pr, const Call& call_in) {
+  Call call = call_in;
+  if (pr->tone_call(&call)) return 1;
+  JH_REQUIRE(pr->center, "predictor was created without CenterDetect weights");
+  return center_heat_plan(pr, pr->center.get(), pr->T * pr->Cloc, call);
 }
 
 static int stage_center_impl(jh_predictor* pr, const Call& call, float* det_dev) {
@@ -118,6 +125,33 @@ static int stage_center_impl(jh_predictor* pr, const Call& call, float* det_dev)
   const Act& h = pr->center->heat;
   JH_PROF("center_argmax", 0.0, 4.0 * N * h.H * h.W,
           launch_center_argmax(h.p, det_dev, N, h.H, h.W, h.Cp, s));
+  return 0;
+}
+
+// Stage 1 on the key rows alone (jh_predictor_set_center_keyframes): the key rows' image pointers into the predictor's
+// table, the key plan on them through the per-image fetch (image n = (key slot, camera): its tone camera is n % C), the
+// arg-max, and the K * C detections into their rows of det_all, zeros elsewhere.
+static int stage_center_keys_impl(jh_predictor* pr, const Call& call_in) {
+  Call call = call_in;
+  if (pr->tone_call(&call)) return 1;
+  hipStream_t s = call.s;
+  jh_predictor::CenterKeys& ck = pr->ck;
+  const FrameSource& fs = call.fs;
+  const void* const* src_table = fs.per_image ? call.cell : nullptr;
+  JH_REQUIRE(fs.per_image || !call.cell, "a centre-keyframe call is not recorded into the predictor's graphs");
+  JH_PROF("center_key_table", 0.0, 16.0 * ck.K * pr->C,
+          launch_center_key_table(ck.table, ck.K, pr->C, ck.every, ck.n_rows, call.frames,
+                                  fs.per_image ? 0 : image_bytes(fs, pr->cfg.img_h, pr->cfg.img_w), src_table, s));
+  Call keys = call;
+  keys.fs.per_image = true;
+  keys.frames = ck.table;
+  keys.cell = ck.table;
+  const int N = ck.K * pr->C;
+  if (center_heat_plan(pr, ck.plan.get(), N, keys)) return 1;
+  const Act& h = ck.plan->heat;
+  JH_PROF("center_argmax", 0.0, 4.0 * N * h.H * h.W, launch_center_argmax(h.p, ck.det, N, h.H, h.W, h.Cp, s));
+  JH_PROF("center_key_scatter", 0.0, 4.0 * 3 * (N + pr->T * pr->C),
+          launch_center_key_scatter(ck.det, pr->det_all, pr->T, pr->C, ck.every, ck.n_rows, s));
   return 0;
 }
 
@@ -152,6 +186,16 @@ static int stage_keypoints_impl(jh_predictor* pr, const Call& call_in, const flo
     JH_PROF(call.mask ? "triangulate_masked" : "triangulate", 0.0, 0.0,
             launch_triangulate(det_all_dev, pr->calib_at(0), pr->c3f, cs.c3i, cs.chm, cs.valid, pr->T, pr->C, k.x, k.y,
                                255.f, pr->B / 2, c.img_w, c.img_h, call.mask, pr->n_active, pr->n_detect, s));
+    if (call.center_keys) {
+      // the key rows have their float centre and validity with the arithmetic of a detected call; the fill gives every
+      // row its centre, and from there on the batch is the centred one
+      JH_PROF("center_key_fill", 0.0, 32.0 * pr->T,
+              launch_center_key_fill(pr->c3f, cs.valid, pr->ck.centers, pr->ck.source, pr->T, pr->ck.every,
+                                     pr->ck.n_rows, s));
+      JH_PROF("centers", 0.0, 0.0,
+              launch_centers(pr->ck.centers, pr->calib_at(0), pr->c3f, cs.c3i, cs.chm, cs.valid, pr->T, pr->C, pr->B / 2,
+                             c.img_w, c.img_h, call.mask, pr->n_active, pr->n_detect, s));
+    }
   }
   if (det_all_dev != pr->det_all)
     JH_CHECK_HIP(hipMemcpyAsync(pr->det_all, det_all_dev, (size_t)pr->T * pr->C * 3 * sizeof(float),
@@ -187,8 +231,12 @@ int jh::stage_3d_impl(jh_predictor* pr, const Call& call, const float* heat_all_
 }
 
 static int forward_eager(jh_predictor* pr, const Call& call, float* points_dev, float* conf_dev, int32_t* valid_dev) {
-  // (centres supplied by the caller: stage 1 does not run at all)
-  if (!pr->centers_on && stage_center_impl(pr, call, pr->det_all)) return 1;
+  // (centres supplied by the caller: stage 1 does not run at all; centre keyframes: on the key rows)
+  if (call.center_keys) {
+    if (stage_center_keys_impl(pr, call)) return 1;
+  } else if (!pr->centers_on && stage_center_impl(pr, call, pr->det_all)) {
+    return 1;
+  }
   if (stage_keypoints_impl(pr, call, pr->det_all, nullptr)) return 1;
   // JH_JOINT_MASK_CONSENSUS: the members of the per-joint consensus over the heat maps stage 2 has just written -- the
   // call's camera mask, the centre set stage 2 wrote and the calibration in force -- become the joint mask of stage 3
@@ -261,6 +309,8 @@ static int forward_impl(jh_predictor* pr, const void* frames_dev, const FrameSou
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "forward needs all cameras local");
   JH_REQUIRE(pr->T3 == pr->T, "forward needs time_batch_3d == time_batch");
   JH_REQUIRE(frames_dev && points_dev && conf_dev, "null frame / output pointer");
+  JH_REQUIRE(!(pr->centers_on && pr->ck.every), "caller-supplied centres (jh_predictor_set_centers) and centre "
+             "keyframes (jh_predictor_set_center_keyframes) are both in force: switch one of them off");
   // (tone tables in force become part of the call's source here, so that the graph slot below sees them)
   if (pr->tone_call(&call)) return 1;
   if (mask_dev)
@@ -269,10 +319,13 @@ static int forward_impl(jh_predictor* pr, const void* frames_dev, const FrameSou
   pr->slot = 0;                               // (the whole-path forward and its captured graph: centre set 0)
   // a joint mask in force (jh_predictor_set_joint_mask): plain launches, no graph slot of its own -- the captured
   // graphs stay as they are and replay again once the mode is off
+  // ... and so do centre keyframes (jh_predictor_set_center_keyframes)
+  call.center_keys = pr->ck.every != 0;
   if (pr->jm_mode != JH_JOINT_MASK_OFF) {
     call.joint_mask = pr->jm_buf;
     return forward_eager(pr, call, points_dev, conf_dev, valid_dev);
   }
+  if (call.center_keys) return forward_eager(pr, call, points_dev, conf_dev, valid_dev);
   // per-launch profiling needs the launches one by one; a caller that is itself capturing this
   // stream gets the plain launches too (its graph then holds them)
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -305,7 +358,7 @@ int jh_predictor_create(const jh_params* center_params, const jh_params* hybrid_
   // (... and with it the blocking of the InstanceNorm / pooled-sum passes, Plan::norm_block_kb; JH_NODE_ROWS=0 switches
   //  every class-dependent form off: one arithmetic for all time batches)
   const int norm_kb = node_class == NodeBatchClass::AtLeast8 && JH_ENV_KNOB("JH_NODE_ROWS") != 0 ? 64 : 0;
-  PlanSetup setup;
+  PlanSetup& setup = pr->setup;
   if (setup.init(&pr->cfg, node_class, norm_kb)) return 1;
   if (center_params) {
     pr->center = setup.efftrack();
@@ -382,7 +435,8 @@ int jh_predictor_precision(const jh_predictor* pr) { return pr ? pr->cfg.precisi
 
 int64_t jh_predictor_device_bytes(const jh_predictor* pr) {
   return (int64_t)((pr->center ? pr->center->device_bytes() : 0) + pr->kp->device_bytes() +
-                   pr->v2v->device_bytes() + pr->spread_bytes + pr->tone.bytes);
+                   pr->v2v->device_bytes() + pr->spread_bytes + pr->tone.bytes +
+                   (pr->ck.plan ? pr->ck.plan->device_bytes() : 0) + pr->ck.bytes);
 }
 
 int jh_predictor_set_calibration(jh_predictor* pr, const float* cam_dev, const float* intr_dev,

@@ -120,6 +120,9 @@ struct Call {
   // what the launches read the frame pointer(s) through: the per-image table, the one-pointer cell of a forward that
   // is being captured, or nullptr = `frames` itself
   const void* const* cell = nullptr;
+  // centre keyframes in force (jh_predictor_set_center_keyframes): stage 1 ran on the key rows, and stage 2 fills the
+  // rows in between behind its triangulation.  Set by the whole-path forward alone: the staged calls never have it.
+  bool center_keys = false;
   hipStream_t s = nullptr;
 };
 inline Call make_call(const void* frames, const FrameSource& fs, void* stream, const unsigned char* mask = nullptr) {
@@ -278,6 +281,21 @@ struct jh_predictor {
   jh::Joints3dParams jm_params{};
   float *jm_points = nullptr, *jm_error = nullptr;
   int* jm_views = nullptr;
+  // Centre keyframes (jh_predictor_set_center_keyframes; center_keys.h has the key rows).  every: 0 = off; n_rows: the
+  // real rows of the batch.  plan: a second CenterDetect plan for K * C images -- K = center_key_slots(T, every) -- in
+  // THIS predictor's time-batch class (setup), so that a key row gets the bits the full plan gives it.  table [T * C]:
+  // the key rows' image pointers, which the plan's fetch reads per image; det [T][C][3]: the key slots' detections;
+  // centers [T][3] / source [T]: what the fill wrote.  The buffers are ONE allocation (bytes: its pieces) and the plan
+  // is built by the first enabling call, never by jh_predictor_create; another `every` builds another plan.
+  struct CenterKeys {
+    int every = 0, n_rows = 0, K = 0;
+    std::unique_ptr<jh::EffTrackPlan> plan;
+    const void** table = nullptr;
+    float *det = nullptr, *centers = nullptr;
+    int* source = nullptr;
+    size_t bytes = 0;
+  } ck;
+  jh::PlanSetup setup;                       // what jh_predictor_create built its plans with
   // Tone tables (jh_predictor_set_tone), all num_cameras cameras': a launch's image n is camera cam_lo + n % Cloc
   jh::ToneState tone;
   int tone_call(jh::Call* c) const { return tone.apply(c, cfg.cam_lo, Cloc); }
@@ -315,6 +333,8 @@ int call_source(const char* who, int format, const jh_yuv_surface* yuv, const jh
                 const jh_pixel_surface* pixels, int h, int w, bool per_image, FrameSource* out);
 int upload_images(Scratch& mem, const void*** table, const void* const* images_host, int n_images, int want,
                   const FrameSource& fs, hipStream_t s);
+// api_frames.hip: bytes from one image of contiguous frames to the next
+long long image_bytes(const FrameSource& fs, int h, int w);
 // api_predictor.hip: the stages
 int center_heat_impl(jh_predictor* pr, const Call& call);
 int stage_3d_impl(jh_predictor* pr, const Call& call, const float* heat_all_dev, int t0, float* points_dev,

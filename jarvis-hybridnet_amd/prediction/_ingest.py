@@ -174,10 +174,10 @@ class FramePipeline:
                 self.dev[slot].copy_(self.host[slot], non_blocking=True)
                 self.uploaded[slot].record(self.copy_stream)
             cur.wait_event(self.uploaded[slot])
-            outs, ev = self._submit(self.dev[slot], slot)
+            outs, ev = self._submit(self.dev[slot], slot, real)
             self.consumed[slot] = ev
         else:
-            outs, ev = self._submit(self.host[slot], slot)
+            outs, ev = self._submit(self.host[slot], slot, real)
         t2 = time.perf_counter()
         self.stats["fill_wait"] += t1 - t0
         self.stats["submit"] += t2 - t1
@@ -190,10 +190,10 @@ class FramePipeline:
         # it) has completed before a pool thread overwrites the host buffer
         assert len(self.inflight) <= self.slots - 1
 
-    def _submit(self, x, slot):
+    def _submit(self, x, slot, real):
         mask, self.masks = batch_mask(self.masks, self.T), []
         centers, self.centers = batch_centers(self.centers, self.T), []
-        return submit_batch(self.submit, x, slot, mask, centers)
+        return submit_batch(self.submit, x, slot, mask, centers, real)
 
     # ---- rows ----------------------------------------------------------------------------------------
     def drain(self, keep=0):
@@ -245,7 +245,7 @@ class DevicePipeline:
         self.drain(self.keep)
         mask, self.masks = batch_mask(self.masks, self.T), []
         centers, self.centers = batch_centers(self.centers, self.T), []
-        outs, ev = submit_batch(self.submit, x, self.n % self.slots, mask, centers)
+        outs, ev = submit_batch(self.submit, x, self.n % self.slots, mask, centers, real)
         self.n += 1
         self.inflight.append((outs, ev, real))
 
@@ -283,12 +283,15 @@ def batch_centers(rows, time_batch):
     return torch.stack(rows + [rows[-1]] * (time_batch - len(rows)))
 
 
-def submit_batch(submit, x, slot, mask, centers):
+def submit_batch(submit, x, slot, mask, centers, real=None):
     """The pipelines' call of `submit`: (x, slot), (x, slot, mask) or (x, slot, mask, centers) by what the batch
-    carries, so that a submit written before masks or centres existed is called as it always was."""
+    carries, so that a submit written before masks or centres existed is called as it always was.  A submit that has
+    the attribute `takes_rows` set is also given rows=real, how many leading rows of the batch are real frame sets
+    (the others pad a short last group)."""
+    kw = {"rows": real} if getattr(submit, "takes_rows", False) else {}
     if centers is not None:
-        return submit(x, slot, mask, centers)
-    return submit(x, slot) if mask is None else submit(x, slot, mask)
+        return submit(x, slot, mask, centers, **kw)
+    return submit(x, slot, **kw) if mask is None else submit(x, slot, mask, **kw)
 
 
 def host_outputs(ring, slot, outs):

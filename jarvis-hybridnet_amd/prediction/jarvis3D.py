@@ -224,12 +224,16 @@ class JarvisPredictor3D(nn.Module):
                          centers, return_spread, return_triangulated, joint_mask)
 
     def _run(self, frames, calib, mask, return_2d, single=False, centers=None, return_spread=False,
-             return_triangulated=False, joint_mask=None):
+             return_triangulated=False, joint_mask=None, center_every=None):
         """The forward of checked frames (a _native.Frames; single: one frame set, lead (C,)) with a checked mask and
         checked centres (_native.centers for the frames' time batch, or None), on the native predictor of their size:
         nothing of the predictor is touched before this.  joint_mask: the argument as given (_native.joint_mask checks
-        it here, for the frames' time batch)."""
+        it here, for the frames' time batch); center_every likewise (_native.center_every; the batched forms only)."""
         check_native_seam(self)
+        keys = N.center_every(center_every, frames.lead[0])
+        if keys is not None and centers is not None:
+            raise ValueError("centers= and center_every= do not combine: a call either brings its centres or detects "
+                             "them on its key rows")
         tri = N.triangulation_params(return_triangulated)   # (True: the defaults; None: not asked for)
         per_frame = False
         if single:
@@ -245,10 +249,13 @@ class JarvisPredictor3D(nn.Module):
         # (return_spread and joint_mask decide for this call alone: the native predictor sets its flags, on or off,
         # before it runs)
         res = pr._forward(frames, None, mask, centers, *((True,) if return_spread else ()),
-                          **({} if jm is None else {"joint_mask": jm}))
+                          **({} if jm is None else {"joint_mask": jm}),
+                          **({} if keys is None else {"center_keys": keys}))
         used = ()
-        if jm is not None:                                   # (the JointMask comes last, behind the Triangulated3D)
+        if keys is not None:                                 # (the CenterKeyframes comes last of all)
             res, used = tuple(res[:-1]), (res[-1],)
+        if jm is not None:                                   # (the JointMask comes behind the Triangulated3D)
+            res, used = tuple(res[:-1]), (res[-1],) + used
         return self._single(pr, res, mask, return_2d, tri, used) if single else \
             self._batch(pr, res, mask, return_2d, tri, used)
 
@@ -324,7 +331,7 @@ class JarvisPredictor3D(nn.Module):
 
     def forward_batch(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
                       camera_mask=None, return_2d=False, frame_layout=None, centers=None, return_spread=False,
-                      return_triangulated=False, joint_mask=None):
+                      return_triangulated=False, joint_mask=None, center_every=None):
         """Throughput form: imgs (T,C,3,H,W) fp32 RGB or (T,C,H,W,3) uint8 BGR,
         independent time steps -> points (T,J,3), confidences (T,J), valid (T) int32;
         no host synchronisation.  frame_format 'i420' / 'nv12': imgs (T,C,3H/2,W) uint8 YUV 4:2:0 (see
@@ -359,7 +366,20 @@ class JarvisPredictor3D(nn.Module):
         fewer than min_views cameras agree.  Under per-frame-set calibration row t uses row t's calibration.
         joint_mask: as forward(), (T,J,C) for a tensor; row t of the batch depends on row t of the mask alone, and an
         invalid frame set is as in the plain call.  The `JointMask` of the batch (cameras (T,J,C), count (T,J)) comes
-        last.  `Triangulated3D.members` of one call is a valid joint_mask of the next."""
+        last.  `Triangulated3D.members` of one call is a valid joint_mask of the next.
+        center_every = k (an int >= 1), or (k, n_rows): the rows of the batch are CONSECUTIVE frame sets, and CenterDetect
+        runs on the key rows alone -- rows 0, k, 2k, ... and the last one (_native.center_keyframe_rows) --; a row in
+        between takes the centre interpolated linearly, on the device, between its two key rows (one of them invalid:
+        the other one's; both: the row is invalid), and every row then runs as under centers= (include/jarvis_hip.h has
+        the definition).  (k, n_rows): only the first n_rows rows are real (a padded last group); the rows behind them
+        hold the last real row's centre and never serve as keys.  The `CenterKeyframes` of the call (centers (T,3),
+        source (T): 0 detected, 1 interpolated, 2 held, -1 none) comes last of all.  k = 1 gives the detected call bit
+        for bit; any k gives, bit for bit, forward_batch(centers=CenterKeyframes.centers).  The flag decides for this
+        call alone; it composes with everything above except centers= (ValueError).  None: every row detects.  Whether
+        a trained network keeps its accuracy under a given k is the user's to measure."""
+        if centers is not None and center_every is not None:
+            raise ValueError("centers= and center_every= do not combine: a call either brings its centres or detects "
+                             "them on its key rows")
         if centers is not None:
             if not torch.is_tensor(imgs) or imgs.dim() < 1:
                 raise ValueError("imgs must be a tensor of time steps")
@@ -371,11 +391,11 @@ class JarvisPredictor3D(nn.Module):
         frames = N.describe_frames(imgs, (None, self.num_cameras), frame_format, frame_layout)
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d,
                          centers=centers, return_spread=return_spread, return_triangulated=return_triangulated,
-                         joint_mask=joint_mask)
+                         joint_mask=joint_mask, center_every=center_every)
 
     def forward_images(self, images, cameraMatrices, intrinsicMatrices, distortionCoefficients, frame_format=None,
                        frame_layout=None, camera_mask=None, return_2d=False, centers=None,
-                       return_spread=False, return_triangulated=False, joint_mask=None):
+                       return_spread=False, return_triangulated=False, joint_mask=None, center_every=None):
         """forward_batch on images that lie where their producers left them: `images` a sequence of C tensors (one
         frame set) or a sequence of T such sequences, each tensor ONE image -- fp32 (3,H,W); uint8 (H,W,3);
         frame_format 'i420' / 'nv12': uint8 (3H/2,W); frame_layout (a YuvSurface or a SensorSurface): 1-D uint8 of at
@@ -390,13 +410,16 @@ class JarvisPredictor3D(nn.Module):
         batch are different subjects seen in the same frames (a detected batch finds the strongest one in every row).
         return_spread, return_triangulated: as forward_batch -- the Spread3D of the batch (covariance in mm^2, peak voxel
         in mm and mass of every joint's heat map), then its Triangulated3D come last.  joint_mask: as forward_batch;
-        its JointMask comes last of all."""
+        its JointMask comes last.  center_every: as forward_batch; its CenterKeyframes comes last of all."""
+        if centers is not None and center_every is not None:
+            raise ValueError("centers= and center_every= do not combine: a call either brings its centres or detects "
+                             "them on its key rows")
         frames = image_frames(self.num_cameras, images, frame_format, frame_layout)
         T = frames.lead[0]
         camera_mask = N.camera_mask(camera_mask, (T, self.num_cameras))
         return self._run(frames, (cameraMatrices, intrinsicMatrices, distortionCoefficients), camera_mask, return_2d,
                          centers=N.centers(centers, T), return_spread=return_spread,
-                         return_triangulated=return_triangulated, joint_mask=joint_mask)
+                         return_triangulated=return_triangulated, joint_mask=joint_mask, center_every=center_every)
 
     def detect_subjects(self, imgs, cameraMatrices, intrinsicMatrices, distortionCoefficients, max_subjects,
                         frame_format=None, frame_layout=None, camera_mask=None, images=False, return_peaks=False,

@@ -185,7 +185,8 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                      distortionCoefficients, cfg, output_dir, params=None, time_batch=1, streams=1,
                      frame_spec=None, frame_format="bgr", camera_mask=None, output_2d=False, camera_names=None,
                      frame_layout=None, centers=None, output_spread=False, output_triangulated=False,
-                     max_subjects=None, subject_params=None, track=None, joint_mask=None, tone=None):
+                     max_subjects=None, subject_params=None, track=None, joint_mask=None, tone=None,
+                     center_every=None):
     """Run `predictor` over an iterable of multi-view frame sets -- (C,H,W,3) uint8 BGR
     arrays / tensors exactly as cv2 delivers them, or (C,3,H,W) fp32 RGB -- and write
     data3D.csv (+ info.yaml when `params` is given).  Returns the number of frames.
@@ -308,7 +309,17 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
     tone: a ToneTables of NUM_CAMERAS cameras (black level, gain, white balance and gamma per camera and channel as one
     byte-to-value table, applied inside the resize / crop fetch): the run is made under predictor.set_tone(tone), and
     its files are byte-identical to those of a run on the fp32 frames tables[c][ch][bytes].  Byte frames only (fp32
-    frame sets raise RuntimeError).  The predictor keeps the setting afterwards; None leaves it as it is."""
+    frame sets raise RuntimeError).  The predictor keeps the setting afterwards; None leaves it as it is.
+
+    center_every = k (an int >= 1): CenterDetect runs on every k-th frame set of a group of time_batch consecutive frame
+    sets and on its last one; the frame sets in between take a centre interpolated linearly between their two key frame
+    sets, and every frame set then runs as under centers= (JarvisPredictor3D.forward_batch(..., center_every=)).  A
+    short last group passes its real row count, so its padding rows never serve as keys for real rows.  With k > 1 THE
+    RESULT DEPENDS ON time_batch: the key rows are rows of the group, so another time_batch detects on other frame sets
+    and interpolates over other spans (and time_batch = 1 makes every frame set a key).  It does not depend on
+    `streams`.  k = 1 gives the rows of the run without the option, byte for byte.  The files and their formats do not
+    change.  Together with centers or max_subjects: ValueError.  Whether a trained network keeps its accuracy under a
+    given k at a rig's frame rate is the user's to measure."""
     import contextlib
     from ..joint_mask import create_header_joint_cameras, joint_cameras_row
     from ._ingest import check_driver_frames, driver_format, host_outputs, pipeline_for
@@ -323,9 +334,17 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             raise ValueError("predict3D_frames takes joint_mask='consensus' or the consensus' parameters, not a mask")
         jm_params = N.joint_mask(joint_mask, 1, 1, 1)[1]
     jm_tail = 2 if jm_params is not None else 0                 # (... then cameras and count of the JointMask, last)
+    time_batch, streams = max(1, int(time_batch)), max(1, int(streams))
+    if center_every is not None:
+        if isinstance(center_every, (tuple, list)):
+            raise ValueError("predict3D_frames takes center_every as one int: the driver knows the rows of its groups")
+        center_every = N.center_every(center_every, time_batch)[0]
+        if centers is not None:
+            raise ValueError("center_every does not combine with centers")
     subj_params, tracker = None, None
     if max_subjects is not None:
         clash = [name for name, on in (("centers", centers is not None), ("output_2d", output_2d),
+                                       ("center_every", center_every is not None),
                                        ("output_spread", output_spread), ("output_triangulated", tri_params is not None),
                                        ("joint_mask", jm_params is not None))
                  if on]
@@ -356,7 +375,6 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
         create_info_file(params)
     J = cfg.KEYPOINTDETECT.NUM_JOINTS
     calib = (cameraMatrices, intrinsicMatrices, distortionCoefficients)
-    time_batch, streams = max(1, int(time_batch)), max(1, int(streams))
     n = 0
     if output_2d:
         num_cams = cfg.HYBRIDNET.NUM_CAMERAS
@@ -434,13 +452,17 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
 
         def written(outs):
             """The tensors of a batch that a file gets: the five of a Triangulated3D cut to points, views, error."""
+            if center_every is not None:                         # (the CenterKeyframes' two tensors: no file holds them)
+                outs = outs[:-2]
             if tri_params is None:
                 return outs
             end = len(outs) - jm_tail
             return tuple(outs[:end - 5]) + (outs[end - 5], outs[end - 4], outs[end - 2]) + tuple(outs[end:])
 
-        def submit(x, slot, mask=None, centers=None):
+        def submit(x, slot, mask=None, centers=None, rows=None):
             kw = {} if mask is None else {"camera_mask": mask}
+            if center_every is not None:
+                kw["center_every"] = (center_every, time_batch if rows is None else rows)
             if centers is not None:
                 kw["centers"] = centers
             if output_2d:
@@ -466,6 +488,8 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
             res = predictor.forward_batch(x, *calib, frame_format=frame_format, **kw) if yuv else \
                 predictor.forward_batch(x, *calib, **kw)
             tri = ()
+            if center_every is not None:
+                res = tuple(res[:-1])                          # (the CenterKeyframes: no file holds it)
             if jm_params is not None:
                 res, tri = tuple(res[:-1]), tuple(res[-1])     # (the JointMask's two tensors go last)
             if tri_params is not None:
@@ -522,6 +546,7 @@ def predict3D_frames(predictor, frame_sets, cameraMatrices, intrinsicMatrices,
                 ev.record()
             return res, ev
 
+        submit.takes_rows = True                               # (the pipelines say how many rows of a batch are real)
         if max_subjects is not None:
             submit, emit = submit_subjects, emit_subjects
 
