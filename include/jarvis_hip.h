@@ -1136,6 +1136,36 @@ int jh_conv_form(int nd, int kind, int k, int stride, int pad, int cin, int cout
  * pooled output).  Fails for a node no form takes. */
 int jh_node_form(int c, int cout, int n, int h, int w, int n_in, const int* modes, int act, int batch_class,
                  int want_pool, char* name, int name_cap, int32_t out[8]);
+/* ---- the keypoint head's box.  A whole-path forward whose voxel gather is the only reader of the heat
+ * maps computes, per image, only the tiles of the head that cover the box of pixels the gather can read; JH_HEAD_ROI=0,
+ * read when a predictor is created, switches that off.
+ * jh_head_roi_form (no GPU needed; csrc/conv_layer.h): does the head of a 3D predictor -- ConvTranspose2d k4 s2 p1,
+ * cin -> cout, at precision 0 / 1 / 2 -- take a box in a call of kind 0 whole-path forward / 1 staged stage 2 /
+ * 2 jh_predictor_hybridnet_forward / 3 whole-path forward on a stream the caller is capturing, with the joint-mask
+ * consensus in force, on a camera-sharded predictor, in a plan built with want_res1?  Reads JH_HEAD_ROI and
+ * JH_DECONV4_WINDOW as they stand at the call.
+ * jh_predictor_views2d / jh_predictor_triangulate_joints on the predictor's own heat maps behind a boxed forward run the
+ * head once more without a box first (the full maps, the same bits); a caller that wants both on every call and
+ * nothing extra sets JH_HEAD_ROI=0. */
+int jh_head_roi_form(int call_kind, int consensus, int sharded, int want_res1, int cin, int cout, int precision,
+                     int32_t* takes_box);
+/* TEST-ONLY: jh_op_conv's ConvTranspose2d k4 s2 p1 (no bias) with one box per image, box_host (n, 4) = (x0, y0, x1, y1)
+ * inclusive in output pixels, or NULL = no box.  The output starts as NaN: what no workgroup stores stays NaN.  Fails
+ * for a layer that is not of the window form. */
+int jh_op_deconv4_box(int cin, int cout, const float* w_host, const float* x_dev, int n, int h, int w,
+                      const int32_t* box_host, float* y_dev, void* stream);
+/* TEST-ONLY: the boxes of t x cams images as stage 2 takes them -- coarse projection of the grid_size^3 grid, then
+ * min / max per camera -> box_dev (t, cams, 4) stored-pixel boxes (x0, y0, x1, y1) of heat maps of side
+ * hs - 2 + 2 heat_pad -- and, with idx_dev (t, cams, grid_size^3), the voxel gather's own indices iv * hs + iu from
+ * that same field.  center3d_dev (t, 3), center_hm_dev (t, cams, 2); valid_dev (t) / mask_dev (t, cams) may be NULL;
+ * calib_per_frame: the calibration arrays hold t * cams rows. */
+int jh_op_repro_box(const float* cam_dev, const float* intr_dev, const float* dist_dev, int calib_per_frame,
+                    const int32_t* center3d_dev, const int32_t* center_hm_dev, const int32_t* valid_dev,
+                    const uint8_t* mask_dev, int t, int cams, int joints, int hs, int heat_pad, int grid_size,
+                    float grid_spacing, int32_t* box_dev, int32_t* idx_dev, void* stream);
+/* TEST-ONLY: the boxes (time_batch, cam_n, 4) the last boxed stage 2 of the predictor wrote (box_dev may be NULL) and
+ * whether the predictor's own heat maps are, right now, complete only inside them. */
+int jh_predictor_debug_head_boxes(jh_predictor* pr, int32_t* box_dev, int32_t* boxed, void* stream);
 /* TEST-ONLY: the operand transform a consumer applies while it stages its input (csrc/jh_common.h: InNorm, SeGate),
  * described from the host so that only the consumer is under test. */
 typedef struct jh_op_operand {

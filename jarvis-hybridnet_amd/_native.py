@@ -298,6 +298,11 @@ _SIGS = {
     "jh_conv_form": (c_int, [c_int] * 12 + [c_char_p, c_int]),
     "jh_node_form": (c_int, [c_int] * 6 + [ctypes.POINTER(c_int)] + [c_int] * 3 +
                      [c_char_p, c_int, ctypes.POINTER(ctypes.c_int32)]),
+    "jh_head_roi_form": (c_int, [c_int] * 7 + [ctypes.POINTER(ctypes.c_int32)]),
+    "jh_op_deconv4_box": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "jh_op_repro_box": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p] +
+                        [c_int] * 6 + [c_float, c_void_p, c_void_p, c_void_p]),
+    "jh_predictor_debug_head_boxes": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int32), c_void_p]),
     "jh_op_conv_operand": (c_int, [c_int] * 7 + [c_void_p, c_void_p, c_void_p] + [c_int] * 4 +
                            [c_void_p, ctypes.POINTER(OpOperand), c_void_p, c_void_p]),
     "jh_op_se_gate": (c_int, [c_void_p, c_int, c_int, c_int, c_float] + [c_void_p] * 6),

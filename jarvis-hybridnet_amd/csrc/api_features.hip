@@ -35,10 +35,13 @@ static int triangulate_joints_workspace(jh_predictor* pr, hipStream_t s, bool ow
 }
 
 // No heat maps given: the predictor's own from frame t0 on, which hold all cameras only when all cameras are local.
-static int own_heat_maps(jh_predictor* pr, int t0, const float** heat_all_dev) {
+// (After a forward whose head ran with its box they are completed first -- jh_predictor::full_heat, on the reader's stream,
+// which is the forward's by this entry's contract.)
+static int own_heat_maps(jh_predictor* pr, int t0, const float** heat_all_dev, hipStream_t s) {
   if (*heat_all_dev) return 0;
   JH_REQUIRE(pr->Cloc == pr->C && pr->cfg.cam_lo == 0, "the predictor's own heat maps hold all cameras only when "
              "all cameras are local");
+  if (pr->full_heat(s)) return 1;
   *heat_all_dev = pr->kp->heat.p + (size_t)t0 * pr->C * pr->Hh * pr->Hh * pr->Jp;
   return 0;
 }
@@ -247,7 +250,7 @@ int jh_predictor_views2d(jh_predictor* pr, const float* heat_all_dev, int t0, co
              "null pointer");
   JH_REQUIRE(t0 >= 0 && t0 + pr->T3 <= pr->T, "frame range of the 2D views");
   const int N = pr->T3 * pr->C;
-  if (own_heat_maps(pr, t0, &heat_all_dev)) return 1;
+  if (own_heat_maps(pr, t0, &heat_all_dev, s)) return 1;
   if (scan_workspace(pr, s, "the first jh_predictor_views2d call of a predictor allocates its workspace: make it "
                      "outside a stream capture")) return 1;
   if (launch_scan(pr, heat_all_dev, s)) return 1;
@@ -311,7 +314,7 @@ int jh_predictor_triangulate_joints(jh_predictor* pr, const float* heat_all_dev,
   if (joints3d_params(params, &jp)) return 1;
   JH_REQUIRE(points_dev && views_dev && members_dev && error_dev, "jh_predictor_triangulate_joints: null output pointer");
   JH_REQUIRE(t0 >= 0 && t0 + pr->T3 <= pr->T, "frame range of the joint triangulation");
-  if (own_heat_maps(pr, t0, &heat_all_dev)) return 1;
+  if (own_heat_maps(pr, t0, &heat_all_dev, s)) return 1;
   // (the observations go straight into the caller's buffer when there is one; the predictor's own, allocated by the
   // first call that brings none, otherwise)
   if (triangulate_joints_workspace(pr, s, !obs_dev, "the first jh_predictor_triangulate_joints call of a predictor "

@@ -2,6 +2,7 @@
 // convolution, gate, norm_apply, depthwise, all-joint argmax or BiFPN node run on its own from host-side operands.
 #include "predictor.h"
 #include "bifpn_node.h"
+#include "reproject.h"
 #include "views2d.h"
 
 using namespace jh;
@@ -52,7 +53,8 @@ static int op_upload_se(Scratch& sc, const double* pool_host, int n, int C, int 
 // statistics, gate tensor or recipe -- raw output).
 static int op_conv_body(int nd, int kind, int k, int stride, int pad, int cin, int cout, const float* w_host,
                         const float* b_host, const float* x_dev, int n, int d, int h, int w, const float* gate_dev,
-                        int norm_act, const jh_op_operand* opd, float* y_dev, hipStream_t s, const char* who) {
+                        int norm_act, const jh_op_operand* opd, float* y_dev, hipStream_t s, const char* who,
+                        const int32_t* box_host = nullptr) {   // box_host: (n, 4) boxes of ConvArgs::box (jh_op_deconv4_box)
   const bool recipe = opd && opd->se_pool_host;
   const bool want_stats = opd ? opd->want_stats != 0 : norm_act >= 0;
   const bool plain_out = !want_stats && !gate_dev && !recipe;
@@ -106,7 +108,17 @@ static int op_conv_body(int nd, int kind, int k, int stride, int pad, int cin, i
                      opd->se_br_host, opd->se_we_host, opd->se_be_host, &se)) return 1;
   }
   if (launch_to_channel_last(x_dev, x, s)) return 1;
-  if (layer.launch(x, y, gate_p, stats, in, recipe ? &se : nullptr, s)) return 1;
+  int4* box = nullptr;
+  if (box_host) {
+    JH_REQUIRE(layer.takes_box(), std::string(who) + ": the layer is not of the window form, which alone takes a box");
+    for (int i = 0; i < n; ++i) {
+      const int32_t* b = box_host + 4 * i;
+      JH_REQUIRE(b[0] >= 0 && b[1] >= 0 && b[0] <= b[2] && b[1] <= b[3] && b[2] < Wo && b[3] < Ho,
+                 std::string(who) + ": a box (x0, y0, x1, y1) inside the output, not empty");
+    }
+    if (op_upload(sc, reinterpret_cast<const int4*>(box_host), (size_t)n, &box)) return 1;
+  }
+  if (layer.launch(x, y, gate_p, stats, in, recipe ? &se : nullptr, s, box)) return 1;
   if (!opd && norm_act >= 0 && launch_norm_apply(y, stats, norm_act, nullptr, nullptr, y.p, nullptr, s)) return 1;
   if (launch_from_channel_last(y, y_dev, s)) return 1;
   std::vector<double> hst(read_stats ? (size_t)n * y.Cp * kStatW : 0);
@@ -286,6 +298,63 @@ int jh_op_conv_operand(int nd, int kind, int k, int stride, int pad, int cin, in
   JH_REQUIRE(!(gate_dev && operand->se_pool_host), "either a gate tensor or a gate recipe");
   return op_conv_body(nd, kind, k, stride, pad, cin, cout, w_host, b_host, x_dev, n, d, h, w, gate_dev, -1, operand,
                       y_dev, static_cast<hipStream_t>(stream), "jh_op_conv_operand");
+}
+
+// ---- the head's box
+int jh_op_deconv4_box(int cin, int cout, const float* w_host, const float* x_dev, int n, int h, int w,
+                      const int32_t* box_host, float* y_dev, void* stream) {
+  JH_REQUIRE(cin >= 1 && cout >= 1 && w_host && x_dev && y_dev && n >= 1 && h >= 1 && w >= 1, "jh_op_deconv4_box: bad "
+             "argument");
+  return op_conv_body(2, 1, 4, 2, 1, cin, cout, w_host, nullptr, x_dev, n, 1, h, w, nullptr, -1, nullptr, y_dev,
+                      static_cast<hipStream_t>(stream), "jh_op_deconv4_box", box_host);
+}
+
+int jh_op_repro_box(const float* cam_dev, const float* intr_dev, const float* dist_dev, int calib_per_frame,
+                    const int32_t* center3d_dev, const int32_t* center_hm_dev, const int32_t* valid_dev,
+                    const uint8_t* mask_dev, int t, int cams, int joints, int hs, int heat_pad, int grid_size,
+                    float grid_spacing, int32_t* box_dev, int32_t* idx_dev, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JH_REQUIRE(cam_dev && intr_dev && dist_dev && center3d_dev && center_hm_dev && box_dev, "jh_op_repro_box: null pointer");
+  JH_REQUIRE(t >= 1 && cams >= 1 && cams <= 64 && joints >= 1 && joints <= 64 && hs >= 3 && (heat_pad == 0 || heat_pad == 1) &&
+             grid_size >= 4 && grid_size % 4 == 0, "jh_op_repro_box: shape");
+  const Calib cal{cam_dev, intr_dev, dist_dev, calib_per_frame ? cams : 0};
+  const int Gh = grid_size / 2, Hh = hs - 2 + 2 * heat_pad;
+  Scratch sc;
+  float2* coarse = nullptr;
+  if (sc.get(reinterpret_cast<void**>(&coarse), (size_t)t * cams * Gh * Gh * Gh * sizeof(float2))) return 1;
+  if (launch_repro_coarse(cal, center3d_dev, center_hm_dev, coarse, t, cams, grid_size, grid_spacing, hs, s)) return 1;
+  if (launch_repro_box(coarse, valid_dev, mask_dev, reinterpret_cast<int4*>(box_dev), t, cams, 0, cams, grid_size, hs,
+                       heat_pad, s)) return 1;
+  if (idx_dev) {   // the gather itself on the field above (coarse_ready), all-zero heat maps: what it reads, not what it sums
+    Act heat, vol;
+    if (sc.act(t * cams, 1, Hh, Hh, joints, &heat) || sc.act(t, grid_size, grid_size, grid_size, joints, &vol)) return 1;
+    JH_CHECK_HIP(hipMemsetAsync(heat.p, 0, heat.bytes(), s));
+    if (launch_reproject(cal, center3d_dev, center_hm_dev, heat.p, coarse, vol.p, idx_dev, t, cams, grid_size,
+                         grid_spacing, hs, heat.Cp, heat_pad, /*div255=*/0, mask_dev, s, nullptr, /*coarse_ready=*/true))
+      return 1;
+  }
+  JH_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int jh_head_roi_form(int call_kind, int consensus, int sharded, int want_res1, int cin, int cout, int precision,
+                     int32_t* takes_box) {
+  JH_REQUIRE(call_kind >= 0 && call_kind <= 3 && cin >= 1 && cout >= 1 && precision >= 0 && precision <= 2 && takes_box,
+             "jh_head_roi_form: bad argument");
+  // the head as EffTrackPlan::build makes it: ConvTranspose2d k4 s2 p1, no bias, no statistics, no gate
+  ConvUse use;
+  use.desc = deconv2d_k4s2p1_desc(cin, cout);
+  use.transposed = true;
+  use.precision = precision;
+  *takes_box = conv_takes_box(choose_conv(use)) && head_roi_knob() &&
+               head_box_allowed(static_cast<HeatCall>(call_kind), consensus != 0, sharded != 0, want_res1 != 0) ? 1 : 0;
+  return 0;
+}
+
+int jh_predictor_debug_head_boxes(jh_predictor* pr, int32_t* box_dev, int32_t* boxed, void* stream) {
+  JH_REQUIRE(pr && boxed, "jh_predictor_debug_head_boxes: null pointer");
+  *boxed = pr->heat_boxed ? 1 : 0;
+  return copy_if(box_dev, pr->head_box, (size_t)pr->T * pr->Cloc * sizeof(int4), static_cast<hipStream_t>(stream));
 }
 
 // The squeeze-excite gate kernel on its own: host pooled sums (n, c) and weights -> gate_dev (n, c).

@@ -67,13 +67,13 @@ int jh_predictor::run_3d(const Call& call, const float* heat_all, int t0, float*
             launch_reproject_joint_masked(calib_at(t0), cur().c3i + t0 * 3, cur().chm + t0 * C * 2, heat_all, coarse,
                                           v2v->input.p, nullptr, T3, C, G, cfg.grid_spacing, hs, J, Jp, /*heat_pad=*/0,
                                           /*div255=*/1, call.mask ? call.mask + (size_t)t0 * C : nullptr,
-                                          call.joint_mask + (size_t)t0 * J * C, js, s, layout));
+                                          call.joint_mask + (size_t)t0 * J * C, js, s, layout, call.head_roi));
   } else {
     JH_PROF(call.mask ? "reproject_gather_masked" : "reproject_gather", 0.0,
             4.0 * T3 * ((double)C * Hh * Hh * J + g3 * J),
             launch_reproject(calib_at(t0), cur().c3i + t0 * 3, cur().chm + t0 * C * 2, heat_all, coarse, v2v->input.p,
                              nullptr, T3, C, G, cfg.grid_spacing, hs, Jp, /*heat_pad=*/0, /*div255=*/1,
-                             call.mask ? call.mask + (size_t)t0 * C : nullptr, s, layout));
+                             call.mask ? call.mask + (size_t)t0 * C : nullptr, s, layout, call.head_roi));
   }
   if (v2v->run(s)) return 1;
   SoftargmaxSpread sp = spread;
@@ -200,6 +200,21 @@ static int stage_keypoints_impl(jh_predictor* pr, const Call& call_in, const flo
   if (det_all_dev != pr->det_all)
     JH_CHECK_HIP(hipMemcpyAsync(pr->det_all, det_all_dev, (size_t)pr->T * pr->C * 3 * sizeof(float),
                                 hipMemcpyDeviceToDevice, s));
+  // The head's box.  The coarse (u, v) field of the voxel gather depends on the calibration and the
+  // centres alone, both known here: it is projected now instead of in stage 3 (run_3d takes it as it is), and the box
+  // of every image -- the heat-map pixels the gather can read -- is taken from it for the keypoint head.
+  JH_REQUIRE(!call.head_roi || (pr->kp->head_takes_box && pr->T3 == pr->T && pr->Cloc == pr->C && c.cam_lo == 0),
+             "a call whose head takes a box: all frames and cameras in one 3D chunk");
+  if (call.head_roi) {
+    JH_PROF("reproject_coarse", 0.0, 8.0 * pr->T * pr->C * pr->Gh * pr->Gh * pr->Gh,
+            launch_repro_coarse(pr->calib_at(0), cs.c3i, cs.chm, pr->coarse, pr->T, pr->C, pr->G, c.grid_spacing,
+                                pr->hs, s));
+    JH_PROF("reproject_box", 0.0, 8.0 * pr->T * pr->C * pr->Gh * pr->Gh * pr->Gh,
+            launch_repro_box(pr->coarse, cs.valid, call.mask, pr->head_box, pr->T, pr->C, c.cam_lo, pr->Cloc, pr->G,
+                             pr->hs, /*heat_pad=*/0, s));
+  }
+  pr->kp->head_box = call.head_roi ? pr->head_box : nullptr;
+  pr->heat_boxed = call.head_roi;
   if (pr->kp->stem_fusable) {
     // crop + normalise happen inside the stem convolution's patch staging (csrc/stem.hip)
     StemSource& src = pr->kp->stem_src;
@@ -297,6 +312,10 @@ static int forward_graph(jh_predictor* pr, const Call& call, float* points_dev, 
   hipLaunchKernelGGL(copy_out_kernel, dim3((n_pts + 255) / 256), dim3(256), 0, s, pr->g_points, pr->g_conf,
                      pr->cset[0].valid, points_dev, conf_dev, valid_dev, n_pts, pr->T * pr->J, pr->T);
   JH_CHECK_HIP(hipGetLastError());
+  // (what stage 2 notes when it is called; a replay calls nothing.  Every call of a slot has the same head_roi: it
+  //  depends on the plan and on modes that never come here.)
+  pr->kp->head_box = call.head_roi ? pr->head_box : nullptr;
+  pr->heat_boxed = call.head_roi;
   return 0;
 }
 
@@ -321,15 +340,21 @@ static int forward_impl(jh_predictor* pr, const void* frames_dev, const FrameSou
   // graphs stay as they are and replay again once the mode is off
   // ... and so do centre keyframes (jh_predictor_set_center_keyframes)
   call.center_keys = pr->ck.every != 0;
+  // is the CALLER capturing this stream?  Its graph then holds the plain launches, which every replay runs again
+  // without this function: such a forward never boxes the head (HeatCall::Captured)
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(call.s, &cs);
+  // the head's box: only where stage 3 of this call is the one reader of the heat maps (conv_layer.h has the rule)
+  call.head_roi = pr->kp->head_takes_box &&
+                  head_box_allowed(cs != hipStreamCaptureStatusNone ? HeatCall::Captured : HeatCall::Forward,
+                                   pr->jm_mode == JH_JOINT_MASK_CONSENSUS, pr->Cloc != pr->C, /*want_res1=*/false);
   if (pr->jm_mode != JH_JOINT_MASK_OFF) {
     call.joint_mask = pr->jm_buf;
     return forward_eager(pr, call, points_dev, conf_dev, valid_dev);
   }
   if (call.center_keys) return forward_eager(pr, call, points_dev, conf_dev, valid_dev);
   // per-launch profiling needs the launches one by one; a caller that is itself capturing this
-  // stream gets the plain launches too (its graph then holds them)
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (pr->use_graph && !profiler().on) (void)hipStreamIsCapturing(call.s, &cs);
+  // stream gets the plain launches too
   if (!pr->use_graph || profiler().on || cs != hipStreamCaptureStatusNone)
     return forward_eager(pr, call, points_dev, conf_dev, valid_dev);
   return forward_graph(pr, call, points_dev, conf_dev, valid_dev);
@@ -385,6 +410,7 @@ int jh_predictor_create(const jh_params* center_params, const jh_params* hybrid_
   }
   if (m.get(reinterpret_cast<void**>(&pr->coarse),
             (size_t)pr->T3 * C * pr->Gh * pr->Gh * pr->Gh * sizeof(float2))) return 1;
+  if (m.get(reinterpret_cast<void**>(&pr->head_box), (size_t)T * pr->Cloc * sizeof(int4))) return 1;
   {   // soft-argmax accumulators and maxima in ONE allocation (zeroed by one launch per forward)
     const size_t pb = (size_t)T * pr->Jp * 4 * kLimbs * sizeof(double), mb = (size_t)T * pr->Jp * sizeof(int);
     if (m.get(reinterpret_cast<void**>(&pr->sa_partial), pb + mb)) return 1;
@@ -623,6 +649,8 @@ int jh_predictor_hybridnet_forward(jh_predictor* pr, const float* crops_dev,
   JH_CHECK_HIP(hipMemcpyAsync(pr->cur().c3i, center3d_dev, (size_t)pr->T * 3 * sizeof(int), hipMemcpyDeviceToDevice, s));
   if (launch_to_channel_last(crops_dev, pr->kp->input, s)) return 1;
   pr->kp->stem_src.mode = 0;                      // (the crops are given: the stem reads the plan's input)
+  pr->kp->head_box = nullptr;                     // (HeatCall::Hybridnet: the heat maps may go to the caller)
+  pr->heat_boxed = false;
   if (pr->kp->run(s)) return 1;
   if (heatmaps_padded_dev) {
     const Act& h = pr->kp->heat;

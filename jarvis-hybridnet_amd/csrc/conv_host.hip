@@ -168,7 +168,8 @@ static int pick_nr(int nb, int taps, bool heavy_staging, long units) {
 }
 
 int launch_conv(const ConvDesc& d, const ConvWeights& w, const Act& x, const Act& y,
-                const float* gate, double* stats, hipStream_t s, const InNorm* in, const SeGate* se) {
+                const float* gate, double* stats, hipStream_t s, const InNorm* in, const SeGate* se,
+                const int4* box) {
   JH_REQUIRE(x.Cp == w.cin_p || (x.Cp == 4 && w.cin_p == 8), "conv input channel padding mismatch");
   JH_REQUIRE(y.Cp == cpad(d.cout), "conv output channel padding mismatch");
   JH_REQUIRE(x.N == y.N, "batch mismatch");
@@ -205,7 +206,9 @@ int launch_conv(const ConvDesc& d, const ConvWeights& w, const Act& x, const Act
   const size_t budget = kConvLdsBudget;
   // the two layouts that one kernel alone reads (csrc/deconv4.hip; each checks the launch against its form)
   switch (w.layout) {
-    case WeightLayout::Window: return launch_deconv4_window(a, s);
+    case WeightLayout::Window:
+      a.box = box;                              // (the one form that reads it: conv_takes_box, csrc/conv_layer.hip)
+      return launch_deconv4_window(a, s);
     case WeightLayout::ChannelPaired: return launch_deconv4_fused(a, s);     // all four parities from one staged patch
     case WeightLayout::TapPaired: case WeightLayout::Plain: break;
   }

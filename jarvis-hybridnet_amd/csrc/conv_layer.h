@@ -43,6 +43,27 @@ ConvChoice choose_conv(const ConvUse& u);
 // "mfma" + "" / "_paired" / "_tappair" / "_window", "wino", "wino_bf16x3", "conv_bf16x3", "deconv4_bf16x3", "deconv_c1"
 std::string conv_choice_name(const ConvChoice& c);
 
+// THE HEAD'S BOX.  A layer whose output has one reader that reads part of it may be given that part as a
+// per-image box (ConvArgs::box).  The two rules are here and nowhere else:
+//  * which layers can use a box: the window form of ConvTranspose2d k4 s2 p1 -- the four-parity kernel and the general
+//    path keep computing everything;
+//  * which calls of a 3D predictor may give its keypoint head one: those in which the voxel gather of the same call is
+//    the ONLY reader of the heat maps (head_box_allowed: anything else that reads them keeps the full map).
+// JH_HEAD_ROI=0, read when the plan is built (EffTrackPlan::build), gives no layer a box: the previous dispatch.
+bool conv_takes_box(const ConvChoice& c);
+bool head_roi_knob();        // JH_HEAD_ROI as it stands now (unset: on)
+// The call forms of a 3D predictor.  Forward: the whole-path forward, launched by the predictor itself (plain
+// launches or its own graph; camera mask, given joint mask, caller-supplied centres and centre keyframes included).
+// Staged: jh_predictor_stage_keypoints*, whose heat maps are the caller's (heat_dev, the exchange of the
+// camera-sharded path).  Hybridnet: jh_predictor_hybridnet_forward, which can export them.  Captured: a whole-path
+// forward on a stream the CALLER is capturing -- its launches run again at every replay, without the predictor's
+// host code, which then cannot know that its own heat maps are complete only inside the boxes (jh_predictor::
+// heat_boxed): no box.
+enum class HeatCall { Forward = 0, Staged = 1, Hybridnet = 2, Captured = 3 };
+// Only the plain Forward, and not with the joint-mask consensus in force (it scans whole heat maps), on a
+// camera-sharded predictor (the heat maps leave the rank) or in a plan built with want_res1.
+bool head_box_allowed(HeatCall kind, bool consensus, bool sharded, bool want_res1);
+
 // [channels][taps] -> [taps][Cp], pad channels zero: the weight order of the vector-ALU kernels (depthwise, deconv_c1)
 std::vector<float> taps_major(const float* w, int channels, int taps, int Cp);
 
@@ -60,8 +81,10 @@ struct ConvLayer {
   size_t table_bytes = 0;
 
   // gate / se: only the Mfma form takes one.  stats: nullptr or the layer's fused statistics.
+  // box: ConvArgs::box, only for a layer that takes_box()
   int launch(const Act& x, const Act& y, const float* gate, double* stats, const InNorm& in, const SeGate* se,
-             hipStream_t s) const;
+             hipStream_t s, const int4* box = nullptr) const;
+  bool takes_box() const { return conv_takes_box(choice); }
   std::string profile_name(int out_w) const;
   // weights and tile table (the bias vector, cout_p16 floats, is not counted)
   size_t device_bytes() const { return w.phase_stride * desc.nphase * sizeof(float) + table_bytes; }

@@ -59,6 +59,14 @@ ConvChoice choose_conv(const ConvUse& u) {
   return ConvChoice{ConvForm::Mfma, conv_weight_layout(u), 0};
 }
 
+bool conv_takes_box(const ConvChoice& c) { return c.form == ConvForm::Mfma && c.layout == WeightLayout::Window; }
+
+bool head_roi_knob() { return knob_now("JH_HEAD_ROI", 1) != 0; }
+
+bool head_box_allowed(HeatCall kind, bool consensus, bool sharded, bool want_res1) {
+  return kind == HeatCall::Forward && !consensus && !sharded && !want_res1;
+}
+
 std::string conv_choice_name(const ConvChoice& c) {
   static const char* const forms[] = {"mfma", "wino", "wino_bf16x3", "conv_bf16x3", "deconv4_bf16x3", "deconv_c1"};
   static const char* const layouts[] = {"", "_paired", "_tappair", "_window"};
@@ -107,15 +115,16 @@ int make_conv_layer(const ConvUse& u, const float* w_host, const float* b_host, 
 }
 
 int ConvLayer::launch(const Act& x, const Act& y, const float* gate, double* stats, const InNorm& in, const SeGate* se,
-                      hipStream_t s) const {
+                      hipStream_t s, const int4* box) const {
   JH_REQUIRE(choice.form == ConvForm::Mfma || (!gate && !(se && se->pool)), "only the MFMA form takes a gate");
+  JH_REQUIRE(!box || takes_box(), "only the window form takes a box");
   switch (choice.form) {
     case ConvForm::DeconvC1: return launch_deconv_c1(x, in.stats, in.inv, in.act, w.w, y, s);
     case ConvForm::ConvBf16x3: return launch_conv_bf16x3(desc, w, x, y, stats, s, &in);
     case ConvForm::Deconv4Bf16x3: return launch_deconv4_bf16x3(w, x, y, s, &in);
     case ConvForm::WinoBf16x3: return launch_conv3d_bf16x3(w, x, y, stats, s, &in);
     case ConvForm::Wino: return launch_conv3d_wino(w, x, y, stats, s, &in, choice.wino_variant, wino_tiles);
-    case ConvForm::Mfma: return launch_conv(desc, w, x, y, gate, stats, s, &in, se);
+    case ConvForm::Mfma: return launch_conv(desc, w, x, y, gate, stats, s, &in, se, box);
   }
   JH_REQUIRE(false, "conv form");
 }

@@ -333,9 +333,11 @@ constexpr int kWELINE = 130, kWEZERO = kWELINE, kWENPIX = kWELINE + 1;      // e
 constexpr int kWLDSPIX = kWNPIX > kWENPIX ? kWNPIX : kWENPIX;
 }  // namespace
 
-// NB: column blocks of 16 over the 4 cout_p columns (even); EDGE: the 1-D list of edge windows
+// NB: column blocks of 16 over the 4 cout_p columns (even); EDGE: the 1-D list of edge windows (unit: which 128 of
+// them); interior: the 8 x 16 tile of windows that starts at (wy0, wx0)
 template <int NB, int KC8, bool EDGE>
-__device__ __forceinline__ void deconv4_window_body(const ConvArgs& a, const int n, const int unit) {
+__device__ __forceinline__ void deconv4_window_body(const ConvArgs& a, const int n, const int unit, const int wy0,
+                                                    const int wx0) {
   constexpr int MR = 2, NT = EDGE ? 3 : 4, NCH = NB / 2, NG = NT * NCH;
   constexpr int KC = KC8 * 8, S = KC + kDSPAD, S2 = S / 2, KP = KC8 / 2;
   constexpr int NPIX = EDGE ? kWENPIX : kWNPIX;
@@ -349,8 +351,6 @@ __device__ __forceinline__ void deconv4_window_body(const ConvArgs& a, const int
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int mrow = lane & 15, kq = lane >> 4;
   const int H = a.Hin, W = a.Win;
-  const int tiles_x = (W + kDTX - 1) / kDTX;
-  const int wy0 = EDGE ? 0 : (unit / tiles_x) * kDTY, wx0 = EDGE ? 0 : (unit % tiles_x) * kDTX;   // first window
   const int e0 = unit * 128;                                                                       // first edge window
 
   // A rows of (tap, row block), float2 units, 16-byte aligned
@@ -501,9 +501,32 @@ __device__ __forceinline__ void deconv4_window_body(const ConvArgs& a, const int
 template <int NB, int KC8>
 __global__ __launch_bounds__(256) void deconv4_window_kernel(const ConvArgs a) {
   const BlockId bid = xcd_block();
-  const int tiles = ((a.Hin + kDTY - 1) / kDTY) * ((a.Win + kDTX - 1) / kDTX);
-  if ((int)bid.x < tiles) deconv4_window_body<NB, KC8, false>(a, bid.z, bid.x);
-  else deconv4_window_body<NB, KC8, true>(a, bid.z, bid.x - tiles);
+  const int H = a.Hin, W = a.Win;
+  const int tiles_x = (W + kDTX - 1) / kDTX;
+  const int tiles = ((H + kDTY - 1) / kDTY) * tiles_x;
+  const bool edge = (int)bid.x >= tiles;
+  const int unit = edge ? (int)bid.x - tiles : (int)bid.x;
+  int wy0 = (unit / tiles_x) * kDTY, wx0 = (unit % tiles_x) * kDTX;                                // first window
+  if (a.box) {
+    // BOX (ConvArgs::box): only the stored pixels [x0, x1] x [y0, y1] of image n have a reader.  Output pixel p
+    // belongs to window (p + 1) / 2, so the box is the windows [wlo, whi] of either axis, and the interior tiles are
+    // laid from its first window instead of from window 0: a tile that starts behind the box's last interior window
+    // has nothing to do and ends here, before it stages anything.  A tile's origin is clamped so that it never
+    // leaves the image -- two tiles may then overlap, and an output is the same bits whichever tile computes it
+    // (its products and their order do not depend on where in a tile its window sits).  The edge workgroups run
+    // only where the box reaches output row 2H - 1 or column 2W - 1.  (n is uniform: one scalar 16-byte load.)
+    const int4 b = a.box[bid.z];
+    const int wx_lo = (b.x + 1) >> 1, wy_lo = (b.y + 1) >> 1, wx_hi = (b.z + 1) >> 1, wy_hi = (b.w + 1) >> 1;
+    if (edge) {
+      if (wy_hi < H && wx_hi < W) return;
+    } else {
+      wy0 += wy_lo; wx0 += wx_lo;
+      if (wy0 > min(wy_hi, H - 1) || wx0 > min(wx_hi, W - 1)) return;
+      wy0 = min(wy0, max(H - kDTY, 0)); wx0 = min(wx0, max(W - kDTX, 0));
+    }
+  }
+  if (!edge) deconv4_window_body<NB, KC8, false>(a, bid.z, unit, wy0, wx0);
+  else deconv4_window_body<NB, KC8, true>(a, bid.z, unit, 0, 0);
 }
 
 // (test-only: how tests/test_hip_deconv4_window.py tells which form a call took; under graph capture it counts

@@ -203,6 +203,11 @@ struct ConvArgs {
   FastDiv fgx, fgy, ftx, fty;   // divisors: grid x / y, tiles per row / column (set by the launcher)
   size_t phase_stride;
   ConvPhase phase[8];
+  // [N] (x0, y0, x1, y1), inclusive, in pixels of the output tensor, or nullptr: the part of image n's output that
+  // has a reader.  Device data, read by the kernel.  The window form of ConvTranspose2d k4 s2 p1 (csrc/deconv4.hip)
+  // computes the tiles that cover it -- what it writes there is what it writes without a box, the rest of the output
+  // is left as it was --; every other form computes everything.
+  const int4* box = nullptr;
 };
 
 // host-side repack: torch layout (cout, cin, k..) [transposed: (cin, cout, k..)]
@@ -220,9 +225,10 @@ struct InNorm {
   float inv = 0.f;
   int act = 0;
 };
+// box: ConvArgs::box (honoured by the window form alone)
 int launch_conv(const ConvDesc& d, const ConvWeights& w, const Act& x, const Act& y,
                 const float* gate, double* stats, hipStream_t s, const InNorm* in = nullptr,
-                const SeGate* se = nullptr);
+                const SeGate* se = nullptr, const int4* box = nullptr);
 // output extent of a conv described by d for an input of extent (D,H,W)
 void conv_out_shape(const ConvDesc& d, int D, int H, int W, int* Do, int* Ho, int* Wo);
 

@@ -61,7 +61,8 @@ class Plan {
   int add_conv(const ParamMap& pm, const ConvDesc& d, const std::string& wkey,
                const std::string& bkey, bool transposed, const Act& x, const Act& y,
                const float* gate, bool want_stats, size_t* stats_off, long in_stats_off = -1,
-               float in_inv = 0.f, int in_act = 0, const SeGate* se = nullptr, long se_pool_off = -1);
+               float in_inv = 0.f, int in_act = 0, const SeGate* se = nullptr, long se_pool_off = -1,
+               const int4* const* box_cell = nullptr);   // box_cell: where every launch reads its ConvArgs::box from
   void add_norm(const Act& x, size_t stats_off, int act, const float* r1, const float* r2,
                 float* y, long pool_off, long r1_stats_off = -1);
 };
@@ -100,6 +101,14 @@ class EffTrackPlan : public Plan {
   Act res1;      // [N][H/4][W/4][Jp]  final_conv1 output (only with want_res1)
   int J = 0;
   int stem_op_ = -1, stem_ch_ = 16;
+  // The head's box (conv_layer.h has the rules).  head_takes_box: the head is a layer that can use one and
+  // JH_HEAD_ROI was not 0 when the plan was built.  head_box: [N] boxes in device memory that the NEXT run()'s head
+  // launch reads (ConvArgs::box), or nullptr = the full map; a caller sets it before run(), as it sets stem_src.
+  bool head_takes_box = false;
+  const int4* head_box = nullptr;
+  // The head's launch alone, without a box, on the operand the last run() left: completes a boxed heat map to exactly
+  // what a box-less run() writes.
+  int run_head(hipStream_t s);
 
  private:
   int mbconv(const ParamMap& pm, const std::string& p, int stage, int k, int stride, int cin,

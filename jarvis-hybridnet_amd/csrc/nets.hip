@@ -103,7 +103,7 @@ int Plan::get(const ParamMap& pm, const std::string& key, size_t numel, const fl
 int Plan::add_conv(const ParamMap& pm, const ConvDesc& d, const std::string& wkey,
                    const std::string& bkey, bool transposed, const Act& x, const Act& y,
                    const float* gate, bool want_stats, size_t* stats_off, long in_stats_off,
-                   float in_inv, int in_act, const SeGate* se, long se_pool_off) {
+                   float in_inv, int in_act, const SeGate* se, long se_pool_off, const int4* const* box_cell) {
   size_t taps;
   if (d.ostride > 1) taps = (d.nd == 2) ? 16 : 8;
   else taps = (size_t)d.k * d.k * (d.nd == 3 ? d.k : 1);
@@ -137,12 +137,13 @@ int Plan::add_conv(const ParamMap& pm, const ConvDesc& d, const std::string& wke
       : 4.0 * ((double)x.N * x.pixels() * d.cin + opix * d.cout + (double)d.cin * d.cout * taps);
   push(layer->profile_name(y.W), flops, bytes,
        [this, layer, x, y, gate, want_stats, off, in_stats_off, in_inv, in_act, sev = se ? *se : SeGate(),
-        se_pool_off](hipStream_t s) {
+        se_pool_off, box_cell](hipStream_t s) {
     InNorm in;
     if (in_stats_off >= 0) { in.stats = sc((size_t)in_stats_off); in.inv = in_inv; in.act = in_act; }
     SeGate seg = sev;
     if (se_pool_off >= 0) seg.pool = sc((size_t)se_pool_off);
-    return layer->launch(x, y, gate, want_stats ? sc(off) : nullptr, in, se_pool_off >= 0 ? &seg : nullptr, s);
+    return layer->launch(x, y, gate, want_stats ? sc(off) : nullptr, in, se_pool_off >= 0 ? &seg : nullptr, s,
+                         box_cell ? *box_cell : nullptr);
   });
   return 0;
 }
@@ -556,9 +557,24 @@ int EffTrackPlan::build(const ParamMap& pm, const std::string& pre, int size, in
                  res1, nullptr, false, nullptr, mid.st, mid.inv, ACT_NONE)) return 1;
   }
   // (J == 1, the CenterDetect head: the one-channel vector-ALU form)
+  // (the head's launches read their box through head_box; JH_HEAD_ROI=0, read here: no box ever)
   if (add_conv(pm, deconv2d_k4s2p1_desc(ss.head, J), pre + "deconv1.weight", "", true, mid.a, heat,
-               nullptr, false, nullptr, mid.st, mid.inv, ACT_NONE)) return 1;
+               nullptr, false, nullptr, mid.st, mid.inv, ACT_NONE, nullptr, -1, &head_box)) return 1;
+  head_takes_box = layers_.back().takes_box() && !want_res1 && head_roi_knob();
   return finish();
+}
+
+int EffTrackPlan::run_head(hipStream_t s) {
+  const int4* const box = head_box;
+  head_box = nullptr;
+  Op& op = ops_.back();                         // (the head is the plan's last launch)
+  Profiler& pf = profiler();
+  if (pf.on) pf.begin(op.name, op.flops, op.bytes, s);
+  const int rc = op.fn(s);
+  head_box = box;
+  if (rc) return 1;
+  if (pf.on) pf.end(s);
+  return 0;
 }
 
 // ------------------------------------------------------------------------- V2V

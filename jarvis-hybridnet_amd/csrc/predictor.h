@@ -123,6 +123,10 @@ struct Call {
   // centre keyframes in force (jh_predictor_set_center_keyframes): stage 1 ran on the key rows, and stage 2 fills the
   // rows in between behind its triangulation.  Set by the whole-path forward alone: the staged calls never have it.
   bool center_keys = false;
+  // The voxel gather of this very call is the only reader of the heat maps stage 2 writes (conv_layer.h: head_box_allowed;
+  // decided by the whole-path forward alone, the staged calls never have it): stage 2 projects the grid right behind
+  // the centres, gives the keypoint head the box of every image and leaves stage 3 the coarse field.
+  bool head_roi = false;
   hipStream_t s = nullptr;
 };
 inline Call make_call(const void* frames, const FrameSource& fs, void* stream, const unsigned char* mask = nullptr) {
@@ -220,6 +224,25 @@ struct jh_predictor {
   int slot = 0;
   const CentreSet& cur() const { return cset[slot]; }
   float2* coarse = nullptr;
+  // The keypoint head's boxes, [T * Cloc] (x0, y0, x1, y1): written by stage 2 of a call with
+  // Call::head_roi, read by the head's launch of that call (device data: a captured graph bakes the pointer only).
+  // heat_boxed: the predictor's own heat maps were last written by such a call -- outside the boxes they hold whatever
+  // they held before -- and whoever reads them afterwards calls full_heat() first, which runs the head once more
+  // without a box on the operand stage 2 left (the same bits a box-less call writes), every time it is needed.
+  // heat_boxed is HOST knowledge about device data, so it is only ever changed by calls whose launches the host makes
+  // itself: a forward on a stream the caller is capturing never boxes (HeatCall::Captured), and a reader that is being
+  // captured -- its launches will run again behind forwards this flag knows nothing of -- records the head's launch
+  // whatever the flag says.
+  int4* head_box = nullptr;
+  bool heat_boxed = false;
+  int full_heat(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s, &cs);
+    if (cs != hipStreamCaptureStatusNone) return kp->head_takes_box ? kp->run_head(s) : 0;
+    if (!heat_boxed) return 0;
+    heat_boxed = false;
+    return kp->run_head(s);
+  }
   double* sa_partial = nullptr;
   int* sa_max = nullptr;
   // hipGraph replay of the whole forward (the reference driver's call pattern: one frame set per
@@ -305,6 +328,7 @@ struct jh_predictor {
   }
 
   // 3D stage for frames t0 .. t0+T3-1 of the batch (heat_all holds those frames): api_predictor.hip
+  // (call.head_roi: stage 2 of this call has projected the grid already -- `coarse` is ready)
   int run_3d(const jh::Call& call, const float* heat_all, int t0, float* heatmap_final, float* points, float* conf,
              const jh::HeatLayout* layout = nullptr);
 };

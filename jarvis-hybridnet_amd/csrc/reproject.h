@@ -15,7 +15,21 @@ namespace jh {
 // division; a frame without any camera gets an all-zero volume); at most 64 cameras then.
 int launch_reproject(const Calib& cal, const int* center3d, const int* center_hm, const float* heat, float2* coarse,
                      float* vol, int* idx_out, int T, int C, int G, float spacing, int hs, int Jp, int heat_pad,
-                     int div255, const unsigned char* mask, hipStream_t s, const HeatLayout* layout = nullptr);
+                     int div255, const unsigned char* mask, hipStream_t s, const HeatLayout* layout = nullptr,
+                     bool coarse_ready = false);
+// The first half of launch_reproject on its own: the coarse (u, v) field of T frames x C cameras, [T][C][(G/2)^3].  It
+// depends on the calibration and the centres alone, so a caller may launch it as soon as those are known and hand the
+// field to launch_reproject / launch_reproject_joint_masked with coarse_ready = true (the same launch, the same bits).
+int launch_repro_coarse(const Calib& cal, const int* center3d, const int* center_hm, float2* coarse, int T, int C, int G,
+                        float spacing, int hs, hipStream_t s);
+// The box of stored heat-map pixels the gather can read, per image: image n = t * cam_n + l is camera
+// cam0 + l of frame t, box[n] = (x0, y0, x1, y1) inclusive.  From the min / max of (u, v) over the camera's coarse
+// field: the x2 trilinear upsampling with edge clamp forms convex combinations only, so every fine (u, v) lies in the
+// coarse hull up to the rounding of the interpolation, for which the box takes the one pixel of margin of the cube
+// gather's own boxes:  [trunc(min / 2) - 1 + heat_pad - 1, trunc(max / 2) - 1 + heat_pad + 1], clipped to the map.
+// A frame that is not valid (valid[t] == 0; valid may be nullptr) and a camera the mask leaves out get the full map.
+int launch_repro_box(const float2* coarse, const int* valid, const unsigned char* mask, int4* box, int T, int C,
+                     int cam0, int cam_n, int G, int hs, int heat_pad, hipStream_t s);
 // Per-joint camera masks -- joint_mask: [T][J][C] bytes on the device, nonzero = camera c counts for
 // joint j of frame t.  With a(t,c) the camera mask (1 without one), the effective set of joint j is
 // e(t,j,c) = a(t,c) && joint_mask[t][j][c]; an empty set falls back to a(t,.), and so do the padding channels.  One
@@ -28,6 +42,6 @@ int launch_reproject_joint_masked(const Calib& cal, const int* center3d, const i
                                   float2* coarse, float* vol, int* idx_out, int T, int C, int G, float spacing, int hs,
                                   int J, int Jp, int heat_pad, int div255, const unsigned char* mask,
                                   const unsigned char* joint_mask, const JointSets& js, hipStream_t s,
-                                  const HeatLayout* layout = nullptr);
+                                  const HeatLayout* layout = nullptr, bool coarse_ready = false);
 
 }  // namespace jh

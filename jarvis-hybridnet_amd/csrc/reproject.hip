@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <atomic>
 #include "jh_common.h"
+#include "reproject.h"
 
 namespace jh {
 
@@ -74,6 +75,48 @@ __global__ __launch_bounds__(256) void repro_coarse_kernel(
   u = __fsub_rn(__fadd_rn(__fsub_rn(u, (float)chx), (float)hs), 1.f);
   v = __fsub_rn(__fadd_rn(__fsub_rn(v, (float)chy), (float)hs), 1.f);
   coarse[((size_t)(t * C + c)) * nvox + vox] = make_float2(u, v);
+}
+
+// The box of heat-map pixels image (t, camera cam0 + l) can be read at by the gather (reproject.h: launch_repro_box):
+// one workgroup per image takes the min and max of u and of v over the camera's coarse field (already clamped to the
+// crop).  Plain min / max: the result does not depend on the order.
+__global__ __launch_bounds__(256) void repro_box_kernel(
+    const float2* __restrict__ coarse, const int* __restrict__ valid, const unsigned char* __restrict__ mask,
+    int4* __restrict__ box, int C, int cam0, int cam_n, int nvox_c, int hs, int heat_pad) {
+  const int t = blockIdx.y, l = blockIdx.x, c = cam0 + l;
+  const int Hh = hs - 2 + 2 * heat_pad;
+  const int tid = threadIdx.x;
+  const bool full = (valid && valid[t] == 0) || (mask && mask[(size_t)t * C + c] == 0);      // (uniform)
+  float ulo = 3.0e38f, uhi = -3.0e38f, vlo = 3.0e38f, vhi = -3.0e38f;
+  if (!full) {
+    // (nvox_c is even -- G % 4 == 0 --: two entries per 16-byte load)
+    const float4* cz = reinterpret_cast<const float4*>(coarse + (size_t)(t * C + c) * nvox_c);
+    for (int i = tid; i < (nvox_c >> 1); i += 256) {
+      const float4 p = cz[i];
+      ulo = fminf(ulo, fminf(p.x, p.z)); uhi = fmaxf(uhi, fmaxf(p.x, p.z));
+      vlo = fminf(vlo, fminf(p.y, p.w)); vhi = fmaxf(vhi, fmaxf(p.y, p.w));
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    ulo = fminf(ulo, __shfl_xor(ulo, m)); uhi = fmaxf(uhi, __shfl_xor(uhi, m));
+    vlo = fminf(vlo, __shfl_xor(vlo, m)); vhi = fmaxf(vhi, __shfl_xor(vhi, m));
+  }
+  __shared__ float red[4][4];
+  if ((tid & 63) == 0) { red[tid >> 6][0] = ulo; red[tid >> 6][1] = uhi; red[tid >> 6][2] = vlo; red[tid >> 6][3] = vhi; }
+  __syncthreads();
+  if (tid != 0) return;
+  int4 b = make_int4(0, 0, Hh - 1, Hh - 1);
+  if (!full) {
+    for (int w = 1; w < 4; ++w) {
+      ulo = fminf(ulo, red[w][0]); uhi = fmaxf(uhi, red[w][1]); vlo = fminf(vlo, red[w][2]); vhi = fmaxf(vhi, red[w][3]);
+    }
+    // padded-heatmap pixel = trunc(u / 2) (the gather's own division), stored pixel = that - 1 + heat_pad
+    const int sh = -1 + heat_pad;
+    b.x = min(max((int)__fdiv_rn(ulo, 2.f) + sh - 1, 0), Hh - 1); b.y = min(max((int)__fdiv_rn(vlo, 2.f) + sh - 1, 0), Hh - 1);
+    b.z = max(min((int)__fdiv_rn(uhi, 2.f) + sh + 1, Hh - 1), 0); b.w = max(min((int)__fdiv_rn(vhi, 2.f) + sh + 1, Hh - 1), 0);
+  }
+  box[(size_t)t * cam_n + l] = b;
 }
 
 // source index and lambdas of the x2 linear upsampling, align_corners=False
@@ -896,7 +939,7 @@ static int launch_cube(const CubeArgs& a, int T, hipStream_t s, const unsigned c
 static int reproject_impl(const Calib& cal, const int* center3d, const int* center_hm, const float* heat, float2* coarse,
                           float* vol, int* idx_out, int T, int C, int G, float spacing, int hs, int Jp, int heat_pad,
                           int div255, const unsigned char* mask, hipStream_t s, const HeatLayout* layout,
-                          const unsigned long long* sets, const int* ncam) {
+                          const unsigned long long* sets, const int* ncam, bool coarse_ready) {
   JH_REQUIRE(!(mask || sets) || C <= 64, "at most 64 cameras");
   const int Gh = G / 2;
   const int Hst = hs - 2 + 2 * heat_pad;
@@ -908,11 +951,8 @@ static int reproject_impl(const Calib& cal, const int* center3d, const int* cent
   JH_REQUIRE(lay.cams_per_block >= 1 && C % lay.cams_per_block == 0, "cameras per heatmap block");
   JH_REQUIRE(G % 2 == 0 && Jp % 8 == 0 && Jp <= 64, "reprojection shape");
   JH_REQUIRE((size_t)hs * hs * Jp * 4 < ((size_t)1 << 31), "one camera's heatmap exceeds 2 GB");
-  if (calib_check(cal, C)) return 1;
-  const int nvc = Gh * Gh * Gh;
-  hipLaunchKernelGGL(repro_coarse_kernel, dim3((nvc + 255) / 256, C, T), dim3(256), 0, s, cal,
-                     center3d, center_hm, coarse, C, Gh, spacing, hs);
-  JH_CHECK_HIP(hipGetLastError());
+  // (coarse_ready: the caller has launched launch_repro_coarse for these frames already)
+  if (!coarse_ready && launch_repro_coarse(cal, center3d, center_hm, coarse, T, C, G, spacing, hs, s)) return 1;
   // cube form: G a multiple of 8 (the cubes' thickness; j and k may leave a ragged last cube: 72 = 4.5 x 16), at most
   // 32 channels (JH_REPRO_CUBE=0: the voxel-row form below; JH_REPRO_CUBE=16: only grids that are multiples of 16)
   if (!sets && G % 8 == 0 && G >= 16 && Jp <= 32 && JH_ENV_KNOB("JH_REPRO_CUBE") != 0 &&
@@ -962,25 +1002,46 @@ static int reproject_impl(const Calib& cal, const int* center3d, const int* cent
   return 0;
 }
 
+int launch_repro_coarse(const Calib& cal, const int* center3d, const int* center_hm, float2* coarse, int T, int C, int G,
+                        float spacing, int hs, hipStream_t s) {
+  JH_REQUIRE(G % 2 == 0 && coarse, "coarse field");
+  if (calib_check(cal, C)) return 1;
+  const int Gh = G / 2, nvc = Gh * Gh * Gh;
+  hipLaunchKernelGGL(repro_coarse_kernel, dim3((nvc + 255) / 256, C, T), dim3(256), 0, s, cal,
+                     center3d, center_hm, coarse, C, Gh, spacing, hs);
+  JH_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_repro_box(const float2* coarse, const int* valid, const unsigned char* mask, int4* box, int T, int C,
+                     int cam0, int cam_n, int G, int hs, int heat_pad, hipStream_t s) {
+  JH_REQUIRE(coarse && box && G % 4 == 0 && T >= 1 && cam0 >= 0 && cam_n >= 1 && cam0 + cam_n <= C, "box of the gather");
+  const int Gh = G / 2;
+  hipLaunchKernelGGL(repro_box_kernel, dim3(cam_n, T), dim3(256), 0, s, coarse, valid, mask, box, C, cam0, cam_n,
+                     Gh * Gh * Gh, hs, heat_pad);
+  JH_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 int launch_reproject(const Calib& cal, const int* center3d, const int* center_hm, const float* heat, float2* coarse,
                      float* vol, int* idx_out, int T, int C, int G, float spacing, int hs, int Jp, int heat_pad,
-                     int div255, const unsigned char* mask, hipStream_t s, const HeatLayout* layout) {
+                     int div255, const unsigned char* mask, hipStream_t s, const HeatLayout* layout, bool coarse_ready) {
   return reproject_impl(cal, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs, Jp, heat_pad, div255,
-                        mask, s, layout, nullptr, nullptr);
+                        mask, s, layout, nullptr, nullptr, coarse_ready);
 }
 
 int launch_reproject_joint_masked(const Calib& cal, const int* center3d, const int* center_hm, const float* heat,
                                   float2* coarse, float* vol, int* idx_out, int T, int C, int G, float spacing, int hs,
                                   int J, int Jp, int heat_pad, int div255, const unsigned char* mask,
                                   const unsigned char* joint_mask, const JointSets& js, hipStream_t s,
-                                  const HeatLayout* layout) {
+                                  const HeatLayout* layout, bool coarse_ready) {
   JH_REQUIRE(joint_mask && js.sets && js.ncam, "joint mask and its workspace");
   JH_REQUIRE(C >= 1 && C <= 64 && J >= 1 && J <= Jp && Jp <= 64, "joint-masked gather: at most 64 cameras and channels");
   hipLaunchKernelGGL(repro_joint_sets_kernel, dim3(T), dim3(64), 0, s, mask, joint_mask, js.sets, js.ncam, js.eff, js.cnt,
                      C, J, Jp);
   JH_CHECK_HIP(hipGetLastError());
   return reproject_impl(cal, center3d, center_hm, heat, coarse, vol, idx_out, T, C, G, spacing, hs, Jp, heat_pad, div255,
-                        nullptr, s, layout, js.sets, js.ncam);
+                        nullptr, s, layout, js.sets, js.ncam, coarse_ready);
 }
 
 }  // namespace jh
